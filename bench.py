@@ -17,6 +17,13 @@ per GPU, and every step ends with the RCCL all-gather of the per-rank (pt, statu
 4000-keypoint pair per GPU, the step a replayed hipGraph), no collective on the data path; the line's `value` is the
 aggregate over the N streams and `per_gpu_ms_per_step` lists each GPU's own step time.
 Rank 0 prints ONE JSON line; `config.mode` says which of the three forms (shard-weak, shard-strong, replicas) ran.
+
+A plain run measures the headline only: set-up, the untimed spin-up, the W warm-up steps, the K timed steps and the
+line.  `--full` adds everything measured or checked beside it: the cold figure, the kernel's own time and the roofline,
+the gather report and the checks of the sharded / replicas forms, and (one GPU) the other step modes, the live and
+host-buffer steps, every BASELINE config, the CPU baseline and the comparison with it (`--no-extras` /
+`--no-cpu-baseline` leave parts of that out).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<field>.npy.
 """
 from __future__ import annotations
 
@@ -143,6 +150,39 @@ def kernel_time_ms(rt, reps: int) -> tuple[float, float]:
     return float(np.mean(trk)), float(np.mean(pyr))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EEDD0
+
+
+def dump_outputs(res: dict, n: int, out_dir: str, prefix: str = "") -> list[str]:
+    """The per-feature results of a step (`res`: distributed.to_numpy of its output, n features) as
+    <out_dir>/<prefix><field>.npy.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the features is written
+    instead (the same indices for the same n), with its indices as <prefix>sample_index.npy."""
+    import numpy as np
+    # the float64 results stay float64, the rest become float32 (status and iteration counts are small integers)
+    dtypes = {"pt_un": np.float32, "pt_dist": np.float32, "status": np.float32, "pix_err": np.float64,
+              "dist_pred": np.float64, "ncc": np.float32, "iters": np.float32}
+    per_feature = sum(np.dtype(dt).itemsize * max(1, int(np.prod(res[k].shape[1:]))) for k, dt in dtypes.items())
+    idx = None
+    if n * per_feature > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (per_feature + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for k, dt in dtypes.items():
+        a = np.asarray(res[k][:n])
+        if idx is not None:
+            a = a[idx]
+        path = os.path.join(out_dir, f"{prefix}{k}.npy")
+        np.save(path, np.ascontiguousarray(a.astype(dt)))
+        written.append(path)
+    if idx is not None:
+        path = os.path.join(out_dir, f"{prefix}sample_index.npy")
+        np.save(path, idx.astype(np.float64))
+        written.append(path)
+    return written
+
+
 def config_row(cfg_idx: int, n: int, device: int, steps: int, streams: int = 1) -> dict:
     """One BASELINE config on this GPU: `streams` independent resident trackers of that shape stepped as a replayed
     hipGraph and as direct launches (the faster mode is the row's ms_per_step; both are listed), plus the tracking
@@ -237,8 +277,13 @@ def main() -> int:
     ap.add_argument("--config", type=int, default=None, help="synth.config index (default 1 = BASELINE configs[1]; 4 with --mode replicas)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: N x the config's keypoints; strong: the config's keypoints split over N GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-config table and the side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (cold figure, kernel time and roofline, "
+                         "gather report and result checks, step modes, every BASELINE config, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-feature results as DIR/<field>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-config table and the side measurements")
     ap.add_argument("--mode", choices=("shard", "replicas"), default="shard",
                     help="shard: one frame pair, keypoints split over the GPUs + all-gather (--scaling weak|strong); "
                          "replicas: an independent camera stream per GPU, no collective (BASELINE configs[4])")
@@ -363,14 +408,15 @@ def main() -> int:
     # step is replayed for a fixed wall time first (synchronised every 20 steps: a deep launch backlog has its own
     # after-effect), THEN the W warm-up steps and the K timed steps follow exactly as the contract says.
     spinup_s = float(os.environ.get("PAGK_BENCH_SPINUP_S", "0.5"))
-    # ... and the contract-pure figure beside it: the SAME W warm-up + K timed steps taken first, on the device as this
-    # fresh process found it (`ms_per_step_cold` / `value_cold` in the line).  `value` is the
-    # steady-state figure and the one compared between rounds; BASELINE.md holds no published number for either.
-    elapsed_cold, _ = time_steps(rt, args.steps, args.warmup, step_mode, barrier)
-    if world > 1:
-        t = torch.tensor([elapsed_cold], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed_cold = float(t.item())
+    # ... and with --full the contract-pure figure beside it: the SAME W warm-up + K timed steps taken first, on the device
+    # as this fresh process found it (`ms_per_step_cold` / `value_cold` in the line).  `value`
+    # is the steady-state figure and the one compared between rounds; BASELINE.md holds no published number for either.
+    if args.full:
+        elapsed_cold, _ = time_steps(rt, args.steps, args.warmup, step_mode, barrier)
+        if world > 1:
+            t = torch.tensor([elapsed_cold], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed_cold = float(t.item())
     if spinup_s > 0:
         def burst(k):
             for _ in range(k):
@@ -399,13 +445,17 @@ def main() -> int:
         elapsed = float(t.item())
     mode_used = rt.mode_used
 
-    kernel_ms, pyramid_ms = kernel_time_ms(rt, min(50, max(10, args.steps)))
-    variant = rt.ctx.last_variant()
-    res = distributed.to_numpy(out)  # full length on every rank (gathered when world > 1)
-
     rt.ctx.check_launch()   # (torch synchronised the streams, not pagk_sync: read the launches' error word)
+    res = distributed.to_numpy(out)  # the last timed step's result, full length on every rank (gathered when world > 1)
+    if args.dump_outputs and (rank == 0 or replicas):
+        # sharded: every rank holds the gathered result, rank 0 writes it; replicas: each rank its own stream's
+        dump_outputs(res, n_total, args.dump_outputs, prefix=f"rank{rank}_" if rank else "")
+
     extras = {}
-    if (world > 1 or force_dist) and not replicas:
+    if args.full:
+        kernel_ms, pyramid_ms = kernel_time_ms(rt, min(50, max(10, args.steps)))
+        variant = rt.ctx.last_variant()
+    if args.full and (world > 1 or force_dist) and not replicas:
         # the collective by itself (events on the stream it runs on), and the same steps without it
         extras["gather"] = rt.gather_report(min(50, max(10, args.steps)))
         extras["gather"]["via"] = gather_via
@@ -429,7 +479,7 @@ def main() -> int:
                 "pix_err_mismatches": int(np.count_nonzero(res["pix_err"][:n] != single["pix_err"][:n])),
                 "compared": int(n),
                 "what": f"all-gathered result of {world} rank(s) vs one unsharded pagk_track of the same {n} features on rank 0's GPU"}
-    if replicas:
+    if args.full and replicas:
         # every stream's own check (no collective on the data path, so nothing else ties the ranks' results to anything):
         # the first 256 features re-tracked by the reference-shaped one-thread-per-feature kernel (pagk_set_kernel 1, an
         # independent device implementation of the loop nest) on the same GPU; gathered for the line over the control plane
@@ -448,7 +498,7 @@ def main() -> int:
         extras["per_stream_check"] = {
             "what": "per GPU: its stream's first features vs the one-thread-per-feature kernel on the same GPU",
             "streams": [{"max_px": float(v[0].item()), "status_mismatches": int(v[1].item()), "compared": int(v[2].item())} for v in allc]}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # the look-ahead step beside the headline, and how the two launches can reach the GPU
         ksteps = max(20, args.steps // 2)
         modes = {}
@@ -497,11 +547,6 @@ def main() -> int:
         extras["configs"] = table
 
     if rank == 0:
-        b_alg = algorithmic_bytes_per_feature(w.half_patch, w.pyramids)
-        achieved = n_active_local * b_alg / (kernel_ms * 1e-3) / 1e9
-        kname = KERNEL_OF_VARIANT.get(variant, "k_track_block")
-        traffic, traffic_tag = measured_traffic(w.name, n_total, kname) if world == 1 and not replicas else (None, None)
-        P = (2 * w.half_patch + 1) ** 2
         it = res["iters"][:n_total]
         max_it = int(it.max())
         line = {
@@ -512,7 +557,6 @@ def main() -> int:
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak" if replicas else args.scaling, "vs_baseline": None,
             "per_gpu_ms_per_step": per_gpu_ms,
-            "ms_per_step_cold": elapsed_cold / args.steps * 1e3, "value_cold": n_active_total * args.steps / elapsed_cold,
             "dtype": "f32 sampling, f64 normal equations", "data": "synthetic", "spinup_s": spinup_s,
             "runtime_env": runtime_env.IN_FORCE,
             "config": {"workload": f"{w.name}: {w.img_ref.shape[1]}x{w.img_ref.shape[0]} pair, "
@@ -532,29 +576,38 @@ def main() -> int:
                                + (" + all-gather of step k on a side stream, awaited before step k+1's tracking"
                                   if world > 1 and not replicas else ""),
                        "step_mode": mode_used},
-            # `bound` names the roofline the contract asks to price against; what actually binds the kernel is in
-            # `binding_resource` (the fraction of HBM peak is tiny by construction: ~3.2 KB of compulsory bytes per
-            # feature against ~10 iterations of 441-step ORDERED f64 accumulation, DESIGN.md section 4.3)
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "traffic_source": (f"profiles/{traffic_tag}/pmc_summary.json: (2*FETCH_SIZE + WRITE_SIZE) KiB "
-                                            "per launch") if traffic else None,
-                         "kernel": kname, "variant": capi.Context.VARIANT_NAMES.get(variant, "?"), "kernel_ms": kernel_ms,
-                         "pyramid_ms": pyramid_ms,
-                         "algorithmic_bytes_per_feature": b_alg, "features_per_launch": n_active_local,
-                         "binding_resource": "latency of the reference-ordered accumulation: the launch lasts as long as its "
-                                             "slowest feature (max iterations x [sampling + 441 dependent f64 FMA steps + "
-                                             "4x4 LLT solve]); not HBM",
-                         "ordered_chain_floor_ms": max_it * P * 5.9 / 2.4e9 * 1e3,
-                         "ordered_chain_floor_note": f"{max_it} iterations of the slowest feature x {P} dependent FMA steps x "
-                                                     "5.9 cycles (measured DPP chain step) at 2.4 GHz: what the ordered sums "
-                                                     "alone cost on its critical path"},
         }
         line["mean_iters_per_feature"] = float(it[w.status_in > 0].mean())
         line["max_iters_per_feature"] = max_it
+
+        if args.full:
+            line["ms_per_step_cold"] = elapsed_cold / args.steps * 1e3
+            line["value_cold"] = n_active_total * args.steps / elapsed_cold
+            b_alg = algorithmic_bytes_per_feature(w.half_patch, w.pyramids)
+            achieved = n_active_local * b_alg / (kernel_ms * 1e-3) / 1e9
+            kname = KERNEL_OF_VARIANT.get(variant, "k_track_block")
+            traffic, traffic_tag = measured_traffic(w.name, n_total, kname) if world == 1 and not replicas else (None, None)
+            P = (2 * w.half_patch + 1) ** 2
+            # `bound` names the roofline the contract asks to price against; what actually binds the kernel is in
+            # `binding_resource` (the fraction of HBM peak is tiny by construction: ~3.2 KB of compulsory bytes per
+            # feature against ~10 iterations of 441-step ORDERED f64 accumulation, DESIGN.md section 4.3)
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                                "traffic_source": (f"profiles/{traffic_tag}/pmc_summary.json: (2*FETCH_SIZE + WRITE_SIZE) KiB "
+                                                   "per launch") if traffic else None,
+                                "kernel": kname, "variant": capi.Context.VARIANT_NAMES.get(variant, "?"), "kernel_ms": kernel_ms,
+                                "pyramid_ms": pyramid_ms,
+                                "algorithmic_bytes_per_feature": b_alg, "features_per_launch": n_active_local,
+                                "binding_resource": "latency of the reference-ordered accumulation: the launch lasts as long as its "
+                                                    "slowest feature (max iterations x [sampling + 441 dependent f64 FMA steps + "
+                                                    "4x4 LLT solve]); not HBM",
+                                "ordered_chain_floor_ms": max_it * P * 5.9 / 2.4e9 * 1e3,
+                                "ordered_chain_floor_note": f"{max_it} iterations of the slowest feature x {P} dependent FMA steps x "
+                                                            "5.9 cycles (measured DPP chain step) at 2.4 GHz: what the ordered sums "
+                                                            "alone cost on its critical path"}
         line.update(extras)
 
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import pagk_oracle as orc   # cpu_baseline leg: the only use of oracle/ here
             threads = host_cores()
             reps, t_cpu = 0, 0.0

@@ -54,7 +54,7 @@ def test_spawned_ranks_get_a_consistent_environment(monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "3", "--no-extras",
                         "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -87,7 +87,7 @@ def test_bench_forced_collective_reports_the_gather():
     """One rank, the collective forced (PAGK_FORCE_DIST=1): the all-gather goes through the library's communicator,
     is reported on its own, and the line keeps its contract."""
     env = dict(os.environ, PAGK_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "3", "--no-extras",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -133,7 +133,7 @@ def test_spawned_ranks_of_the_replicas_mode(monkeypatch):
 def test_bench_replicas_mode_on_one_gpu():
     """The replicas form with one rank: configs[4]'s stream shape, graph step, no collective, the mode named in the line."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29534")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "replicas", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "replicas", "--steps", "6", "--warmup", "2",
                         "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
@@ -157,3 +157,83 @@ def test_the_multi_gpu_line_carries_its_own_proof():
     from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi
     lib = capi.load()
     assert hasattr(lib, "pagk_multi_comm_count")
+
+
+def _load_bench(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_offers_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_writes_every_field_as_float(tmp_path):
+    import numpy as np
+    bench = _load_bench("bench_dump")
+    n = 37
+    rng = np.random.default_rng(3)
+    res = {"pt_un": rng.random((n + 5, 2), dtype=np.float32), "pt_dist": rng.random((n + 5, 2), dtype=np.float32),
+           "status": (rng.random(n + 5) > 0.3).astype(np.uint8), "pix_err": rng.random(n + 5),
+           "dist_pred": rng.random(n + 5), "ncc": rng.random(n + 5, dtype=np.float32),
+           "iters": rng.integers(0, 90, n + 5).astype(np.int32)}
+    written = bench.dump_outputs(res, n, str(tmp_path / "out"))
+    assert sorted(os.path.basename(p) for p in written) == sorted(f"{k}.npy" for k in res)
+    for k, v in res.items():
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == (np.float64 if v.dtype == np.float64 else np.float32), k
+        assert a.shape == v[:n].shape and np.array_equal(a, v[:n].astype(a.dtype)), k
+
+
+def test_dump_outputs_samples_a_fixed_subset_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _load_bench("bench_dump_sample")
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    n = 1000
+    res = {"pt_un": np.arange(2 * n, dtype=np.float32).reshape(n, 2), "pt_dist": np.zeros((n, 2), np.float32),
+           "status": np.ones(n, np.uint8), "pix_err": np.arange(n, dtype=np.float64), "dist_pred": np.zeros(n),
+           "ncc": np.zeros(n, np.float32), "iters": np.full(n, 7, np.int32)}
+    bench.dump_outputs(res, n, str(tmp_path / "a"))
+    bench.dump_outputs(res, n, str(tmp_path / "b"))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 4096 + 128 * len(os.listdir(tmp_path / "a"))   # (+ the .npy headers)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert 0 < idx.size < n and np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "pix_err.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "pt_un.npy")[:, 0], 2 * idx.astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_timed_result(tmp_path):
+    """A plain run: one line with the headline keys and nothing measured beside it; --dump-outputs holds the last timed
+    step's result, which is the CPU oracle's, field for field."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "3",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, "exactly one JSON line on stdout"
+    b = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool),
+                 ("dtype", str), ("steps", int), ("warmup", int)):
+        assert isinstance(b[k], t), k
+    assert b["steps"] == 8 and b["warmup"] == 3 and b["unit"] == "features/s" and b["higher_is_better"] is True
+    assert abs(b["value"] - b["config"]["features_active"] / (b["ms_per_step"] * 1e-3)) <= 1e-6 * b["value"]
+    for k in ("ms_per_step_cold", "roofline", "cpu_baseline", "px_err_vs_cpu", "configs", "step_modes_ms", "live_step"):
+        assert k not in b, k
+    sys.path.insert(0, ROOT)
+    from oracle import pagk_oracle as orc
+    from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, synth
+    w = synth.config(1, n=1000)
+    p = capi.make_params(half_patch=w.half_patch, iterations=w.iterations, pyramids=w.pyramids, has_gyro=w.has_gyro,
+                         camera=w.camera)
+    ref = orc.track(p, w.img_ref, w.img_cur, w.pt_ref, w.pt_init, w.affine, w.status_in, nthreads=8)
+    for k in ("pt_un", "pt_dist", "status", "pix_err", "dist_pred", "iters"):
+        a = np.load(out_dir / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == w.n, k
+        assert np.array_equal(a, ref[k][:w.n].astype(a.dtype), equal_nan=True), k
