@@ -576,7 +576,8 @@ class Context:
 
     def check_launch(self):
         """The error state pagk_sync would return, without synchronising: for callers that synchronise the stream
-        themselves (a torch stream).  Raises PAGK_E_HIP once for a kernel-7 launch in which a wave gave up its wait."""
+        themselves (a torch stream).  Raises PAGK_E_HIP once for a launch in which a wave gave up its wait
+        (kernel 7's level hand-off, the 4-wave kernel's solve)."""
         self._check(self.lib.pagk_check_launch(self.h), "pagk_check_launch")
 
     def set_stream(self, stream_ptr: int | None):

@@ -736,12 +736,21 @@ __device__ __forceinline__ double solve_bcast(double v)
     else
         return lane_bcast(v, K);
 }
-template <bool FAST, bool ROWB = false>
+// LATE: late.issue() is called in column 0 once its pivot's square root is taken, late() between column 0 and column 1.
+// Column 0 reads H00, H10, H20, H30 and b0 only, so a caller whose other entries (H11, H21, H31, b1, b2, b3) arrive later
+// may start fetching them in issue() and store them into M and b in late() (the pipelined 4-wave kernel: the other chain
+// wave's sums); the form reads those entries after the call.  No arithmetic depends on the hook.
+struct SolveNoLate {
+    __device__ __forceinline__ void issue() const {}
+    __device__ __forceinline__ void operator()() const {}
+};
+template <bool FAST, bool ROWB = false, class LATE = SolveNoLate>
 __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4][4], const double (&b)[4], int l,
-                                                            double (&x)[4], uint32_t sv, OperandRange &rg)
+                                                            double (&x)[4], uint32_t sv, OperandRange &rg,
+                                                            const LATE &late = LATE{})
 {
-    const double H00 = M[0][0], H10 = M[1][0], H11 = M[1][1], H20 = M[2][0], H21 = M[2][1], H22 = M[2][2];
-    const double H30 = M[3][0], H31 = M[3][1], H32 = M[3][2], H33 = M[3][3];
+    const double H00 = M[0][0], H10 = M[1][0], H20 = M[2][0], H22 = M[2][2];
+    const double H30 = M[3][0], H32 = M[3][2], H33 = M[3][3];
     const bool recip = (sv & SV_LLT_RECIP) != 0;
     // a column's scaling: n / d (Eigen 3.3) or n * (1 / d) (<= 3.2); `fwd`: this lane's quotient is the forward
     // substitution's rhs[k] /= L(k,k), a true division in every version
@@ -754,12 +763,15 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
     // column 0: lane 0 -> r0 = b0 / d0, lane i -> L(i,0) = H(i,0) / d0
     const bool ok0 = FAST || (!(H00 <= 0.0));
     const double d0 = pivot_root_early<FAST>(ok0, H00, H00, rg);
+    late.issue();
     const Den D0 = den_prepare<FAST>(d0, rg);
     const double n0 = l == 0 ? b[0] : (l == 1 ? H10 : (l == 2 ? H20 : H30));
     const double q0 = column(n0, D0, l == 0);
     const double own0 = (l == 0 || ok0) ? q0 : n0;
     double r0 = solve_bcast<0, ROWB>(own0);
     const double L10 = solve_bcast<1, ROWB>(own0), L20 = solve_bcast<2, ROWB>(own0), L30 = solve_bcast<3, ROWB>(own0);
+    late();
+    const double H11 = M[1][1], H21 = M[2][1], H31 = M[3][1];
     // column 1: lane 1 -> r1, lanes 2, 3 -> L(i,1)
     const double x1 = H11 - L10 * L10;
     const bool ok1 = FAST || (ok0 && !(x1 <= 0.0));
@@ -799,12 +811,13 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
 
 // (the calling lanes -- four, or a whole wave whose lanes 0..3 matter -- take the decision together: the form
 // broadcasts between them)
-template <bool ROWB = false>
+// With a LATE hook (see the form) the plain-division redo reads M and b as the hook completed them.
+template <bool ROWB = false, class LATE = SolveNoLate>
 __device__ __forceinline__ double llt4_solve_nsq_lanes(const double (&M)[4][4], const double (&b)[4], int l,
-                                                       double (&x)[4], uint32_t sv)
+                                                       double (&x)[4], uint32_t sv, const LATE &late = LATE{})
 {
     OperandRange rg;
-    double nsq = llt4_solve_nsq_lanes_form<true, ROWB>(M, b, l, x, sv, rg);
+    double nsq = llt4_solve_nsq_lanes_form<true, ROWB>(M, b, l, x, sv, rg, late);
 #ifndef PAGK_EXPERIMENT_NO_REDO
     if (__builtin_amdgcn_ballot_w64(!rg.in_range() && l < 4) != 0) nsq = llt4_solve_nsq_lanes_form<false, ROWB>(M, b, l, x, sv, rg);
 #endif

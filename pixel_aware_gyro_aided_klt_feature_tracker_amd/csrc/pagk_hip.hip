@@ -443,12 +443,13 @@ void fill_level(DevLevel &d, const FrameSlot &s, int l)
 // Resident waves of k_track_quad<NCH> on this device: the kernel's own occupancy (registers, its 10000 B of LDS) times
 // the CU count, asked once per context and patch size.
 // A wave of a one-level-per-wave launch that gave up waiting for the level above (never expected: the wait is on a wave
-// that started earlier) leaves results that must not be used.
+// that started earlier), or a solving wave of the pipelined 4-wave body that gave up waiting for the other chain wave's
+// sums, leaves results that must not be used.
 int lv_check(pagk_ctx *ctx)
 {
     if (ctx->lv_error && *static_cast<volatile int *>(ctx->lv_error) != 0) {
         *static_cast<volatile int *>(ctx->lv_error) = 0;
-        snprintf(ctx->err, sizeof(ctx->err), "a wave of the level-by-level tracking launch gave up waiting for the level above");
+        snprintf(ctx->err, sizeof(ctx->err), "a wave of a tracking launch gave up waiting (for the level above, or for the other chain wave's sums)");
         return PAGK_E_HIP;
     }
     return PAGK_OK;
@@ -586,6 +587,7 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
     a.prio_k = ctx->prio_k;
     a.prio_stats = ctx->prio_stats;
     a.prio_kbuf = ctx->prio_stats ? reinterpret_cast<const int *>(ctx->prio_stats + 2) : nullptr;
+    a.lv_error = ctx->lv_error_dev;   // (the pipelined 4-wave body raises it too: a solve that gave up waiting for its sums)
 
     if (ctx->ev_trk[0] && !in_capture(ctx)) HIPCHK(ctx, hipEventRecord(ctx->ev_trk[0], ctx->stream));
     if (n > 0) {

@@ -10,10 +10,11 @@
 // second round themselves.  Here, per iteration:
 //
 //   all waves   round 0: pixel p = tid (0..255) -> streams, esq                       __syncthreads (B1)
-//   wave 0, 1   eight DPP rows: XX YX YY XE | YE X Y E, pixels 0..255 at once, then -- flags permitting -- 256..P-1
+//   wave 0, 1   eight DPP rows: XX YX X XE | YY YE Y E, pixels 0..255 at once, then -- flags permitting -- 256..P-1
 //               (chain_rows_f64_piped: the waits are inside the chain, the ready case costs no bubble)
 //               wave 1: acc -> LDS, flag;  then, in a level's first iteration, H22 of the NEXT level (repeat_sum_f64)
-//               wave 0: acc -> LDS, waits for wave 1's flag, solves in lanes 0..3, update -> LDS
+//               wave 0: its own sums (column 0's inputs) by v_readlane, solves in lanes 0..3 -- wave 1's sums are read
+//               inside column 0 and taken at column 1 --, update -> LDS
 //   wave 2      samples batch A = [256, 320) and C = [384, P): gathers of both in flight together; flag after each
 //   wave 3      samples batch B = [320, 384); flag; then the ordered f32 cost chain (:294) with the same embedded waits.
 //               The solve does not read the cost (the penalty's e_pen^2 is added afterwards, :313), so this chain has
@@ -30,7 +31,10 @@
 // iteration number for C and for wave 1's accumulators).  The consumer reads the flag BEFORE the data it vouches for;
 // LDS executes one wave's instructions in order.  Every wait is on a wave of the same workgroup that needs nothing from
 // the waiter (A, B, C depend on B1 only; wave 1's flag on A, B, C), so there is no cycle; B2 closes the iteration and
-// separates its readers from the next iteration's writers.
+// separates its readers from the next iteration's writers.  Every wait is bounded (kPipeWaitLooks); one that runs out
+// (never expected) leaves NaN, so the feature ends with succ = 0.  The solve's wait for wave 1's sums also raises the
+// context's error word (TrackArgs::lv_error): pagk_sync / pagk_check_launch then report the launch as failed.  (The
+// same store inside chain_rows_*_piped was measured: +1.5 % per step, not kept.)
 #pragma once
 
 namespace pagk {
@@ -38,18 +42,8 @@ namespace pagk {
 // LDS of the pipelined body: the streams / esq / cslot / acc / update area of track_block_body, then
 // int flags[4] (A+B counter, C, wave 1's accumulators, pad), double h22[2], double pen (track_block_lds_bytes).
 
-// bounded like the waits inside the chains (kPipeWaitLooks); false: it ran out
-__device__ __forceinline__ bool lds_wait_ge(const int *flag, int want)
-{
-    for (uint32_t look = 0; look < kPipeWaitLooks; look++) {
-        if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int *>(flag)) >= want) return true;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return false;
-}
-
 // a flag word behind the data it vouches for: every lane stores the same value to the same address (no exec juggling)
-__device__ __forceinline__ void lds_store_b32(uint32_t addr, int v)
+__device__ __forceinline__ void lds_write_b32(uint32_t addr, int v)
 {
     asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
@@ -118,18 +112,21 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
 
     // accumulator rows (waves 0, 1), as in track_block_body: a DPP row broadcasts one stream value per step to its sixteen
     // lanes, the second FMA factor and the accumulator are per lane
-    //   row:      0    1    2    3    4    5          6          7
-    //   stream:   XX   YX   YY   XE   YE   X          Y          E
-    //   entry:    H00  H10  H11  b0   b1   H20 | H30  H21 | H31  b2 | b3        (lane 0 | lane 1 of the row)
+    //   row:      0    1    2          3    4    5    6          7
+    //   stream:   XX   YX   X          XE   YY   YE   Y          E
+    //   entry:    H00  H10  H20 | H30  b0   H11  b1   H21 | H31  b2 | b3        (lane 0 | lane 1 of the row)
+    // Wave 0's rows are exactly what column 0 of the solve reads (H00, H10, H20, H30, b0): it starts the solve on its own
+    // sums, and wave 1's are first needed at column 1.
     // wave 3's four rows all walk esq (the f32 cost chain; lane 0 is read)
     const int lr = lane & 15;
     const int cid = wave * 4 + (lane >> 4);
-    const uint32_t row_addr = wave < 2 ? lds_off(stream + (size_t)cid * PS) + 16u * lr : lds_off(esq) + 8u * lr;
+    const int row_stream = (0x76423510 >> (4 * cid)) & 15;  // row -> stream: XX YX X XE | YY YE Y E
+    const uint32_t row_addr = wave < 2 ? lds_off(stream + (size_t)row_stream * PS) + 16u * lr : lds_off(esq) + 8u * lr;
     const uint32_t flag_addr = lds_off(flags);
-    // where this lane's sum goes (slots as the solve reads them: H00 H10 H11 b0 b1 H20 H21 H30 H31 b2 b3), or -1:
-    // lane 0 of a row -> H00 H10 H11 b0 | b1 H20 H21 b2, lane 1 of rows X Y E -> H30 H31 b3.  Fixed for the kernel, so
-    // publishing a chain's result is one masked store.
-    const int acc_slot = wave < 2 ? (lr == 0 ? (cid == 7 ? 9 : cid) : ((lr == 1 && cid >= 5) ? (cid == 7 ? 10 : cid + 2) : -1)) : -1;
+    // where a lane of wave 1 publishes its sum (acc[0..5] = H11 b1 H21 H31 b2 b3: three ds_read_b128 for wave 0), or -1:
+    // lane 0 of its rows -> H11 b1 H21 b2, lane 1 of rows Y E -> H31 b3.  Fixed for the kernel, so publishing a chain's
+    // result is one masked store.  Wave 0 publishes nothing: its sums stay in registers.
+    const int acc_slot = wave == 1 ? (lr == 0 ? (cid == 7 ? 4 : cid - 4) : ((lr == 1 && cid >= 6) ? 2 * cid - 9 : -1)) : -1;
 
     int succ = 1, iters = 0, seq = 0;
     [[maybe_unused]] constexpr bool kPrioByWork = true;  // pagk_prio.h
@@ -202,8 +199,8 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
         // second FMA factor of this lane's row (:264  J = (Ix, Iy, de_dg, 1))
         double row_s1 = 1.0;  // H00 H10 H11
         switch (cid) {
-            case 3: case 4: row_s1 = -1.0; break;                  // b0 b1:  -J * e
-            case 5: case 6: row_s1 = lr == 0 ? cd : 1.0; break;    // H20 | H30,  H21 | H31
+            case 3: case 5: row_s1 = -1.0; break;                  // b0 b1:  -J * e
+            case 2: case 6: row_s1 = lr == 0 ? cd : 1.0; break;    // H20 | H30,  H21 | H31
             case 7: row_s1 = lr == 0 ? -cd : -1.0; break;          // b2 | b3
             default: break;
         }
@@ -265,13 +262,13 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
                 const uint32_t seq_ab = (uint32_t)__builtin_amdgcn_readfirstlane((HAS_B ? 2 : 1) * seq);
                 const uint32_t seq_c = (uint32_t)__builtin_amdgcn_readfirstlane(seq);
                 const double s = chain_rows_f64_piped<H>(row_addr, row_s1, flag_addr, seq_ab, seq_c);
-                if (acc_slot >= 0) acc[acc_slot] = s;
                 if (wave == 1) {
+                    if (acc_slot >= 0) acc[acc_slot] = s;
                     // the flag right behind the sums: LDS executes one wave's instructions in order, so whoever reads the
                     // flag's new value reads the sums stored before it (no s_waitcnt in between: it would only delay the flag)
                     // (an explicit ds_write: through a volatile pointer the compiler stored with flat_store_dword sc0 sc1 +
                     // s_waitcnt vmcnt(0) -- the flat path into LDS, on the way from wave 1's sums to wave 0's solve)
-                    lds_store_b32(flag_addr + 8u, seq);
+                    lds_write_b32(flag_addr + 8u, seq);
                     STAMP(4)   // (wave 1) B1 -> its accumulators published
                     PRIO(PAGK_PRIO_N_REST)
                     if (iter == iter_first && level > 0) {
@@ -283,61 +280,107 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
                         if (lane == 0) h22[(level - 1) & 1] = s22;
                     }
                 } else {
-                    // the eleven sums, wave 1's among them: the flag is read FIRST and the sums behind it in the same
-                    // batch -- one LDS round trip once the flag is up.  Bounded like every wait of this kernel; a wait that
-                    // ran out must not pass for a result.
+                    // wave 0's own sums, straight from the rows' lanes into scalar registers: H00 (lane 0), H10 (16),
+                    // H20 | H30 (32 | 33), b0 (48) -- column 0 of the solve needs nothing else
+                    const double H00 = lane_bcast(s, 0), H10 = lane_bcast(s, 16), H20 = lane_bcast(s, 32);
+                    const double H30 = lane_bcast(s, 33), B0 = lane_bcast(s, 48);
                     typedef double f64x2 __attribute__((ext_vector_type(2)));
-                    f64x2 q0, q1, q2, q3, q4, q5;
-                    bool acc_there = false;
-                    {
-                        int f;
-                        const uint32_t fad = flag_addr + 8u, aad = lds_off(acc);
-                        for (uint32_t look = 0; look < kPipeWaitLooks; look++) {
-                            asm volatile("ds_read_b32 %[f], %[fa]\n\t"
-                                         "ds_read_b128 %[q0], %[aa]\n\t"
-                                         "ds_read_b128 %[q1], %[aa] offset:16\n\t"
-                                         "ds_read_b128 %[q2], %[aa] offset:32\n\t"
-                                         "ds_read_b128 %[q3], %[aa] offset:48\n\t"
-                                         "ds_read_b128 %[q4], %[aa] offset:64\n\t"
-                                         "ds_read_b128 %[q5], %[aa] offset:80\n\t"
-                                         "s_waitcnt lgkmcnt(0)"
-                                         : [f] "=&v"(f), [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [q3] "=&v"(q3),
-                                           [q4] "=&v"(q4), [q5] "=&v"(q5)
-                                         : [fa] "v"(fad), [aa] "v"(aad)
-                                         : "memory");
-                            if (__builtin_amdgcn_readfirstlane(f) >= seq) {
-                                acc_there = true;
-                                break;
-                            }
-                            if (look >= 8) __builtin_amdgcn_s_sleep(1);  // (the other chain wave ends within a look or two)
-                        }
-                    }
                     STAMP(2)
                     POINT(2)
                     // ---- solve (:302-319) --------------------------------------------------------------------------
                     if (tid < 4) {
                         double Hm[4][4], b[4], upd[4];
-                        // acc: H00 H10 H11 b0 b1 H20 H21 H30 H31 b2 b3
-                        Hm[0][0] = acc_there ? q0.x : __builtin_nan("");
-                        Hm[1][0] = q0.y;
-                        Hm[1][1] = q1.x;
-                        b[0] = q1.y;
-                        b[1] = q2.x;
-                        Hm[2][0] = q2.y;
-                        Hm[2][1] = q3.x;
-                        Hm[3][0] = q3.y;
-                        Hm[3][1] = q4.x;
-                        b[2] = q4.y;
-                        b[3] = q5.x;
+                        Hm[0][0] = H00;
+                        Hm[1][0] = H10;
+                        Hm[2][0] = H20;
+                        Hm[3][0] = H30;
+                        b[0] = B0;
                         Hm[2][2] = h22[level & 1];
                         Hm[3][2] = (double)P * cd;  // sum of c*1.0: every partial sum k*c is exact
                         Hm[3][3] = (double)P;       // sum of 1.0*1.0
-                        double epsq = 0.0;
-                        if constexpr (!LEAN) {
+                        // wave 1's six sums, first needed at column 1 (or by the penalty, which adds to them): the flag
+                        // FIRST and the sums behind it, issued inside column 0 so that wave 1 has normally published by
+                        // then and the LDS round trip runs under the rest of the column.  Bounded like every wait of this
+                        // kernel; a wait that runs out raises the context's error word and must not pass for a result
+                        // (NaN: the feature ends with succ = 0)
+                        struct Late {
+                            const TrackArgs &a;
+                            double (&Hm)[4][4];
+                            double (&b)[4];
+                            uint32_t fad, aad;
+                            int seq;
+                            mutable int f;
+                            mutable f64x2 q0, q1, q2;
+                            mutable bool issued, taken;
+                            __device__ __forceinline__ void read(bool wait) const
+                            {
+                                if (wait)
+                                    asm volatile("ds_read_b32 %[f], %[fa]\n\t"
+                                                 "ds_read_b128 %[q0], %[aa]\n\t"
+                                                 "ds_read_b128 %[q1], %[aa] offset:16\n\t"
+                                                 "ds_read_b128 %[q2], %[aa] offset:32\n\t"
+                                                 "s_waitcnt lgkmcnt(0)"
+                                                 : [f] "=&v"(f), [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2)
+                                                 : [fa] "v"(fad), [aa] "v"(aad)
+                                                 : "memory");
+                                else
+                                    asm volatile("ds_read_b32 %[f], %[fa]\n\t"
+                                                 "ds_read_b128 %[q0], %[aa]\n\t"
+                                                 "ds_read_b128 %[q1], %[aa] offset:16\n\t"
+                                                 "ds_read_b128 %[q2], %[aa] offset:32"
+                                                 : [f] "=&v"(f), [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2)
+                                                 : [fa] "v"(fad), [aa] "v"(aad)
+                                                 : "memory");
+                            }
+                            __device__ __forceinline__ void issue() const
+                            {
+                                if (issued) return;
+                                issued = true;
+                                read(false);
+                            }
+                            __device__ __forceinline__ void operator()() const
+                            {
+                                if (taken) return;
+                                taken = true;
+                                issue();
+                                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f), "+v"(q0), "+v"(q1), "+v"(q2) : : "memory");
+                                if (__builtin_amdgcn_readfirstlane(f) < seq) {
+                                    bool there = false;
+                                    for (uint32_t look = 0; look < kPipeWaitLooks; look++) {
+                                        if (look >= 8) __builtin_amdgcn_s_sleep(1);
+                                        read(true);
+                                        if (__builtin_amdgcn_readfirstlane(f) >= seq) {
+                                            there = true;
+                                            break;
+                                        }
+                                    }
+                                    if (!there) {
+                                        if (threadIdx.x == 0 && a.lv_error) st_agent(a.lv_error, 1);
+                                        q0.x = __builtin_nan("");
+                                    }
+                                }
+                                // acc: H11 b1 H21 H31 b2 b3
+                                Hm[1][1] = q0.x;
+                                b[1] = q0.y;
+                                Hm[2][1] = q1.x;
+                                Hm[3][1] = q1.y;
+                                b[2] = q2.x;
+                                b[3] = q2.y;
+                            }
+                        };
+                        const Late take_late{a, Hm, b, flag_addr + 8u, lds_off(acc), seq};
+                        double epsq = 0.0, unorm;
+                        // four lanes share the divides of each Cholesky column (pagk_device.h); all end with the result,
+                        // update.squaredNorm()
+                        if constexpr (LEAN) {
+                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, 0u, take_late);
+                        } else {
+                            // the generic instantiations take wave 1's sums before the solve: the penalty adds to them,
+                            // and the late form's live ranges cost these kernels spills
+                            take_late();
                             if (a.penalty) epsq = add_penalty_hb(a, dx, dy, Hm, b);
+                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, a.solver);
                         }
-                        // four lanes share the divides of each Cholesky column (pagk_device.h); all end with the result
-                        const double unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, LEAN ? 0u : a.solver);  // update.squaredNorm()
                         if (tid == 0) {
                             sh_upd[0] = upd[0];
                             sh_upd[1] = upd[1];
@@ -364,7 +407,7 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
                         STAMP(8)   // (wave 2) B1 -> batch A published
                         emit(tc, pix[2], s1[2]);
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        lds_store_b32(flag_addr + 4u, seq);
+                        lds_write_b32(flag_addr + 4u, seq);
                         STAMP(9)   // (wave 2) A published -> C published
                     } else {
                         emit(ta, pix[1], s1[1]);
