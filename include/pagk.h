@@ -320,7 +320,7 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
 /* hipGraph capture of the per-frame work (BASELINE configs[4], "hipGraph-captured iterate").  A camera
  * stream issues the same launches on the same device pointers every frame; between pagk_graph_begin and
  * pagk_graph_end the *_device entry points (pagk_frame_set_device, pagk_gyro_predict_device[_rot],
- * pagk_track_device, pagk_geometry_scores_device) are recorded on the context stream instead of executed,
+ * pagk_track_device, pagk_geometry_scores_device, pagk_geometry_fit_device, pagk_geometry_validation_device) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while
  * capturing; the context stream must not be the legacy default stream; the kernel timers
@@ -339,10 +339,9 @@ int pagk_graph_destroy(pagk_ctx *ctx, int32_t graph_id);
 
 /* Geometry validation, the consumer after the post-filter:
  * the per-correspondence scoring loops of GyroAidedTracker::CheckHomography
- * (src/gyro_aided_tracker.cpp:620-676) and ::CheckFundamental (:704-768).  The RANSAC fits in front
- * of them (cv::findHomography / cv::findFundamentalMat, :596, :699) and H21.inv() (:597) are
- * third-party and stay with the caller, who passes the fitted 3x3 matrices (row-major double, the
- * layout of a CV_64F cv::Mat).  One launch scores both models (the reference runs them on two
+ * (src/gyro_aided_tracker.cpp:620-676) and ::CheckFundamental (:704-768) on models the caller fitted
+ * (cv::findHomography / cv::findFundamentalMat, :596, :699, and H21.inv(), :597 -- or pagk_geometry_fit
+ * below), passed as 3x3 matrices (row-major double, the layout of a CV_64F cv::Mat).  One launch scores both models (the reference runs them on two
  * threads, :455-460); inlier flags and the float scores, accumulated in index order, are
  * bit-identical to the reference loops.  pts1 / pts2: n x 2 float (mvKeysRefUn[i].pt, mvPtPredictUn[i]
  * of the status-true features, :434-440).
@@ -366,6 +365,83 @@ int pagk_geometry_select(float score_H, float score_F);
 int pagk_geometry_validation(pagk_ctx *ctx, const double *H21, const double *H12, const double *F21,
                              int32_t n, const float *pt_ref_un, const float *pt_predict_un,
                              uint8_t *status, float sigma, float *track_score);
+
+/* ---- the RANSAC fits of GeometryValidation, on the device (src/gyro_aided_tracker.cpp:429-480, 589-768) ------ */
+/* The reference fits H21 with cv::findHomography(vPts1, vPts2, cv::RANSAC, 3) (:597) and F21 with
+ * cv::findFundamentalMat(vPts1, vPts2, CV_FM_RANSAC, 3., 0.99) (:691).  These entry points fit both models with a
+ * DETERMINISTIC RANSAC instead.  Parity contract: NO parity with OpenCV is claimed (its random generator, minimal
+ * solvers and Levenberg-Marquardt refinement are third-party and randomised); for a given seed and input the result is
+ * bit-identical to the plain-C restatement in tests/geometry_fit_ref.c, and on clean two-view scenes the fits recover
+ * the true models and inlier sets.  An application that needs OpenCV's own models keeps its fitter
+ * (GyroAidedTracker::SetModelFitter, pagk_geometry_validation).
+ *
+ * The algorithm (m = the status-true correspondences, compacted in index order; all model arithmetic f64):
+ *   sampling   hypothesis h of model k (0 = H, 4 points; 1 = F, 8 points): draw d = 0, 1, ... (at most 64) gives
+ *              index ((z >> 32) * m) >> 32 with z = SplitMix64(seed ^ SplitMix64((k << 56) | (h << 8) | d)); a
+ *              repeated index is redrawn; 64 draws without a full sample make the hypothesis invalid.
+ *   degenerate H samples with three of the four points collinear in either image (sin^2 of the angle <= 1e-6) are
+ *              invalid.
+ *   solve      each image's sample is normalised (centroid to the origin, RMS distance sqrt(2), from the sums
+ *              x, y, x^2 + y^2 taken in sample order); H: 4-point DLT, F: 8-point linear system; the null vector of the
+ *              8x9 system (h9 = 1) by Gaussian elimination with partial pivoting -- a pivot at or below 1e-6 of the
+ *              largest |entry|, a degenerate normalisation or a non-finite model make the hypothesis invalid
+ *              (count -1, never chosen); the model is denormalised (H = T2^-1 Hn T1, F = T2^T Fn T1).
+ *   consensus  H: |p2 w - H p1|^2 <= thresh_H^2 w^2 with w = (H p1)_3 (the squared forward transfer error, without its
+ *              division); F: both squared point-to-epipolar-line distances <= thresh_F^2, compared as
+ *              num^2 <= thresh^2 (a^2 + b^2).  Highest count wins, the lowest index on a tie.
+ *   refit      once, on the best hypothesis' inliers: normalisation from their sums, the 9x9 normal matrix of the linear
+ *              system (each sum: 256 partials over a stride of 256, a fixed tree), its smallest eigenvector by 10 steps
+ *              of inverse iteration on M + 1e-12 tr(M) I (Cholesky); F is made rank 2 by F - (F v) v^T, v from a
+ *              10-sweep cyclic Jacobi on F^T F; no Levenberg-Marquardt refinement (cv::findHomography has one).
+ *              H21 is scaled to h33 = 1 (no model when |h33| <= 1e-12 max |h|), H12 is its inverse (cofactors / det),
+ *              F21 is scaled to f33 = 1, or -- when |f33| <= 1e-12 max |f| -- to its largest |entry| = 1.  The masks are
+ *              the refit models' inliers under the same tests.  No valid hypothesis, fewer inliers than a sample, or a
+ *              non-finite refit: "no model" (info status 0, the model's doubles 0, its mask all 0).
+ *   m <= 8     nothing is fitted (:445): no model, every hypothesis count -1.
+ * Info words, PAGK_FIT_INFO_WORDS int32, six per model (H at 0, F at 6): status (1 = model, 0 = no model), the best
+ * hypothesis (-1: none), its count, the refit model's inlier count, the number of valid hypotheses, and OpenCV's adaptive
+ * iteration count ceil(log(1 - conf) / log(1 - w^s)) for w = best count / m (log restated with + - * /; 0 without a
+ * valid hypothesis) -- more than iters_* means the budget was short of the confidence asked for. */
+#define PAGK_FIT_INFO_WORDS 12
+#define PAGK_FIT_MAX_ITERS 1048576
+typedef struct pagk_fit_params {
+    uint64_t seed;
+    int32_t iters_H;   /* hypotheses of the homography, default 2000 (findHomography's maxIters), 1 .. PAGK_FIT_MAX_ITERS */
+    int32_t iters_F;   /* hypotheses of the fundamental matrix, default 1000                                         */
+    double thresh_H;   /* px, default 3 (:597 ransacReprojThreshold)                                                  */
+    double thresh_F;   /* px, default 3 (:691 param1)                                                                 */
+    double conf_H;     /* default 0.995, reported adaptive count only                                                 */
+    double conf_F;     /* default 0.99 (:691 param2), reported adaptive count only                                    */
+} pagk_fit_params;
+void pagk_fit_params_default(pagk_fit_params *p);
+/* Device pointers, asynchronous on the context stream, capturable (run the same call once before capturing: the
+ * workspace is sized for n and the budgets by a call outside a capture).  d_status may be NULL (every point takes
+ * part); d_models: 27 doubles H21 | H12 | F21 (row-major); d_mask_H / d_mask_F: n flags each, or NULL; d_info:
+ * PAGK_FIT_INFO_WORDS; d_hyp_counts: iters_H + iters_F consensus counts (-1 = invalid), or NULL. */
+int pagk_geometry_fit_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pts1,
+                             const float *d_pts2, const uint8_t *d_status, double *d_models, uint8_t *d_mask_H,
+                             uint8_t *d_mask_F, int32_t *d_info, int32_t *d_hyp_counts);
+/* The same with host buffers, synchronous.  status, mask_H, mask_F and hyp_counts may be NULL. */
+int pagk_geometry_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *pts1, const float *pts2,
+                      const uint8_t *status, double *models, uint8_t *mask_H, uint8_t *mask_F, int32_t *info,
+                      int32_t *hyp_counts);
+/* GyroAidedTracker::GeometryValidation (:429-480) with the fits above, entirely on the device: compaction of the
+ * status-true correspondences, the fits, the scoring loops of pagk_geometry_scores on the fitted models (read from
+ * device memory), the choice of pagk_geometry_select, the chosen model's outliers cleared in d_status (in place).
+ * d_cnt (1 int32) receives cnt_inlier, d_score (1 float) the chosen model's score.  Nothing changes in d_status (and
+ * both outputs are 0) when at most 8 points take part or neither model could be fitted; a model that could not be
+ * fitted scores 0 with no inliers.  Device pointers, asynchronous, capturable like pagk_geometry_fit_device. */
+int pagk_geometry_validation_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pt_ref_un,
+                                    const float *d_pt_predict_un, uint8_t *d_status, float sigma, int32_t *d_cnt,
+                                    float *d_score);
+/* pagk_geometry_validation without models: host buffers, synchronous; returns cnt_inlier (>= 0) or a negative
+ * error.  Equal to pagk_geometry_validation fed with the models of pagk_geometry_fit. */
+int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *pt_ref_un,
+                                 const float *pt_predict_un, uint8_t *status, float sigma, float *track_score);
+/* Diagnostic: the drawn index sets of hypotheses first .. first + count - 1 of model (0 = H: 4 indices each, 1 = F: 8)
+ * among m points, -1s for a hypothesis whose draws ran out.  Host buffer idx, synchronous. */
+int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32_t m, int32_t first, int32_t count,
+                              int32_t *idx);
 
 /* ---- NCC nearest-neighbour matching ------------------------------ */
 /* GyroAidedTracker::FindAndSortNearNeighbor (src/gyro_aided_tracker.cpp:788-851) for all n reference keypoints

@@ -42,6 +42,16 @@ class Params(C.Structure):
     ]
 
 
+class FitParams(C.Structure):
+    """pagk_fit_params (include/pagk.h)."""
+    _fields_ = [("seed", C.c_uint64), ("iters_H", C.c_int32), ("iters_F", C.c_int32), ("thresh_H", C.c_double),
+                ("thresh_F", C.c_double), ("conf_H", C.c_double), ("conf_F", C.c_double)]
+
+
+FIT_INFO_WORDS = 12
+FIT_INFO_FIELDS = ("status", "best", "best_count", "refit_count", "valid", "adaptive")
+
+
 class Outputs(C.Structure):
     _fields_ = [("pt_un", C.c_void_p), ("pt_dist", C.c_void_p), ("status", C.c_void_p),
                 ("pix_err", C.c_void_p), ("dist_pred", C.c_void_p), ("ncc", C.c_void_p),
@@ -201,6 +211,18 @@ def declare(lib) -> None:
     lib.pagk_geometry_select.argtypes = [f32, f32]
     lib.pagk_geometry_validation.restype = C.c_int
     lib.pagk_geometry_validation.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, f32, _P(f32)]
+    lib.pagk_fit_params_default.restype = None
+    lib.pagk_fit_params_default.argtypes = [_P(FitParams)]
+    lib.pagk_geometry_fit_device.restype = C.c_int
+    lib.pagk_geometry_fit_device.argtypes = [vp, _P(FitParams), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pagk_geometry_fit.restype = C.c_int
+    lib.pagk_geometry_fit.argtypes = [vp, _P(FitParams), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pagk_geometry_validation_device.restype = C.c_int
+    lib.pagk_geometry_validation_device.argtypes = [vp, _P(FitParams), i32, vp, vp, vp, f32, vp, vp]
+    lib.pagk_geometry_validation_fit.restype = C.c_int
+    lib.pagk_geometry_validation_fit.argtypes = [vp, _P(FitParams), i32, vp, vp, vp, f32, _P(f32)]
+    lib.pagk_selftest_fit_samples.restype = C.c_int
+    lib.pagk_selftest_fit_samples.argtypes = [vp, C.c_uint64, i32, i32, i32, i32, vp]
     lib.pagk_near_neighbors_device.restype = C.c_int
     lib.pagk_near_neighbors_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, i32, i32,
                                                vp, vp, vp, vp]
@@ -269,7 +291,20 @@ EXPORTED_SYMBOLS = [
     "pagk_multi_allgather", "pagk_track_sharded", "pagk_selftest_divide", "pagk_selftest_solve",
     "pagk_selftest_repeat_sum", "pagk_check_launch", "pagk_track_device_batch", "pagk_frame_set_device_batch", "pagk_priority_threshold",
     "pagk_multi_comm_count", "pagk_has_variant",
+    "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
+    "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
 ]
+
+
+def fit_params_default(**overrides) -> FitParams:
+    """pagk_fit_params_default() with overrides (seed, iters_H, iters_F, thresh_H, thresh_F, conf_H, conf_F)."""
+    p = FitParams()
+    load().pagk_fit_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(FitParams._fields_):
+            raise TypeError(f"pagk_fit_params has no field {k}")
+        setattr(p, k, v)
+    return p
 
 
 def load():
@@ -479,6 +514,72 @@ class Context:
         if rc < 0:
             self._check(rc, "pagk_geometry_validation")
         return rc, st, np.float32(ts.value)
+
+    # the RANSAC fits of GeometryValidation on the device (src/gyro_aided_tracker.cpp:429-480, 589-768) ------------
+    fit_params_default = staticmethod(fit_params_default)
+
+    def geometry_fit(self, pts1, pts2, status=None, params: FitParams | None = None, hyp_counts: bool = False):
+        """Deterministic RANSAC fits of H21 and F21 (include/pagk.h pagk_geometry_fit), host buffers -> dict(H21, H12,
+        F21, mask_H, mask_F, info, H / F: the info words by name, hyp_counts when asked for)."""
+        params = params if params is not None else fit_params_default()
+        pts1 = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2)
+        pts2 = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+        n = pts1.shape[0]
+        if pts2.shape[0] != n:
+            raise ValueError("pts1 / pts2 differ in length")
+        st = None if status is None else np.ascontiguousarray(status, np.uint8)
+        if st is not None and st.shape[0] != n:
+            raise ValueError("status has the wrong length")
+        models = np.zeros(27, np.float64)
+        mH, mF = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        info = np.zeros(FIT_INFO_WORDS, np.int32)
+        hc = np.zeros(params.iters_H + params.iters_F, np.int32) if hyp_counts else None
+        self._check(self.lib.pagk_geometry_fit(self.h, C.byref(params), n, _ptr(pts1), _ptr(pts2), _ptr(st),
+                                               _ptr(models), _ptr(mH), _ptr(mF), _ptr(info), _ptr(hc)),
+                    "pagk_geometry_fit")
+        out = dict(models=models, H21=models[:9].reshape(3, 3), H12=models[9:18].reshape(3, 3),
+                   F21=models[18:].reshape(3, 3), mask_H=mH[:n], mask_F=mF[:n], info=info,
+                   H=dict(zip(FIT_INFO_FIELDS, info[:6].tolist())), F=dict(zip(FIT_INFO_FIELDS, info[6:].tolist())))
+        if hc is not None:
+            out["hyp_counts"] = hc
+        return out
+
+    def geometry_fit_device(self, params: FitParams, n: int, d_pts1, d_pts2, d_status, d_models, d_mask_H, d_mask_F,
+                            d_info, d_hyp_counts=None):
+        """pagk_geometry_fit_device on device arrays (asynchronous, capturable)."""
+        self._check(self.lib.pagk_geometry_fit_device(self.h, C.byref(params), n, _ptr(d_pts1), _ptr(d_pts2),
+                                                      _ptr(d_status), _ptr(d_models), _ptr(d_mask_H), _ptr(d_mask_F),
+                                                      _ptr(d_info), _ptr(d_hyp_counts)), "pagk_geometry_fit_device")
+
+    def geometry_validation_fit(self, pt_ref_un, pt_predict_un, status, sigma: float = 1.0,
+                                params: FitParams | None = None):
+        """GyroAidedTracker::GeometryValidation with the device fits (src/gyro_aided_tracker.cpp:429-480)
+        -> (cnt_inlier, status, track_score)."""
+        params = params if params is not None else fit_params_default()
+        p1 = np.ascontiguousarray(pt_ref_un, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(pt_predict_un, np.float32).reshape(-1, 2)
+        st = np.array(status, np.uint8, copy=True)
+        ts = C.c_float(0)
+        rc = self.lib.pagk_geometry_validation_fit(self.h, C.byref(params), st.shape[0], _ptr(p1), _ptr(p2), _ptr(st),
+                                                   sigma, C.byref(ts))
+        if rc < 0:
+            self._check(rc, "pagk_geometry_validation_fit")
+        return rc, st, np.float32(ts.value)
+
+    def geometry_validation_device(self, params: FitParams, n: int, d_pt_ref_un, d_pt_predict_un, d_status,
+                                   sigma: float, d_cnt, d_score):
+        """pagk_geometry_validation_device: d_status updated in place, d_cnt (int32) and d_score (float32) written;
+        asynchronous, capturable."""
+        self._check(self.lib.pagk_geometry_validation_device(self.h, C.byref(params), n, _ptr(d_pt_ref_un),
+                                                             _ptr(d_pt_predict_un), _ptr(d_status), sigma, _ptr(d_cnt),
+                                                             _ptr(d_score)), "pagk_geometry_validation_device")
+
+    def selftest_fit_samples(self, seed: int, model: int, m: int, first: int, count: int) -> np.ndarray:
+        """The drawn index sets of hypotheses [first, first + count) of model 0 (H, 4 each) or 1 (F, 8 each)."""
+        out = np.zeros((max(count, 1), 8 if model else 4), np.int32)
+        self._check(self.lib.pagk_selftest_fit_samples(self.h, seed, model, m, first, count, _ptr(out)),
+                    "pagk_selftest_fit_samples")
+        return out[:count]
 
     # NCC nearest-neighbour matching (SURVEY.md section 8 row f3) ------------------------------
     def find_near_neighbors(self, img_ref, img_cur, half_patch, keys_ref, pt_predict_un, status, affine, keys_cur,

@@ -312,9 +312,30 @@ void GyroAidedTracker::SetModelFitter(ModelFitter fitter) { model_fitter() = std
 
 int GyroAidedTracker::GeometryValidation()
 {
-    if (!model_fitter())
-        throw std::runtime_error("GyroAidedTracker::GeometryValidation(): no model fitter installed "
-                                 "(cv::findHomography / cv::findFundamentalMat are the application's)");
+    if (!model_fitter()) {  // the fits on the device (:429-480, 589-768)
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<float> p1(2 * (size_t)mN + 2), p2(2 * (size_t)mN + 2);
+        std::vector<cv::uchar> status(mN ? mN : 1);
+        for (int i = 0; i < mN; i++) {
+            p1[2 * i] = mvKeysRefUn[i].pt.x, p1[2 * i + 1] = mvKeysRefUn[i].pt.y;
+            p2[2 * i] = mvPtPredictUn[i].x, p2[2 * i + 1] = mvPtPredictUn[i].y;
+            status[i] = mvStatus[i];
+        }
+        pagk_fit_params fp;
+        pagk_fit_params_default(&fp);
+        fp.seed = mFitSeed;
+        float score = 0;
+        int cnt_inlier = pagk_geometry_validation_fit(PatchMatch::Context(), &fp, mN, p1.data(), p2.data(),
+                                                      status.data(), 1.0f, &score);
+        if (cnt_inlier < 0)
+            throw std::runtime_error(std::string("pagk_geometry_validation_fit failed: ") + pagk_strerror(cnt_inlier));
+        for (int i = 0; i < mN; i++) mvStatus[i] = status[i];  // :472-476
+        mTrackScore = score;
+        mTimeCostGeometryValidation = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
+        mTImeCostTotalFeatureTrack =
+            mTimeCostGyroPredict + mTimeCostOptFlow + mTimeCostOptFlowResultFilterOut + mTimeCostGeometryValidation;
+        return cnt_inlier;
+    }
     std::vector<cv::Point2f> vPts1, vPts2;  // :433-440
     for (size_t i = 0, iend = mvKeysRefUn.size(); i < iend; i++)
         if (mvStatus[i]) {

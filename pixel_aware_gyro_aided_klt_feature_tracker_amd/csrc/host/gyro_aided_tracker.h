@@ -111,13 +111,20 @@ public:
 
     // Step 2 of the tracker, reference include/gyro_aided_tracker.h:134 / src/gyro_aided_tracker.cpp:429-480.
     // The reference fits H21 and F21 inside CheckHomography / CheckFundamental with OpenCV's RANSAC
-    // (:596, :699) and inverts H21 with cv::Mat::inv (:597); here the application supplies those three
+    // (:596, :699) and inverts H21 with cv::Mat::inv (:597); here an application may supply those three
     // 3x3 row-major double matrices -- through a fitter installed once, or per call -- and the scoring
     // loops, the model choice and the outlier marking run behind pagk_geometry_validation.
     using ModelFitter = std::function<bool(const std::vector<cv::Point2f> &vPts1, const std::vector<cv::Point2f> &vPts2,
                                            double H21[9], double H12[9], double F21[9])>;
+    // Without an installed fitter, GeometryValidation() fits both models on the device (pagk_geometry_validation_fit:
+    // a deterministic RANSAC, NOT OpenCV's -- include/pagk.h states the contract); an installed fitter takes precedence.
     static void SetModelFitter(ModelFitter fitter);
-    int GeometryValidation();  // reference signature; needs a fitter (throws std::runtime_error without one)
+    int GeometryValidation();  // reference signature
+    // Seed of the device fit (pagk_fit_params::seed); kDefaultFitSeed unless set.  Budgets and thresholds are
+    // pagk_fit_params_default()'s: the reference's 3 px (:597, :691).
+    static constexpr uint64_t kDefaultFitSeed = 0x5EED0F17ull;
+    void SetFitSeed(uint64_t seed) { mFitSeed = seed; }
+    uint64_t mFitSeed = kDefaultFitSeed;
     int GeometryValidation(const double *H21, const double *H12, const double *F21, float sigma = 1.0f);
     float mTrackScore = 0;  // `track_score` of the reference's log line (:447, :465-470)
     void IntegrateGyroMeasurements();

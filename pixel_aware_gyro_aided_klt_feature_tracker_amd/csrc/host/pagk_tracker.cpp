@@ -124,6 +124,36 @@ int pagk_tracker_geometry_validation(int n, const float *keys_ref_un, const floa
     }
 }
 
+// The same without models: GeometryValidation() with no fitter installed, i.e. the device fits
+// (pagk_geometry_validation_fit) seeded with `seed`.  Returns cnt_inlier or -100 on an exception.
+int pagk_tracker_geometry_validation_fit(int n, const float *keys_ref_un, const float *pt_predict_un,
+                                         unsigned char *status, unsigned long long seed, float *track_score)
+{
+    try {
+        static unsigned char px = 0;
+        cv::Mat img(1, 1, cv::CV_8UC1, &px, 1);
+        std::vector<cv::KeyPoint> keys(n), none;
+        for (int i = 0; i < n; i++) keys[i].pt = cv::Point2f(keys_ref_un[2 * i], keys_ref_un[2 * i + 1]);
+        cv::Mat Km = cv::Mat::eye(3, 3, cv::CV_32F), Dm(1, 4, cv::CV_32F), table;
+        for (int k = 0; k < 4; k++) Dm.at<float>(k) = 0;
+        std::vector<IMU::Point> vimu;
+        GyroAidedTracker trk(0, 0, img, img, keys, none, keys, none, vimu, cv::Point3f(0, 0, 0), Km, Dm, table);
+        for (int i = 0; i < n; i++) {
+            trk.mvStatus[i] = status[i];
+            trk.mvPtPredictUn[i] = cv::Point2f(pt_predict_un[2 * i], pt_predict_un[2 * i + 1]);
+        }
+        GyroAidedTracker::SetModelFitter(nullptr);
+        trk.SetFitSeed(seed);
+        int ret = trk.GeometryValidation();
+        for (int i = 0; i < n; i++) status[i] = trk.mvStatus[i];
+        if (track_score) *track_score = trk.mTrackScore;
+        return ret;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -100;
+    }
+}
+
 // ---- sequence formats (sequence_io.h), flat C views for tests and other languages ------------------
 // Each returns the number of records (written up to `cap`), or -1 if the file cannot be opened.
 int pagk_seq_load_keypoints(const char *path, float *xy /*cap x 2*/, int cap)

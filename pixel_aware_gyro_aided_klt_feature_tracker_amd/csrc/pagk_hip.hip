@@ -47,6 +47,9 @@ struct pagk_ctx {
     FrameSlot slots[kSlots];
     FeatBuf feat;
     FeatBuf score;  // scratch of the host-buffer geometry scoring path
+    FeatBuf fit;    // workspace of the device RANSAC fits (pagk_fit_kernel.h): sized outside captures, pointed into by graphs
+    int fit_n = 0, fit_iters = 0;  // what `fit` holds room for
+    FeatBuf fitio;  // scratch of the host-buffer fit / validation entry points
     void *quad_ws = nullptr;  // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
     size_t quad_ws_bytes = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
@@ -1203,6 +1206,8 @@ void pagk_destroy(pagk_ctx *ctx)
     if (ctx->feat.block) (void)hipFree(ctx->feat.block);
     if (ctx->feat.host) (void)hipHostFree(ctx->feat.host);
     if (ctx->score.block) (void)hipFree(ctx->score.block);
+    if (ctx->fit.block) (void)hipFree(ctx->fit.block);
+    if (ctx->fitio.block) (void)hipFree(ctx->fitio.block);
     if (ctx->quad_ws) (void)hipFree(ctx->quad_ws);
     if (ctx->susp) (void)hipFree(ctx->susp);
     if (ctx->queue) (void)hipFree(ctx->queue);
@@ -2088,6 +2093,236 @@ int pagk_geometry_validation(pagk_ctx *ctx, const double *H21, const double *H12
     }
 }
 
+// ---- the RANSAC fits on the device (pagk_fit_kernel.h) ----------------------------------------------------------
+void pagk_fit_params_default(pagk_fit_params *p)
+{
+    if (!p) return;
+    p->seed = 0;
+    p->iters_H = 2000;  // findHomography's default maxIters
+    p->iters_F = 1000;
+    p->thresh_H = 3.0;  // src/gyro_aided_tracker.cpp:597
+    p->thresh_F = 3.0;  // :691
+    p->conf_H = 0.995;
+    p->conf_F = 0.99;   // :691
+}
+
+namespace {
+
+bool fit_params_ok(const pagk_fit_params *p)
+{
+    return p && p->iters_H >= 1 && p->iters_H <= PAGK_FIT_MAX_ITERS && p->iters_F >= 1 &&
+           p->iters_F <= PAGK_FIT_MAX_ITERS && std::isfinite(p->thresh_H) && p->thresh_H > 0 &&
+           std::isfinite(p->thresh_F) && p->thresh_F > 0 && p->conf_H > 0 && p->conf_H < 1 && p->conf_F > 0 &&
+           p->conf_F < 1;
+}
+
+// the fit workspace: FitHdr | p1 | p2 | idx | hypothesis models | hypothesis counts | models | info | scores |
+// inl_H | inl_F (the last three for the validation path)
+struct FitWs {
+    FitHdr *hdr;
+    float *p1, *p2;
+    int32_t *idx;
+    double *hyp_models;
+    int32_t *hyp_counts;
+    double *models;
+    int32_t *info;
+    float *scores;
+    uint8_t *inl_H, *inl_F;
+};
+
+size_t fit_layout(int32_t n, int32_t iters, size_t off[11])
+{
+    const size_t nn = (size_t)(n < 1 ? 1 : n), hh = (size_t)iters;
+    const size_t sizes[11] = {sizeof(FitHdr), nn * 8, nn * 8, nn * 4, hh * 72, hh * 4, 27 * 8, kFitInfoWords * 4, 8, nn, nn};
+    size_t total = 0;
+    for (int k = 0; k < 11; k++) {
+        off[k] = total;
+        total = align_up(total + sizes[k], 256);
+    }
+    return total;
+}
+
+// Room for n correspondences and `iters` hypotheses; grows only outside a capture and while no graph of this context
+// is alive (its nodes point into the workspace).
+int fit_workspace(pagk_ctx *ctx, int32_t n, int32_t iters, FitWs *w)
+{
+    size_t off[11];
+    if (n > ctx->fit_n || iters > ctx->fit_iters || !ctx->fit.block) {
+        if (in_capture(ctx)) {
+            snprintf(ctx->err, sizeof(ctx->err), "the geometry fit's workspace would have to grow inside a capture: run the "
+                     "call once with at least %d correspondences and %d hypotheses before capturing", n, iters);
+            return PAGK_E_ARG;
+        }
+        int rc = no_live_graphs(ctx, "the geometry fit's workspace");
+        if (rc) return rc;
+        const int32_t n2 = n > ctx->fit_n ? n : ctx->fit_n, it2 = iters > ctx->fit_iters ? iters : ctx->fit_iters;
+        if (ctx->fit.block) HIPCHK(ctx, hipFree(ctx->fit.block));
+        ctx->fit.block = nullptr;
+        ctx->fit_n = ctx->fit_iters = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->fit.block, fit_layout(n2, it2, off)));
+        ctx->fit_n = n2, ctx->fit_iters = it2;
+    }
+    fit_layout(ctx->fit_n, ctx->fit_iters, off);
+    uint8_t *b = static_cast<uint8_t *>(ctx->fit.block);
+    w->hdr = reinterpret_cast<FitHdr *>(b + off[0]);
+    w->p1 = reinterpret_cast<float *>(b + off[1]);
+    w->p2 = reinterpret_cast<float *>(b + off[2]);
+    w->idx = reinterpret_cast<int32_t *>(b + off[3]);
+    w->hyp_models = reinterpret_cast<double *>(b + off[4]);
+    w->hyp_counts = reinterpret_cast<int32_t *>(b + off[5]);
+    w->models = reinterpret_cast<double *>(b + off[6]);
+    w->info = reinterpret_cast<int32_t *>(b + off[7]);
+    w->scores = reinterpret_cast<float *>(b + off[8]);
+    w->inl_H = b + off[9];
+    w->inl_F = b + off[10];
+    return PAGK_OK;
+}
+
+// compaction + hypotheses + refit on the context stream
+int fit_launch(pagk_ctx *ctx, const pagk_fit_params *p, int32_t n, const float *d_pts1, const float *d_pts2,
+               const uint8_t *d_status, double *d_models, uint8_t *d_mask_H, uint8_t *d_mask_F, int32_t *d_info,
+               int32_t *d_hyp_counts, FitWs *w)
+{
+    int rc = fit_workspace(ctx, n, p->iters_H + p->iters_F, w);
+    if (rc) return rc;
+    double *models = d_models ? d_models : w->models;
+    int32_t *info = d_info ? d_info : w->info;
+    hipLaunchKernelGGL(k_fit_compact, dim3(1), dim3(1024), 0, ctx->stream, n, d_pts1, d_pts2, d_status, w->p1, w->p2,
+                       w->idx, w->hdr, models, info, d_mask_H, d_mask_F);
+    HIPCHK(ctx, hipGetLastError());
+    FitArgs a;
+    memset(&a, 0, sizeof a);
+    a.p1 = w->p1, a.p2 = w->p2, a.idx = w->idx, a.hdr = w->hdr, a.hyp_models = w->hyp_models;
+    a.hyp_counts = d_hyp_counts ? d_hyp_counts : w->hyp_counts;
+    a.models = models, a.info = info, a.mask_H = d_mask_H, a.mask_F = d_mask_F;
+    a.seed = p->seed;
+    a.iters[0] = p->iters_H, a.iters[1] = p->iters_F;
+    a.nblk_H = (p->iters_H + kFitHypPerBlock - 1) / kFitHypPerBlock;
+    a.t2[0] = p->thresh_H * p->thresh_H, a.t2[1] = p->thresh_F * p->thresh_F;
+    a.conf[0] = p->conf_H, a.conf[1] = p->conf_F;
+    const int nblk = a.nblk_H + (p->iters_F + kFitHypPerBlock - 1) / kFitHypPerBlock;
+    hipLaunchKernelGGL(k_fit_hyp, dim3(nblk), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fit_refit, dim3(2), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    w->models = models, w->info = info;
+    return PAGK_OK;
+}
+
+// host-path I/O scratch of `bytes`
+int fitio_reserve(pagk_ctx *ctx, size_t bytes)
+{
+    if (bytes > ctx->fitio.bytes) {
+        if (ctx->fitio.block) HIPCHK(ctx, hipFree(ctx->fitio.block));
+        ctx->fitio.block = nullptr;
+        ctx->fitio.bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->fitio.block, bytes));
+        ctx->fitio.bytes = bytes;
+    }
+    return PAGK_OK;
+}
+
+}  // namespace
+
+int pagk_geometry_fit_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pts1,
+                             const float *d_pts2, const uint8_t *d_status, double *d_models, uint8_t *d_mask_H,
+                             uint8_t *d_mask_F, int32_t *d_info, int32_t *d_hyp_counts)
+{
+    if (!ctx || !fit_params_ok(params) || n < 0 || !d_models || !d_info) return PAGK_E_ARG;
+    if (n > 0 && (!d_pts1 || !d_pts2)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FitWs w;
+    return fit_launch(ctx, params, n, d_pts1, d_pts2, d_status, d_models, d_mask_H, d_mask_F, d_info, d_hyp_counts, &w);
+}
+
+int pagk_geometry_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *pts1, const float *pts2,
+                      const uint8_t *status, double *models, uint8_t *mask_H, uint8_t *mask_F, int32_t *info,
+                      int32_t *hyp_counts)
+{
+    if (!ctx || !fit_params_ok(params) || n < 0 || !models || !info) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_geometry_fit");
+    if (n > 0 && (!pts1 || !pts2)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)(n < 1 ? 1 : n), hh = (size_t)params->iters_H + (size_t)params->iters_F;
+    const size_t o_p2 = align_up(nn * 8, 256), o_st = o_p2 + align_up(nn * 8, 256), o_h = o_st + align_up(nn, 256);
+    const size_t o_f = o_h + align_up(nn, 256), o_c = o_f + align_up(nn, 256), o_m = o_c + align_up(hh * 4, 256);
+    const size_t o_i = o_m + 256, total = o_i + 256;
+    int rc = fitio_reserve(ctx, total);
+    if (rc) return rc;
+    uint8_t *b = static_cast<uint8_t *>(ctx->fitio.block);
+    if (n > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(b, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(b + o_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (status) HIPCHK(ctx, hipMemcpyAsync(b + o_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    FitWs w;
+    rc = fit_launch(ctx, params, n, reinterpret_cast<float *>(b), reinterpret_cast<float *>(b + o_p2),
+                    status ? b + o_st : nullptr, reinterpret_cast<double *>(b + o_m), b + o_h, b + o_f,
+                    reinterpret_cast<int32_t *>(b + o_i), reinterpret_cast<int32_t *>(b + o_c), &w);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(models, b + o_m, 27 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(info, b + o_i, PAGK_FIT_INFO_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && mask_H) HIPCHK(ctx, hipMemcpyAsync(mask_H, b + o_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && mask_F) HIPCHK(ctx, hipMemcpyAsync(mask_F, b + o_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (hyp_counts) HIPCHK(ctx, hipMemcpyAsync(hyp_counts, b + o_c, hh * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_geometry_validation_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pt_ref_un,
+                                    const float *d_pt_predict_un, uint8_t *d_status, float sigma, int32_t *d_cnt,
+                                    float *d_score)
+{
+    if (!ctx || !fit_params_ok(params) || n < 0 || !d_cnt || !d_score) return PAGK_E_ARG;
+    if (n > 0 && (!d_pt_ref_un || !d_pt_predict_un || !d_status)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FitWs w;
+    int rc = fit_launch(ctx, params, n, d_pt_ref_un, d_pt_predict_un, d_status, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, &w);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_geometry_scores_fit, dim3(2), dim3(256), 0, ctx->stream, w.models, w.info, &w.hdr->m, w.p1,
+                       w.p2, sigma, w.inl_H, w.inl_F, w.scores);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fit_select, dim3(1), dim3(1024), 0, ctx->stream, w.hdr, w.info, w.scores, w.inl_H, w.inl_F,
+                       w.idx, d_status, d_cnt, d_score);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *pt_ref_un,
+                                 const float *pt_predict_un, uint8_t *status, float sigma, float *track_score)
+{
+    if (!ctx || !fit_params_ok(params) || n < 0) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_geometry_validation_fit");
+    if (n > 0 && (!pt_ref_un || !pt_predict_un || !status)) return PAGK_E_ARG;
+    if (track_score) *track_score = 0;  // :447
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)(n < 1 ? 1 : n);
+    const size_t o_p2 = align_up(nn * 8, 256), o_st = o_p2 + align_up(nn * 8, 256), o_c = o_st + align_up(nn, 256);
+    const size_t total = o_c + 256;
+    int rc = fitio_reserve(ctx, total);
+    if (rc) return rc;
+    uint8_t *b = static_cast<uint8_t *>(ctx->fitio.block);
+    if (n > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(b, pt_ref_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(b + o_p2, pt_predict_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(b + o_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int32_t *d_cnt = reinterpret_cast<int32_t *>(b + o_c);
+    float *d_score = reinterpret_cast<float *>(b + o_c + 8);
+    rc = pagk_geometry_validation_device(ctx, params, n, reinterpret_cast<float *>(b), reinterpret_cast<float *>(b + o_p2),
+                                         b + o_st, sigma, d_cnt, d_score);
+    if (rc) return rc;
+    int32_t cnt = 0;
+    float sc = 0;
+    if (n > 0) HIPCHK(ctx, hipMemcpyAsync(status, b + o_st, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&sc, d_score, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (track_score) *track_score = sc;
+    return cnt;
+}
+
 // ---- NCC nearest-neighbour matching ---------------------------------
 static int near_neighbors_launch(pagk_ctx *ctx, const FrameSlot &sr, const FrameSlot &sc, int32_t half_patch, int32_t n,
                                  const float *d_keys_ref, const float *d_pt_predict_un, const uint8_t *d_status,
@@ -2285,6 +2520,25 @@ int pagk_selftest_divide(pagk_ctx *ctx, int32_t n, const double *num, const doub
     HIPCHK(ctx, hipMemcpyAsync(q_prepared, d + 3 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(root, d + 4 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(root_lean, d + 5 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32_t m, int32_t first, int32_t count,
+                              int32_t *idx)
+{
+    if (!ctx || (model != 0 && model != 1) || m < 1 || first < 0 || count < 0 || !idx) return PAGK_E_ARG;
+    if ((int64_t)first + count > (int64_t)PAGK_FIT_MAX_ITERS) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_fit_samples");
+    if (count == 0) return PAGK_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch s;
+    const size_t bytes = (size_t)count * (model ? 8 : 4) * sizeof(int32_t);
+    HIPCHK(ctx, hipMalloc(&s.p, bytes));
+    hipLaunchKernelGGL(k_fit_samples, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long)seed, model,
+                       m, first, count, static_cast<int32_t *>(s.p));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(idx, s.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }

@@ -1270,5 +1270,6 @@ __global__ void __launch_bounds__(256, 4) k_track_block_pyr(TrackArgs a, PyrArgs
 #include "pagk_rows_kernel.h"
 #endif
 #include "pagk_score_kernel.h"
+#include "pagk_fit_kernel.h"
 #include "pagk_neighbor_kernel.h"
 #include "pagk_selftest_kernel.h"

@@ -1,8 +1,7 @@
 // pagk_score_kernel.h -- the per-correspondence scoring loops of GyroAidedTracker::GeometryValidation
 // (reference src/gyro_aided_tracker.cpp:589-768): CheckHomography (symmetric transfer error, chi-square
-// 5.99) and CheckFundamental (point-to-epipolar-line distance, 3.84 / 5.99).  The RANSAC model fit that
-// precedes them is third-party (cv::findHomography / cv::findFundamentalMat) and stays with the caller:
-// the fitted matrices come in as arguments.
+// 5.99) and CheckFundamental (point-to-epipolar-line distance, 3.84 / 5.99).  The fitted matrices come in as
+// arguments (the caller's own fit), or from device memory behind the library's fit (pagk_fit_kernel.h).
 //
 // One launch scores both models, block 0 the homography and block 1 the fundamental matrix (the
 // reference runs the two loops on two std::threads, :455-460).  The per-point arithmetic is
@@ -93,26 +92,28 @@ __device__ __forceinline__ int score_f_point(const double *f, float u1, float v1
     return bIn;
 }
 
-__global__ void __launch_bounds__(256) k_geometry_scores(ScoreArgs a)
+// Both scoring loops of one launch: workgroup `model` (0: homography, 1: fundamental) scores the n correspondences
+// and writes its inlier flags and its score.  The models may live in the kernel arguments or in device memory.
+__device__ __forceinline__ void score_model(int model, const double *H21, const double *H12, const double *F21,
+                                            const float *pts1, const float *pts2, int n, float sigma, uint8_t *inl,
+                                            float *scores)
 {
     // [0] carry, [1 .. 2*chunk] terms, + one block the chain may read past the end
     __shared__ __attribute__((aligned(16))) float terms[1 + 2 * kScoreChunk + 32];
-    const int model = blockIdx.x;  // 0: homography, 1: fundamental
     const int tid = threadIdx.x;
-    const float invSigmaSquare = (float)(1.0 / (double)(a.sigma * a.sigma));  // :625 / :709
-    uint8_t *inl = model == 0 ? a.inl_H : a.inl_F;
+    const float invSigmaSquare = (float)(1.0 / (double)(sigma * sigma));  // :625 / :709
     float carry = 0.0f;  // :623 / :706
-    for (int base = 0; base < a.n; base += kScoreChunk) {
-        const int cnt = a.n - base < kScoreChunk ? a.n - base : kScoreChunk;
+    for (int base = 0; base < n; base += kScoreChunk) {
+        const int cnt = n - base < kScoreChunk ? n - base : kScoreChunk;
         const int nfull = (2 * cnt + 31) / 32;  // chain length = 32 * nfull + 1
         if (tid == 0) terms[0] = carry;
         for (int k = tid; k < 16 * nfull; k += 256) {
             float t2 = 0.0f, t1 = 0.0f;  // padding past cnt: +0.0f
             if (k < cnt) {
                 const int i = base + k;
-                const float u1 = a.pts1[2 * i], v1 = a.pts1[2 * i + 1], u2 = a.pts2[2 * i], v2 = a.pts2[2 * i + 1];
-                const int bIn = model == 0 ? score_h_point(a.H21, a.H12, u1, v1, u2, v2, invSigmaSquare, t2, t1)
-                                           : score_f_point(a.F21, u1, v1, u2, v2, invSigmaSquare, t2, t1);
+                const float u1 = pts1[2 * i], v1 = pts1[2 * i + 1], u2 = pts2[2 * i], v2 = pts2[2 * i + 1];
+                const int bIn = model == 0 ? score_h_point(H21, H12, u1, v1, u2, v2, invSigmaSquare, t2, t1)
+                                           : score_f_point(F21, u1, v1, u2, v2, invSigmaSquare, t2, t1);
                 inl[i] = (uint8_t)bIn;
             }
             terms[1 + 2 * k] = t2;
@@ -125,7 +126,32 @@ __global__ void __launch_bounds__(256) k_geometry_scores(ScoreArgs a)
         }
         __syncthreads();  // the chain has read the chunk before the next one is written
     }
-    if (tid == 0) a.scores[model] = carry;
+    if (tid == 0) scores[model] = carry;
+}
+
+__global__ void __launch_bounds__(256) k_geometry_scores(ScoreArgs a)
+{
+    const int model = blockIdx.x;
+    score_model(model, a.H21, a.H12, a.F21, a.pts1, a.pts2, a.n, a.sigma, model == 0 ? a.inl_H : a.inl_F, a.scores);
+}
+
+// The same loops on the output of a device fit (pagk_fit_kernel.h): models (H21 | H12 | F21), the correspondence count
+// and whether each model exists are read from device memory, so that a captured graph replays them with each frame's
+// fit.  A model that was not fitted has no inliers and scores 0; with m <= 8 nothing is scored (:445).
+__global__ void __launch_bounds__(256) k_geometry_scores_fit(const double *models, const int32_t *info,
+                                                             const int32_t *d_n, const float *pts1, const float *pts2,
+                                                             float sigma, uint8_t *inl_H, uint8_t *inl_F, float *scores)
+{
+    const int model = blockIdx.x;
+    const int n = *d_n;
+    if (n <= 8) return;
+    uint8_t *inl = model == 0 ? inl_H : inl_F;
+    if (info[6 * model] == 0) {
+        for (int k = threadIdx.x; k < n; k += 256) inl[k] = 0;
+        if (threadIdx.x == 0) scores[model] = 0.0f;
+        return;
+    }
+    score_model(model, models, models + 9, models + 18, pts1, pts2, n, sigma, inl, scores);
 }
 
 }  // namespace pagk

@@ -26,6 +26,8 @@ def load():
                                                     C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.pagk_tracker_geometry_validation.restype = C.c_int
         lib.pagk_tracker_geometry_validation.argtypes = [i, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+        lib.pagk_tracker_geometry_validation_fit.restype = C.c_int
+        lib.pagk_tracker_geometry_validation_fit.argtypes = [i, vp, vp, vp, C.c_ulonglong, C.POINTER(C.c_float)]
         lib.pagk_seq_load_keypoints.restype = C.c_int
         lib.pagk_seq_load_keypoints.argtypes = [C.c_char_p, vp, i]
         lib.pagk_seq_load_correspondences.restype = C.c_int
@@ -89,6 +91,24 @@ def geometry_validation(keys_ref_un, pt_predict_un, status, H21, H12, F21):
 
 
 # ---- sequence formats of the reference's demo (csrc/host/sequence_io.h) ----
+def geometry_validation_fit(keys_ref_un, pt_predict_un, status, seed=None):
+    """GyroAidedTracker::GeometryValidation() with no fitter installed: the device fits (reference
+    src/gyro_aided_tracker.cpp:429-480, 589-768) -> (cnt_inlier, status, track_score).  seed None = the shell's default."""
+    lib = load()
+    k = np.ascontiguousarray(keys_ref_un, np.float32).reshape(-1, 2)
+    q = np.ascontiguousarray(pt_predict_un, np.float32).reshape(-1, 2)
+    st = np.array(status, np.uint8, copy=True)
+    ts = C.c_float(0)
+    ret = lib.pagk_tracker_geometry_validation_fit(int(st.shape[0]), k.ctypes.data, q.ctypes.data, st.ctypes.data,
+                                                   DEFAULT_FIT_SEED if seed is None else int(seed), C.byref(ts))
+    if ret == -100:
+        raise RuntimeError("GyroAidedTracker: " + lib.pagk_tracker_last_error().decode())
+    return ret, st, np.float32(ts.value)
+
+
+DEFAULT_FIT_SEED = 0x5EED0F17   # GyroAidedTracker::kDefaultFitSeed
+
+
 def load_keypoints(path: str) -> np.ndarray:
     """SuperPoint keypoint list "idx, x, y" (reference src/frame.cpp:222-240) -> n x 2 float32."""
     lib = load()
