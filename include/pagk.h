@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PAGK_VERSION 303 /* 0.3.3: + pagk_priority_threshold; 0.3.2: + pagk_frame_set_device_batch; 0.3.1: pipelined 4-wave kernel, pagk_track_device_batch, pagk_check_launch, pagk_selftest_repeat_sum */
+#define PAGK_VERSION 303 /* 0.3.3: + pagk_priority_threshold (the fits, pagk_post_filter_device, pagk_frame_handover[_device] and pagk_gyro_predict_device_live came later under the same number: ask for a symbol, not for the number); 0.3.2: + pagk_frame_set_device_batch; 0.3.1: pipelined 4-wave kernel, pagk_track_device_batch, pagk_check_launch, pagk_selftest_repeat_sum */
 
 #define PAGK_MAX_PYRAMIDS 8
 #define PAGK_MAX_HALF_PATCH 15 /* (2h+1)^2 <= 961 pixels */
@@ -296,6 +296,73 @@ int pagk_post_filter(int32_t n, int32_t half_patch, const uint8_t *status_pm,
                      const double *pix_err, const double *dist_pred, const float *pt_pm,
                      const float *pt_pm_un, uint8_t *status_out, float *pt_predict,
                      float *pt_predict_un);
+/* The same on the device: all pointers are device pointers, asynchronous on the context stream, capturable.  Results
+ * are bit-identical to pagk_post_filter on the same arrays: `sum` (:298-303) is the f64 sum of d_pix_err[i] over the
+ * status-true i in index order, one rounding per add (one wavefront walks the array as an ordered lane-to-lane chain;
+ * a status-false entry enters as +0.0, an identity of this running sum); avg = sum / cnt, NaN for cnt == 0, and the
+ * threshold then falls back to half_patch (:305-308).  Survivors' points are copied, other entries of
+ * d_pt_predict(_un) are left untouched.  d_kept (1 int32) receives what pagk_post_filter returns, d_thresholds (2
+ * doubles, or NULL) th_pix and th_dist.  d_status_out may alias d_status_pm (the mask then feeds
+ * pagk_geometry_validation_device in place): every read of the input status is over before the first write.
+ * d_pt_pm / d_pt_predict and d_pt_pm_un / d_pt_predict_un may be NULL pairwise, as in the host function. */
+int pagk_post_filter_device(pagk_ctx *ctx, int32_t n, int32_t half_patch, const uint8_t *d_status_pm,
+                            const double *d_pix_err, const double *d_dist_pred, const float *d_pt_pm,
+                            const float *d_pt_pm_un, uint8_t *d_status_out, float *d_pt_predict,
+                            float *d_pt_predict_un, int32_t *d_kept, double *d_thresholds /* 2, or NULL */);
+
+/* pagk_gyro_predict_device_rot with a live mask: a feature with d_live[i] == 0 takes the outcome of a prediction that
+ * leaves the image (status 0, points (0,0), affine untouched); with d_live all ones the same bytes as _rot.  This is
+ * what lets every launch of a frame be sized by a fixed capacity inside a graph: a dead slot reaches the tracking
+ * kernels as status_in = 0 and returns at once.  (With has_gyro_predict_initial == 0 there is no prediction: pass
+ * d_live as d_status_in.) */
+int pagk_gyro_predict_device_live(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                                  const float *d_rot, int32_t n, const float *d_pt_ref_un, const uint8_t *d_live,
+                                  float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status, float *d_affine);
+
+/* ---- frame hand-over: the results of pair (k-1, k) become the keypoints of pair (k, k+1) ---------------------- */
+/* GyroAidedTracker::SetBackToFrame (src/gyro_aided_tracker.cpp:97-111), Frame::SetPredictKeyPointsAndMask
+ * (src/frame.cpp:115-153) and the top-up rule all three detectors of the reference end in (Frame::DetectKeyPoints
+ * :156-218, Frame::LoadDetectedKeypointFromFile :222-281, ORBextractor.cc:1199-1203), on the device.  The detector
+ * stays the application's: it delivers a candidate list (undistorted points) in device memory.  In the reference's order:
+ *   survivors  for i in index order with d_status[i] != 0 (cap entries): keys[m] = pt_predict[i], keys_un[m] =
+ *              pt_predict_un[i], keys_normal[m] = ((x_un - cx) * fx_inv, (y_un - cy) * fy_inv) in f32 with fx_inv =
+ *              (float)(1.0 / fx) (src/frame.cpp:70, :128-129), index_in_last[m] = i  (a stable compaction).
+ *   mask       width x height bytes, all 1 (:89), then for every survivor a 14 x 14 block of 0 starting at
+ *              _x = min(max(0, int(x_un) - 7), width - 14), _y likewise with height (:148-151); int() truncates toward
+ *              zero.  d_mask NULL: the context owns the buffer (sized by a call outside a capture).
+ *   top-up     num_predicted = m.  Runs only if (num_predicted < new_point_threshold || !reach_flag) and n_new =
+ *              target_n - num_predicted > 0 (:164-169).  Candidates j = 0 .. *d_n_cand - 1 (clamped to [0, cand_cap])
+ *              are taken in list order; one is accepted iff mask[int(y) * width + int(x)] != 0, until n_new are accepted
+ *              (:252-266).  A candidate whose truncated coordinates fall outside the image is REJECTED: the reference
+ *              would read out of bounds there, so this is the library's definition.  Accepted candidates do not change
+ *              the mask.  Each appends keys_un = cand, keys = DistortVecPoints(cand) (src/utils.cpp:49-76; a copy when
+ *              dist_coef[0] == 0, like the tracking epilogue), keys_normal as above, index_in_last = -1.  Then
+ *              reach_flag = (total == target_n) (:214); when the top-up did not run the flag keeps its value.
+ *   outputs    d_live[i] = i < total for all cap entries; entries of the key arrays at and beyond total are zeroed
+ *              (index_in_last: -1).  d_state, PAGK_HANDOVER_STATE_WORDS int32: [0] total (the next pair's live count),
+ *              [1] reach_flag -- it persists between calls (the reference's `static bool`): zero the block once --,
+ *              [2] survivors, [3] added, [4] the candidates j < *d_n_cand that fail the acceptance test (mask 0 or
+ *              outside the image), counted over the whole list on every call; the rest reserved, written 0.
+ * target_n = Frame::mN, new_point_threshold = mThresholdOfPredictNewKeyPoint = mN * th (:79).  cap >= target_n
+ * (PAGK_E_ARG otherwise); total <= cap whenever cap >= max(target_n, previous live count).  width, height >= 14.  A call
+ * with an all-zero d_status is the reference's first-frame detection (Examples/Demo/RealSenseD435i.cpp:221-235): the
+ * first target_n in-image candidates.  The output key arrays must not alias the inputs (the caller ping-pongs two
+ * sets).  Device pointers, asynchronous, capturable; no count is read on the host: every launch is sized by cap /
+ * cand_cap.  camera model from params (fx fy cx cy dist_coef).  mvFlowVelocityInNormalPlane (:139-143) is not computed. */
+#define PAGK_HANDOVER_STATE_WORDS 8
+int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                               const float *d_pt_predict, const float *d_pt_predict_un, int32_t cand_cap,
+                               const int32_t *d_n_cand, const float *d_cand_un, float *d_keys, float *d_keys_un,
+                               float *d_keys_normal /* or NULL */, int32_t *d_index_in_last, uint8_t *d_live,
+                               uint8_t *d_mask /* width * height, or NULL */, int32_t *d_state);
+/* The same with host buffers, synchronous (C hosts, tests).  state is read (reach_flag) and written; keys_normal and
+ * mask may be NULL. */
+int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                        int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
+                        const float *pt_predict_un, int32_t cand_cap, const int32_t *n_cand, const float *cand_un,
+                        float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live,
+                        uint8_t *mask, int32_t *state);
 
 /* Diagnostics (never on the tracking path): the arithmetic of H.llt().solve(b) / update.norm()
  * (src/patch_match.cpp:319,343) on the caller's operands, so that a host can check on its own device -- and, with
@@ -320,7 +387,8 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
 /* hipGraph capture of the per-frame work (BASELINE configs[4], "hipGraph-captured iterate").  A camera
  * stream issues the same launches on the same device pointers every frame; between pagk_graph_begin and
  * pagk_graph_end the *_device entry points (pagk_frame_set_device, pagk_gyro_predict_device[_rot],
- * pagk_track_device, pagk_geometry_scores_device, pagk_geometry_fit_device, pagk_geometry_validation_device) are recorded on the context stream instead of executed,
+ * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
+ * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while
  * capturing; the context stream must not be the legacy default stream; the kernel timers

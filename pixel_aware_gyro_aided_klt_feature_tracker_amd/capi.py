@@ -193,6 +193,15 @@ def declare(lib) -> None:
     lib.pagk_gyro_predict_device_rot.argtypes = [vp, _P(Params), i32, i32, vp, i32, vp, vp, vp, vp, vp]
     lib.pagk_post_filter.restype = C.c_int
     lib.pagk_post_filter.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "pagk_frame_handover_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_post_filter_device.restype = C.c_int
+        lib.pagk_post_filter_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_gyro_predict_device_live.restype = C.c_int
+        lib.pagk_gyro_predict_device_live.argtypes = [vp, _P(Params), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+        for name in ("pagk_frame_handover_device", "pagk_frame_handover"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -293,7 +302,11 @@ EXPORTED_SYMBOLS = [
     "pagk_multi_comm_count", "pagk_has_variant",
     "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
     "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
+    "pagk_post_filter_device", "pagk_gyro_predict_device_live", "pagk_frame_handover_device", "pagk_frame_handover",
 ]
+
+HANDOVER_STATE_WORDS = 8
+HANDOVER_STATE_FIELDS = ("total", "reach_flag", "survivors", "added", "rejected")
 
 
 def fit_params_default(**overrides) -> FitParams:
@@ -656,6 +669,70 @@ class Context:
                                                           _ptr(d_pt_ref), _ptr(d_pt_predict_un), _ptr(d_pt_predict),
                                                           _ptr(d_status), _ptr(d_affine)),
                     "pagk_gyro_predict_device_rot")
+
+    def gyro_predict_device_live(self, params: Params, width: int, height: int, d_rot, n: int, d_pt_ref, d_live,
+                                 d_pt_predict_un, d_pt_predict, d_status, d_affine):
+        """pagk_gyro_predict_device_rot with a live mask: dead slots (d_live[i] == 0) come out as status 0, points (0,0)."""
+        if d_rot is None or (n > 0 and d_live is None):
+            raise ValueError("d_rot and d_live are required")
+        self._check(self.lib.pagk_gyro_predict_device_live(self.h, C.byref(params), width, height, _ptr(d_rot), n,
+                                                           _ptr(d_pt_ref), _ptr(d_live), _ptr(d_pt_predict_un),
+                                                           _ptr(d_pt_predict), _ptr(d_status), _ptr(d_affine)),
+                    "pagk_gyro_predict_device_live")
+
+    # Step 3 and the frame hand-over on the device (include/pagk.h) -----------------------------
+    def post_filter_device(self, n: int, half_patch: int, d_status_pm, d_pix_err, d_dist_pred, d_pt_pm, d_pt_pm_un,
+                           d_status_out, d_pt_predict, d_pt_predict_un, d_kept, d_thresholds=None):
+        """pagk_post_filter_device on device arrays (asynchronous, capturable); d_status_out may be d_status_pm."""
+        if d_kept is None:
+            raise ValueError("d_kept is required")
+        self._check(self.lib.pagk_post_filter_device(self.h, n, half_patch, _ptr(d_status_pm), _ptr(d_pix_err),
+                                                     _ptr(d_dist_pred), _ptr(d_pt_pm), _ptr(d_pt_pm_un),
+                                                     _ptr(d_status_out), _ptr(d_pt_predict), _ptr(d_pt_predict_un),
+                                                     _ptr(d_kept), _ptr(d_thresholds)), "pagk_post_filter_device")
+
+    def frame_handover_device(self, params: Params, width: int, height: int, cap: int, target_n: int,
+                              new_point_threshold: float, d_status, d_pt_predict, d_pt_predict_un, cand_cap: int,
+                              d_n_cand, d_cand_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
+                              d_state):
+        """pagk_frame_handover_device on device arrays (asynchronous, capturable)."""
+        if cap < target_n:
+            raise ValueError("cap must be at least target_n")
+        self._check(self.lib.pagk_frame_handover_device(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
+            _ptr(d_pt_predict), _ptr(d_pt_predict_un), cand_cap, _ptr(d_n_cand), _ptr(d_cand_un), _ptr(d_keys),
+            _ptr(d_keys_un), _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state)),
+            "pagk_frame_handover_device")
+
+    def frame_handover(self, params: Params, width: int, height: int, cap: int, target_n: int,
+                       new_point_threshold: float, status, pt_predict, pt_predict_un, candidates, state=None,
+                       cand_cap: int | None = None) -> dict:
+        """pagk_frame_handover, host buffers -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state).
+        `state` (8 int32, reach_flag in [1]) is copied, not updated in place; status / points are padded to cap."""
+        def pad(a, dtype, width_):
+            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
+            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
+            if a.shape[0] > cap:
+                raise ValueError("more entries than cap")
+            out[:a.shape[0]] = a
+            return out
+        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
+        cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 2)
+        cc = cand.shape[0] if cand_cap is None else int(cand_cap)
+        if cc < cand.shape[0]:
+            raise ValueError("cand_cap is smaller than the candidate list")
+        cbuf = np.zeros((max(cc, 1), 2), np.float32)
+        cbuf[:cand.shape[0]] = cand
+        ncand = np.array([cand.shape[0]], np.int32)
+        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
+                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
+                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state)
+        self._check(self.lib.pagk_frame_handover(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
+            _ptr(ppu), cc, _ptr(ncand), _ptr(cbuf), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
+            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state)), "pagk_frame_handover")
+        return out
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------
     def graph_begin(self):

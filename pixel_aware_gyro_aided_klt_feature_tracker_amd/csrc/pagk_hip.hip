@@ -50,6 +50,8 @@ struct pagk_ctx {
     FeatBuf fit;    // workspace of the device RANSAC fits (pagk_fit_kernel.h): sized outside captures, pointed into by graphs
     int fit_n = 0, fit_iters = 0;  // what `fit` holds room for
     FeatBuf fitio;  // scratch of the host-buffer fit / validation entry points
+    FeatBuf hand;   // the frame hand-over's own mask (pagk_handover_kernel.h): sized outside captures, pointed into by graphs
+    FeatBuf handio; // scratch of the host-buffer hand-over
     void *quad_ws = nullptr;  // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
     size_t quad_ws_bytes = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
@@ -1208,6 +1210,8 @@ void pagk_destroy(pagk_ctx *ctx)
     if (ctx->score.block) (void)hipFree(ctx->score.block);
     if (ctx->fit.block) (void)hipFree(ctx->fit.block);
     if (ctx->fitio.block) (void)hipFree(ctx->fitio.block);
+    if (ctx->hand.block) (void)hipFree(ctx->hand.block);
+    if (ctx->handio.block) (void)hipFree(ctx->handio.block);
     if (ctx->quad_ws) (void)hipFree(ctx->quad_ws);
     if (ctx->susp) (void)hipFree(ctx->susp);
     if (ctx->queue) (void)hipFree(ctx->queue);
@@ -1799,7 +1803,7 @@ int pagk_track_pyr(pagk_ctx *ctx, const pagk_params *params, int32_t n_levels, c
 static int gyro_predict_any(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
                             const float *KRKinv, const float *r3, const float *d_rot, int32_t n,
                             const float *d_pt_ref_un, float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status,
-                            float *d_affine)
+                            float *d_affine, const uint8_t *d_live = nullptr)
 {
     if (!ctx || !params || (!d_rot && (!KRKinv || !r3)) || n < 0 || width < 1 || height < 1) return PAGK_E_ARG;
     if (params->half_patch < 1 || params->half_patch > PAGK_MAX_HALF_PATCH) return PAGK_E_ARG;
@@ -1832,6 +1836,7 @@ static int gyro_predict_any(pagk_ctx *ctx, const pagk_params *params, int32_t wi
     a.pt_dist = d_pt_predict;
     a.status = d_status;
     a.affine = d_affine;
+    a.live = d_live;
     if (n > 0) {
         hipLaunchKernelGGL(k_gyro_predict, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
         HIPCHK(ctx, hipGetLastError());
@@ -1854,6 +1859,15 @@ int pagk_gyro_predict_device_rot(pagk_ctx *ctx, const pagk_params *params, int32
     if (!d_rot) return PAGK_E_ARG;
     return gyro_predict_any(ctx, params, width, height, nullptr, nullptr, d_rot, n, d_pt_ref_un, d_pt_predict_un,
                             d_pt_predict, d_status, d_affine);
+}
+
+int pagk_gyro_predict_device_live(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                                  const float *d_rot, int32_t n, const float *d_pt_ref_un, const uint8_t *d_live,
+                                  float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status, float *d_affine)
+{
+    if (!d_rot || (n > 0 && !d_live)) return PAGK_E_ARG;
+    return gyro_predict_any(ctx, params, width, height, nullptr, nullptr, d_rot, n, d_pt_ref_un, d_pt_predict_un,
+                            d_pt_predict, d_status, d_affine, d_live);
 }
 
 // GyroAidedTracker::GyroPredictFeaturesAndOpticalFlowRefined, Step 3,
@@ -1889,6 +1903,148 @@ int pagk_post_filter(int32_t n, int32_t half_patch, const uint8_t *status_pm, co
         kept++;
     }
     return kept;
+}
+
+
+// Step 3 on the device (k_post_filter): the same mask, points, count and thresholds as pagk_post_filter, bit for bit.
+int pagk_post_filter_device(pagk_ctx *ctx, int32_t n, int32_t half_patch, const uint8_t *d_status_pm,
+                            const double *d_pix_err, const double *d_dist_pred, const float *d_pt_pm,
+                            const float *d_pt_pm_un, uint8_t *d_status_out, float *d_pt_predict,
+                            float *d_pt_predict_un, int32_t *d_kept, double *d_thresholds)
+{
+    if (!ctx || n < 0 || !d_kept) return PAGK_E_ARG;
+    if (n > 0 && (!d_status_pm || !d_pix_err || !d_dist_pred || !d_status_out)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_post_filter, dim3(1), dim3(1024), 0, ctx->stream, n, half_patch, d_status_pm, d_pix_err,
+                       d_dist_pred, d_pt_pm, d_pt_pm_un, d_status_out, d_pt_predict, d_pt_predict_un, d_kept, d_thresholds);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// ---- frame hand-over (pagk_handover_kernel.h) ------------------------------------------------------------------
+namespace {
+
+bool handover_args_ok(const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                      double new_point_threshold, int32_t cand_cap)
+{
+    // 14 = the mask's hole (src/frame.cpp:117-119): a smaller image has no place for one
+    return params && width >= 14 && height >= 14 && (int64_t)width * height <= 0x7fffffff && cap >= 1 && target_n >= 0 &&
+           cap >= target_n && cand_cap >= 0 && !std::isnan(new_point_threshold);
+}
+
+// the context's own mask; grows only outside a capture and while no graph of this context is alive
+int handover_mask(pagk_ctx *ctx, size_t bytes, uint8_t **mask)
+{
+    bytes = align_up(bytes, 256);
+    if (bytes > ctx->hand.bytes) {
+        if (in_capture(ctx)) {
+            snprintf(ctx->err, sizeof(ctx->err), "the hand-over's mask would have to grow inside a capture: run the call once "
+                     "with this image size before capturing, or pass d_mask");
+            return PAGK_E_ARG;
+        }
+        int rc = no_live_graphs(ctx, "the hand-over's mask");
+        if (rc) return rc;
+        if (ctx->hand.block) HIPCHK(ctx, hipFree(ctx->hand.block));
+        ctx->hand.block = nullptr;
+        ctx->hand.bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->hand.block, bytes));
+        ctx->hand.bytes = bytes;
+    }
+    *mask = static_cast<uint8_t *>(ctx->hand.block);
+    return PAGK_OK;
+}
+
+}  // namespace
+
+int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                               const float *d_pt_predict, const float *d_pt_predict_un, int32_t cand_cap,
+                               const int32_t *d_n_cand, const float *d_cand_un, float *d_keys, float *d_keys_un,
+                               float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                               int32_t *d_state)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, cand_cap)) return PAGK_E_ARG;
+    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_n_cand || (cand_cap > 0 && !d_cand_un) || !d_keys ||
+        !d_keys_un || !d_index_in_last || !d_live || !d_state)
+        return PAGK_E_ARG;
+    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int64_t bytes = (int64_t)width * height;
+    uint8_t *mask = d_mask;
+    if (!mask) {
+        int rc = handover_mask(ctx, (size_t)bytes, &mask);
+        if (rc) return rc;
+    }
+    HandoverArgs a;
+    memset(&a, 0, sizeof a);
+    a.cap = cap, a.cand_cap = cand_cap, a.width = width, a.height = height, a.target_n = target_n;
+    a.new_point_threshold = new_point_threshold;
+    a.fx = params->fx, a.fy = params->fy, a.cx = params->cx, a.cy = params->cy;
+    a.fx_inv = (float)(1.0 / (double)params->fx);  // src/frame.cpp:70
+    a.fy_inv = (float)(1.0 / (double)params->fy);
+    a.k1 = params->dist_coef[0], a.k2 = params->dist_coef[1], a.p1 = params->dist_coef[2], a.p2 = params->dist_coef[3];
+    a.k3 = params->n_dist_coef == 5 ? params->dist_coef[4] : 0.0f;
+    a.distort_on = params->dist_coef[0] != 0.0f;
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.n_cand = d_n_cand, a.cand_un = d_cand_un;
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
+    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
+                       width, height, d_status, d_pt_predict_un, mask);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                        int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
+                        const float *pt_predict_un, int32_t cand_cap, const int32_t *n_cand, const float *cand_un,
+                        float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live,
+                        uint8_t *mask, int32_t *state)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, cand_cap)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover");
+    if (!status || !pt_predict || !pt_predict_un || !n_cand || (cand_cap > 0 && !cand_un) || !keys || !keys_un ||
+        !index_in_last || !live || !state)
+        return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)cap, cc = (size_t)(cand_cap > 0 ? cand_cap : 1), px = (size_t)width * height;
+    // status | pt_predict | pt_predict_un | n_cand | cand | keys | keys_un | keys_normal | index | live | state | mask
+    const size_t sizes[12] = {nc, nc * 8, nc * 8, 4, cc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4, px};
+    size_t off[12], total = 0;
+    for (int k = 0; k < 12; k++) {
+        off[k] = total;
+        total += align_up(sizes[k], 256);
+    }
+    if (total > ctx->handio.bytes) {
+        if (ctx->handio.block) HIPCHK(ctx, hipFree(ctx->handio.block));
+        ctx->handio.block = nullptr;
+        ctx->handio.bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->handio.block, total));
+        ctx->handio.bytes = total;
+    }
+    uint8_t *b = static_cast<uint8_t *>(ctx->handio.block);
+    const void *src[5] = {status, pt_predict, pt_predict_un, n_cand, cand_un};
+    for (int k = 0; k < 5; k++)
+        if (src[k] && (k != 4 || cand_cap > 0))
+            HIPCHK(ctx, hipMemcpyAsync(b + off[k], src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b + off[10], state, sizes[10], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
+    int rc = pagk_frame_handover_device(
+        ctx, params, width, height, cap, target_n, new_point_threshold, b + off[0], reinterpret_cast<float *>(b + off[1]),
+        reinterpret_cast<float *>(b + off[2]), cand_cap, reinterpret_cast<int32_t *>(b + off[3]),
+        reinterpret_cast<float *>(b + off[4]), reinterpret_cast<float *>(b + off[5]), reinterpret_cast<float *>(b + off[6]),
+        keys_normal ? reinterpret_cast<float *>(b + off[7]) : nullptr, reinterpret_cast<int32_t *>(b + off[8]), b + off[9],
+        b + off[11], reinterpret_cast<int32_t *>(b + off[10]));
+    if (rc) return rc;
+    void *dst[7] = {keys, keys_un, keys_normal, index_in_last, live, state, mask};
+    const int from[7] = {5, 6, 7, 8, 9, 10, 11};
+    for (int k = 0; k < 7; k++)
+        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], b + off[from[k]], sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
 }
 
 

@@ -197,6 +197,8 @@ struct PredictArgs {
     // when non-null: 9 floats on the device, rows 0 and 1 of mKRKinv then the third row of mRcl; they replace
     // K[] and r31..r33 above (the rotation of a captured graph must not be baked into its kernel arguments)
     const float *d_rot;
+    // when non-null: n flags; a feature with live[i] == 0 takes the outcome of a prediction that leaves the image
+    const uint8_t *live;
 };
 
 // GyroPredictOnePixel (:194-256): PIXEL_AWARE_PREDICTION (:212-231) or SINGLE_HOMOGRAPHY (:233-253, lambda = 1.0)
@@ -233,6 +235,7 @@ __global__ void __launch_bounds__(256) k_gyro_predict(PredictArgs a)
     a.status[i] = 0;
     a.pt_un[2 * i] = a.pt_un[2 * i + 1] = 0.0f;
     a.pt_dist[2 * i] = a.pt_dist[2 * i + 1] = 0.0f;
+    if (a.live && !a.live[i]) return;  // a dead slot of a fixed-capacity frame loop (pagk_gyro_predict_device_live)
     const float rx = a.pt_ref[2 * i], ry = a.pt_ref[2 * i + 1];
     float ux, uy, dxs, dys;
     predict_one(a, rx, ry, ux, uy, dxs, dys);
@@ -1271,5 +1274,6 @@ __global__ void __launch_bounds__(256, 4) k_track_block_pyr(TrackArgs a, PyrArgs
 #endif
 #include "pagk_score_kernel.h"
 #include "pagk_fit_kernel.h"
+#include "pagk_handover_kernel.h"
 #include "pagk_neighbor_kernel.h"
 #include "pagk_selftest_kernel.h"

@@ -166,3 +166,58 @@ def imu_windows(imu_path: str, frame_times):
     if n < 0:
         raise FileNotFoundError(imu_path)
     return first[:len(ft)], counts[:len(ft)]
+
+
+# ---- Step 3 and the frame hand-over on the device (include/pagk.h), for hosts that hold numpy arrays ----
+def _device_context(ctx):
+    """A caller's capi.Context, or one this module keeps for its own calls."""
+    global _ctx
+    if ctx is not None:
+        return ctx
+    if _ctx is None:
+        _ctx = capi.Context(0)
+    return _ctx
+
+
+_ctx = None
+
+
+def post_filter_device(half_patch: int, status_pm, pix_err, dist_pred, pt_pm, pt_pm_un, ctx=None):
+    """pagk_post_filter_device on host arrays (copied up, filtered on the device, copied back) ->
+    (kept, status, pt_predict, pt_predict_un, (th_pix, th_dist)); bit-identical to capi.post_filter."""
+    import torch
+    c = _device_context(ctx)
+    st = np.ascontiguousarray(status_pm, np.uint8)
+    n = int(st.shape[0])
+    arrays = (st, np.ascontiguousarray(pix_err, np.float64), np.ascontiguousarray(dist_pred, np.float64),
+              np.ascontiguousarray(pt_pm, np.float32).reshape(-1, 2), np.ascontiguousarray(pt_pm_un, np.float32).reshape(-1, 2))
+    if any(a.shape[0] != n for a in arrays):
+        raise ValueError("the five input arrays differ in length")
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(a if n else np.zeros((1,) + a.shape[1:], a.dtype)).to(dev) for a in arrays]
+    d_out = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+    d_pp, d_ppu = torch.zeros((max(n, 1), 2), device=dev), torch.zeros((max(n, 1), 2), device=dev)
+    d_kept, d_th = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    c.post_filter_device(n, half_patch, d[0], d[1], d[2], d[3], d[4], d_out, d_pp, d_ppu, d_kept, d_th)
+    c.sync()
+    th = d_th.cpu().numpy()
+    return int(d_kept.cpu()[0]), d_out.cpu().numpy()[:n], d_pp.cpu().numpy()[:n], d_ppu.cpu().numpy()[:n], (th[0], th[1])
+
+
+def frame_handover(params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un,
+                   candidates, state=None, ctx=None) -> dict:
+    """pagk_frame_handover (host buffers): the survivors of a pair and the accepted candidates as the next pair's
+    keypoints -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state)."""
+    return _device_context(ctx).frame_handover(params, width, height, cap, target_n, new_point_threshold, status,
+                                               pt_predict, pt_predict_un, candidates, state=state)
+
+
+def frame_handover_device(ctx, *args):
+    """pagk_frame_handover_device on device arrays: capi.Context.frame_handover_device."""
+    return ctx.frame_handover_device(*args)
+
+
+def gyro_predict_device_live(ctx, *args):
+    """pagk_gyro_predict_device_live on device arrays: capi.Context.gyro_predict_device_live."""
+    return ctx.gyro_predict_device_live(*args)

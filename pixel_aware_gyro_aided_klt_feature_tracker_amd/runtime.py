@@ -469,3 +469,206 @@ class CameraBatch:
         self.stream.synchronize()
         for c in self.cams:
             c.ctx.check_launch()
+
+
+def _carve(buf: torch.Tensor, fields):
+    """Typed views into one byte buffer: fields = [(name, dtype, rows, cols)], every block 256-byte aligned."""
+    out, off = {}, 0
+    for name, dt, rows, cols in fields:
+        nbytes = torch.empty(0, dtype=dt).element_size() * rows * cols
+        v = buf[off:off + nbytes].view(dt)
+        out[name] = v.view(rows, cols) if cols > 1 else v
+        off += (nbytes + 255) // 256 * 256
+    return out
+
+
+def _carve_size(fields) -> int:
+    return sum((torch.empty(0, dtype=dt).element_size() * rows * cols + 255) // 256 * 256 for _, dt, rows, cols in fields)
+
+
+class FrameResult:
+    """What one SequenceTracker step leaves behind: the keypoints of the next pair (keys, keys_un, keys_normal,
+    index_in_last, live: `cap` entries each) and the hand-over's state words, as device tensors, with the event that was
+    recorded behind the work that produces them.  to_numpy() waits for that event (and for nothing issued later)."""
+
+    FIELDS = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state")
+
+    def __init__(self, tensors: dict, event, side, snapshot: bool):
+        self.tensors, self.event, self._side, self.snapshot = tensors, event, side, snapshot
+
+    def to_numpy(self) -> dict:
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(self.event)
+            host = {k: self.tensors[k].to("cpu", non_blocking=False) for k in self.FIELDS}
+        out = {k: v.numpy() for k, v in host.items()}
+        out.update(zip(capi.HANDOVER_STATE_FIELDS, (int(v) for v in out["state"][:5])))
+        return out
+
+
+class SequenceTracker:
+    """A tracker's per-frame loop with everything between two frame pairs on the device (reference
+    Examples/Demo/RealSenseD435i.cpp:199-321): step() enqueues
+        [frame -> pyramid -> pagk_gyro_predict_device_live -> pagk_track_device -> pagk_post_filter_device ->
+         pagk_geometry_validation_device -> pagk_frame_handover_device]
+    on one stream, with no host synchronisation and no device-to-host copy.  Every launch is sized by the fixed
+    capacity `cap`; the live count stays in device memory (dead slots are status_in = 0 for the tracking kernels).
+    What changes from frame to frame -- the image, the nine rotation floats, the candidate list and its length -- goes
+    through ONE pinned block and one host-to-device copy into a fixed device block in front of the frame's work.
+    The even and the odd frame (they differ in their frame slots and key-array sets) are captured as two graphs after
+    one direct run of each; mode="direct" issues the same calls without a graph.
+
+    target_n = Frame::mN, new_point_ratio = th of mThresholdOfPredictNewKeyPoint = mN * th (src/frame.cpp:79).
+    fit_params None leaves the geometry validation out."""
+
+    RING = 4   # pinned input blocks: one is rewritten only after the copy that read it, four frames earlier, has run
+
+    def __init__(self, params: capi.Params, width: int, height: int, cap: int, target_n: int, new_point_ratio: float,
+                 fit_params: "capi.FitParams | None" = None, *, device: int = 0, cand_cap: int = 1024, sigma: float = 1.0):
+        if not torch.cuda.is_available():
+            raise RuntimeError("SequenceTracker needs a HIP device (torch.cuda.is_available() is False)")
+        if cap < target_n or target_n < 1 or cand_cap < 1:
+            raise ValueError("cap >= target_n >= 1 and cand_cap >= 1 are required")
+        self.params, self.fit_params, self.sigma = params, fit_params, float(sigma)
+        self.w, self.h, self.cap, self.target_n, self.cand_cap = int(width), int(height), int(cap), int(target_n), int(cand_cap)
+        self.threshold = float(target_n * new_point_ratio)
+        self.dev = torch.device("cuda", device)
+        torch.cuda.set_device(self.dev)
+        self.ctx = capi.Context(device)
+        self.main = torch.cuda.Stream(device=self.dev)   # never the legacy default stream (it cannot be captured)
+        self.side = torch.cuda.Stream(device=self.dev)   # readers of a FrameResult
+        self.ctx.set_stream(self.main.cuda_stream)
+        u8, f32, f64, i32 = torch.uint8, torch.float32, torch.float64, torch.int32
+        n = self.cap
+        self._in_fields = [("img", u8, self.h, self.w), ("rot", f32, 9, 1), ("n_cand", i32, 1, 1), ("cand", f32, self.cand_cap, 2)]
+        nbytes = _carve_size(self._in_fields)
+        self._d_in_buf = torch.zeros(nbytes, dtype=u8, device=self.dev)
+        self.d_in = _carve(self._d_in_buf, self._in_fields)
+        self._pinned = [torch.zeros(nbytes, dtype=u8).pin_memory() for _ in range(self.RING)]
+        self._pinned_views = [_carve(b, self._in_fields) for b in self._pinned]
+        self._pinned_free = [None] * self.RING
+        set_fields = [("keys", f32, n, 2), ("keys_un", f32, n, 2), ("keys_normal", f32, n, 2), ("index_in_last", i32, n, 1),
+                      ("live", u8, n, 1)]
+        self._set_bufs = [torch.zeros(_carve_size(set_fields), dtype=u8, device=self.dev) for _ in range(2)]
+        self._set_fields = set_fields
+        self.sets = [_carve(b, set_fields) for b in self._set_bufs]
+        work = [("pu", f32, n, 2), ("pd", f32, n, 2), ("st_in", u8, n, 1), ("aff", f32, n, 4), ("pt_un", f32, n, 2),
+                ("pt_dist", f32, n, 2), ("status", u8, n, 1), ("pix_err", f64, n, 1), ("dist_pred", f64, n, 1),
+                ("st", u8, n, 1), ("pp", f32, n, 2), ("ppu", f32, n, 2), ("kept", i32, 1, 1), ("th", f64, 2, 1),
+                ("cnt", i32, 1, 1), ("score", f32, 1, 1), ("zero", u8, n, 1)]
+        self._work_buf = torch.zeros(_carve_size(work), dtype=u8, device=self.dev)
+        self.wk = _carve(self._work_buf, work)
+        self.wk["aff"].copy_(torch.tensor([1.0, 0.0, 0.0, 1.0], device=self.dev).repeat(n, 1))
+        self.out = {k: self.wk[k] for k in ("pt_un", "pt_dist", "status", "pix_err", "dist_pred")}
+        self.state = torch.zeros(capi.HANDOVER_STATE_WORDS, dtype=i32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        self.frame = -1          # index of the last frame handed in
+        self._turn = 0
+        self._graphs = {}        # parity -> graph id
+        self._direct_done = set()
+        self.mode_used = None
+
+    def close(self):
+        for gid in self._graphs.values():
+            self.ctx.graph_destroy(gid)
+        self._graphs = {}
+        self.ctx.close()
+
+    # -- inputs ------------------------------------------------------------------------------------------------
+    def _feed(self, img, rot9, candidates):
+        """This frame's inputs into the next pinned block, then one asynchronous copy into the fixed device block."""
+        k = self._turn
+        self._turn = (k + 1) % self.RING
+        if self._pinned_free[k] is not None:
+            self._pinned_free[k].synchronize()   # the copy issued RING frames ago has read this block (flow control only)
+        pv = self._pinned_views[k]
+        img = np.asarray(img)
+        if img.shape != (self.h, self.w) or img.dtype != np.uint8:
+            raise ValueError("frame must be a uint8 array of the tracker's size")
+        pv["img"].numpy()[...] = img
+        if rot9 is not None:
+            pv["rot"].numpy()[...] = np.asarray(rot9, np.float32).reshape(9)
+        cand = np.asarray(candidates, np.float32).reshape(-1, 2) if candidates is not None else np.zeros((0, 2), np.float32)
+        if cand.shape[0] > self.cand_cap:
+            raise ValueError("more candidates than cand_cap")
+        pv["cand"].numpy()[:cand.shape[0]] = cand
+        pv["n_cand"].numpy()[0] = cand.shape[0]
+        self._d_in_buf.copy_(self._pinned[k], non_blocking=True)
+        self._pinned_free[k] = _event_on(self.main)
+
+    # -- the frame's launches ----------------------------------------------------------------------------------
+    def _handover(self, status, pp, ppu, dst):
+        self.ctx.frame_handover_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold, status, pp, ppu,
+                                       self.cand_cap, self.d_in["n_cand"], self.d_in["cand"], dst["keys"], dst["keys_un"],
+                                       dst["keys_normal"], dst["index_in_last"], dst["live"], None, self.state)
+
+    def _issue(self, p: int):
+        """The work of a frame of parity p: frame slot p is the current frame, slot 1 - p the reference; key set 1 - p
+        holds the reference keypoints, set p receives the next pair's."""
+        c, pr, wk = self.ctx, self.params, self.wk
+        ref, dst = self.sets[1 - p], self.sets[p]
+        c.frame_set_device(p, self.d_in["img"].data_ptr(), self.w, self.h, self.w, pr.pyramids)
+        if pr.has_gyro_predict_initial:
+            c.gyro_predict_device_live(pr, self.w, self.h, self.d_in["rot"], self.cap, ref["keys_un"], ref["live"],
+                                       wk["pu"], wk["pd"], wk["st_in"], wk["aff"])
+            c.track_device(pr, 1 - p, p, self.cap, ref["keys_un"], wk["pu"], wk["aff"], wk["st_in"], self.out)
+        else:   # no prediction: the live mask is the tracking kernels' status_in
+            c.track_device(pr, 1 - p, p, self.cap, ref["keys_un"], ref["keys_un"], wk["aff"], ref["live"], self.out)
+        c.post_filter_device(self.cap, pr.half_patch, wk["status"], wk["pix_err"], wk["dist_pred"], wk["pt_dist"],
+                             wk["pt_un"], wk["st"], wk["pp"], wk["ppu"], wk["kept"], wk["th"])
+        if self.fit_params is not None:
+            c.geometry_validation_device(self.fit_params, self.cap, ref["keys_un"], wk["ppu"], wk["st"], self.sigma,
+                                         wk["cnt"], wk["score"])
+        self._handover(wk["st"], wk["pp"], wk["ppu"], dst)
+
+    def _result(self, p: int, snapshot: bool) -> FrameResult:
+        if snapshot:   # two device-to-device copies: the set's block and the state words
+            t = _carve(self._set_bufs[p].clone(), self._set_fields)
+            t["state"] = self.state.clone()
+        else:          # views: valid until the frame after next rewrites this set
+            t = dict(self.sets[p])
+            t["state"] = self.state
+        return FrameResult(t, _event_on(self.main), self.side, snapshot)
+
+    def start(self, img, candidates, snapshot: bool = True) -> FrameResult:
+        """The first frame (Examples/Demo/RealSenseD435i.cpp:221-235): its pyramid into slot 0, and the first-frame
+        hand-over -- an all-zero status -- takes the first target_n in-image candidates into key set 0."""
+        with torch.cuda.stream(self.main):
+            self.state.zero_()
+            self._feed(img, None, candidates)
+            self.ctx.frame_set_device(0, self.d_in["img"].data_ptr(), self.w, self.h, self.w, self.params.pyramids)
+            self._handover(self.wk["zero"], self.wk["pp"], self.wk["ppu"], self.sets[0])
+            self.frame = 0
+            self.mode_used = "direct"
+            return self._result(0, snapshot)
+
+    def step(self, img, rot9, candidates, mode: str = "graph", snapshot: bool = True) -> FrameResult:
+        """Frame k >= 1: tracks pair (k-1, k) and hands over to pair (k, k+1).  rot9 = rows 0 and 1 of K R K^-1 followed
+        by the third row of R (pagk_gyro_predict_device_rot).  Nothing is synchronised; the result carries its event."""
+        if self.frame < 0:
+            raise RuntimeError("start() hands in the first frame")
+        if mode not in ("graph", "direct"):
+            raise ValueError(mode)
+        k = self.frame + 1
+        p = k & 1
+        with torch.cuda.stream(self.main):
+            self._feed(img, rot9, candidates)
+            if mode == "graph" and p in self._direct_done:
+                if p not in self._graphs:
+                    self.ctx.graph_begin()
+                    try:
+                        self._issue(p)
+                    finally:
+                        self._graphs[p] = self.ctx.graph_end()
+                self.ctx.graph_launch(self._graphs[p])
+                self.mode_used = "graph"
+            else:   # also the first frame of each parity in graph mode: allocations happen outside a capture
+                self._issue(p)
+                self._direct_done.add(p)
+                self.mode_used = "direct"
+            self.frame = k
+            return self._result(p, snapshot)
+
+    def synchronize(self):
+        self.main.synchronize()
+        self.side.synchronize()
+        self.ctx.check_launch()
