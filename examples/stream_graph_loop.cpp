@@ -10,6 +10,11 @@
 // so the program prints the lines of stream_resident: dead slots and the stable compaction leave every live feature and
 // the ordered Step-3 sum as they are there.  Counts and points are read back only to print them.
 //
+// --detect closes the loop: the hand-over is pagk_frame_handover_detect_device, so the keypoints of the first frame and
+// every later top-up are the reference's goodFeaturesToTrack corners (src/frame.cpp:181-184), detected on the device on
+// the current frame under the mask the hand-over has just built.  The file's keypoints then only give the count
+// (target_n); no candidate list goes to the device at all, and each line also tells how many corners were added.
+//
 // Input: the file of stream_resident.cpp.
 // Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I /opt/rocm/include -I include examples/stream_graph_loop.cpp
 //        -L <pkg> -l:libpagk_hip.so -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,<pkg> -Wl,-rpath,/opt/rocm/lib
@@ -18,6 +23,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "pagk.h"
@@ -47,8 +53,15 @@ struct KeySet {
 
 int main(int argc, char **argv)
 {
+    bool detect = false;
+    for (int k = 1; k < argc; k++)
+        if (!std::strcmp(argv[k], "--detect")) {
+            detect = true;
+            for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--, k--;
+        }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s sequence.bin [half_patch iterations pyramids]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--detect] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
         return 2;
     }
     const int half = argc > 2 ? std::atoi(argv[2]) : 5, iters = argc > 3 ? std::atoi(argv[3]) : 10,
@@ -104,7 +117,7 @@ int main(int argc, char **argv)
     float *d_rot, *d_cand, *d_pu, *d_pd, *d_aff, *d_ptun, *d_ptdist, *d_pp, *d_ppu;
     uint8_t *d_st_in, *d_st_pm, *d_st;
     double *d_err, *d_dist;
-    int32_t *d_ncand, *d_kept, *d_state;
+    int32_t *d_ncand, *d_kept, *d_state, *d_info;
     CHECK_HIP(hipMalloc((void **)&d_frame, (size_t)w * h));
     CHECK_HIP(hipMalloc((void **)&d_rot, 9 * 4));
     CHECK_HIP(hipMalloc((void **)&d_cand, n8));
@@ -123,11 +136,16 @@ int main(int argc, char **argv)
     CHECK_HIP(hipMalloc((void **)&d_ncand, 4));
     CHECK_HIP(hipMalloc((void **)&d_kept, 4));
     CHECK_HIP(hipMalloc((void **)&d_state, PAGK_HANDOVER_STATE_WORDS * 4));
+    CHECK_HIP(hipMalloc((void **)&d_info, PAGK_DETECT_INFO_WORDS * 4));
     CHECK_HIP(hipMemset(d_st, 0, (size_t)cap));
     CHECK_HIP(hipMemset(d_pp, 0, n8));
     CHECK_HIP(hipMemset(d_ppu, 0, n8));
     CHECK_HIP(hipMemset(d_state, 0, PAGK_HANDOVER_STATE_WORDS * 4));  // reach_flag starts down
     pagk_outputs d_out{d_ptun, d_ptdist, d_st_pm, d_err, d_dist, nullptr, nullptr};
+    // --detect: Frame::DetectKeyPoints' arguments (src/frame.cpp:181-184) and mThresholdOfPredictNewKeyPoint = 0.8 mN
+    pagk_detect_params det;
+    pagk_detect_params_default(&det);
+    const double new_point_threshold = detect ? 0.8 * nk : 0.0;
 
     // first frame (Examples/Demo/RealSenseD435i.cpp:221-235): its pyramid, and the hand-over with an all-zero status
     // takes the file's keypoints, in order, into key set 0
@@ -136,9 +154,14 @@ int main(int argc, char **argv)
     CHECK_HIP(hipMemcpy(d_ncand, &n_cand, 4, hipMemcpyHostToDevice));
     CHECK_HIP(hipMemcpy(d_frame, img[0].data(), (size_t)w * h, hipMemcpyHostToDevice));
     CHECK_PAGK(pagk_frame_set_device(ctx, 0, d_frame, w, h, w, pyr));
-    CHECK_PAGK(pagk_frame_handover_device(ctx, &p, w, h, cap, nk, 0.0, d_st, d_pp, d_ppu, cap, d_ncand, d_cand, ks[0].keys,
-                                          ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last, ks[0].live, nullptr,
-                                          d_state));
+    if (detect)
+        CHECK_PAGK(pagk_frame_handover_detect_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &det, 0,
+                                                     ks[0].keys, ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last,
+                                                     ks[0].live, nullptr, d_state, d_info));
+    else
+        CHECK_PAGK(pagk_frame_handover_device(ctx, &p, w, h, cap, nk, 0.0, d_st, d_pp, d_ppu, cap, d_ncand, d_cand, ks[0].keys,
+                                              ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last, ks[0].live, nullptr,
+                                              d_state));
     CHECK_PAGK(pagk_sync(ctx));
     n_cand = 0;  // no detector from here on: the list only shrinks, as in stream_resident
     CHECK_HIP(hipMemcpy(d_ncand, &n_cand, 4, hipMemcpyHostToDevice));
@@ -152,14 +175,25 @@ int main(int argc, char **argv)
         // Step 3 (src/gyro_aided_tracker.cpp:289-341), then Examples/Demo/RealSenseD435i.cpp:254-258 on the device
         CHECK_PAGK(pagk_post_filter_device(ctx, cap, half, d_st_pm, d_err, d_dist, d_ptdist, d_ptun, d_st, d_pp, d_ppu,
                                            d_kept, nullptr));
-        CHECK_PAGK(pagk_frame_handover_device(ctx, &p, w, h, cap, nk, 0.0, d_st, d_pp, d_ppu, cap, d_ncand, d_cand, dst.keys,
-                                              dst.keys_un, dst.keys_normal, dst.index_in_last, dst.live, nullptr, d_state));
+        if (detect)   // the top-up comes from the frame just tracked into, under this call's mask
+            CHECK_PAGK(pagk_frame_handover_detect_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &det,
+                                                         par, dst.keys, dst.keys_un, dst.keys_normal, dst.index_in_last,
+                                                         dst.live, nullptr, d_state, d_info));
+        else
+            CHECK_PAGK(pagk_frame_handover_device(ctx, &p, w, h, cap, nk, 0.0, d_st, d_pp, d_ppu, cap, d_ncand, d_cand, dst.keys,
+                                                  dst.keys_un, dst.keys_normal, dst.index_in_last, dst.live, nullptr, d_state));
         return 0;
     };
 
     int32_t graph[2] = {-1, -1};
     bool ran_directly[2] = {false, false};
     int n = nk;
+    if (detect) {
+        int32_t state[PAGK_HANDOVER_STATE_WORDS];
+        CHECK_HIP(hipMemcpy(state, d_state, sizeof state, hipMemcpyDeviceToHost));
+        n = state[0];
+        std::printf("first frame detected %d of %d\n", n, nk);
+    }
     double checksum = 0;
     std::vector<float> keys_un((size_t)cap * 2);
     for (int k = 1; k < nf && n > 0; k++) {
@@ -188,7 +222,10 @@ int main(int argc, char **argv)
         CHECK_HIP(hipMemcpy(&kept, d_kept, 4, hipMemcpyDeviceToHost));
         CHECK_HIP(hipMemcpy(state, d_state, sizeof state, hipMemcpyDeviceToHost));
         CHECK_HIP(hipMemcpy(keys_un.data(), ks[par].keys_un, n8, hipMemcpyDeviceToHost));
-        std::printf("pair %d tracked %d of %d\n", k, kept, n);
+        if (detect)
+            std::printf("pair %d tracked %d of %d, added %d\n", k, kept, n, state[3]);
+        else
+            std::printf("pair %d tracked %d of %d\n", k, kept, n);
         for (int i = 0; i < state[2]; i++) checksum += keys_un[2 * i] + 2.0 * keys_un[2 * i + 1];
         n = state[0];
     }

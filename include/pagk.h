@@ -323,7 +323,8 @@ int pagk_gyro_predict_device_live(pagk_ctx *ctx, const pagk_params *params, int3
 /* GyroAidedTracker::SetBackToFrame (src/gyro_aided_tracker.cpp:97-111), Frame::SetPredictKeyPointsAndMask
  * (src/frame.cpp:115-153) and the top-up rule all three detectors of the reference end in (Frame::DetectKeyPoints
  * :156-218, Frame::LoadDetectedKeypointFromFile :222-281, ORBextractor.cc:1199-1203), on the device.  The detector
- * stays the application's: it delivers a candidate list (undistorted points) in device memory.  In the reference's order:
+ * stays the application's here: it delivers a candidate list (undistorted points) in device memory (ORB, SuperPoint; for
+ * the reference's goodFeaturesToTrack call see pagk_frame_handover_detect_device below).  In the reference's order:
  *   survivors  for i in index order with d_status[i] != 0 (cap entries): keys[m] = pt_predict[i], keys_un[m] =
  *              pt_predict_un[i], keys_normal[m] = ((x_un - cx) * fx_inv, (y_un - cy) * fy_inv) in f32 with fx_inv =
  *              (float)(1.0 / fx) (src/frame.cpp:70, :128-129), index_in_last[m] = i  (a stable compaction).
@@ -364,6 +365,92 @@ int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width,
                         float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live,
                         uint8_t *mask, int32_t *state);
 
+/* ---- corner detection on the device: the reference's goodFeaturesToTrack call ------------------------------------- */
+/* Frame::DetectKeyPoints (src/frame.cpp:156-218) tops a frame up with
+ *     cv::goodFeaturesToTrack(mGray, corners_un, n_new, 0.005, 20, mMask, 3, true, 0.04)               (:181-184)
+ * OpenCV's SIMD paths fix no operation order, so NO parity with OpenCV's arithmetic is claimed.  The contract is this
+ * definition, bit for bit (restated in plain C in tests/corner_detect_ref.c); it follows goodFeaturesToTrack with
+ * useHarrisDetector = true step by step, and says where it is the library's own choice.
+ *   input      an 8-bit image W x H (level 0 of a frame slot), W, H >= 14 as for the hand-over; an optional byte mask
+ *              W x H, rows W bytes apart (the hand-over's layout), NULL = all ones.
+ *   gradients  3 x 3 Sobel dx, dy in integers, unscaled; pixels outside the image by reflection without repeating the
+ *              edge (index -1 is 1, index W is W - 2).
+ *   block sums a = sum dx*dx, b = sum dx*dy, c = sum dy*dy over the 3 x 3 block around the pixel, in integers; the
+ *              product maps are indexed with the same reflection.  |dx|, |dy| <= 1020: every sum <= 9 363 600 < 2^24.
+ *   response   R64 = (a*c - b*b) - k * ((a + c) * (a + c)) in f64: a*c, b*b, their difference and (a + c)^2 are exact,
+ *              so R64 has exactly two roundings (the product with k, the subtraction), never contracted into an FMA;
+ *              R = (float)R64.  OpenCV's scale factor is left out (library's choice: a positive constant, and every
+ *              later test compares responses with each other).
+ *   threshold  Rmax = the largest R over the pixels with mask != 0, the outer ring included.  No unmasked pixel, or
+ *              Rmax <= 0: no corners.  A pixel passes if (double)R > quality_level * (double)Rmax.
+ *   non-max    only 1 <= x <= W - 2, 1 <= y <= H - 2 with mask != 0 can be corners.  The pixel must be >= its four
+ *              neighbours that come earlier in raster order (NW, N, NE, W) and > the four that come later; the
+ *              neighbours' responses count whatever their mask says.  This tie rule is the library's own (OpenCV keeps
+ *              both pixels of an exact tie and lets the minimum distance drop one).  At most one pixel of any 2 x 2
+ *              block survives: never more than ceil((W-2)/2) * ceil((H-2)/2) raw candidates.
+ *   order      descending by the 64-bit key (bits(R) << 32) | (y * W + x); R > 0 here, so its bits order like its value;
+ *              a tie goes to the higher pixel index, in agreement with the non-maximum rule.
+ *   distance   the candidates are walked in that order; one is accepted unless an already accepted corner lies at
+ *              (double)(ddx*ddx + ddy*ddy) < min_distance * min_distance, in integer pixel coordinates; the walk stops
+ *              once max_corners are accepted.  min_distance < 1 switches the test off.
+ *   output     the accepted corners as (float)x, (float)y in acceptance order, and their number; entries beyond the
+ *              number are zeroed.  No sub-pixel step (goodFeaturesToTrack has none either).
+ *   overflow   the caller sizes the raw-candidate buffer (raw_cap).  If more raw candidates exist than fit, which of
+ *              them were stored is a matter of timing: the call then returns NO corners and sets the overflow word, never
+ *              a result that depends on timing.  raw_cap = 0: the context owns a buffer of the bound above (sized by a
+ *              call outside a capture, like d_mask == NULL in the hand-over).
+ * Block size 3 and aperture 3 are fixed; cornerMinEigenVal (useHarrisDetector = false) and ORBextractor are not provided.
+ * quality_level, min_distance >= 0 and finite, harris_k finite, raw_cap >= 0 (PAGK_E_ARG otherwise).
+ * info, PAGK_DETECT_INFO_WORDS int32: [0] corners returned, [1] raw candidates found (the true number, also on
+ * overflow), [2] overflow, [3] the bits of Rmax (0 if there is none or Rmax <= 0), [4] the candidates the distance walk
+ * visited (the index of the last accepted one + 1 when it stopped at the limit), the rest 0. */
+typedef struct pagk_detect_params {
+    double quality_level; /* qualityLevel  0.005 (src/frame.cpp:183) */
+    double min_distance;  /* minDistance   20                         */
+    double harris_k;      /* k             0.04  (:184)               */
+    int32_t raw_cap;      /* raw-candidate buffer; 0 = the bound, owned by the context */
+} pagk_detect_params;
+#define PAGK_DETECT_INFO_WORDS 8
+/* 0.005, 20, 0.04, 0: the arguments at src/frame.cpp:181-184 */
+void pagk_detect_params_default(pagk_detect_params *p);
+/* Frame::DetectKeyPoints' detector call (src/frame.cpp:156-218, the call at :181-184) on level 0 of frame slot `slot`
+ * (pagk_frame_set_device, its batch form and pagk_track_device_fused read the caller's image in place: detection on a slot
+ * is defined only until the caller rewrites the buffer the slot was set from, not merely until the slot is set again --
+ * a loop that feeds every frame through one buffer can detect on the slot of the current frame only).  d_mask: W * H bytes or NULL.
+ * d_corners: cap x 2 float, d_info: PAGK_DETECT_INFO_WORDS int32.  The effective limit is min(cap, max(0,
+ * *d_max_corners)); d_max_corners NULL = cap.  Device pointers, asynchronous on the context stream, capturable; no count
+ * is read on the host: every launch is sized by W, H, raw_cap and cap.  Run it once outside a capture first (workspace). */
+int pagk_detect_corners_device(pagk_ctx *ctx, const pagk_detect_params *det, int32_t slot, const uint8_t *d_mask,
+                               int32_t cap, const int32_t *d_max_corners, float *d_corners, int32_t *d_info);
+/* The same with host buffers, synchronous (src/frame.cpp:156-218): corners holds max_corners x 2 floats, mask (or NULL)
+ * img->width * img->height bytes, info (or NULL) PAGK_DETECT_INFO_WORDS words.  max_corners >= 0. */
+int pagk_detect_corners(pagk_ctx *ctx, const pagk_detect_params *det, const pagk_image *img, const uint8_t *mask,
+                        int32_t max_corners, float *corners, int32_t *info);
+/* pagk_frame_handover_device with the reference's own detector as the source of the candidates (Frame::DetectKeyPoints,
+ * src/frame.cpp:156-218, in one call): its result is BY DEFINITION what pagk_frame_handover_device returns when the
+ * candidate list is detect(level 0 of `slot`, the mask this call builds, max_corners = n_new) -- the mask of THIS frame,
+ * as the reference passes it (:158, :184), not last frame's.  `slot` is the frame just tracked INTO (the current image).
+ * The list is empty when the top-up does not run (:164-169): the detector's kernels then return early on a device-side
+ * flag and d_info is all zero.  State words [0]-[4] keep their meaning; [4] is 0 by construction (a detected corner lies
+ * on an unmasked pixel of the image).  A call with an all-zero d_status detects the first frame's target_n keypoints.
+ * d_info: PAGK_DETECT_INFO_WORDS int32.  Otherwise the arguments and rules of pagk_frame_handover_device. */
+int pagk_frame_handover_detect_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                                      int32_t cap, int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                                      const float *d_pt_predict, const float *d_pt_predict_un,
+                                      const pagk_detect_params *det, int32_t slot, float *d_keys, float *d_keys_un,
+                                      float *d_keys_normal /* or NULL */, int32_t *d_index_in_last, uint8_t *d_live,
+                                      uint8_t *d_mask /* width * height, or NULL */, int32_t *d_state, int32_t *d_info);
+/* The same with host buffers, synchronous (src/frame.cpp:156-218); the current image comes as a pagk_image of
+ * width x height.  state is read (reach_flag) and written; keys_normal, mask and info may be NULL. */
+int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *status,
+                               const float *pt_predict, const float *pt_predict_un, const pagk_detect_params *det,
+                               const pagk_image *img, float *keys, float *keys_un, float *keys_normal,
+                               int32_t *index_in_last, uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info);
+/* Diagnostic: the response map R alone (img->width * img->height floats, harris_k = 0.04), host buffers: localises a
+ * mismatch to the first stage of the detector (src/frame.cpp:156-218 has no counterpart: OpenCV keeps the map inside). */
+int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R);
+
 /* Diagnostics (never on the tracking path): the arithmetic of H.llt().solve(b) / update.norm()
  * (src/patch_match.cpp:319,343) on the caller's operands, so that a host can check on its own device -- and, with
  * Eigen at hand, against its own Eigen -- what pagk_params::solver_variant selects.
@@ -388,7 +475,8 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
  * stream issues the same launches on the same device pointers every frame; between pagk_graph_begin and
  * pagk_graph_end the *_device entry points (pagk_frame_set_device, pagk_gyro_predict_device[_rot],
  * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
- * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device) are recorded on the context stream instead of executed,
+ * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
+ * pagk_frame_handover_detect_device) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while
  * capturing; the context stream must not be the legacy default stream; the kernel timers

@@ -48,6 +48,14 @@ class FitParams(C.Structure):
                 ("thresh_F", C.c_double), ("conf_H", C.c_double), ("conf_F", C.c_double)]
 
 
+class DetectParams(C.Structure):
+    """pagk_detect_params (include/pagk.h): the arguments of the reference's goodFeaturesToTrack call."""
+    _fields_ = [("quality_level", C.c_double), ("min_distance", C.c_double), ("harris_k", C.c_double),
+                ("raw_cap", C.c_int32)]
+
+
+DETECT_INFO_WORDS = 8
+DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
 FIT_INFO_WORDS = 12
 FIT_INFO_FIELDS = ("status", "best", "best_count", "refit_count", "valid", "adaptive")
 
@@ -202,6 +210,21 @@ def declare(lib) -> None:
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp, i32, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "pagk_detect_corners_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_detect_params_default.restype = None
+        lib.pagk_detect_params_default.argtypes = [_P(DetectParams)]
+        lib.pagk_detect_corners_device.restype = C.c_int
+        lib.pagk_detect_corners_device.argtypes = [vp, _P(DetectParams), i32, vp, i32, vp, vp, vp]
+        lib.pagk_detect_corners.restype = C.c_int
+        lib.pagk_detect_corners.argtypes = [vp, _P(DetectParams), _P(Image), vp, i32, vp, vp]
+        lib.pagk_frame_handover_detect_device.restype = C.c_int
+        lib.pagk_frame_handover_detect_device.argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp,
+                                                          _P(DetectParams), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_frame_handover_detect.restype = C.c_int
+        lib.pagk_frame_handover_detect.argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp,
+                                                   _P(DetectParams), _P(Image), vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_selftest_corner_response.restype = C.c_int
+        lib.pagk_selftest_corner_response.argtypes = [vp, _P(Image), vp]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -303,6 +326,8 @@ EXPORTED_SYMBOLS = [
     "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
     "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
     "pagk_post_filter_device", "pagk_gyro_predict_device_live", "pagk_frame_handover_device", "pagk_frame_handover",
+    "pagk_detect_params_default", "pagk_detect_corners_device", "pagk_detect_corners",
+    "pagk_frame_handover_detect_device", "pagk_frame_handover_detect", "pagk_selftest_corner_response",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -316,6 +341,17 @@ def fit_params_default(**overrides) -> FitParams:
     for k, v in overrides.items():
         if k not in dict(FitParams._fields_):
             raise TypeError(f"pagk_fit_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def detect_params_default(**overrides) -> DetectParams:
+    """pagk_detect_params_default() with overrides (quality_level, min_distance, harris_k, raw_cap)."""
+    p = DetectParams()
+    load().pagk_detect_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(DetectParams._fields_):
+            raise TypeError(f"pagk_detect_params has no field {k}")
         setattr(p, k, v)
     return p
 
@@ -732,6 +768,82 @@ class Context:
             self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
             _ptr(ppu), cc, _ptr(ncand), _ptr(cbuf), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
             _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state)), "pagk_frame_handover")
+        return out
+
+    # the corner detector (reference src/frame.cpp:156-218: goodFeaturesToTrack with the Harris response) -------
+    detect_params_default = staticmethod(detect_params_default)
+
+    def detect_corners_device(self, det: DetectParams, slot: int, d_mask, cap: int, d_max_corners, d_corners, d_info):
+        """pagk_detect_corners_device on level 0 of frame slot `slot` (asynchronous, capturable).  d_mask / d_max_corners
+        may be None (all ones / cap)."""
+        if d_corners is None or d_info is None:
+            raise ValueError("d_corners and d_info are required")
+        self._check(self.lib.pagk_detect_corners_device(self.h, C.byref(det), slot, _ptr(d_mask), cap, _ptr(d_max_corners),
+                                                        _ptr(d_corners), _ptr(d_info)), "pagk_detect_corners_device")
+
+    def detect_corners(self, img: np.ndarray, mask, max_corners: int, det: DetectParams | None = None) -> dict:
+        """pagk_detect_corners, host buffers -> dict(corners (the accepted ones, n x 2), buffer (max_corners x 2, zero
+        beyond n), info, and the info words by name)."""
+        det = det if det is not None else detect_params_default()
+        iv = image_view(img)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != img.shape:
+            raise ValueError("the mask has the wrong shape")
+        buf = np.zeros((max(int(max_corners), 1), 2), np.float32)
+        info = np.zeros(DETECT_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_detect_corners(self.h, C.byref(det), C.byref(iv), _ptr(m), int(max_corners), _ptr(buf),
+                                                 _ptr(info)), "pagk_detect_corners")
+        out = dict(corners=buf[:int(info[0])], buffer=buf, info=info)
+        out.update(zip(DETECT_INFO_FIELDS, (int(v) for v in info[:5])))
+        return out
+
+    def selftest_corner_response(self, img: np.ndarray) -> np.ndarray:
+        """The detector's response map R (float32, harris_k = 0.04) of an image, computed on the device."""
+        iv = image_view(img)
+        R = np.zeros(img.shape, np.float32)
+        self._check(self.lib.pagk_selftest_corner_response(self.h, C.byref(iv), _ptr(R)), "pagk_selftest_corner_response")
+        return R
+
+    def frame_handover_detect_device(self, params: Params, width: int, height: int, cap: int, target_n: int,
+                                     new_point_threshold: float, d_status, d_pt_predict, d_pt_predict_un,
+                                     det: DetectParams, slot: int, d_keys, d_keys_un, d_keys_normal, d_index_in_last,
+                                     d_live, d_mask, d_state, d_info):
+        """pagk_frame_handover_detect_device on device arrays (asynchronous, capturable): the hand-over with the
+        candidates detected on level 0 of frame slot `slot` under the mask the call builds."""
+        if cap < target_n:
+            raise ValueError("cap must be at least target_n")
+        self._check(self.lib.pagk_frame_handover_detect_device(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
+            _ptr(d_pt_predict), _ptr(d_pt_predict_un), C.byref(det), slot, _ptr(d_keys), _ptr(d_keys_un),
+            _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state), _ptr(d_info)),
+            "pagk_frame_handover_detect_device")
+
+    def frame_handover_detect(self, params: Params, img: np.ndarray, cap: int, target_n: int, new_point_threshold: float,
+                              status, pt_predict, pt_predict_un, det: DetectParams | None = None, state=None) -> dict:
+        """pagk_frame_handover_detect, host buffers -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state,
+        info).  `state` is copied, not updated in place; status / points are padded to cap."""
+        det = det if det is not None else detect_params_default()
+        height, width = img.shape
+
+        def pad(a, dtype, width_):
+            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
+            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
+            if a.shape[0] > cap:
+                raise ValueError("more entries than cap")
+            out[:a.shape[0]] = a
+            return out
+        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
+        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+        iv = image_view(img)
+        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
+                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
+                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state,
+                   info=np.zeros(DETECT_INFO_WORDS, np.int32))
+        self._check(self.lib.pagk_frame_handover_detect(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
+            _ptr(ppu), C.byref(det), C.byref(iv), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
+            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
+            "pagk_frame_handover_detect")
         return out
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------

@@ -26,6 +26,8 @@ struct FrameSlot {
     int pad0 = 0;                    // min(step - cols, 2) of the level-0 source (free GetPixelValue, x == cols)
     uint8_t *u8[kMaxLevels] = {};    // u8[0] is our contiguous copy of level 0 (pitch = w)
     uint32_t *quad[kMaxLevels] = {};
+    const uint8_t *img0 = nullptr;   // level 0 where the pyramid was built from (our copy, or the caller's device image
+    int64_t pitch0 = 0;              // read in place): what the corner detector reads (pagk_detect_kernel.h)
     void *block = nullptr;           // one allocation for everything above
     size_t block_bytes = 0;
     bool valid = false;
@@ -52,6 +54,7 @@ struct pagk_ctx {
     FeatBuf fitio;  // scratch of the host-buffer fit / validation entry points
     FeatBuf hand;   // the frame hand-over's own mask (pagk_handover_kernel.h): sized outside captures, pointed into by graphs
     FeatBuf handio; // scratch of the host-buffer hand-over
+    FeatBuf det;    // workspace of the corner detector (pagk_detect_kernel.h): sized outside captures, pointed into by graphs
     void *quad_ws = nullptr;  // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
     size_t quad_ws_bytes = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
@@ -365,6 +368,7 @@ bool pyramid_fusable(const FrameSlot &s)
 int slot_build(pagk_ctx *ctx, FrameSlot &s, const uint8_t *src0, int64_t pitch0, int wrap0)
 {
     s.pad0 = wrap0 ? 0 : 2;  // callers that know the source's step refine this (frame_upload_any, pagk_frame_set_device)
+    s.img0 = src0, s.pitch0 = pitch0;
     int lw[kMaxLevels], lh[kMaxLevels];
     level_dims(s.w, s.h, s.L, lw, lh);
     dim3 blk(32, 8);
@@ -1212,6 +1216,7 @@ void pagk_destroy(pagk_ctx *ctx)
     if (ctx->fitio.block) (void)hipFree(ctx->fitio.block);
     if (ctx->hand.block) (void)hipFree(ctx->hand.block);
     if (ctx->handio.block) (void)hipFree(ctx->handio.block);
+    if (ctx->det.block) (void)hipFree(ctx->det.block);
     if (ctx->quad_ws) (void)hipFree(ctx->quad_ws);
     if (ctx->susp) (void)hipFree(ctx->susp);
     if (ctx->queue) (void)hipFree(ctx->queue);
@@ -1475,6 +1480,7 @@ int pagk_frame_set_device_batch(pagk_ctx *const *ctxs, int32_t k, const int32_t 
         FrameSlot &s = ctxs[j]->slots[slot[j]];
         s.wrap0 = step[j] == width[j];
         s.pad0 = (int)(step[j] - width[j] > 2 ? 2 : step[j] - width[j]);
+        s.img0 = static_cast<const uint8_t *>(d_data[j]), s.pitch0 = step[j];
         s.valid = true;
     }
     return PAGK_OK;
@@ -1706,6 +1712,7 @@ int pagk_track_device_fused(pagk_ctx *ctx, const pagk_params *params, int32_t sl
         if (fused) {
             sn.wrap0 = wrap0;
             sn.pad0 = (int)(step - width > 2 ? 2 : step - width);
+            sn.img0 = src0, sn.pitch0 = step;
             sn.valid = true;
             return PAGK_OK;
         }
@@ -1794,6 +1801,7 @@ int pagk_track_pyr(pagk_ctx *ctx, const pagk_params *params, int32_t n_levels, c
         HIPCHK(ctx, hipGetLastError());
         s.wrap0 = lv[k][0].step == lv[k][0].width;
         s.pad0 = (int)(lv[k][0].step - lv[k][0].width > 2 ? 2 : lv[k][0].step - lv[k][0].width);
+        s.img0 = s.u8[0], s.pitch0 = s.w;
         s.valid = true;
     }
     return track_host_common(ctx, params, n, pt_ref_un, pt_init_un, affine, status_in, out, ctx->slots[4],
@@ -1954,6 +1962,23 @@ int handover_mask(pagk_ctx *ctx, size_t bytes, uint8_t **mask)
     return PAGK_OK;
 }
 
+// the sizes, the rule's constants and the camera model of a hand-over; the pointers are the caller's to fill
+void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                        int32_t target_n, double new_point_threshold)
+{
+    HandoverArgs a;
+    memset(&a, 0, sizeof a);
+    a.cap = cap, a.width = width, a.height = height, a.target_n = target_n;
+    a.new_point_threshold = new_point_threshold;
+    a.fx = params->fx, a.fy = params->fy, a.cx = params->cx, a.cy = params->cy;
+    a.fx_inv = (float)(1.0 / (double)params->fx);  // src/frame.cpp:70
+    a.fy_inv = (float)(1.0 / (double)params->fy);
+    a.k1 = params->dist_coef[0], a.k2 = params->dist_coef[1], a.p1 = params->dist_coef[2], a.p2 = params->dist_coef[3];
+    a.k3 = params->n_dist_coef == 5 ? params->dist_coef[4] : 0.0f;
+    a.distort_on = params->dist_coef[0] != 0.0f;
+    *out = a;
+}
+
 }  // namespace
 
 int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -1976,15 +2001,8 @@ int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t
         if (rc) return rc;
     }
     HandoverArgs a;
-    memset(&a, 0, sizeof a);
-    a.cap = cap, a.cand_cap = cand_cap, a.width = width, a.height = height, a.target_n = target_n;
-    a.new_point_threshold = new_point_threshold;
-    a.fx = params->fx, a.fy = params->fy, a.cx = params->cx, a.cy = params->cy;
-    a.fx_inv = (float)(1.0 / (double)params->fx);  // src/frame.cpp:70
-    a.fy_inv = (float)(1.0 / (double)params->fy);
-    a.k1 = params->dist_coef[0], a.k2 = params->dist_coef[1], a.p1 = params->dist_coef[2], a.p2 = params->dist_coef[3];
-    a.k3 = params->n_dist_coef == 5 ? params->dist_coef[4] : 0.0f;
-    a.distort_on = params->dist_coef[0] != 0.0f;
+    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
+    a.cand_cap = cand_cap;
     a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
     a.n_cand = d_n_cand, a.cand_un = d_cand_un;
     a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
@@ -2047,6 +2065,309 @@ int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width,
     return PAGK_OK;
 }
 
+// ---- corner detection (pagk_detect_kernel.h) -------------------------------------------------------------------
+namespace {
+
+// a device block of a synchronous host-buffer entry point, freed when the call returns
+struct Scratch {
+    void *p = nullptr;
+    ~Scratch() { if (p) (void)hipFree(p); }
+};
+
+bool detect_params_ok(const pagk_detect_params *d)
+{
+    return d && std::isfinite(d->quality_level) && d->quality_level >= 0.0 && std::isfinite(d->min_distance) &&
+           d->min_distance >= 0.0 && std::isfinite(d->harris_k) && d->raw_cap >= 0;
+}
+
+// at most one pixel of any 2 x 2 block passes the non-maximum test
+int64_t detect_raw_bound(int w, int h) { return (int64_t)((w - 2 + 1) / 2) * ((h - 2 + 1) / 2); }
+
+// The detector's workspace for one call: control words | response map | sort keys (a power of two, at least one sort
+// block) | the fused call's candidate list | its plan's spare info | the distance grid when it does not fit the LDS.
+struct DetectWs {
+    int32_t *ctl = nullptr, *grid = nullptr;
+    float *R = nullptr, *cand = nullptr;
+    uint64_t *keys = nullptr;
+    uint32_t key_slots = 0;
+    int32_t raw_cap = 0, cell = 1, grid_w = 1, grid_h = 1, reach = 1;
+};
+
+int detect_workspace(pagk_ctx *ctx, const pagk_detect_params *det, int w, int h, int cap, DetectWs *ws)
+{
+    const int64_t bound = detect_raw_bound(w, h);
+    const int64_t raw_cap = det->raw_cap > 0 ? det->raw_cap : bound;
+    if (raw_cap > (1 << 30)) return PAGK_E_ARG;
+    uint32_t slots = kDetSortBlock;
+    while ((int64_t)slots < raw_cap) slots <<= 1;
+    // cells of at most min_distance / sqrt(2) pixels: two pixels of one cell are closer than min_distance
+    const double d = det->min_distance;
+    int64_t cell = (int64_t)std::floor(d / std::sqrt(2.0));
+    const int64_t longest = w > h ? w : h;
+    cell = cell < 1 ? 1 : (cell > longest ? longest : cell);
+    const int64_t gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
+    int64_t reach = (int64_t)std::ceil(d / (double)cell);
+    reach = reach > longest ? longest : reach;
+    const bool grid_global = d >= 1.0 && gw * gh > kDetGridLds;
+    const size_t px = (size_t)w * h;
+    const size_t sizes[5] = {256, px * 4, (size_t)slots * 8, (size_t)cap * 8, grid_global ? (size_t)(gw * gh) * 4 : 0};
+    size_t off[5], total = 0;
+    for (int k = 0; k < 5; k++) {
+        off[k] = total;
+        total += align_up(sizes[k], 256);
+    }
+    if (total > ctx->det.bytes) {
+        if (in_capture(ctx)) {
+            snprintf(ctx->err, sizeof(ctx->err), "the detector's workspace would have to grow inside a capture: run the call once "
+                     "with this image size, raw_cap, cap and min_distance before capturing");
+            return PAGK_E_ARG;
+        }
+        int rc = no_live_graphs(ctx, "the detector's workspace");
+        if (rc) return rc;
+        if (ctx->det.block) HIPCHK(ctx, hipFree(ctx->det.block));
+        ctx->det.block = nullptr;
+        ctx->det.bytes = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->det.block, total));
+        ctx->det.bytes = total;
+    }
+    uint8_t *b = static_cast<uint8_t *>(ctx->det.block);
+    ws->ctl = reinterpret_cast<int32_t *>(b + off[0]);
+    ws->R = reinterpret_cast<float *>(b + off[1]);
+    ws->keys = reinterpret_cast<uint64_t *>(b + off[2]);
+    ws->cand = reinterpret_cast<float *>(b + off[3]);
+    ws->grid = grid_global ? reinterpret_cast<int32_t *>(b + off[4]) : nullptr;
+    ws->key_slots = slots;
+    ws->raw_cap = (int32_t)raw_cap;
+    ws->cell = (int32_t)cell, ws->grid_w = (int32_t)gw, ws->grid_h = (int32_t)gh, ws->reach = (int32_t)reach;
+    return PAGK_OK;
+}
+
+int detect_response_launch(pagk_ctx *ctx, const FrameSlot &s, const uint8_t *d_mask, double harris_k, const DetectWs &ws,
+                           const int32_t *d_skip)
+{
+    hipLaunchKernelGGL(k_detect_response, dim3((s.w + kDetTileW - 1) / kDetTileW, (s.h + kDetTileH - 1) / kDetTileH), dim3(256),
+                       0, ctx->stream, s.img0, s.pitch0, s.w, s.h, d_mask, harris_k, ws.R, ws.ctl, d_skip);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// The detector's launches on frame slot `s`.  d_max_corners / d_skip: device words or NULL.  The first two control
+// words (Rmax, the raw count) are cleared here; the fused call's plan (words 2, 3) is written in front of this.
+int detect_launch(pagk_ctx *ctx, const pagk_detect_params *det, const FrameSlot &s, const uint8_t *d_mask, int32_t cap,
+                  const int32_t *d_max_corners, const int32_t *d_skip, float *d_corners, int32_t *d_info, const DetectWs &ws)
+{
+    HIPCHK(ctx, hipMemsetAsync(ws.ctl, 0, 8, ctx->stream));
+    int rc = detect_response_launch(ctx, s, d_mask, det->harris_k, ws, d_skip);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_detect_nms, dim3((s.w + 63) / 64, (s.h + 3) / 4), dim3(256), 0, ctx->stream, ws.R, s.w, s.h, d_mask,
+                       det->quality_level, ws.ctl, ws.keys, ws.raw_cap, d_skip);
+    HIPCHK(ctx, hipGetLastError());
+    // bitonic network over key_slots: every launch is there whatever the count; the blocks that hold nothing return
+    const uint32_t N = ws.key_slots;
+    const size_t sort_lds = (size_t)kDetSortBlock * sizeof(uint64_t);   // 128 KiB: beyond the default limit of a launch
+    if (!in_capture(ctx))   // (a capture follows a direct run of the same call, which has set it)
+        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_detect_sort_local),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds));
+    hipLaunchKernelGGL(k_detect_sort_local, dim3(N / kDetSortBlock), dim3(1024), sort_lds, ctx->stream, ws.keys, ws.ctl,
+                       ws.raw_cap, 0u, d_skip);
+    for (uint32_t k = 2 * kDetSortBlock; k <= N; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= (uint32_t)kDetSortBlock; j >>= 1)
+            hipLaunchKernelGGL(k_detect_sort_step, dim3(N / 2 / 256), dim3(256), 0, ctx->stream, ws.keys, ws.ctl, ws.raw_cap, k, j,
+                               d_skip);
+        hipLaunchKernelGGL(k_detect_sort_local, dim3(N / kDetSortBlock), dim3(1024), sort_lds, ctx->stream, ws.keys, ws.ctl,
+                           ws.raw_cap, k, d_skip);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    DetectWalkArgs a;
+    memset(&a, 0, sizeof a);
+    a.keys = ws.keys, a.ctl = ws.ctl, a.max_corners = d_max_corners, a.skip = d_skip;
+    a.raw_cap = ws.raw_cap, a.cap = cap, a.width = s.w, a.height = s.h;
+    a.min_distance = det->min_distance;
+    a.cell = ws.cell, a.grid_w = ws.grid_w, a.grid_h = ws.grid_h, a.reach = ws.reach, a.grid = ws.grid;
+    a.corners = d_corners, a.info = d_info;
+    hipLaunchKernelGGL(k_detect_walk, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+bool detect_slot_ok(const FrameSlot &s) { return s.valid && s.img0 && s.w >= 14 && s.h >= 14; }
+
+int detect_corners_slot(pagk_ctx *ctx, const pagk_detect_params *det, int32_t slot, const uint8_t *d_mask, int32_t cap,
+                        const int32_t *d_max_corners, float *d_corners, int32_t *d_info)
+{
+    const FrameSlot &s = ctx->slots[slot];
+    if (!detect_slot_ok(s)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DetectWs ws;
+    int rc = detect_workspace(ctx, det, s.w, s.h, cap, &ws);
+    if (rc) return rc;
+    return detect_launch(ctx, det, s, d_mask, cap, d_max_corners, nullptr, d_corners, d_info, ws);
+}
+
+int handover_detect_slot(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                         int32_t target_n, double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
+                         const float *d_pt_predict_un, const pagk_detect_params *det, int32_t slot, float *d_keys,
+                         float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                         int32_t *d_state, int32_t *d_info)
+{
+    const FrameSlot &s = ctx->slots[slot];
+    if (!detect_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int64_t bytes = (int64_t)width * height;
+    uint8_t *mask = d_mask;
+    if (!mask) {
+        int rc = handover_mask(ctx, (size_t)bytes, &mask);
+        if (rc) return rc;
+    }
+    DetectWs ws;
+    int rc = detect_workspace(ctx, det, width, height, cap, &ws);
+    if (rc) return rc;
+    HandoverArgs a;
+    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
+    a.cand_cap = cap;   // n_new <= target_n <= cap corners at most
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.n_cand = d_info, a.cand_un = ws.cand;   // info[0] = the corners the detector returned
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
+    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
+                       width, height, d_status, d_pt_predict_un, mask);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
+                       (const int32_t *)d_state, ws.ctl);
+    HIPCHK(ctx, hipGetLastError());
+    rc = detect_launch(ctx, det, s, mask, cap, ws.ctl + kDetCtlLimit, ws.ctl + kDetCtlSkip, ws.cand, d_info, ws);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+}  // namespace
+
+void pagk_detect_params_default(pagk_detect_params *p)
+{
+    if (!p) return;
+    p->quality_level = 0.005;   // src/frame.cpp:183
+    p->min_distance = 20.0;
+    p->harris_k = 0.04;         // :184
+    p->raw_cap = 0;
+}
+
+int pagk_detect_corners_device(pagk_ctx *ctx, const pagk_detect_params *det, int32_t slot, const uint8_t *d_mask,
+                               int32_t cap, const int32_t *d_max_corners, float *d_corners, int32_t *d_info)
+{
+    if (!ctx || !detect_params_ok(det) || slot < 0 || slot >= kUserSlots || cap < 1 || !d_corners || !d_info) return PAGK_E_ARG;
+    return detect_corners_slot(ctx, det, slot, d_mask, cap, d_max_corners, d_corners, d_info);
+}
+
+int pagk_detect_corners(pagk_ctx *ctx, const pagk_detect_params *det, const pagk_image *img, const uint8_t *mask,
+                        int32_t max_corners, float *corners, int32_t *info)
+{
+    if (!ctx || !detect_params_ok(det) || !img || max_corners < 0 || (max_corners > 0 && !corners)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_detect_corners");
+    if (img->width < 14 || img->height < 14) return PAGK_E_ARG;
+    int rc = frame_upload_any(ctx, 4, img, 1);
+    if (rc) return rc;
+    const size_t px = (size_t)img->width * img->height, cap = (size_t)(max_corners > 0 ? max_corners : 1);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, align_up(px, 256) + align_up(cap * 8, 256) + 512));
+    uint8_t *b = static_cast<uint8_t *>(s.p);
+    uint8_t *d_mask = mask ? b : nullptr;
+    float *d_corners = reinterpret_cast<float *>(b + align_up(px, 256));
+    int32_t *d_info = reinterpret_cast<int32_t *>(b + align_up(px, 256) + align_up(cap * 8, 256)), *d_max = d_info + 64;
+    if (mask) HIPCHK(ctx, hipMemcpyAsync(d_mask, mask, px, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_max, &max_corners, 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = detect_corners_slot(ctx, det, 4, d_mask, (int32_t)cap, d_max, d_corners, d_info);
+    if (rc) return rc;
+    if (max_corners > 0)
+        HIPCHK(ctx, hipMemcpyAsync(corners, d_corners, (size_t)max_corners * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, d_info, kDetectInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R)
+{
+    if (!ctx || !img || !R) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_corner_response");
+    if (img->width < 14 || img->height < 14) return PAGK_E_ARG;
+    int rc = frame_upload_any(ctx, 4, img, 1);
+    if (rc) return rc;
+    pagk_detect_params det;
+    pagk_detect_params_default(&det);
+    DetectWs ws;
+    if ((rc = detect_workspace(ctx, &det, img->width, img->height, 1, &ws))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ws.ctl, 0, 8, ctx->stream));
+    if ((rc = detect_response_launch(ctx, ctx->slots[4], nullptr, det.harris_k, ws, nullptr))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(R, ws.R, (size_t)img->width * img->height * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_frame_handover_detect_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                                      int32_t cap, int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                                      const float *d_pt_predict, const float *d_pt_predict_un,
+                                      const pagk_detect_params *det, int32_t slot, float *d_keys, float *d_keys_un,
+                                      float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                                      int32_t *d_state, int32_t *d_info)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0) || !detect_params_ok(det) ||
+        slot < 0 || slot >= kUserSlots)
+        return PAGK_E_ARG;
+    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_keys || !d_keys_un || !d_index_in_last || !d_live || !d_state ||
+        !d_info)
+        return PAGK_E_ARG;
+    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
+    return handover_detect_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                                d_pt_predict_un, det, slot, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
+                                d_state, d_info);
+}
+
+int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *status,
+                               const float *pt_predict, const float *pt_predict_un, const pagk_detect_params *det,
+                               const pagk_image *img, float *keys, float *keys_un, float *keys_normal,
+                               int32_t *index_in_last, uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0) || !detect_params_ok(det))
+        return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover_detect");
+    if (!status || !pt_predict || !pt_predict_un || !img || img->width != width || img->height != height || !keys || !keys_un ||
+        !index_in_last || !live || !state)
+        return PAGK_E_ARG;
+    int rc = frame_upload_any(ctx, 4, img, 1);
+    if (rc) return rc;
+    const size_t nc = (size_t)cap, px = (size_t)width * height;
+    // status | pt_predict | pt_predict_un | keys | keys_un | keys_normal | index | live | state | info | mask
+    const size_t sizes[11] = {nc, nc * 8, nc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4,
+                              kDetectInfoWords * 4, px};
+    size_t off[11], total = 0;
+    for (int k = 0; k < 11; k++) {
+        off[k] = total;
+        total += align_up(sizes[k], 256);
+    }
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, total));
+    uint8_t *b = static_cast<uint8_t *>(s.p);
+    const void *src[3] = {status, pt_predict, pt_predict_un};
+    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(b + off[k], src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b + off[8], state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
+    rc = handover_detect_slot(ctx, params, width, height, cap, target_n, new_point_threshold, b + off[0],
+                              reinterpret_cast<float *>(b + off[1]), reinterpret_cast<float *>(b + off[2]), det, 4,
+                              reinterpret_cast<float *>(b + off[3]), reinterpret_cast<float *>(b + off[4]),
+                              keys_normal ? reinterpret_cast<float *>(b + off[5]) : nullptr,
+                              reinterpret_cast<int32_t *>(b + off[6]), b + off[7], b + off[10],
+                              reinterpret_cast<int32_t *>(b + off[8]), reinterpret_cast<int32_t *>(b + off[9]));
+    if (rc) return rc;
+    void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
+    const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
+    for (int k = 0; k < 8; k++)
+        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], b + off[from[k]], sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
 
 // ---- hipGraph capture of the per-frame work ---------------------------------------------------
 // BASELINE configs[4] ("hipGraph-captured iterate"): a camera stream issues the same launches with the same
@@ -2647,13 +2968,6 @@ int pagk_ncc_free(pagk_ctx *ctx, const pagk_image *ref, const pagk_image *cur, i
 }
 
 // ---- diagnostics: the solve's arithmetic on arbitrary operands (pagk_selftest_kernel.h) --------------------------
-namespace {
-// n doubles-per-item arrays in, copied to the device as one block; returns device pointers through `d`
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
-}  // namespace
 
 int pagk_selftest_divide(pagk_ctx *ctx, int32_t n, const double *num, const double *den, double *q_plain,
                          double *q_prepared, double *root, double *root_lean)

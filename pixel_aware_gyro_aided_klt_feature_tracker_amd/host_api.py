@@ -221,3 +221,24 @@ def frame_handover_device(ctx, *args):
 def gyro_predict_device_live(ctx, *args):
     """pagk_gyro_predict_device_live on device arrays: capi.Context.gyro_predict_device_live."""
     return ctx.gyro_predict_device_live(*args)
+
+
+# ---- the corner detector (reference src/frame.cpp:156-218), array in, array out ----
+def detect_corners(img, mask=None, max_corners: int = 1000, det=None, ctx=None) -> dict:
+    """pagk_detect_corners (host buffers): the reference's goodFeaturesToTrack call with the Harris response on an 8-bit
+    image -> dict(corners (n x 2 float32, strongest first), info and its words by name)."""
+    return _device_context(ctx).detect_corners(np.ascontiguousarray(img, np.uint8), mask, max_corners, det)
+
+
+def frame_handover_detect(params, img, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, det=None,
+                          state=None, ctx=None) -> dict:
+    """pagk_frame_handover_detect (host buffers): the hand-over with the top-up detected on `img` under the mask the call
+    builds -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state, info)."""
+    return _device_context(ctx).frame_handover_detect(params, np.ascontiguousarray(img, np.uint8), cap, target_n,
+                                                      new_point_threshold, status, pt_predict, pt_predict_un, det=det,
+                                                      state=state)
+
+
+def corner_response(img, ctx=None) -> np.ndarray:
+    """pagk_selftest_corner_response: the detector's response map of an image (float32, harris_k = 0.04)."""
+    return _device_context(ctx).selftest_corner_response(np.ascontiguousarray(img, np.uint8))

@@ -489,7 +489,8 @@ def _carve_size(fields) -> int:
 class FrameResult:
     """What one SequenceTracker step leaves behind: the keypoints of the next pair (keys, keys_un, keys_normal,
     index_in_last, live: `cap` entries each) and the hand-over's state words, as device tensors, with the event that was
-    recorded behind the work that produces them.  to_numpy() waits for that event (and for nothing issued later)."""
+    recorded behind the work that produces them.  to_numpy() waits for that event (and for nothing issued later).  A
+    tracker with a detector adds the detector's info words ("info")."""
 
     FIELDS = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state")
 
@@ -500,6 +501,8 @@ class FrameResult:
         with torch.cuda.stream(self._side):
             self._side.wait_event(self.event)
             host = {k: self.tensors[k].to("cpu", non_blocking=False) for k in self.FIELDS}
+            if "info" in self.tensors:
+                host["info"] = self.tensors["info"].to("cpu", non_blocking=False)
         out = {k: v.numpy() for k, v in host.items()}
         out.update(zip(capi.HANDOVER_STATE_FIELDS, (int(v) for v in out["state"][:5])))
         return out
@@ -518,17 +521,23 @@ class SequenceTracker:
     one direct run of each; mode="direct" issues the same calls without a graph.
 
     target_n = Frame::mN, new_point_ratio = th of mThresholdOfPredictNewKeyPoint = mN * th (src/frame.cpp:79).
-    fit_params None leaves the geometry validation out."""
+    fit_params None leaves the geometry validation out.
+
+    detector (a capi.DetectParams) closes the loop: the hand-over becomes pagk_frame_handover_detect_device, which
+    detects the top-up on the current frame under the mask it has just built (Frame::DetectKeyPoints, src/frame.cpp:
+    156-218), so start() and step() take no candidate list and a sequence starts with no keypoints from outside.
+    detector=None is the loop with the application's own candidates."""
 
     RING = 4   # pinned input blocks: one is rewritten only after the copy that read it, four frames earlier, has run
 
     def __init__(self, params: capi.Params, width: int, height: int, cap: int, target_n: int, new_point_ratio: float,
-                 fit_params: "capi.FitParams | None" = None, *, device: int = 0, cand_cap: int = 1024, sigma: float = 1.0):
+                 fit_params: "capi.FitParams | None" = None, *, device: int = 0, cand_cap: int = 1024, sigma: float = 1.0,
+                 detector: "capi.DetectParams | None" = None):
         if not torch.cuda.is_available():
             raise RuntimeError("SequenceTracker needs a HIP device (torch.cuda.is_available() is False)")
-        if cap < target_n or target_n < 1 or cand_cap < 1:
+        if cap < target_n or target_n < 1 or (detector is None and cand_cap < 1):
             raise ValueError("cap >= target_n >= 1 and cand_cap >= 1 are required")
-        self.params, self.fit_params, self.sigma = params, fit_params, float(sigma)
+        self.params, self.fit_params, self.sigma, self.detector = params, fit_params, float(sigma), detector
         self.w, self.h, self.cap, self.target_n, self.cand_cap = int(width), int(height), int(cap), int(target_n), int(cand_cap)
         self.threshold = float(target_n * new_point_ratio)
         self.dev = torch.device("cuda", device)
@@ -539,7 +548,9 @@ class SequenceTracker:
         self.ctx.set_stream(self.main.cuda_stream)
         u8, f32, f64, i32 = torch.uint8, torch.float32, torch.float64, torch.int32
         n = self.cap
-        self._in_fields = [("img", u8, self.h, self.w), ("rot", f32, 9, 1), ("n_cand", i32, 1, 1), ("cand", f32, self.cand_cap, 2)]
+        self._in_fields = [("img", u8, self.h, self.w), ("rot", f32, 9, 1)]
+        if detector is None:   # with a detector no candidate list exists: the input block is the image and the rotation
+            self._in_fields += [("n_cand", i32, 1, 1), ("cand", f32, self.cand_cap, 2)]
         nbytes = _carve_size(self._in_fields)
         self._d_in_buf = torch.zeros(nbytes, dtype=u8, device=self.dev)
         self.d_in = _carve(self._d_in_buf, self._in_fields)
@@ -560,6 +571,7 @@ class SequenceTracker:
         self.wk["aff"].copy_(torch.tensor([1.0, 0.0, 0.0, 1.0], device=self.dev).repeat(n, 1))
         self.out = {k: self.wk[k] for k in ("pt_un", "pt_dist", "status", "pix_err", "dist_pred")}
         self.state = torch.zeros(capi.HANDOVER_STATE_WORDS, dtype=i32, device=self.dev)
+        self.info = torch.zeros(capi.DETECT_INFO_WORDS, dtype=i32, device=self.dev) if detector is not None else None
         torch.cuda.synchronize(self.dev)
         self.frame = -1          # index of the last frame handed in
         self._turn = 0
@@ -587,16 +599,23 @@ class SequenceTracker:
         pv["img"].numpy()[...] = img
         if rot9 is not None:
             pv["rot"].numpy()[...] = np.asarray(rot9, np.float32).reshape(9)
-        cand = np.asarray(candidates, np.float32).reshape(-1, 2) if candidates is not None else np.zeros((0, 2), np.float32)
-        if cand.shape[0] > self.cand_cap:
-            raise ValueError("more candidates than cand_cap")
-        pv["cand"].numpy()[:cand.shape[0]] = cand
-        pv["n_cand"].numpy()[0] = cand.shape[0]
+        if self.detector is None:
+            cand = np.asarray(candidates, np.float32).reshape(-1, 2)
+            if cand.shape[0] > self.cand_cap:
+                raise ValueError("more candidates than cand_cap")
+            pv["cand"].numpy()[:cand.shape[0]] = cand
+            pv["n_cand"].numpy()[0] = cand.shape[0]
         self._d_in_buf.copy_(self._pinned[k], non_blocking=True)
         self._pinned_free[k] = _event_on(self.main)
 
     # -- the frame's launches ----------------------------------------------------------------------------------
-    def _handover(self, status, pp, ppu, dst):
+    def _handover(self, status, pp, ppu, dst, slot: int):
+        if self.detector is not None:   # the candidates are detected on the frame in `slot`, under this call's mask
+            self.ctx.frame_handover_detect_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold,
+                                                  status, pp, ppu, self.detector, slot, dst["keys"], dst["keys_un"],
+                                                  dst["keys_normal"], dst["index_in_last"], dst["live"], None,
+                                                  self.state, self.info)
+            return
         self.ctx.frame_handover_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold, status, pp, ppu,
                                        self.cand_cap, self.d_in["n_cand"], self.d_in["cand"], dst["keys"], dst["keys_un"],
                                        dst["keys_normal"], dst["index_in_last"], dst["live"], None, self.state)
@@ -618,36 +637,50 @@ class SequenceTracker:
         if self.fit_params is not None:
             c.geometry_validation_device(self.fit_params, self.cap, ref["keys_un"], wk["ppu"], wk["st"], self.sigma,
                                          wk["cnt"], wk["score"])
-        self._handover(wk["st"], wk["pp"], wk["ppu"], dst)
+        self._handover(wk["st"], wk["pp"], wk["ppu"], dst, p)
 
     def _result(self, p: int, snapshot: bool) -> FrameResult:
         if snapshot:   # two device-to-device copies: the set's block and the state words
             t = _carve(self._set_bufs[p].clone(), self._set_fields)
             t["state"] = self.state.clone()
+            if self.info is not None:
+                t["info"] = self.info.clone()
         else:          # views: valid until the frame after next rewrites this set
             t = dict(self.sets[p])
             t["state"] = self.state
+            if self.info is not None:
+                t["info"] = self.info
         return FrameResult(t, _event_on(self.main), self.side, snapshot)
 
-    def start(self, img, candidates, snapshot: bool = True) -> FrameResult:
+    def _check_list(self, candidates):
+        """A candidate list is required without a detector (an empty array for "none") and refused with one."""
+        if self.detector is not None and candidates is not None:
+            raise ValueError("this tracker detects its own keypoints (detector=...): pass no candidate list")
+        if self.detector is None and candidates is None:
+            raise TypeError("a tracker without a detector needs the frame's candidate list (an empty array for none)")
+
+    def start(self, img, candidates=None, snapshot: bool = True) -> FrameResult:
         """The first frame (Examples/Demo/RealSenseD435i.cpp:221-235): its pyramid into slot 0, and the first-frame
-        hand-over -- an all-zero status -- takes the first target_n in-image candidates into key set 0."""
+        hand-over -- an all-zero status -- takes the first target_n in-image candidates into key set 0 (with a
+        detector: the target_n strongest corners of the frame that keep their distance)."""
+        self._check_list(candidates)
         with torch.cuda.stream(self.main):
             self.state.zero_()
             self._feed(img, None, candidates)
             self.ctx.frame_set_device(0, self.d_in["img"].data_ptr(), self.w, self.h, self.w, self.params.pyramids)
-            self._handover(self.wk["zero"], self.wk["pp"], self.wk["ppu"], self.sets[0])
+            self._handover(self.wk["zero"], self.wk["pp"], self.wk["ppu"], self.sets[0], 0)
             self.frame = 0
             self.mode_used = "direct"
             return self._result(0, snapshot)
 
-    def step(self, img, rot9, candidates, mode: str = "graph", snapshot: bool = True) -> FrameResult:
+    def step(self, img, rot9, candidates=None, mode: str = "graph", snapshot: bool = True) -> FrameResult:
         """Frame k >= 1: tracks pair (k-1, k) and hands over to pair (k, k+1).  rot9 = rows 0 and 1 of K R K^-1 followed
         by the third row of R (pagk_gyro_predict_device_rot).  Nothing is synchronised; the result carries its event."""
         if self.frame < 0:
             raise RuntimeError("start() hands in the first frame")
         if mode not in ("graph", "direct"):
             raise ValueError(mode)
+        self._check_list(candidates)
         k = self.frame + 1
         p = k & 1
         with torch.cuda.stream(self.main):
