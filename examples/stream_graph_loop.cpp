@@ -15,11 +15,18 @@
 // the current frame under the mask the hand-over has just built.  The file's keypoints then only give the count
 // (target_n); no candidate list goes to the device at all, and each line also tells how many corners were added.
 //
+// --rectify puts the camera's lens in front of the loop (reference Examples/Demo/RealSenseD435i.cpp:202: cv::remap on every
+// frame): the file's images are taken for the ideal view, the program synthesises the DISTORTED frames a real lens would
+// deliver (the inverse of the file's Brown-Conrady model, by fixed-point iteration, applied with pagk_rectify), and the
+// loop then feeds those raw frames: pagk_frame_rectify_device (maps from pagk_undistort_maps, set once) replaces
+// pagk_frame_set_device inside each graph.  The same lines are printed.  --detect and --rectify combine.
+//
 // Input: the file of stream_resident.cpp.
 // Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I /opt/rocm/include -I include examples/stream_graph_loop.cpp
 //        -L <pkg> -l:libpagk_hip.so -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,<pkg> -Wl,-rpath,/opt/rocm/lib
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -53,15 +60,15 @@ struct KeySet {
 
 int main(int argc, char **argv)
 {
-    bool detect = false;
+    bool detect = false, rectify = false;
     for (int k = 1; k < argc; k++)
-        if (!std::strcmp(argv[k], "--detect")) {
-            detect = true;
+        if (!std::strcmp(argv[k], "--detect") || !std::strcmp(argv[k], "--rectify")) {
+            (argv[k][2] == 'd' ? detect : rectify) = true;
             for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
             argc--, k--;
         }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s [--detect] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--detect] [--rectify] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
         return 2;
     }
     const int half = argc > 2 ? std::atoi(argv[2]) : 5, iters = argc > 3 ? std::atoi(argv[3]) : 10,
@@ -98,6 +105,42 @@ int main(int argc, char **argv)
     p.fx = K[0], p.fy = K[4], p.cx = K[2], p.cy = K[5];
     p.n_dist_coef = 4;
     for (int k = 0; k < 4; k++) p.dist_coef[k] = dist[k];
+
+    pagk_rectify_params rp;
+    pagk_rectify_params_default(&rp);   // one channel
+    if (rectify) {
+        // the distorted frames: raw(u, v) = ideal(K x), x the undistorted normalised point of (u, v) -- five rounds of
+        // x <- (x_d - tangential(x)) / radial(x), cv::undistortPoints' iteration -- sampled with the library's own remap
+        const size_t px = (size_t)w * h;
+        std::vector<float> mx(px), my(px);
+        const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3];
+        for (int v = 0; v < h; v++)
+            for (int u = 0; u < w; u++) {
+                const double xd = (u - K[2]) / K[0], yd = (v - K[5]) / K[4];
+                double x = xd, y = yd;
+                for (int it = 0; it < 5; it++) {
+                    const double r2 = x * x + y * y, kr = 1.0 + (k2 * r2 + k1) * r2;
+                    x = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / kr;
+                    y = (yd - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) / kr;
+                }
+                mx[(size_t)v * w + u] = (float)(K[0] * x + K[2]);
+                my[(size_t)v * w + u] = (float)(K[4] * y + K[5]);
+            }
+        CHECK_PAGK(pagk_rectify_set_maps(ctx, mx.data(), my.data(), w, h, (int64_t)w * 4));
+        std::vector<unsigned char> raw(px);
+        for (auto &im : img) {
+            CHECK_PAGK(pagk_rectify(ctx, &rp, im.data(), w, h, w, raw.data(), w));
+            im = raw;
+        }
+        // ... and the maps the loop rectifies them with: initUndistortRectifyMap of the same camera (include/imu_types.h:60-65)
+        const double d4[4] = {k1, k2, p1, p2};
+        CHECK_PAGK(pagk_undistort_maps(K[0], K[4], K[2], K[5], d4, 4, K[0], K[4], K[2], K[5], w, h, mx.data(), my.data()));
+        CHECK_PAGK(pagk_rectify_set_maps(ctx, mx.data(), my.data(), w, h, (int64_t)w * 4));
+    }
+    // a frame into a slot: the image as it is, or the raw frame through the maps
+    auto frame_into = [&](int slot, const unsigned char *d_img) -> int {
+        return rectify ? pagk_frame_rectify_device(ctx, slot, &rp, d_img, w, h, w, pyr) : pagk_frame_set_device(ctx, slot, d_img, w, h, w, pyr);
+    };
 
     // everything a frame touches lives at a fixed device address; the capacity is the initial keypoint count
     const int32_t cap = nk;
@@ -153,7 +196,7 @@ int main(int argc, char **argv)
     CHECK_HIP(hipMemcpy(d_cand, kp.data(), n8, hipMemcpyHostToDevice));
     CHECK_HIP(hipMemcpy(d_ncand, &n_cand, 4, hipMemcpyHostToDevice));
     CHECK_HIP(hipMemcpy(d_frame, img[0].data(), (size_t)w * h, hipMemcpyHostToDevice));
-    CHECK_PAGK(pagk_frame_set_device(ctx, 0, d_frame, w, h, w, pyr));
+    CHECK_PAGK(frame_into(0, d_frame));
     if (detect)
         CHECK_PAGK(pagk_frame_handover_detect_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &det, 0,
                                                      ks[0].keys, ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last,
@@ -168,7 +211,7 @@ int main(int argc, char **argv)
 
     auto frame_work = [&](int par) -> int {  // frame slot `par` = current, key set 1 - par = reference keypoints
         const KeySet &ref = ks[1 - par], &dst = ks[par];
-        CHECK_PAGK(pagk_frame_set_device(ctx, par, d_frame, w, h, w, pyr));
+        CHECK_PAGK(frame_into(par, d_frame));
         CHECK_PAGK(pagk_gyro_predict_device_live(ctx, &p, w, h, d_rot, cap, ref.keys_un, ref.live, d_pu, d_pd, d_st_in,
                                                  d_aff));
         CHECK_PAGK(pagk_track_device(ctx, &p, 1 - par, par, cap, ref.keys_un, d_pu, d_aff, d_st_in, &d_out));

@@ -161,7 +161,8 @@ int pagk_frame_set_device(pagk_ctx *ctx, int32_t slot, const void *d_data, int32
  * dimension, more than four levels) make the call k per-context launches.  k <= 64. */
 int pagk_frame_set_device_batch(pagk_ctx *const *ctxs, int32_t k, const int32_t *slot, const void *const *d_data,
                                 const int32_t *width, const int32_t *height, const int64_t *step, int32_t pyramids);
-/* Copy one pyramid level of a slot back to the host (tests: pyramid parity). */
+/* Copy one pyramid level of a slot back to the host (tests: pyramid parity).  Level 0 is the image the pyramid was built
+ * from: the slot's own copy, or the caller's device image where the slot reads it in place. */
 int pagk_frame_download_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst,
                               int32_t *width, int32_t *height);
 
@@ -451,6 +452,79 @@ int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t
  * mismatch to the first stage of the detector (src/frame.cpp:156-218 has no counterpart: OpenCV keeps the map inside). */
 int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R);
 
+/* ---- rectification: a raw camera frame into a frame slot ------------------------------------------------------------ */
+/* Both front-ends of the reference rectify every frame with
+ *     cv::remap(image_cur_distort, image_cur, M1, M2, cv::INTER_LINEAR)
+ * (Examples/Demo/RealSenseD435i.cpp:202, Examples/ROS/.../feature_tracker.cpp:137; M1, M2 = the CV_32F planes of
+ * cv::initUndistortRectifyMap, include/imu_types.h:60-65) and Frame::Frame turns a 3- or 4-channel image into mGray
+ * (src/frame.cpp:81-87).  These entry points do both on the device, in one pass.
+ * Parity contract: OpenCV is third-party and its SIMD paths are not restated here, so parity with OpenCV's bytes is NOT
+ * pinned.  The contract is this definition, bit for bit (restated in plain C in tests/rectify_ref.c).  It follows OpenCV
+ * 3.4's remap for 8-bit images, INTER_LINEAR, planar CV_32FC1 maps, BORDER_CONSTANT with value 0, and its 8-bit RGB2GRAY,
+ * step by step, and says where it is the library's own rule.  After one exact float step everything is integer arithmetic.
+ * For destination pixel (r, c) of a W x H map pair and a source of Ws x Hs pixels with cn interleaved channels:
+ *   fixed point  sx = rne(map_x[r][c] * 32), sy = rne(map_y[r][c] * 32): the float product is exact (a power of two), rne
+ *                is round to nearest, ties to even (cvRound).
+ *   split        ix = sat_i16(sx >> 5), fx = sx & 31, likewise iy, fy: the shift is arithmetic and the mask acts on the
+ *                two's-complement value, so negative coordinates floor (-0.25 is ix = -1, fx = 24).
+ *   taps         (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1); a tap outside [0, Ws) x [0, Hs) is 0.
+ *   interpolate  per channel v = (p00 (32-fx)(32-fy) + p01 fx (32-fy) + p10 (32-fx) fy + p11 fx fy + 512) >> 10.  This is
+ *                OpenCV's table form (sum of p * w * 32 + (1 << 14)) >> 15 with w the four products above; the one weight
+ *                OpenCV saturates to 16 bits (32768 -> 32767, at fx = fy = 0) gives the same byte for every p <= 255
+ *                ((p * 32767 + 16384) >> 15 = p), so the two forms agree on every input.
+ *   no pixel     a non-finite map value, or one with |map * 32| >= 2^31, gives pixel 0 (the library's own rule: cvRound
+ *                of such a value is undefined).
+ *   limits       Ws, Hs <= 32767 (16-bit tap coordinates); larger: PAGK_E_ARG.
+ *   gray         cn == 1: the byte is v.  cn == 3 or 4: the remap runs first, per channel, and the conversion follows it,
+ *                as in the reference: gray = (v0 w0 + v1 w1 + v2 w2 + (1 << (shift - 1))) >> shift; channel 3 is ignored.
+ * pagk_rectify_params carries the last step.  The defaults are 4899, 9617, 1868 and 14: CV_RGB2GRAY on channel order R, G,
+ * B in OpenCV 3.4 (a BGR frame passes them reversed).  A host built against another OpenCV passes its own weights -- the
+ * same idea as pagk_params::solver_variant.  For channels 3 and 4 the weights must be non-negative and sum to 1 << shift
+ * with 1 <= shift <= 15 (the gray byte then never exceeds 255); channels == 1 does not read them.  Others: PAGK_E_ARG. */
+typedef struct pagk_rectify_params {
+    int32_t channels;       /* cn: 1, 3 or 4 interleaved bytes per source pixel */
+    int32_t gray_weight[3]; /* w0 w1 w2, applied to channels 0 1 2              */
+    int32_t gray_shift;     /* shift                                            */
+} pagk_rectify_params;
+/* channels 1; 4899, 9617, 1868; 14 */
+void pagk_rectify_params_default(pagk_rectify_params *p);
+/* PAGK_OK if the rules above hold for *p, PAGK_E_ARG otherwise (needs no device). */
+int pagk_rectify_params_check(const pagk_rectify_params *p);
+/* The maps: host pointers to two float planes of width x height, rows step_bytes apart (M1, M2 of the reference, or the
+ * planes pagk_undistort_maps fills).  Converted ONCE into a packed entry per pixel (ix, iy, fx, fy: 8 bytes) in device
+ * memory the context owns.  Synchronous; PAGK_E_ARG inside a capture.  Maps of another size can only be set while no
+ * graph of the context is alive (its nodes hold the old pointer). */
+int pagk_rectify_set_maps(pagk_ctx *ctx, const float *map_x, const float *map_y, int32_t width, int32_t height,
+                          int64_t step_bytes);
+/* The raw frame d_raw (DEVICE memory: src_height rows of src_step bytes, src_width pixels of params->channels bytes)
+ * is rectified into frame slot `slot`, then the slot's pyramid is built as pagk_frame_upload builds it.  The rectified
+ * image goes into the slot's own level-0 buffer: from then on the slot cannot be told from one filled by pagk_frame_upload
+ * of the rectified image (a continuous image of the maps' size), and -- unlike a slot set with pagk_frame_set_device -- it
+ * does not depend on the caller's buffer any longer, so pagk_detect_corners_device may run on it at any time.
+ * Asynchronous on the context stream, capturable (run the same call once before capturing).  PAGK_E_ARG, with a text in
+ * pagk_last_error: no maps set; the slot holds a frame of another size than the maps; channels not 1, 3 or 4 (or bad
+ * weights); src_step < src_width * channels; a source dimension beyond 32767. */
+int pagk_frame_rectify_device(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *d_raw,
+                              int32_t src_width, int32_t src_height, int64_t src_step, int32_t pyramids);
+/* The same for a raw frame in PINNED host memory (a camera ring buffer): it is copied into a staging buffer the context
+ * owns (sized by a call outside a capture), then rectified.  Asynchronous and capturable like pagk_frame_upload_pinned. */
+int pagk_frame_rectify_pinned(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *raw,
+                              int32_t src_width, int32_t src_height, int64_t src_step, int32_t pyramids);
+/* Host buffers, synchronous: the rectified gray image (the maps' size, rows dst_step bytes apart) into dst. */
+int pagk_rectify(pagk_ctx *ctx, const pagk_rectify_params *params, const void *raw, int32_t src_width, int32_t src_height,
+                 int64_t src_step, uint8_t *dst, int64_t dst_step);
+/* Host helper, run once: the maps of cv::initUndistortRectifyMap(K, dist, R = I, newK, size, CV_32FC1) for the Brown-Conrady
+ * model (dist_coef = k1 k2 p1 p2 [k3], n_dist_coef 0, 4 or 5).  This is the library's OWN definition -- an application
+ * with OpenCV passes its M1 / M2 to pagk_rectify_set_maps --: a closed form per pixel in f64 (OpenCV walks running sums),
+ * one rounding per operation, in this order, for pixel (r, c):
+ *   x = (c - new_cx) / new_fx, y = (r - new_cy) / new_fy, x2 = x x, y2 = y y, r2 = x2 + y2, xy2 = (2 x) y,
+ *   kr = 1 + ((k3 r2 + k2) r2 + k1) r2, xd = (x kr + p1 xy2) + p2 (r2 + 2 x2), yd = (y kr + p1 (r2 + 2 y2)) + p2 xy2,
+ *   map_x = (float)(fx xd + cx), map_y = (float)(fy yd + cy).
+ * map_x, map_y: width * height floats each, dense.  No device needed. */
+int pagk_undistort_maps(double fx, double fy, double cx, double cy, const double *dist_coef, int32_t n_dist_coef,
+                        double new_fx, double new_fy, double new_cx, double new_cy, int32_t width, int32_t height,
+                        float *map_x, float *map_y);
+
 /* Diagnostics (never on the tracking path): the arithmetic of H.llt().solve(b) / update.norm()
  * (src/patch_match.cpp:319,343) on the caller's operands, so that a host can check on its own device -- and, with
  * Eigen at hand, against its own Eigen -- what pagk_params::solver_variant selects.
@@ -476,7 +550,8 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
  * pagk_graph_end the *_device entry points (pagk_frame_set_device, pagk_gyro_predict_device[_rot],
  * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
- * pagk_frame_handover_detect_device) are recorded on the context stream instead of executed,
+ * pagk_frame_handover_detect_device, pagk_frame_rectify_device; and the pinned-memory forms pagk_frame_upload_pinned,
+ * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while
  * capturing; the context stream must not be the legacy default stream; the kernel timers

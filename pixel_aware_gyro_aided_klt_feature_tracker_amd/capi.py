@@ -54,6 +54,11 @@ class DetectParams(C.Structure):
                 ("raw_cap", C.c_int32)]
 
 
+class RectifyParams(C.Structure):
+    """pagk_rectify_params (include/pagk.h): source channels and the integer RGB-to-gray step behind the remap."""
+    _fields_ = [("channels", C.c_int32), ("gray_weight", C.c_int32 * 3), ("gray_shift", C.c_int32)]
+
+
 DETECT_INFO_WORDS = 8
 DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
 FIT_INFO_WORDS = 12
@@ -225,6 +230,21 @@ def declare(lib) -> None:
                                                    _P(DetectParams), _P(Image), vp, vp, vp, vp, vp, vp, vp, vp]
         lib.pagk_selftest_corner_response.restype = C.c_int
         lib.pagk_selftest_corner_response.argtypes = [vp, _P(Image), vp]
+    if hasattr(lib, "pagk_frame_rectify_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_rectify_params_default.restype = None
+        lib.pagk_rectify_params_default.argtypes = [_P(RectifyParams)]
+        lib.pagk_rectify_params_check.restype = C.c_int
+        lib.pagk_rectify_params_check.argtypes = [_P(RectifyParams)]
+        lib.pagk_rectify_set_maps.restype = C.c_int
+        lib.pagk_rectify_set_maps.argtypes = [vp, vp, vp, i32, i32, C.c_int64]
+        for name in ("pagk_frame_rectify_device", "pagk_frame_rectify_pinned"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [vp, i32, _P(RectifyParams), vp, i32, i32, C.c_int64, i32]
+        lib.pagk_rectify.restype = C.c_int
+        lib.pagk_rectify.argtypes = [vp, _P(RectifyParams), vp, i32, i32, C.c_int64, vp, C.c_int64]
+        f64 = C.c_double
+        lib.pagk_undistort_maps.restype = C.c_int
+        lib.pagk_undistort_maps.argtypes = [f64, f64, f64, f64, vp, i32, f64, f64, f64, f64, i32, i32, vp, vp]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -328,6 +348,8 @@ EXPORTED_SYMBOLS = [
     "pagk_post_filter_device", "pagk_gyro_predict_device_live", "pagk_frame_handover_device", "pagk_frame_handover",
     "pagk_detect_params_default", "pagk_detect_corners_device", "pagk_detect_corners",
     "pagk_frame_handover_detect_device", "pagk_frame_handover_detect", "pagk_selftest_corner_response",
+    "pagk_rectify_params_default", "pagk_rectify_params_check", "pagk_rectify_set_maps", "pagk_frame_rectify_device",
+    "pagk_frame_rectify_pinned", "pagk_rectify", "pagk_undistort_maps",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -354,6 +376,32 @@ def detect_params_default(**overrides) -> DetectParams:
             raise TypeError(f"pagk_detect_params has no field {k}")
         setattr(p, k, v)
     return p
+
+
+def rectify_params_default(**overrides) -> RectifyParams:
+    """pagk_rectify_params_default() with overrides (channels, gray_weight = three integers, gray_shift)."""
+    p = RectifyParams()
+    load().pagk_rectify_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(RectifyParams._fields_):
+            raise TypeError(f"pagk_rectify_params has no field {k}")
+        if k == "gray_weight":
+            v = (C.c_int32 * 3)(*[int(x) for x in v])
+        setattr(p, k, v)
+    return p
+
+
+def undistort_maps(fx, fy, cx, cy, dist, width: int, height: int, new_camera=None):
+    """pagk_undistort_maps (host, no device): the float32 planes map_x, map_y (height x width) of the Brown-Conrady camera
+    (fx fy cx cy, dist = k1 k2 p1 p2 [k3]) seen through new_camera = (fx, fy, cx, cy), the same camera by default."""
+    d = np.ascontiguousarray(dist, np.float64).ravel()
+    nfx, nfy, ncx, ncy = new_camera if new_camera is not None else (fx, fy, cx, cy)
+    mx, my = np.zeros((height, width), np.float32), np.zeros((height, width), np.float32)
+    rc = load().pagk_undistort_maps(fx, fy, cx, cy, d.ctypes.data if d.size else None, int(d.size), nfx, nfy, ncx, ncy,
+                                    int(width), int(height), mx.ctypes.data, my.ctypes.data)
+    if rc != PAGK_OK:
+        raise PagkError(rc, "pagk_undistort_maps")
+    return mx, my
 
 
 def load():
@@ -845,6 +893,45 @@ class Context:
             _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
             "pagk_frame_handover_detect")
         return out
+
+    # rectification: a raw camera frame (distorted, 1 / 3 / 4 channels) into a frame slot ----
+    def rectify_set_maps(self, map_x: np.ndarray, map_y: np.ndarray):
+        """pagk_rectify_set_maps: two float32 planes of one shape (rows may be strided, elements not)."""
+        if map_x.dtype != np.float32 or map_y.dtype != np.float32 or map_x.ndim != 2 or map_x.shape != map_y.shape:
+            raise ValueError("the maps are two float32 planes of one shape")
+        if map_x.strides != map_y.strides or map_x.strides[1] != 4:
+            raise ValueError("the maps must share one row step and have dense rows")
+        self._check(self.lib.pagk_rectify_set_maps(self.h, map_x.ctypes.data, map_y.ctypes.data, map_x.shape[1],
+                                                   map_x.shape[0], map_x.strides[0]), "pagk_rectify_set_maps")
+        self._rect_shape = map_x.shape
+
+    def frame_rectify_device(self, slot: int, rp: RectifyParams, d_raw_ptr: int, src_width: int, src_height: int,
+                             src_step: int, pyramids: int):
+        """pagk_frame_rectify_device: raw frame in device memory -> rectified gray level 0 of `slot` -> its pyramid
+        (asynchronous, capturable)."""
+        self._check(self.lib.pagk_frame_rectify_device(self.h, slot, C.byref(rp), d_raw_ptr, src_width, src_height,
+                                                       src_step, pyramids), "pagk_frame_rectify_device")
+
+    def frame_rectify_pinned(self, slot: int, rp: RectifyParams, host_ptr: int, src_width: int, src_height: int,
+                             src_step: int, pyramids: int):
+        """pagk_frame_rectify_pinned: the same for a raw frame in pinned host memory (asynchronous, capturable)."""
+        self._check(self.lib.pagk_frame_rectify_pinned(self.h, slot, C.byref(rp), host_ptr, src_width, src_height,
+                                                       src_step, pyramids), "pagk_frame_rectify_pinned")
+
+    def rectify(self, rp: RectifyParams, raw: np.ndarray) -> np.ndarray:
+        """pagk_rectify, host buffers: raw is Hs x Ws (channels 1) or Hs x Ws x channels uint8, rows may be strided;
+        returns the rectified gray image of the maps' size (rectify_set_maps)."""
+        cn = int(rp.channels)
+        if raw.dtype != np.uint8 or raw.ndim not in (2, 3) or (raw.ndim == 3 and raw.shape[2] != cn) or (raw.ndim == 2 and cn != 1):
+            raise ValueError("raw must be uint8, Hs x Ws or Hs x Ws x channels")
+        if raw.strides[-1] != 1 or (raw.ndim == 3 and raw.strides[1] != cn):
+            raise ValueError("the pixels of a row must be dense")
+        if not getattr(self, "_rect_shape", None):
+            raise ValueError("rectify_set_maps first")
+        dst = np.zeros(self._rect_shape, np.uint8)
+        self._check(self.lib.pagk_rectify(self.h, C.byref(rp), raw.ctypes.data, raw.shape[1], raw.shape[0], raw.strides[0],
+                                          dst.ctypes.data, dst.strides[0]), "pagk_rectify")
+        return dst
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------
     def graph_begin(self):

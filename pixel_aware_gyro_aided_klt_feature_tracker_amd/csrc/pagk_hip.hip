@@ -55,6 +55,12 @@ struct pagk_ctx {
     FeatBuf hand;   // the frame hand-over's own mask (pagk_handover_kernel.h): sized outside captures, pointed into by graphs
     FeatBuf handio; // scratch of the host-buffer hand-over
     FeatBuf det;    // workspace of the corner detector (pagk_detect_kernel.h): sized outside captures, pointed into by graphs
+    // rectification (pagk_rectify_kernel.h): the packed map entries of pagk_rectify_set_maps and the staging buffer of the raw
+    // frame of the pinned / host-buffer forms; both sized outside captures, pointed into by graphs
+    void *rect_entries = nullptr;
+    int rect_w = 0, rect_h = 0, rect_wp = 0;
+    void *rect_stage = nullptr;
+    size_t rect_stage_bytes = 0;
     void *quad_ws = nullptr;  // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
     size_t quad_ws_bytes = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
@@ -1217,6 +1223,8 @@ void pagk_destroy(pagk_ctx *ctx)
     if (ctx->hand.block) (void)hipFree(ctx->hand.block);
     if (ctx->handio.block) (void)hipFree(ctx->handio.block);
     if (ctx->det.block) (void)hipFree(ctx->det.block);
+    if (ctx->rect_entries) (void)hipFree(ctx->rect_entries);
+    if (ctx->rect_stage) (void)hipFree(ctx->rect_stage);
     if (ctx->quad_ws) (void)hipFree(ctx->quad_ws);
     if (ctx->susp) (void)hipFree(ctx->susp);
     if (ctx->queue) (void)hipFree(ctx->queue);
@@ -1486,16 +1494,252 @@ int pagk_frame_set_device_batch(pagk_ctx *const *ctxs, int32_t k, const int32_t 
     return PAGK_OK;
 }
 
+// ---- rectification: cv::remap + RGB-to-gray of a raw camera frame into a frame slot (include/pagk.h "rectification") ----
+void pagk_rectify_params_default(pagk_rectify_params *p)
+{
+    if (!p) return;
+    p->channels = 1;
+    p->gray_weight[0] = 4899, p->gray_weight[1] = 9617, p->gray_weight[2] = 1868;   // CV_RGB2GRAY on R, G, B (OpenCV 3.4)
+    p->gray_shift = 14;
+}
+
+int pagk_rectify_params_check(const pagk_rectify_params *p)
+{
+    if (!p) return PAGK_E_ARG;
+    if (p->channels != 1 && p->channels != 3 && p->channels != 4) return PAGK_E_ARG;
+    if (p->channels == 1) return PAGK_OK;   // (no gray step: the weights are not read)
+    if (p->gray_shift < 1 || p->gray_shift > 15) return PAGK_E_ARG;
+    int64_t sum = 0;
+    for (int k = 0; k < 3; k++) {
+        if (p->gray_weight[k] < 0) return PAGK_E_ARG;
+        sum += p->gray_weight[k];
+    }
+    return sum == (int64_t)1 << p->gray_shift ? PAGK_OK : PAGK_E_ARG;
+}
+
+int pagk_undistort_maps(double fx, double fy, double cx, double cy, const double *dist_coef, int32_t n_dist_coef,
+                        double new_fx, double new_fy, double new_cx, double new_cy, int32_t width, int32_t height,
+                        float *map_x, float *map_y)
+{
+    if (!map_x || !map_y || width < 1 || height < 1 || (n_dist_coef != 0 && n_dist_coef != 4 && n_dist_coef != 5)) return PAGK_E_ARG;
+    if (n_dist_coef > 0 && !dist_coef) return PAGK_E_ARG;
+    if (!std::isfinite(new_fx) || !std::isfinite(new_fy) || new_fx == 0.0 || new_fy == 0.0) return PAGK_E_ARG;
+    const double k1 = n_dist_coef >= 4 ? dist_coef[0] : 0.0, k2 = n_dist_coef >= 4 ? dist_coef[1] : 0.0;
+    const double p1 = n_dist_coef >= 4 ? dist_coef[2] : 0.0, p2 = n_dist_coef >= 4 ? dist_coef[3] : 0.0;
+    const double k3 = n_dist_coef >= 5 ? dist_coef[4] : 0.0;
+    for (int32_t r = 0; r < height; r++)
+        for (int32_t c = 0; c < width; c++) {
+            // one rounding per operation, in exactly this order (the build never contracts a * b + c)
+            const double x = ((double)c - new_cx) / new_fx, y = ((double)r - new_cy) / new_fy;
+            const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = (2.0 * x) * y;
+            const double kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
+            const double xd = (x * kr + p1 * xy2) + p2 * (r2 + 2.0 * x2);
+            const double yd = (y * kr + p1 * (r2 + 2.0 * y2)) + p2 * xy2;
+            map_x[(size_t)r * width + c] = (float)(fx * xd + cx);
+            map_y[(size_t)r * width + c] = (float)(fy * yd + cy);
+        }
+    return PAGK_OK;
+}
+
+namespace {
+
+// sx = rne(m * 32) of the definition -> *s; false = "no pixel" (non-finite, or |m * 32| >= 2^31)
+bool rect_fixed(float m, int32_t *s)
+{
+    const float p = m * 32.0f;                       // exact (a power of two), or +-inf
+    if (!(std::fabs(p) < 2147483648.0f)) return false;   // (NaN fails the comparison too)
+    *s = (int32_t)std::nearbyintf(p);                // round to nearest, ties to even (the default rounding mode)
+    return true;
+}
+
+inline int32_t sat_i16(int32_t v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+int rect_check_src(pagk_ctx *ctx, const pagk_rectify_params *params, int32_t sw, int32_t sh, int64_t sstep, const char *what)
+{
+    if (pagk_rectify_params_check(params) != PAGK_OK) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: channels must be 1, 3 or 4; for 3 and 4 the gray weights must be non-negative and sum to 1 << gray_shift, 1 <= gray_shift <= 15", what);
+        return PAGK_E_ARG;
+    }
+    if (!ctx->rect_entries) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: no maps set (pagk_rectify_set_maps)", what);
+        return PAGK_E_ARG;
+    }
+    if (sw < 1 || sh < 1 || sw > 32767 || sh > 32767) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: source %d x %d: both dimensions must be in 1 .. 32767 (16-bit tap coordinates)", what, sw, sh);
+        return PAGK_E_ARG;
+    }
+    if (sstep < (int64_t)sw * params->channels) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: src_step %lld is less than src_width * channels = %lld", what, (long long)sstep, (long long)sw * params->channels);
+        return PAGK_E_ARG;
+    }
+    return PAGK_OK;
+}
+
+// the kernel: d_raw -> dst (rect_w x rect_h bytes, pitch rect_w); arguments checked by the caller
+int rect_launch(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_raw, int32_t sw, int32_t sh, int64_t sstep,
+                uint8_t *dst)
+{
+    RectArgs a;
+    a.entries = static_cast<const RectEntry *>(ctx->rect_entries);
+    a.src = static_cast<const uint8_t *>(d_raw);
+    a.dst = dst;
+    a.src_step = sstep;
+    a.W = ctx->rect_w, a.H = ctx->rect_h, a.wp = ctx->rect_wp, a.Ws = sw, a.Hs = sh;
+    a.gw0 = params->gray_weight[0], a.gw1 = params->gray_weight[1], a.gw2 = params->gray_weight[2], a.gshift = params->gray_shift;
+    const long long threads = (long long)(a.wp >> 2) * a.H;
+    const dim3 grd((unsigned)((threads + 255) / 256)), blk(256);
+    const bool pair = sw >= 2;   // the two-taps-per-load form needs a second pixel in every source row
+    if (params->channels == 1) {
+        if (pair) hipLaunchKernelGGL((k_rectify<1, true>), grd, blk, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_rectify<1, false>), grd, blk, 0, ctx->stream, a);
+    } else if (params->channels == 3) {
+        if (pair) hipLaunchKernelGGL((k_rectify<3, true>), grd, blk, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_rectify<3, false>), grd, blk, 0, ctx->stream, a);
+    } else {
+        if (pair) hipLaunchKernelGGL((k_rectify<4, true>), grd, blk, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_rectify<4, false>), grd, blk, 0, ctx->stream, a);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// the context's staging buffer for a raw frame that arrives from the host
+int rect_stage_reserve(pagk_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->rect_stage_bytes) return PAGK_OK;
+    if (in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "the raw frame's staging buffer would have to be allocated during graph capture: issue the same call once before capturing");
+        return PAGK_E_ARG;
+    }
+    int rc = no_live_graphs(ctx, "the raw frame's staging buffer");
+    if (rc) return rc;
+    if (ctx->rect_stage) HIPCHK(ctx, hipFree(ctx->rect_stage));
+    ctx->rect_stage = nullptr, ctx->rect_stage_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->rect_stage, bytes));
+    ctx->rect_stage_bytes = bytes;
+    return PAGK_OK;
+}
+
+int rect_into_slot(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *raw, bool raw_on_host,
+                   int32_t sw, int32_t sh, int64_t sstep, int32_t pyramids, const char *what)
+{
+    if (!ctx || slot < 0 || slot >= kSlots || !raw || pyramids < 1 || pyramids > PAGK_MAX_PYRAMIDS) return PAGK_E_ARG;
+    int rc = rect_check_src(ctx, params, sw, sh, sstep, what);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FrameSlot &s = ctx->slots[slot];
+    // the maps decide the size: an unused slot takes it; one that holds a frame of another size is the caller's mistake
+    // (two cameras' frames mixed up), not something to resize silently
+    if (slot < kUserSlots && s.w && (s.w != ctx->rect_w || s.h != ctx->rect_h)) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: slot %d holds a %d x %d frame, the maps are %d x %d", what, slot, s.w, s.h, ctx->rect_w, ctx->rect_h);
+        return PAGK_E_ARG;
+    }
+    s.valid = false;
+    if ((rc = slot_reserve(ctx, s, ctx->rect_w, ctx->rect_h, pyramids))) return rc;
+    if (raw_on_host) {
+        const size_t row = (size_t)sw * params->channels;
+        if ((rc = rect_stage_reserve(ctx, row * sh))) return rc;
+        HIPCHK(ctx, hipMemcpy2DAsync(ctx->rect_stage, row, raw, (size_t)sstep, row, (size_t)sh, hipMemcpyHostToDevice, ctx->stream));
+        raw = ctx->rect_stage, sstep = (int64_t)row;
+    }
+    if ((rc = rect_launch(ctx, params, raw, sw, sh, sstep, s.u8[0]))) return rc;
+    rc = slot_build(ctx, s, s.u8[0], s.w, 1);   // as frame_upload_any leaves a continuous image: wrap0 = 1 ...
+    s.pad0 = 0;                                  // ... pad0 = 0
+    return rc;
+}
+
+}  // namespace
+
+int pagk_rectify_set_maps(pagk_ctx *ctx, const float *map_x, const float *map_y, int32_t width, int32_t height,
+                          int64_t step_bytes)
+{
+    if (!ctx || !map_x || !map_y || width < 1 || height < 1 || step_bytes < (int64_t)width * 4) return PAGK_E_ARG;
+    if (width >= (1 << 24) || height >= (1 << 24) || (int64_t)width * height >= (1ll << 31)) return PAGK_E_ARG;   // (check_image)
+    NOT_WHILE_CAPTURING(ctx, "pagk_rectify_set_maps");
+    if (in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_rectify_set_maps allocates and synchronises: not inside a stream capture");
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int wp = (width + 3) & ~3;
+    std::vector<RectEntry> e;
+    try {
+        e.assign((size_t)wp * height, RectEntry{kRectNoPixelLo, 0u});
+    } catch (const std::bad_alloc &) {
+        return PAGK_E_NOMEM;
+    }
+    for (int32_t r = 0; r < height; r++) {
+        const float *mx = reinterpret_cast<const float *>(reinterpret_cast<const char *>(map_x) + (size_t)r * step_bytes);
+        const float *my = reinterpret_cast<const float *>(reinterpret_cast<const char *>(map_y) + (size_t)r * step_bytes);
+        for (int32_t c = 0; c < width; c++) {
+            int32_t sx, sy;
+            if (!rect_fixed(mx[c], &sx) || !rect_fixed(my[c], &sy)) continue;   // "no pixel"
+            const int32_t ix = sat_i16(sx >> 5), iy = sat_i16(sy >> 5);         // arithmetic shifts: negative coordinates floor
+            RectEntry &o = e[(size_t)r * wp + c];
+            o.lo = ((uint32_t)ix & 0xffffu) | ((uint32_t)iy << 16);
+            o.hi = (uint32_t)(sx & 31) | ((uint32_t)(sy & 31) << 8);
+        }
+    }
+    const size_t bytes = e.size() * sizeof(RectEntry);
+    if (wp != ctx->rect_wp || height != ctx->rect_h || !ctx->rect_entries) {
+        int rc = no_live_graphs(ctx, "the map entries (maps of another size)");
+        if (rc) return rc;
+        // nothing enqueued may still read the old entries
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->rect_entries) HIPCHK(ctx, hipFree(ctx->rect_entries));
+        ctx->rect_entries = nullptr, ctx->rect_w = ctx->rect_h = ctx->rect_wp = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->rect_entries, bytes));
+    }
+    ctx->rect_w = width, ctx->rect_h = height, ctx->rect_wp = wp;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rect_entries, e.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (e goes out of scope)
+    return PAGK_OK;
+}
+
+int pagk_frame_rectify_device(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *d_raw,
+                              int32_t src_width, int32_t src_height, int64_t src_step, int32_t pyramids)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return rect_into_slot(ctx, slot, params, d_raw, false, src_width, src_height, src_step, pyramids, "pagk_frame_rectify_device");
+}
+
+int pagk_frame_rectify_pinned(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *raw,
+                              int32_t src_width, int32_t src_height, int64_t src_step, int32_t pyramids)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return rect_into_slot(ctx, slot, params, raw, true, src_width, src_height, src_step, pyramids, "pagk_frame_rectify_pinned");
+}
+
+int pagk_rectify(pagk_ctx *ctx, const pagk_rectify_params *params, const void *raw, int32_t src_width, int32_t src_height,
+                 int64_t src_step, uint8_t *dst, int64_t dst_step)
+{
+    if (!ctx || !raw || !dst) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_rectify");
+    if (ctx->rect_entries && dst_step < ctx->rect_w) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_rectify: dst_step %lld is less than the maps' width %d", (long long)dst_step, ctx->rect_w);
+        return PAGK_E_ARG;
+    }
+    int rc = rect_into_slot(ctx, 4, params, raw, true, src_width, src_height, src_step, 1, "pagk_rectify");
+    if (rc) return rc;
+    const FrameSlot &s = ctx->slots[4];
+    HIPCHK(ctx, hipMemcpy2DAsync(dst, (size_t)dst_step, s.u8[0], (size_t)s.w, (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
 int pagk_frame_download_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int32_t *width,
                               int32_t *height)
 {
     if (!ctx || slot < 0 || slot >= kUserSlots || !dst) return PAGK_E_ARG;
     NOT_WHILE_CAPTURING(ctx, "pagk_frame_download_level");
     FrameSlot &s = ctx->slots[slot];
-    if (!s.valid || level < 1 || level >= s.L) return PAGK_E_ARG;  // level 0 is the caller's own image
+    if (!s.valid || level < 0 || level >= s.L || (level == 0 && !s.img0)) return PAGK_E_ARG;
     int lw[kMaxLevels], lh[kMaxLevels];
     level_dims(s.w, s.h, s.L, lw, lh);
-    HIPCHK(ctx, hipMemcpyAsync(dst, s.u8[level], (size_t)lw[level] * lh[level], hipMemcpyDeviceToHost, ctx->stream));
+    if (level == 0)   // where the pyramid was built from: the slot's own copy, or the caller's device image read in place
+        HIPCHK(ctx, hipMemcpy2DAsync(dst, (size_t)s.w, s.img0, (size_t)s.pitch0, (size_t)s.w, (size_t)s.h, hipMemcpyDeviceToHost, ctx->stream));
+    else
+        HIPCHK(ctx, hipMemcpyAsync(dst, s.u8[level], (size_t)lw[level] * lh[level], hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (width) *width = lw[level];
     if (height) *height = lh[level];

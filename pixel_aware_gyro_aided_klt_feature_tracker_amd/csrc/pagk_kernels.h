@@ -1276,5 +1276,6 @@ __global__ void __launch_bounds__(256, 4) k_track_block_pyr(TrackArgs a, PyrArgs
 #include "pagk_fit_kernel.h"
 #include "pagk_handover_kernel.h"
 #include "pagk_detect_kernel.h"
+#include "pagk_rectify_kernel.h"
 #include "pagk_neighbor_kernel.h"
 #include "pagk_selftest_kernel.h"

@@ -526,13 +526,19 @@ class SequenceTracker:
     detector (a capi.DetectParams) closes the loop: the hand-over becomes pagk_frame_handover_detect_device, which
     detects the top-up on the current frame under the mask it has just built (Frame::DetectKeyPoints, src/frame.cpp:
     156-218), so start() and step() take no candidate list and a sequence starts with no keypoints from outside.
-    detector=None is the loop with the application's own candidates."""
+    detector=None is the loop with the application's own candidates.
+
+    rectify = (map_x, map_y, rectify_params, (src_height, src_width)) puts the reference's per-frame cv::remap and the
+    RGB-to-gray step of Frame::Frame (Examples/Demo/RealSenseD435i.cpp:202, src/frame.cpp:81-87) in front of the pyramid,
+    on the device: start() and step() then take the RAW camera frame (src_height x src_width, or x channels), the maps
+    (float32, height x width) are converted once here, and each frame slot holds its own rectified image
+    (pagk_frame_rectify_device instead of pagk_frame_set_device).  rectify=None issues exactly the calls described above."""
 
     RING = 4   # pinned input blocks: one is rewritten only after the copy that read it, four frames earlier, has run
 
     def __init__(self, params: capi.Params, width: int, height: int, cap: int, target_n: int, new_point_ratio: float,
                  fit_params: "capi.FitParams | None" = None, *, device: int = 0, cand_cap: int = 1024, sigma: float = 1.0,
-                 detector: "capi.DetectParams | None" = None):
+                 detector: "capi.DetectParams | None" = None, rectify=None):
         if not torch.cuda.is_available():
             raise RuntimeError("SequenceTracker needs a HIP device (torch.cuda.is_available() is False)")
         if cap < target_n or target_n < 1 or (detector is None and cand_cap < 1):
@@ -548,7 +554,16 @@ class SequenceTracker:
         self.ctx.set_stream(self.main.cuda_stream)
         u8, f32, f64, i32 = torch.uint8, torch.float32, torch.float64, torch.int32
         n = self.cap
-        self._in_fields = [("img", u8, self.h, self.w), ("rot", f32, 9, 1)]
+        self.rectify = None
+        img_rows, img_cols = self.h, self.w
+        if rectify is not None:
+            map_x, map_y, rp, (hs, ws) = rectify
+            if np.shape(map_x) != (self.h, self.w) or np.shape(map_y) != (self.h, self.w):
+                raise ValueError("the maps must have the tracker's size (height x width)")
+            self.ctx.rectify_set_maps(np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32))
+            self.rectify = (rp, int(ws), int(hs), int(rp.channels))
+            img_rows, img_cols = int(hs), int(ws) * int(rp.channels)   # the input block's "img" is the raw frame
+        self._in_fields = [("img", u8, img_rows, img_cols), ("rot", f32, 9, 1)]
         if detector is None:   # with a detector no candidate list exists: the input block is the image and the rotation
             self._in_fields += [("n_cand", i32, 1, 1), ("cand", f32, self.cand_cap, 2)]
         nbytes = _carve_size(self._in_fields)
@@ -594,7 +609,12 @@ class SequenceTracker:
             self._pinned_free[k].synchronize()   # the copy issued RING frames ago has read this block (flow control only)
         pv = self._pinned_views[k]
         img = np.asarray(img)
-        if img.shape != (self.h, self.w) or img.dtype != np.uint8:
+        if self.rectify is not None:
+            _, ws, hs, cn = self.rectify
+            if img.dtype != np.uint8 or img.shape not in (((hs, ws, cn),) if cn > 1 else ((hs, ws), (hs, ws, 1))):
+                raise ValueError("frame must be the raw uint8 frame, src_height x src_width (x channels)")
+            img = img.reshape(hs, ws * cn)
+        elif img.shape != (self.h, self.w) or img.dtype != np.uint8:
             raise ValueError("frame must be a uint8 array of the tracker's size")
         pv["img"].numpy()[...] = img
         if rot9 is not None:
@@ -609,6 +629,14 @@ class SequenceTracker:
         self._pinned_free[k] = _event_on(self.main)
 
     # -- the frame's launches ----------------------------------------------------------------------------------
+    def _frame(self, slot: int):
+        """The frame in the fixed device block into frame slot `slot`: its pyramid, behind the rectification if there is one."""
+        if self.rectify is not None:
+            rp, ws, hs, cn = self.rectify
+            self.ctx.frame_rectify_device(slot, rp, self.d_in["img"].data_ptr(), ws, hs, ws * cn, self.params.pyramids)
+            return
+        self.ctx.frame_set_device(slot, self.d_in["img"].data_ptr(), self.w, self.h, self.w, self.params.pyramids)
+
     def _handover(self, status, pp, ppu, dst, slot: int):
         if self.detector is not None:   # the candidates are detected on the frame in `slot`, under this call's mask
             self.ctx.frame_handover_detect_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold,
@@ -625,7 +653,7 @@ class SequenceTracker:
         holds the reference keypoints, set p receives the next pair's."""
         c, pr, wk = self.ctx, self.params, self.wk
         ref, dst = self.sets[1 - p], self.sets[p]
-        c.frame_set_device(p, self.d_in["img"].data_ptr(), self.w, self.h, self.w, pr.pyramids)
+        self._frame(p)
         if pr.has_gyro_predict_initial:
             c.gyro_predict_device_live(pr, self.w, self.h, self.d_in["rot"], self.cap, ref["keys_un"], ref["live"],
                                        wk["pu"], wk["pd"], wk["st_in"], wk["aff"])
@@ -667,7 +695,7 @@ class SequenceTracker:
         with torch.cuda.stream(self.main):
             self.state.zero_()
             self._feed(img, None, candidates)
-            self.ctx.frame_set_device(0, self.d_in["img"].data_ptr(), self.w, self.h, self.w, self.params.pyramids)
+            self._frame(0)
             self._handover(self.wk["zero"], self.wk["pp"], self.wk["ppu"], self.sets[0], 0)
             self.frame = 0
             self.mode_used = "direct"
