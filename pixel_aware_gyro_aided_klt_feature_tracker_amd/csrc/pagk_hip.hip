@@ -12,6 +12,7 @@
 
 #include "../../include/pagk.h"
 #include "pagk_kernels.h"
+#include "pagk_layout.h"
 
 using namespace pagk;
 
@@ -19,6 +20,14 @@ namespace {
 
 constexpr int kSlots = 6;        // 0..3 for the caller, 4/5 = scratch pair of the host-buffer path
 constexpr int kUserSlots = 4;
+
+// A device buffer the library owns: it only ever grows, through reserve(), and is freed by pagk_destroy.
+struct DevBuf {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    void *host = nullptr;   // `mirrored` buffers: pinned host memory of the same size (one copy in, one copy out)
+    bool mirrored = false;
+};
 
 struct FrameSlot {
     int w = 0, h = 0, L = 0;
@@ -28,16 +37,8 @@ struct FrameSlot {
     uint32_t *quad[kMaxLevels] = {};
     const uint8_t *img0 = nullptr;   // level 0 where the pyramid was built from (our copy, or the caller's device image
     int64_t pitch0 = 0;              // read in place): what the corner detector reads (pagk_detect_kernel.h)
-    void *block = nullptr;           // one allocation for everything above
-    size_t block_bytes = 0;
+    DevBuf block;                    // one allocation for everything above
     bool valid = false;
-};
-
-struct FeatBuf {
-    void *block = nullptr;
-    void *host = nullptr;  // pinned mirror of `block` (host-buffer path: one copy in, one copy out)
-    size_t bytes = 0;
-    int cap = 0;
 };
 
 }  // namespace
@@ -47,31 +48,31 @@ struct pagk_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     FrameSlot slots[kSlots];
-    FeatBuf feat;
-    FeatBuf score;  // scratch of the host-buffer geometry scoring path
-    FeatBuf fit;    // workspace of the device RANSAC fits (pagk_fit_kernel.h): sized outside captures, pointed into by graphs
-    int fit_n = 0, fit_iters = 0;  // what `fit` holds room for
-    FeatBuf fitio;  // scratch of the host-buffer fit / validation entry points
-    FeatBuf hand;   // the frame hand-over's own mask (pagk_handover_kernel.h): sized outside captures, pointed into by graphs
-    FeatBuf handio; // scratch of the host-buffer hand-over
-    FeatBuf det;    // workspace of the corner detector (pagk_detect_kernel.h): sized outside captures, pointed into by graphs
-    // rectification (pagk_rectify_kernel.h): the packed map entries of pagk_rectify_set_maps and the staging buffer of the raw
-    // frame of the pinned / host-buffer forms; both sized outside captures, pointed into by graphs
-    void *rect_entries = nullptr;
+    // Every buffer that grows with the calls (DESIGN.md section 2 has the table: what sizes it, when it may grow).
+    // pagk_destroy frees them in one loop: a new one is a new name in front of kBufs.
+    enum Buf {
+        FEAT,          // the per-feature arrays of the host-buffer tracking path, and their pinned mirror
+        SCORE,         // scratch of the host-buffer geometry scoring and neighbour paths
+        FIT,           // workspace of the device RANSAC fits (pagk_fit_kernel.h): sized for fit_n correspondences and fit_iters hypotheses
+        FITIO,         // scratch of the host-buffer fit / validation entry points
+        HAND,          // the frame hand-over's own mask (pagk_handover_kernel.h)
+        HANDIO,        // scratch of the host-buffer hand-over
+        DET,           // workspace of the corner detector (pagk_detect_kernel.h)
+        RECT_ENTRIES,  // rectification (pagk_rectify_kernel.h): the packed map entries of pagk_rectify_set_maps
+        RECT_STAGE,    // ... and the staging buffer of a raw frame that arrives from the host
+        QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
+        SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
+        LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
+        kBufs
+    };
+    DevBuf buf[kBufs];
+    int fit_n = 0, fit_iters = 0;  // what buf[FIT]'s layout was computed for
     int rect_w = 0, rect_h = 0, rect_wp = 0;
-    void *rect_stage = nullptr;
-    size_t rect_stage_bytes = 0;
-    void *quad_ws = nullptr;  // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
-    size_t quad_ws_bytes = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
     int quad_capacity[3] = {0, 0, 0};  // resident waves of k_track_quad<2 / 4 / 7> (occupancy x CUs): the hand-over rule's "round"
     int rows_capacity[3] = {0, 0, 0};  // resident waves of k_track_rows<2 / 4 / 7> on this device (occupancy x CUs)
     int rows_waves_cap = 0;            // PAGK_ROWS_WAVES: upper bound of that grid (tests: a small grid, a long queue)
-    void *susp = nullptr;     // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
-    size_t susp_bytes = 0;
-    int *susp_count_dev = nullptr;  // the hand-over count of the last launch that used one (in `susp` or in `lv`)
-    void *lv = nullptr;       // one-level-per-wave launches: 8 sequences' counters (8 x 4096 B) | ready lists | float state[4 n]
-    size_t lv_bytes = 0;
+    int *susp_count_dev = nullptr;  // the hand-over count of the last launch that used one (in buf[SUSP] or in buf[LV])
     // pagk_track_device_batch (lead context): the BatchStream array of a launch and its pinned source.  The copy to the
     // device is asynchronous, and a captured copy is replayed long after the call: a pair is therefore never rewritten
     // while something may still read it.  Direct launches take the pairs of a ring in turn (a pair is reused six calls
@@ -171,8 +172,6 @@ namespace {
         }                                                                                              \
     } while (0)
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int level_dims(int w, int h, int L, int *lw, int *lh)
 {
     lw[0] = w;
@@ -194,6 +193,57 @@ bool in_capture(pagk_ctx *ctx)
     if (ctx->capturing) return true;
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(ctx->stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+}
+
+// Library-owned device buffers that captured graphs point into may only be reallocated while no instantiated graph of
+// this context is alive: the caller destroys its graphs (pagk_graph_destroy), or does what `hint` says BEFORE capturing,
+// as include/pagk.h asks.
+int no_live_graphs(pagk_ctx *ctx, const char *what, const char *hint)
+{
+    for (int k = 0; k < pagk_ctx::kGraphs; k++)
+        if (ctx->graph_execs[k]) {
+            snprintf(ctx->err, sizeof(ctx->err), "%s would have to grow while graph %d of this context is alive (its nodes hold the old "
+                     "pointers): destroy the graph first, or %s", what, k, hint);
+            return PAGK_E_ARG;
+        }
+    return PAGK_OK;
+}
+
+// When a buffer may grow.  One that the nodes of a captured graph point into (memsets, kernel arguments) must not move
+// under that graph: nothing allocates while a capture records, and replaying a graph after its buffers moved would write
+// freed memory.  GROW_FREELY is for the scratch of host-buffer entry points, which NOT_WHILE_CAPTURING keeps out of
+// captures and which no graph can therefore point into.
+enum GrowPolicy {
+    GROW_FREELY = 0,
+    NOT_IN_CAPTURE = 1,     // PAGK_E_ARG inside a capture
+    NOT_UNDER_GRAPH = 2,    // PAGK_E_ARG while a graph of this context is alive
+    NOT_IN_CAPTURE_NOR_UNDER_GRAPH = NOT_IN_CAPTURE | NOT_UNDER_GRAPH,
+};
+
+int release(pagk_ctx *ctx, DevBuf &b)
+{
+    if (b.ptr) HIPCHK(ctx, hipFree(b.ptr));
+    if (b.host) HIPCHK(ctx, hipHostFree(b.host));
+    b.ptr = b.host = nullptr;
+    b.bytes = 0;
+    return PAGK_OK;
+}
+
+// Room for `bytes` in `b`: a buffer that is too small is freed and allocated anew (its content is scratch), and is left
+// empty when that fails.  `what` names the buffer in ctx->err, `hint` is what the caller does instead of growing it here.
+int reserve(pagk_ctx *ctx, DevBuf &b, size_t bytes, GrowPolicy policy, const char *what, const char *hint = "")
+{
+    if (bytes <= b.bytes) return PAGK_OK;
+    if ((policy & NOT_IN_CAPTURE) && in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s would have to grow inside a graph capture: %s", what, hint);
+        return PAGK_E_ARG;
+    }
+    int rc = (policy & NOT_UNDER_GRAPH) ? no_live_graphs(ctx, what, hint) : PAGK_OK;
+    if (rc || (rc = release(ctx, b))) return rc;
+    HIPCHK(ctx, hipMalloc(&b.ptr, bytes));
+    if (b.mirrored) HIPCHK(ctx, hipHostMalloc(&b.host, bytes, hipHostMallocDefault));
+    b.bytes = bytes;
+    return PAGK_OK;
 }
 
 // Close the open capture segment of pagk_graph_begin (what was recorded so far becomes one instantiated graph in
@@ -296,39 +346,32 @@ int batch_desc_used(pagk_ctx *lead, pagk_ctx::BatchDesc *desc)
     return PAGK_OK;
 }
 
+// A slot's block for levels of lw[l] x lh[l] pixels: the u8 levels, then their packed taps
+int slot_alloc(pagk_ctx *ctx, FrameSlot &s, const int *lw, const int *lh, int L, GrowPolicy policy)
+{
+    size_t sizes[2 * kMaxLevels];
+    for (int l = 0; l < L; l++) {
+        sizes[l] = (size_t)lw[l] * lh[l];
+        sizes[L + l] = sizes[l] * 4;
+    }
+    const Layout<2 * kMaxLevels> lay(sizes, 2 * L);
+    int rc = reserve(ctx, s.block, lay.total, policy, "the frame slot", "run the same calls once before pagk_graph_begin");
+    if (rc) return rc;
+    for (int l = 0; l < L; l++) {
+        s.u8[l] = lay.at<uint8_t>(s.block.ptr, l);
+        s.quad[l] = lay.at<uint32_t>(s.block.ptr, L + l);
+    }
+    s.w = lw[0];
+    s.h = lh[0];
+    s.L = L;
+    return PAGK_OK;
+}
+
 int slot_reserve(pagk_ctx *ctx, FrameSlot &s, int w, int h, int L)
 {
     int lw[kMaxLevels], lh[kMaxLevels];
     int rc = level_dims(w, h, L, lw, lh);
-    if (rc) return rc;
-    size_t total = 0, off_u8[kMaxLevels], off_q[kMaxLevels];
-    for (int l = 0; l < L; l++) {
-        off_u8[l] = total;
-        total = align_up(total + (size_t)lw[l] * lh[l], 256);
-    }
-    for (int l = 0; l < L; l++) {
-        off_q[l] = total;
-        total = align_up(total + (size_t)lw[l] * lh[l] * 4, 256);
-    }
-    if (total > s.block_bytes) {
-        if (in_capture(ctx)) {  // run the same calls once before pagk_graph_begin so that nothing allocates here
-            snprintf(ctx->err, sizeof(ctx->err), "frame slot would have to be (re)allocated during graph capture");
-            return PAGK_E_ARG;
-        }
-        if (s.block) HIPCHK(ctx, hipFree(s.block));
-        s.block = nullptr;
-        s.block_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&s.block, total));
-        s.block_bytes = total;
-    }
-    for (int l = 0; l < L; l++) {
-        s.u8[l] = static_cast<uint8_t *>(s.block) + off_u8[l];
-        s.quad[l] = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(s.block) + off_q[l]);
-    }
-    s.w = w;
-    s.h = h;
-    s.L = L;
-    return PAGK_OK;
+    return rc ? rc : slot_alloc(ctx, s, lw, lh, L, NOT_IN_CAPTURE);
 }
 
 // Arguments of the single-launch pyramid (k_pyramid_fused / the trailing blocks of k_track_block_pyr) for a
@@ -470,20 +513,6 @@ int lv_check(pagk_ctx *ctx)
     return PAGK_OK;
 }
 
-// Library-owned device buffers that captured graphs point into (quad_ws, lv, susp) may only be reallocated while no
-// instantiated graph of this context is alive: the caller destroys its graphs (pagk_graph_destroy), or runs the larger
-// launch once BEFORE capturing, as include/pagk.h asks.
-int no_live_graphs(pagk_ctx *ctx, const char *what)
-{
-    for (int k = 0; k < pagk_ctx::kGraphs; k++)
-        if (ctx->graph_execs[k]) {
-            snprintf(ctx->err, sizeof(ctx->err), "%s would have to grow while graph %d of this context is alive (its nodes hold the old "
-                     "pointers): destroy the graph first, or run the largest launch once before capturing", what, k);
-            return PAGK_E_ARG;
-        }
-    return PAGK_OK;
-}
-
 int quad_capacity(pagk_ctx *ctx, int half)
 {
     const int slot = half == 5 ? 0 : (half == 7 ? 1 : 2);
@@ -567,6 +596,29 @@ void fill_param_args(TrackArgs &a, const pagk_params *p)
     a.fy_inv = (float)(1.0 / (double)p->fy);
     a.k1 = p->dist_coef[0], a.k2 = p->dist_coef[1], a.p1 = p->dist_coef[2], a.p2 = p->dist_coef[3];
     a.k3 = p->n_dist_coef == 5 ? p->dist_coef[4] : 0.0f;
+}
+
+constexpr const char *kLargestLaunchFirst = "run the largest launch once before capturing";
+static_assert(sizeof(SuspState) == kSuspStateBytes, "levels_layout (pagk_layout.h) carves SuspState records");
+
+// The workspaces of a four-features-per-wave launch: `need` bytes of img1 samples and, for one level per wave (lvl), the
+// level workspace, whose base is returned in *lb.
+int quad_workspace(pagk_ctx *ctx, size_t need, const LevelsLayout *lvl, TrackArgs *a, uint8_t **lb)
+{
+    const char *what = "the quad kernel's workspace";
+    DevBuf &ws = ctx->buf[pagk_ctx::QUAD_WS], &lv = ctx->buf[pagk_ctx::LV];
+    int rc = reserve(ctx, ws, need, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, what, kLargestLaunchFirst);
+    if (rc || (rc = reserve(ctx, lv, lvl ? lvl->total : 0, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, what, kLargestLaunchFirst))) return rc;
+    a->ws = static_cast<float *>(ws.ptr);
+    if (!lvl) return PAGK_OK;
+    *lb = static_cast<uint8_t *>(lv.ptr);
+    a->queue = reinterpret_cast<int *>(*lb);
+    a->lv_ready = reinterpret_cast<int *>(*lb + lvl->ready);
+    a->lv_state = reinterpret_cast<float *>(*lb + lvl->state);
+    a->lv_error = ctx->lv_error_dev;
+    a->lv_polls = ctx->level_polls;
+    a->lv_shift = ctx->levels_shift;
+    return PAGK_OK;
 }
 
 int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const FrameSlot &sc, int n,
@@ -654,19 +706,9 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
             int waves = (n + 3) / 4 < ctx->rows_capacity[slot] ? (n + 3) / 4 : ctx->rows_capacity[slot];
             if (ctx->rows_waves_cap > 0 && waves > ctx->rows_waves_cap) waves = ctx->rows_waves_cap;
             const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
-            if (need > ctx->quad_ws_bytes) {
-                if (in_capture(ctx)) {
-                    snprintf(ctx->err, sizeof(ctx->err), "the row kernel's workspace would have to be (re)allocated during graph capture");
-                    return PAGK_E_ARG;
-                }
-                if (int gr = no_live_graphs(ctx, "the row kernel's workspace")) return gr;
-                if (ctx->quad_ws) HIPCHK(ctx, hipFree(ctx->quad_ws));
-                ctx->quad_ws = nullptr;
-                ctx->quad_ws_bytes = 0;
-                HIPCHK(ctx, hipMalloc(&ctx->quad_ws, need));
-                ctx->quad_ws_bytes = need;
-            }
-            a.ws = static_cast<float *>(ctx->quad_ws);
+            if (int gr = reserve(ctx, ctx->buf[pagk_ctx::QUAD_WS], need, NOT_IN_CAPTURE_NOR_UNDER_GRAPH,
+                                 "the row kernel's workspace", kLargestLaunchFirst)) return gr;
+            a.ws = static_cast<float *>(ctx->buf[pagk_ctx::QUAD_WS].ptr);
             a.queue = static_cast<int *>(ctx->queue);
             HIPCHK(ctx, hipMemsetAsync(a.queue, 0, 4, ctx->stream));
             auto launch = [&](auto kern) -> hipError_t {
@@ -684,87 +726,42 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
             // wave (pyramids x ceil(n / 4) waves)
             const int nch = (Pm + 63) / 64, nq = (n + 3) / 4, waves = use_levels ? nq * p->pyramids : nq;
             const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
-            const size_t ready_bytes = use_levels ? align_up((size_t)(p->pyramids - 1) * 8 * ((nq + 7) / 8) * 4, 256) : 0;
-            // one-level-per-wave launches keep everything that must be zero before the launch in ONE block (one memset):
-            // counters | ready lists | hand-over count | hand-over list; then the two state arrays
-            const size_t susp_zero = 256 + align_up((size_t)n * 4, 256);
-            const size_t need_lv = use_levels ? 32768 + ready_bytes + susp_zero + (size_t)n * 16 + (size_t)n * sizeof(SuspState) : 0;
-            if (need > ctx->quad_ws_bytes || need_lv > ctx->lv_bytes) {
-                if (in_capture(ctx)) {
-                    snprintf(ctx->err, sizeof(ctx->err), "the quad kernel's workspace would have to be (re)allocated during graph capture");
-                    return PAGK_E_ARG;
-                }
-                // an instantiated graph keeps the old pointers in its nodes (memset, kernel arguments): replaying it after
-                // the buffers moved would write freed memory
-                if (int gr = no_live_graphs(ctx, "the quad kernel's workspace")) return gr;
-                if (need > ctx->quad_ws_bytes) {
-                    if (ctx->quad_ws) HIPCHK(ctx, hipFree(ctx->quad_ws));
-                    ctx->quad_ws = nullptr;
-                    ctx->quad_ws_bytes = 0;
-                    HIPCHK(ctx, hipMalloc(&ctx->quad_ws, need));
-                    ctx->quad_ws_bytes = need;
-                }
-                if (need_lv > ctx->lv_bytes) {
-                    if (ctx->lv) HIPCHK(ctx, hipFree(ctx->lv));
-                    ctx->lv = nullptr;
-                    ctx->lv_bytes = 0;
-                    HIPCHK(ctx, hipMalloc(&ctx->lv, need_lv));
-                    ctx->lv_bytes = need_lv;
-                }
-            }
-            a.ws = static_cast<float *>(ctx->quad_ws);
+            const LevelsLayout lvl = levels_layout((size_t)n, (size_t)nq, p->pyramids);
+            uint8_t *lb = nullptr;
+            if (int gr = quad_workspace(ctx, need, use_levels ? &lvl : nullptr, &a, &lb)) return gr;
             a.susp_polls = ctx->finisher_polls;
-            if (use_levels) {
-                uint8_t *lb = static_cast<uint8_t *>(ctx->lv);
-                a.queue = reinterpret_cast<int *>(lb);
-                a.lv_ready = reinterpret_cast<int *>(lb + 32768);
-                a.lv_state = reinterpret_cast<float *>(lb + 32768 + ready_bytes + susp_zero);
-                a.lv_error = ctx->lv_error_dev;
-                a.lv_polls = ctx->level_polls;
-                a.lv_shift = ctx->levels_shift;
-            }
             // continuation buffers; the hand-over needs the 4-wave kernel's LDS (<= 48 KB at these patch sizes)
             bool live_ok = true;
             const int budget = use_levels ? levels_budget_for(ctx, nq, p->iterations, p->pyramids, a.half, &live_ok)
                                           : quad_budget_for(ctx, nq, p->iterations, p->pyramids, a.half);
             const bool handover = budget > 0;
             ctx->last_handover = handover;
-            if (use_levels) {
-                uint8_t *lb = static_cast<uint8_t *>(ctx->lv), *sb = lb + 32768 + ready_bytes;
-                if (handover) {
-                    a.iter_budget = budget;
-                    a.susp_count = reinterpret_cast<int *>(sb);
-                    a.susp_list = reinterpret_cast<int *>(sb + 256);
-                    a.susp_state = reinterpret_cast<SuspState *>(sb + susp_zero + (size_t)n * 16);
-                    a.susp_waves = nq;   // the waves that report their end: a quad's last-level wave
-                    a.susp_lone = ctx->susp_lone;
-                    ctx->susp_count_dev = a.susp_count;
+            if (handover) {
+                // the continuation buffers: inside the level workspace, or -- whole features per wave -- a block of their own
+                if (use_levels) {
+                    a.susp_count = reinterpret_cast<int *>(lb + lvl.susp_count);
+                    a.susp_list = reinterpret_cast<int *>(lb + lvl.susp_list);
+                    a.susp_state = reinterpret_cast<SuspState *>(lb + lvl.susp_state);
+                } else {
+                    const size_t sizes[3] = {kSuspCountBytes, (size_t)n * 4, (size_t)n * sizeof(SuspState)};
+                    const Layout<3> lay(sizes);
+                    DevBuf &susp = ctx->buf[pagk_ctx::SUSP];
+                    if (int gr = reserve(ctx, susp, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the continuation buffers",
+                                         kLargestLaunchFirst)) return gr;
+                    a.susp_count = lay.at<int>(susp.ptr, 0);
+                    a.susp_list = lay.at<int>(susp.ptr, 1);
+                    a.susp_state = lay.at<SuspState>(susp.ptr, 2);
                 }
-                HIPCHK(ctx, hipMemsetAsync(lb, 0, 32768 + ready_bytes + (handover ? 256 + (size_t)n * 4 : 0), ctx->stream));
-            } else if (handover) {
-                const size_t need_s = 256 + align_up((size_t)n * 4, 256) + (size_t)n * sizeof(SuspState);
-                if (need_s > ctx->susp_bytes) {
-                    if (in_capture(ctx)) {
-                        snprintf(ctx->err, sizeof(ctx->err), "the continuation buffers would have to be (re)allocated during graph capture");
-                        return PAGK_E_ARG;
-                    }
-                    if (int gr = no_live_graphs(ctx, "the continuation buffers")) return gr;
-                    if (ctx->susp) HIPCHK(ctx, hipFree(ctx->susp));
-                    ctx->susp = nullptr;
-                    ctx->susp_bytes = 0;
-                    HIPCHK(ctx, hipMalloc(&ctx->susp, need_s));
-                    ctx->susp_bytes = need_s;
-                }
-                uint8_t *sb = static_cast<uint8_t *>(ctx->susp);
                 a.iter_budget = budget;
-                a.susp_count = reinterpret_cast<int *>(sb);
-                a.susp_list = reinterpret_cast<int *>(sb + 256);
-                a.susp_state = reinterpret_cast<SuspState *>(sb + 256 + align_up((size_t)n * 4, 256));
-                a.susp_waves = nq;   // the waves that report their end: all of them
+                a.susp_waves = nq;   // the waves that report their end: a quad's last-level wave / all of them
                 a.susp_lone = ctx->susp_lone;
                 ctx->susp_count_dev = a.susp_count;
-                HIPCHK(ctx, hipMemsetAsync(sb, 0, 256 + (size_t)n * 4, ctx->stream));  // counters and list
             }
+            // what must be zero before the launch: counters and ready lists, the hand-over's count and list
+            if (use_levels)
+                HIPCHK(ctx, hipMemsetAsync(lb, 0, handover ? lvl.susp_list + (size_t)n * 4 : lvl.susp_count, ctx->stream));
+            else if (handover)
+                HIPCHK(ctx, hipMemsetAsync(a.susp_count, 0, kSuspCountBytes + (size_t)n * 4, ctx->stream));
             // the live finisher runs beside the throughput kernel, on the context's auxiliary stream (inside a graph
             // capture the auxiliary stream joins the capture through the fork event: a parallel branch of the graph)
             const bool live = handover && live_ok && ctx->finisher_wgs > 0 && ctx->aux_stream;
@@ -946,9 +943,8 @@ struct FeatPtrs {
     float *pt_ref, *pt_init, *affine;
     uint8_t *status_in;
     pagk_outputs out;
-    size_t offs[11];   // byte offsets of the eleven arrays inside the block (and its pinned mirror)
-    size_t in_bytes;   // [0, in_bytes) = the four input arrays; [in_bytes, total) = the outputs
-    size_t total;
+    Layout<11> lay;    // the eleven arrays inside the block (and its pinned mirror)
+    size_t in_bytes;   // [0, in_bytes) = the four input arrays; [in_bytes, lay.total) = the outputs
 };
 
 int feat_reserve(pagk_ctx *ctx, int n, FeatPtrs *fp)
@@ -956,36 +952,19 @@ int feat_reserve(pagk_ctx *ctx, int n, FeatPtrs *fp)
     int cap = n < 1 ? 1 : n;
     // per feature: 8+8+16+1 in, 8+8+1+8+8+4+4 out; every array 256-aligned
     size_t sizes[11] = {8, 8, 16, 1, 8, 8, 1, 8, 8, 4, 4};
-    size_t offs[11], total = 0;
-    for (int k = 0; k < 11; k++) {
-        offs[k] = total;
-        total = align_up(total + sizes[k] * (size_t)cap, 256);
-    }
-    if (total > ctx->feat.bytes) {
-        if (ctx->feat.block) HIPCHK(ctx, hipFree(ctx->feat.block));
-        if (ctx->feat.host) HIPCHK(ctx, hipHostFree(ctx->feat.host));
-        ctx->feat.block = nullptr;
-        ctx->feat.host = nullptr;
-        ctx->feat.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->feat.block, total));
-        HIPCHK(ctx, hipHostMalloc(&ctx->feat.host, total, hipHostMallocDefault));
-        ctx->feat.bytes = total;
-    }
-    for (int k = 0; k < 11; k++) fp->offs[k] = offs[k];
-    fp->in_bytes = offs[4];
-    fp->total = total;
-    uint8_t *b = static_cast<uint8_t *>(ctx->feat.block);
-    fp->pt_ref = reinterpret_cast<float *>(b + offs[0]);
-    fp->pt_init = reinterpret_cast<float *>(b + offs[1]);
-    fp->affine = reinterpret_cast<float *>(b + offs[2]);
-    fp->status_in = b + offs[3];
-    fp->out.pt_un = reinterpret_cast<float *>(b + offs[4]);
-    fp->out.pt_dist = reinterpret_cast<float *>(b + offs[5]);
-    fp->out.status = b + offs[6];
-    fp->out.pix_err = reinterpret_cast<double *>(b + offs[7]);
-    fp->out.dist_pred = reinterpret_cast<double *>(b + offs[8]);
-    fp->out.ncc = reinterpret_cast<float *>(b + offs[9]);
-    fp->out.iters = reinterpret_cast<int32_t *>(b + offs[10]);
+    for (size_t &sz : sizes) sz *= (size_t)cap;
+    const Layout<11> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::FEAT], lay.total, GROW_FREELY, "the feature arrays");
+    if (rc) return rc;
+    void *b = ctx->buf[pagk_ctx::FEAT].ptr;
+    fp->lay = lay;
+    fp->in_bytes = lay.off[4];
+    fp->pt_ref = lay.at<float>(b, 0);
+    fp->pt_init = lay.at<float>(b, 1);
+    fp->affine = lay.at<float>(b, 2);
+    fp->status_in = lay.at<uint8_t>(b, 3);
+    fp->out = {lay.at<float>(b, 4), lay.at<float>(b, 5), lay.at<uint8_t>(b, 6), lay.at<double>(b, 7),
+               lay.at<double>(b, 8), lay.at<float>(b, 9), lay.at<int32_t>(b, 10)};
     return PAGK_OK;
 }
 
@@ -1017,14 +996,15 @@ int track_host_common(pagk_ctx *ctx, const pagk_params *p, int n, const float *p
     FeatPtrs fp;
     int rc = feat_reserve(ctx, n, &fp);
     if (rc) return rc;
-    uint8_t *hb = static_cast<uint8_t *>(ctx->feat.host), *db = static_cast<uint8_t *>(ctx->feat.block);
+    const size_t *offs = fp.lay.off;
+    uint8_t *hb = static_cast<uint8_t *>(ctx->buf[pagk_ctx::FEAT].host), *db = static_cast<uint8_t *>(ctx->buf[pagk_ctx::FEAT].ptr);
     if (n > 0) {
         // gather the (up to) four input arrays into the pinned mirror, ship them with ONE copy
         size_t nn = (size_t)n;
-        memcpy(hb + fp.offs[0], pt_ref, nn * 8);
-        if (pt_init) memcpy(hb + fp.offs[1], pt_init, nn * 8);
-        if (affine) memcpy(hb + fp.offs[2], affine, nn * 16);
-        memcpy(hb + fp.offs[3], status_in, nn);
+        memcpy(hb + offs[0], pt_ref, nn * 8);
+        if (pt_init) memcpy(hb + offs[1], pt_init, nn * 8);
+        if (affine) memcpy(hb + offs[2], affine, nn * 16);
+        memcpy(hb + offs[3], status_in, nn);
         HIPCHK(ctx, hipMemcpyAsync(db, hb, fp.in_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     pagk_outputs dout = fp.out;
@@ -1037,19 +1017,19 @@ int track_host_common(pagk_ctx *ctx, const pagk_params *p, int n, const float *p
                       fp.status_in, &dout);
     if (rc) return rc;
     if (n > 0)  // every output array with ONE copy into the pinned mirror, scattered to the caller after the sync
-        HIPCHK(ctx, hipMemcpyAsync(hb + fp.in_bytes, db + fp.in_bytes, fp.total - fp.in_bytes, hipMemcpyDeviceToHost,
+        HIPCHK(ctx, hipMemcpyAsync(hb + fp.in_bytes, db + fp.in_bytes, fp.lay.total - fp.in_bytes, hipMemcpyDeviceToHost,
                                    ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (int lr = lv_check(ctx)) return lr;
     if (n > 0) {
         size_t nn = (size_t)n;
-        memcpy(out->pt_un, hb + fp.offs[4], nn * 8);
-        if (out->pt_dist) memcpy(out->pt_dist, hb + fp.offs[5], nn * 8);
-        memcpy(out->status, hb + fp.offs[6], nn);
-        if (out->pix_err) memcpy(out->pix_err, hb + fp.offs[7], nn * 8);
-        if (out->dist_pred) memcpy(out->dist_pred, hb + fp.offs[8], nn * 8);
-        if (out->ncc) memcpy(out->ncc, hb + fp.offs[9], nn * 4);
-        if (out->iters) memcpy(out->iters, hb + fp.offs[10], nn * 4);
+        memcpy(out->pt_un, hb + offs[4], nn * 8);
+        if (out->pt_dist) memcpy(out->pt_dist, hb + offs[5], nn * 8);
+        memcpy(out->status, hb + offs[6], nn);
+        if (out->pix_err) memcpy(out->pix_err, hb + offs[7], nn * 8);
+        if (out->dist_pred) memcpy(out->dist_pred, hb + offs[8], nn * 8);
+        if (out->ncc) memcpy(out->ncc, hb + offs[9], nn * 4);
+        if (out->iters) memcpy(out->iters, hb + offs[10], nn * 4);
     }
     return PAGK_OK;
 }
@@ -1124,6 +1104,7 @@ int pagk_create(pagk_ctx **out, int device)
         return PAGK_E_HIP;
     }
     ctx->stream = ctx->own_stream;
+    ctx->buf[pagk_ctx::FEAT].mirrored = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
         pagk_destroy(ctx);
@@ -1213,22 +1194,9 @@ void pagk_destroy(pagk_ctx *ctx)
         destroy_segs(ctx->pre_segs[k]);
     }
     destroy_segs(ctx->cap_segs);
-    for (auto &s : ctx->slots)
-        if (s.block) (void)hipFree(s.block);
-    if (ctx->feat.block) (void)hipFree(ctx->feat.block);
-    if (ctx->feat.host) (void)hipHostFree(ctx->feat.host);
-    if (ctx->score.block) (void)hipFree(ctx->score.block);
-    if (ctx->fit.block) (void)hipFree(ctx->fit.block);
-    if (ctx->fitio.block) (void)hipFree(ctx->fitio.block);
-    if (ctx->hand.block) (void)hipFree(ctx->hand.block);
-    if (ctx->handio.block) (void)hipFree(ctx->handio.block);
-    if (ctx->det.block) (void)hipFree(ctx->det.block);
-    if (ctx->rect_entries) (void)hipFree(ctx->rect_entries);
-    if (ctx->rect_stage) (void)hipFree(ctx->rect_stage);
-    if (ctx->quad_ws) (void)hipFree(ctx->quad_ws);
-    if (ctx->susp) (void)hipFree(ctx->susp);
+    for (auto &s : ctx->slots) (void)release(ctx, s.block);
+    for (auto &b : ctx->buf) (void)release(ctx, b);
     if (ctx->queue) (void)hipFree(ctx->queue);
-    if (ctx->lv) (void)hipFree(ctx->lv);
     if (ctx->prio_stats) (void)hipFree(ctx->prio_stats);
     for (auto &d : ctx->batch_ring) batch_desc_free(d);
     batch_desc_free(ctx->cap_batch);
@@ -1560,7 +1528,7 @@ int rect_check_src(pagk_ctx *ctx, const pagk_rectify_params *params, int32_t sw,
         snprintf(ctx->err, sizeof(ctx->err), "%s: channels must be 1, 3 or 4; for 3 and 4 the gray weights must be non-negative and sum to 1 << gray_shift, 1 <= gray_shift <= 15", what);
         return PAGK_E_ARG;
     }
-    if (!ctx->rect_entries) {
+    if (!ctx->buf[pagk_ctx::RECT_ENTRIES].ptr) {
         snprintf(ctx->err, sizeof(ctx->err), "%s: no maps set (pagk_rectify_set_maps)", what);
         return PAGK_E_ARG;
     }
@@ -1580,7 +1548,7 @@ int rect_launch(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_
                 uint8_t *dst)
 {
     RectArgs a;
-    a.entries = static_cast<const RectEntry *>(ctx->rect_entries);
+    a.entries = static_cast<const RectEntry *>(ctx->buf[pagk_ctx::RECT_ENTRIES].ptr);
     a.src = static_cast<const uint8_t *>(d_raw);
     a.dst = dst;
     a.src_step = sstep;
@@ -1603,23 +1571,6 @@ int rect_launch(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_
     return PAGK_OK;
 }
 
-// the context's staging buffer for a raw frame that arrives from the host
-int rect_stage_reserve(pagk_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->rect_stage_bytes) return PAGK_OK;
-    if (in_capture(ctx)) {
-        snprintf(ctx->err, sizeof(ctx->err), "the raw frame's staging buffer would have to be allocated during graph capture: issue the same call once before capturing");
-        return PAGK_E_ARG;
-    }
-    int rc = no_live_graphs(ctx, "the raw frame's staging buffer");
-    if (rc) return rc;
-    if (ctx->rect_stage) HIPCHK(ctx, hipFree(ctx->rect_stage));
-    ctx->rect_stage = nullptr, ctx->rect_stage_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->rect_stage, bytes));
-    ctx->rect_stage_bytes = bytes;
-    return PAGK_OK;
-}
-
 int rect_into_slot(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *params, const void *raw, bool raw_on_host,
                    int32_t sw, int32_t sh, int64_t sstep, int32_t pyramids, const char *what)
 {
@@ -1638,9 +1589,12 @@ int rect_into_slot(pagk_ctx *ctx, int32_t slot, const pagk_rectify_params *param
     if ((rc = slot_reserve(ctx, s, ctx->rect_w, ctx->rect_h, pyramids))) return rc;
     if (raw_on_host) {
         const size_t row = (size_t)sw * params->channels;
-        if ((rc = rect_stage_reserve(ctx, row * sh))) return rc;
-        HIPCHK(ctx, hipMemcpy2DAsync(ctx->rect_stage, row, raw, (size_t)sstep, row, (size_t)sh, hipMemcpyHostToDevice, ctx->stream));
-        raw = ctx->rect_stage, sstep = (int64_t)row;
+        // the context's staging buffer for a raw frame that arrives from the host
+        DevBuf &stage = ctx->buf[pagk_ctx::RECT_STAGE];
+        if ((rc = reserve(ctx, stage, row * sh, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the raw frame's staging buffer",
+                          "issue the same call once before capturing"))) return rc;
+        HIPCHK(ctx, hipMemcpy2DAsync(stage.ptr, row, raw, (size_t)sstep, row, (size_t)sh, hipMemcpyHostToDevice, ctx->stream));
+        raw = stage.ptr, sstep = (int64_t)row;
     }
     if ((rc = rect_launch(ctx, params, raw, sw, sh, sstep, s.u8[0]))) return rc;
     rc = slot_build(ctx, s, s.u8[0], s.w, 1);   // as frame_upload_any leaves a continuous image: wrap0 = 1 ...
@@ -1681,17 +1635,19 @@ int pagk_rectify_set_maps(pagk_ctx *ctx, const float *map_x, const float *map_y,
         }
     }
     const size_t bytes = e.size() * sizeof(RectEntry);
-    if (wp != ctx->rect_wp || height != ctx->rect_h || !ctx->rect_entries) {
-        int rc = no_live_graphs(ctx, "the map entries (maps of another size)");
+    DevBuf &entries = ctx->buf[pagk_ctx::RECT_ENTRIES];
+    if (wp != ctx->rect_wp || height != ctx->rect_h || !entries.ptr) {   // keyed by the maps' size, not grow-only
+        int rc = no_live_graphs(ctx, "the map entries (maps of another size)", "set maps of this size before capturing");
         if (rc) return rc;
         // nothing enqueued may still read the old entries
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->rect_entries) HIPCHK(ctx, hipFree(ctx->rect_entries));
-        ctx->rect_entries = nullptr, ctx->rect_w = ctx->rect_h = ctx->rect_wp = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->rect_entries, bytes));
+        if ((rc = release(ctx, entries))) return rc;
+        ctx->rect_w = ctx->rect_h = ctx->rect_wp = 0;
+        HIPCHK(ctx, hipMalloc(&entries.ptr, bytes));
+        entries.bytes = bytes;
     }
     ctx->rect_w = width, ctx->rect_h = height, ctx->rect_wp = wp;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rect_entries, e.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(entries.ptr, e.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (e goes out of scope)
     return PAGK_OK;
 }
@@ -1715,7 +1671,7 @@ int pagk_rectify(pagk_ctx *ctx, const pagk_rectify_params *params, const void *r
 {
     if (!ctx || !raw || !dst) return PAGK_E_ARG;
     NOT_WHILE_CAPTURING(ctx, "pagk_rectify");
-    if (ctx->rect_entries && dst_step < ctx->rect_w) {
+    if (ctx->buf[pagk_ctx::RECT_ENTRIES].ptr && dst_step < ctx->rect_w) {
         snprintf(ctx->err, sizeof(ctx->err), "pagk_rectify: dst_step %lld is less than the maps' width %d", (long long)dst_step, ctx->rect_w);
         return PAGK_E_ARG;
     }
@@ -1859,37 +1815,10 @@ int pagk_track_device_batch(pagk_ctx *const *ctxs, int32_t k, const pagk_params 
     // workspaces of a one-level-per-wave launch (launch_track), for the batch's quads; no hand-over
     const int Pm = (2 * a.half + 1) * (2 * a.half + 1), nch = (Pm + 63) / 64, nq = total_q, waves = nq * params->pyramids;
     const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
-    const size_t ready_bytes = align_up((size_t)(params->pyramids - 1) * 8 * ((nq + 7) / 8) * 4, 256);
-    const size_t susp_zero = 256 + align_up((size_t)a.n * 4, 256);
-    const size_t need_lv = 32768 + ready_bytes + susp_zero + (size_t)a.n * 16 + (size_t)a.n * sizeof(SuspState);
-    if (need > lead->quad_ws_bytes || need_lv > lead->lv_bytes) {
-        if (in_capture(lead)) {
-            snprintf(lead->err, sizeof(lead->err), "the quad kernel's workspace would have to be (re)allocated during graph capture");
-            return PAGK_E_ARG;
-        }
-        if (int gr = no_live_graphs(lead, "the quad kernel's workspace")) return gr;
-        if (need > lead->quad_ws_bytes) {
-            if (lead->quad_ws) HIPCHK(lead, hipFree(lead->quad_ws));
-            lead->quad_ws = nullptr, lead->quad_ws_bytes = 0;
-            HIPCHK(lead, hipMalloc(&lead->quad_ws, need));
-            lead->quad_ws_bytes = need;
-        }
-        if (need_lv > lead->lv_bytes) {
-            if (lead->lv) HIPCHK(lead, hipFree(lead->lv));
-            lead->lv = nullptr, lead->lv_bytes = 0;
-            HIPCHK(lead, hipMalloc(&lead->lv, need_lv));
-            lead->lv_bytes = need_lv;
-        }
-    }
-    uint8_t *lb = static_cast<uint8_t *>(lead->lv);
-    a.ws = static_cast<float *>(lead->quad_ws);
-    a.queue = reinterpret_cast<int *>(lb);
-    a.lv_ready = reinterpret_cast<int *>(lb + 32768);
-    a.lv_state = reinterpret_cast<float *>(lb + 32768 + ready_bytes + susp_zero);
-    a.lv_error = lead->lv_error_dev;
-    a.lv_polls = lead->level_polls;
-    a.lv_shift = lead->levels_shift;
-    HIPCHK(lead, hipMemsetAsync(lb, 0, 32768 + ready_bytes, lead->stream));
+    const LevelsLayout lvl = levels_layout((size_t)a.n, (size_t)nq, params->pyramids);
+    uint8_t *lb = nullptr;
+    if ((rc = quad_workspace(lead, need, &lvl, &a, &lb))) return rc;
+    HIPCHK(lead, hipMemsetAsync(lb, 0, lvl.susp_count, lead->stream));
     if (lead->ev_trk[0] && !in_capture(lead)) HIPCHK(lead, hipEventRecord(lead->ev_trk[0], lead->stream));
     const bool lean = !a.penalty && a.solver == 0;
     auto launch = [&](auto kern) -> hipError_t {
@@ -2012,30 +1941,12 @@ int pagk_track_pyr(pagk_ctx *ctx, const pagk_params *params, int32_t n_levels, c
         FrameSlot &s = *sl[k];
         s.valid = false;
         // reserve without the even-parent restriction
-        size_t total = 0, off_u8[kMaxLevels], off_q[kMaxLevels];
-        for (int l = 0; l < n_levels; l++) {
-            off_u8[l] = total;
-            total = align_up(total + (size_t)lv[k][l].width * lv[k][l].height, 256);
-        }
-        for (int l = 0; l < n_levels; l++) {
-            off_q[l] = total;
-            total = align_up(total + (size_t)lv[k][l].width * lv[k][l].height * 4, 256);
-        }
-        if (total > s.block_bytes) {
-            if (s.block) HIPCHK(ctx, hipFree(s.block));
-            s.block = nullptr;
-            s.block_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&s.block, total));
-            s.block_bytes = total;
-        }
-        s.w = lv[k][0].width;
-        s.h = lv[k][0].height;
-        s.L = n_levels;
+        int lw[kMaxLevels], lh[kMaxLevels];
+        for (int l = 0; l < n_levels; l++) lw[l] = lv[k][l].width, lh[l] = lv[k][l].height;
+        if ((rc = slot_alloc(ctx, s, lw, lh, n_levels, GROW_FREELY))) return rc;
         dim3 blk(32, 8);
         for (int l = 0; l < n_levels; l++) {
             const pagk_image &im = lv[k][l];
-            s.u8[l] = static_cast<uint8_t *>(s.block) + off_u8[l];
-            s.quad[l] = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(s.block) + off_q[l]);
             HIPCHK(ctx, hipMemcpy2DAsync(s.u8[l], (size_t)im.width, im.data, (size_t)im.step, (size_t)im.width,
                                          (size_t)im.height, hipMemcpyHostToDevice, ctx->stream));
             dim3 grd((im.width + 31) / 32, (im.height + 7) / 8);
@@ -2184,28 +2095,6 @@ bool handover_args_ok(const pagk_params *params, int32_t width, int32_t height, 
            cap >= target_n && cand_cap >= 0 && !std::isnan(new_point_threshold);
 }
 
-// the context's own mask; grows only outside a capture and while no graph of this context is alive
-int handover_mask(pagk_ctx *ctx, size_t bytes, uint8_t **mask)
-{
-    bytes = align_up(bytes, 256);
-    if (bytes > ctx->hand.bytes) {
-        if (in_capture(ctx)) {
-            snprintf(ctx->err, sizeof(ctx->err), "the hand-over's mask would have to grow inside a capture: run the call once "
-                     "with this image size before capturing, or pass d_mask");
-            return PAGK_E_ARG;
-        }
-        int rc = no_live_graphs(ctx, "the hand-over's mask");
-        if (rc) return rc;
-        if (ctx->hand.block) HIPCHK(ctx, hipFree(ctx->hand.block));
-        ctx->hand.block = nullptr;
-        ctx->hand.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->hand.block, bytes));
-        ctx->hand.bytes = bytes;
-    }
-    *mask = static_cast<uint8_t *>(ctx->hand.block);
-    return PAGK_OK;
-}
-
 // the sizes, the rule's constants and the camera model of a hand-over; the pointers are the caller's to fill
 void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
                         int32_t target_n, double new_point_threshold)
@@ -2223,6 +2112,16 @@ void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t wi
     *out = a;
 }
 
+// The hand-over's launches on the context's stream: fill -> holes -> [plan -> detector] -> keys.  Without d_mask the
+// context's own mask is used.  With the detector leg (det, the frame's slot s, d_info) the candidates are not the
+// caller's but the corners found under the mask: at most n_new <= target_n <= cap of them, counted in d_info[0].
+int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                    double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
+                    const float *d_pt_predict_un, int32_t cand_cap, const int32_t *d_n_cand, const float *d_cand_un,
+                    float *d_keys, float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live,
+                    uint8_t *d_mask, int32_t *d_state, const pagk_detect_params *det = nullptr,
+                    const FrameSlot *s = nullptr, int32_t *d_info = nullptr);
+
 }  // namespace
 
 int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -2237,28 +2136,9 @@ int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t
         !d_keys_un || !d_index_in_last || !d_live || !d_state)
         return PAGK_E_ARG;
     if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int64_t bytes = (int64_t)width * height;
-    uint8_t *mask = d_mask;
-    if (!mask) {
-        int rc = handover_mask(ctx, (size_t)bytes, &mask);
-        if (rc) return rc;
-    }
-    HandoverArgs a;
-    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
-    a.cand_cap = cand_cap;
-    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
-    a.n_cand = d_n_cand, a.cand_un = d_cand_un;
-    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
-    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
-    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
-                       width, height, d_status, d_pt_predict_un, mask);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
-    HIPCHK(ctx, hipGetLastError());
-    return PAGK_OK;
+    return handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                           d_pt_predict_un, cand_cap, d_n_cand, d_cand_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last,
+                           d_live, d_mask, d_state);
 }
 
 int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -2276,35 +2156,25 @@ int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width,
     const size_t nc = (size_t)cap, cc = (size_t)(cand_cap > 0 ? cand_cap : 1), px = (size_t)width * height;
     // status | pt_predict | pt_predict_un | n_cand | cand | keys | keys_un | keys_normal | index | live | state | mask
     const size_t sizes[12] = {nc, nc * 8, nc * 8, 4, cc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4, px};
-    size_t off[12], total = 0;
-    for (int k = 0; k < 12; k++) {
-        off[k] = total;
-        total += align_up(sizes[k], 256);
-    }
-    if (total > ctx->handio.bytes) {
-        if (ctx->handio.block) HIPCHK(ctx, hipFree(ctx->handio.block));
-        ctx->handio.block = nullptr;
-        ctx->handio.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->handio.block, total));
-        ctx->handio.bytes = total;
-    }
-    uint8_t *b = static_cast<uint8_t *>(ctx->handio.block);
+    const Layout<12> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::HANDIO], lay.total, GROW_FREELY, "the host-buffer hand-over's scratch");
+    if (rc) return rc;
+    void *b = ctx->buf[pagk_ctx::HANDIO].ptr;
     const void *src[5] = {status, pt_predict, pt_predict_un, n_cand, cand_un};
     for (int k = 0; k < 5; k++)
         if (src[k] && (k != 4 || cand_cap > 0))
-            HIPCHK(ctx, hipMemcpyAsync(b + off[k], src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b + off[10], state, sizes[10], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
-    int rc = pagk_frame_handover_device(
-        ctx, params, width, height, cap, target_n, new_point_threshold, b + off[0], reinterpret_cast<float *>(b + off[1]),
-        reinterpret_cast<float *>(b + off[2]), cand_cap, reinterpret_cast<int32_t *>(b + off[3]),
-        reinterpret_cast<float *>(b + off[4]), reinterpret_cast<float *>(b + off[5]), reinterpret_cast<float *>(b + off[6]),
-        keys_normal ? reinterpret_cast<float *>(b + off[7]) : nullptr, reinterpret_cast<int32_t *>(b + off[8]), b + off[9],
-        b + off[11], reinterpret_cast<int32_t *>(b + off[10]));
+            HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 10), state, sizes[10], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
+    rc = pagk_frame_handover_device(
+        ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0), lay.at<float>(b, 1),
+        lay.at<float>(b, 2), cand_cap, lay.at<int32_t>(b, 3), lay.at<float>(b, 4), lay.at<float>(b, 5), lay.at<float>(b, 6),
+        keys_normal ? lay.at<float>(b, 7) : nullptr, lay.at<int32_t>(b, 8), lay.at<uint8_t>(b, 9), lay.at<uint8_t>(b, 11),
+        lay.at<int32_t>(b, 10));
     if (rc) return rc;
     void *dst[7] = {keys, keys_un, keys_normal, index_in_last, live, state, mask};
     const int from[7] = {5, 6, 7, 8, 9, 10, 11};
     for (int k = 0; k < 7; k++)
-        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], b + off[from[k]], sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }
@@ -2355,31 +2225,16 @@ int detect_workspace(pagk_ctx *ctx, const pagk_detect_params *det, int w, int h,
     const bool grid_global = d >= 1.0 && gw * gh > kDetGridLds;
     const size_t px = (size_t)w * h;
     const size_t sizes[5] = {256, px * 4, (size_t)slots * 8, (size_t)cap * 8, grid_global ? (size_t)(gw * gh) * 4 : 0};
-    size_t off[5], total = 0;
-    for (int k = 0; k < 5; k++) {
-        off[k] = total;
-        total += align_up(sizes[k], 256);
-    }
-    if (total > ctx->det.bytes) {
-        if (in_capture(ctx)) {
-            snprintf(ctx->err, sizeof(ctx->err), "the detector's workspace would have to grow inside a capture: run the call once "
-                     "with this image size, raw_cap, cap and min_distance before capturing");
-            return PAGK_E_ARG;
-        }
-        int rc = no_live_graphs(ctx, "the detector's workspace");
-        if (rc) return rc;
-        if (ctx->det.block) HIPCHK(ctx, hipFree(ctx->det.block));
-        ctx->det.block = nullptr;
-        ctx->det.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->det.block, total));
-        ctx->det.bytes = total;
-    }
-    uint8_t *b = static_cast<uint8_t *>(ctx->det.block);
-    ws->ctl = reinterpret_cast<int32_t *>(b + off[0]);
-    ws->R = reinterpret_cast<float *>(b + off[1]);
-    ws->keys = reinterpret_cast<uint64_t *>(b + off[2]);
-    ws->cand = reinterpret_cast<float *>(b + off[3]);
-    ws->grid = grid_global ? reinterpret_cast<int32_t *>(b + off[4]) : nullptr;
+    const Layout<5> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::DET], lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the detector's workspace",
+                     "run the call once with this image size, raw_cap, cap and min_distance before capturing");
+    if (rc) return rc;
+    void *b = ctx->buf[pagk_ctx::DET].ptr;
+    ws->ctl = lay.at<int32_t>(b, 0);
+    ws->R = lay.at<float>(b, 1);
+    ws->keys = lay.at<uint64_t>(b, 2);
+    ws->cand = lay.at<float>(b, 3);
+    ws->grid = grid_global ? lay.at<int32_t>(b, 4) : nullptr;
     ws->key_slots = slots;
     ws->raw_cap = (int32_t)raw_cap;
     ws->cell = (int32_t)cell, ws->grid_w = (int32_t)gw, ws->grid_h = (int32_t)gh, ws->reach = (int32_t)reach;
@@ -2448,29 +2303,30 @@ int detect_corners_slot(pagk_ctx *ctx, const pagk_detect_params *det, int32_t sl
     return detect_launch(ctx, det, s, d_mask, cap, d_max_corners, nullptr, d_corners, d_info, ws);
 }
 
-int handover_detect_slot(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                         int32_t target_n, double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
-                         const float *d_pt_predict_un, const pagk_detect_params *det, int32_t slot, float *d_keys,
-                         float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
-                         int32_t *d_state, int32_t *d_info)
+int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                    double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
+                    const float *d_pt_predict_un, int32_t cand_cap, const int32_t *d_n_cand, const float *d_cand_un,
+                    float *d_keys, float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live,
+                    uint8_t *d_mask, int32_t *d_state, const pagk_detect_params *det, const FrameSlot *s, int32_t *d_info)
 {
-    const FrameSlot &s = ctx->slots[slot];
-    if (!detect_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int64_t bytes = (int64_t)width * height;
-    uint8_t *mask = d_mask;
-    if (!mask) {
-        int rc = handover_mask(ctx, (size_t)bytes, &mask);
-        if (rc) return rc;
-    }
-    DetectWs ws;
-    int rc = detect_workspace(ctx, det, width, height, cap, &ws);
+    DevBuf &hand = ctx->buf[pagk_ctx::HAND];   // the context's own mask, for a caller that passes none
+    int rc = d_mask ? PAGK_OK
+                    : reserve(ctx, hand, align_up((size_t)bytes, kPartAlign), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the hand-over's mask",
+                              "run the call once with this image size before capturing, or pass d_mask");
     if (rc) return rc;
+    uint8_t *mask = d_mask ? d_mask : static_cast<uint8_t *>(hand.ptr);
+    DetectWs ws;
+    if (det) {
+        if ((rc = detect_workspace(ctx, det, width, height, cap, &ws))) return rc;
+        cand_cap = cap, d_n_cand = d_info, d_cand_un = ws.cand;
+    }
     HandoverArgs a;
     handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
-    a.cand_cap = cap;   // n_new <= target_n <= cap corners at most
+    a.cand_cap = cand_cap;
     a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
-    a.n_cand = d_info, a.cand_un = ws.cand;   // info[0] = the corners the detector returned
+    a.n_cand = d_n_cand, a.cand_un = d_cand_un;
     a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
     a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
     hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
@@ -2478,11 +2334,13 @@ int handover_detect_slot(pagk_ctx *ctx, const pagk_params *params, int32_t width
     hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
                        width, height, d_status, d_pt_predict_un, mask);
     HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
-                       (const int32_t *)d_state, ws.ctl);
-    HIPCHK(ctx, hipGetLastError());
-    rc = detect_launch(ctx, det, s, mask, cap, ws.ctl + kDetCtlLimit, ws.ctl + kDetCtlSkip, ws.cand, d_info, ws);
-    if (rc) return rc;
+    if (det) {
+        hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
+                           (const int32_t *)d_state, ws.ctl);
+        HIPCHK(ctx, hipGetLastError());
+        if ((rc = detect_launch(ctx, det, *s, mask, cap, ws.ctl + kDetCtlLimit, ws.ctl + kDetCtlSkip, ws.cand, d_info, ws)))
+            return rc;
+    }
     hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
     return PAGK_OK;
@@ -2515,12 +2373,13 @@ int pagk_detect_corners(pagk_ctx *ctx, const pagk_detect_params *det, const pagk
     int rc = frame_upload_any(ctx, 4, img, 1);
     if (rc) return rc;
     const size_t px = (size_t)img->width * img->height, cap = (size_t)(max_corners > 0 ? max_corners : 1);
+    const size_t sizes[3] = {px, cap * 8, 512};   // mask | corners | info words, then max_corners
+    const Layout<3> lay(sizes);
     Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, align_up(px, 256) + align_up(cap * 8, 256) + 512));
-    uint8_t *b = static_cast<uint8_t *>(s.p);
-    uint8_t *d_mask = mask ? b : nullptr;
-    float *d_corners = reinterpret_cast<float *>(b + align_up(px, 256));
-    int32_t *d_info = reinterpret_cast<int32_t *>(b + align_up(px, 256) + align_up(cap * 8, 256)), *d_max = d_info + 64;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    uint8_t *d_mask = mask ? lay.at<uint8_t>(s.p, 0) : nullptr;
+    float *d_corners = lay.at<float>(s.p, 1);
+    int32_t *d_info = lay.at<int32_t>(s.p, 2), *d_max = d_info + 64;
     if (mask) HIPCHK(ctx, hipMemcpyAsync(d_mask, mask, px, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_max, &max_corners, 4, hipMemcpyHostToDevice, ctx->stream));
     rc = detect_corners_slot(ctx, det, 4, d_mask, (int32_t)cap, d_max, d_corners, d_info);
@@ -2564,9 +2423,11 @@ int pagk_frame_handover_detect_device(pagk_ctx *ctx, const pagk_params *params, 
         !d_info)
         return PAGK_E_ARG;
     if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
-    return handover_detect_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
-                                d_pt_predict_un, det, slot, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
-                                d_state, d_info);
+    const FrameSlot &s = ctx->slots[slot];
+    if (!detect_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
+    return handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                           d_pt_predict_un, 0, nullptr, nullptr, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live,
+                           d_mask, d_state, det, &s, d_info);
 }
 
 int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -2587,28 +2448,22 @@ int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t
     // status | pt_predict | pt_predict_un | keys | keys_un | keys_normal | index | live | state | info | mask
     const size_t sizes[11] = {nc, nc * 8, nc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4,
                               kDetectInfoWords * 4, px};
-    size_t off[11], total = 0;
-    for (int k = 0; k < 11; k++) {
-        off[k] = total;
-        total += align_up(sizes[k], 256);
-    }
+    const Layout<11> lay(sizes);
     Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, total));
-    uint8_t *b = static_cast<uint8_t *>(s.p);
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    void *b = s.p;
     const void *src[3] = {status, pt_predict, pt_predict_un};
-    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(b + off[k], src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b + off[8], state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
-    rc = handover_detect_slot(ctx, params, width, height, cap, target_n, new_point_threshold, b + off[0],
-                              reinterpret_cast<float *>(b + off[1]), reinterpret_cast<float *>(b + off[2]), det, 4,
-                              reinterpret_cast<float *>(b + off[3]), reinterpret_cast<float *>(b + off[4]),
-                              keys_normal ? reinterpret_cast<float *>(b + off[5]) : nullptr,
-                              reinterpret_cast<int32_t *>(b + off[6]), b + off[7], b + off[10],
-                              reinterpret_cast<int32_t *>(b + off[8]), reinterpret_cast<int32_t *>(b + off[9]));
+    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 8), state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
+    rc = handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0),
+                         lay.at<float>(b, 1), lay.at<float>(b, 2), 0, nullptr, nullptr, lay.at<float>(b, 3), lay.at<float>(b, 4),
+                         keys_normal ? lay.at<float>(b, 5) : nullptr, lay.at<int32_t>(b, 6), lay.at<uint8_t>(b, 7),
+                         lay.at<uint8_t>(b, 10), lay.at<int32_t>(b, 8), det, &ctx->slots[4], lay.at<int32_t>(b, 9));
     if (rc) return rc;
     void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
     const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
     for (int k = 0; k < 8; k++)
-        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], b + off[from[k]], sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }
@@ -2739,28 +2594,23 @@ int pagk_geometry_scores(pagk_ctx *ctx, const double *H21, const double *H12, co
     if (n > 0 && (!pts1 || !pts2 || !inliers_H || !inliers_F)) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)(n < 1 ? 1 : n);
-    const size_t o_p2 = align_up(nn * 8, 256), o_h = o_p2 + align_up(nn * 8, 256), o_f = o_h + align_up(nn, 256);
-    const size_t o_s = o_f + align_up(nn, 256), total = o_s + 256;
-    if (total > ctx->score.bytes) {
-        if (ctx->score.block) HIPCHK(ctx, hipFree(ctx->score.block));
-        ctx->score.block = nullptr;
-        ctx->score.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->score.block, total));
-        ctx->score.bytes = total;
-    }
-    uint8_t *b = static_cast<uint8_t *>(ctx->score.block);
-    float *d_p1 = reinterpret_cast<float *>(b), *d_p2 = reinterpret_cast<float *>(b + o_p2);
-    float *d_s = reinterpret_cast<float *>(b + o_s);
+    const size_t sizes[5] = {nn * 8, nn * 8, nn, nn, 256};   // pts1 | pts2 | inliers_H | inliers_F | scores
+    const Layout<5> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::SCORE], lay.total, GROW_FREELY, "the geometry scores' scratch");
+    if (rc) return rc;
+    void *b = ctx->buf[pagk_ctx::SCORE].ptr;
+    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1), *d_s = lay.at<float>(b, 4);
+    uint8_t *d_h = lay.at<uint8_t>(b, 2), *d_f = lay.at<uint8_t>(b, 3);
     if (n > 0) {
         HIPCHK(ctx, hipMemcpyAsync(d_p1, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(d_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    int rc = pagk_geometry_scores_device(ctx, H21, H12, F21, n, d_p1, d_p2, sigma, b + o_h, b + o_f, d_s);
+    rc = pagk_geometry_scores_device(ctx, H21, H12, F21, n, d_p1, d_p2, sigma, d_h, d_f, d_s);
     if (rc) return rc;
     float sc[2];
     if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(inliers_H, b + o_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(inliers_F, b + o_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(inliers_H, d_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(inliers_F, d_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(ctx, hipMemcpyAsync(sc, d_s, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2851,51 +2701,24 @@ struct FitWs {
     uint8_t *inl_H, *inl_F;
 };
 
-size_t fit_layout(int32_t n, int32_t iters, size_t off[11])
-{
-    const size_t nn = (size_t)(n < 1 ? 1 : n), hh = (size_t)iters;
-    const size_t sizes[11] = {sizeof(FitHdr), nn * 8, nn * 8, nn * 4, hh * 72, hh * 4, 27 * 8, kFitInfoWords * 4, 8, nn, nn};
-    size_t total = 0;
-    for (int k = 0; k < 11; k++) {
-        off[k] = total;
-        total = align_up(total + sizes[k], 256);
-    }
-    return total;
-}
-
 // Room for n correspondences and `iters` hypotheses; grows only outside a capture and while no graph of this context
 // is alive (its nodes point into the workspace).
 int fit_workspace(pagk_ctx *ctx, int32_t n, int32_t iters, FitWs *w)
 {
-    size_t off[11];
-    if (n > ctx->fit_n || iters > ctx->fit_iters || !ctx->fit.block) {
-        if (in_capture(ctx)) {
-            snprintf(ctx->err, sizeof(ctx->err), "the geometry fit's workspace would have to grow inside a capture: run the "
-                     "call once with at least %d correspondences and %d hypotheses before capturing", n, iters);
-            return PAGK_E_ARG;
-        }
-        int rc = no_live_graphs(ctx, "the geometry fit's workspace");
-        if (rc) return rc;
-        const int32_t n2 = n > ctx->fit_n ? n : ctx->fit_n, it2 = iters > ctx->fit_iters ? iters : ctx->fit_iters;
-        if (ctx->fit.block) HIPCHK(ctx, hipFree(ctx->fit.block));
-        ctx->fit.block = nullptr;
-        ctx->fit_n = ctx->fit_iters = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->fit.block, fit_layout(n2, it2, off)));
-        ctx->fit_n = n2, ctx->fit_iters = it2;
-    }
-    fit_layout(ctx->fit_n, ctx->fit_iters, off);
-    uint8_t *b = static_cast<uint8_t *>(ctx->fit.block);
-    w->hdr = reinterpret_cast<FitHdr *>(b + off[0]);
-    w->p1 = reinterpret_cast<float *>(b + off[1]);
-    w->p2 = reinterpret_cast<float *>(b + off[2]);
-    w->idx = reinterpret_cast<int32_t *>(b + off[3]);
-    w->hyp_models = reinterpret_cast<double *>(b + off[4]);
-    w->hyp_counts = reinterpret_cast<int32_t *>(b + off[5]);
-    w->models = reinterpret_cast<double *>(b + off[6]);
-    w->info = reinterpret_cast<int32_t *>(b + off[7]);
-    w->scores = reinterpret_cast<float *>(b + off[8]);
-    w->inl_H = b + off[9];
-    w->inl_F = b + off[10];
+    // the layout for the largest n and the largest iters seen so far: it grows in both, and so do its bytes
+    const int32_t n2 = n > ctx->fit_n ? n : ctx->fit_n, it2 = iters > ctx->fit_iters ? iters : ctx->fit_iters;
+    const size_t nn = (size_t)(n2 < 1 ? 1 : n2), hh = (size_t)it2;
+    const size_t sizes[11] = {sizeof(FitHdr), nn * 8, nn * 8, nn * 4, hh * 72, hh * 4, 27 * 8, kFitInfoWords * 4, 8, nn, nn};
+    const Layout<11> lay(sizes);
+    char hint[128];
+    snprintf(hint, sizeof hint, "run the call once with at least %d correspondences and %d hypotheses before capturing", n, iters);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::FIT], lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the geometry fit's workspace", hint);
+    if (rc) return rc;
+    ctx->fit_n = n2, ctx->fit_iters = it2;
+    void *b = ctx->buf[pagk_ctx::FIT].ptr;
+    *w = FitWs{lay.at<FitHdr>(b, 0), lay.at<float>(b, 1), lay.at<float>(b, 2), lay.at<int32_t>(b, 3), lay.at<double>(b, 4),
+               lay.at<int32_t>(b, 5), lay.at<double>(b, 6), lay.at<int32_t>(b, 7), lay.at<float>(b, 8), lay.at<uint8_t>(b, 9),
+               lay.at<uint8_t>(b, 10)};   // (the workspace's parts in the order of FitWs' members)
     return PAGK_OK;
 }
 
@@ -2930,19 +2753,6 @@ int fit_launch(pagk_ctx *ctx, const pagk_fit_params *p, int32_t n, const float *
     return PAGK_OK;
 }
 
-// host-path I/O scratch of `bytes`
-int fitio_reserve(pagk_ctx *ctx, size_t bytes)
-{
-    if (bytes > ctx->fitio.bytes) {
-        if (ctx->fitio.block) HIPCHK(ctx, hipFree(ctx->fitio.block));
-        ctx->fitio.block = nullptr;
-        ctx->fitio.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->fitio.block, bytes));
-        ctx->fitio.bytes = bytes;
-    }
-    return PAGK_OK;
-}
-
 }  // namespace
 
 int pagk_geometry_fit_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pts1,
@@ -2965,27 +2775,29 @@ int pagk_geometry_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, c
     if (n > 0 && (!pts1 || !pts2)) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)(n < 1 ? 1 : n), hh = (size_t)params->iters_H + (size_t)params->iters_F;
-    const size_t o_p2 = align_up(nn * 8, 256), o_st = o_p2 + align_up(nn * 8, 256), o_h = o_st + align_up(nn, 256);
-    const size_t o_f = o_h + align_up(nn, 256), o_c = o_f + align_up(nn, 256), o_m = o_c + align_up(hh * 4, 256);
-    const size_t o_i = o_m + 256, total = o_i + 256;
-    int rc = fitio_reserve(ctx, total);
+    // pts1 | pts2 | status | mask_H | mask_F | hyp_counts | models | info
+    const size_t sizes[8] = {nn * 8, nn * 8, nn, nn, nn, hh * 4, 256, 256};
+    const Layout<8> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::FITIO], lay.total, GROW_FREELY, "the host-buffer fit's scratch");
     if (rc) return rc;
-    uint8_t *b = static_cast<uint8_t *>(ctx->fitio.block);
+    void *b = ctx->buf[pagk_ctx::FITIO].ptr;
+    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1);
+    uint8_t *d_st = lay.at<uint8_t>(b, 2), *d_h = lay.at<uint8_t>(b, 3), *d_f = lay.at<uint8_t>(b, 4);
+    int32_t *d_c = lay.at<int32_t>(b, 5), *d_i = lay.at<int32_t>(b, 7);
+    double *d_m = lay.at<double>(b, 6);
     if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(b, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b + o_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (status) HIPCHK(ctx, hipMemcpyAsync(b + o_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_p1, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (status) HIPCHK(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     }
     FitWs w;
-    rc = fit_launch(ctx, params, n, reinterpret_cast<float *>(b), reinterpret_cast<float *>(b + o_p2),
-                    status ? b + o_st : nullptr, reinterpret_cast<double *>(b + o_m), b + o_h, b + o_f,
-                    reinterpret_cast<int32_t *>(b + o_i), reinterpret_cast<int32_t *>(b + o_c), &w);
+    rc = fit_launch(ctx, params, n, d_p1, d_p2, status ? d_st : nullptr, d_m, d_h, d_f, d_i, d_c, &w);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(models, b + o_m, 27 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(info, b + o_i, PAGK_FIT_INFO_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0 && mask_H) HIPCHK(ctx, hipMemcpyAsync(mask_H, b + o_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0 && mask_F) HIPCHK(ctx, hipMemcpyAsync(mask_F, b + o_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (hyp_counts) HIPCHK(ctx, hipMemcpyAsync(hyp_counts, b + o_c, hh * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(models, d_m, 27 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(info, d_i, PAGK_FIT_INFO_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && mask_H) HIPCHK(ctx, hipMemcpyAsync(mask_H, d_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && mask_F) HIPCHK(ctx, hipMemcpyAsync(mask_F, d_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (hyp_counts) HIPCHK(ctx, hipMemcpyAsync(hyp_counts, d_c, hh * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }
@@ -3019,24 +2831,25 @@ int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, i
     if (track_score) *track_score = 0;  // :447
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)(n < 1 ? 1 : n);
-    const size_t o_p2 = align_up(nn * 8, 256), o_st = o_p2 + align_up(nn * 8, 256), o_c = o_st + align_up(nn, 256);
-    const size_t total = o_c + 256;
-    int rc = fitio_reserve(ctx, total);
+    const size_t sizes[4] = {nn * 8, nn * 8, nn, 256};   // pt_ref_un | pt_predict_un | status | count, score
+    const Layout<4> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::FITIO], lay.total, GROW_FREELY, "the host-buffer fit's scratch");
     if (rc) return rc;
-    uint8_t *b = static_cast<uint8_t *>(ctx->fitio.block);
+    void *b = ctx->buf[pagk_ctx::FITIO].ptr;
+    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1);
+    uint8_t *d_st = lay.at<uint8_t>(b, 2);
     if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(b, pt_ref_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b + o_p2, pt_predict_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b + o_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_p1, pt_ref_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_p2, pt_predict_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     }
-    int32_t *d_cnt = reinterpret_cast<int32_t *>(b + o_c);
-    float *d_score = reinterpret_cast<float *>(b + o_c + 8);
-    rc = pagk_geometry_validation_device(ctx, params, n, reinterpret_cast<float *>(b), reinterpret_cast<float *>(b + o_p2),
-                                         b + o_st, sigma, d_cnt, d_score);
+    int32_t *d_cnt = lay.at<int32_t>(b, 3);
+    float *d_score = reinterpret_cast<float *>(d_cnt + 2);
+    rc = pagk_geometry_validation_device(ctx, params, n, d_p1, d_p2, d_st, sigma, d_cnt, d_score);
     if (rc) return rc;
     int32_t cnt = 0;
     float sc = 0;
-    if (n > 0) HIPCHK(ctx, hipMemcpyAsync(status, b + o_st, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0) HIPCHK(ctx, hipMemcpyAsync(status, d_st, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&sc, d_score, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -3124,22 +2937,12 @@ static int neighbors_host(pagk_ctx *ctx, const pagk_image *ref, const pagk_image
     if ((rc = check_image(ref)) || (rc = check_image(cur))) return rc;
     if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
     const size_t nn = (size_t)(n < 1 ? 1 : n), mm = (size_t)(m < 1 ? 1 : m), cc = (size_t)cap;
-    size_t off[11], total = 0;
     const size_t sizes[11] = {nn * 8, nn * 8, nn, nn * 16, mm * 8, mm * 8, nn * 4, nn * cc * 4, nn * cc * 4, nn * cc * 4, 0};
-    for (int k = 0; k < 11; k++) {
-        off[k] = total;
-        total = align_up(total + sizes[k], 256);
-    }
-    if (total > ctx->score.bytes) {
-        if (ctx->score.block) HIPCHK(ctx, hipFree(ctx->score.block));
-        ctx->score.block = nullptr;
-        ctx->score.bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->score.block, total));
-        ctx->score.bytes = total;
-    }
-    uint8_t *b = static_cast<uint8_t *>(ctx->score.block);
+    const Layout<11> lay(sizes);
+    if ((rc = reserve(ctx, ctx->buf[pagk_ctx::SCORE], lay.total, GROW_FREELY, "the neighbour search's scratch"))) return rc;
+    void *b = ctx->buf[pagk_ctx::SCORE].ptr;
     auto up = [&](int k, const void *src, size_t bytes) -> int {
-        if (src && bytes) HIPCHK(ctx, hipMemcpyAsync(b + off[k], src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (src && bytes) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src, bytes, hipMemcpyHostToDevice, ctx->stream));
         return PAGK_OK;
     };
     if (n > 0) {
@@ -3152,19 +2955,16 @@ static int neighbors_host(pagk_ctx *ctx, const pagk_image *ref, const pagk_image
     if (!pairs && n > 0 && ((rc = up(7, nbr_idx, (size_t)n * cc * 4)) || (rc = up(8, nbr_dist, (size_t)n * cc * 4)) ||
                             (rc = up(9, nbr_ncc, (size_t)n * cc * 4))))
         return rc;
-    rc = near_neighbors_launch(ctx, ctx->slots[4], ctx->slots[5], half_patch, n, reinterpret_cast<float *>(b + off[0]),
-                               reinterpret_cast<float *>(b + off[1]), b + off[2],
-                               affine ? reinterpret_cast<float *>(b + off[3]) : nullptr, m,
-                               reinterpret_cast<float *>(b + off[4]), reinterpret_cast<float *>(b + off[5]), level,
-                               radius_unit, use_ncc, pairs, cap, reinterpret_cast<int32_t *>(b + off[6]),
-                               reinterpret_cast<int32_t *>(b + off[7]), reinterpret_cast<float *>(b + off[8]),
-                               reinterpret_cast<float *>(b + off[9]));
+    rc = near_neighbors_launch(ctx, ctx->slots[4], ctx->slots[5], half_patch, n, lay.at<float>(b, 0), lay.at<float>(b, 1),
+                               lay.at<uint8_t>(b, 2), affine ? lay.at<float>(b, 3) : nullptr, m, lay.at<float>(b, 4),
+                               lay.at<float>(b, 5), level, radius_unit, use_ncc, pairs, cap, lay.at<int32_t>(b, 6),
+                               lay.at<int32_t>(b, 7), lay.at<float>(b, 8), lay.at<float>(b, 9));
     if (rc) return rc;
     if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(count, b + off[6], (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (nbr_idx) HIPCHK(ctx, hipMemcpyAsync(nbr_idx, b + off[7], (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (nbr_dist) HIPCHK(ctx, hipMemcpyAsync(nbr_dist, b + off[8], (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(nbr_ncc, b + off[9], (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(count, lay.at<void>(b, 6), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (nbr_idx) HIPCHK(ctx, hipMemcpyAsync(nbr_idx, lay.at<void>(b, 7), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (nbr_dist) HIPCHK(ctx, hipMemcpyAsync(nbr_dist, lay.at<void>(b, 8), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(nbr_ncc, lay.at<void>(b, 9), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
