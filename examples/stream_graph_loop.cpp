@@ -15,11 +15,15 @@
 // the current frame under the mask the hand-over has just built.  The file's keypoints then only give the count
 // (target_n); no candidate list goes to the device at all, and each line also tells how many corners were added.
 //
+// --detect-fast closes the loop the same way with the detector the reference's front-ends construct (ORBextractor with
+// one level, src/ORBextractor.cc:1148-1205: FAST in cells of about 30 pixels, then the quadtree down to target_n nodes):
+// the hand-over is pagk_frame_handover_fast_device.  The lines are those of --detect.
+//
 // --rectify puts the camera's lens in front of the loop (reference Examples/Demo/RealSenseD435i.cpp:202: cv::remap on every
 // frame): the file's images are taken for the ideal view, the program synthesises the DISTORTED frames a real lens would
 // deliver (the inverse of the file's Brown-Conrady model, by fixed-point iteration, applied with pagk_rectify), and the
 // loop then feeds those raw frames: pagk_frame_rectify_device (maps from pagk_undistort_maps, set once) replaces
-// pagk_frame_set_device inside each graph.  The same lines are printed.  --detect and --rectify combine.
+// pagk_frame_set_device inside each graph.  The same lines are printed.  --detect / --detect-fast and --rectify combine.
 //
 // Input: the file of stream_resident.cpp.
 // Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I /opt/rocm/include -I include examples/stream_graph_loop.cpp
@@ -60,15 +64,16 @@ struct KeySet {
 
 int main(int argc, char **argv)
 {
-    bool detect = false, rectify = false;
+    bool detect = false, rectify = false, fast = false;   // fast: the detector of --detect is the FAST one
     for (int k = 1; k < argc; k++)
-        if (!std::strcmp(argv[k], "--detect") || !std::strcmp(argv[k], "--rectify")) {
+        if (!std::strcmp(argv[k], "--detect") || !std::strcmp(argv[k], "--rectify") || !std::strcmp(argv[k], "--detect-fast")) {
             (argv[k][2] == 'd' ? detect : rectify) = true;
+            if (!std::strcmp(argv[k], "--detect-fast")) fast = true;
             for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
             argc--, k--;
         }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s [--detect] [--rectify] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--detect | --detect-fast] [--rectify] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
         return 2;
     }
     const int half = argc > 2 ? std::atoi(argv[2]) : 5, iters = argc > 3 ? std::atoi(argv[3]) : 10,
@@ -189,6 +194,9 @@ int main(int argc, char **argv)
     pagk_detect_params det;
     pagk_detect_params_default(&det);
     const double new_point_threshold = detect ? 0.8 * nk : 0.0;
+    // --detect-fast: the ORBextractor both front-ends construct (20, 7, one level); nfeatures = target_n
+    pagk_fast_params fp;
+    pagk_fast_params_default(&fp);
 
     // first frame (Examples/Demo/RealSenseD435i.cpp:221-235): its pyramid, and the hand-over with an all-zero status
     // takes the file's keypoints, in order, into key set 0
@@ -197,7 +205,11 @@ int main(int argc, char **argv)
     CHECK_HIP(hipMemcpy(d_ncand, &n_cand, 4, hipMemcpyHostToDevice));
     CHECK_HIP(hipMemcpy(d_frame, img[0].data(), (size_t)w * h, hipMemcpyHostToDevice));
     CHECK_PAGK(frame_into(0, d_frame));
-    if (detect)
+    if (fast)
+        CHECK_PAGK(pagk_frame_handover_fast_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &fp, 0,
+                                                   ks[0].keys, ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last,
+                                                   ks[0].live, nullptr, d_state, d_info));
+    else if (detect)
         CHECK_PAGK(pagk_frame_handover_detect_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &det, 0,
                                                      ks[0].keys, ks[0].keys_un, ks[0].keys_normal, ks[0].index_in_last,
                                                      ks[0].live, nullptr, d_state, d_info));
@@ -218,7 +230,11 @@ int main(int argc, char **argv)
         // Step 3 (src/gyro_aided_tracker.cpp:289-341), then Examples/Demo/RealSenseD435i.cpp:254-258 on the device
         CHECK_PAGK(pagk_post_filter_device(ctx, cap, half, d_st_pm, d_err, d_dist, d_ptdist, d_ptun, d_st, d_pp, d_ppu,
                                            d_kept, nullptr));
-        if (detect)   // the top-up comes from the frame just tracked into, under this call's mask
+        if (fast)
+            CHECK_PAGK(pagk_frame_handover_fast_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &fp, par,
+                                                       dst.keys, dst.keys_un, dst.keys_normal, dst.index_in_last, dst.live,
+                                                       nullptr, d_state, d_info));
+        else if (detect)   // the top-up comes from the frame just tracked into, under this call's mask
             CHECK_PAGK(pagk_frame_handover_detect_device(ctx, &p, w, h, cap, nk, new_point_threshold, d_st, d_pp, d_ppu, &det,
                                                          par, dst.keys, dst.keys_un, dst.keys_normal, dst.index_in_last,
                                                          dst.live, nullptr, d_state, d_info));

@@ -324,8 +324,8 @@ int pagk_gyro_predict_device_live(pagk_ctx *ctx, const pagk_params *params, int3
 /* GyroAidedTracker::SetBackToFrame (src/gyro_aided_tracker.cpp:97-111), Frame::SetPredictKeyPointsAndMask
  * (src/frame.cpp:115-153) and the top-up rule all three detectors of the reference end in (Frame::DetectKeyPoints
  * :156-218, Frame::LoadDetectedKeypointFromFile :222-281, ORBextractor.cc:1199-1203), on the device.  The detector
- * stays the application's here: it delivers a candidate list (undistorted points) in device memory (ORB, SuperPoint; for
- * the reference's goodFeaturesToTrack call see pagk_frame_handover_detect_device below).  In the reference's order:
+ * stays the application's here: it delivers a candidate list (undistorted points) in device memory (SuperPoint, a file; for
+ * the reference's own two detectors see pagk_frame_handover_fast_device and pagk_frame_handover_detect_device below).  In the reference's order:
  *   survivors  for i in index order with d_status[i] != 0 (cap entries): keys[m] = pt_predict[i], keys_un[m] =
  *              pt_predict_un[i], keys_normal[m] = ((x_un - cx) * fx_inv, (y_un - cy) * fy_inv) in f32 with fx_inv =
  *              (float)(1.0 / fx) (src/frame.cpp:70, :128-129), index_in_last[m] = i  (a stable compaction).
@@ -400,7 +400,8 @@ int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width,
  *              them were stored is a matter of timing: the call then returns NO corners and sets the overflow word, never
  *              a result that depends on timing.  raw_cap = 0: the context owns a buffer of the bound above (sized by a
  *              call outside a capture, like d_mask == NULL in the hand-over).
- * Block size 3 and aperture 3 are fixed; cornerMinEigenVal (useHarrisDetector = false) and ORBextractor are not provided.
+ * Block size 3 and aperture 3 are fixed; cornerMinEigenVal (useHarrisDetector = false) is not provided.  This is the `else`
+ * branch of Frame::DetectKeyPoints; the branch the shipped front-ends take (ORBextractor) is pagk_detect_fast_device below.
  * quality_level, min_distance >= 0 and finite, harris_k finite, raw_cap >= 0 (PAGK_E_ARG otherwise).
  * info, PAGK_DETECT_INFO_WORDS int32: [0] corners returned, [1] raw candidates found (the true number, also on
  * overflow), [2] overflow, [3] the bits of Rmax (0 if there is none or Rmax <= 0), [4] the candidates the distance walk
@@ -451,6 +452,120 @@ int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t
 /* Diagnostic: the response map R alone (img->width * img->height floats, harris_k = 0.04), host buffers: localises a
  * mismatch to the first stage of the detector (src/frame.cpp:156-218 has no counterpart: OpenCV keeps the map inside). */
 int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R);
+
+/* ---- the detector the reference's front-ends run: FAST in cells, then the quadtree ---------------------------------- */
+/* Both shipped front-ends construct an ORBextractor(nFeatures, 1.2, nLevels = 1, iniThFAST = 20, minThFAST = 7)
+ * (Examples/Demo/RealSenseD435i.cpp:184-190, Examples/ROS/.../feature_tracker.cpp:367-371), so Frame::DetectKeyPoints
+ * (src/frame.cpp:156-218) takes its first branch, pORBextractor->DetectFeatures(mGray, mMask, keypoints) (:172-179):
+ * ORBextractor::DetectFeatures (src/ORBextractor.cc:1148-1205), ComputeKeyPointsOctTree (:789-871), DistributeOctTree
+ * (:563-787), ExtractorNode::DivideNode (:505-561).  This section is that branch for nlevels = 1.  Parity with OpenCV's
+ * cv::FAST is NOT claimed (it cannot be built here); the contract is this definition, bit for bit (restated in plain C in
+ * tests/fast_detect_ref.c).  It is integer arithmetic throughout, so a host with OpenCV can pin it.  Multi-level ORB
+ * (cv::resize at 1 / 1.2), computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and descriptors are not
+ * provided.
+ *   input      an 8-bit image W x H (level 0 of a frame slot, read through its pitch).  At level 0 without orientation
+ *              every FAST window lies inside the image: the border image of ComputePyramid is never read.  EDGE_THRESHOLD
+ *              = 19: minBorder = 16, maxBorderX = W - 16, maxBorderY = H - 16.
+ *   cells      (:805-830) width = maxBorderX - 16, height = maxBorderY - 16 as floats; nCols = int(width / 30), nRows =
+ *              int(height / 30); wCell = ceil(width / nCols), hCell = ceil(height / nRows).  Cell (i, j) is the sub-image
+ *              rows [iniY, maxY) x columns [iniX, maxX): iniY = 16 + i * hCell, maxY = min(iniY + hCell + 6, maxBorderY),
+ *              the row is skipped if iniY >= maxBorderY - 3; iniX = 16 + j * wCell, maxX = min(iniX + wCell + 6,
+ *              maxBorderX), the cell is skipped if iniX >= maxBorderX - 6 (3 for rows, 6 for columns: the reference's).
+ *              62 <= W, H <= 32767 and nIni >= 1 (below): PAGK_E_ARG otherwise -- the reference divides by zero there; the
+ *              upper limit is the library's own (16-bit key coordinates).
+ *   FAST-9/16  the ring is the 16 offsets of the Bresenham circle of radius 3 (OpenCV's order from (0, 3); only the cyclic
+ *              order matters).  For a pixel p whose ring lies inside the cell's sub-image (local x in [3, w - 3), y in
+ *              [3, h - 3)): m(p) = the maximum, over the 16 arcs of 9 consecutive ring pixels and both polarities, of the
+ *              minimum over the arc of ring - centre (or centre - ring).  p is a corner at threshold t iff m(p) > t; its
+ *              score is m(p) - 1, the largest t at which it still is one (cv::FAST's response).  S_t(p) = m(p) - 1 for a
+ *              corner at t, 0 otherwise and 0 outside the detection region of the CELL.
+ *   non-max    p is kept iff S_t(p) > S_t of all eight neighbours, strictly: both pixels of a tie go.  A neighbouring
+ *              cell's scores are not seen (FAST on a sub-matrix).  At most one pixel of any 2 x 2 block is kept: a cell
+ *              yields at most ceil(wCell / 2) * ceil(hCell / 2) keypoints, and has a fixed segment of that size.
+ *   fall-back  pass 1 uses t = ini_threshold; a cell that keeps NO keypoint runs pass 2 with t = min_threshold (:833-840).
+ *              A cell's keypoints come from exactly one pass.
+ *   raw list   cells in loop order (i outer, j inner), raster order inside a cell; coordinates (x_local + j * wCell,
+ *              y_local + i * hCell) as floats relative to minBorder (:846-847).
+ *   target     N = n_features (mnFeaturesPerLevel[0] = nfeatures for one level, :459-470).  The tree distributes over the
+ *              whole image and does not see the mask; the mask is applied after it (the reference's order: it changes
+ *              which points are returned).
+ *   quadtree   (:563-787) nIni = round((float)(maxX - minX) / (maxY - minY)), half away from zero; hX = (float)(maxX -
+ *              minX) / nIni; initial node i spans x in [int(hX * i), int(hX * (i + 1))); a key goes to node int(pt.x /
+ *              hX).  Empty nodes are erased; a node with one key is final.  An outer round walks the list front to back
+ *              and splits every node that is not final (DivideNode: half sizes ceil(float(extent) / 2), child test x <
+ *              n1.UR.x, y < n1.BR.y, keys keep their order inside a child); the non-empty children are pushed to the
+ *              FRONT in the order n1, n2, n3, n4 and the parent is erased.  After a round: finished if size >= N or size
+ *              == prevSize; otherwise, if size + 3 * nToExpand > N (nToExpand: children of the round with more than one
+ *              key), the inner loop takes over: the children of the previous pass that have more than one key are sorted
+ *              ascending and walked from the back, each split the same way, and the walk BREAKS as soon as size >= N;
+ *              then the same finish test.
+ *   tie rule   the reference sorts pair<int, ExtractorNode*>: nodes of equal size are ordered by heap address, the one
+ *              place where it is not a function of its input.  The library's rule: every node gets a creation number when
+ *              it is pushed into the list (initial nodes in order, then children in push order); the sort key is (size,
+ *              creation number).
+ *   result     one keypoint per node in list order, front to back: the key with the largest response, the first one on a
+ *              tie (:768-784).  The list can be longer than N: at most max(N + 2, 4 * nIni) nodes (a full round runs
+ *              only while size + 3 * nToExpand <= N, except the first, which starts from at most nIni nodes; the inner
+ *              loop adds at most 3 per split before its break).  minBorder is added to both coordinates (:866-867), then
+ *              every keypoint with mask[int(y) * W + int(x)] == 0 is dropped (:1199-1203; mask NULL = all ones) and the
+ *              rest goes out in list order as (float x, float y) plus, optionally, the response; entries beyond the count
+ *              are zeroed.  The trimming to n_new is the hand-over's (src/frame.cpp:176-179), not the detector's.
+ * info, PAGK_DETECT_INFO_WORDS int32: [0] keypoints returned, [1] raw FAST keypoints, [2] cells whose first pass was empty,
+ * [3] cells empty after both passes, [4] nodes at the end (the count before the mask), [5] splitting passes run (outer
+ * rounds plus inner passes; 1 for an image without keypoints), the rest 0 ([7] would be -1, with no keypoints returned, if a
+ * list ever outgrew the bound above: the kernel then stops instead of writing past a buffer). */
+typedef struct pagk_fast_params {
+    int32_t ini_threshold; /* iniThFAST 20 */
+    int32_t min_threshold; /* minThFAST 7  */
+    int32_t n_features;    /* nfeatures; 0 = the call's target_n (fused form), PAGK_E_ARG in the stand-alone forms */
+    int32_t n_levels;      /* nlevels: must be 1 (PAGK_E_UNSUPPORTED otherwise) */
+} pagk_fast_params;
+/* 20, 7, 0, 1: the constructor arguments of both front-ends that src/ORBextractor.cc:1148-1205 runs with */
+void pagk_fast_params_default(pagk_fast_params *p);
+/* PAGK_OK if *p can be run by the entry points below (src/ORBextractor.cc:1148-1205 with one level): thresholds in
+ * [0, 255], n_features >= 0 (PAGK_E_ARG otherwise), n_levels == 1 (PAGK_E_UNSUPPORTED otherwise).  Needs no device. */
+int pagk_fast_params_check(const pagk_fast_params *p);
+/* The sizes a caller needs for src/ORBextractor.cc:1148-1205 on a width x height image with n_features >= 1: *raw_bound =
+ * nRows * nCols * ceil(wCell / 2) * ceil(hCell / 2) raw keypoints at most, *out_bound = max(n_features + 2, 4 * nIni)
+ * keypoints returned at most.  PAGK_E_ARG for a size the definition excludes.  Needs no device; either pointer may be NULL. */
+int pagk_detect_fast_bounds(int32_t width, int32_t height, int32_t n_features, int32_t *raw_bound, int32_t *out_bound);
+/* ORBextractor::DetectFeatures (src/ORBextractor.cc:1148-1205) on level 0 of frame slot `slot` (for how long a slot can
+ * be detected on see pagk_detect_corners_device).  d_mask: W * H bytes or NULL.  d_keypoints: cap x 2 float, d_response:
+ * cap float or NULL, d_info: PAGK_DETECT_INFO_WORDS int32.  cap >= out_bound (PAGK_E_ARG otherwise).  Device pointers,
+ * asynchronous on the context stream, capturable; no count is read on the host: every launch is sized by W, H and the
+ * bounds.  Run it once outside a capture first (workspace). */
+int pagk_detect_fast_device(pagk_ctx *ctx, const pagk_fast_params *params, int32_t slot, const uint8_t *d_mask, int32_t cap,
+                            float *d_keypoints, float *d_response /* or NULL */, int32_t *d_info);
+/* The same with host buffers, synchronous (src/ORBextractor.cc:1148-1205): keypoints holds cap x 2 floats, response (or
+ * NULL) cap floats, mask (or NULL) img->width * img->height bytes, info (or NULL) PAGK_DETECT_INFO_WORDS words. */
+int pagk_detect_fast(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_image *img, const uint8_t *mask, int32_t cap,
+                     float *keypoints, float *response, int32_t *info);
+/* pagk_frame_handover_device with src/ORBextractor.cc:1148-1205 as the source of the candidates (the first branch of
+ * Frame::DetectKeyPoints, src/frame.cpp:172-179, in one call): its result is BY DEFINITION what pagk_frame_handover_device
+ * returns when the candidate list is the detector's output on level 0 of `slot` with NO mask, N = fast->n_features (0:
+ * target_n), cand_cap = out_bound and *d_n_cand = the detector's count.  The hand-over's own acceptance test, against the
+ * mask this call builds, is the reference's mask test (:1199-1203), and its "first n_new accepted" is src/frame.cpp:176-179.
+ * State word [4] is meaningful here: the candidates the mask rejects.  When the top-up does not run (:164-169) the
+ * detector's kernels return early on a device-side flag and d_info is all zero.  d_info: PAGK_DETECT_INFO_WORDS int32.
+ * Otherwise the arguments and rules of pagk_frame_handover_detect_device. */
+int pagk_frame_handover_fast_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                                    int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                                    const float *d_pt_predict, const float *d_pt_predict_un, const pagk_fast_params *fast,
+                                    int32_t slot, float *d_keys, float *d_keys_un, float *d_keys_normal /* or NULL */,
+                                    int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask /* width * height, or NULL */,
+                                    int32_t *d_state, int32_t *d_info);
+/* The same with host buffers, synchronous (src/ORBextractor.cc:1148-1205 inside src/frame.cpp:156-218); the current image
+ * comes as a pagk_image of width x height.  state is read (reach_flag) and written; keys_normal, mask and info may be NULL. */
+int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                             int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
+                             const float *pt_predict_un, const pagk_fast_params *fast, const pagk_image *img, float *keys,
+                             float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live, uint8_t *mask,
+                             int32_t *state, int32_t *info);
+/* Diagnostic: the raw list alone (the FAST stage of src/ORBextractor.cc:1148-1205, before the tree), in its defined order,
+ * host buffers: raw_xy raw_bound x 2 floats relative to minBorder, raw_score raw_bound int32, *n the count.  Localises a
+ * mismatch to FAST or to the tree.  n_features is not read. */
+int pagk_selftest_fast_cells(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_image *img, float *raw_xy,
+                             int32_t *raw_score, int32_t *n);
 
 /* ---- rectification: a raw camera frame into a frame slot ------------------------------------------------------------ */
 /* Both front-ends of the reference rectify every frame with
@@ -550,7 +665,8 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
  * pagk_graph_end the *_device entry points (pagk_frame_set_device, pagk_gyro_predict_device[_rot],
  * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
- * pagk_frame_handover_detect_device, pagk_frame_rectify_device; and the pinned-memory forms pagk_frame_upload_pinned,
+ * pagk_frame_handover_detect_device, pagk_detect_fast_device,
+ * pagk_frame_handover_fast_device, pagk_frame_rectify_device; and the pinned-memory forms pagk_frame_upload_pinned,
  * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while

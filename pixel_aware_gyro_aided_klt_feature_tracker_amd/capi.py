@@ -54,6 +54,12 @@ class DetectParams(C.Structure):
                 ("raw_cap", C.c_int32)]
 
 
+class FastParams(C.Structure):
+    """pagk_fast_params (include/pagk.h): the ORBextractor constructor arguments the FAST-and-quadtree detector reads."""
+    _fields_ = [("ini_threshold", C.c_int32), ("min_threshold", C.c_int32), ("n_features", C.c_int32),
+                ("n_levels", C.c_int32)]
+
+
 class RectifyParams(C.Structure):
     """pagk_rectify_params (include/pagk.h): source channels and the integer RGB-to-gray step behind the remap."""
     _fields_ = [("channels", C.c_int32), ("gray_weight", C.c_int32 * 3), ("gray_shift", C.c_int32)]
@@ -61,6 +67,7 @@ class RectifyParams(C.Structure):
 
 DETECT_INFO_WORDS = 8
 DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
+FAST_INFO_FIELDS = ("n_keypoints", "raw", "first_pass_empty", "empty_cells", "nodes", "passes")
 FIT_INFO_WORDS = 12
 FIT_INFO_FIELDS = ("status", "best", "best_count", "refit_count", "valid", "adaptive")
 
@@ -230,6 +237,25 @@ def declare(lib) -> None:
                                                    _P(DetectParams), _P(Image), vp, vp, vp, vp, vp, vp, vp, vp]
         lib.pagk_selftest_corner_response.restype = C.c_int
         lib.pagk_selftest_corner_response.argtypes = [vp, _P(Image), vp]
+    if hasattr(lib, "pagk_detect_fast_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_fast_params_default.restype = None
+        lib.pagk_fast_params_default.argtypes = [_P(FastParams)]
+        lib.pagk_fast_params_check.restype = C.c_int
+        lib.pagk_fast_params_check.argtypes = [_P(FastParams)]
+        lib.pagk_detect_fast_bounds.restype = C.c_int
+        lib.pagk_detect_fast_bounds.argtypes = [i32, i32, i32, _P(i32), _P(i32)]
+        lib.pagk_detect_fast_device.restype = C.c_int
+        lib.pagk_detect_fast_device.argtypes = [vp, _P(FastParams), i32, vp, i32, vp, vp, vp]
+        lib.pagk_detect_fast.restype = C.c_int
+        lib.pagk_detect_fast.argtypes = [vp, _P(FastParams), _P(Image), vp, i32, vp, vp, vp]
+        lib.pagk_frame_handover_fast_device.restype = C.c_int
+        lib.pagk_frame_handover_fast_device.argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp,
+                                                        _P(FastParams), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_frame_handover_fast.restype = C.c_int
+        lib.pagk_frame_handover_fast.argtypes = [vp, _P(Params), i32, i32, i32, i32, C.c_double, vp, vp, vp,
+                                                 _P(FastParams), _P(Image), vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_selftest_fast_cells.restype = C.c_int
+        lib.pagk_selftest_fast_cells.argtypes = [vp, _P(FastParams), _P(Image), vp, vp, _P(i32)]
     if hasattr(lib, "pagk_frame_rectify_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
         lib.pagk_rectify_params_default.restype = None
         lib.pagk_rectify_params_default.argtypes = [_P(RectifyParams)]
@@ -348,6 +374,8 @@ EXPORTED_SYMBOLS = [
     "pagk_post_filter_device", "pagk_gyro_predict_device_live", "pagk_frame_handover_device", "pagk_frame_handover",
     "pagk_detect_params_default", "pagk_detect_corners_device", "pagk_detect_corners",
     "pagk_frame_handover_detect_device", "pagk_frame_handover_detect", "pagk_selftest_corner_response",
+    "pagk_fast_params_default", "pagk_fast_params_check", "pagk_detect_fast_bounds", "pagk_detect_fast_device",
+    "pagk_detect_fast", "pagk_frame_handover_fast_device", "pagk_frame_handover_fast", "pagk_selftest_fast_cells",
     "pagk_rectify_params_default", "pagk_rectify_params_check", "pagk_rectify_set_maps", "pagk_frame_rectify_device",
     "pagk_frame_rectify_pinned", "pagk_rectify", "pagk_undistort_maps",
 ]
@@ -376,6 +404,31 @@ def detect_params_default(**overrides) -> DetectParams:
             raise TypeError(f"pagk_detect_params has no field {k}")
         setattr(p, k, v)
     return p
+
+
+def fast_params_default(**overrides) -> FastParams:
+    """pagk_fast_params_default() with overrides (ini_threshold, min_threshold, n_features, n_levels)."""
+    p = FastParams()
+    load().pagk_fast_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(FastParams._fields_):
+            raise TypeError(f"pagk_fast_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def fast_params_check(p: FastParams) -> int:
+    """pagk_fast_params_check: PAGK_OK, PAGK_E_ARG or PAGK_E_UNSUPPORTED (needs no device)."""
+    return int(load().pagk_fast_params_check(C.byref(p)))
+
+
+def detect_fast_bounds(width: int, height: int, n_features: int):
+    """pagk_detect_fast_bounds -> (raw_bound, out_bound); PagkError for a size the definition excludes (needs no device)."""
+    raw, out = C.c_int32(0), C.c_int32(0)
+    rc = load().pagk_detect_fast_bounds(int(width), int(height), int(n_features), C.byref(raw), C.byref(out))
+    if rc != 0:
+        raise PagkError(rc, "pagk_detect_fast_bounds")
+    return raw.value, out.value
 
 
 def rectify_params_default(**overrides) -> RectifyParams:
@@ -892,6 +945,90 @@ class Context:
             _ptr(ppu), C.byref(det), C.byref(iv), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
             _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
             "pagk_frame_handover_detect")
+        return out
+
+    # the detector of the reference's front-ends (src/ORBextractor.cc:1148-1205: FAST in cells, then the quadtree) ----
+    fast_params_default = staticmethod(fast_params_default)
+    detect_fast_bounds = staticmethod(detect_fast_bounds)
+
+    def detect_fast_device(self, fast: FastParams, slot: int, d_mask, cap: int, d_keypoints, d_response, d_info):
+        """pagk_detect_fast_device on level 0 of frame slot `slot` (asynchronous, capturable).  d_mask / d_response may be
+        None.  cap >= detect_fast_bounds(...)[1]."""
+        if d_keypoints is None or d_info is None:
+            raise ValueError("d_keypoints and d_info are required")
+        self._check(self.lib.pagk_detect_fast_device(self.h, C.byref(fast), slot, _ptr(d_mask), cap, _ptr(d_keypoints),
+                                                     _ptr(d_response), _ptr(d_info)), "pagk_detect_fast_device")
+
+    def detect_fast(self, img: np.ndarray, mask, n_features: int, fast: FastParams | None = None, cap: int | None = None) -> dict:
+        """pagk_detect_fast, host buffers -> dict(keypoints (the returned ones, n x 2), response (n), buffer and
+        response_buffer (cap entries, zero beyond n), info, and the info words by name)."""
+        fast = fast if fast is not None else fast_params_default()
+        fp = FastParams(fast.ini_threshold, fast.min_threshold, int(n_features), fast.n_levels)
+        iv = image_view(img)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != img.shape:
+            raise ValueError("the mask has the wrong shape")
+        if cap is None:
+            cap = detect_fast_bounds(img.shape[1], img.shape[0], n_features)[1]
+        buf, resp = np.zeros((max(int(cap), 1), 2), np.float32), np.zeros(max(int(cap), 1), np.float32)
+        info = np.zeros(DETECT_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_detect_fast(self.h, C.byref(fp), C.byref(iv), _ptr(m), int(cap), _ptr(buf), _ptr(resp),
+                                              _ptr(info)), "pagk_detect_fast")
+        n = int(info[0])
+        out = dict(keypoints=buf[:n], response=resp[:n], buffer=buf, response_buffer=resp, info=info)
+        out.update(zip(FAST_INFO_FIELDS, (int(v) for v in info[:6])))
+        return out
+
+    def selftest_fast_cells(self, img: np.ndarray, fast: FastParams | None = None) -> dict:
+        """pagk_selftest_fast_cells -> dict(xy (n x 2, relative to minBorder), score (n), n): the raw list in its order."""
+        fast = fast if fast is not None else fast_params_default()
+        iv = image_view(img)
+        rb = detect_fast_bounds(img.shape[1], img.shape[0], 1)[0]
+        xy, sc, n = np.zeros((rb, 2), np.float32), np.zeros(rb, np.int32), C.c_int32(0)
+        self._check(self.lib.pagk_selftest_fast_cells(self.h, C.byref(fast), C.byref(iv), _ptr(xy), _ptr(sc), C.byref(n)),
+                    "pagk_selftest_fast_cells")
+        return dict(xy=xy[:n.value].copy(), score=sc[:n.value].copy(), n=n.value)
+
+    def frame_handover_fast_device(self, params: Params, width: int, height: int, cap: int, target_n: int,
+                                   new_point_threshold: float, d_status, d_pt_predict, d_pt_predict_un, fast: FastParams,
+                                   slot: int, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask, d_state,
+                                   d_info):
+        """pagk_frame_handover_fast_device on device arrays (asynchronous, capturable): the hand-over with the
+        candidates = the FAST-and-quadtree detector's output on level 0 of frame slot `slot`."""
+        if cap < target_n:
+            raise ValueError("cap must be at least target_n")
+        self._check(self.lib.pagk_frame_handover_fast_device(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
+            _ptr(d_pt_predict), _ptr(d_pt_predict_un), C.byref(fast), slot, _ptr(d_keys), _ptr(d_keys_un),
+            _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state), _ptr(d_info)),
+            "pagk_frame_handover_fast_device")
+
+    def frame_handover_fast(self, params: Params, img: np.ndarray, cap: int, target_n: int, new_point_threshold: float,
+                            status, pt_predict, pt_predict_un, fast: FastParams | None = None, state=None) -> dict:
+        """pagk_frame_handover_fast, host buffers -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state,
+        info).  `state` is copied, not updated in place; status / points are padded to cap."""
+        fast = fast if fast is not None else fast_params_default()
+        height, width = img.shape
+
+        def pad(a, dtype, width_):
+            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
+            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
+            if a.shape[0] > cap:
+                raise ValueError("more entries than cap")
+            out[:a.shape[0]] = a
+            return out
+        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
+        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+        iv = image_view(img)
+        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
+                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
+                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state,
+                   info=np.zeros(DETECT_INFO_WORDS, np.int32))
+        self._check(self.lib.pagk_frame_handover_fast(
+            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
+            _ptr(ppu), C.byref(fast), C.byref(iv), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
+            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
+            "pagk_frame_handover_fast")
         return out
 
     # rectification: a raw camera frame (distorted, 1 / 3 / 4 channels) into a frame slot ----

@@ -3,6 +3,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared  (see __graft_entry__.py)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +59,7 @@ struct pagk_ctx {
         HAND,          // the frame hand-over's own mask (pagk_handover_kernel.h)
         HANDIO,        // scratch of the host-buffer hand-over
         DET,           // workspace of the corner detector (pagk_detect_kernel.h)
+        FAST,          // workspace of the FAST detector (pagk_fast_kernel.h): sized by W, H and n_features
         RECT_ENTRIES,  // rectification (pagk_rectify_kernel.h): the packed map entries of pagk_rectify_set_maps
         RECT_STAGE,    // ... and the staging buffer of a raw frame that arrives from the host
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
@@ -2459,6 +2461,334 @@ int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t
                          lay.at<float>(b, 1), lay.at<float>(b, 2), 0, nullptr, nullptr, lay.at<float>(b, 3), lay.at<float>(b, 4),
                          keys_normal ? lay.at<float>(b, 5) : nullptr, lay.at<int32_t>(b, 6), lay.at<uint8_t>(b, 7),
                          lay.at<uint8_t>(b, 10), lay.at<int32_t>(b, 8), det, &ctx->slots[4], lay.at<int32_t>(b, 9));
+    if (rc) return rc;
+    void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
+    const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
+    for (int k = 0; k < 8; k++)
+        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+// ---- the FAST detector: cells and quadtree (pagk_fast_kernel.h) --------------------------------------------------
+namespace {
+
+// The cell grid (src/ORBextractor.cc:805-830) and the initial nodes (:563-580) of a W x H image.  false where the
+// reference would divide by zero (fewer than one cell, or no initial node), or where a coordinate leaves 15 bits.
+bool fast_grid(int w, int h, FastGrid *g)
+{
+    if (w < 62 || h < 62 || w > 32767 || h > 32767) return false;
+    g->W = w, g->H = h, g->max_bx = w - kFastBorder, g->max_by = h - kFastBorder;
+    const float width = (float)(g->max_bx - kFastBorder), height = (float)(g->max_by - kFastBorder);
+    g->n_cols = (int)(width / kFastCell), g->n_rows = (int)(height / kFastCell);
+    if (g->n_cols < 1 || g->n_rows < 1) return false;
+    g->w_cell = (int)std::ceil(width / g->n_cols), g->h_cell = (int)std::ceil(height / g->n_rows);
+    g->seg = ((g->w_cell + 1) / 2) * ((g->h_cell + 1) / 2);   // at most one pixel of any 2 x 2 block survives
+    g->n_ini = (int)std::round(width / height);               // half away from zero (:567)
+    if (g->n_ini < 1) return false;
+    g->hx = width / g->n_ini;
+    return true;
+}
+
+int fast_params_check(const pagk_fast_params *p)
+{
+    if (!p || p->ini_threshold < 0 || p->ini_threshold > 255 || p->min_threshold < 0 || p->min_threshold > 255 ||
+        p->n_features < 0 || p->n_features > (1 << 24))
+        return PAGK_E_ARG;
+    return p->n_levels == 1 ? PAGK_OK : PAGK_E_UNSUPPORTED;   // cv::resize at 1 / 1.2 is not restated
+}
+
+int64_t fast_raw_bound(const FastGrid &g) { return (int64_t)g.n_rows * g.n_cols * g.seg; }
+int32_t fast_out_bound(const FastGrid &g, int32_t n_features) { return std::max(n_features + 2, 4 * g.n_ini); }
+
+struct FastWs {
+    int32_t *ctl = nullptr, *cell_cnt = nullptr, *cell_off = nullptr, *seg_score = nullptr, *kscore = nullptr, *knode = nullptr;
+    int32_t *ncnt[2] = {}, *ncand[2] = {}, *cnt4 = nullptr, *cbase = nullptr, *split = nullptr;
+    uint32_t *seg_xy = nullptr, *kxy = nullptr;
+    int4 *box[2] = {};
+    unsigned long long *sortk = nullptr, *best = nullptr;
+    float *cand = nullptr;   // the fused call's candidate list, out_bound x 2
+    uint32_t sort_slots = 0;
+    int32_t raw_bound = 0, out_bound = 0, n_cells = 0;
+};
+
+int fast_workspace(pagk_ctx *ctx, const FastGrid &g, int32_t n_features, FastWs *ws)
+{
+    const int64_t rb64 = fast_raw_bound(g);
+    if (rb64 > (1 << 30)) return PAGK_E_ARG;
+    const size_t rb = (size_t)rb64, ob = (size_t)fast_out_bound(g, n_features), nc = (size_t)g.n_rows * g.n_cols;
+    uint32_t slots = 2;
+    while (slots < ob) slots <<= 1;
+    const size_t sizes[20] = {256,    nc * 4, nc * 4, rb * 4, rb * 4, rb * 4, rb * 4,  rb * 4, ob * 16,           ob * 16,
+                              ob * 4, ob * 4, ob * 4, ob * 4, ob * 16, ob * 4, ob * 4, (size_t)slots * 8, ob * 8, ob * 8};
+    const Layout<20> lay(sizes);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::FAST], lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the FAST detector's workspace",
+                     "run the call once with this image size and n_features before capturing");
+    if (rc) return rc;
+    void *b = ctx->buf[pagk_ctx::FAST].ptr;
+    ws->ctl = lay.at<int32_t>(b, 0), ws->cell_cnt = lay.at<int32_t>(b, 1), ws->cell_off = lay.at<int32_t>(b, 2);
+    ws->seg_xy = lay.at<uint32_t>(b, 3), ws->seg_score = lay.at<int32_t>(b, 4);
+    ws->kxy = lay.at<uint32_t>(b, 5), ws->kscore = lay.at<int32_t>(b, 6), ws->knode = lay.at<int32_t>(b, 7);
+    ws->box[0] = lay.at<int4>(b, 8), ws->box[1] = lay.at<int4>(b, 9);
+    ws->ncnt[0] = lay.at<int32_t>(b, 10), ws->ncnt[1] = lay.at<int32_t>(b, 11);
+    ws->ncand[0] = lay.at<int32_t>(b, 12), ws->ncand[1] = lay.at<int32_t>(b, 13);
+    ws->cnt4 = lay.at<int32_t>(b, 14), ws->cbase = lay.at<int32_t>(b, 15), ws->split = lay.at<int32_t>(b, 16);
+    ws->sortk = lay.at<unsigned long long>(b, 17), ws->best = lay.at<unsigned long long>(b, 18);
+    ws->cand = lay.at<float>(b, 19);
+    ws->sort_slots = slots, ws->raw_bound = (int32_t)rb, ws->out_bound = (int32_t)ob, ws->n_cells = (int32_t)nc;
+    return PAGK_OK;
+}
+
+// FAST in cells and the raw list (step 3 of the definition) of frame slot `s`; d_skip: a device word or NULL.
+int fast_cells_launch(pagk_ctx *ctx, const pagk_fast_params *fp, const FrameSlot &s, const FastGrid &g, const FastWs &ws,
+                      const int32_t *d_skip)
+{
+    FastCellArgs c;
+    memset(&c, 0, sizeof c);
+    c.img = s.img0, c.pitch = s.pitch0, c.g = g, c.t_ini = fp->ini_threshold, c.t_min = fp->min_threshold;
+    c.seg_xy = ws.seg_xy, c.seg_score = ws.seg_score, c.cell_cnt = ws.cell_cnt, c.skip = d_skip;
+    hipLaunchKernelGGL(k_fast_cells, dim3(ws.n_cells), dim3(256), 0, ctx->stream, c);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_offsets, dim3(1), dim3(1024), 0, ctx->stream, ws.n_cells, (const int32_t *)ws.cell_cnt, ws.cell_off,
+                       ws.ctl, d_skip);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_gather, dim3(ws.n_cells), dim3(256), 0, ctx->stream, g.seg, (const int32_t *)ws.cell_cnt,
+                       (const int32_t *)ws.cell_off, (const uint32_t *)ws.seg_xy, (const int32_t *)ws.seg_score, ws.kxy, ws.kscore,
+                       d_skip);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// The detector's launches: cells -> raw list -> tree, best keys, mask, output.
+int fast_launch(pagk_ctx *ctx, const pagk_fast_params *fp, int32_t n_features, const FrameSlot &s, const FastGrid &g,
+                const uint8_t *d_mask, int32_t cap, float *d_keypoints, float *d_response, int32_t *d_info,
+                const int32_t *d_skip, const FastWs &ws)
+{
+    int rc = fast_cells_launch(ctx, fp, s, g, ws, d_skip);
+    if (rc) return rc;
+    FastTreeArgs t;
+    memset(&t, 0, sizeof t);
+    t.g = g, t.n_features = n_features, t.cap = cap, t.out_bound = ws.out_bound, t.raw_bound = ws.raw_bound;
+    t.sort_slots = ws.sort_slots, t.ctl = ws.ctl, t.kxy = ws.kxy, t.kscore = ws.kscore, t.knode = ws.knode;
+    for (int k = 0; k < 2; k++) t.box[k] = ws.box[k], t.ncnt[k] = ws.ncnt[k], t.ncand[k] = ws.ncand[k];
+    t.cnt4 = ws.cnt4, t.cbase = ws.cbase, t.split = ws.split, t.sortk = ws.sortk, t.best = ws.best;
+    t.mask = d_mask, t.out_xy = d_keypoints, t.out_resp = d_response, t.info = d_info, t.skip = d_skip;
+    hipLaunchKernelGGL(k_fast_tree, dim3(1), dim3(1024), 0, ctx->stream, t);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+bool fast_slot_ok(const FrameSlot &s) { return s.valid && s.img0; }
+
+// pagk_frame_handover_device with the candidate list = the FAST detector's output on slot `s`, no mask: fill -> holes ->
+// plan -> detector -> keys.  The acceptance test of k_handover_keys is the reference's mask test (:1199-1203).
+int handover_fast_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                         int32_t target_n, double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
+                         const float *d_pt_predict_un, const pagk_fast_params *fp, const FrameSlot &s, float *d_keys,
+                         float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                         int32_t *d_state, int32_t *d_info)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FastGrid g;
+    if (!fast_grid(width, height, &g)) return PAGK_E_ARG;
+    const int32_t n_features = fp->n_features ? fp->n_features : target_n;
+    if (n_features < 1) return PAGK_E_ARG;
+    const int64_t bytes = (int64_t)width * height;
+    DevBuf &hand = ctx->buf[pagk_ctx::HAND];   // the context's own mask, for a caller that passes none
+    int rc = d_mask ? PAGK_OK
+                    : reserve(ctx, hand, align_up((size_t)bytes, kPartAlign), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the hand-over's mask",
+                              "run the call once with this image size before capturing, or pass d_mask");
+    if (rc) return rc;
+    uint8_t *mask = d_mask ? d_mask : static_cast<uint8_t *>(hand.ptr);
+    FastWs ws;
+    if ((rc = fast_workspace(ctx, g, n_features, &ws))) return rc;
+    HandoverArgs a;
+    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
+    a.cand_cap = ws.out_bound;
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.n_cand = d_info, a.cand_un = ws.cand;
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
+    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
+                       width, height, d_status, d_pt_predict_un, mask);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
+                       (const int32_t *)d_state, ws.ctl);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = fast_launch(ctx, fp, n_features, s, g, nullptr, ws.out_bound, ws.cand, nullptr, d_info, ws.ctl + kFastCtlSkip, ws)))
+        return rc;
+    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+}  // namespace
+
+void pagk_fast_params_default(pagk_fast_params *p)
+{
+    if (!p) return;
+    p->ini_threshold = 20;   // iniThFAST, Examples/Demo/RealSenseD435i.cpp:184-190
+    p->min_threshold = 7;    // minThFAST
+    p->n_features = 0;       // the call's target
+    p->n_levels = 1;
+}
+
+int pagk_fast_params_check(const pagk_fast_params *p) { return fast_params_check(p); }
+
+int pagk_detect_fast_bounds(int32_t width, int32_t height, int32_t n_features, int32_t *raw_bound, int32_t *out_bound)
+{
+    FastGrid g;
+    if (n_features < 1 || n_features > (1 << 24) || !fast_grid(width, height, &g) || fast_raw_bound(g) > (1 << 30)) return PAGK_E_ARG;
+    if (raw_bound) *raw_bound = (int32_t)fast_raw_bound(g);
+    if (out_bound) *out_bound = fast_out_bound(g, n_features);
+    return PAGK_OK;
+}
+
+// (slots 4 and 5 are the host-buffer forms' own)
+static int detect_fast_slot(pagk_ctx *ctx, const pagk_fast_params *params, int32_t slot, const uint8_t *d_mask, int32_t cap,
+                            float *d_keypoints, float *d_response, int32_t *d_info)
+{
+    if (!ctx) return PAGK_E_ARG;
+    int rc = fast_params_check(params);
+    if (rc) return rc;
+    if (params->n_features < 1 || slot < 0 || slot >= kSlots || !d_keypoints || !d_info) return PAGK_E_ARG;
+    const FrameSlot &s = ctx->slots[slot];
+    FastGrid g;
+    if (!fast_slot_ok(s) || !fast_grid(s.w, s.h, &g) || cap < fast_out_bound(g, params->n_features)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FastWs ws;
+    if ((rc = fast_workspace(ctx, g, params->n_features, &ws))) return rc;
+    return fast_launch(ctx, params, params->n_features, s, g, d_mask, cap, d_keypoints, d_response, d_info, nullptr, ws);
+}
+
+int pagk_detect_fast_device(pagk_ctx *ctx, const pagk_fast_params *params, int32_t slot, const uint8_t *d_mask, int32_t cap,
+                            float *d_keypoints, float *d_response, int32_t *d_info)
+{
+    if (slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return detect_fast_slot(ctx, params, slot, d_mask, cap, d_keypoints, d_response, d_info);
+}
+
+int pagk_detect_fast(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_image *img, const uint8_t *mask, int32_t cap,
+                     float *keypoints, float *response, int32_t *info)
+{
+    if (!ctx || !img) return PAGK_E_ARG;
+    int rc = fast_params_check(params);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_detect_fast");
+    FastGrid g;
+    if (params->n_features < 1 || !keypoints || !fast_grid(img->width, img->height, &g) ||
+        cap < fast_out_bound(g, params->n_features))
+        return PAGK_E_ARG;
+    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
+    const size_t px = (size_t)img->width * img->height, nc = (size_t)cap;
+    const size_t sizes[4] = {px, nc * 8, nc * 4, 256};   // mask | keypoints | response | info
+    const Layout<4> lay(sizes);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    uint8_t *d_mask = mask ? lay.at<uint8_t>(s.p, 0) : nullptr;
+    if (mask) HIPCHK(ctx, hipMemcpyAsync(d_mask, mask, px, hipMemcpyHostToDevice, ctx->stream));
+    rc = detect_fast_slot(ctx, params, 4, d_mask, cap, lay.at<float>(s.p, 1), lay.at<float>(s.p, 2), lay.at<int32_t>(s.p, 3));
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(keypoints, lay.at<void>(s.p, 1), nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (response) HIPCHK(ctx, hipMemcpyAsync(response, lay.at<void>(s.p, 2), nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 3), kDetectInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_selftest_fast_cells(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_image *img, float *raw_xy,
+                             int32_t *raw_score, int32_t *n)
+{
+    if (!ctx || !img || !raw_xy || !raw_score || !n) return PAGK_E_ARG;
+    int rc = fast_params_check(params);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_fast_cells");
+    FastGrid g;
+    if (!fast_grid(img->width, img->height, &g)) return PAGK_E_ARG;
+    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
+    FastWs ws;
+    if ((rc = fast_workspace(ctx, g, 1, &ws))) return rc;
+    if ((rc = fast_cells_launch(ctx, params, ctx->slots[4], g, ws, nullptr))) return rc;
+    int32_t cnt = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&cnt, ws.ctl + kFastCtlCount, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (cnt < 0 || cnt > ws.raw_bound) return PAGK_E_HIP;
+    std::vector<uint32_t> xy((size_t)cnt);
+    if (cnt) {
+        HIPCHK(ctx, hipMemcpy(xy.data(), ws.kxy, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(raw_score, ws.kscore, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    }
+    for (int32_t k = 0; k < cnt; k++) raw_xy[2 * k] = (float)(xy[k] & 0xffffu), raw_xy[2 * k + 1] = (float)(xy[k] >> 16);
+    *n = cnt;
+    return PAGK_OK;
+}
+
+static int handover_fast_slot(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                              int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                              const float *d_pt_predict, const float *d_pt_predict_un, const pagk_fast_params *fast,
+                              int32_t slot, float *d_keys, float *d_keys_un, float *d_keys_normal,
+                              int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask, int32_t *d_state,
+                              int32_t *d_info)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0)) return PAGK_E_ARG;
+    int rc = fast_params_check(fast);
+    if (rc) return rc;
+    if (slot < 0 || slot >= kSlots) return PAGK_E_ARG;
+    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_keys || !d_keys_un || !d_index_in_last || !d_live || !d_state ||
+        !d_info)
+        return PAGK_E_ARG;
+    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
+    const FrameSlot &s = ctx->slots[slot];
+    if (!fast_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
+    return handover_fast_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                                d_pt_predict_un, fast, s, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
+                                d_state, d_info);
+}
+
+int pagk_frame_handover_fast_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                                    int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                                    const float *d_pt_predict, const float *d_pt_predict_un, const pagk_fast_params *fast,
+                                    int32_t slot, float *d_keys, float *d_keys_un, float *d_keys_normal,
+                                    int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask, int32_t *d_state,
+                                    int32_t *d_info)
+{
+    if (slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                              d_pt_predict_un, fast, slot, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
+                              d_state, d_info);
+}
+
+int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                             int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
+                             const float *pt_predict_un, const pagk_fast_params *fast, const pagk_image *img, float *keys,
+                             float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live, uint8_t *mask,
+                             int32_t *state, int32_t *info)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0)) return PAGK_E_ARG;
+    int rc = fast_params_check(fast);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover_fast");
+    if (!status || !pt_predict || !pt_predict_un || !img || img->width != width || img->height != height || !keys || !keys_un ||
+        !index_in_last || !live || !state)
+        return PAGK_E_ARG;
+    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
+    const size_t nc = (size_t)cap, px = (size_t)width * height;
+    // status | pt_predict | pt_predict_un | keys | keys_un | keys_normal | index | live | state | info | mask
+    const size_t sizes[11] = {nc, nc * 8, nc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4,
+                              kDetectInfoWords * 4, px};
+    const Layout<11> lay(sizes);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    void *b = s.p;
+    const void *src[3] = {status, pt_predict, pt_predict_un};
+    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 8), state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
+    rc = handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0),
+                                         lay.at<float>(b, 1), lay.at<float>(b, 2), fast, 4, lay.at<float>(b, 3),
+                                         lay.at<float>(b, 4), keys_normal ? lay.at<float>(b, 5) : nullptr, lay.at<int32_t>(b, 6),
+                                         lay.at<uint8_t>(b, 7), lay.at<uint8_t>(b, 10), lay.at<int32_t>(b, 8), lay.at<int32_t>(b, 9));
     if (rc) return rc;
     void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
     const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};

@@ -242,3 +242,20 @@ def frame_handover_detect(params, img, cap, target_n, new_point_threshold, statu
 def corner_response(img, ctx=None) -> np.ndarray:
     """pagk_selftest_corner_response: the detector's response map of an image (float32, harris_k = 0.04)."""
     return _device_context(ctx).selftest_corner_response(np.ascontiguousarray(img, np.uint8))
+
+
+# ---- the detector of the reference's front-ends (src/ORBextractor.cc:1148-1205), array in, array out ----
+def detect_fast(img, mask=None, n_features: int = 1000, fast=None, ctx=None) -> dict:
+    """pagk_detect_fast (host buffers): FAST-9/16 in cells of about 30 pixels with the fall-back threshold, the quadtree
+    down to n_features nodes, the mask test -> dict(keypoints (n x 2 float32, list order), response (n), info and its
+    words by name)."""
+    return _device_context(ctx).detect_fast(np.ascontiguousarray(img, np.uint8), mask, n_features, fast)
+
+
+def frame_handover_fast(params, img, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, fast=None,
+                        state=None, ctx=None) -> dict:
+    """pagk_frame_handover_fast (host buffers): the hand-over with the candidates = detect_fast(img, no mask) ->
+    dict(keys, keys_un, keys_normal, index_in_last, live, mask, state, info)."""
+    return _device_context(ctx).frame_handover_fast(params, np.ascontiguousarray(img, np.uint8), cap, target_n,
+                                                    new_point_threshold, status, pt_predict, pt_predict_un, fast=fast,
+                                                    state=state)

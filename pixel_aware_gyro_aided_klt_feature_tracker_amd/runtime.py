@@ -526,7 +526,9 @@ class SequenceTracker:
     detector (a capi.DetectParams) closes the loop: the hand-over becomes pagk_frame_handover_detect_device, which
     detects the top-up on the current frame under the mask it has just built (Frame::DetectKeyPoints, src/frame.cpp:
     156-218), so start() and step() take no candidate list and a sequence starts with no keypoints from outside.
-    detector=None is the loop with the application's own candidates.
+    detector=None is the loop with the application's own candidates.  A capi.FastParams as the detector selects the
+    branch the reference's front-ends take instead (ORBextractor::DetectFeatures, src/ORBextractor.cc:1148-1205: FAST in
+    cells, then the quadtree): the hand-over becomes pagk_frame_handover_fast_device.
 
     rectify = (map_x, map_y, rectify_params, (src_height, src_width)) puts the reference's per-frame cv::remap and the
     RGB-to-gray step of Frame::Frame (Examples/Demo/RealSenseD435i.cpp:202, src/frame.cpp:81-87) in front of the pyramid,
@@ -538,7 +540,7 @@ class SequenceTracker:
 
     def __init__(self, params: capi.Params, width: int, height: int, cap: int, target_n: int, new_point_ratio: float,
                  fit_params: "capi.FitParams | None" = None, *, device: int = 0, cand_cap: int = 1024, sigma: float = 1.0,
-                 detector: "capi.DetectParams | None" = None, rectify=None):
+                 detector: "capi.DetectParams | capi.FastParams | None" = None, rectify=None):
         if not torch.cuda.is_available():
             raise RuntimeError("SequenceTracker needs a HIP device (torch.cuda.is_available() is False)")
         if cap < target_n or target_n < 1 or (detector is None and cand_cap < 1):
@@ -638,6 +640,12 @@ class SequenceTracker:
         self.ctx.frame_set_device(slot, self.d_in["img"].data_ptr(), self.w, self.h, self.w, self.params.pyramids)
 
     def _handover(self, status, pp, ppu, dst, slot: int):
+        if isinstance(self.detector, capi.FastParams):   # FAST in cells and the quadtree on the frame in `slot`
+            self.ctx.frame_handover_fast_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold,
+                                                status, pp, ppu, self.detector, slot, dst["keys"], dst["keys_un"],
+                                                dst["keys_normal"], dst["index_in_last"], dst["live"], None,
+                                                self.state, self.info)
+            return
         if self.detector is not None:   # the candidates are detected on the frame in `slot`, under this call's mask
             self.ctx.frame_handover_detect_device(self.params, self.w, self.h, self.cap, self.target_n, self.threshold,
                                                   status, pp, ppu, self.detector, slot, dst["keys"], dst["keys_un"],
