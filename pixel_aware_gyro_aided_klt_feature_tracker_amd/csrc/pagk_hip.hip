@@ -4,16 +4,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/pagk.h"
 #include "pagk_kernels.h"
 #include "pagk_layout.h"
+#include "pagk_select.h"
 
 using namespace pagk;
 
@@ -71,8 +74,9 @@ struct pagk_ctx {
     int fit_n = 0, fit_iters = 0;  // what buf[FIT]'s layout was computed for
     int rect_w = 0, rect_h = 0, rect_wp = 0;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
-    int quad_capacity[3] = {0, 0, 0};  // resident waves of k_track_quad<2 / 4 / 7> (occupancy x CUs): the hand-over rule's "round"
-    int rows_capacity[3] = {0, 0, 0};  // resident waves of k_track_rows<2 / 4 / 7> on this device (occupancy x CUs)
+    // per half patch (0 = not asked yet), the resident waves (occupancy x CUs) on this device of ...
+    int quad_capacity[PAGK_MAX_HALF_PATCH + 1] = {};  // ... the generic whole-feature k_track_quad: the hand-over rule's "round"
+    int rows_capacity[PAGK_MAX_HALF_PATCH + 1] = {};  // ... k_track_rows
     int rows_waves_cap = 0;            // PAGK_ROWS_WAVES: upper bound of that grid (tests: a small grid, a long queue)
     int *susp_count_dev = nullptr;  // the hand-over count of the last launch that used one (in buf[SUSP] or in buf[LV])
     // pagk_track_device_batch (lead context): the BatchStream array of a launch and its pinned source.  The copy to the
@@ -133,7 +137,8 @@ struct pagk_ctx {
     bool last_handover = false;  // the last tracking launch used the hand-over (pagk_last_handover)
     int concurrency = 1;    // pagk_set_concurrency: contexts like this one running at the same time on the device
     int last_variant = -1;  // variant the last tracking launch used (pagk_last_variant)
-    // auto-selection thresholds, measured on MI355X at h = 10 (tools/sweep_n.py, profiles/r03_sweep_n.log): after round
+    // auto-selection thresholds (the rule that applies them: select_variant in pagk_select.h, as a table in DESIGN.md
+    // section 4.3), measured on MI355X at h = 10 (tools/sweep_n.py, profiles/r03_sweep_n.log): after round
     // 3's instruction diet the 4-wave DPP kernel is the fastest up to ~5000 features (it used to lose to the 2-wave MFMA
     // variant from 2500; that variant no longer wins at any size and is selected explicitly only), one wave per feature
     // wins between ~5000 and ~7000, four features per wave from there.  Later in round 3: four features per wave with
@@ -490,18 +495,6 @@ void fill_level(DevLevel &d, const FrameSlot &s, int l)
     d.frows_m1 = (float)(h - 1);
 }
 
-// pyr / pyr_blocks / pyr_done: optionally, another slot's pyramid to be built by trailing workgroups of the
-// tracking launch (k_track_block_pyr).  Honoured when the 4-wave kernel is the one selected; *pyr_done tells the
-// caller whether it was (otherwise the caller launches the pyramid itself).
-// Hand-over budget of a four-features-per-wave launch of `waves` wavefronts.  The hand-over pays where the launch ends
-// with an exposed tail -- between half a round and 1.25 rounds of resident waves (quad_capacity: the kernel's occupancy
-// on this device x its CU count; 16 x 256 on MI355X): a handful of features
-// with 3-5x the mean iteration count would otherwise each keep a wave alive long after the rest has finished
-// (configs[3], 20000 features: -6 %; 8000: -4 %).  With a fuller second round the first round's stragglers are already
-// hidden behind it and the finisher only displaces throughput waves (30000: +8 %), and a context that shares the device
-// (pagk_set_concurrency) has other launches to fill its tail.  profiles/r02_ab_runs.md.
-// Resident waves of k_track_quad<NCH> on this device: the kernel's own occupancy (registers, its 10000 B of LDS) times
-// the CU count, asked once per context and patch size.
 // A wave of a one-level-per-wave launch that gave up waiting for the level above (never expected: the wait is on a wave
 // that started earlier), or a solving wave of the pipelined 4-wave body that gave up waiting for the other chain wave's
 // sums, leaves results that must not be used.
@@ -515,20 +508,104 @@ int lv_check(pagk_ctx *ctx)
     return PAGK_OK;
 }
 
-int quad_capacity(pagk_ctx *ctx, int half)
+// The tracking kernels of one half patch, [lean] where a kernel has both forms: LEAN for the reference's defaults (no
+// regularisation penalty, solver_variant 0 -- both compile-time facts there), generic for everything else.  Null where
+// a kernel is not instantiated for the patch size: all but the 4-wave kernel exist for the common sizes only
+// (pagk_select.h), block5 for h = 10, mfma and rows in a -DPAGK_ALL_VARIANTS build.
+using TrackFn = void (*)(TrackArgs);
+struct TrackKernels {
+    TrackFn block[2] = {}, block5 = nullptr;         // 4-wave workgroup per feature; its build for five workgroups per CU
+    void (*block_pyr[2])(TrackArgs, PyrArgs) = {};   // ... with another frame's pyramid built by trailing workgroups
+    TrackFn resume[2] = {}, resume_live[2] = {};     // the hand-over's sweep and live finisher
+    TrackFn wave[2] = {};                            // one wave per feature
+    TrackFn quad[2] = {}, levels[2] = {}, batch[2] = {};  // four features per wave: whole features, one level per wave, ... of k streams
+    TrackFn relaxed = nullptr;                       // relaxed-order experiment
+    TrackFn mfma[2] = {}, rows = nullptr;            // 2-wave workgroup; four independent rows per wave
+};
+
+template <int H>
+constexpr TrackKernels track_kernels()
 {
-    const int slot = half == 5 ? 0 : (half == 7 ? 1 : 2);
-    if (ctx->quad_capacity[slot] == 0) {
-        int per_cu = 0;
-        hipError_t e = half == 5   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_quad<2>, 64, 0)
-                       : half == 7 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_quad<4>, 64, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_quad<7>, 64, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 16;
-        ctx->quad_capacity[slot] = per_cu * (ctx->cus > 0 ? ctx->cus : 256);
+    constexpr PatchShape s = patch_shape(H);
+    TrackKernels k;
+    k.block[0] = k_track_block<s.nr, s.tail>;
+    k.block[1] = k_track_block<s.nr, s.tail, 4, false, false, true>;
+    if constexpr (H == 10) k.block5 = k_track_block5<s.nr, s.tail, true>;
+    if constexpr (common_patch(H)) {
+        k.block_pyr[0] = k_track_block_pyr<s.nr, s.tail>;
+        k.block_pyr[1] = k_track_block_pyr<s.nr, s.tail, true>;
+        k.resume[0] = k_track_resume<s.nr, s.tail>;
+        k.resume[1] = k_track_resume<s.nr, s.tail, true>;
+        k.resume_live[0] = k_track_resume_live<s.nr, s.tail>;
+        k.resume_live[1] = k_track_resume_live<s.nr, s.tail, true>;
+        k.wave[0] = k_track_wave<s.nch, s.tail>;
+        k.wave[1] = k_track_wave<s.nch, s.tail, true>;
+        k.quad[0] = k_track_quad<s.nch>;
+        k.quad[1] = k_track_quad<s.nch, true>;
+        k.levels[0] = k_track_quad<s.nch, false, true>;
+        k.levels[1] = k_track_quad<s.nch, true, true>;
+        k.batch[0] = k_track_quad<s.nch, false, true, true>;
+        k.batch[1] = k_track_quad<s.nch, true, true, true>;
+        k.relaxed = k_track_block<s.nr, s.tail, 4, false, true>;
+#ifdef PAGK_ALL_VARIANTS
+        k.mfma[0] = k_track_block<s.mfma_nr, s.tail, 2, true>;
+        k.mfma[1] = k_track_block<s.mfma_nr, s.tail, 2, true, false, true>;
+        k.rows = k_track_rows<s.nch>;
+#endif
     }
-    return ctx->quad_capacity[slot];
+    return k;
 }
 
+template <int... H0>
+constexpr std::array<TrackKernels, sizeof...(H0)> track_table(std::integer_sequence<int, H0...>)
+{
+    return {track_kernels<H0 + 1>()...};
+}
+constexpr auto kTrackTable = track_table(std::make_integer_sequence<int, PAGK_MAX_HALF_PATCH>{});
+const TrackKernels &track_kernels_of(int half) { return kTrackTable[(size_t)half - 1]; }   // half: 1..15 (check_params)
+
+#ifdef PAGK_ALL_VARIANTS
+constexpr bool kAllVariants = true;
+#else
+constexpr bool kAllVariants = false;   // variants 2 and 6 are not in this build (pagk_has_variant)
+#endif
+
+// One launch of a tracking kernel; a kernel the table does not have for this patch size is an error, not a crash.
+hipError_t launch(TrackFn kern, int grid, int block, size_t lds, hipStream_t stream, const TrackArgs &a)
+{
+    if (!kern) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a);
+    return hipGetLastError();
+}
+
+// What select_variant (pagk_select.h) reads of a context and its parameters, for a launch of n features.
+SelectIn select_in(const pagk_ctx *ctx, const pagk_params *p, long long n)
+{
+    return {ctx->kernel, p->half_patch, p->calculate_ncc != 0, p->pyramids, p->iterations, n, ctx->concurrency,
+            ctx->lv_error != nullptr, ctx->levels_shared, ctx->mfma_min_features, ctx->wave_min_features,
+            ctx->quad_min_features, ctx->levels_min_features, kAllVariants};
+}
+
+// Resident waves of k_track_quad<NCH> on this device: the kernel's own occupancy (registers, its 10000 B of LDS) times
+// the CU count, asked once per context and patch size.
+int quad_capacity(pagk_ctx *ctx, int half)
+{
+    if (ctx->quad_capacity[half] == 0) {
+        int per_cu = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, track_kernels_of(half).quad[0], 64, 0);
+        if (e != hipSuccess || per_cu <= 0) per_cu = 16;
+        ctx->quad_capacity[half] = per_cu * (ctx->cus > 0 ? ctx->cus : 256);
+    }
+    return ctx->quad_capacity[half];
+}
+
+// Hand-over budget of a four-features-per-wave launch of `waves` wavefronts.  The hand-over pays where the launch ends
+// with an exposed tail -- between half a round and 1.25 rounds of resident waves (quad_capacity: the kernel's occupancy
+// on this device x its CU count; 16 x 256 on MI355X): a handful of features
+// with 3-5x the mean iteration count would otherwise each keep a wave alive long after the rest has finished
+// (configs[3], 20000 features: -6 %; 8000: -4 %).  With a fuller second round the first round's stragglers are already
+// hidden behind it and the finisher only displaces throughput waves (30000: +8 %), and a context that shares the device
+// (pagk_set_concurrency) has other launches to fill its tail.  profiles/r02_ab_runs.md.
 int quad_budget_for(pagk_ctx *ctx, int waves, int iterations, int levels, int half)
 {
     if (ctx->quad_budget >= 0) return ctx->quad_budget;
@@ -623,6 +700,149 @@ int quad_workspace(pagk_ctx *ctx, size_t need, const LevelsLayout *lvl, TrackArg
     return PAGK_OK;
 }
 
+// Variant 6 (pagk_rows_kernel.h): four features per wave with the four rows of a wave independent + a work queue.
+int launch_rows(pagk_ctx *ctx, const TrackKernels &k, int n, TrackArgs &a)
+{
+    int &capacity = ctx->rows_capacity[a.half];
+    if (capacity == 0) {
+        int per_cu = 0, cus = 0;
+        HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.rows, 64, 0));
+        HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        capacity = per_cu * cus > 0 ? per_cu * cus : 1024;
+    }
+    // a resident grid: every wave starts at once, rows pull the features past 4 * grid from the queue
+    int waves = (n + 3) / 4 < capacity ? (n + 3) / 4 : capacity;
+    if (ctx->rows_waves_cap > 0 && waves > ctx->rows_waves_cap) waves = ctx->rows_waves_cap;
+    const size_t need = (size_t)waves * 4 * patch_shape(a.half).nch * 64 * sizeof(float);
+    if (int gr = reserve(ctx, ctx->buf[pagk_ctx::QUAD_WS], need, NOT_IN_CAPTURE_NOR_UNDER_GRAPH,
+                         "the row kernel's workspace", kLargestLaunchFirst)) return gr;
+    a.ws = static_cast<float *>(ctx->buf[pagk_ctx::QUAD_WS].ptr);
+    a.queue = static_cast<int *>(ctx->queue);
+    HIPCHK(ctx, hipMemsetAsync(a.queue, 0, 4, ctx->stream));
+    HIPCHK(ctx, launch(k.rows, waves, 64, 0, ctx->stream, a));
+    return PAGK_OK;
+}
+
+// Variants 5 and 7 (pagk_quad_kernel.h): four features per wave -- whole features per wave, or (use_levels) one pyramid
+// level per wave (pyramids x ceil(n / 4) waves) -- with the hand-over of long features to the 4-wave kernel.
+int launch_quad(pagk_ctx *ctx, const pagk_params *p, const TrackKernels &k, bool lean, bool use_levels, int n, TrackArgs &a)
+{
+    const int nch = patch_shape(a.half).nch, nq = (n + 3) / 4, waves = use_levels ? nq * p->pyramids : nq;
+    const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
+    const LevelsLayout lvl = levels_layout((size_t)n, (size_t)nq, p->pyramids);
+    uint8_t *lb = nullptr;
+    if (int gr = quad_workspace(ctx, need, use_levels ? &lvl : nullptr, &a, &lb)) return gr;
+    a.susp_polls = ctx->finisher_polls;
+    // continuation buffers; the hand-over needs the 4-wave kernel's LDS (<= 48 KB at these patch sizes)
+    bool live_ok = true;
+    const int budget = use_levels ? levels_budget_for(ctx, nq, p->iterations, p->pyramids, a.half, &live_ok)
+                                  : quad_budget_for(ctx, nq, p->iterations, p->pyramids, a.half);
+    const bool handover = budget > 0;
+    ctx->last_handover = handover;
+    if (handover) {
+        // the continuation buffers: inside the level workspace, or -- whole features per wave -- a block of their own
+        if (use_levels) {
+            a.susp_count = reinterpret_cast<int *>(lb + lvl.susp_count);
+            a.susp_list = reinterpret_cast<int *>(lb + lvl.susp_list);
+            a.susp_state = reinterpret_cast<SuspState *>(lb + lvl.susp_state);
+        } else {
+            const size_t sizes[3] = {kSuspCountBytes, (size_t)n * 4, (size_t)n * sizeof(SuspState)};
+            const Layout<3> lay(sizes);
+            DevBuf &susp = ctx->buf[pagk_ctx::SUSP];
+            if (int gr = reserve(ctx, susp, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the continuation buffers",
+                                 kLargestLaunchFirst)) return gr;
+            a.susp_count = lay.at<int>(susp.ptr, 0);
+            a.susp_list = lay.at<int>(susp.ptr, 1);
+            a.susp_state = lay.at<SuspState>(susp.ptr, 2);
+        }
+        a.iter_budget = budget;
+        a.susp_waves = nq;   // the waves that report their end: a quad's last-level wave / all of them
+        a.susp_lone = ctx->susp_lone;
+        ctx->susp_count_dev = a.susp_count;
+    }
+    // what must be zero before the launch: counters and ready lists, the hand-over's count and list
+    if (use_levels)
+        HIPCHK(ctx, hipMemsetAsync(lb, 0, handover ? lvl.susp_list + (size_t)n * 4 : lvl.susp_count, ctx->stream));
+    else if (handover)
+        HIPCHK(ctx, hipMemsetAsync(a.susp_count, 0, kSuspCountBytes + (size_t)n * 4, ctx->stream));
+    // the live finisher runs beside the throughput kernel, on the context's auxiliary stream (inside a graph
+    // capture the auxiliary stream joins the capture through the fork event: a parallel branch of the graph)
+    const bool live = handover && live_ok && ctx->finisher_wgs > 0 && ctx->aux_stream;
+    // inside pagk_graph_begin's capture the finisher is not a node of the graph but a launch of its own between
+    // two segments of it (see pagk_ctx::GraphSeg); PAGK_GRAPH_BRANCH=1 keeps the old parallel-branch form (tests)
+    const bool segmented = live && ctx->capturing && !getenv("PAGK_GRAPH_BRANCH");
+    int fin_seg = -1;
+    if (segmented) {
+        if (int sr = capture_split(ctx)) return sr;
+        ctx->cap_segs.emplace_back();
+        ctx->cap_segs.back().kind = pagk_ctx::GraphSeg::FINISHER;   // (filled in below, once its arguments exist)
+        fin_seg = (int)ctx->cap_segs.size() - 1;
+    } else if (live) {
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+    }
+    HIPCHK(ctx, launch(use_levels ? k.levels[lean] : k.quad[lean], waves, 64, 0, ctx->stream, a));
+    TrackArgs af = a;   // what the latency kernels get
+#ifdef PAGK_STAMPS
+    if (af.dbg) af.dbg += (size_t)16 * (waves - nq);  // (diagnostic build: their records follow the throughput waves')
+#endif
+    const size_t lds = track_block_lds_bytes(a.half);
+    if (live) {
+        if (segmented) {   // remembered, not launched: pagk_graph_launch issues it beside the kernel's segment
+            pagk_ctx::GraphSeg &fs = ctx->cap_segs[(size_t)fin_seg];
+            fs.fn = reinterpret_cast<const void *>(k.resume_live[lean]);
+            fs.args = af;
+            fs.grid = ctx->finisher_wgs;
+            fs.lds = lds;
+            // the kernel's own segment ends here; what follows (the sweep, whatever the caller records next) waits
+            // for the finisher at replay
+            if (int sr = capture_split(ctx)) return sr;
+            ctx->cap_segs.emplace_back();
+            ctx->cap_segs.back().kind = pagk_ctx::GraphSeg::JOIN;
+        } else {
+            HIPCHK(ctx, launch(k.resume_live[lean], ctx->finisher_wgs, kBlock, lds, ctx->aux_stream, af));
+            HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        }
+    }
+    // the sweep: the latency kernel finishes what is still waiting in the list (a fixed grid walks it)
+    if (handover) HIPCHK(ctx, launch(k.resume[lean], live ? 64 : (n < 1024 ? n : 1024), kBlock, lds, ctx->stream, af));
+    return PAGK_OK;
+}
+
+// Variant 0: the 4-wave workgroup per feature, for every patch size.  pyr / pyr_blocks / pyr_done: see launch_track.
+int launch_block(pagk_ctx *ctx, const TrackKernels &k, bool lean, int n, const TrackArgs &a, const PyrArgs *pyr,
+                 int pyr_blocks, bool *pyr_done)
+{
+    const size_t lds = track_block_lds_bytes(a.half);
+    if (pyr && pyr_blocks > 0 && k.block_pyr[lean] && lds <= 48 * 1024) {
+        hipLaunchKernelGGL(k.block_pyr[lean], dim3(n + pyr_blocks), dim3(kBlock), lds, ctx->stream, a, *pyr);
+        HIPCHK(ctx, hipGetLastError());
+        if (pyr_done) *pyr_done = true;
+        return PAGK_OK;
+    }
+    // h = 10, lean, several rounds of workgroups: the build for five workgroups per CU
+    // ... and a launch that five workgroups per CU hold at once but four do not (1025..1280 features on 256 CUs:
+    // one round instead of two, 104 -> 97 us at 1100 features; from 1300 on the pipelined kernel is
+    // equal or faster again, profiles/r04_block5_sweep_1100_3000.log)
+    const bool five = lean && k.block5 && select_block5(n, ctx->block5_min_features, ctx->block5_window, ctx->cus);
+    const TrackFn kern = five ? k.block5 : k.block[lean];
+    if (lds > 48 * 1024) {
+        // more than 48 KB of dynamic LDS (h >= 14) needs the attribute; set it once per kernel and device
+        static thread_local bool configured[PAGK_MAX_HALF_PATCH + 1][2][16] = {};
+        bool &done = configured[a.half][lean][ctx->device & 15];
+        if (!done) {
+            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            done = true;
+        }
+    }
+    HIPCHK(ctx, launch(kern, n, kBlock, lds, ctx->stream, a));
+    return PAGK_OK;
+}
+
+// pyr / pyr_blocks / pyr_done: optionally, another slot's pyramid to be built by trailing workgroups of the
+// tracking launch (k_track_block_pyr).  Honoured when the 4-wave kernel is the one selected; *pyr_done tells the
+// caller whether it was (otherwise the caller launches the pyramid itself).
 int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const FrameSlot &sc, int n,
                  const float *d_pt_ref, const float *d_pt_init, const float *d_affine, const uint8_t *d_status,
                  const pagk_outputs *o, const PyrArgs *pyr = nullptr, int pyr_blocks = 0, bool *pyr_done = nullptr)
@@ -660,279 +880,27 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
 
     if (ctx->ev_trk[0] && !in_capture(ctx)) HIPCHK(ctx, hipEventRecord(ctx->ev_trk[0], ctx->stream));
     if (n > 0) {
-        const int Pm = (2 * a.half + 1) * (2 * a.half + 1);
-        // MFMA variant: instantiated for the common patch sizes; chosen explicitly (kernel 2) or,
-        // by default, when the launch has more features than can be resident at once
-        const bool mfma_ok = a.half == 5 || a.half == 7 || a.half == 10;
-        // four features per wave: no NCC epilogue of its own (calc_ncc launches run the one-wave-per-feature variant)
-        // ... and with the four rows of a wave independent + a work queue (pagk_rows_kernel.h)
         ctx->last_handover = false;
         // the reference's defaults (no regularisation penalty, solver_variant 0) run kernels in which both are
         // compile-time facts (LEAN); everything else runs the generic instantiations
         const bool lean = !a.penalty && a.solver == 0;
-        const long long n_sel = (long long)n * ctx->concurrency;  // what the automatic thresholds are applied to
-#ifdef PAGK_ALL_VARIANTS
-        const bool use_rows = mfma_ok && !a.calc_ncc && a.iterations >= 1 && ctx->kernel == 6;
-#else
-        const bool use_rows = false;   // (variant (e) is not in this build: pagk_set_kernel(ctx, 6) was refused)
-#endif
-        // four features per wave, one level per wave (needs more than one level to differ from the quad kernel)
-        const bool use_levels = mfma_ok && !a.calc_ncc && p->pyramids >= 2 && ctx->lv_error &&
-                                (ctx->kernel == 7 || (ctx->kernel == 0 && (ctx->concurrency == 1 || ctx->levels_shared) &&
-                                                      n_sel >= ctx->levels_min_features));
-        const bool quad_like = ctx->kernel == 5 || ctx->kernel == 6 || ctx->kernel == 7;
-        const bool use_quad = !use_rows && !use_levels && mfma_ok && !a.calc_ncc && (quad_like || (ctx->kernel == 0 && n_sel >= ctx->quad_min_features));
-        const bool use_wave = !use_quad && !use_rows && !use_levels && mfma_ok && (ctx->kernel == 3 || quad_like || (ctx->kernel == 0 && n_sel >= ctx->wave_min_features));
-#ifdef PAGK_ALL_VARIANTS
-        const bool use_mfma = !use_wave && mfma_ok && (ctx->kernel == 2 || (ctx->kernel == 0 && n_sel >= ctx->mfma_min_features));
-#else
-        const bool use_mfma = false;   // (variant (b) is not in this build)
-#endif
-        ctx->last_variant = ctx->kernel == 1 ? 1 : use_levels ? 7 : use_rows ? 6 : (use_quad ? 5 : (use_wave ? 3 : ((ctx->kernel == 4 && mfma_ok) ? 4 : (use_mfma ? 2 : 0))));
-        if (ctx->kernel == 1) {
-            hipLaunchKernelGGL(k_track_thread, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a);
-#ifdef PAGK_ALL_VARIANTS
-        } else if (use_rows) {
-            const int nch = (Pm + 63) / 64;
-            const int slot = a.half == 5 ? 0 : (a.half == 7 ? 1 : 2);
-            if (ctx->rows_capacity[slot] == 0) {
-                int per_cu = 0, cus = 0;
-                hipError_t oe = a.half == 5   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_rows<2>, 64, 0)
-                                : a.half == 7 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_rows<4>, 64, 0)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_rows<7>, 64, 0);
-                HIPCHK(ctx, oe);
-                HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-                ctx->rows_capacity[slot] = per_cu * cus > 0 ? per_cu * cus : 1024;
-            }
-            // a resident grid: every wave starts at once, rows pull the features past 4 * grid from the queue
-            int waves = (n + 3) / 4 < ctx->rows_capacity[slot] ? (n + 3) / 4 : ctx->rows_capacity[slot];
-            if (ctx->rows_waves_cap > 0 && waves > ctx->rows_waves_cap) waves = ctx->rows_waves_cap;
-            const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
-            if (int gr = reserve(ctx, ctx->buf[pagk_ctx::QUAD_WS], need, NOT_IN_CAPTURE_NOR_UNDER_GRAPH,
-                                 "the row kernel's workspace", kLargestLaunchFirst)) return gr;
-            a.ws = static_cast<float *>(ctx->buf[pagk_ctx::QUAD_WS].ptr);
-            a.queue = static_cast<int *>(ctx->queue);
-            HIPCHK(ctx, hipMemsetAsync(a.queue, 0, 4, ctx->stream));
-            auto launch = [&](auto kern) -> hipError_t {
-                hipLaunchKernelGGL(kern, dim3(waves), dim3(64), 0, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e = hipErrorInvalidValue;
-            if (a.half == 5) e = launch(k_track_rows<2>);
-            else if (a.half == 7) e = launch(k_track_rows<4>);
-            else if (a.half == 10) e = launch(k_track_rows<7>);
-            HIPCHK(ctx, e);
-#endif
-        } else if (use_quad || use_levels) {
-            // four features per wave (pagk_quad_kernel.h): whole features per wave, or -- LEVELS -- one pyramid level per
-            // wave (pyramids x ceil(n / 4) waves)
-            const int nch = (Pm + 63) / 64, nq = (n + 3) / 4, waves = use_levels ? nq * p->pyramids : nq;
-            const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
-            const LevelsLayout lvl = levels_layout((size_t)n, (size_t)nq, p->pyramids);
-            uint8_t *lb = nullptr;
-            if (int gr = quad_workspace(ctx, need, use_levels ? &lvl : nullptr, &a, &lb)) return gr;
-            a.susp_polls = ctx->finisher_polls;
-            // continuation buffers; the hand-over needs the 4-wave kernel's LDS (<= 48 KB at these patch sizes)
-            bool live_ok = true;
-            const int budget = use_levels ? levels_budget_for(ctx, nq, p->iterations, p->pyramids, a.half, &live_ok)
-                                          : quad_budget_for(ctx, nq, p->iterations, p->pyramids, a.half);
-            const bool handover = budget > 0;
-            ctx->last_handover = handover;
-            if (handover) {
-                // the continuation buffers: inside the level workspace, or -- whole features per wave -- a block of their own
-                if (use_levels) {
-                    a.susp_count = reinterpret_cast<int *>(lb + lvl.susp_count);
-                    a.susp_list = reinterpret_cast<int *>(lb + lvl.susp_list);
-                    a.susp_state = reinterpret_cast<SuspState *>(lb + lvl.susp_state);
-                } else {
-                    const size_t sizes[3] = {kSuspCountBytes, (size_t)n * 4, (size_t)n * sizeof(SuspState)};
-                    const Layout<3> lay(sizes);
-                    DevBuf &susp = ctx->buf[pagk_ctx::SUSP];
-                    if (int gr = reserve(ctx, susp, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the continuation buffers",
-                                         kLargestLaunchFirst)) return gr;
-                    a.susp_count = lay.at<int>(susp.ptr, 0);
-                    a.susp_list = lay.at<int>(susp.ptr, 1);
-                    a.susp_state = lay.at<SuspState>(susp.ptr, 2);
-                }
-                a.iter_budget = budget;
-                a.susp_waves = nq;   // the waves that report their end: a quad's last-level wave / all of them
-                a.susp_lone = ctx->susp_lone;
-                ctx->susp_count_dev = a.susp_count;
-            }
-            // what must be zero before the launch: counters and ready lists, the hand-over's count and list
-            if (use_levels)
-                HIPCHK(ctx, hipMemsetAsync(lb, 0, handover ? lvl.susp_list + (size_t)n * 4 : lvl.susp_count, ctx->stream));
-            else if (handover)
-                HIPCHK(ctx, hipMemsetAsync(a.susp_count, 0, kSuspCountBytes + (size_t)n * 4, ctx->stream));
-            // the live finisher runs beside the throughput kernel, on the context's auxiliary stream (inside a graph
-            // capture the auxiliary stream joins the capture through the fork event: a parallel branch of the graph)
-            const bool live = handover && live_ok && ctx->finisher_wgs > 0 && ctx->aux_stream;
-            // inside pagk_graph_begin's capture the finisher is not a node of the graph but a launch of its own between
-            // two segments of it (see pagk_ctx::GraphSeg); PAGK_GRAPH_BRANCH=1 keeps the old parallel-branch form (tests)
-            const bool segmented = live && ctx->capturing && !getenv("PAGK_GRAPH_BRANCH");
-            int fin_seg = -1;
-            if (segmented) {
-                if (int sr = capture_split(ctx)) return sr;
-                ctx->cap_segs.emplace_back();
-                ctx->cap_segs.back().kind = pagk_ctx::GraphSeg::FINISHER;   // (filled in below, once its arguments exist)
-                fin_seg = (int)ctx->cap_segs.size() - 1;
-            } else if (live) {
-                HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-            }
-            auto launch = [&](auto kern) -> hipError_t {
-                hipLaunchKernelGGL(kern, dim3(waves), dim3(64), 0, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e = hipErrorInvalidValue;
-            if (use_levels) {
-                if (a.half == 5) e = lean ? launch(k_track_quad<2, true, true>) : launch(k_track_quad<2, false, true>);
-                else if (a.half == 7) e = lean ? launch(k_track_quad<4, true, true>) : launch(k_track_quad<4, false, true>);
-                else if (a.half == 10) e = lean ? launch(k_track_quad<7, true, true>) : launch(k_track_quad<7, false, true>);
-            } else {
-                if (a.half == 5) e = lean ? launch(k_track_quad<2, true>) : launch(k_track_quad<2>);        // P = 121: 2 chunks of 64 pixels
-                else if (a.half == 7) e = lean ? launch(k_track_quad<4, true>) : launch(k_track_quad<4>);   // P = 225
-                else if (a.half == 10) e = lean ? launch(k_track_quad<7, true>) : launch(k_track_quad<7>);  // P = 441
-            }
-            HIPCHK(ctx, e);
-            TrackArgs af = a;   // what the latency kernels get
-#ifdef PAGK_STAMPS
-            if (af.dbg) af.dbg += (size_t)16 * (waves - nq);  // (diagnostic build: their records follow the throughput waves')
-#endif
-            if (live) {
-                const size_t lds = track_block_lds_bytes(a.half);
-                auto finisher = [&](auto kern) -> hipError_t {
-                    if (segmented) {   // remembered, not launched: pagk_graph_launch issues it beside the kernel's segment
-                        pagk_ctx::GraphSeg &fs = ctx->cap_segs[(size_t)fin_seg];
-                        fs.fn = reinterpret_cast<const void *>(kern);
-                        fs.args = af;
-                        fs.grid = ctx->finisher_wgs;
-                        fs.lds = lds;
-                        return hipSuccess;
-                    }
-                    hipLaunchKernelGGL(kern, dim3(ctx->finisher_wgs), dim3(kBlock), lds, ctx->aux_stream, af);
-                    return hipGetLastError();
-                };
-                if (a.half == 5) e = lean ? finisher(k_track_resume_live<1, 25, true>) : finisher(k_track_resume_live<1, 25>);
-                else if (a.half == 7) e = lean ? finisher(k_track_resume_live<1, 1, true>) : finisher(k_track_resume_live<1, 1>);
-                else e = lean ? finisher(k_track_resume_live<2, 25, true>) : finisher(k_track_resume_live<2, 25>);
-                HIPCHK(ctx, e);
-                if (segmented) {
-                    // the kernel's own segment ends here; what follows (the sweep, whatever the caller records next) waits
-                    // for the finisher at replay
-                    if (int sr = capture_split(ctx)) return sr;
-                    ctx->cap_segs.emplace_back();
-                    ctx->cap_segs.back().kind = pagk_ctx::GraphSeg::JOIN;
-                } else {
-                    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
-                    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-                }
-            }
-            if (handover) {
-                // the sweep: the latency kernel finishes what is still waiting in the list (a fixed grid walks it)
-                const size_t lds = track_block_lds_bytes(a.half);
-                const int grid = live ? 64 : (n < 1024 ? n : 1024);
-                auto resume = [&](auto kern) -> hipError_t {
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, ctx->stream, af);
-                    return hipGetLastError();
-                };
-                if (a.half == 5) e = lean ? resume(k_track_resume<1, 25, true>) : resume(k_track_resume<1, 25>);
-                else if (a.half == 7) e = lean ? resume(k_track_resume<1, 1, true>) : resume(k_track_resume<1, 1>);
-                else e = lean ? resume(k_track_resume<2, 25, true>) : resume(k_track_resume<2, 25>);
-                HIPCHK(ctx, e);
-            }
-        } else if (use_wave) {
-            // one wavefront per feature (pagk_wave_kernel.h)
-            const size_t lds = track_wave_lds_bytes(a.half);
-            auto launch = [&](auto kern) -> hipError_t {
-                hipLaunchKernelGGL(kern, dim3(n), dim3(64), lds, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e = hipErrorInvalidValue;
-            if (a.half == 5) e = lean ? launch(k_track_wave<2, 25, true>) : launch(k_track_wave<2, 25>);        // P = 121
-            else if (a.half == 7) e = lean ? launch(k_track_wave<4, 1, true>) : launch(k_track_wave<4, 1>);    // P = 225
-            else if (a.half == 10) e = lean ? launch(k_track_wave<7, 25, true>) : launch(k_track_wave<7, 25>);  // P = 441
-            HIPCHK(ctx, e);
-        } else if (ctx->kernel == 4 && mfma_ok) {
+        const TrackKernels &k = track_kernels_of(a.half);
+        const int variant = ctx->last_variant = select_variant(select_in(ctx, p, n));
+        int rc = PAGK_OK;
+        hipError_t e = hipSuccess;
+        switch (variant) {
+            case 1: e = launch(k_track_thread, (n + 63) / 64, 64, 0, ctx->stream, a); break;
+            case 2: e = launch(k.mfma[lean], n, 128, track_mfma_lds_bytes(a.half), ctx->stream, a); break;
+            case 3: e = launch(k.wave[lean], n, 64, track_wave_lds_bytes(a.half), ctx->stream, a); break;   // pagk_wave_kernel.h
             // relaxed-order experiment (NOT parity-exact; never chosen automatically)
-            const size_t lds = track_block_lds_bytes(a.half);
-            auto launch = [&](auto kern) -> hipError_t {
-                hipLaunchKernelGGL(kern, dim3(n), dim3(kBlock), lds, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e = hipErrorInvalidValue;
-            if (a.half == 5) e = launch(k_track_block<1, 25, 4, false, true>);
-            else if (a.half == 7) e = launch(k_track_block<1, 1, 4, false, true>);
-            else if (a.half == 10) e = launch(k_track_block<2, 25, 4, false, true>);
-            HIPCHK(ctx, e);
-#ifdef PAGK_ALL_VARIANTS
-        } else if (use_mfma) {
-            const size_t lds = track_mfma_lds_bytes(a.half);
-            auto launch = [&](auto kern) -> hipError_t {
-                hipLaunchKernelGGL(kern, dim3(n), dim3(128), lds, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e = hipErrorInvalidValue;
-            (void)Pm;
-            if (a.half == 5) e = lean ? launch(k_track_block<1, 25, 2, true, false, true>) : launch(k_track_block<1, 25, 2, true>);        // P = 121
-            else if (a.half == 7) e = lean ? launch(k_track_block<2, 1, 2, true, false, true>) : launch(k_track_block<2, 1, 2, true>);    // P = 225
-            else if (a.half == 10) e = lean ? launch(k_track_block<4, 25, 2, true, false, true>) : launch(k_track_block<4, 25, 2, true>);  // P = 441
-            HIPCHK(ctx, e);
-#endif
-        } else {
-            const int P = (2 * a.half + 1) * (2 * a.half + 1);
-            const int nr = (P + kBlock - 1) / kBlock, tail = P % 32;
-            const size_t lds = track_block_lds_bytes(a.half);
-            auto launch = [&](auto kern) -> hipError_t {
-                // > 64 KB of dynamic LDS (h >= 14) needs the attribute; set it once per kernel and device
-                static thread_local const void *configured[16] = {};
-                const void *fn = reinterpret_cast<const void *>(kern);
-                const int slot = ctx->device & 15;
-                if (lds > 48 * 1024 && configured[slot] != fn) {
-                    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (e != hipSuccess) return e;
-                    configured[slot] = fn;
-                }
-                hipLaunchKernelGGL(kern, dim3(n), dim3(kBlock), lds, ctx->stream, a);
-                return hipGetLastError();
-            };
-            // (NR, TAIL) for h = 1..15: P = (2h+1)^2 is an odd square, so P mod 32 is 1, 9, 17 or 25
-            hipError_t e = hipErrorInvalidValue;
-            if (pyr && pyr_blocks > 0 && mfma_ok && lds <= 48 * 1024) {
-                auto launch_pyr = [&](auto kern) -> hipError_t {
-                    hipLaunchKernelGGL(kern, dim3(n + pyr_blocks), dim3(kBlock), lds, ctx->stream, a, *pyr);
-                    return hipGetLastError();
-                };
-                if (a.half == 5) e = lean ? launch_pyr(k_track_block_pyr<1, 25, true>) : launch_pyr(k_track_block_pyr<1, 25>);
-                else if (a.half == 7) e = lean ? launch_pyr(k_track_block_pyr<1, 1, true>) : launch_pyr(k_track_block_pyr<1, 1>);
-                else e = lean ? launch_pyr(k_track_block_pyr<2, 25, true>) : launch_pyr(k_track_block_pyr<2, 25>);
-                HIPCHK(ctx, e);
-                if (pyr_done) *pyr_done = true;
-            } else
-            switch (nr * 100 + tail) {
-                case 101: e = lean ? launch(k_track_block<1, 1, 4, false, false, true>) : launch(k_track_block<1, 1>); break;    // h = 7
-                case 109: e = lean ? launch(k_track_block<1, 9, 4, false, false, true>) : launch(k_track_block<1, 9>); break;    // h = 1, 6
-                case 117: e = lean ? launch(k_track_block<1, 17, 4, false, false, true>) : launch(k_track_block<1, 17>); break;   // h = 3, 4
-                case 125: e = lean ? launch(k_track_block<1, 25, 4, false, false, true>) : launch(k_track_block<1, 25>); break;   // h = 2, 5
-                case 201: e = lean ? launch(k_track_block<2, 1, 4, false, false, true>) : launch(k_track_block<2, 1>); break;    // h = 8
-                case 209: e = lean ? launch(k_track_block<2, 9, 4, false, false, true>) : launch(k_track_block<2, 9>); break;    // h = 9
-                case 225:   // h = 10; several rounds of workgroups: the build for five workgroups per CU
-                    // ... and a launch that five workgroups per CU hold at once but four do not (1025..1280 features on 256 CUs:
-                    // one round instead of two, 104 -> 97 us at 1100 features; from 1300 on the pipelined kernel is
-                    // equal or faster again, profiles/r04_block5_sweep_1100_3000.log)
-                    e = lean ? ((n >= ctx->block5_min_features || (ctx->block5_window && n > 4 * ctx->cus && n <= 5 * ctx->cus))
-                                    ? launch(k_track_block5<2, 25, true>)
-                                    : launch(k_track_block<2, 25, 4, false, false, true>))
-                             : launch(k_track_block<2, 25>);
-                    break;
-                case 317: e = lean ? launch(k_track_block<3, 17, 4, false, false, true>) : launch(k_track_block<3, 17>); break;   // h = 11, 12
-                case 325: e = lean ? launch(k_track_block<3, 25, 4, false, false, true>) : launch(k_track_block<3, 25>); break;   // h = 13
-                case 409: e = lean ? launch(k_track_block<4, 9, 4, false, false, true>) : launch(k_track_block<4, 9>); break;    // h = 14
-                case 401: e = lean ? launch(k_track_block<4, 1, 4, false, false, true>) : launch(k_track_block<4, 1>); break;    // h = 15
-                default: break;
-            }
-            if (!(pyr_done && *pyr_done)) HIPCHK(ctx, e);
+            case 4: e = launch(k.relaxed, n, kBlock, track_block_lds_bytes(a.half), ctx->stream, a); break;
+            case 5:
+            case 7: rc = launch_quad(ctx, p, k, lean, variant == 7, n, a); break;
+            case 6: rc = launch_rows(ctx, k, n, a); break;
+            default: rc = launch_block(ctx, k, lean, n, a, pyr, pyr_blocks, pyr_done); break;
         }
+        if (rc) return rc;
+        HIPCHK(ctx, e);
         HIPCHK(ctx, hipGetLastError());
     }
     if (ctx->ev_trk[1] && !in_capture(ctx)) HIPCHK(ctx, hipEventRecord(ctx->ev_trk[1], ctx->stream));
@@ -1227,11 +1195,7 @@ int pagk_set_stream(pagk_ctx *ctx, void *hip_stream)
 // instantiations.
 int pagk_has_variant(int32_t which)
 {
-#ifdef PAGK_ALL_VARIANTS
-    return which >= 0 && which <= 7;
-#else
-    return which >= 0 && which <= 7 && which != 2 && which != 6;
-#endif
+    return which >= 0 && which <= 7 && (kAllVariants || (which != 2 && which != 6));
 }
 
 int pagk_set_kernel(pagk_ctx *ctx, int32_t which)
@@ -1759,9 +1723,7 @@ int pagk_track_device_batch(pagk_ctx *const *ctxs, int32_t k, const pagk_params 
         total_q += (n[j] + 3) / 4;
     }
     HIPCHK(lead, hipSetDevice(lead->device));
-    const bool mfma_ok = params->half_patch == 5 || params->half_patch == 7 || params->half_patch == 10;
-    const bool batched = mfma_ok && !params->calculate_ncc && params->pyramids >= 2 && lead->lv_error && total_q > 0 &&
-                         (lead->kernel == 7 || (lead->kernel == 0 && total_n >= lead->levels_min_features));
+    const bool batched = select_batched(select_in(lead, params, 0), total_n, total_q);
     if (!batched) {
         // every stream as its own launch on its own context (small batches, NCC launches, a forced variant)
         for (int j = 0; j < k; j++) {
@@ -1815,7 +1777,7 @@ int pagk_track_device_batch(pagk_ctx *const *ctxs, int32_t k, const pagk_params 
     HIPCHK(lead, hipMemcpyAsync(desc->dev, hb, (size_t)k * sizeof(BatchStream), hipMemcpyHostToDevice, lead->stream));
     a.batch = static_cast<const BatchStream *>(desc->dev);
     // workspaces of a one-level-per-wave launch (launch_track), for the batch's quads; no hand-over
-    const int Pm = (2 * a.half + 1) * (2 * a.half + 1), nch = (Pm + 63) / 64, nq = total_q, waves = nq * params->pyramids;
+    const int nch = patch_shape(a.half).nch, nq = total_q, waves = nq * params->pyramids;
     const size_t need = (size_t)waves * 4 * nch * 64 * sizeof(float);
     const LevelsLayout lvl = levels_layout((size_t)a.n, (size_t)nq, params->pyramids);
     uint8_t *lb = nullptr;
@@ -1823,15 +1785,7 @@ int pagk_track_device_batch(pagk_ctx *const *ctxs, int32_t k, const pagk_params 
     HIPCHK(lead, hipMemsetAsync(lb, 0, lvl.susp_count, lead->stream));
     if (lead->ev_trk[0] && !in_capture(lead)) HIPCHK(lead, hipEventRecord(lead->ev_trk[0], lead->stream));
     const bool lean = !a.penalty && a.solver == 0;
-    auto launch = [&](auto kern) -> hipError_t {
-        hipLaunchKernelGGL(kern, dim3(waves), dim3(64), 0, lead->stream, a);
-        return hipGetLastError();
-    };
-    hipError_t e = hipErrorInvalidValue;
-    if (a.half == 5) e = lean ? launch(k_track_quad<2, true, true, true>) : launch(k_track_quad<2, false, true, true>);
-    else if (a.half == 7) e = lean ? launch(k_track_quad<4, true, true, true>) : launch(k_track_quad<4, false, true, true>);
-    else e = lean ? launch(k_track_quad<7, true, true, true>) : launch(k_track_quad<7, false, true, true>);
-    HIPCHK(lead, e);
+    HIPCHK(lead, launch(track_kernels_of(a.half).batch[lean], waves, 64, 0, lead->stream, a));
     if ((rc = batch_desc_used(lead, desc)) != PAGK_OK) return rc;
     if (lead->ev_trk[1] && !in_capture(lead)) HIPCHK(lead, hipEventRecord(lead->ev_trk[1], lead->stream));
     if (!in_capture(lead)) lead->trk_timed = true;

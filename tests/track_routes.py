@@ -15,7 +15,8 @@ with P = (2h + 1)^2 pixels per patch: NR = ceil(P / (64 * WAVES)), TAIL = P mod 
 import dataclasses
 import re
 
-# (NR, TAIL) of the 4-wave kernels for every half patch the library accepts (launch_track's switch in csrc/pagk_hip.hip)
+# (NR, TAIL) of the 4-wave kernels for every half patch the library accepts (the kernel table of csrc/pagk_hip.hip
+# builds them from patch_shape in csrc/pagk_select.h; this is the independent restatement it is checked against)
 BLOCK_ARGS = {1: (1, 9), 2: (1, 25), 3: (1, 17), 4: (1, 17), 5: (1, 25), 6: (1, 9), 7: (1, 1), 8: (2, 1), 9: (2, 9),
               10: (2, 25), 11: (3, 17), 12: (3, 17), 13: (3, 25), 14: (4, 9), 15: (4, 1)}
 # the patch sizes of the throughput kernels, the continuation and the fused launch: NCH, and (NR, TAIL) of the 2-wave form
