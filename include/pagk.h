@@ -461,8 +461,8 @@ int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R
  * (:563-787), ExtractorNode::DivideNode (:505-561).  This section is that branch for nlevels = 1.  Parity with OpenCV's
  * cv::FAST is NOT claimed (it cannot be built here); the contract is this definition, bit for bit (restated in plain C in
  * tests/fast_detect_ref.c).  It is integer arithmetic throughout, so a host with OpenCV can pin it.  Multi-level ORB
- * (cv::resize at 1 / 1.2), computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and descriptors are not
- * provided.
+ * (cv::resize at 1 / 1.2) is not provided; computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and the
+ * descriptors are pagk_orb_describe_device below ("ORB descriptors and matching").
  *   input      an 8-bit image W x H (level 0 of a frame slot, read through its pitch).  At level 0 without orientation
  *              every FAST window lies inside the image: the border image of ComputePyramid is never read.  EDGE_THRESHOLD
  *              = 19: minBorder = 16, maxBorderX = W - 16, maxBorderY = H - 16.
@@ -640,6 +640,111 @@ int pagk_undistort_maps(double fx, double fy, double cx, double cy, const double
                         double new_fx, double new_fy, double new_cx, double new_cy, int32_t width, int32_t height,
                         float *map_x, float *map_y);
 
+/* ---- ORB descriptors and matching: the comparison arm of the reference's front-ends, one level ---------------------- */
+/* Both front-ends run ORBDetectAndDespMatcher::FindFeatureMatches (src/ORBDetectAndDespMatcher.cpp:55-91) on every frame
+ * pair (Examples/Demo/RealSenseD435i.cpp:282, Examples/ROS/.../feature_tracker.cpp:272): ORBextractor::operator() on both
+ * images -- ComputeKeyPointsOctTree, computeOrientation / IC_Angle (src/ORBextractor.cc:101-128, 496-503), a 7 x 7 Gaussian
+ * blur and the steered rBRIEF descriptors (:131-171, 1057-1064, 1113-1130) --, then BruteForce-Hamming matching and a
+ * distance filter.  The detector half is pagk_detect_fast_device with mask = NULL (ComputeKeyPointsOctTree for the one
+ * level the front-ends construct); this section is the describe and the match half, for nlevels = 1.
+ * Parity contract: parity with OpenCV's own arithmetic (GaussianBlur, fastAtan2, cvRound, BFMatcher) is NOT claimed (it
+ * cannot be built here); the contract is this definition, bit for bit (restated in plain C in tests/orb_ref.c).  It follows
+ * OpenCV 3.4's scalar code paths step by step and says where it is the library's own rule.
+ *   pattern    the 512 sampling points of bit_pattern_31_ (:174) are the host's: 1024 int32, x then y per point, pair q of
+ *              the descriptor = points 2q and 2q + 1.  Every coordinate lies in [-13, 13] (the reference's table spans
+ *              [-13, 12], largest radius 18.38): every rotated tap then rounds to at most 18 < EDGE_THRESHOLD = 19.
+ *   blur       (:1123-1124) a separable 7-tap kernel in Q8, w[0..3] for offsets 0, +-1, +-2, +-3, w >= 0 and
+ *              w0 + 2 (w1 + w2 + w3) == 256.  Border index r(i) = -i below 0 and 2 (n - 1) - i at or above n
+ *              (BORDER_REFLECT_101); 4 <= W, H <= 32767.  Horizontal pass, exact integers: Hx = sum_k w[|k|] src[y][r(x + k)]
+ *              (at most 65280); vertical pass: out = (sum_k w[|k|] Hx[r(y + k)][x] + 32768) >> 16, never above 255.  The
+ *              defaults 54, 49, 34, 18 are exp(-k^2 / 8) normalised, times 256 (55.32, 48.82, 33.56, 17.96), rounded to
+ *              nearest with the centre absorbing the remainder: the library's own fixed-point kernel, not OpenCV's.
+ *   centre     cx = rintf(x), cy = rintf(y), ties to even (cvRound).  A keypoint with cx outside [19, W - 19) or cy outside
+ *              [19, H - 19) (a NaN included) gets an all-zero descriptor and angle -1 and is counted in info[1]: the
+ *              reference would read out of bounds there.
+ *   angle      (:101-128) on the UNBLURRED image: m10 = sum u I(cx + u, cy + v), m01 = sum v I(cx + u, cy + v) in int32
+ *              over the disc |v| <= 15, |u| <= umax[|v|], umax = 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3 (what :478-493
+ *              evaluates to; 749 pixels).  angle = fastAtan2((float)m01, (float)m10) in degrees, OpenCV's scalar polynomial
+ *              restated in f32 with one rounding per operation: ax = |x|, ay = |y|; if ax >= ay: c = ay / (ax + e),
+ *              a = (((p7 c2 + p5) c2 + p3) c2 + p1) c with c2 = c c; else c = ax / (ay + e), a = 90 - that polynomial;
+ *              x < 0: a = 180 - a; then y < 0: a = 360 - a.  e = (float)DBL_EPSILON = 0x1p-52f; the coefficients are
+ *              OpenCV's times (float)(180 / pi) in f32: p1 = 0x1.ca44dep+5f (57.283627), p3 = -0x1.2aaddcp+4f (-18.667446),
+ *              p5 = 0x1.1d3f7ep+3f (8.9140005), p7 = -0x1.4515b2p+1f (-2.5397246).  fastAtan2(0, 0) = 0.
+ *   steering   (:136-137) r = angle * 0x1.1df46ap-6f in f32 ((float)(CV_PI / 180.f)); a = (float)cos(r), b = (float)sin(r)
+ *              with the f64 cosine and sine computed by THIS algorithm on both sides (not by a library's cos / sin, which
+ *              differ in the last place so that a tap could flip); only f64 + - * and comparisons, absolute error <= 2^-45:
+ *                x = (double)r; k = (int)(x * 0x1.45f306dc9c883p-1 + 0.5); t = (x - k * 0x1.921fb544p+0)
+ *                - k * 0x1.0b4611a626331p-34 (Cody-Waite by pi / 2 in two parts: the first product is exact); z = t t;
+ *                s = t + t (z (S1 + z (S2 + z (S3 + z (S4 + z (S5 + z S6)))))),
+ *                c = 1 - z (0.5 - z (C1 + z (C2 + z (C3 + z (C4 + z (C5 + z C6)))))) with
+ *                S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+ *                S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10,
+ *                C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+ *                C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+ *                (cos, sin) = (c, s), (-s, c), (-c, -s), (s, -c) for k & 3 = 0, 1, 2, 3.
+ *   descriptor (:139-168) on the BLURRED image: tap of point (px, py) at row cy + rintf(px b + py a), column
+ *              cx + rintf(px a - py b), f32 arithmetic with one rounding per operation (no contraction).  Bit j of byte i is
+ *              tap(point 16 i + 2 j) < tap(point 16 i + 2 j + 1), strictly.
+ *   match      (src/ORBDetectAndDespMatcher.cpp:61-65; BruteForce-Hamming, no cross-check) for each query row q < nq the
+ *              train row with the smallest popcount of the 256-bit XOR; on a tie the LOWEST index (the library's stated
+ *              rule).  nt == 0: no matches; every row gets train_idx -1, distance 257, keep 0.
+ *   filter     (:67-81) min_dist, max_dist over all matches; threshold = max(2 min_dist, match_floor); keep[q] =
+ *              distance[q] <= threshold.  Without a match (nq == 0 or nt == 0): min_dist = max_dist = 0, threshold =
+ *              match_floor (the library's rule: the reference's 10000 / 0 start values are never used there).
+ * Describe info, PAGK_ORB_INFO_WORDS int32: [0] keypoints described, [1] keypoints outside the border, the rest 0.
+ * Match info: [0] nq, [1] matches, [2] kept (the three counts the reference logs per frame, :84-89), [3] min_dist,
+ * [4] max_dist, [5] threshold, the rest 0. */
+typedef struct pagk_orb_params {
+    int32_t blur_weights[4]; /* Q8 taps for offsets 0, +-1, +-2, +-3: 54 49 34 18 (a host that has pinned OpenCV's passes its own) */
+    int32_t match_floor;     /* experiment_value 30 (src/ORBDetectAndDespMatcher.cpp:76); 0 .. 256 */
+    int32_t n_levels;        /* nlevels: must be 1 (PAGK_E_UNSUPPORTED otherwise) */
+} pagk_orb_params;
+#define PAGK_ORB_INFO_WORDS 8
+#define PAGK_ORB_MAX_ROWS 1048576
+/* 54, 49, 34, 18; 30; 1: the blur of src/ORBextractor.cc:1123-1124 in the library's fixed point and experiment_value of
+ * src/ORBDetectAndDespMatcher.cpp:76 */
+void pagk_orb_params_default(pagk_orb_params *p);
+/* PAGK_OK if *p can be run by the entry points below (src/ORBextractor.cc:1113-1130 with one level): weights >= 0 with
+ * w0 + 2 (w1 + w2 + w3) == 256, 0 <= match_floor <= 256 (PAGK_E_ARG otherwise), n_levels == 1 (PAGK_E_UNSUPPORTED
+ * otherwise).  Needs no device. */
+int pagk_orb_params_check(const pagk_orb_params *p);
+/* PAGK_OK if every one of the 1024 coordinates of a sampling pattern (bit_pattern_31_, src/ORBextractor.cc:174) lies in
+ * [-13, 13], PAGK_E_ARG otherwise or for NULL.  Needs no device. */
+int pagk_orb_pattern_check(const int32_t pattern[1024]);
+/* The sampling pattern (src/ORBextractor.cc:174, copied into `pattern` by the constructor, :442-445): a host pointer to
+ * 1024 int32, uploaded ONCE into device memory the context owns, as pagk_rectify_set_maps does with M1 / M2.  The table
+ * itself is the reference's and is not part of this library: INTEGRATION.md section 11 has the one line a host built against
+ * the reference writes.  Synchronous; PAGK_E_ARG inside a capture or for a pattern pagk_orb_pattern_check refuses. */
+int pagk_orb_set_pattern(pagk_ctx *ctx, const int32_t pattern[1024]);
+/* computeOrientation and computeDescriptors of ORBextractor::operator() (src/ORBextractor.cc:101-171, 1113-1130) for the
+ * keypoints of level 0 of frame slot `slot`, read through its pitch (for how long a slot can be read see
+ * pagk_detect_corners_device).  d_keypoints: cap x 2 float and d_n: a device count (clamped to [0, cap]) -- the layout
+ * pagk_detect_fast_device writes (its d_keypoints and d_info).  d_angle: cap float or NULL, d_desc: cap x 32 bytes on a
+ * 16-byte boundary, d_info: PAGK_ORB_INFO_WORDS int32.  Rows at or beyond the count are zeroed.  1 <= cap <=
+ * PAGK_ORB_MAX_ROWS.  Device pointers, asynchronous on the context stream, capturable; no count is read on the host.  Run
+ * it once outside a capture first (the blurred image is a buffer of the context).  PAGK_E_ARG without a pattern. */
+int pagk_orb_describe_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t slot, int32_t cap,
+                             const float *d_keypoints, const int32_t *d_n, float *d_angle /* or NULL */, uint8_t *d_desc,
+                             int32_t *d_info);
+/* The same with host buffers, synchronous (src/ORBextractor.cc:101-171, 1113-1130): keypoints n x 2 floats, angle (or
+ * NULL) n floats, desc n x 32 bytes, info (or NULL) PAGK_ORB_INFO_WORDS words.  0 <= n <= PAGK_ORB_MAX_ROWS. */
+int pagk_orb_describe(pagk_ctx *ctx, const pagk_orb_params *params, const pagk_image *img, int32_t n,
+                      const float *keypoints, float *angle, uint8_t *desc, int32_t *info);
+/* matcher->match and the distance filter of FindFeatureMatches (src/ORBDetectAndDespMatcher.cpp:61-81).  d_desc_q: cap_q x
+ * 32 bytes, d_desc_t: cap_t x 32 bytes, both on a 16-byte boundary; d_nq, d_nt: device counts (clamped to [0, cap]);
+ * d_train_idx, d_distance: cap_q int32 each, d_keep: cap_q bytes, d_info: PAGK_ORB_INFO_WORDS int32.  Rows at or beyond nq
+ * get -1 / 257 / 0.  1 <= cap_q, cap_t <= PAGK_ORB_MAX_ROWS.  The result does not depend on the order in which the
+ * workgroups run.  Device pointers, asynchronous on the context stream, capturable; nothing is read on the host.  Run it
+ * once outside a capture first (the match keys are a buffer of the context). */
+int pagk_orb_match_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t cap_q, const uint8_t *d_desc_q,
+                          const int32_t *d_nq, int32_t cap_t, const uint8_t *d_desc_t, const int32_t *d_nt,
+                          int32_t *d_train_idx, int32_t *d_distance, uint8_t *d_keep, int32_t *d_info);
+/* The same with host buffers, synchronous (src/ORBDetectAndDespMatcher.cpp:61-81): desc_q nq x 32 bytes, desc_t nt x 32
+ * bytes, train_idx / distance nq int32, keep nq bytes, info (or NULL) PAGK_ORB_INFO_WORDS words.  0 <= nq, nt <=
+ * PAGK_ORB_MAX_ROWS. */
+int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, const uint8_t *desc_q, int32_t nt,
+                   const uint8_t *desc_t, int32_t *train_idx, int32_t *distance, uint8_t *keep, int32_t *info);
+
 /* Diagnostics (never on the tracking path): the arithmetic of H.llt().solve(b) / update.norm()
  * (src/patch_match.cpp:319,343) on the caller's operands, so that a host can check on its own device -- and, with
  * Eigen at hand, against its own Eigen -- what pagk_params::solver_variant selects.
@@ -666,7 +771,8 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
  * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
  * pagk_frame_handover_detect_device, pagk_detect_fast_device,
- * pagk_frame_handover_fast_device, pagk_frame_rectify_device; and the pinned-memory forms pagk_frame_upload_pinned,
+ * pagk_frame_handover_fast_device, pagk_frame_rectify_device, pagk_orb_describe_device, pagk_orb_match_device; and the
+ * pinned-memory forms pagk_frame_upload_pinned,
  * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
  * (nothing may allocate during capture); host-buffer and synchronising entry points return PAGK_E_ARG while

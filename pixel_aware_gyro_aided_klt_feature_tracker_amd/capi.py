@@ -65,7 +65,15 @@ class RectifyParams(C.Structure):
     _fields_ = [("channels", C.c_int32), ("gray_weight", C.c_int32 * 3), ("gray_shift", C.c_int32)]
 
 
+class OrbParams(C.Structure):
+    """pagk_orb_params (include/pagk.h): the Q8 blur taps, the matcher's distance floor, the number of levels (1)."""
+    _fields_ = [("blur_weights", C.c_int32 * 4), ("match_floor", C.c_int32), ("n_levels", C.c_int32)]
+
+
 DETECT_INFO_WORDS = 8
+ORB_INFO_WORDS = 8
+ORB_DESCRIBE_INFO_FIELDS = ("described", "outside")
+ORB_MATCH_INFO_FIELDS = ("nq", "matches", "kept", "min_dist", "max_dist", "threshold")
 DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
 FAST_INFO_FIELDS = ("n_keypoints", "raw", "first_pass_empty", "empty_cells", "nodes", "passes")
 FIT_INFO_WORDS = 12
@@ -271,6 +279,23 @@ def declare(lib) -> None:
         f64 = C.c_double
         lib.pagk_undistort_maps.restype = C.c_int
         lib.pagk_undistort_maps.argtypes = [f64, f64, f64, f64, vp, i32, f64, f64, f64, f64, i32, i32, vp, vp]
+    if hasattr(lib, "pagk_orb_describe_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_orb_params_default.restype = None
+        lib.pagk_orb_params_default.argtypes = [_P(OrbParams)]
+        lib.pagk_orb_params_check.restype = C.c_int
+        lib.pagk_orb_params_check.argtypes = [_P(OrbParams)]
+        lib.pagk_orb_pattern_check.restype = C.c_int
+        lib.pagk_orb_pattern_check.argtypes = [vp]
+        lib.pagk_orb_set_pattern.restype = C.c_int
+        lib.pagk_orb_set_pattern.argtypes = [vp, vp]
+        lib.pagk_orb_describe_device.restype = C.c_int
+        lib.pagk_orb_describe_device.argtypes = [vp, _P(OrbParams), i32, i32, vp, vp, vp, vp, vp]
+        lib.pagk_orb_describe.restype = C.c_int
+        lib.pagk_orb_describe.argtypes = [vp, _P(OrbParams), _P(Image), i32, vp, vp, vp, vp]
+        lib.pagk_orb_match_device.restype = C.c_int
+        lib.pagk_orb_match_device.argtypes = [vp, _P(OrbParams), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        lib.pagk_orb_match.restype = C.c_int
+        lib.pagk_orb_match.argtypes = [vp, _P(OrbParams), i32, vp, i32, vp, vp, vp, vp, vp]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -378,6 +403,8 @@ EXPORTED_SYMBOLS = [
     "pagk_detect_fast", "pagk_frame_handover_fast_device", "pagk_frame_handover_fast", "pagk_selftest_fast_cells",
     "pagk_rectify_params_default", "pagk_rectify_params_check", "pagk_rectify_set_maps", "pagk_frame_rectify_device",
     "pagk_frame_rectify_pinned", "pagk_rectify", "pagk_undistort_maps",
+    "pagk_orb_params_default", "pagk_orb_params_check", "pagk_orb_pattern_check", "pagk_orb_set_pattern",
+    "pagk_orb_describe_device", "pagk_orb_describe", "pagk_orb_match_device", "pagk_orb_match",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -429,6 +456,36 @@ def detect_fast_bounds(width: int, height: int, n_features: int):
     if rc != 0:
         raise PagkError(rc, "pagk_detect_fast_bounds")
     return raw.value, out.value
+
+
+def orb_params_default(**overrides) -> OrbParams:
+    """pagk_orb_params_default() with overrides (blur_weights = four integers, match_floor, n_levels)."""
+    p = OrbParams()
+    load().pagk_orb_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(OrbParams._fields_):
+            raise TypeError(f"pagk_orb_params has no field {k}")
+        if k == "blur_weights":
+            v = (C.c_int32 * 4)(*[int(x) for x in v])
+        setattr(p, k, v)
+    return p
+
+
+def orb_params_check(p: OrbParams) -> int:
+    """pagk_orb_params_check: PAGK_OK, PAGK_E_ARG or PAGK_E_UNSUPPORTED (needs no device)."""
+    return int(load().pagk_orb_params_check(C.byref(p)))
+
+
+def _orb_pattern(pattern) -> np.ndarray:
+    pat = np.ascontiguousarray(pattern, np.int32).reshape(-1)
+    if pat.shape[0] != 1024:
+        raise ValueError("a sampling pattern is 512 points: 1024 integers, x then y")
+    return pat
+
+
+def orb_pattern_check(pattern) -> int:
+    """pagk_orb_pattern_check: PAGK_OK if every coordinate lies in [-13, 13] (needs no device)."""
+    return int(load().pagk_orb_pattern_check(_orb_pattern(pattern).ctypes.data))
 
 
 def rectify_params_default(**overrides) -> RectifyParams:
@@ -1069,6 +1126,57 @@ class Context:
         self._check(self.lib.pagk_rectify(self.h, C.byref(rp), raw.ctypes.data, raw.shape[1], raw.shape[0], raw.strides[0],
                                           dst.ctypes.data, dst.strides[0]), "pagk_rectify")
         return dst
+
+    # ORB descriptors and matching (src/ORBextractor.cc:101-171, 1113-1130; src/ORBDetectAndDespMatcher.cpp:55-91) ----
+    orb_params_default = staticmethod(orb_params_default)
+
+    def orb_set_pattern(self, pattern):
+        """pagk_orb_set_pattern: 512 sampling points as 1024 integers (x then y), every one in [-13, 13]."""
+        self._check(self.lib.pagk_orb_set_pattern(self.h, _orb_pattern(pattern).ctypes.data), "pagk_orb_set_pattern")
+
+    def orb_describe_device(self, orb: OrbParams, slot: int, cap: int, d_keypoints, d_n, d_angle, d_desc, d_info):
+        """pagk_orb_describe_device on level 0 of frame slot `slot` (asynchronous, capturable): d_keypoints cap x 2 float
+        and the device count d_n as pagk_detect_fast_device writes them; d_angle may be None."""
+        if d_keypoints is None or d_n is None or d_desc is None or d_info is None:
+            raise ValueError("d_keypoints, d_n, d_desc and d_info are required")
+        self._check(self.lib.pagk_orb_describe_device(self.h, C.byref(orb), slot, cap, _ptr(d_keypoints), _ptr(d_n),
+                                                      _ptr(d_angle), _ptr(d_desc), _ptr(d_info)), "pagk_orb_describe_device")
+
+    def orb_describe(self, img: np.ndarray, keypoints, orb: OrbParams | None = None) -> dict:
+        """pagk_orb_describe, host buffers -> dict(angle (n), desc (n x 32), info, and the info words by name)."""
+        orb = orb if orb is not None else orb_params_default()
+        kp = np.ascontiguousarray(keypoints, np.float32).reshape(-1, 2)
+        n = int(kp.shape[0])
+        iv = image_view(img)
+        ang, desc = np.zeros(max(n, 1), np.float32), np.zeros((max(n, 1), 32), np.uint8)
+        info = np.zeros(ORB_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_describe(self.h, C.byref(orb), C.byref(iv), n, _ptr(kp) if n else None, _ptr(ang),
+                                               _ptr(desc), _ptr(info)), "pagk_orb_describe")
+        out = dict(angle=ang[:n], desc=desc[:n], info=info)
+        out.update(zip(ORB_DESCRIBE_INFO_FIELDS, (int(v) for v in info[:2])))
+        return out
+
+    def orb_match_device(self, orb: OrbParams, cap_q: int, d_desc_q, d_nq, cap_t: int, d_desc_t, d_nt, d_train_idx,
+                         d_distance, d_keep, d_info):
+        """pagk_orb_match_device (asynchronous, capturable): best train row per query row by Hamming distance, the lowest
+        index on a tie, and the reference's distance filter; counts are device words."""
+        self._check(self.lib.pagk_orb_match_device(self.h, C.byref(orb), cap_q, _ptr(d_desc_q), _ptr(d_nq), cap_t,
+                                                   _ptr(d_desc_t), _ptr(d_nt), _ptr(d_train_idx), _ptr(d_distance),
+                                                   _ptr(d_keep), _ptr(d_info)), "pagk_orb_match_device")
+
+    def orb_match(self, desc_q, desc_t, orb: OrbParams | None = None) -> dict:
+        """pagk_orb_match, host buffers -> dict(train_idx (nq), distance (nq), keep (nq), info, and the info words by name)."""
+        orb = orb if orb is not None else orb_params_default()
+        dq = np.ascontiguousarray(desc_q, np.uint8).reshape(-1, 32)
+        dt = np.ascontiguousarray(desc_t, np.uint8).reshape(-1, 32)
+        nq, nt = int(dq.shape[0]), int(dt.shape[0])
+        idx, dist = np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1), np.int32)
+        keep, info = np.zeros(max(nq, 1), np.uint8), np.zeros(ORB_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_match(self.h, C.byref(orb), nq, _ptr(dq) if nq else None, nt, _ptr(dt) if nt else None,
+                                            _ptr(idx), _ptr(dist), _ptr(keep), _ptr(info)), "pagk_orb_match")
+        out = dict(train_idx=idx[:nq], distance=dist[:nq], keep=keep[:nq], info=info)
+        out.update(zip(ORB_MATCH_INFO_FIELDS, (int(v) for v in info[:6])))
+        return out
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------
     def graph_begin(self):

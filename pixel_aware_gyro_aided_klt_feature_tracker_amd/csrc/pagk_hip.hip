@@ -65,6 +65,9 @@ struct pagk_ctx {
         FAST,          // workspace of the FAST detector (pagk_fast_kernel.h): sized by W, H and n_features
         RECT_ENTRIES,  // rectification (pagk_rectify_kernel.h): the packed map entries of pagk_rectify_set_maps
         RECT_STAGE,    // ... and the staging buffer of a raw frame that arrives from the host
+        ORB_PATTERN,   // ORB (pagk_orb_kernel.h): the sampling pattern of pagk_orb_set_pattern, 1024 int32
+        ORB_BLUR,      // ... the blurred image of the slot being described: sized by W and H
+        ORB_KEYS,      // ... the matcher's best-match keys: sized by cap_q
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
@@ -73,6 +76,7 @@ struct pagk_ctx {
     DevBuf buf[kBufs];
     int fit_n = 0, fit_iters = 0;  // what buf[FIT]'s layout was computed for
     int rect_w = 0, rect_h = 0, rect_wp = 0;
+    bool orb_pattern_set = false;
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
     // per half patch (0 = not asked yet), the resident waves (occupancy x CUs) on this device of ...
     int quad_capacity[PAGK_MAX_HALF_PATCH + 1] = {};  // ... the generic whole-feature k_track_quad: the hand-over rule's "round"
@@ -2748,6 +2752,213 @@ int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t w
     const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
     for (int k = 0; k < 8; k++)
         if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+// ---- ORB descriptors and matching (pagk_orb_kernel.h) ----------------------------------------------------------
+namespace {
+
+int orb_params_check(const pagk_orb_params *p)
+{
+    if (!p) return PAGK_E_ARG;
+    const int32_t *w = p->blur_weights;
+    if (w[0] < 0 || w[1] < 0 || w[2] < 0 || w[3] < 0 || w[0] > 256 || w[1] > 128 || w[2] > 128 || w[3] > 128 ||
+        w[0] + 2 * (w[1] + w[2] + w[3]) != 256 || p->match_floor < 0 || p->match_floor > 256)
+        return PAGK_E_ARG;
+    return p->n_levels == 1 ? PAGK_OK : PAGK_E_UNSUPPORTED;   // cv::resize at 1 / 1.2 is not restated
+}
+
+int orb_pattern_check(const int32_t *pattern)
+{
+    if (!pattern) return PAGK_E_ARG;
+    for (int k = 0; k < kOrbPatternInts; k++)
+        if (pattern[k] < -13 || pattern[k] > 13) return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// blur -> orientation and descriptors of the keypoints of slot `s`; arguments checked by the caller
+int orb_describe_launch(pagk_ctx *ctx, const pagk_orb_params *params, const FrameSlot &s, int32_t cap, const float *d_keypoints,
+                        const int32_t *d_n, float *d_angle, uint8_t *d_desc, int32_t *d_info)
+{
+    const int wp = (s.w + 3) & ~3;
+    const size_t sizes[1] = {(size_t)wp * s.h};
+    const Layout<1> lay(sizes);
+    DevBuf &blur = ctx->buf[pagk_ctx::ORB_BLUR];
+    int rc = reserve(ctx, blur, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the blurred image of the ORB descriptors",
+                     "run the call once with this image size before capturing");
+    if (rc) return rc;
+    OrbBlurArgs b;
+    b.img = s.img0, b.pitch = s.pitch0, b.blur = lay.at<uint8_t>(blur.ptr, 0), b.info = d_info;
+    b.W = s.w, b.H = s.h, b.wp = wp;
+    b.w0 = params->blur_weights[0], b.w1 = params->blur_weights[1], b.w2 = params->blur_weights[2], b.w3 = params->blur_weights[3];
+    hipLaunchKernelGGL(k_orb_blur, dim3((unsigned)((s.w + kOrbBlurTx - 1) / kOrbBlurTx), (unsigned)((s.h + kOrbBlurTy - 1) / kOrbBlurTy)),
+                       dim3(256), 0, ctx->stream, b);
+    HIPCHK(ctx, hipGetLastError());
+    OrbDescArgs d;
+    d.img = s.img0, d.pitch = s.pitch0, d.blur = b.blur;
+    d.pattern = static_cast<const int32_t *>(ctx->buf[pagk_ctx::ORB_PATTERN].ptr);
+    d.keypoints = d_keypoints, d.n = d_n, d.angle = d_angle, d.desc = d_desc, d.info = d_info;
+    d.W = s.w, d.H = s.h, d.wp = wp, d.cap = cap;
+    hipLaunchKernelGGL(k_orb_describe, dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, ctx->stream, d);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// (slots 4 and 5 are the host-buffer forms' own)
+int orb_describe_slot(pagk_ctx *ctx, const pagk_orb_params *params, int32_t slot, int32_t cap, const float *d_keypoints,
+                      const int32_t *d_n, float *d_angle, uint8_t *d_desc, int32_t *d_info)
+{
+    if (!ctx) return PAGK_E_ARG;
+    int rc = orb_params_check(params);
+    if (rc) return rc;
+    if (slot < 0 || slot >= kSlots || cap < 1 || cap > kOrbMaxRows || !d_keypoints || !d_n || !d_desc || !d_info || !aligned16(d_desc))
+        return PAGK_E_ARG;
+    if (!ctx->orb_pattern_set) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_orb_describe: no sampling pattern set (pagk_orb_set_pattern)");
+        return PAGK_E_ARG;
+    }
+    const FrameSlot &s = ctx->slots[slot];
+    if (!fast_slot_ok(s) || s.w < 4 || s.h < 4 || s.w > 32767 || s.h > 32767) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return orb_describe_launch(ctx, params, s, cap, d_keypoints, d_n, d_angle, d_desc, d_info);
+}
+
+}  // namespace
+
+void pagk_orb_params_default(pagk_orb_params *p)
+{
+    if (!p) return;
+    p->blur_weights[0] = 54, p->blur_weights[1] = 49, p->blur_weights[2] = 34, p->blur_weights[3] = 18;
+    p->match_floor = 30;   // experiment_value, src/ORBDetectAndDespMatcher.cpp:76
+    p->n_levels = 1;
+}
+
+int pagk_orb_params_check(const pagk_orb_params *p) { return orb_params_check(p); }
+
+int pagk_orb_pattern_check(const int32_t pattern[1024]) { return orb_pattern_check(pattern); }
+
+int pagk_orb_set_pattern(pagk_ctx *ctx, const int32_t pattern[1024])
+{
+    if (!ctx || orb_pattern_check(pattern) != PAGK_OK) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_set_pattern");
+    if (in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_orb_set_pattern allocates and synchronises: not inside a stream capture");
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf &pat = ctx->buf[pagk_ctx::ORB_PATTERN];   // grows once, to its only size: graphs keep pointing at it
+    int rc = reserve(ctx, pat, kOrbPatternInts * sizeof(int32_t), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the ORB sampling pattern",
+                     "set a pattern before capturing");
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(pat.ptr, pattern, kOrbPatternInts * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->orb_pattern_set = true;
+    return PAGK_OK;
+}
+
+int pagk_orb_describe_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t slot, int32_t cap,
+                             const float *d_keypoints, const int32_t *d_n, float *d_angle, uint8_t *d_desc, int32_t *d_info)
+{
+    if (slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return orb_describe_slot(ctx, params, slot, cap, d_keypoints, d_n, d_angle, d_desc, d_info);
+}
+
+int pagk_orb_describe(pagk_ctx *ctx, const pagk_orb_params *params, const pagk_image *img, int32_t n,
+                      const float *keypoints, float *angle, uint8_t *desc, int32_t *info)
+{
+    if (!ctx || !img) return PAGK_E_ARG;
+    int rc = orb_params_check(params);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_describe");
+    if (n < 0 || n > kOrbMaxRows || (n && (!keypoints || !desc))) return PAGK_E_ARG;
+    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
+    const size_t nc = (size_t)std::max(n, 1);
+    const size_t sizes[5] = {nc * 8, 256, nc * 4, nc * 32, 256};   // keypoints | count | angle | descriptors | info
+    const Layout<5> lay(sizes);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), keypoints, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), &n, 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = orb_describe_slot(ctx, params, 4, (int32_t)nc, lay.at<float>(s.p, 0), lay.at<int32_t>(s.p, 1), lay.at<float>(s.p, 2),
+                           lay.at<uint8_t>(s.p, 3), lay.at<int32_t>(s.p, 4));
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);   // (&n is read by the copy above)
+        return rc;
+    }
+    if (n && angle) HIPCHK(ctx, hipMemcpyAsync(angle, lay.at<void>(s.p, 2), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(desc, lay.at<void>(s.p, 3), (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 4), kOrbInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_orb_match_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t cap_q, const uint8_t *d_desc_q,
+                          const int32_t *d_nq, int32_t cap_t, const uint8_t *d_desc_t, const int32_t *d_nt,
+                          int32_t *d_train_idx, int32_t *d_distance, uint8_t *d_keep, int32_t *d_info)
+{
+    if (!ctx) return PAGK_E_ARG;
+    int rc = orb_params_check(params);
+    if (rc) return rc;
+    if (cap_q < 1 || cap_q > kOrbMaxRows || cap_t < 1 || cap_t > kOrbMaxRows || !d_desc_q || !d_nq || !d_desc_t || !d_nt ||
+        !d_train_idx || !d_distance || !d_keep || !d_info || !aligned16(d_desc_q) || !aligned16(d_desc_t))
+        return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t sizes[1] = {(size_t)cap_q * 4};
+    const Layout<1> lay(sizes);
+    DevBuf &keys = ctx->buf[pagk_ctx::ORB_KEYS];
+    if ((rc = reserve(ctx, keys, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the ORB matcher's keys",
+                      "run the call once with this cap_q before capturing")))
+        return rc;
+    OrbMatchArgs a;
+    a.desc_q = d_desc_q, a.desc_t = d_desc_t, a.nq = d_nq, a.nt = d_nt, a.keys = lay.at<uint32_t>(keys.ptr, 0);
+    a.train_idx = d_train_idx, a.distance = d_distance, a.keep = d_keep, a.info = d_info;
+    a.cap_q = cap_q, a.cap_t = cap_t, a.match_floor = params->match_floor;
+    HIPCHK(ctx, hipMemsetAsync(a.keys, 0xff, sizes[0], ctx->stream));
+    const unsigned groups = (unsigned)std::min((cap_t + kOrbMatchChunk - 1) / kOrbMatchChunk, kOrbMatchMaxChunkGroups);
+    hipLaunchKernelGGL(k_orb_match, dim3((unsigned)((cap_q + 63) / 64), groups), dim3(64), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_orb_match_finish, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, const uint8_t *desc_q, int32_t nt,
+                   const uint8_t *desc_t, int32_t *train_idx, int32_t *distance, uint8_t *keep, int32_t *info)
+{
+    if (!ctx) return PAGK_E_ARG;
+    int rc = orb_params_check(params);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_match");
+    if (nq < 0 || nq > kOrbMaxRows || nt < 0 || nt > kOrbMaxRows || (nq && (!desc_q || !train_idx || !distance || !keep)) ||
+        (nt && !desc_t))
+        return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t cq = (size_t)std::max(nq, 1), ct = (size_t)std::max(nt, 1);
+    const int32_t counts[2] = {nq, nt};
+    // query rows | train rows | counts | train_idx | distance | keep | info
+    const size_t sizes[7] = {cq * 32, ct * 32, 256, cq * 4, cq * 4, cq, 256};
+    const Layout<7> lay(sizes);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    if (nq) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), desc_q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (nt) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), desc_t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 2), counts, 8, hipMemcpyHostToDevice, ctx->stream));
+    rc = pagk_orb_match_device(ctx, params, (int32_t)cq, lay.at<uint8_t>(s.p, 0), lay.at<int32_t>(s.p, 2), (int32_t)ct,
+                               lay.at<uint8_t>(s.p, 1), lay.at<int32_t>(s.p, 2) + 1, lay.at<int32_t>(s.p, 3),
+                               lay.at<int32_t>(s.p, 4), lay.at<uint8_t>(s.p, 5), lay.at<int32_t>(s.p, 6));
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);   // (counts is read by the copy above)
+        return rc;
+    }
+    if (nq) {
+        HIPCHK(ctx, hipMemcpyAsync(train_idx, lay.at<void>(s.p, 3), (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(distance, lay.at<void>(s.p, 4), (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(keep, lay.at<void>(s.p, 5), (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 6), kOrbInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }

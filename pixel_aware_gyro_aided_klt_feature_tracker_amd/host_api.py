@@ -259,3 +259,30 @@ def frame_handover_fast(params, img, cap, target_n, new_point_threshold, status,
     return _device_context(ctx).frame_handover_fast(params, np.ascontiguousarray(img, np.uint8), cap, target_n,
                                                     new_point_threshold, status, pt_predict, pt_predict_un, fast=fast,
                                                     state=state)
+
+
+# ---- the ORB baseline of the reference's front-ends for one level (src/ORBextractor.cc:1066-1145, ----
+# ---- src/ORBDetectAndDespMatcher.cpp:55-91), array in, array out ----
+def orb_extract(img, n_features: int, pattern, fast=None, orb=None, ctx=None) -> dict:
+    """ORBextractor::operator() with one level: detect_fast with no mask, then pagk_orb_describe on its keypoints ->
+    dict(keypoints (n x 2 float32), response (n), angle (n), desc (n x 32 uint8), detect_info, describe_info).  `pattern`
+    is the host's sampling table (1024 integers); it is uploaded to the context on every call."""
+    c = _device_context(ctx)
+    img = np.ascontiguousarray(img, np.uint8)
+    c.orb_set_pattern(pattern)
+    det = c.detect_fast(img, None, n_features, fast)
+    d = c.orb_describe(img, det["keypoints"], orb)
+    return dict(keypoints=det["keypoints"], response=det["response"], angle=d["angle"], desc=d["desc"],
+                detect_info=det["info"], describe_info=d["info"])
+
+
+def orb_match_pair(img_ref, img_cur, n_features: int, pattern, fast=None, orb=None, ctx=None) -> dict:
+    """ORBDetectAndDespMatcher::FindFeatureMatches: orb_extract on both images, then pagk_orb_match with the reference
+    image's descriptors as the query rows -> dict(ref, cur (the two orb_extract results), train_idx, distance, keep, info
+    and its words by name: nq, matches, kept -- the three counts the reference logs --, min_dist, max_dist, threshold)."""
+    c = _device_context(ctx)
+    ref = orb_extract(img_ref, n_features, pattern, fast, orb, c)
+    cur = orb_extract(img_cur, n_features, pattern, fast, orb, c)
+    out = c.orb_match(ref["desc"], cur["desc"], orb)
+    out.update(ref=ref, cur=cur)
+    return out
