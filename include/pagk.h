@@ -764,6 +764,16 @@ int pagk_selftest_solve(pagk_ctx *ctx, int32_t n, const double *H, const double 
  * closed form (closed[i]) beside the loop s = fma(c, c, s) (loop[i]) for the caller's c[i].  57 < count <= 480.
  * Host pointers. */
 int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t count, double *closed, double *loop);
+/* pagk_selftest_sample: the bilinear sampler every tracking kernel shares (PatchMatch::GetPixelValue,
+ * src/patch_match.cpp:391-406) on level `level` of a built slot, at the caller's n coordinates xy = (x, y) pairs: one thread
+ * per coordinate reads the level's own packed taps.  mode 0: the clamped sampler, out = n floats.  mode 1: the clamp-free
+ * sampler the kernels use for a patch that lies inside the image, n floats.  mode 2: the five clamped samples of one
+ * Gauss-Newton pixel, out = 5 n floats (x, y), (x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1), the +-1 formed in float.
+ * mode 3: the same five clamp-free.  The clamped modes take any float (NaN samples column / row 0).  The clamp-free modes
+ * read without a test, so the call checks every coordinate first and returns PAGK_E_ARG, launching nothing, unless
+ * 0 <= x < cols - 1 and 0 <= y < rows - 1 (mode 1) or 1 <= x < cols - 2 and 1 <= y < rows - 2 (mode 3) hold for all of them
+ * (NaN fails).  Host pointers, synchronous, not between pagk_graph_begin and pagk_graph_end. */
+int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mode, int32_t n, const float *xy, float *out);
 
 /* hipGraph capture of the per-frame work (BASELINE configs[4], "hipGraph-captured iterate").  A camera
  * stream issues the same launches on the same device pointers every frame; between pagk_graph_begin and

@@ -639,6 +639,17 @@ static int view_to_level(const pagk_image *im, level_t *lv)
     return PAGK_OK;
 }
 
+/* get_pixel_value on a caller's image view at n coordinates xy = (x, y) pairs: the sampler by itself. */
+int pagk_oracle_sample(const pagk_image *image, int32_t n, const float *xy, float *out)
+{
+    level_t lv;
+    int rc = view_to_level(image, &lv);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!xy || !out))) return PAGK_E_ARG;
+    for (int32_t i = 0; i < n; i++) out[i] = get_pixel_value(&lv, xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+    return PAGK_OK;
+}
+
 int pagk_oracle_track_pyr(const pagk_params *params, int32_t n_levels, const pagk_image *ref_levels,
                           const pagk_image *cur_levels, int32_t n, const float *pt_ref_un,
                           const float *pt_init_un, const float *affine, const uint8_t *status_in,

@@ -28,6 +28,11 @@ extern "C" {
  * other (odd) size its 11-bit fixed-point bilinear.  dst is (int)(w*0.5) x (int)(h*0.5), contiguous. */
 int pagk_oracle_pyr_down(const uint8_t *src, int32_t w, int32_t h, int64_t step, uint8_t *dst);
 
+/* PatchMatch::GetPixelValue (src/patch_match.cpp:391-406) on an image view at n coordinates xy = (x, y) pairs, one float
+ * each: the sampler that every other function here calls, by itself.  Taps past the buffer and row-padding bytes are 0, a
+ * NaN coordinate samples column / row 0 (oracle/README.md). */
+int pagk_oracle_sample(const pagk_image *image, int32_t n, const float *xy, float *out);
+
 /* PatchMatch::OpticalFlowMultiLevel (src/patch_match.cpp:79-142) on host buffers;
  * same arguments as pagk_track.  nthreads stripes features over pthreads the way
  * cv::parallel_for_ does (:103); nthreads <= 0 means one thread. */

@@ -36,6 +36,8 @@ def load():
         vp, i32, P = C.c_void_p, C.c_int32, C.POINTER
         lib.pagk_oracle_pyr_down.restype = C.c_int
         lib.pagk_oracle_pyr_down.argtypes = [vp, i32, i32, C.c_int64, vp]
+        lib.pagk_oracle_sample.restype = C.c_int
+        lib.pagk_oracle_sample.argtypes = [P(Image), i32, vp, vp]
         lib.pagk_oracle_track.restype = C.c_int
         lib.pagk_oracle_track.argtypes = [P(Params), P(Image), P(Image), i32, vp, vp, vp, vp, P(Outputs), i32]
         lib.pagk_oracle_track_pyr.restype = C.c_int
@@ -83,6 +85,19 @@ def pyr_down(img: np.ndarray) -> np.ndarray:
     if rc:
         raise RuntimeError(f"pagk_oracle_pyr_down: {rc}")
     return out
+
+
+def sample(img: np.ndarray, xy: np.ndarray) -> np.ndarray:
+    """PatchMatch::GetPixelValue (reference src/patch_match.cpp:391-406) on `img` (a row-strided view keeps its stride) at the
+    (x, y) rows of `xy` -> float32 per row."""
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    n = int(xy.shape[0])
+    out = np.zeros(max(n, 1), np.float32)
+    iv = image_view(img)
+    rc = load().pagk_oracle_sample(C.byref(iv), n, _p(xy), _p(out))
+    if rc:
+        raise RuntimeError(f"pagk_oracle_sample: {rc}")
+    return out[:n]
 
 
 def track(params: Params, img_ref, img_cur, pt_ref, pt_init, affine, status_in, nthreads: int = 1, out=None):

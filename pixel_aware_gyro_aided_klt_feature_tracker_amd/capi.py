@@ -348,6 +348,9 @@ def declare(lib) -> None:
     if hasattr(lib, "pagk_selftest_repeat_sum"):
         lib.pagk_selftest_repeat_sum.restype = C.c_int
         lib.pagk_selftest_repeat_sum.argtypes = [vp, i32, vp, i32, vp, vp]
+    if hasattr(lib, "pagk_selftest_sample"):
+        lib.pagk_selftest_sample.restype = C.c_int
+        lib.pagk_selftest_sample.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.pagk_match_features.restype = C.c_int
     lib.pagk_match_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     # the sharded path
@@ -405,6 +408,7 @@ EXPORTED_SYMBOLS = [
     "pagk_frame_rectify_pinned", "pagk_rectify", "pagk_undistort_maps",
     "pagk_orb_params_default", "pagk_orb_params_check", "pagk_orb_pattern_check", "pagk_orb_set_pattern",
     "pagk_orb_describe_device", "pagk_orb_describe", "pagk_orb_match_device", "pagk_orb_match",
+    "pagk_selftest_sample",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -844,6 +848,16 @@ class Context:
         self._check(self.lib.pagk_selftest_repeat_sum(self.h, n, _ptr(c), int(count), _ptr(closed), _ptr(loop)),
                     "pagk_selftest_repeat_sum")
         return closed, loop
+
+    def selftest_sample(self, slot: int, level: int, mode: int, xy: np.ndarray) -> np.ndarray:
+        """pagk_selftest_sample: the device sampler on a built slot's level at the (x, y) rows of `xy`.  mode 0 / 1: the
+        clamped / clamp-free sample, n floats; mode 2 / 3: the five samples of a Gauss-Newton pixel, n x 5 floats."""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        n = int(xy.shape[0])
+        out = np.zeros((max(n, 1), 5) if mode >= 2 else max(n, 1), np.float32)
+        self._check(self.lib.pagk_selftest_sample(self.h, int(slot), int(level), int(mode), n, _ptr(xy), _ptr(out)),
+                    "pagk_selftest_sample")
+        return out[:n]
 
     def selftest_solve(self, H: np.ndarray, b: np.ndarray, solver_variant: int = 0):
         """H.llt().solve(b) and the update's norm for n 4x4 systems: (x, norm) of the one-lane form and

@@ -3600,6 +3600,46 @@ int pagk_selftest_solve(pagk_ctx *ctx, int32_t n, const double *H, const double 
     return PAGK_OK;
 }
 
+// The sampler of pagk_device.h on level `level` of a built slot.  A clamp-free sample reads the quad at (int(y), int(x)) with
+// no test at all, so every coordinate of modes 1 and 3 is held against the domain first -- written so that NaN fails.
+int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mode, int32_t n, const float *xy, float *out)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots || mode < 0 || mode > 3 || n < 0) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_sample");
+    const FrameSlot &s = ctx->slots[slot];
+    if (!s.valid || level < 0 || level >= s.L) return PAGK_E_ARG;
+    if (n == 0) return PAGK_OK;
+    if (!xy || !out) return PAGK_E_ARG;
+    DevLevel lv;
+    fill_level(lv, s, level);
+    const bool clamp = mode == 0 || mode == 2, five = mode >= 2;
+    if (!clamp) {
+        const float lo = five ? 1.0f : 0.0f;
+        const float hx = (float)(lv.cols - (five ? 2 : 1)), hy = (float)(lv.rows - (five ? 2 : 1));
+        for (int32_t i = 0; i < n; i++) {
+            const float x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+            if (!(x >= lo && x < hx && y >= lo && y < hy)) return PAGK_E_ARG;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Scratch sc;
+    const size_t nn = (size_t)n, per = five ? 5 : 1;
+    HIPCHK(ctx, hipMalloc(&sc.p, nn * (2 + per) * sizeof(float)));
+    float *d_xy = static_cast<float *>(sc.p), *d_out = d_xy + 2 * nn;
+    HIPCHK(ctx, hipMemcpyAsync(d_xy, xy, 2 * nn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grd((n + 255) / 256), blk(256);
+    switch (mode) {
+    case 0: hipLaunchKernelGGL((k_selftest_sample<true, false>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
+    case 1: hipLaunchKernelGGL((k_selftest_sample<false, false>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
+    case 2: hipLaunchKernelGGL((k_selftest_sample<true, true>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
+    default: hipLaunchKernelGGL((k_selftest_sample<false, true>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, nn * per * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
 // GyroAidedTracker::MatchFeatures, src/gyro_aided_tracker.cpp:949-1008.  Host-side: a sequential pass whose
 // decisions depend on the matches accepted so far.
 int pagk_match_features(int32_t n, int32_t cap, const int32_t *count, const int32_t *nbr_idx, const float *nbr_dist,

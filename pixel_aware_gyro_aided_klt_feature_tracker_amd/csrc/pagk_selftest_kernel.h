@@ -6,7 +6,9 @@
 //     equivalent to `norm < 1e-2`;
 //   * H.llt().solve(b) and update.norm() (src/patch_match.cpp:319,343) -- one lane per system and four lanes per
 //     system -- return the bits of the CPU restatement for any matrix, including failed pivots, zeros, NaN and
-//     out-of-range magnitudes.
+//     out-of-range magnitudes;
+// and, below them all, the one routine every tracking variant shares (pagk_selftest_sample): the bilinear sampler of
+// pagk_device.h on a built slot's own tap plane, clamped and clamp-free, one sample and the five of a Gauss-Newton pixel.
 #pragma once
 #include "pagk_device.h"
 
@@ -73,6 +75,24 @@ __global__ void __launch_bounds__(64) k_selftest_solve(int n, const double *H, c
             for (int k = 0; k < 4; k++) x_serial[(size_t)sys * 4 + k] = x[k];
             norm_serial[sys] = nrm;
         }
+    }
+}
+
+// One thread per coordinate on a built level: the product's own sample<CLAMP> / sample5<CLAMP> (same translation unit,
+// same flags).  out: one float per coordinate, or five (c, x+1, x-1, y+1, y-1).  The host has checked every coordinate of a
+// clamp-free call against the domain in which its taps stay inside the plane.
+template <bool CLAMP, bool FIVE>
+__global__ void __launch_bounds__(256) k_selftest_sample(DevLevel L, int n, const float *xy, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+    if (FIVE) {
+        const Five f = sample5<CLAMP>(L, x, y);
+        float *o = out + 5 * (size_t)i;
+        o[0] = f.c, o[1] = f.xp, o[2] = f.xm, o[3] = f.yp, o[4] = f.ym;
+    } else {
+        out[i] = sample<CLAMP>(L, x, y);
     }
 }
 

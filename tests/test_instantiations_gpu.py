@@ -15,14 +15,13 @@ The rows force their variant with pagk_set_kernel; test_auto_selection_reaches_e
 lets the launch size decide, on the same workload."""
 import dataclasses
 
-import numpy as np
 import pytest
-import torch
 
 from oracle import pagk_oracle as orc
-from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, distributed
+from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi
 
 import instantiation_cases as cases
+import route_runner as rr
 import track_routes as tr
 from util import assert_parity, needs_variant
 
@@ -39,103 +38,13 @@ def _cases():
     return out
 
 
-def _after_launch(c, r, variant, what):
-    assert c.last_variant() == variant, f"{what}: ran variant {c.last_variant()}, the row names {variant}"
-    handed = c.last_handover()
-    assert (handed > 0) == r.handover, f"{what}: {handed} features handed over, the row says hand-over = {r.handover}"
-    c.check_launch()   # raises when a wave of the launch gave up a wait: the error word must be clear
-
-
-def _run_track(c, r, h):
-    """Host-buffer entry point: every selector of the row x every mode."""
-    w = cases.workload(h)
-    for selector, variant in zip(r.selectors, r.variants):
-        for mode in cases.MODES:
-            what = f"{r.name} h={h} kernel {selector} {mode}"
-            c.set_kernel(selector)
-            try:
-                got = c.track(cases.params(w, mode), w.img_ref, w.img_cur, w.pt_ref, w.pt_init, w.affine, w.status_in)
-            finally:
-                c.set_kernel(0)
-            assert_parity(got, cases.oracle(h, mode), w.n, exact=True, what=what)
-            _after_launch(c, r, variant, what)
-
-
-def _device_inputs(w, dev):
-    # (copies: the shared arrays are read-only)
-    return [torch.from_numpy(x.copy()).to(dev) for x in (w.pt_ref, w.pt_init, w.affine, w.status_in)]
-
-
-def _run_fused(r, h):
-    """pagk_track_device_fused: the tracked outputs, and every level of the slot that the same launch built from another
-    frame (a new one per mode, so that no mode can pass on the levels the one before it left)."""
-    w = cases.workload(h)
-    stream, dev = torch.cuda.Stream(), torch.device("cuda", 0)
-    c = capi.Context(0)
-    try:
-        with torch.cuda.stream(stream):
-            c.set_stream(stream.cuda_stream)
-            c.frame_upload(0, w.img_ref, cases.PYRAMIDS)
-            c.frame_upload(1, w.img_cur, cases.PYRAMIDS)
-            d = _device_inputs(w, dev)
-            for k, mode in enumerate(cases.MODES):
-                what = f"{r.name} h={h} {mode}"
-                nxt = np.random.default_rng(16 * h + k).integers(0, 256, (cases.HEIGHT, cases.WIDTH), dtype=np.uint8)
-                d_next = torch.from_numpy(nxt).to(dev)
-                out = distributed.alloc_device_outputs(w.n, dev)
-                c.track_device_fused(cases.params(w, mode), 0, 1, w.n, d[0], d[1], d[2], d[3], out, 2, d_next.data_ptr(),
-                                     cases.WIDTH, cases.HEIGHT, cases.WIDTH, cases.PYRAMIDS)
-                stream.synchronize()
-                got = {name: out[name].cpu().numpy() for name, _, _ in distributed.FIELDS}
-                assert_parity(got, cases.oracle(h, mode), w.n, exact=True, what=what)
-                lvl = nxt
-                for l in range(1, cases.PYRAMIDS):   # (level 0 of a slot is the caller's own image)
-                    lvl = orc.pyr_down(lvl)
-                    assert np.array_equal(c.frame_download_level(2, l, cases.WIDTH, cases.HEIGHT), lvl), f"{what}: next-frame pyramid level {l}"
-                _after_launch(c, r, r.variants[0], what)
-                # ... and the slot is usable as the next pair's current frame (its level 0 taps included)
-                out = distributed.alloc_device_outputs(w.n, dev)
-                c.track_device(cases.params(w, mode), 1, 2, w.n, d[0], d[1], d[2], d[3], out)
-                stream.synchronize()
-                ref = cases.run_oracle(w, mode, pair=(w.img_cur, nxt))
-                got = {name: out[name].cpu().numpy() for name, _, _ in distributed.FIELDS}
-                assert_parity(got, ref, w.n, exact=True, what=f"{what}: pair (cur, next) on the fused-built slot")
-                _after_launch(c, r, r.variants[0], what)
-    finally:
-        c.set_stream(None)
-        c.close()
-
-
-def _run_batch(r, h):
-    """pagk_track_device_batch: three streams (1, 67 and 30 features, two frame sizes) as one launch of the lead context;
-    every stream's outputs against that stream's own oracle run."""
-    ws = cases.batch_workloads(h)
-    stream, dev = torch.cuda.Stream(), torch.device("cuda", 0)
-    ctxs = []
-    try:
-        with torch.cuda.stream(stream):
-            for w in ws:
-                c = capi.Context(0)
-                ctxs.append(c)
-                c.set_stream(stream.cuda_stream)
-                c.frame_upload(0, w.img_ref, cases.PYRAMIDS)
-                c.frame_upload(1, w.img_cur, cases.PYRAMIDS)
-            ctxs[0].set_kernel(r.selectors[0])
-            d = [_device_inputs(w, dev) for w in ws]
-            for mode in cases.MODES:
-                outs = [distributed.alloc_device_outputs(w.n, dev) for w in ws]
-                capi.Context.track_device_batch(ctxs, cases.params(ws[0], mode), [0] * 3, [1] * 3, [w.n for w in ws],
-                                                [x[0] for x in d], [x[1] for x in d], [x[2] for x in d], [x[3] for x in d], outs)
-                stream.synchronize()
-                for j, (w, out, ref) in enumerate(zip(ws, outs, cases.batch_oracles(h, mode))):
-                    what = f"{r.name} h={h} {mode}, stream {j} ({w.n} features)"
-                    got = {name: out[name].cpu().numpy() for name, _, _ in distributed.FIELDS}
-                    assert_parity(got, ref, w.n, exact=True, what=what)
-                    _after_launch(ctxs[j], r, r.variants[0], what)
-    finally:
-        for c in ctxs:
-            c.set_stream(None)
-            c.close()
+def _case(r, h):
+    """The row's case at half patch `h`: the matrix's one workload, its four modes, the variants the row names."""
+    ws = cases.batch_workloads(h) if r.entry == "track_device_batch" else ()
+    return rr.Case(what=f"{r.name} h={h}", w=cases.workload(h), modes=tuple(cases.MODES), params=cases.params,
+                   oracle=lambda mode: cases.oracle(h, mode), run_oracle=cases.run_oracle, variants=r.variants,
+                   next_seed=16 * h, batch=ws, batch_oracles=lambda mode: cases.batch_oracles(h, mode),
+                   batch_variants=(r.variants[0],) * len(ws))
 
 
 def test_auto_selection_reaches_each_variant(monkeypatch):
@@ -172,18 +81,5 @@ def test_auto_selection_reaches_each_variant(monkeypatch):
 def test_route(request, monkeypatch, name, h):
     r = tr.route(name)
     cases.check_not_vacuous(h, continuation=r.handover)
-    for var, value in r.env:
-        monkeypatch.setenv(var, value)
-    if r.entry == "track_device_fused":
-        _run_fused(r, h)
-    elif r.entry == "track_device_batch":
-        _run_batch(r, h)
-    elif r.env:   # a context of its own, created under the row's environment
-        c = capi.Context(0)
-        try:
-            _run_track(c, r, h)
-        finally:
-            c.close()
-    else:
-        _run_track(request.getfixturevalue("ctx"), r, h)
+    rr.run_route(request, monkeypatch, r, _case(r, h))
 

@@ -1,11 +1,12 @@
 """The route table (track_routes.py) against the build: every tracking kernel the product library carries is reached
 by a row of the table or exempted with a reason, and every kernel a row names exists.  Works from the kernel NAMES in
 kernel_resources.json (written by build_hip) alone.  Also: the conditions under which the rows of the GPU matrix say
-something, checked on the CPU oracle for every patch size."""
+something, checked on the CPU oracle for every patch size -- of the instantiation matrix and of the shape matrix."""
 import json
 
 import pytest
 
+import shape_cases as sc
 import track_routes as tr
 
 
@@ -80,3 +81,37 @@ def test_matrix_rows_cannot_pass_vacuously(built, h):
     sizes of the continuation rows) most live features run past the hand-over budget."""
     import instantiation_cases as cases
     cases.check_not_vacuous(h, continuation=h in tr.COMMON)
+
+
+def _shape_halves():
+    return sorted({h for r in tr.ROUTES if r.test.startswith("test_instantiations_gpu.py") for h in sc.halves(r.name)})
+
+
+@pytest.mark.parametrize("shape", sc.SHAPES, ids=sc.shape_id)
+def test_shape_rows_cannot_pass_vacuously(built, shape):
+    """The shape matrix (test_shapes_gpu.py) on the oracle alone, for every half patch a row runs: enough features are live
+    and tracked, the two modes differ, most features pass the continuation routes' budget, and every level of every
+    stream of the batch exists."""
+    assert _shape_halves() == [1, 5, 7, 10, 15]
+    for h in _shape_halves():
+        sc.check_not_vacuous(sc.workload(shape, h), sc.budget(shape[2]) if h in tr.COMMON else None)
+    for h in tr.COMMON:
+        ws = sc.batch_workloads(shape, h)
+        assert [w.n for w in ws] == [1, 67, 30] and ws[1] is sc.workload(shape, h)
+        assert len({w.img_ref.shape for w in ws}) == 3 and {w.pyramids for w in ws} == {shape[2]}
+        assert all(min(w.img_ref.shape) >> (shape[2] - 1) >= 1 for w in ws)
+        for mode in sc.MODES:
+            assert all(ref["status"][:w.n].any() or w.n == 1 for w, ref in zip(ws, sc.batch_oracles(shape, h, mode)))
+
+
+def test_deep_slot_rows_cannot_pass_vacuously(built):
+    for h in sorted({h for name in sc.DEEP_ROUTES for h in sc.halves(name)}):
+        sc.check_not_vacuous(sc.deep_workload(h))
+
+
+def test_shape_matrix_variants_follow_select_variant():
+    """shape_cases.expected_variants restates the one rule of csrc/pagk_select.h that depends on the depth."""
+    assert sc.expected_variants("levels", 1) == (5,) and sc.expected_variants("levels", 2) == (7,)
+    assert sc.expected_variants("continuation-live", 1) == (5, 5) and sc.expected_variants("continuation-live", 8) == (5, 7)
+    assert sc.expected_variants("batch", 1) == (5,) and sc.expected_variants("block", 1) == (0,)
+    assert sc.budget(1) == 1 and {sc.budget(L) for L in range(2, 9)} == {3}
