@@ -745,6 +745,105 @@ int pagk_orb_match_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t 
 int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, const uint8_t *desc_q, int32_t nt,
                    const uint8_t *desc_t, int32_t *train_idx, int32_t *distance, uint8_t *keep, int32_t *info);
 
+/* ---- Pyramidal Lucas-Kanade: tracker type 0, the image-only baseline of the reference's comparison ------------------ */
+/* GyroAidedTracker::TrackFeatures with mType == OPENCV_OPTICAL_FLOW_PYR_LK (src/gyro_aided_tracker.cpp:353-380) calls
+ * cv::calcOpticalFlowPyrLK on the two gray images with winSize = 2 half_patch + 1, maxLevel = 2,
+ * TermCriteria(COUNT + EPS, 30, 0.01), flags = 0, minEigThreshold = 1e-4, clears the status of features with err >= 12
+ * (:371-375) and forms the flow.  This section is that call for 8-bit one-channel images.
+ * Parity contract: parity with OpenCV is NOT claimed (it cannot be built here); the contract is this definition, bit for
+ * bit (restated in plain C in tests/lk_ref.c).  It follows OpenCV 3.4's scalar code path step by step and says where it is
+ * the library's own rule.  win = 2 h + 1; r(i) = -i below 0 and 2 (n - 1) - i at or above n (BORDER_REFLECT_101, the r of
+ * the ORB section).
+ *   pyramid    level 0 is level 0 of the frame slot.  Level l + 1 has size ((W_l + 1) / 2, (H_l + 1) / 2); its pixel (x, y)
+ *              is (sum_{i, j = 0..4} w_i w_j src(r(2 x + i - 2), r(2 y + j - 2)) + 128) >> 8 with w = 1 4 6 4 1: exact
+ *              integers.  The effective top level is the largest L <= max_level such that every level 1 .. L has W_l > win
+ *              and H_l > win (buildOpticalFlowPyramid's stop rule); level 0 itself must have W, H > win (PAGK_E_ARG
+ *              otherwise).  These are NOT the slot's cv::resize levels (CreatePyramids, src/patch_match.cpp:61-76), which
+ *              stay as they are.
+ *   reads      gray values at any coordinate in [-win, W + win) x [-win, H + win) are read through r(); no read goes
+ *              further.  Derivatives outside [0, W) x [0, H) are 0 (the constant border of derivI).
+ *   derivative Scharr as calcSharrDeriv computes it, int arithmetic, neighbours through r():
+ *              t0(x, y) = 3 (I(x, y - 1) + I(x, y + 1)) + 10 I(x, y), t1(x, y) = I(x, y + 1) - I(x, y - 1),
+ *              dx = t0(x + 1, y) - t0(x - 1, y), dy = 3 (t1(x - 1, y) + t1(x + 1, y)) + 10 t1(x, y); both in [-4080, 4080].
+ *   per feature, from the top level L down to 0; status starts at 1, err at 0:
+ *   1 start    prev = pt_ref 2^-l (an exact f32 scaling).  At the top level next = prev, otherwise next = 2.f next of the
+ *              level above.  next is stored before any test.  half = (win - 1) 0.5f.
+ *   2 template p = prev - half, ip = floorf(p).  Out of range: ip.x < -win, ip.x >= W_l, ip.y < -win or ip.y >= H_l; a
+ *              non-finite coordinate counts as out of range (the library's rule: decided in f32 before any conversion to
+ *              int).  Out of range at level 0: status = 0, err = 0, the feature is done; at a higher level: on to the next
+ *              level.
+ *   3 weights  a = p.x - ip.x, b = p.y - ip.y; iw00 = rintf((1.f - a) (1.f - b) 16384.f), iw01 = rintf(a (1.f - b) 16384.f),
+ *              iw10 = rintf((1.f - a) b 16384.f), iw11 = 16384 - iw00 - iw01 - iw10; f32 with one rounding per operation,
+ *              no contraction; rintf rounds ties to even (cvRound).
+ *   4 sums     for every window pixel Ival = (sum I iw + 256) >> 9 (0 .. 8160) over the four neighbours (x, y), (x + 1, y),
+ *              (x, y + 1), (x + 1, y + 1) with iw00, iw01, iw10, iw11; ix, iy = (sum d iw + 8192) >> 14, arithmetic shifts.
+ *              S11 = sum ix ix, S12 = sum ix iy, S22 = sum iy iy.  The library's rule: these sums, B1, B2 and the error sum
+ *              below are EXACT integers in 64 bits, each converted to f32 once, round to nearest even (OpenCV accumulates
+ *              in f32 in an order that differs between its scalar and SIMD builds; an exact sum is a function of the input
+ *              and of nothing else, and needs no ordered chain on the device).  A11 = (float)S11 0x1p-20f, likewise A12, A22.
+ *   5 test     D = A11 A22 - A12 A12; minEig = (A22 + A11 - sqrtf((A11 - A22) (A11 - A22) + 4.f A12 A12)) /
+ *              (float)(2 win win): f32, one rounding per operation, left to right as written, correctly rounded sqrtf and
+ *              division.  If (double)minEig < min_eig_threshold or D < FLT_EPSILON: status = 0 at level 0; on to the next
+ *              level.  Otherwise D = 1.f / D.
+ *   6 iterate  q = next - half; at most max_count times: iq = floorf(q), range as in step 2 (out of range at level 0:
+ *              status = 0; either way leave the loop); weights from q as in step 3; diff = ((sum J iw + 256) >> 9) - Ival;
+ *              B1 = sum diff ix, B2 = sum diff iy (exact); b1 = (float)B1 0x1p-20f, likewise b2;
+ *              delta = ((A12 b2 - A22 b1) D, (A12 b1 - A11 b2) D) in f32; q += delta; next = q + half.  Stop if
+ *              (double)delta.x delta.x + (double)delta.y delta.y <= epsilon epsilon (f64, left to right, no contraction).
+ *              From the second iteration on: if (double)fabsf(delta.x + previous delta.x) < 0.01 and the same for y, then
+ *              next -= delta 0.5f and stop.
+ *   7 error    at level 0 with status still 1: e = next - half, range as in step 2 (out of range: status = 0); otherwise
+ *              weights from e and err = (float)(sum |diff|) / (float)(32 win win).  err stays 0 wherever it is not written.
+ *   filter     (:371-375) kept = status_raw && !(err >= err_threshold); flow = pt_out - pt_ref.
+ * Info, PAGK_LK_INFO_WORDS int32: [0] n, [1] features with raw status 1, [2] kept, [3] the effective top level, [4] lost to
+ * the min-eigenvalue test at level 0, [5] lost out of range at level 0, the rest 0.
+ * Not provided: OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, images with more than one channel. */
+typedef struct pagk_lk_params {
+    int32_t half_patch;        /* mHalfPatchSize: 10; winSize = 2 half_patch + 1 (:361) */
+    int32_t max_level;         /* maxLevel 2 (:362) */
+    int32_t max_count;         /* TermCriteria count 30 (:363) */
+    double epsilon;            /* TermCriteria epsilon 0.01 (:363) */
+    double min_eig_threshold;  /* 1e-4 (:366) */
+    float err_threshold;       /* 12 (:372) */
+} pagk_lk_params;
+#define PAGK_LK_INFO_WORDS 8
+#define PAGK_LK_MAX_ROWS 16777216
+/* 10, 2, 30, 0.01, 1e-4, 12: the constants of src/gyro_aided_tracker.cpp:353-380 */
+void pagk_lk_params_default(pagk_lk_params *p);
+/* PAGK_OK if *p can be run by the entry points below (src/gyro_aided_tracker.cpp:353-380): 1 <= half_patch <=
+ * PAGK_MAX_HALF_PATCH, 0 <= max_level < PAGK_MAX_PYRAMIDS, max_count >= 1, epsilon, min_eig_threshold and err_threshold
+ * finite and >= 0; PAGK_E_ARG otherwise or for NULL.  Needs no device. */
+int pagk_lk_params_check(const pagk_lk_params *p);
+/* The effective top level of a width x height image under *params (the stop rule of the pyramid that
+ * src/gyro_aided_tracker.cpp:353-380 has calcOpticalFlowPyrLK build), 0 .. max_level, or PAGK_E_ARG for parameters the check
+ * refuses or a level 0 that is not larger than the window in both directions.  Needs no device. */
+int pagk_lk_levels(int32_t width, int32_t height, const pagk_lk_params *params);
+/* The pyrDown levels 1 .. top of frame slot `slot` (the pyramid cv::calcOpticalFlowPyrLK builds for each image,
+ * src/gyro_aided_tracker.cpp:353-380) into a buffer the context owns for that slot; level 0 is read from the slot itself
+ * (for how long a slot can be read see pagk_detect_corners_device).  Call it again whenever the slot's image has changed.
+ * Asynchronous on the context stream, capturable.  Run it once outside a capture first (the buffer is the context's). */
+int pagk_lk_pyramid_device(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot);
+/* cv::calcOpticalFlowPyrLK and the error filter of src/gyro_aided_tracker.cpp:353-380 from slot_ref to slot_cur, which
+ * have the same size and whose pyramids pagk_lk_pyramid_device has built for at least the top level of *params.
+ * d_pt_ref, d_pt_out: cap x 2 float; d_n: a device count (clamped to [0, cap]) or NULL for cap; d_status: cap bytes (after
+ * the filter); d_status_raw: cap bytes or NULL (before it); d_err: cap float; d_flow: cap x 2 float or NULL; d_info:
+ * PAGK_LK_INFO_WORDS int32.  Rows at or beyond the count are zeroed.  1 <= cap <= PAGK_LK_MAX_ROWS.  The result does not
+ * depend on the order in which the workgroups run.  Device pointers, asynchronous on the context stream, capturable;
+ * nothing is read on the host. */
+int pagk_lk_track_device(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
+                         const float *d_pt_ref, const int32_t *d_n /* or NULL: cap */, float *d_pt_out, uint8_t *d_status,
+                         uint8_t *d_status_raw /* or NULL */, float *d_err, float *d_flow /* or NULL */, int32_t *d_info);
+/* The same with host buffers, synchronous (src/gyro_aided_tracker.cpp:353-380): both images are uploaded and their
+ * pyramids built; pt_ref, pt_out n x 2 floats, status n bytes, status_raw (or NULL) n bytes, err n floats, flow (or NULL)
+ * n x 2 floats, info (or NULL) PAGK_LK_INFO_WORDS words.  0 <= n <= PAGK_LK_MAX_ROWS. */
+int pagk_lk_track(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_image *ref, const pagk_image *cur, int32_t n,
+                  const float *pt_ref, float *pt_out, uint8_t *status, uint8_t *status_raw, float *err, float *flow,
+                  int32_t *info);
+/* Diagnostic, never on the tracking path: level `level` (1 .. the top level built) of the pyramid that
+ * pagk_lk_pyramid_device built for `slot` (the pyrDown levels behind src/gyro_aided_tracker.cpp:353-380), into dst with
+ * rows of `pitch` bytes.  Host pointer, synchronous, not between pagk_graph_begin and pagk_graph_end. */
+int pagk_selftest_lk_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int64_t pitch);
+
 /* Diagnostics (never on the tracking path): the arithmetic of H.llt().solve(b) / update.norm()
  * (src/patch_match.cpp:319,343) on the caller's operands, so that a host can check on its own device -- and, with
  * Eigen at hand, against its own Eigen -- what pagk_params::solver_variant selects.
@@ -781,7 +880,8 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
  * pagk_gyro_predict_device_live, pagk_track_device, pagk_post_filter_device, pagk_geometry_scores_device,
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
  * pagk_frame_handover_detect_device, pagk_detect_fast_device,
- * pagk_frame_handover_fast_device, pagk_frame_rectify_device, pagk_orb_describe_device, pagk_orb_match_device; and the
+ * pagk_frame_handover_fast_device, pagk_frame_rectify_device, pagk_orb_describe_device, pagk_orb_match_device,
+ * pagk_lk_pyramid_device, pagk_lk_track_device; and the
  * pinned-memory forms pagk_frame_upload_pinned,
  * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing

@@ -70,8 +70,16 @@ class OrbParams(C.Structure):
     _fields_ = [("blur_weights", C.c_int32 * 4), ("match_floor", C.c_int32), ("n_levels", C.c_int32)]
 
 
+class LkParams(C.Structure):
+    """pagk_lk_params (include/pagk.h): the constants of the reference's calcOpticalFlowPyrLK call and its error filter."""
+    _fields_ = [("half_patch", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double),
+                ("min_eig_threshold", C.c_double), ("err_threshold", C.c_float)]
+
+
 DETECT_INFO_WORDS = 8
 ORB_INFO_WORDS = 8
+LK_INFO_WORDS = 8
+LK_INFO_FIELDS = ("n", "raw", "kept", "top_level", "lost_min_eig", "lost_out_of_range")
 ORB_DESCRIBE_INFO_FIELDS = ("described", "outside")
 ORB_MATCH_INFO_FIELDS = ("nq", "matches", "kept", "min_dist", "max_dist", "threshold")
 DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
@@ -296,6 +304,21 @@ def declare(lib) -> None:
         lib.pagk_orb_match_device.argtypes = [vp, _P(OrbParams), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         lib.pagk_orb_match.restype = C.c_int
         lib.pagk_orb_match.argtypes = [vp, _P(OrbParams), i32, vp, i32, vp, vp, vp, vp, vp]
+    if hasattr(lib, "pagk_lk_track_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_lk_params_default.restype = None
+        lib.pagk_lk_params_default.argtypes = [_P(LkParams)]
+        lib.pagk_lk_params_check.restype = C.c_int
+        lib.pagk_lk_params_check.argtypes = [_P(LkParams)]
+        lib.pagk_lk_levels.restype = C.c_int
+        lib.pagk_lk_levels.argtypes = [i32, i32, _P(LkParams)]
+        lib.pagk_lk_pyramid_device.restype = C.c_int
+        lib.pagk_lk_pyramid_device.argtypes = [vp, _P(LkParams), i32]
+        lib.pagk_lk_track_device.restype = C.c_int
+        lib.pagk_lk_track_device.argtypes = [vp, _P(LkParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_lk_track.restype = C.c_int
+        lib.pagk_lk_track.argtypes = [vp, _P(LkParams), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp]
+        lib.pagk_selftest_lk_level.restype = C.c_int
+        lib.pagk_selftest_lk_level.argtypes = [vp, i32, i32, vp, C.c_int64]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -409,6 +432,8 @@ EXPORTED_SYMBOLS = [
     "pagk_orb_params_default", "pagk_orb_params_check", "pagk_orb_pattern_check", "pagk_orb_set_pattern",
     "pagk_orb_describe_device", "pagk_orb_describe", "pagk_orb_match_device", "pagk_orb_match",
     "pagk_selftest_sample",
+    "pagk_lk_params_default", "pagk_lk_params_check", "pagk_lk_levels", "pagk_lk_pyramid_device", "pagk_lk_track_device",
+    "pagk_lk_track", "pagk_selftest_lk_level",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -490,6 +515,29 @@ def _orb_pattern(pattern) -> np.ndarray:
 def orb_pattern_check(pattern) -> int:
     """pagk_orb_pattern_check: PAGK_OK if every coordinate lies in [-13, 13] (needs no device)."""
     return int(load().pagk_orb_pattern_check(_orb_pattern(pattern).ctypes.data))
+
+
+def lk_params_default(**overrides) -> LkParams:
+    """pagk_lk_params_default() with overrides (half_patch, max_level, max_count, epsilon, min_eig_threshold, err_threshold)."""
+    p = LkParams()
+    load().pagk_lk_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(LkParams._fields_):
+            raise TypeError(f"pagk_lk_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def lk_params_check(p: LkParams) -> int:
+    """pagk_lk_params_check: PAGK_OK or PAGK_E_ARG (needs no device)."""
+    return int(load().pagk_lk_params_check(C.byref(p)))
+
+
+def lk_levels(width: int, height: int, lk: LkParams | None = None) -> int:
+    """pagk_lk_levels: the effective top level of the Lucas-Kanade pyramid of a width x height image, or PAGK_E_ARG
+    (needs no device)."""
+    lk = lk if lk is not None else lk_params_default()
+    return int(load().pagk_lk_levels(int(width), int(height), C.byref(lk)))
 
 
 def rectify_params_default(**overrides) -> RectifyParams:
@@ -1191,6 +1239,48 @@ class Context:
         out = dict(train_idx=idx[:nq], distance=dist[:nq], keep=keep[:nq], info=info)
         out.update(zip(ORB_MATCH_INFO_FIELDS, (int(v) for v in info[:6])))
         return out
+
+    # pyramidal Lucas-Kanade, tracker type 0 (src/gyro_aided_tracker.cpp:353-380) -------------------------------------
+    lk_params_default = staticmethod(lk_params_default)
+
+    def lk_pyramid_device(self, lk: LkParams, slot: int):
+        """pagk_lk_pyramid_device: the pyrDown levels of frame slot `slot` (asynchronous, capturable)."""
+        self._check(self.lib.pagk_lk_pyramid_device(self.h, C.byref(lk), slot), "pagk_lk_pyramid_device")
+
+    def lk_track_device(self, lk: LkParams, slot_ref: int, slot_cur: int, cap: int, d_pt_ref, d_n, d_pt_out, d_status,
+                        d_status_raw, d_err, d_flow, d_info):
+        """pagk_lk_track_device (asynchronous, capturable): d_n, d_status_raw and d_flow may be None."""
+        if d_pt_ref is None or d_pt_out is None or d_status is None or d_err is None or d_info is None:
+            raise ValueError("d_pt_ref, d_pt_out, d_status, d_err and d_info are required")
+        self._check(self.lib.pagk_lk_track_device(self.h, C.byref(lk), slot_ref, slot_cur, cap, _ptr(d_pt_ref), _ptr(d_n),
+                                                  _ptr(d_pt_out), _ptr(d_status), _ptr(d_status_raw), _ptr(d_err),
+                                                  _ptr(d_flow), _ptr(d_info)), "pagk_lk_track_device")
+
+    def lk_track(self, img_ref: np.ndarray, img_cur: np.ndarray, pts, lk: LkParams | None = None) -> dict:
+        """pagk_lk_track, host buffers -> dict(pt_out (n x 2), status (n), status_raw (n), err (n), flow (n x 2), info, and
+        the info words by name)."""
+        lk = lk if lk is not None else lk_params_default()
+        pt = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = int(pt.shape[0])
+        nn = max(n, 1)
+        ir, ic = image_view(img_ref), image_view(img_cur)
+        out = dict(pt_out=np.zeros((nn, 2), np.float32), status=np.zeros(nn, np.uint8), status_raw=np.zeros(nn, np.uint8),
+                   err=np.zeros(nn, np.float32), flow=np.zeros((nn, 2), np.float32))
+        info = np.zeros(LK_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_lk_track(self.h, C.byref(lk), C.byref(ir), C.byref(ic), n, _ptr(pt) if n else None,
+                                           _ptr(out["pt_out"]), _ptr(out["status"]), _ptr(out["status_raw"]),
+                                           _ptr(out["err"]), _ptr(out["flow"]), _ptr(info)), "pagk_lk_track")
+        out = {k: v[:n] for k, v in out.items()}
+        out["info"] = info
+        out.update(zip(LK_INFO_FIELDS, (int(v) for v in info[:6])))
+        return out
+
+    def selftest_lk_level(self, slot: int, level: int, width: int, height: int, pitch: int | None = None) -> np.ndarray:
+        """pagk_selftest_lk_level: level `level` (>= 1) of the slot's Lucas-Kanade pyramid, height x width."""
+        pitch = width if pitch is None else int(pitch)
+        buf = np.zeros((height, pitch), np.uint8)
+        self._check(self.lib.pagk_selftest_lk_level(self.h, slot, level, buf.ctypes.data, pitch), "pagk_selftest_lk_level")
+        return buf[:, :width]
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------
     def graph_begin(self):

@@ -264,9 +264,32 @@ int GyroAidedTracker::TrackFeatures()
     IntegrateGyroMeasurements();
     int n_predict = -1;
     if (mType == OPENCV_OPTICAL_FLOW_PYR_LK) {
-        // cv::calcOpticalFlowPyrLK (:353-380) is the OpenCV baseline the paper compares against; it
-        // is third-party code outside the hot path and is not provided here.
-        return -1;
+        // :353-380.  cv::calcOpticalFlowPyrLK is the library's pagk_lk_track (its definition, not OpenCV's arithmetic:
+        // include/pagk.h "Pyramidal Lucas-Kanade") with the constants of :361-366 and the error filter of :371-375.
+        std::vector<float> ptRef(2 * (size_t)mN + 2), ptOut(2 * (size_t)mN + 2, 0.f), flow(2 * (size_t)mN + 2, 0.f);
+        std::vector<cv::uchar> status((size_t)mN + 1, 0);
+        for (int i = 0; i < mN; i++) ptRef[2 * i] = mvKeysRefUn[i].pt.x, ptRef[2 * i + 1] = mvKeysRefUn[i].pt.y;  // :355-358
+        pagk_lk_params lk;
+        pagk_lk_params_default(&lk);  // maxLevel 2, (COUNT + EPS, 30, 0.01), minEigThreshold 1e-4, 12.0
+        lk.half_patch = mHalfPatchSize;  // :361
+        const cv::Mat &r = mImgGrayRef, &c = mImgGrayCur;
+        pagk_image ref{r.data, r.cols, r.rows, (int64_t)r.step}, cur{c.data, c.cols, c.rows, (int64_t)c.step};
+        mvError.assign(mN, 0.f);
+        int32_t info[PAGK_LK_INFO_WORDS] = {0};
+        int rc = pagk_lk_track(PatchMatch::Context(), &lk, &ref, &cur, mN, ptRef.data(), ptOut.data(), status.data(), nullptr,
+                               mN ? mvError.data() : nullptr, flow.data(), info);
+        if (rc != PAGK_OK)
+            throw std::runtime_error(std::string("GyroAidedTracker::TrackFeatures: pagk_lk_track: ") + pagk_strerror(rc) + " " +
+                                     pagk_last_error(PatchMatch::Context()));
+        mvPtPredictUn.resize(mN);
+        for (int i = 0; i < mN; i++) {
+            mvPtPredictUn[i] = cv::Point2f(ptOut[2 * i], ptOut[2 * i + 1]);
+            mvStatus[i] = status[i];                                              // :371-373
+            mvFlowsPredictUn[i] = cv::Point2f(flow[2 * i], flow[2 * i + 1]);      // :375
+        }
+        PatchMatch::DistortVecPoints(mvPtPredictUn, mvPtPredict, mK, mDistCoef);  // :379
+        // The reference returns n_predict uninitialised on this branch; the library's rule: the number of kept features.
+        n_predict = info[2];
     } else if (mType == GYRO_PREDICT) {
         n_predict = GyroPredictFeatures();
     } else {

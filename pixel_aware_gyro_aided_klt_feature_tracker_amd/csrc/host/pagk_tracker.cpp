@@ -20,13 +20,14 @@ const char *pagk_tracker_last_error(void) { return g_err.c_str(); }
 //   Rcl: 9 floats row-major, or NULL to integrate `imu` (n_imu x 7: ax ay az wx wy wz t) like the reference.
 // Outputs (n each): final mvStatus, mvPtPredictUn, mvPtPredict, and PatchMatch's raw vectors.
 // Returns the number of tracked features (TrackFeatures' return value) or -100 on an exception.
-int pagk_tracker_track_features(const unsigned char *img_ref, const unsigned char *img_cur, int width, int height,
-                                long step, int n, const float *keys_ref /*n x 2*/, const float *K /*3x3*/,
-                                const float *dist /*4*/, int type, int half_patch, int iterations, int pyramids,
+// error_out / flows_un_out (n / n x 2 floats, or NULL): mvError and mvFlowsPredictUn, which tracker type 0 fills (:367-375).
+int pagk_tracker_track_features_ex(const unsigned char *img_ref, const unsigned char *img_cur, int width, int height,
+                                   long step, int n, const float *keys_ref /*n x 2*/, const float *K /*3x3*/,
+                                   const float *dist /*4*/, int type, int half_patch, int iterations, int pyramids,
                                 const float *Rcl, const double *imu, int n_imu, double t_ref, double t_cur,
                                 unsigned char *status_out, float *pt_predict_un, float *pt_predict,
                                 unsigned char *status_pm, float *pt_pm_un, double *pix_err, double *dist_pred,
-                                float *affine_out /*n x 4 or NULL*/)
+                                float *affine_out /*n x 4 or NULL*/, float *error_out, float *flows_un_out)
 {
     try {
         cv::Mat ref(height, width, cv::CV_8UC1, const_cast<unsigned char *>(img_ref), (size_t)step);
@@ -50,7 +51,9 @@ int pagk_tracker_track_features(const unsigned char *img_ref, const unsigned cha
             // TrackFeatures() starts with IntegrateGyroMeasurements(); with no IMU samples that
             // leaves Rcl = I, so set the rotation afterwards through the same dispatch by hand.
             trk.SetRcl(R);
-            if (type == GyroAidedTracker::GYRO_PREDICT)
+            if (type == GyroAidedTracker::OPENCV_OPTICAL_FLOW_PYR_LK)
+                ret = trk.TrackFeatures();  // (image only: no rotation enters)
+            else if (type == GyroAidedTracker::GYRO_PREDICT)
                 ret = trk.GyroPredictFeatures();
             else {
                 // flags as TrackFeatures sets them (:384-414)
@@ -79,12 +82,27 @@ int pagk_tracker_track_features(const unsigned char *img_ref, const unsigned cha
                 const cv::Mat &A = trk.mvAffineDeformationMatrix[i];
                 for (int k = 0; k < 4; k++) affine_out[4 * i + k] = A.empty() ? 0.f : A.at<float>(k / 2, k % 2);
             }
+            if (error_out) error_out[i] = trk.mvError[i];
+            if (flows_un_out) flows_un_out[2 * i] = trk.mvFlowsPredictUn[i].x, flows_un_out[2 * i + 1] = trk.mvFlowsPredictUn[i].y;
         }
         return ret;
     } catch (const std::exception &e) {
         g_err = e.what();
         return -100;
     }
+}
+
+// The same without mvError and mvFlowsPredictUn.
+int pagk_tracker_track_features(const unsigned char *img_ref, const unsigned char *img_cur, int width, int height,
+                                long step, int n, const float *keys_ref, const float *K, const float *dist, int type,
+                                int half_patch, int iterations, int pyramids, const float *Rcl, const double *imu, int n_imu,
+                                double t_ref, double t_cur, unsigned char *status_out, float *pt_predict_un, float *pt_predict,
+                                unsigned char *status_pm, float *pt_pm_un, double *pix_err, double *dist_pred,
+                                float *affine_out)
+{
+    return pagk_tracker_track_features_ex(img_ref, img_cur, width, height, step, n, keys_ref, K, dist, type, half_patch,
+                                          iterations, pyramids, Rcl, imu, n_imu, t_ref, t_cur, status_out, pt_predict_un,
+                                          pt_predict, status_pm, pt_pm_un, pix_err, dist_pred, affine_out, nullptr, nullptr);
 }
 
 // GyroAidedTracker::GeometryValidation (reference :429-480) on a tracker whose state is given by the

@@ -176,6 +176,24 @@ void PatchMatch::OpticalFlowConsideringIlluminationChange_onePixel(const int i, 
         mvNcc[i] = 1;
 }
 
+// src/utils.cpp:49-76
+void PatchMatch::DistortVecPoints(const std::vector<cv::Point2f> &vpts, std::vector<cv::Point2f> &vpts_dist, const cv::Mat &K,
+                                  const cv::Mat &DistCoef)
+{
+    const float fx = K.at<float>(0, 0), fy = K.at<float>(1, 1), cx = K.at<float>(0, 2), cy = K.at<float>(1, 2);
+    const float fx_inv = 1.0 / fx, fy_inv = 1.0 / fy;
+    const float k1 = DistCoef.at<float>(0), k2 = DistCoef.at<float>(1), p1 = DistCoef.at<float>(2),
+                p2 = DistCoef.at<float>(3), k3 = DistCoef.total() == 5 ? DistCoef.at<float>(4) : 0;
+    vpts_dist.resize(vpts.size());
+    for (size_t i = 0; i < vpts.size(); i++) {
+        const float x = (vpts[i].x - cx) * fx_inv, y = (vpts[i].y - cy) * fy_inv;
+        const float r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+        const float xd = x * (1 + k1 * r2 + k2 * r4 + k3 * r6) + 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
+        const float yd = y * (1 + k1 * r2 + k2 * r4 + k3 * r6) + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+        vpts_dist[i] = cv::Point2f(fx * xd + cx, fy * yd + cy);
+    }
+}
+
 // :409-416 -> src/utils.cpp:49-76
 void PatchMatch::DistortPoints()
 {
@@ -184,18 +202,7 @@ void PatchMatch::DistortPoints()
         mvPtPyr2 = mvPtPyr2Un;
         return;
     }
-    const float fx = T.mK.at<float>(0, 0), fy = T.mK.at<float>(1, 1), cx = T.mK.at<float>(0, 2), cy = T.mK.at<float>(1, 2);
-    const float fx_inv = 1.0 / fx, fy_inv = 1.0 / fy;
-    const float k1 = T.mDistCoef.at<float>(0), k2 = T.mDistCoef.at<float>(1), p1 = T.mDistCoef.at<float>(2),
-                p2 = T.mDistCoef.at<float>(3), k3 = T.mDistCoef.total() == 5 ? T.mDistCoef.at<float>(4) : 0;
-    mvPtPyr2.resize(mvPtPyr2Un.size());
-    for (size_t i = 0; i < mvPtPyr2Un.size(); i++) {
-        const float x = (mvPtPyr2Un[i].x - cx) * fx_inv, y = (mvPtPyr2Un[i].y - cy) * fy_inv;
-        const float r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-        const float xd = x * (1 + k1 * r2 + k2 * r4 + k3 * r6) + 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
-        const float yd = y * (1 + k1 * r2 + k2 * r4 + k3 * r6) + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
-        mvPtPyr2[i] = cv::Point2f(fx * xd + cx, fy * yd + cy);
-    }
+    DistortVecPoints(mvPtPyr2Un, mvPtPyr2, T.mK, T.mDistCoef);
 }
 
 // :370-388

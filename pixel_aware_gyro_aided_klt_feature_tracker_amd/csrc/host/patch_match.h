@@ -43,6 +43,10 @@ public:
 
     // reference :66, src/patch_match.cpp:409-416 -> DistortVecPoints src/utils.cpp:49-76: mvPtPyr2 from mvPtPyr2Un
     void DistortPoints();
+    // reference src/utils.cpp:49-76 (a free function there): the distortion model on a vector of points, as DistortPoints
+    // and the Lucas-Kanade branch of GyroAidedTracker::TrackFeatures (src/gyro_aided_tracker.cpp:379) apply it
+    static void DistortVecPoints(const std::vector<cv::Point2f> &vpts, std::vector<cv::Point2f> &vpts_dist, const cv::Mat &K,
+                                 const cv::Mat &DistCoef);
 
     // reference :69, src/patch_match.cpp:433-469: zero-normalised cross correlation, x outer / y inner, float sums
     float NCC(int halfPathSize, const cv::Mat &ref, const cv::Mat &cur, const cv::Point2f &pt_ref, const cv::Point2f &pt_cur,

@@ -68,6 +68,8 @@ struct pagk_ctx {
         ORB_PATTERN,   // ORB (pagk_orb_kernel.h): the sampling pattern of pagk_orb_set_pattern, 1024 int32
         ORB_BLUR,      // ... the blurred image of the slot being described: sized by W and H
         ORB_KEYS,      // ... the matcher's best-match keys: sized by cap_q
+        LK_PYR,        // Lucas-Kanade (pagk_lk_kernel.h): the pyrDown levels of slot 0 ...
+        LK_PYR_LAST = LK_PYR + kSlots - 1,   // ... to slot kSlots - 1, each sized by W, H and the top level
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
@@ -77,6 +79,7 @@ struct pagk_ctx {
     int fit_n = 0, fit_iters = 0;  // what buf[FIT]'s layout was computed for
     int rect_w = 0, rect_h = 0, rect_wp = 0;
     bool orb_pattern_set = false;
+    struct LkPyr { int w = 0, h = 0, top = -1; } lk_pyr[kSlots];   // what buf[LK_PYR + slot] holds (top -1: nothing)
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
     // per half patch (0 = not asked yet), the resident waves (occupancy x CUs) on this device of ...
     int quad_capacity[PAGK_MAX_HALF_PATCH + 1] = {};  // ... the generic whole-feature k_track_quad: the hand-over rule's "round"
@@ -2959,6 +2962,231 @@ int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, con
         HIPCHK(ctx, hipMemcpyAsync(keep, lay.at<void>(s.p, 5), (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 6), kOrbInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+// ---- pyramidal Lucas-Kanade, tracker type 0 (pagk_lk_kernel.h) ---------------------------------------------------
+namespace {
+
+int lk_params_check(const pagk_lk_params *p)
+{
+    if (!p || p->half_patch < 1 || p->half_patch > PAGK_MAX_HALF_PATCH || p->max_level < 0 || p->max_level >= PAGK_MAX_PYRAMIDS ||
+        p->max_count < 1 || !std::isfinite(p->epsilon) || p->epsilon < 0.0 || !std::isfinite(p->min_eig_threshold) ||
+        p->min_eig_threshold < 0.0 || !std::isfinite(p->err_threshold) || p->err_threshold < 0.0f)
+        return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+// sizes of levels 0 .. top and the top level itself (buildOpticalFlowPyramid's stop rule), or PAGK_E_ARG
+int lk_levels(int w, int h, const pagk_lk_params *p, int *lw, int *lh)
+{
+    const int win = 2 * p->half_patch + 1;
+    if (w <= win || h <= win) return PAGK_E_ARG;
+    lw[0] = w, lh[0] = h;
+    int top = 0;
+    while (top < p->max_level) {
+        const int nw = (lw[top] + 1) / 2, nh = (lh[top] + 1) / 2;
+        if (nw <= win || nh <= win) break;
+        top++;
+        lw[top] = nw, lh[top] = nh;
+    }
+    return top;
+}
+
+// where the levels 1 .. top lie in buf[LK_PYR + slot] (part l - 1 is level l, rows of lw[l] bytes)
+Layout<kLkMaxLevels> lk_layout(const int *lw, const int *lh, int top)
+{
+    size_t sizes[kLkMaxLevels] = {};
+    for (int l = 1; l <= top; l++) sizes[l - 1] = (size_t)lw[l] * lh[l];
+    return Layout<kLkMaxLevels>(sizes, std::max(top, 1));
+}
+
+bool lk_slot_ok(const FrameSlot &s) { return s.valid && s.img0; }
+
+// (slots 4 and 5 are the host-buffer form's own)
+int lk_pyramid_slot(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot)
+{
+    if (!ctx || lk_params_check(params) || slot < 0 || slot >= kSlots) return PAGK_E_ARG;
+    const FrameSlot &s = ctx->slots[slot];
+    if (!lk_slot_ok(s)) return PAGK_E_ARG;
+    int lw[kLkMaxLevels], lh[kLkMaxLevels];
+    const int top = lk_levels(s.w, s.h, params, lw, lh);
+    if (top < 0) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const Layout<kLkMaxLevels> lay = lk_layout(lw, lh, top);
+    DevBuf &pyr = ctx->buf[pagk_ctx::LK_PYR + slot];
+    int rc = reserve(ctx, pyr, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the Lucas-Kanade pyramid of a slot",
+                     "run the call once with this image size and these parameters before capturing");
+    if (rc) {
+        if (!pyr.ptr) ctx->lk_pyr[slot].top = -1;   // (a failed allocation left the buffer empty: the slot has no pyramid)
+        return rc;
+    }
+    ctx->lk_pyr[slot].top = -1;   // nothing valid until every level has been enqueued
+    for (int l = 1; l <= top; l++) {
+        LkPyrArgs a;
+        a.src = l == 1 ? s.img0 : lay.at<uint8_t>(pyr.ptr, l - 2);
+        a.spitch = l == 1 ? (long long)s.pitch0 : (long long)lw[l - 1];
+        a.dst = lay.at<uint8_t>(pyr.ptr, l - 1);
+        a.sw = lw[l - 1], a.sh = lh[l - 1], a.dw = lw[l], a.dh = lh[l];
+        hipLaunchKernelGGL(k_lk_pyrdown, dim3((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + 3) / 4)), dim3(256), 0, ctx->stream, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    ctx->lk_pyr[slot].w = s.w, ctx->lk_pyr[slot].h = s.h, ctx->lk_pyr[slot].top = top;
+    return PAGK_OK;
+}
+
+using LkKernel = void (*)(LkTrackArgs);
+LkKernel lk_kernel(int win)
+{
+    switch (lk_npix(win)) {
+        case 1: return k_lk_track<1>;
+        case 2: return k_lk_track<2>;
+        case 4: return k_lk_track<4>;
+        case 8: return k_lk_track<8>;
+        default: return k_lk_track<16>;
+    }
+}
+
+int lk_track_slots(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
+                   const float *d_pt_ref, const int32_t *d_n, float *d_pt_out, uint8_t *d_status, uint8_t *d_status_raw,
+                   float *d_err, float *d_flow, int32_t *d_info)
+{
+    if (!ctx || lk_params_check(params) || slot_ref < 0 || slot_ref >= kSlots || slot_cur < 0 || slot_cur >= kSlots ||
+        cap < 1 || cap > kLkMaxRows || !d_pt_ref || !d_pt_out || !d_status || !d_err || !d_info)
+        return PAGK_E_ARG;
+    const FrameSlot &r = ctx->slots[slot_ref], &c = ctx->slots[slot_cur];
+    if (!lk_slot_ok(r) || !lk_slot_ok(c) || r.w != c.w || r.h != c.h) return PAGK_E_ARG;
+    int lw[kLkMaxLevels], lh[kLkMaxLevels];
+    const int top = lk_levels(r.w, r.h, params, lw, lh);
+    if (top < 0) return PAGK_E_ARG;
+    const int32_t both[2] = {slot_ref, slot_cur};
+    for (int32_t slot : both) {
+        const pagk_ctx::LkPyr &p = ctx->lk_pyr[slot];
+        if (p.top < top || p.w != r.w || p.h != r.h) {
+            snprintf(ctx->err, sizeof(ctx->err), "pagk_lk_track_device: slot %d has no Lucas-Kanade pyramid of %d x %d with top level %d "
+                     "(pagk_lk_pyramid_device)", slot, r.w, r.h, top);
+            return PAGK_E_ARG;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LkTrackArgs a = {};
+    for (int k = 0; k < 2; k++) {
+        const FrameSlot &s = k ? c : r;
+        // (a level's offset depends on the levels below it alone: the same whatever top level the buffer was carved for)
+        const Layout<kLkMaxLevels> lay = lk_layout(lw, lh, top);
+        void *base = ctx->buf[pagk_ctx::LK_PYR + both[k]].ptr;
+        for (int l = 0; l <= top; l++) {
+            const uint8_t *img = l ? lay.at<uint8_t>(base, l - 1) : s.img0;
+            const long long pitch = l ? (long long)lw[l] : (long long)s.pitch0;
+            if (k)
+                a.lv[l].J = img, a.lv[l].pitch_j = pitch;
+            else
+                a.lv[l].I = img, a.lv[l].pitch_i = pitch;
+            a.lv[l].w = lw[l], a.lv[l].h = lh[l];
+        }
+    }
+    a.pt_ref = d_pt_ref, a.n = d_n, a.pt_out = d_pt_out, a.status = d_status, a.status_raw = d_status_raw, a.err = d_err;
+    a.flow = d_flow, a.info = d_info;
+    a.eps2 = params->epsilon * params->epsilon, a.min_eig = params->min_eig_threshold, a.err_threshold = params->err_threshold;
+    a.cap = cap, a.win = 2 * params->half_patch + 1, a.top = top, a.max_count = params->max_count;
+    HIPCHK(ctx, hipMemsetAsync(d_info, 0, kLkInfoWords * sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(lk_kernel(a.win), dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+}  // namespace
+
+void pagk_lk_params_default(pagk_lk_params *p)
+{
+    if (!p) return;
+    p->half_patch = 10;           // mHalfPatchSize of the reference's experiment
+    p->max_level = 2;             // src/gyro_aided_tracker.cpp:362
+    p->max_count = 30;            // :363
+    p->epsilon = 0.01;            // :363
+    p->min_eig_threshold = 1e-4;  // :366
+    p->err_threshold = 12.0f;     // :372
+}
+
+int pagk_lk_params_check(const pagk_lk_params *p) { return lk_params_check(p); }
+
+int pagk_lk_levels(int32_t width, int32_t height, const pagk_lk_params *params)
+{
+    if (lk_params_check(params) || width < 1 || height < 1) return PAGK_E_ARG;
+    int lw[kLkMaxLevels], lh[kLkMaxLevels];
+    return lk_levels(width, height, params, lw, lh);
+}
+
+int pagk_lk_pyramid_device(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot)
+{
+    if (slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return lk_pyramid_slot(ctx, params, slot);
+}
+
+int pagk_lk_track_device(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
+                         const float *d_pt_ref, const int32_t *d_n, float *d_pt_out, uint8_t *d_status, uint8_t *d_status_raw,
+                         float *d_err, float *d_flow, int32_t *d_info)
+{
+    if (slot_ref < 0 || slot_ref >= kUserSlots || slot_cur < 0 || slot_cur >= kUserSlots) return PAGK_E_ARG;
+    return lk_track_slots(ctx, params, slot_ref, slot_cur, cap, d_pt_ref, d_n, d_pt_out, d_status, d_status_raw, d_err, d_flow,
+                          d_info);
+}
+
+int pagk_lk_track(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_image *ref, const pagk_image *cur, int32_t n,
+                  const float *pt_ref, float *pt_out, uint8_t *status, uint8_t *status_raw, float *err, float *flow,
+                  int32_t *info)
+{
+    if (!ctx || !ref || !cur || lk_params_check(params)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_lk_track");
+    if (n < 0 || n > kLkMaxRows || (n && (!pt_ref || !pt_out || !status || !err))) return PAGK_E_ARG;
+    if (ref->width != cur->width || ref->height != cur->height || pagk_lk_levels(ref->width, ref->height, params) < 0)
+        return PAGK_E_ARG;
+    int rc;
+    if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
+    if ((rc = lk_pyramid_slot(ctx, params, 4)) || (rc = lk_pyramid_slot(ctx, params, 5))) return rc;
+    const size_t nc = (size_t)std::max(n, 1);
+    // points in | count | points out | status | raw status | err | flow | info
+    const size_t sizes[8] = {nc * 8, 256, nc * 8, nc, nc, nc * 4, nc * 8, 256};
+    const Layout<8> lay(sizes);
+    Scratch s;
+    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), pt_ref, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), &n, 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = lk_track_slots(ctx, params, 4, 5, (int32_t)nc, lay.at<float>(s.p, 0), lay.at<int32_t>(s.p, 1), lay.at<float>(s.p, 2),
+                        lay.at<uint8_t>(s.p, 3), lay.at<uint8_t>(s.p, 4), lay.at<float>(s.p, 5), lay.at<float>(s.p, 6),
+                        lay.at<int32_t>(s.p, 7));
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);   // (&n is read by the copy above)
+        return rc;
+    }
+    if (n) {
+        HIPCHK(ctx, hipMemcpyAsync(pt_out, lay.at<void>(s.p, 2), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(status, lay.at<void>(s.p, 3), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        if (status_raw) HIPCHK(ctx, hipMemcpyAsync(status_raw, lay.at<void>(s.p, 4), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(err, lay.at<void>(s.p, 5), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (flow) HIPCHK(ctx, hipMemcpyAsync(flow, lay.at<void>(s.p, 6), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 7), kLkInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+int pagk_selftest_lk_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int64_t pitch)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots || !dst) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_lk_level");
+    const FrameSlot &s = ctx->slots[slot];
+    const pagk_ctx::LkPyr &p = ctx->lk_pyr[slot];
+    if (!lk_slot_ok(s) || p.top < 0 || p.w != s.w || p.h != s.h || level < 1 || level > p.top) return PAGK_E_ARG;
+    int lw[kLkMaxLevels], lh[kLkMaxLevels];
+    lw[0] = s.w, lh[0] = s.h;
+    for (int l = 1; l <= p.top; l++) lw[l] = (lw[l - 1] + 1) / 2, lh[l] = (lh[l - 1] + 1) / 2;
+    if (pitch < lw[level]) return PAGK_E_ARG;
+    const Layout<kLkMaxLevels> lay = lk_layout(lw, lh, p.top);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpy2DAsync(dst, (size_t)pitch, lay.at<uint8_t>(ctx->buf[pagk_ctx::LK_PYR + slot].ptr, level - 1),
+                                 (size_t)lw[level], (size_t)lw[level], (size_t)lh[level], hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
 }

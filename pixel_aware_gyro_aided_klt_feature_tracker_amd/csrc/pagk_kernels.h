@@ -1279,5 +1279,6 @@ __global__ void __launch_bounds__(256, 4) k_track_block_pyr(TrackArgs a, PyrArgs
 #include "pagk_fast_kernel.h"
 #include "pagk_rectify_kernel.h"
 #include "pagk_orb_kernel.h"
+#include "pagk_lk_kernel.h"
 #include "pagk_neighbor_kernel.h"
 #include "pagk_selftest_kernel.h"

@@ -24,6 +24,9 @@ def load():
         lib.pagk_tracker_track_features.restype = C.c_int
         lib.pagk_tracker_track_features.argtypes = [vp, vp, i, i, C.c_long, i, vp, vp, vp, i, i, i, i, vp, vp, i,
                                                     C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(lib, "pagk_tracker_track_features_ex"):   # (absent from an older shell loaded for an A/B run)
+            lib.pagk_tracker_track_features_ex.restype = C.c_int
+            lib.pagk_tracker_track_features_ex.argtypes = lib.pagk_tracker_track_features.argtypes + [vp, vp]
         lib.pagk_tracker_geometry_validation.restype = C.c_int
         lib.pagk_tracker_geometry_validation.argtypes = [i, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
         lib.pagk_tracker_geometry_validation_fit.restype = C.c_int
@@ -48,7 +51,9 @@ def load():
 
 def track_features(img_ref, img_cur, keys_ref, K, dist, *, type=4, half_patch=5, iterations=10, pyramids=3,
                    Rcl=None, imu=None, t_ref=0.0, t_cur=0.0):
-    """GyroAidedTracker(ctor #1) -> TrackFeatures() (reference Examples/Demo/RealSenseD435i.cpp:244-251)."""
+    """GyroAidedTracker(ctor #1) -> TrackFeatures() (reference Examples/Demo/RealSenseD435i.cpp:244-251).  type 0 (pyramidal
+    Lucas-Kanade, src/gyro_aided_tracker.cpp:353-380) fills status, pt_predict_un, pt_predict, error (mvError) and
+    flows_predict_un (mvFlowsPredictUn) and returns the number of kept features."""
     lib = load()
     n = int(keys_ref.shape[0])
     nn = max(n, 1)
@@ -60,15 +65,19 @@ def track_features(img_ref, img_cur, keys_ref, K, dist, *, type=4, half_patch=5,
     out = dict(status=np.zeros(nn, np.uint8), pt_predict_un=np.zeros((nn, 2), np.float32),
                pt_predict=np.zeros((nn, 2), np.float32), status_pm=np.zeros(nn, np.uint8),
                pt_pm_un=np.zeros((nn, 2), np.float32), pix_err=np.zeros(nn, np.float64),
-               dist_pred=np.zeros(nn, np.float64), affine=np.zeros((nn, 4), np.float32))
-    ret = lib.pagk_tracker_track_features(
-        img_ref.ctypes.data, img_cur.ctypes.data, img_ref.shape[1], img_ref.shape[0], img_ref.strides[0], n,
-        keys_ref.ctypes.data, K.ctypes.data, dist.ctypes.data, type, half_patch, iterations, pyramids,
-        None if R is None else R.ctypes.data, None if imu_a is None else imu_a.ctypes.data,
-        0 if imu_a is None else int(imu_a.shape[0]), t_ref, t_cur,
-        out["status"].ctypes.data, out["pt_predict_un"].ctypes.data, out["pt_predict"].ctypes.data,
-        out["status_pm"].ctypes.data, out["pt_pm_un"].ctypes.data, out["pix_err"].ctypes.data,
-        out["dist_pred"].ctypes.data, out["affine"].ctypes.data)
+               dist_pred=np.zeros(nn, np.float64), affine=np.zeros((nn, 4), np.float32),
+               error=np.zeros(nn, np.float32), flows_predict_un=np.zeros((nn, 2), np.float32))
+    args = [img_ref.ctypes.data, img_cur.ctypes.data, img_ref.shape[1], img_ref.shape[0], img_ref.strides[0], n,
+            keys_ref.ctypes.data, K.ctypes.data, dist.ctypes.data, type, half_patch, iterations, pyramids,
+            None if R is None else R.ctypes.data, None if imu_a is None else imu_a.ctypes.data,
+            0 if imu_a is None else int(imu_a.shape[0]), t_ref, t_cur,
+            out["status"].ctypes.data, out["pt_predict_un"].ctypes.data, out["pt_predict"].ctypes.data,
+            out["status_pm"].ctypes.data, out["pt_pm_un"].ctypes.data, out["pix_err"].ctypes.data,
+            out["dist_pred"].ctypes.data, out["affine"].ctypes.data]
+    if hasattr(lib, "pagk_tracker_track_features_ex"):
+        ret = lib.pagk_tracker_track_features_ex(*args, out["error"].ctypes.data, out["flows_predict_un"].ctypes.data)
+    else:   # an older shell: no type 0, error and flows_predict_un stay zero
+        ret = lib.pagk_tracker_track_features(*args)
     if ret == -100:
         raise RuntimeError("GyroAidedTracker: " + lib.pagk_tracker_last_error().decode())
     return ret, {k: v[:n] for k, v in out.items()}
@@ -286,3 +295,13 @@ def orb_match_pair(img_ref, img_cur, n_features: int, pattern, fast=None, orb=No
     out = c.orb_match(ref["desc"], cur["desc"], orb)
     out.update(ref=ref, cur=cur)
     return out
+
+
+# ---- pyramidal Lucas-Kanade, the image-only baseline of the comparison (src/gyro_aided_tracker.cpp:353-380), ----
+# ---- array in, array out ----
+def lk_track(img_ref, img_cur, pts, lk=None, ctx=None) -> dict:
+    """cv::calcOpticalFlowPyrLK and the error filter of TrackFeatures' type 0 by the library's definition (pagk_lk_track) ->
+    dict(pt_out (n x 2 float32), status (n, after the filter), status_raw (n), err (n), flow (n x 2), info and its words by
+    name: n, raw, kept, top_level, lost_min_eig, lost_out_of_range)."""
+    return _device_context(ctx).lk_track(np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8),
+                                         pts, lk)
