@@ -134,12 +134,24 @@ int lk_ref_level(const uint8_t *img, int32_t w, int32_t h, int64_t step, int32_t
     return 0;
 }
 
+/* why a feature left a level (the optional record `why` of lk_ref_track) */
+enum {
+    WHY_NOT_VISITED = 0,   /* the level is above the effective top level, or the feature was done */
+    WHY_TEMPLATE = 1,      /* step 2: the template is out of range */
+    WHY_MIN_EIG = 2,       /* step 5: the min-eigenvalue or the determinant test failed */
+    WHY_RANGE = 3,         /* step 6: out of range inside the iteration */
+    WHY_EPSILON = 4,       /* step 6: stopped by epsilon */
+    WHY_OSCILLATION = 5,   /* step 6: stopped by the oscillation rule */
+    WHY_COUNT = 6          /* step 6: the iteration count was used up */
+};
+
 /* The tracker.  pt_ref, pt_out, flow: cap x 2; status, status_raw: cap bytes; err: cap; info: INFO_WORDS; iters (or NULL):
- * cap int32, the iterations run at level 0.  Rows at or beyond n (clamped to [0, cap]) are zeroed. */
+ * cap int32, the iterations run at level 0; why (or NULL): cap x MAX_LEVELS bytes, byte [k][l] says why feature k left level
+ * l (the WHY_ codes above).  Rows at or beyond n (clamped to [0, cap]) are zeroed. */
 int lk_ref_track(const uint8_t *ref, const uint8_t *cur, int32_t w, int32_t h, int64_t step_ref, int64_t step_cur,
                  int32_t half_patch, int32_t max_level, int32_t max_count, double epsilon, double min_eig_threshold,
                  float err_threshold, int32_t n, int32_t cap, const float *pt_ref, float *pt_out, uint8_t *status,
-                 uint8_t *status_raw, float *err, float *flow, int32_t *info, int32_t *iters)
+                 uint8_t *status_raw, float *err, float *flow, int32_t *info, int32_t *iters, uint8_t *why)
 {
     const int win = 2 * half_patch + 1;
     const int top = lk_ref_levels(w, h, half_patch, max_level);
@@ -156,7 +168,9 @@ int lk_ref_track(const uint8_t *ref, const uint8_t *cur, int32_t w, int32_t h, i
         pt_out[2 * k] = pt_out[2 * k + 1] = flow[2 * k] = flow[2 * k + 1] = err[k] = 0.f;
         status[k] = status_raw[k] = 0;
         if (iters) iters[k] = 0;
+        if (why) memset(why + (size_t)k * MAX_LEVELS, WHY_NOT_VISITED, MAX_LEVELS);
         if (k >= n) continue;
+        uint8_t *const left = why ? why + (size_t)k * MAX_LEVELS : NULL;
         int st = 1;
         float e = 0.f, nx = 0.f, ny = 0.f;
         for (int l = top; l >= 0; l--) {
@@ -170,6 +184,7 @@ int lk_ref_track(const uint8_t *ref, const uint8_t *cur, int32_t w, int32_t h, i
             const float fx = floorf(px), fy = floorf(py);
             if (out_of_range(fx, fy, win, I->w, I->h)) {
                 if (l == 0) st = 0, e = 0.f, info[5]++;
+                if (left) left[l] = WHY_TEMPLATE;
                 continue;
             }
             const int ipx = (int)fx, ipy = (int)fy;
@@ -194,14 +209,17 @@ int lk_ref_track(const uint8_t *ref, const uint8_t *cur, int32_t w, int32_t h, i
             const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
             if ((double)minEig < min_eig_threshold || D < FLT_EPSILON) {
                 if (l == 0) st = 0, info[4]++;
+                if (left) left[l] = WHY_MIN_EIG;
                 continue;
             }
             D = 1.f / D;
             float qx = nx - half, qy = ny - half, pdx = 0.f, pdy = 0.f;
+            int code = WHY_COUNT;
             for (int j = 0; j < max_count; j++) {
                 const float gx = floorf(qx), gy = floorf(qy);
                 if (out_of_range(gx, gy, win, J->w, J->h)) {
                     if (l == 0) st = 0, info[5]++;
+                    code = WHY_RANGE;
                     break;
                 }
                 if (l == 0 && iters) iters[k] = j + 1;
@@ -217,13 +235,18 @@ int lk_ref_track(const uint8_t *ref, const uint8_t *cur, int32_t w, int32_t h, i
                 const float ddx = (A12 * b2 - A22 * b1) * D, ddy = (A12 * b1 - A11 * b2) * D;
                 qx += ddx, qy += ddy;
                 nx = qx + half, ny = qy + half;
-                if ((double)ddx * ddx + (double)ddy * ddy <= epsilon * epsilon) break;
+                if ((double)ddx * ddx + (double)ddy * ddy <= epsilon * epsilon) {
+                    code = WHY_EPSILON;
+                    break;
+                }
                 if (j > 0 && (double)fabsf(ddx + pdx) < 0.01 && (double)fabsf(ddy + pdy) < 0.01) {
                     nx -= ddx * 0.5f, ny -= ddy * 0.5f;
+                    code = WHY_OSCILLATION;
                     break;
                 }
                 pdx = ddx, pdy = ddy;
             }
+            if (left) left[l] = (uint8_t)code;
             if (l == 0 && st) {
                 const float ex = nx - half, ey = ny - half, gx = floorf(ex), gy = floorf(ey);
                 if (out_of_range(gx, gy, win, J->w, J->h)) {

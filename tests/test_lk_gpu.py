@@ -1,6 +1,8 @@
 """GPU tests of pyramidal Lucas-Kanade (tracker type 0): pagk_lk_pyramid_device, pagk_lk_track_device and pagk_lk_track against
 the plain-C restatement (tests/lk_ref.c), bit for bit, on the smallest shapes at which each rule can go wrong; capture and
-replay; the argument checks on a live context; GyroAidedTracker::TrackFeatures with type 0 through the C++ shell."""
+replay; a second table of edge cases (every k_lk_track<NPIX> at both ends of its window range, parameters off their defaults,
+extreme contrast, unequal pitches, the pyramid kernel's grid); the argument checks on a live context;
+GyroAidedTracker::TrackFeatures with type 0 through the C++ shell."""
 import numpy as np
 import pytest
 import torch
@@ -22,13 +24,17 @@ def shapes():
     return lu.shapes(synth)
 
 
+EDGE = lu.edge_shapes(synth)          # the second table (built here for the test ids)
+PYRAMIDS = lu.pyramid_shapes()
+
+
 @pytest.fixture(scope="module")
 def restated(ref, shapes):
-    """name -> the restatement of that shape, computed once and left unchanged."""
+    """name (of either table) -> the restatement of that shape, computed once and left unchanged."""
     memo = {}
 
     def get(name, n=None):
-        c = shapes[name]
+        c = shapes[name] if name in shapes else EDGE[name]
         n = c["n"] if n is None else n
         if (name, n) not in memo:
             memo[(name, n)] = lu.ref_track(ref, c["ref"], c["cur"], c["pts"], c["p"], c["cap"], n)
@@ -40,14 +46,17 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
-def _set_slot(ctx, slot, img, pitch=None):
+def _set_slot(ctx, slot, img, pitch=None, junk=None):
     """The image into a frame slot: uploaded, or read in place from the left columns of a wider device buffer (returned:
-    the caller keeps it alive while the slot is used)."""
+    the caller keeps it alive while the slot is used); right of the image 255, or seeded junk."""
     h, w = img.shape
     if pitch is None:
         ctx.frame_upload(slot, img, 1)
         return None
-    keep = torch.full((h, pitch), 255, dtype=torch.uint8, device=DEV)
+    if junk is None:
+        keep = torch.full((h, pitch), 255, dtype=torch.uint8, device=DEV)
+    else:
+        keep = _dev(np.random.default_rng(junk).integers(0, 256, (h, pitch), dtype=np.uint8))
     keep[:, :w] = _dev(img)
     torch.cuda.synchronize()
     ctx.frame_set_device(slot, keep.data_ptr(), w, h, pitch, 1)
@@ -59,11 +68,17 @@ def _lk(p: dict):
 
 
 def _device_track(ctx, c, n=None, pitch=None, with_optional=True, with_count=True):
-    """pagk_lk_pyramid_device on slots 0 and 1, then pagk_lk_track_device: every output pre-filled with junk."""
+    """pagk_lk_pyramid_device on slots 0 and 1, then pagk_lk_track_device: every output pre-filled with junk.  pitch: None,
+    one pitch for both slots, or the pair (reference, current) with junk right of the image.  A case may name other
+    parameters for its pyramids ("pyr")."""
     lk = _lk(c["p"])
-    keep = [_set_slot(ctx, s, img, pitch) for s, img in ((0, c["ref"]), (1, c["cur"]))]
-    ctx.lk_pyramid_device(lk, 0)
-    ctx.lk_pyramid_device(lk, 1)
+    if isinstance(pitch, tuple):
+        keep = [_set_slot(ctx, s, img, pt, junk=80 + s) for s, img, pt in ((0, c["ref"], pitch[0]), (1, c["cur"], pitch[1]))]
+    else:
+        keep = [_set_slot(ctx, s, img, pitch) for s, img in ((0, c["ref"]), (1, c["cur"]))]
+    lk_pyr = _lk(c["pyr"]) if c.get("pyr") else lk
+    ctx.lk_pyramid_device(lk_pyr, 0)
+    ctx.lk_pyramid_device(lk_pyr, 1)
     cap = max(len(c["pts"]), 1) if c["cap"] is None else c["cap"]
     n = (len(c["pts"]) if c["n"] is None else c["n"]) if n is None else n
     buf = np.zeros((cap, 2), np.float32)                  # (rows beyond the list: as the restatement's helper fills them)
@@ -155,6 +170,53 @@ def test_host_form_equals_the_device_form(ctx, shapes, restated):
     assert lu.differing(via, restated(SHAPES[1])) == []
 
 
+# ---- the edge table ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(EDGE))
+def test_edge_track_device_equals_the_restatement(ctx, restated, name):
+    """Every case of lk_ref_util.edge_shapes() (tests/test_lk_cpu.py says which exits of the level loop they take): the name
+    says the window and k_lk_track<NPIX>, or the parameter that left its default."""
+    c = EDGE[name]
+    got = _device_track(ctx, c, pitch=c["pitch"])
+    want = restated(name)
+    print(f"{name}: k_lk_track<{c['npix']}>, info {got['info'][:6].tolist()} (restated {want['info'][:6].tolist()})")
+    bad = lu.differing(got, want)
+    if bad:                                                # the first differing feature and why it left each level
+        key = next(k for k in bad if k != "info") if bad != ["info"] else "info"
+        if key != "info":
+            k = int(np.flatnonzero([not lu.same_array(a, b) for a, b in zip(got[key], want[key])])[0])
+            print(f"  {key}[{k}]: device {got[key][k]}, restated {want[key][k]}, pt_ref {c['pts'][k]}, why {want['why'][k].tolist()}")
+    assert bad == []
+
+
+@pytest.mark.parametrize("name", [n for n, c in EDGE.items() if c["host"]])
+def test_edge_host_form_equals_the_restatement(ctx, restated, name):
+    """pagk_lk_track on the smallest legal frame of every window and on every k_lk_track<4> case that needs no device slot
+    of its own (pitches, deeper pyramids)."""
+    c = EDGE[name]
+    got = ctx.lk_track(c["ref"], c["cur"], c["pts"], _lk(c["p"]))
+    want = restated(name)
+    assert lu.differing(got, want) == []
+    assert (got["n"], got["raw"], got["kept"], got["top_level"]) == tuple(int(v) for v in want["info"][:4])
+
+
+@pytest.mark.parametrize("name", list(PYRAMIDS))
+def test_pyramid_grid_equals_the_restatement(ctx, ref, name):
+    """k_lk_pyrdown beyond its first 64 x 4 block in both directions: level widths 63, 64, 65, 128 and 129, level heights of
+    every residue modulo 4, the source slot with and without a pitch."""
+    img = PYRAMIDS[name]
+    p = lu.params(half_patch=1, max_level=7)
+    lk = _lk(p)
+    levels = lu.ref_levels(ref, img, p)
+    assert len(levels) - 1 == capi.lk_levels(img.shape[1], img.shape[0], lk) >= 1
+    for pitch in (None, img.shape[1] + 13):
+        keep = _set_slot(ctx, 2, img, pitch, junk=81)
+        ctx.lk_pyramid_device(lk, 2)
+        for l in range(1, len(levels)):
+            h, w = levels[l].shape
+            assert np.array_equal(ctx.selftest_lk_level(2, l, w, h), levels[l]), (name, pitch, l)
+        del keep
+
+
 # ---- capture -----------------------------------------------------------------------------------------------------------
 def test_capture_pyramids_and_track_and_replay(ref):
     w, h, cap = 96, 64, 40
@@ -206,6 +268,61 @@ def test_capture_pyramids_and_track_and_replay(ref):
                 gid = c.graph_end()
             for k in (1, 2):                          # replayed twice, the second frame changed in place
                 feed(k)
+                for t in outs:
+                    t.fill_(9)
+                c.graph_launch(gid)
+                assert lu.differing(result(), want[k]) == [], ("replay", k)
+            c.graph_destroy(gid)
+    finally:
+        c.set_stream(None)
+        c.close()
+
+
+def test_capture_and_replay_half_patch_7(ref):
+    """The pattern of test_capture_pyramids_and_track_and_replay on k_lk_track<4> (window 15, three levels): replayed twice,
+    the current frame changed in place in between, each replay held to the restatement."""
+    w, h, cap = 96, 80, 40
+    frames = [lu.texture_pair(synth, w, h, 45, s)[1] for s in ((0, 0), (1.4, -0.9), (-1.8, 2.2))]
+    pts = lu.mixed_points(w, h, 15, 37, 46, nonfinite=True)
+    p = lu.params(half_patch=7)
+    lk = _lk(p)
+    c = capi.Context(0)
+    try:
+        stream = torch.cuda.Stream()
+        with torch.cuda.stream(stream):
+            c.set_stream(stream.cuda_stream)
+            d_img = [torch.full((h, w + 16), 0xa5, dtype=torch.uint8, device=DEV) for _ in range(2)]
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)     # noqa: E731
+            buf = np.zeros((cap, 2), np.float32)
+            buf[:len(pts)] = pts
+            d_p, d_n = _dev(buf), _dev(np.array([len(pts)], np.int32))
+            outs = [z((cap, 2), torch.float32), z(cap, torch.uint8), z(cap, torch.uint8), z(cap, torch.float32),
+                    z((cap, 2), torch.float32), z(capi.LK_INFO_WORDS, torch.int32)]
+            d_img[0][:, :w] = _dev(frames[0])
+
+            def work():
+                for s in range(2):
+                    c.frame_set_device(s, d_img[s].data_ptr(), w, h, w + 16, 1)
+                    c.lk_pyramid_device(lk, s)
+                c.lk_track_device(lk, 0, 1, cap, d_p, d_n, outs[0], outs[1], outs[2], outs[3], outs[4], outs[5])
+
+            def result():
+                stream.synchronize()
+                o = [t.cpu().numpy() for t in outs]
+                return dict(pt_out=o[0], status=o[1], status_raw=o[2], err=o[3], flow=o[4], info=o[5])
+
+            want = {k: lu.ref_track(ref, frames[0], frames[k], pts, p, cap) for k in (1, 2)}
+            assert want[1]["info"][3] == 2 and lu.differing(want[1], want[2]) != []
+            d_img[1][:, :w] = _dev(frames[1])
+            work()                                    # the direct call sizes the pyramids' buffers
+            assert lu.differing(result(), want[1]) == [], "direct"
+            c.graph_begin()
+            try:
+                work()
+            finally:
+                gid = c.graph_end()
+            for k in (2, 1):                          # replayed twice, the current frame changed in place
+                d_img[1][:, :w] = _dev(frames[k])
                 for t in outs:
                     t.fill_(9)
                 c.graph_launch(gid)
