@@ -260,6 +260,59 @@ int reserve(pagk_ctx *ctx, DevBuf &b, size_t bytes, GrowPolicy policy, const cha
     return PAGK_OK;
 }
 
+// One synchronous host-buffer call: a device block carved into N parts, inputs copied in, the device form's launches,
+// outputs copied out, one synchronisation.  The block is a context buffer (`keep`, grown freely) or the call's own, freed
+// with the object.  The host side of a queued copy is a caller's array or a local of the entry point, so no path returns
+// with a copy pending: an object that dies with copies queued and finish() not reached synchronises first.  Declare the
+// locals that copies read or write in front of the object.
+template <int N>
+class Staged {
+public:
+    Staged(pagk_ctx *ctx, const size_t (&sizes)[N]) : ctx_(ctx), lay_(sizes) {}
+    Staged(const Staged &) = delete;
+    Staged &operator=(const Staged &) = delete;
+    ~Staged()
+    {
+        if (pending_) (void)hipStreamSynchronize(ctx_->stream);
+        if (own_) (void)hipFree(own_);
+    }
+    int open(DevBuf *keep, const char *what)
+    {
+        if (keep) {
+            int rc = reserve(ctx_, *keep, lay_.total, GROW_FREELY, what);
+            base_ = keep->ptr;
+            return rc;
+        }
+        HIPCHK(ctx_, hipMalloc(&own_, lay_.total));
+        base_ = own_;
+        return PAGK_OK;
+    }
+    template <class T>
+    T *at(int k) const { return lay_.template at<T>(base_, k); }
+    // queue a copy into / out of part k; nothing when the host array is NULL or there are no bytes
+    int in(int k, const void *src, size_t bytes) { return copy(at<void>(k), src, bytes, hipMemcpyHostToDevice); }
+    int out(int k, void *dst, size_t bytes) { return copy(dst, at<void>(k), bytes, hipMemcpyDeviceToHost); }
+    int finish()
+    {
+        pending_ = false;
+        HIPCHK(ctx_, hipStreamSynchronize(ctx_->stream));
+        return PAGK_OK;
+    }
+
+private:
+    int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+    {
+        if (!dst || !src || !bytes) return PAGK_OK;
+        pending_ = true;
+        HIPCHK(ctx_, hipMemcpyAsync(dst, src, bytes, kind, ctx_->stream));
+        return PAGK_OK;
+    }
+    pagk_ctx *ctx_;
+    Layout<N> lay_;
+    void *base_ = nullptr, *own_ = nullptr;
+    bool pending_ = false;
+};
+
 // Close the open capture segment of pagk_graph_begin (what was recorded so far becomes one instantiated graph in
 // ctx->cap_segs) and open the next one.  Used around a launch whose finisher must not be a graph node.
 int capture_split(pagk_ctx *ctx)
@@ -2085,6 +2138,15 @@ int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int
                     uint8_t *d_mask, int32_t *d_state, const pagk_detect_params *det = nullptr,
                     const FrameSlot *s = nullptr, int32_t *d_info = nullptr);
 
+// The host-buffer hand-overs: the caller's arrays through one device block around the device step.  The candidates are the
+// caller's list (neither det nor fast), or the corners (det) or FAST keypoints (fast) found on scratch slot 4 and counted
+// in info.
+int handover_host(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                  double new_point_threshold, const uint8_t *status, const float *pt_predict, const float *pt_predict_un,
+                  int32_t cand_cap, const int32_t *n_cand, const float *cand_un, const pagk_detect_params *det,
+                  const pagk_fast_params *fast, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
+                  uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info);
+
 }  // namespace
 
 int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -2116,40 +2178,13 @@ int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width,
         !index_in_last || !live || !state)
         return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nc = (size_t)cap, cc = (size_t)(cand_cap > 0 ? cand_cap : 1), px = (size_t)width * height;
-    // status | pt_predict | pt_predict_un | n_cand | cand | keys | keys_un | keys_normal | index | live | state | mask
-    const size_t sizes[12] = {nc, nc * 8, nc * 8, 4, cc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4, px};
-    const Layout<12> lay(sizes);
-    int rc = reserve(ctx, ctx->buf[pagk_ctx::HANDIO], lay.total, GROW_FREELY, "the host-buffer hand-over's scratch");
-    if (rc) return rc;
-    void *b = ctx->buf[pagk_ctx::HANDIO].ptr;
-    const void *src[5] = {status, pt_predict, pt_predict_un, n_cand, cand_un};
-    for (int k = 0; k < 5; k++)
-        if (src[k] && (k != 4 || cand_cap > 0))
-            HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 10), state, sizes[10], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
-    rc = pagk_frame_handover_device(
-        ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0), lay.at<float>(b, 1),
-        lay.at<float>(b, 2), cand_cap, lay.at<int32_t>(b, 3), lay.at<float>(b, 4), lay.at<float>(b, 5), lay.at<float>(b, 6),
-        keys_normal ? lay.at<float>(b, 7) : nullptr, lay.at<int32_t>(b, 8), lay.at<uint8_t>(b, 9), lay.at<uint8_t>(b, 11),
-        lay.at<int32_t>(b, 10));
-    if (rc) return rc;
-    void *dst[7] = {keys, keys_un, keys_normal, index_in_last, live, state, mask};
-    const int from[7] = {5, 6, 7, 8, 9, 10, 11};
-    for (int k = 0; k < 7; k++)
-        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un,
+                         cand_cap, n_cand, cand_un, nullptr, nullptr, keys, keys_un, keys_normal, index_in_last, live, mask, state,
+                         nullptr);
 }
 
 // ---- corner detection (pagk_detect_kernel.h) -------------------------------------------------------------------
 namespace {
-
-// a device block of a synchronous host-buffer entry point, freed when the call returns
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-};
 
 bool detect_params_ok(const pagk_detect_params *d)
 {
@@ -2336,22 +2371,13 @@ int pagk_detect_corners(pagk_ctx *ctx, const pagk_detect_params *det, const pagk
     int rc = frame_upload_any(ctx, 4, img, 1);
     if (rc) return rc;
     const size_t px = (size_t)img->width * img->height, cap = (size_t)(max_corners > 0 ? max_corners : 1);
-    const size_t sizes[3] = {px, cap * 8, 512};   // mask | corners | info words, then max_corners
-    const Layout<3> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    uint8_t *d_mask = mask ? lay.at<uint8_t>(s.p, 0) : nullptr;
-    float *d_corners = lay.at<float>(s.p, 1);
-    int32_t *d_info = lay.at<int32_t>(s.p, 2), *d_max = d_info + 64;
-    if (mask) HIPCHK(ctx, hipMemcpyAsync(d_mask, mask, px, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_max, &max_corners, 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = detect_corners_slot(ctx, det, 4, d_mask, (int32_t)cap, d_max, d_corners, d_info);
-    if (rc) return rc;
-    if (max_corners > 0)
-        HIPCHK(ctx, hipMemcpyAsync(corners, d_corners, (size_t)max_corners * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, d_info, kDetectInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    const size_t sizes[4] = {px, cap * 8, 256, 256};   // mask | corners | info | max_corners
+    Staged<4> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, mask, px)) || (rc = s.in(3, &max_corners, 4))) return rc;
+    rc = detect_corners_slot(ctx, det, 4, mask ? s.at<uint8_t>(0) : nullptr, (int32_t)cap, s.at<int32_t>(3), s.at<float>(1),
+                             s.at<int32_t>(2));
+    if (rc || (rc = s.out(1, corners, (size_t)max_corners * 8)) || (rc = s.out(2, info, kDetectInfoWords * 4))) return rc;
+    return s.finish();
 }
 
 int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R)
@@ -2407,28 +2433,8 @@ int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t
         return PAGK_E_ARG;
     int rc = frame_upload_any(ctx, 4, img, 1);
     if (rc) return rc;
-    const size_t nc = (size_t)cap, px = (size_t)width * height;
-    // status | pt_predict | pt_predict_un | keys | keys_un | keys_normal | index | live | state | info | mask
-    const size_t sizes[11] = {nc, nc * 8, nc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4,
-                              kDetectInfoWords * 4, px};
-    const Layout<11> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    void *b = s.p;
-    const void *src[3] = {status, pt_predict, pt_predict_un};
-    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 8), state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
-    rc = handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0),
-                         lay.at<float>(b, 1), lay.at<float>(b, 2), 0, nullptr, nullptr, lay.at<float>(b, 3), lay.at<float>(b, 4),
-                         keys_normal ? lay.at<float>(b, 5) : nullptr, lay.at<int32_t>(b, 6), lay.at<uint8_t>(b, 7),
-                         lay.at<uint8_t>(b, 10), lay.at<int32_t>(b, 8), det, &ctx->slots[4], lay.at<int32_t>(b, 9));
-    if (rc) return rc;
-    void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
-    const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
-    for (int k = 0; k < 8; k++)
-        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, 0,
+                         nullptr, nullptr, det, nullptr, keys, keys_un, keys_normal, index_in_last, live, mask, state, info);
 }
 
 // ---- the FAST detector: cells and quadtree (pagk_fast_kernel.h) --------------------------------------------------
@@ -2645,18 +2651,12 @@ int pagk_detect_fast(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_i
     if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
     const size_t px = (size_t)img->width * img->height, nc = (size_t)cap;
     const size_t sizes[4] = {px, nc * 8, nc * 4, 256};   // mask | keypoints | response | info
-    const Layout<4> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    uint8_t *d_mask = mask ? lay.at<uint8_t>(s.p, 0) : nullptr;
-    if (mask) HIPCHK(ctx, hipMemcpyAsync(d_mask, mask, px, hipMemcpyHostToDevice, ctx->stream));
-    rc = detect_fast_slot(ctx, params, 4, d_mask, cap, lay.at<float>(s.p, 1), lay.at<float>(s.p, 2), lay.at<int32_t>(s.p, 3));
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(keypoints, lay.at<void>(s.p, 1), nc * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (response) HIPCHK(ctx, hipMemcpyAsync(response, lay.at<void>(s.p, 2), nc * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 3), kDetectInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    Staged<4> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, mask, px))) return rc;
+    rc = detect_fast_slot(ctx, params, 4, mask ? s.at<uint8_t>(0) : nullptr, cap, s.at<float>(1), s.at<float>(2), s.at<int32_t>(3));
+    if (rc || (rc = s.out(1, keypoints, nc * 8)) || (rc = s.out(2, response, nc * 4)) || (rc = s.out(3, info, kDetectInfoWords * 4)))
+        return rc;
+    return s.finish();
 }
 
 int pagk_selftest_fast_cells(pagk_ctx *ctx, const pagk_fast_params *params, const pagk_image *img, float *raw_xy,
@@ -2708,6 +2708,52 @@ static int handover_fast_slot(pagk_ctx *ctx, const pagk_params *params, int32_t 
                                 d_state, d_info);
 }
 
+namespace {
+
+int handover_host(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                  double new_point_threshold, const uint8_t *status, const float *pt_predict, const float *pt_predict_un,
+                  int32_t cand_cap, const int32_t *n_cand, const float *cand_un, const pagk_detect_params *det,
+                  const pagk_fast_params *fast, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
+                  uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info)
+{
+    const bool given = !det && !fast;   // the caller's candidates: a count and a list go in, no info comes out
+    const size_t nc = (size_t)cap, cc = (size_t)(cand_cap > 0 ? cand_cap : 1), px = (size_t)width * height;
+    enum { STATUS, PREDICT, PREDICT_UN, N_CAND, CAND, KEYS, KEYS_UN, KEYS_NORMAL, INDEX, LIVE, STATE, INFO, MASK, PARTS };
+    const size_t sizes[PARTS] = {nc,     nc * 8, nc * 8, given ? 4 : 0u, given ? cc * 8 : 0u,     nc * 8,
+                                 nc * 8, nc * 8, nc * 4, nc,             kHandoverStateWords * 4, given ? 0u : kDetectInfoWords * 4,
+                                 px};
+    Staged<PARTS> s(ctx, sizes);
+    // (the form with the caller's candidates keeps its block in the context; the detecting forms take one per call)
+    int rc = s.open(given ? &ctx->buf[pagk_ctx::HANDIO] : nullptr, "the host-buffer hand-over's scratch");
+    if (rc) return rc;
+    const void *src[] = {status, pt_predict, pt_predict_un, n_cand, cand_cap > 0 ? cand_un : nullptr};
+    for (int k = STATUS; k <= CAND; k++)
+        if ((rc = s.in(k, src[k], sizes[k]))) return rc;
+    if ((rc = s.in(STATE, state, sizes[STATE]))) return rc;   // reach_flag persists
+    uint8_t *d_status = s.at<uint8_t>(STATUS), *d_live = s.at<uint8_t>(LIVE), *d_mask = s.at<uint8_t>(MASK);
+    float *d_predict = s.at<float>(PREDICT), *d_predict_un = s.at<float>(PREDICT_UN), *d_keys = s.at<float>(KEYS);
+    float *d_keys_un = s.at<float>(KEYS_UN), *d_keys_normal = keys_normal ? s.at<float>(KEYS_NORMAL) : nullptr;
+    int32_t *d_index = s.at<int32_t>(INDEX), *d_state = s.at<int32_t>(STATE), *d_info = s.at<int32_t>(INFO);
+    if (given)
+        rc = pagk_frame_handover_device(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict,
+                                        d_predict_un, cand_cap, s.at<int32_t>(N_CAND), s.at<float>(CAND), d_keys, d_keys_un,
+                                        d_keys_normal, d_index, d_live, d_mask, d_state);
+    else if (det)
+        rc = handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict, d_predict_un, 0,
+                             nullptr, nullptr, d_keys, d_keys_un, d_keys_normal, d_index, d_live, d_mask, d_state, det,
+                             &ctx->slots[4], d_info);
+    else
+        rc = handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict, d_predict_un,
+                                fast, 4, d_keys, d_keys_un, d_keys_normal, d_index, d_live, d_mask, d_state, d_info);
+    if (rc) return rc;
+    void *dst[] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
+    for (int k = KEYS; k <= MASK; k++)
+        if ((rc = s.out(k, dst[k - KEYS], sizes[k]))) return rc;
+    return s.finish();
+}
+
+}  // namespace
+
 int pagk_frame_handover_fast_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
                                     int32_t target_n, double new_point_threshold, const uint8_t *d_status,
                                     const float *d_pt_predict, const float *d_pt_predict_un, const pagk_fast_params *fast,
@@ -2735,28 +2781,8 @@ int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t w
         !index_in_last || !live || !state)
         return PAGK_E_ARG;
     if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
-    const size_t nc = (size_t)cap, px = (size_t)width * height;
-    // status | pt_predict | pt_predict_un | keys | keys_un | keys_normal | index | live | state | info | mask
-    const size_t sizes[11] = {nc, nc * 8, nc * 8, nc * 8, nc * 8, nc * 8, nc * 4, nc, kHandoverStateWords * 4,
-                              kDetectInfoWords * 4, px};
-    const Layout<11> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    void *b = s.p;
-    const void *src[3] = {status, pt_predict, pt_predict_un};
-    for (int k = 0; k < 3; k++) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src[k], sizes[k], hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, 8), state, sizes[8], hipMemcpyHostToDevice, ctx->stream));  // reach_flag persists
-    rc = handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, lay.at<uint8_t>(b, 0),
-                                         lay.at<float>(b, 1), lay.at<float>(b, 2), fast, 4, lay.at<float>(b, 3),
-                                         lay.at<float>(b, 4), keys_normal ? lay.at<float>(b, 5) : nullptr, lay.at<int32_t>(b, 6),
-                                         lay.at<uint8_t>(b, 7), lay.at<uint8_t>(b, 10), lay.at<int32_t>(b, 8), lay.at<int32_t>(b, 9));
-    if (rc) return rc;
-    void *dst[8] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
-    const int from[8] = {3, 4, 5, 6, 7, 8, 9, 10};
-    for (int k = 0; k < 8; k++)
-        if (dst[k]) HIPCHK(ctx, hipMemcpyAsync(dst[k], lay.at<void>(b, from[k]), sizes[from[k]], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, 0,
+                         nullptr, nullptr, nullptr, fast, keys, keys_un, keys_normal, index_in_last, live, mask, state, info);
 }
 
 // ---- ORB descriptors and matching (pagk_orb_kernel.h) ----------------------------------------------------------
@@ -2880,22 +2906,14 @@ int pagk_orb_describe(pagk_ctx *ctx, const pagk_orb_params *params, const pagk_i
     if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
     const size_t nc = (size_t)std::max(n, 1);
     const size_t sizes[5] = {nc * 8, 256, nc * 4, nc * 32, 256};   // keypoints | count | angle | descriptors | info
-    const Layout<5> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), keypoints, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), &n, 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = orb_describe_slot(ctx, params, 4, (int32_t)nc, lay.at<float>(s.p, 0), lay.at<int32_t>(s.p, 1), lay.at<float>(s.p, 2),
-                           lay.at<uint8_t>(s.p, 3), lay.at<int32_t>(s.p, 4));
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);   // (&n is read by the copy above)
+    Staged<5> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, keypoints, (size_t)n * 8)) || (rc = s.in(1, &n, 4))) return rc;
+    rc = orb_describe_slot(ctx, params, 4, (int32_t)nc, s.at<float>(0), s.at<int32_t>(1), s.at<float>(2), s.at<uint8_t>(3),
+                           s.at<int32_t>(4));
+    if (rc || (rc = s.out(2, angle, (size_t)n * 4)) || (rc = s.out(3, desc, (size_t)n * 32)) ||
+        (rc = s.out(4, info, kOrbInfoWords * 4)))
         return rc;
-    }
-    if (n && angle) HIPCHK(ctx, hipMemcpyAsync(angle, lay.at<void>(s.p, 2), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(desc, lay.at<void>(s.p, 3), (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 4), kOrbInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    return s.finish();
 }
 
 int pagk_orb_match_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t cap_q, const uint8_t *d_desc_q,
@@ -2943,27 +2961,16 @@ int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, con
     const int32_t counts[2] = {nq, nt};
     // query rows | train rows | counts | train_idx | distance | keep | info
     const size_t sizes[7] = {cq * 32, ct * 32, 256, cq * 4, cq * 4, cq, 256};
-    const Layout<7> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    if (nq) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), desc_q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
-    if (nt) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), desc_t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 2), counts, 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = pagk_orb_match_device(ctx, params, (int32_t)cq, lay.at<uint8_t>(s.p, 0), lay.at<int32_t>(s.p, 2), (int32_t)ct,
-                               lay.at<uint8_t>(s.p, 1), lay.at<int32_t>(s.p, 2) + 1, lay.at<int32_t>(s.p, 3),
-                               lay.at<int32_t>(s.p, 4), lay.at<uint8_t>(s.p, 5), lay.at<int32_t>(s.p, 6));
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);   // (counts is read by the copy above)
+    Staged<7> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, desc_q, (size_t)nq * 32)) || (rc = s.in(1, desc_t, (size_t)nt * 32)) ||
+        (rc = s.in(2, counts, 8)))
         return rc;
-    }
-    if (nq) {
-        HIPCHK(ctx, hipMemcpyAsync(train_idx, lay.at<void>(s.p, 3), (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(distance, lay.at<void>(s.p, 4), (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(keep, lay.at<void>(s.p, 5), (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 6), kOrbInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    rc = pagk_orb_match_device(ctx, params, (int32_t)cq, s.at<uint8_t>(0), s.at<int32_t>(2), (int32_t)ct, s.at<uint8_t>(1),
+                               s.at<int32_t>(2) + 1, s.at<int32_t>(3), s.at<int32_t>(4), s.at<uint8_t>(5), s.at<int32_t>(6));
+    if (rc || (rc = s.out(3, train_idx, (size_t)nq * 4)) || (rc = s.out(4, distance, (size_t)nq * 4)) ||
+        (rc = s.out(5, keep, (size_t)nq)) || (rc = s.out(6, info, kOrbInfoWords * 4)))
+        return rc;
+    return s.finish();
 }
 
 // ---- pyramidal Lucas-Kanade, tracker type 0 (pagk_lk_kernel.h) ---------------------------------------------------
@@ -3148,28 +3155,15 @@ int pagk_lk_track(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_image 
     const size_t nc = (size_t)std::max(n, 1);
     // points in | count | points out | status | raw status | err | flow | info
     const size_t sizes[8] = {nc * 8, 256, nc * 8, nc, nc, nc * 4, nc * 8, 256};
-    const Layout<8> lay(sizes);
-    Scratch s;
-    HIPCHK(ctx, hipMalloc(&s.p, lay.total));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 0), pt_ref, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(s.p, 1), &n, 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = lk_track_slots(ctx, params, 4, 5, (int32_t)nc, lay.at<float>(s.p, 0), lay.at<int32_t>(s.p, 1), lay.at<float>(s.p, 2),
-                        lay.at<uint8_t>(s.p, 3), lay.at<uint8_t>(s.p, 4), lay.at<float>(s.p, 5), lay.at<float>(s.p, 6),
-                        lay.at<int32_t>(s.p, 7));
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);   // (&n is read by the copy above)
+    const size_t nn = (size_t)n;
+    Staged<8> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, pt_ref, nn * 8)) || (rc = s.in(1, &n, 4))) return rc;
+    rc = lk_track_slots(ctx, params, 4, 5, (int32_t)nc, s.at<float>(0), s.at<int32_t>(1), s.at<float>(2), s.at<uint8_t>(3),
+                        s.at<uint8_t>(4), s.at<float>(5), s.at<float>(6), s.at<int32_t>(7));
+    if (rc || (rc = s.out(2, pt_out, nn * 8)) || (rc = s.out(3, status, nn)) || (rc = s.out(4, status_raw, nn)) ||
+        (rc = s.out(5, err, nn * 4)) || (rc = s.out(6, flow, nn * 8)) || (rc = s.out(7, info, kLkInfoWords * 4)))
         return rc;
-    }
-    if (n) {
-        HIPCHK(ctx, hipMemcpyAsync(pt_out, lay.at<void>(s.p, 2), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(status, lay.at<void>(s.p, 3), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        if (status_raw) HIPCHK(ctx, hipMemcpyAsync(status_raw, lay.at<void>(s.p, 4), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(err, lay.at<void>(s.p, 5), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (flow) HIPCHK(ctx, hipMemcpyAsync(flow, lay.at<void>(s.p, 6), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(s.p, 7), kLkInfoWords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    return s.finish();
 }
 
 int pagk_selftest_lk_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int64_t pitch)
@@ -3318,25 +3312,17 @@ int pagk_geometry_scores(pagk_ctx *ctx, const double *H21, const double *H12, co
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)(n < 1 ? 1 : n);
     const size_t sizes[5] = {nn * 8, nn * 8, nn, nn, 256};   // pts1 | pts2 | inliers_H | inliers_F | scores
-    const Layout<5> lay(sizes);
-    int rc = reserve(ctx, ctx->buf[pagk_ctx::SCORE], lay.total, GROW_FREELY, "the geometry scores' scratch");
-    if (rc) return rc;
-    void *b = ctx->buf[pagk_ctx::SCORE].ptr;
-    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1), *d_s = lay.at<float>(b, 4);
-    uint8_t *d_h = lay.at<uint8_t>(b, 2), *d_f = lay.at<uint8_t>(b, 3);
-    if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(d_p1, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = pagk_geometry_scores_device(ctx, H21, H12, F21, n, d_p1, d_p2, sigma, d_h, d_f, d_s);
-    if (rc) return rc;
     float sc[2];
-    if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(inliers_H, d_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(inliers_F, d_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(sc, d_s, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    Staged<5> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(&ctx->buf[pagk_ctx::SCORE], "the geometry scores' scratch")) || (rc = s.in(0, pts1, (size_t)n * 8)) ||
+        (rc = s.in(1, pts2, (size_t)n * 8)))
+        return rc;
+    rc = pagk_geometry_scores_device(ctx, H21, H12, F21, n, s.at<float>(0), s.at<float>(1), sigma, s.at<uint8_t>(2),
+                                     s.at<uint8_t>(3), s.at<float>(4));
+    if (rc || (rc = s.out(2, inliers_H, (size_t)n)) || (rc = s.out(3, inliers_F, (size_t)n)) || (rc = s.out(4, sc, 8)) ||
+        (rc = s.finish()))
+        return rc;
     *score_H = sc[0];
     *score_F = sc[1];
     return PAGK_OK;
@@ -3500,29 +3486,18 @@ int pagk_geometry_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, c
     const size_t nn = (size_t)(n < 1 ? 1 : n), hh = (size_t)params->iters_H + (size_t)params->iters_F;
     // pts1 | pts2 | status | mask_H | mask_F | hyp_counts | models | info
     const size_t sizes[8] = {nn * 8, nn * 8, nn, nn, nn, hh * 4, 256, 256};
-    const Layout<8> lay(sizes);
-    int rc = reserve(ctx, ctx->buf[pagk_ctx::FITIO], lay.total, GROW_FREELY, "the host-buffer fit's scratch");
-    if (rc) return rc;
-    void *b = ctx->buf[pagk_ctx::FITIO].ptr;
-    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1);
-    uint8_t *d_st = lay.at<uint8_t>(b, 2), *d_h = lay.at<uint8_t>(b, 3), *d_f = lay.at<uint8_t>(b, 4);
-    int32_t *d_c = lay.at<int32_t>(b, 5), *d_i = lay.at<int32_t>(b, 7);
-    double *d_m = lay.at<double>(b, 6);
-    if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(d_p1, pts1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_p2, pts2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        if (status) HIPCHK(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    }
+    Staged<8> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(&ctx->buf[pagk_ctx::FITIO], "the host-buffer fit's scratch")) || (rc = s.in(0, pts1, (size_t)n * 8)) ||
+        (rc = s.in(1, pts2, (size_t)n * 8)) || (rc = s.in(2, status, (size_t)n)))
+        return rc;
     FitWs w;
-    rc = fit_launch(ctx, params, n, d_p1, d_p2, status ? d_st : nullptr, d_m, d_h, d_f, d_i, d_c, &w);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(models, d_m, 27 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(info, d_i, PAGK_FIT_INFO_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0 && mask_H) HIPCHK(ctx, hipMemcpyAsync(mask_H, d_h, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0 && mask_F) HIPCHK(ctx, hipMemcpyAsync(mask_F, d_f, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (hyp_counts) HIPCHK(ctx, hipMemcpyAsync(hyp_counts, d_c, hh * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    rc = fit_launch(ctx, params, n, s.at<float>(0), s.at<float>(1), status ? s.at<uint8_t>(2) : nullptr, s.at<double>(6),
+                    s.at<uint8_t>(3), s.at<uint8_t>(4), s.at<int32_t>(7), s.at<int32_t>(5), &w);
+    if (rc || (rc = s.out(6, models, 27 * sizeof(double))) || (rc = s.out(7, info, PAGK_FIT_INFO_WORDS * sizeof(int32_t))) ||
+        (rc = s.out(3, mask_H, (size_t)n)) || (rc = s.out(4, mask_F, (size_t)n)) || (rc = s.out(5, hyp_counts, hh * 4)))
+        return rc;
+    return s.finish();
 }
 
 int pagk_geometry_validation_device(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *d_pt_ref_un,
@@ -3554,28 +3529,18 @@ int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, i
     if (track_score) *track_score = 0;  // :447
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)(n < 1 ? 1 : n);
-    const size_t sizes[4] = {nn * 8, nn * 8, nn, 256};   // pt_ref_un | pt_predict_un | status | count, score
-    const Layout<4> lay(sizes);
-    int rc = reserve(ctx, ctx->buf[pagk_ctx::FITIO], lay.total, GROW_FREELY, "the host-buffer fit's scratch");
-    if (rc) return rc;
-    void *b = ctx->buf[pagk_ctx::FITIO].ptr;
-    float *d_p1 = lay.at<float>(b, 0), *d_p2 = lay.at<float>(b, 1);
-    uint8_t *d_st = lay.at<uint8_t>(b, 2);
-    if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(d_p1, pt_ref_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_p2, pt_predict_un, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_st, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int32_t *d_cnt = lay.at<int32_t>(b, 3);
-    float *d_score = reinterpret_cast<float *>(d_cnt + 2);
-    rc = pagk_geometry_validation_device(ctx, params, n, d_p1, d_p2, d_st, sigma, d_cnt, d_score);
-    if (rc) return rc;
+    const size_t sizes[5] = {nn * 8, nn * 8, nn, 256, 256};   // pt_ref_un | pt_predict_un | status | count | score
     int32_t cnt = 0;
     float sc = 0;
-    if (n > 0) HIPCHK(ctx, hipMemcpyAsync(status, d_st, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&sc, d_score, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    Staged<5> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(&ctx->buf[pagk_ctx::FITIO], "the host-buffer fit's scratch")) || (rc = s.in(0, pt_ref_un, (size_t)n * 8)) ||
+        (rc = s.in(1, pt_predict_un, (size_t)n * 8)) || (rc = s.in(2, status, (size_t)n)))
+        return rc;
+    rc = pagk_geometry_validation_device(ctx, params, n, s.at<float>(0), s.at<float>(1), s.at<uint8_t>(2), sigma,
+                                         s.at<int32_t>(3), s.at<float>(4));
+    if (rc || (rc = s.out(2, status, (size_t)n)) || (rc = s.out(3, &cnt, 4)) || (rc = s.out(4, &sc, 4)) || (rc = s.finish()))
+        return rc;
     if (track_score) *track_score = sc;
     return cnt;
 }
@@ -3660,37 +3625,23 @@ static int neighbors_host(pagk_ctx *ctx, const pagk_image *ref, const pagk_image
     if ((rc = check_image(ref)) || (rc = check_image(cur))) return rc;
     if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
     const size_t nn = (size_t)(n < 1 ? 1 : n), mm = (size_t)(m < 1 ? 1 : m), cc = (size_t)cap;
-    const size_t sizes[11] = {nn * 8, nn * 8, nn, nn * 16, mm * 8, mm * 8, nn * 4, nn * cc * 4, nn * cc * 4, nn * cc * 4, 0};
-    const Layout<11> lay(sizes);
-    if ((rc = reserve(ctx, ctx->buf[pagk_ctx::SCORE], lay.total, GROW_FREELY, "the neighbour search's scratch"))) return rc;
-    void *b = ctx->buf[pagk_ctx::SCORE].ptr;
-    auto up = [&](int k, const void *src, size_t bytes) -> int {
-        if (src && bytes) HIPCHK(ctx, hipMemcpyAsync(lay.at<void>(b, k), src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return PAGK_OK;
-    };
-    if (n > 0) {
-        if ((rc = up(0, keys_ref, (size_t)n * 8)) || (rc = up(1, pt_predict_un, (size_t)n * 8)) ||
-            (rc = up(2, status, (size_t)n)) || (rc = up(3, affine, (size_t)n * 16)) || (rc = up(6, count, (size_t)n * 4)))
-            return rc;
-    }
-    if (m > 0 && ((rc = up(4, keys_cur, (size_t)m * 8)) || (rc = up(5, keys_cur_un, (size_t)m * 8)))) return rc;
-    // the lists of skipped features (status 0, or already filled at a smaller radius) keep the caller's content
-    if (!pairs && n > 0 && ((rc = up(7, nbr_idx, (size_t)n * cc * 4)) || (rc = up(8, nbr_dist, (size_t)n * cc * 4)) ||
-                            (rc = up(9, nbr_ncc, (size_t)n * cc * 4))))
+    // keys_ref | pt_predict_un | status | affine | keys_cur | keys_cur_un | count | nbr_idx | nbr_dist | nbr_ncc
+    const size_t sizes[10] = {nn * 8, nn * 8, nn, nn * 16, mm * 8, mm * 8, nn * 4, nn * cc * 4, nn * cc * 4, nn * cc * 4};
+    const size_t fn = (size_t)n, fm = (size_t)m, list = fn * cc * 4;   // what is copied: the features, not the padded parts
+    Staged<10> s(ctx, sizes);
+    if ((rc = s.open(&ctx->buf[pagk_ctx::SCORE], "the neighbour search's scratch")) || (rc = s.in(0, keys_ref, fn * 8)) ||
+        (rc = s.in(1, pt_predict_un, fn * 8)) || (rc = s.in(2, status, fn)) || (rc = s.in(3, affine, fn * 16)) ||
+        (rc = s.in(6, count, fn * 4)) || (rc = s.in(4, keys_cur, fm * 8)) || (rc = s.in(5, keys_cur_un, fm * 8)))
         return rc;
-    rc = near_neighbors_launch(ctx, ctx->slots[4], ctx->slots[5], half_patch, n, lay.at<float>(b, 0), lay.at<float>(b, 1),
-                               lay.at<uint8_t>(b, 2), affine ? lay.at<float>(b, 3) : nullptr, m, lay.at<float>(b, 4),
-                               lay.at<float>(b, 5), level, radius_unit, use_ncc, pairs, cap, lay.at<int32_t>(b, 6),
-                               lay.at<int32_t>(b, 7), lay.at<float>(b, 8), lay.at<float>(b, 9));
-    if (rc) return rc;
-    if (n > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(count, lay.at<void>(b, 6), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (nbr_idx) HIPCHK(ctx, hipMemcpyAsync(nbr_idx, lay.at<void>(b, 7), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (nbr_dist) HIPCHK(ctx, hipMemcpyAsync(nbr_dist, lay.at<void>(b, 8), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(nbr_ncc, lay.at<void>(b, 9), (size_t)n * cc * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    // the lists of skipped features (status 0, or already filled at a smaller radius) keep the caller's content
+    if (!pairs && ((rc = s.in(7, nbr_idx, list)) || (rc = s.in(8, nbr_dist, list)) || (rc = s.in(9, nbr_ncc, list)))) return rc;
+    rc = near_neighbors_launch(ctx, ctx->slots[4], ctx->slots[5], half_patch, n, s.at<float>(0), s.at<float>(1), s.at<uint8_t>(2),
+                               affine ? s.at<float>(3) : nullptr, m, s.at<float>(4), s.at<float>(5), level, radius_unit, use_ncc,
+                               pairs, cap, s.at<int32_t>(6), s.at<int32_t>(7), s.at<float>(8), s.at<float>(9));
+    if (rc || (rc = s.out(6, count, fn * 4)) || (rc = s.out(7, nbr_idx, list)) || (rc = s.out(8, nbr_dist, list)) ||
+        (rc = s.out(9, nbr_ncc, list)))
+        return rc;
+    return s.finish();
 }
 
 int pagk_find_near_neighbors(pagk_ctx *ctx, const pagk_image *ref, const pagk_image *cur, int32_t half_patch, int32_t n,
@@ -3744,21 +3695,17 @@ int pagk_selftest_divide(pagk_ctx *ctx, int32_t n, const double *num, const doub
     if (n == 0) return PAGK_OK;
     if (!num || !den || !q_plain || !q_prepared || !root || !root_lean) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    Scratch s;
     const size_t nb = (size_t)n * sizeof(double);
-    HIPCHK(ctx, hipMalloc(&s.p, 6 * nb));
-    double *d = static_cast<double *>(s.p);
-    HIPCHK(ctx, hipMemcpyAsync(d, num, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d + n, den, nb, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_selftest_divide, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d, d + n, d + 2 * (size_t)n,
-                       d + 3 * (size_t)n, d + 4 * (size_t)n, d + 5 * (size_t)n);
+    const size_t sizes[6] = {nb, nb, nb, nb, nb, nb};   // num | den | q_plain | q_prepared | root | root_lean
+    Staged<6> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, num, nb)) || (rc = s.in(1, den, nb))) return rc;
+    hipLaunchKernelGGL(k_selftest_divide, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, s.at<double>(0), s.at<double>(1),
+                       s.at<double>(2), s.at<double>(3), s.at<double>(4), s.at<double>(5));
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(q_plain, d + 2 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(q_prepared, d + 3 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(root, d + 4 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(root_lean, d + 5 * (size_t)n, nb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    if ((rc = s.out(2, q_plain, nb)) || (rc = s.out(3, q_prepared, nb)) || (rc = s.out(4, root, nb)) || (rc = s.out(5, root_lean, nb)))
+        return rc;
+    return s.finish();
 }
 
 int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32_t m, int32_t first, int32_t count,
@@ -3769,15 +3716,15 @@ int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32
     NOT_WHILE_CAPTURING(ctx, "pagk_selftest_fit_samples");
     if (count == 0) return PAGK_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    Scratch s;
-    const size_t bytes = (size_t)count * (model ? 8 : 4) * sizeof(int32_t);
-    HIPCHK(ctx, hipMalloc(&s.p, bytes));
+    const size_t sizes[1] = {(size_t)count * (model ? 8 : 4) * sizeof(int32_t)};
+    Staged<1> s(ctx, sizes);
+    int rc = s.open(nullptr, nullptr);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_fit_samples, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, (unsigned long long)seed, model,
-                       m, first, count, static_cast<int32_t *>(s.p));
+                       m, first, count, s.at<int32_t>(0));
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(idx, s.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    if ((rc = s.out(0, idx, sizes[0]))) return rc;
+    return s.finish();
 }
 
 int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t count, double *closed, double *loop)
@@ -3787,18 +3734,16 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
     if (n == 0) return PAGK_OK;
     if (!c || !closed || !loop) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    Scratch s;
     const size_t nn = (size_t)n;
-    HIPCHK(ctx, hipMalloc(&s.p, nn * (2 * sizeof(double) + sizeof(float))));
-    double *d_closed = static_cast<double *>(s.p), *d_loop = d_closed + nn;
-    float *d_c = reinterpret_cast<float *>(d_loop + nn);
-    HIPCHK(ctx, hipMemcpyAsync(d_c, c, nn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_selftest_repeat_sum, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_c, count, d_closed, d_loop);
+    const size_t sizes[3] = {nn * sizeof(double), nn * sizeof(double), nn * sizeof(float)};   // closed | loop | c
+    Staged<3> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(2, c, sizes[2]))) return rc;
+    hipLaunchKernelGGL(k_selftest_repeat_sum, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, s.at<float>(2), count,
+                       s.at<double>(0), s.at<double>(1));
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(closed, d_closed, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(loop, d_loop, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    if ((rc = s.out(0, closed, sizes[0])) || (rc = s.out(1, loop, sizes[1]))) return rc;
+    return s.finish();
 }
 
 int pagk_selftest_solve(pagk_ctx *ctx, int32_t n, const double *H, const double *b, uint32_t solver_variant,
@@ -3810,22 +3755,18 @@ int pagk_selftest_solve(pagk_ctx *ctx, int32_t n, const double *H, const double 
     if (n == 0) return PAGK_OK;
     if (!H || !b || !x_serial || !norm_serial || !x_lanes || !nsq_lanes) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    Scratch s;
-    const size_t nn = (size_t)n;
-    HIPCHK(ctx, hipMalloc(&s.p, (16 + 4 + 4 + 1 + 4 + 1) * nn * sizeof(double)));
-    double *dH = static_cast<double *>(s.p), *db = dH + 16 * nn, *dxs = db + 4 * nn, *dns = dxs + 4 * nn,
-           *dxl = dns + nn, *dnl = dxl + 4 * nn;
-    HIPCHK(ctx, hipMemcpyAsync(dH, H, 16 * nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(db, b, 4 * nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_selftest_solve, dim3((n + 15) / 16), dim3(64), 0, ctx->stream, n, dH, db, solver_variant, dxs, dns,
-                       dxl, dnl);
+    const size_t nb = (size_t)n * sizeof(double);
+    const size_t sizes[6] = {16 * nb, 4 * nb, 4 * nb, nb, 4 * nb, nb};   // H | b | x_serial | norm_serial | x_lanes | nsq_lanes
+    Staged<6> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, H, sizes[0])) || (rc = s.in(1, b, sizes[1]))) return rc;
+    hipLaunchKernelGGL(k_selftest_solve, dim3((n + 15) / 16), dim3(64), 0, ctx->stream, n, s.at<double>(0), s.at<double>(1),
+                       solver_variant, s.at<double>(2), s.at<double>(3), s.at<double>(4), s.at<double>(5));
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(x_serial, dxs, 4 * nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(norm_serial, dns, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(x_lanes, dxl, 4 * nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(nsq_lanes, dnl, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    if ((rc = s.out(2, x_serial, sizes[2])) || (rc = s.out(3, norm_serial, sizes[3])) || (rc = s.out(4, x_lanes, sizes[4])) ||
+        (rc = s.out(5, nsq_lanes, sizes[5])))
+        return rc;
+    return s.finish();
 }
 
 // The sampler of pagk_device.h on level `level` of a built slot.  A clamp-free sample reads the quad at (int(y), int(x)) with
@@ -3850,11 +3791,12 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
         }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    Scratch sc;
     const size_t nn = (size_t)n, per = five ? 5 : 1;
-    HIPCHK(ctx, hipMalloc(&sc.p, nn * (2 + per) * sizeof(float)));
-    float *d_xy = static_cast<float *>(sc.p), *d_out = d_xy + 2 * nn;
-    HIPCHK(ctx, hipMemcpyAsync(d_xy, xy, 2 * nn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const size_t sizes[2] = {2 * nn * sizeof(float), nn * per * sizeof(float)};   // xy | out
+    Staged<2> st(ctx, sizes);
+    int rc;
+    if ((rc = st.open(nullptr, nullptr)) || (rc = st.in(0, xy, sizes[0]))) return rc;
+    float *d_xy = st.at<float>(0), *d_out = st.at<float>(1);
     const dim3 grd((n + 255) / 256), blk(256);
     switch (mode) {
     case 0: hipLaunchKernelGGL((k_selftest_sample<true, false>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
@@ -3863,9 +3805,8 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
     default: hipLaunchKernelGGL((k_selftest_sample<false, true>), grd, blk, 0, ctx->stream, lv, n, d_xy, d_out); break;
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out, nn * per * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return PAGK_OK;
+    if ((rc = st.out(1, out, sizes[1]))) return rc;
+    return st.finish();
 }
 
 // GyroAidedTracker::MatchFeatures, src/gyro_aided_tracker.cpp:949-1008.  Host-side: a sequential pass whose
