@@ -322,8 +322,30 @@ struct Five {
 // The same in two halves, so that a kernel can put other work (or a phase stamp) between the gathers and
 // their first use: sample5_issue computes the six coordinates and issues the five tap loads, sample5_finish
 // interpolates.
+//
+// The minus side of the clamp-free form is not prepared at all.  For a float32 1 <= X < 2^24 (every image is narrower:
+// cols, rows < 2^24 is checked at upload) the difference X - 1.0f is exact: X and 1 are multiples of ulp(X), so is
+// their difference, and it is no larger than X -- it lies on X's grid or a finer one and needs no rounding.  An exact
+// X - 1 has the integer part int(X) - 1 and the fraction of X, hence the same weight 1 - xx: the tap of (X - 1, Y) is
+// the quad one to the left of the centre's, idx_c - 1, with the centre's x fraction, and the tap of (X, Y - 1) is the
+// quad one row up, idx_c - cols, with the centre's y fraction.  (tests/test_sampler_minus_cpu.py sweeps every float32
+// in [1, 2048) and the floats below each binade top up to 8192: no exception.)
+// The PLUS side keeps its own add, truncation and fract: X + 1.0f ROUNDS where it crosses the top of a binade (the
+// result's grid is twice as coarse: odd last mantissa bits are ties), so fract(X + 1) != fract(X) there, and just
+// below 2^k the sum rounds up to 2^k + 1 or further: int(X + 1) can be int(X) + 2.  The same test asserts that this
+// set is not empty.
+// Domain: X >= 1 and Y >= 1.  Every caller of sample5_issue<false> selects it by the same `interior` test,
+// bx - ext >= 0 with ext = fl(fl(fl(|A00| h) + fl(|A01| h)) + 2) and X = fl(bx + wx), wx = fl(fl(A00 x) + fl(A01 y)),
+// |x|, |y| <= h.  Rounding is monotone, so |wx| <= E = fl(fl(|A00| h) + fl(|A01| h)) and X >= fl(bx - E); the test
+// gives bx >= fl(E + 2) >= E + 2 - ulp(E + 2) / 2, and E + 2 < 2^24 (bx + ext < cols - 1 < 2^24), so
+// bx - E >= 1.5 and X >= fl(1.5) > 1.  (The test was written for fl(X - 1) >= 0, which is the same statement.)  Every
+// fl() above is one rounding of one operation: the library is built with -ffp-contract=off, so neither ext nor wx is
+// contracted into an fma, whose single rounding the bound on |wx| does not cover.
+// pagk_selftest_sample refuses a clamp-free call outside [1, cols - 2) x [1, rows - 2).
+// The clamped form prepares all six coordinates: its clamp acts on X - 1 itself.
 #ifdef PAGK_PK_BILERP
-// five tap loads in flight and the six fractions; the (1 - xx, xx) pairs are formed at use
+// five tap loads in flight and the six fractions; the (1 - xx, xx) pairs are formed at use.  In the clamp-free form
+// fxm, fym are fx, fy themselves: no register of their own, and sample5_finish forms four weight pairs, not six
 struct FiveTaps {
     Taps q0, q1, q2, q3, q4;
     float fx, fxp, fxm, fy, fyp, fym;
@@ -333,20 +355,32 @@ __device__ __forceinline__ FiveTaps sample5_issue(const DevLevel &L, float X, fl
 {
     const CoordPk cx = prep_coord_pk<CLAMP>(X, L.fcols, L.fcols_m1);
     const CoordPk cxp = prep_coord_pk<CLAMP>(X + 1.0f, L.fcols, L.fcols_m1);
-    const CoordPk cxm = prep_coord_pk<CLAMP>(X - 1.0f, L.fcols, L.fcols_m1);
     const CoordPk cy = prep_coord_pk<CLAMP>(Y, L.frows, L.frows_m1);
     const CoordPk cyp = prep_coord_pk<CLAMP>(Y + 1.0f, L.frows, L.frows_m1);
-    const CoordPk cym = prep_coord_pk<CLAMP>(Y - 1.0f, L.frows, L.frows_m1);
     // row offsets: both factors are < 2^24 (checked at upload), full-rate 24-bit multiply-add
-    const int rc = __mul24(cy.i, L.cols), rp = __mul24(cyp.i, L.cols), rm = __mul24(cym.i, L.cols);
-    const TapSrc ts = tap_src(L);
+    const int rc = __mul24(cy.i, L.cols), rp = __mul24(cyp.i, L.cols);
+    const int ic = rc + cx.i;
+    int im, iu;  // the quads of (X - 1, Y) and (X, Y - 1)
     FiveTaps t;
-    t.q0 = load_taps(ts, rc + cx.i);
+    if constexpr (CLAMP) {
+        const CoordPk cxm = prep_coord_pk<true>(X - 1.0f, L.fcols, L.fcols_m1);
+        const CoordPk cym = prep_coord_pk<true>(Y - 1.0f, L.frows, L.frows_m1);
+        im = rc + cxm.i;
+        iu = __mul24(cym.i, L.cols) + cx.i;
+        t.fxm = cxm.w.y, t.fym = cym.w.y;
+    } else {
+        // X, Y >= 1: the centre's left and upper neighbours, with the centre's fractions (above)
+        im = ic - 1;
+        iu = ic - L.cols;
+        t.fxm = cx.w.y, t.fym = cy.w.y;
+    }
+    const TapSrc ts = tap_src(L);
+    t.q0 = load_taps(ts, ic);
     t.q1 = load_taps(ts, rc + cxp.i);
-    t.q2 = load_taps(ts, rc + cxm.i);
+    t.q2 = load_taps(ts, im);
     t.q3 = load_taps(ts, rp + cx.i);
-    t.q4 = load_taps(ts, rm + cx.i);
-    t.fx = cx.w.y, t.fxp = cxp.w.y, t.fxm = cxm.w.y, t.fy = cy.w.y, t.fyp = cyp.w.y, t.fym = cym.w.y;
+    t.q4 = load_taps(ts, iu);
+    t.fx = cx.w.y, t.fxp = cxp.w.y, t.fy = cy.w.y, t.fyp = cyp.w.y;
     return t;
 }
 __device__ __forceinline__ pagk_f32x2 weights_pk(float f)
@@ -380,20 +414,32 @@ __device__ __forceinline__ FiveTaps sample5_issue(const DevLevel &L, float X, fl
 {
     const Coord cx = prep_coord<CLAMP>(X, L.fcols, L.fcols_m1);
     const Coord cxp = prep_coord<CLAMP>(X + 1.0f, L.fcols, L.fcols_m1);
-    const Coord cxm = prep_coord<CLAMP>(X - 1.0f, L.fcols, L.fcols_m1);
     const Coord cy = prep_coord<CLAMP>(Y, L.frows, L.frows_m1);
     const Coord cyp = prep_coord<CLAMP>(Y + 1.0f, L.frows, L.frows_m1);
-    const Coord cym = prep_coord<CLAMP>(Y - 1.0f, L.frows, L.frows_m1);
-    const int rc = __mul24(cy.i, L.cols), rp = __mul24(cyp.i, L.cols), rm = __mul24(cym.i, L.cols);
-    const uint32_t *q = L.quad;
+    const int rc = __mul24(cy.i, L.cols), rp = __mul24(cyp.i, L.cols);
+    const int ic = rc + cx.i;
+    int im, iu;  // the quads of (X - 1, Y) and (X, Y - 1)
     FiveTaps t;
+    if constexpr (CLAMP) {
+        const Coord cxm = prep_coord<true>(X - 1.0f, L.fcols, L.fcols_m1);
+        const Coord cym = prep_coord<true>(Y - 1.0f, L.frows, L.frows_m1);
+        im = rc + cxm.i;
+        iu = __mul24(cym.i, L.cols) + cx.i;
+        t.fxm = cxm.f, t.fym = cym.f;
+    } else {
+        // X, Y >= 1: the centre's left and upper neighbours, with the centre's fractions (above)
+        im = ic - 1;
+        iu = ic - L.cols;
+        t.fxm = cx.f, t.fym = cy.f;
+    }
+    const uint32_t *q = L.quad;
     // unsigned 32-bit element offsets: SGPR base + VGPR offset addressing, no 64-bit pointer math
-    t.q0 = q[(uint32_t)(rc + cx.i)];
+    t.q0 = q[(uint32_t)ic];
     t.q1 = q[(uint32_t)(rc + cxp.i)];
-    t.q2 = q[(uint32_t)(rc + cxm.i)];
+    t.q2 = q[(uint32_t)im];
     t.q3 = q[(uint32_t)(rp + cx.i)];
-    t.q4 = q[(uint32_t)(rm + cx.i)];
-    t.fx = cx.f, t.fxp = cxp.f, t.fxm = cxm.f, t.fy = cy.f, t.fyp = cyp.f, t.fym = cym.f;
+    t.q4 = q[(uint32_t)iu];
+    t.fx = cx.f, t.fxp = cxp.f, t.fy = cy.f, t.fyp = cyp.f;
     return t;
 }
 __device__ __forceinline__ Five sample5_finish(const FiveTaps &t)
