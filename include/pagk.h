@@ -881,7 +881,8 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
  * pagk_frame_handover_detect_device, pagk_detect_fast_device,
  * pagk_frame_handover_fast_device, pagk_frame_rectify_device, pagk_orb_describe_device, pagk_orb_match_device,
- * pagk_lk_pyramid_device, pagk_lk_track_device; and the
+ * pagk_lk_pyramid_device, pagk_lk_track_device, pagk_match_features_device, pagk_search_gyro_predict_device,
+ * pagk_search_klt_device; and the
  * pinned-memory forms pagk_frame_upload_pinned,
  * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,
  * pagk_graph_launch replays them with one hipGraphLaunch.  Rules: run the same calls once before capturing
@@ -1042,11 +1043,131 @@ int pagk_ncc_free(pagk_ctx *ctx, const pagk_image *ref, const pagk_image *cur, i
                   const float *pt_ref, const float *pt_cur, const float *affine, float *ncc);
 /* GyroAidedTracker::MatchFeatures (src/gyro_aided_tracker.cpp:949-1008) on the lists above: thresholds
  * TH_NCC_HIGH 0.6, TH_NCC_LOW 0.3, TH_RATIO 0.75 (:7-9), one match per current keypoint -- a keypoint claimed
- * twice loses every match and stays banned (:991-1005).  Host-side (sequential by nature).  match_*: capacity n
+ * twice loses every match and stays banned (:991-1005).  Host-side, written as the reference's sequential pass; the result
+ * is a count and a stable compaction, which pagk_match_features_device computes on the device.  match_*: capacity n
  * (match_dist / match_ncc may be NULL).  Returns mvMatches.size() or a negative error. */
 int pagk_match_features(int32_t n, int32_t cap, const int32_t *count, const int32_t *nbr_idx, const float *nbr_dist,
                         const float *nbr_ncc, int32_t use_ncc, int32_t *match_query, int32_t *match_train,
                         float *match_dist, float *match_ncc);
+
+/* ---- Track-to-detection association: which detected keypoint a tracked point belongs to -------------------------------- */
+/* The two public methods of GyroAidedTracker that tie a tracked point to a keypoint detected independently in the current
+ * frame: SearchByGyroPredict (src/gyro_aided_tracker.cpp:859-939) and SearchByOpencvKLT (:1017-1136), behind a finished
+ * prediction / PatchMatch and behind pyramidal Lucas-Kanade.  Everything runs on the device, the "fewer than 100 matches"
+ * retry (:921) and both filters included; nothing is read on the host.  The contract is this definition, bit for bit,
+ * restated sequentially in plain C in tests/associate_ref.c (the std::set and erase loop of :949-1008 and the iterator loop
+ * of :1111-1129, literally).  f32 arithmetic has one rounding per operation, no contraction.
+ *
+ * MatchFeatures (:949-1008) on the lists of the section above, n features, m current keypoints, lists of capacity cap:
+ *   choice     feature i with c = count[i], its two best entries (ncc0, ncc1), (dist0, dist1) and t = nbr_idx[i][0] (:955-990):
+ *              c <= 0: none.  use_ncc: ncc0 > th_ncc_high takes t; otherwise, with c > 1: ncc0 < th_ncc_low: none;
+ *              ncc1 < ncc0 * th_ratio takes t; otherwise none.  Distance mode: c == 1 takes t; c > 1: dist0 < dist1 * th_ratio
+ *              takes t.  The comparisons are written as pagk_match_features writes them (NaN falls the same way).
+ *   own rules  the treatment of over-long lists and bad indices is the library's own: c > cap: none, counted in info[1]
+ *              (pagk_match_features returns PAGK_E_CAPACITY instead); a taken t outside [0, m): none, counted in info[2]
+ *              (the reference has no such index).
+ *   uniqueness a current keypoint enters sFoundInCurPts at its first claim, every later claim erases all matches to it, and
+ *              it is never admitted again (:993-1007).  So feature i keeps its choice t if and only if exactly one feature
+ *              chose t, and the matches stand in increasing i: a count and a stable compaction, no sequential pass.
+ *   outputs    match_query, match_train, match_dist (= dist0), match_ncc (= ncc0) in match order, the count in *d_n_matches;
+ *              rows at or beyond the count: -1, -1, 0, 0.  With the default thresholds equal to pagk_match_features byte for
+ *              byte whenever no list exceeds cap.
+ *   flow error (:928-933) flows_err[i] = keys_cur_un[t] - pt_predict_un[i] (f32) for a kept feature, (0, 0) for every other.
+ *   info       PAGK_ASSOC_INFO_WORDS int32: [0] features with a choice, [1] lists longer than cap, [2] train indices out of
+ *              range, [3] current keypoints claimed more than once, [4] matches, [5] 1 if the level-2 search ran, the rest 0.
+ *
+ * SearchByOpencvKLT (:1017-1136) behind Lucas-Kanade (the section "Pyramidal Lucas-Kanade"), cap rows, m detected keypoints.
+ * Parity with OpenCV's BFMatcher is NOT claimed; where a rule is the library's own it says so:
+ *   queries    row i is live iff i < n (the device count clamped to [0, cap]) and status[i] != 0 after the err filter
+ *              (:1047-1057); its query point q is Lucas-Kanade's pt_out[i].
+ *   neighbours radiusMatch (:1067): the detected keypoints j < m (the device count clamped to [0, m]) in index order,
+ *              d = sqrtf(dx*dx + dy*dy) with dx = q.x - t.x, dy = q.y - t.y, f32, left to right, correctly rounded sqrtf;
+ *              j is a neighbour iff d <= klt_max_distance (`<=` at the radius: the library's own rule; NaN is no neighbour).
+ *              The best and the second best are kept, replacement under strict `<`: equal distances keep the lower index in
+ *              front (tie order of equal distances: the library's own rule, std::sort in OpenCV is unstable there).
+ *   choice     (:1076-1087) exactly one neighbour: it.  Two or more: (double)(d0 / d1) < klt_ratio takes the best, an f32
+ *              division then widened (:1080); 0 / 0 is NaN and rejects.  None: no choice.
+ *   uniqueness (:1089-1105) first come: of the queries that chose t the lowest index keeps it, the others are dropped.
+ *   disparity  (:1096-1102) disp = (double)sqrtf((rx-cx)*(rx-cx) + (ry-cy)*(ry-cy)), r = keys_ref[i], c = keys_cur[t]: the
+ *              detected keypoint, not the tracked point; std::sqrt of a float is the f32 overload.
+ *   filter     (:1108-1130) sum1 = the f64 sum of disp in match order, one rounding per add; avg1 = sum1 / (double)k (k == 0:
+ *              NaN, nothing is dropped); th = avg1 * klt_disparity_factor; matches with disp > th are dropped, the order of
+ *              the others stays.
+ *   outputs    match_query, match_train, match_dist (= d0), disparity (f64) in match order, the count; rows at or beyond
+ *              the count: -1, -1, 0, 0.  stats, PAGK_ASSOC_STATS_WORDS doubles: [0] avg1, [1] avg2 (:1130), [2], [3] the
+ *              largest disparity before and after the filter (from 0; NaN never replaces), [4] th, [5] sum1, [6] sum2, [7] 0.
+ *   info       PAGK_ASSOC_INFO_WORDS int32: [0] live queries, [1] / [2] / [3] queries with 0 / 1 / 2 or more neighbours,
+ *              [4] ratio rejects, [5] lost to an earlier claimer, [6] dropped by the disparity filter, [7] matches.
+ * Workspaces belong to the context: run a call once with its sizes outside a capture first.  The results do not depend on
+ * the order in which workgroups run (the only atomics are integer adds and minima). */
+typedef struct pagk_assoc_params {
+    float th_ncc_high;            /* TH_NCC_HIGH 0.6 (:7) */
+    float th_ncc_low;             /* TH_NCC_LOW 0.3 (:8) */
+    float th_ratio;               /* TH_RATIO 0.75 (:9) */
+    int32_t use_ncc;              /* mbNCC: 1 (:60) */
+    int32_t min_matches;          /* 100 (:921): fewer matches than this and the search is repeated at twice the radius */
+    float klt_max_distance;       /* maxDistance 4 (:1066) */
+    double klt_ratio;             /* 0.7 (:1081) */
+    double klt_disparity_factor;  /* filterOutFactor 1.5 (:1115) */
+} pagk_assoc_params;
+#define PAGK_ASSOC_INFO_WORDS 8
+#define PAGK_ASSOC_STATS_WORDS 8
+/* 0.6, 0.3, 0.75, 1, 100, 4, 0.7, 1.5: the constants of src/gyro_aided_tracker.cpp:7-9, :60, :921, :1066, :1081, :1115 */
+void pagk_assoc_params_default(pagk_assoc_params *p);
+/* PAGK_OK if *p can be run by the entry points below (src/gyro_aided_tracker.cpp:859-939, :1017-1136): every threshold
+ * finite and >= 0, use_ncc 0 or 1, min_matches >= 0; PAGK_E_ARG otherwise or for NULL.  Needs no device. */
+int pagk_assoc_params_check(const pagk_assoc_params *p);
+/* MatchFeatures (src/gyro_aided_tracker.cpp:949-1008) on device lists, as defined above: d_count n, d_nbr_* n x cap,
+ * d_match_* n rows (d_match_dist / d_match_ncc may be NULL), d_n_matches one int32, d_info PAGK_ASSOC_INFO_WORDS.  n, m >= 0,
+ * cap >= 1.  Device pointers, asynchronous on the context stream, capturable; nothing is read on the host. */
+int pagk_match_features_device(pagk_ctx *ctx, const pagk_assoc_params *params, int32_t n, int32_t m, int32_t cap,
+                               const int32_t *d_count, const int32_t *d_nbr_idx, const float *d_nbr_dist,
+                               const float *d_nbr_ncc, int32_t *d_match_query, int32_t *d_match_train,
+                               float *d_match_dist /* or NULL */, float *d_match_ncc /* or NULL */, int32_t *d_n_matches,
+                               int32_t *d_info);
+/* Steps 2 and 3 of SearchByGyroPredict (src/gyro_aided_tracker.cpp:909-938) behind a finished prediction or PatchMatch;
+ * the arguments of pagk_near_neighbors_device without `level` (use_ncc comes from *params).  The call zeroes d_count, then:
+ * the neighbour search at level 1; choose and compact; the search at level 2 -- every workgroup of it returns at once
+ * unless *d_n_matches < min_matches, and it fills only the empty lists (:793); choose and compact again (the same result
+ * when level 2 did not run).  d_m: a device count of the live current keypoints (clamped to [0, m]) or NULL for m;
+ * d_flows_err: n x 2 float or NULL.  A list longer than cap leaves its true size in d_count[i] and is counted in info[1].
+ * Device pointers, asynchronous on the context stream, capturable: the retry is decided on the device at every replay. */
+int pagk_search_gyro_predict_device(pagk_ctx *ctx, const pagk_assoc_params *params, int32_t slot_ref, int32_t slot_cur,
+                                    int32_t half_patch, int32_t n, const float *d_keys_ref, const float *d_pt_predict_un,
+                                    const uint8_t *d_status, const float *d_affine, int32_t m, const float *d_keys_cur,
+                                    const float *d_keys_cur_un, const int32_t *d_m /* or NULL: m */, float radius_unit,
+                                    int32_t cap, int32_t *d_count, int32_t *d_nbr_idx, float *d_nbr_dist, float *d_nbr_ncc,
+                                    int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist /* or NULL */,
+                                    float *d_match_ncc /* or NULL */, int32_t *d_n_matches, float *d_flows_err /* or NULL */,
+                                    int32_t *d_info);
+/* The same with host buffers, synchronous (src/gyro_aided_tracker.cpp:909-938): both images are uploaded.  Returns
+ * mvMatches.size(), or PAGK_E_CAPACITY when info[1] is not zero (count[] then holds the sizes needed, as in
+ * pagk_find_near_neighbors; the device form only reports the word), or another negative error.  info may be NULL. */
+int pagk_search_gyro_predict(pagk_ctx *ctx, const pagk_assoc_params *params, const pagk_image *ref, const pagk_image *cur,
+                             int32_t half_patch, int32_t n, const float *keys_ref, const float *pt_predict_un,
+                             const uint8_t *status, const float *affine, int32_t m, const float *keys_cur,
+                             const float *keys_cur_un, float radius_unit, int32_t cap, int32_t *count, int32_t *nbr_idx,
+                             float *nbr_dist, float *nbr_ncc, int32_t *match_query, int32_t *match_train, float *match_dist,
+                             float *match_ncc, float *flows_err, int32_t *info);
+/* SearchByOpencvKLT (src/gyro_aided_tracker.cpp:1017-1136): pagk_lk_track_device from slot_ref to slot_cur (whose pyramids
+ * pagk_lk_pyramid_device has built), then the association defined above.  d_keys_ref, d_pt_out cap x 2 float; d_n, d_m device
+ * counts or NULL for cap, m; d_keys_cur m x 2 float; d_status cap bytes, d_err cap float (Lucas-Kanade's, after the err
+ * filter); d_match_query, d_match_train cap int32, d_match_dist cap float or NULL, d_disparity cap double, d_n_matches one
+ * int32, d_stats PAGK_ASSOC_STATS_WORDS double, d_info PAGK_ASSOC_INFO_WORDS and d_lk_info PAGK_LK_INFO_WORDS int32.
+ * Device pointers, asynchronous on the context stream, capturable; nothing is read on the host. */
+int pagk_search_klt_device(pagk_ctx *ctx, const pagk_lk_params *lk_params, const pagk_assoc_params *assoc_params,
+                           int32_t slot_ref, int32_t slot_cur, int32_t cap, const float *d_keys_ref,
+                           const int32_t *d_n /* or NULL: cap */, int32_t m, const float *d_keys_cur,
+                           const int32_t *d_m /* or NULL: m */, float *d_pt_out, uint8_t *d_status, float *d_err,
+                           int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist /* or NULL */,
+                           double *d_disparity, int32_t *d_n_matches, double *d_stats, int32_t *d_info, int32_t *d_lk_info);
+/* The same with host buffers, synchronous (src/gyro_aided_tracker.cpp:1017-1136): both images are uploaded and their
+ * pyramids built.  Returns mvMatches.size() or a negative error.  match_dist, stats, info and lk_info may be NULL. */
+int pagk_search_klt(pagk_ctx *ctx, const pagk_lk_params *lk_params, const pagk_assoc_params *assoc_params,
+                    const pagk_image *ref, const pagk_image *cur, int32_t n, const float *keys_ref, int32_t m,
+                    const float *keys_cur, float *pt_out, uint8_t *status, float *err, int32_t *match_query,
+                    int32_t *match_train, float *match_dist, double *disparity, double *stats, int32_t *info,
+                    int32_t *lk_info);
 
 /* ---- the path sharded over the GPUs of one node ---------------------- */
 /* Features are independent units (the cv::parallel_for_ of src/patch_match.cpp:103), so the path shards by

@@ -76,6 +76,20 @@ class LkParams(C.Structure):
                 ("min_eig_threshold", C.c_double), ("err_threshold", C.c_float)]
 
 
+class AssocParams(C.Structure):
+    """pagk_assoc_params (include/pagk.h): the constants of MatchFeatures, of the retry of SearchByGyroPredict and of
+    SearchByOpencvKLT's association."""
+    _fields_ = [("th_ncc_high", C.c_float), ("th_ncc_low", C.c_float), ("th_ratio", C.c_float), ("use_ncc", C.c_int32),
+                ("min_matches", C.c_int32), ("klt_max_distance", C.c_float), ("klt_ratio", C.c_double),
+                ("klt_disparity_factor", C.c_double)]
+
+
+ASSOC_INFO_WORDS = 8
+ASSOC_STATS_WORDS = 8
+ASSOC_MATCH_INFO_FIELDS = ("chosen", "overlong", "out_of_range", "claimed_twice", "matches", "level2_ran")
+ASSOC_KLT_INFO_FIELDS = ("live", "no_neighbour", "one_neighbour", "more_neighbours", "ratio_rejects", "lost_to_earlier",
+                         "dropped_by_disparity", "matches")
+ASSOC_STATS_FIELDS = ("avg1", "avg2", "max1", "max2", "threshold", "sum1", "sum2")
 DETECT_INFO_WORDS = 8
 ORB_INFO_WORDS = 8
 LK_INFO_WORDS = 8
@@ -337,6 +351,24 @@ def declare(lib) -> None:
     lib.pagk_geometry_select.argtypes = [f32, f32]
     lib.pagk_geometry_validation.restype = C.c_int
     lib.pagk_geometry_validation.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, f32, _P(f32)]
+    if hasattr(lib, "pagk_search_klt_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        ap, lp, f32_ = _P(AssocParams), _P(LkParams), C.c_float
+        lib.pagk_assoc_params_default.restype = None
+        lib.pagk_assoc_params_default.argtypes = [ap]
+        lib.pagk_assoc_params_check.restype = C.c_int
+        lib.pagk_assoc_params_check.argtypes = [ap]
+        lib.pagk_match_features_device.restype = C.c_int
+        lib.pagk_match_features_device.argtypes = [vp, ap, i32, i32, i32] + [vp] * 10
+        lib.pagk_search_gyro_predict_device.restype = C.c_int
+        lib.pagk_search_gyro_predict_device.argtypes = ([vp, ap, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32_, i32]
+                                                        + [vp] * 11)
+        lib.pagk_search_gyro_predict.restype = C.c_int
+        lib.pagk_search_gyro_predict.argtypes = ([vp, ap, _P(Image), _P(Image), i32, i32, vp, vp, vp, vp, i32, vp, vp, f32_, i32]
+                                                 + [vp] * 10)
+        lib.pagk_search_klt_device.restype = C.c_int
+        lib.pagk_search_klt_device.argtypes = [vp, lp, ap, i32, i32, i32, vp, vp, i32, vp, vp] + [vp] * 11
+        lib.pagk_search_klt.restype = C.c_int
+        lib.pagk_search_klt.argtypes = [vp, lp, ap, _P(Image), _P(Image), i32, vp, i32, vp] + [vp] * 10
     lib.pagk_fit_params_default.restype = None
     lib.pagk_fit_params_default.argtypes = [_P(FitParams)]
     lib.pagk_geometry_fit_device.restype = C.c_int
@@ -434,6 +466,8 @@ EXPORTED_SYMBOLS = [
     "pagk_selftest_sample",
     "pagk_lk_params_default", "pagk_lk_params_check", "pagk_lk_levels", "pagk_lk_pyramid_device", "pagk_lk_track_device",
     "pagk_lk_track", "pagk_selftest_lk_level",
+    "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
+    "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
 
 HANDOVER_STATE_WORDS = 8
@@ -538,6 +572,23 @@ def lk_levels(width: int, height: int, lk: LkParams | None = None) -> int:
     (needs no device)."""
     lk = lk if lk is not None else lk_params_default()
     return int(load().pagk_lk_levels(int(width), int(height), C.byref(lk)))
+
+
+def assoc_params_default(**overrides) -> AssocParams:
+    """pagk_assoc_params_default() with overrides (th_ncc_high, th_ncc_low, th_ratio, use_ncc, min_matches, klt_max_distance,
+    klt_ratio, klt_disparity_factor)."""
+    p = AssocParams()
+    load().pagk_assoc_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(AssocParams._fields_):
+            raise TypeError(f"pagk_assoc_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def assoc_params_check(p: AssocParams) -> int:
+    """pagk_assoc_params_check: PAGK_OK or PAGK_E_ARG (needs no device)."""
+    return int(load().pagk_assoc_params_check(C.byref(p)))
 
 
 def rectify_params_default(**overrides) -> RectifyParams:
@@ -1281,6 +1332,92 @@ class Context:
         buf = np.zeros((height, pitch), np.uint8)
         self._check(self.lib.pagk_selftest_lk_level(self.h, slot, level, buf.ctypes.data, pitch), "pagk_selftest_lk_level")
         return buf[:, :width]
+
+    # track-to-detection association (src/gyro_aided_tracker.cpp:859-939, :1017-1136) ---------------------------------------
+    assoc_params_default = staticmethod(assoc_params_default)
+
+    def match_features_device(self, ap: AssocParams, n: int, m: int, cap: int, d_count, d_idx, d_dist, d_ncc, d_match_query,
+                              d_match_train, d_match_dist, d_match_ncc, d_n_matches, d_info):
+        """pagk_match_features_device (asynchronous, capturable): d_match_dist and d_match_ncc may be None."""
+        self._check(self.lib.pagk_match_features_device(self.h, C.byref(ap), n, m, cap, _ptr(d_count), _ptr(d_idx), _ptr(d_dist),
+                                                        _ptr(d_ncc), _ptr(d_match_query), _ptr(d_match_train),
+                                                        _ptr(d_match_dist), _ptr(d_match_ncc), _ptr(d_n_matches), _ptr(d_info)),
+                    "pagk_match_features_device")
+
+    def search_gyro_predict_device(self, ap: AssocParams, slot_ref: int, slot_cur: int, half_patch: int, n: int, d_keys_ref,
+                                   d_pt_predict_un, d_status, d_affine, m: int, d_keys_cur, d_keys_cur_un, d_m,
+                                   radius_unit: float, cap: int, d_count, d_idx, d_dist, d_ncc, d_match_query, d_match_train,
+                                   d_match_dist, d_match_ncc, d_n_matches, d_flows_err, d_info):
+        """pagk_search_gyro_predict_device (asynchronous, capturable): d_affine, d_m, d_match_dist, d_match_ncc and
+        d_flows_err may be None."""
+        self._check(self.lib.pagk_search_gyro_predict_device(
+            self.h, C.byref(ap), slot_ref, slot_cur, half_patch, n, _ptr(d_keys_ref), _ptr(d_pt_predict_un), _ptr(d_status),
+            _ptr(d_affine), m, _ptr(d_keys_cur), _ptr(d_keys_cur_un), _ptr(d_m), float(radius_unit), cap, _ptr(d_count),
+            _ptr(d_idx), _ptr(d_dist), _ptr(d_ncc), _ptr(d_match_query), _ptr(d_match_train), _ptr(d_match_dist),
+            _ptr(d_match_ncc), _ptr(d_n_matches), _ptr(d_flows_err), _ptr(d_info)), "pagk_search_gyro_predict_device")
+
+    def search_gyro_predict(self, img_ref, img_cur, half_patch, keys_ref, pt_predict_un, status, affine, keys_cur, keys_cur_un,
+                            ap: AssocParams | None = None, radius_unit=None, cap=64) -> dict:
+        """pagk_search_gyro_predict, host buffers -> dict(rc, n_matches, query, train, dist, ncc (n_matches rows),
+        flows_err (n x 2), count, idx, dist_lists, ncc_lists, info and the info words by name); rc is the number of matches or
+        PAGK_E_CAPACITY (count then holds the sizes needed)."""
+        ap = ap if ap is not None else assoc_params_default()
+        n, m = int(keys_ref.shape[0]), int(keys_cur.shape[0])
+        nn = max(n, 1)
+        ir, ic = image_view(img_ref), image_view(img_cur)
+        count = np.zeros(nn, np.int32)
+        idx = np.full((nn, cap), -1, np.int32)
+        dist, ncc = np.zeros((nn, cap), np.float32), np.zeros((nn, cap), np.float32)
+        q, t = np.full(nn, -1, np.int32), np.full(nn, -1, np.int32)
+        md, mc = np.zeros(nn, np.float32), np.zeros(nn, np.float32)
+        flows = np.zeros((nn, 2), np.float32)
+        info = np.zeros(ASSOC_INFO_WORDS, np.int32)
+        ru = float(2 * half_patch) if radius_unit is None else float(radius_unit)
+        rc = self.lib.pagk_search_gyro_predict(self.h, C.byref(ap), C.byref(ir), C.byref(ic), half_patch, n, _ptr(keys_ref),
+                                               _ptr(pt_predict_un), _ptr(status), _ptr(affine), m, _ptr(keys_cur),
+                                               _ptr(keys_cur_un), ru, cap, _ptr(count), _ptr(idx), _ptr(dist), _ptr(ncc),
+                                               _ptr(q), _ptr(t), _ptr(md), _ptr(mc), _ptr(flows), _ptr(info))
+        if rc < 0 and rc != PAGK_E_CAPACITY:
+            self._check(rc, "pagk_search_gyro_predict")
+        k = int(info[4])
+        out = dict(rc=rc, n_matches=k, query=q[:k], train=t[:k], dist=md[:k], ncc=mc[:k], flows_err=flows[:n], count=count[:n],
+                   idx=idx[:n], dist_lists=dist[:n], ncc_lists=ncc[:n], info=info)
+        out.update(zip(ASSOC_MATCH_INFO_FIELDS, (int(v) for v in info[:6])))
+        return out
+
+    def search_klt_device(self, lk: LkParams, ap: AssocParams, slot_ref: int, slot_cur: int, cap: int, d_keys_ref, d_n, m: int,
+                          d_keys_cur, d_m, d_pt_out, d_status, d_err, d_match_query, d_match_train, d_match_dist, d_disparity,
+                          d_n_matches, d_stats, d_info, d_lk_info):
+        """pagk_search_klt_device (asynchronous, capturable): d_n, d_m and d_match_dist may be None."""
+        self._check(self.lib.pagk_search_klt_device(
+            self.h, C.byref(lk), C.byref(ap), slot_ref, slot_cur, cap, _ptr(d_keys_ref), _ptr(d_n), m, _ptr(d_keys_cur), _ptr(d_m),
+            _ptr(d_pt_out), _ptr(d_status), _ptr(d_err), _ptr(d_match_query), _ptr(d_match_train), _ptr(d_match_dist),
+            _ptr(d_disparity), _ptr(d_n_matches), _ptr(d_stats), _ptr(d_info), _ptr(d_lk_info)), "pagk_search_klt_device")
+
+    def search_klt(self, img_ref, img_cur, keys_ref, keys_cur, lk: LkParams | None = None, ap: AssocParams | None = None) -> dict:
+        """pagk_search_klt, host buffers -> dict(n_matches, query, train, dist, disparity (n_matches rows), pt_out, status, err
+        (n rows), stats, info, lk_info and the info words and statistics by name)."""
+        lk = lk if lk is not None else lk_params_default()
+        ap = ap if ap is not None else assoc_params_default()
+        kr = np.ascontiguousarray(keys_ref, np.float32).reshape(-1, 2)
+        kc = np.ascontiguousarray(keys_cur, np.float32).reshape(-1, 2)
+        n, m = int(kr.shape[0]), int(kc.shape[0])
+        nn = max(n, 1)
+        ir, ic = image_view(img_ref), image_view(img_cur)
+        pt_out, status, err = np.zeros((nn, 2), np.float32), np.zeros(nn, np.uint8), np.zeros(nn, np.float32)
+        q, t = np.full(nn, -1, np.int32), np.full(nn, -1, np.int32)
+        md, disp = np.zeros(nn, np.float32), np.zeros(nn, np.float64)
+        stats = np.zeros(ASSOC_STATS_WORDS, np.float64)
+        info, lk_info = np.zeros(ASSOC_INFO_WORDS, np.int32), np.zeros(LK_INFO_WORDS, np.int32)
+        k = self.lib.pagk_search_klt(self.h, C.byref(lk), C.byref(ap), C.byref(ir), C.byref(ic), n, _ptr(kr) if n else None, m,
+                                     _ptr(kc) if m else None, _ptr(pt_out), _ptr(status), _ptr(err), _ptr(q), _ptr(t), _ptr(md),
+                                     _ptr(disp), _ptr(stats), _ptr(info), _ptr(lk_info))
+        self._check(min(k, 0), "pagk_search_klt")
+        out = dict(n_matches=k, query=q[:k], train=t[:k], dist=md[:k], disparity=disp[:k], pt_out=pt_out[:n], status=status[:n],
+                   err=err[:n], stats=stats, info=info, lk_info=lk_info)
+        out.update(zip(ASSOC_KLT_INFO_FIELDS, (int(v) for v in info)))
+        out.update(zip(ASSOC_STATS_FIELDS, (float(v) for v in stats[:7])))
+        return out
 
     # hipGraph capture of the *_device calls issued on the context stream --------------------
     def graph_begin(self):

@@ -30,6 +30,12 @@ inline Point3f operator+(const Point3f &a, const Point3f &b) { return Point3f(a.
 inline Point3f operator-(const Point3f &a, const Point3f &b) { return Point3f(a.x - b.x, a.y - b.y, a.z - b.z); }
 inline Point3f operator*(const Point3f &a, float s) { return Point3f(a.x * s, a.y * s, a.z * s); }
 
+struct Range {
+    int start = 0, end = 0;
+    Range() {}
+    Range(int start_, int end_) : start(start_), end(end_) {}
+};
+
 struct KeyPoint {
     Point2f pt;
     float size = 1, angle = -1, response = 0;

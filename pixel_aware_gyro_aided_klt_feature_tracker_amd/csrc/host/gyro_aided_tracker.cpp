@@ -47,7 +47,11 @@ void GyroAidedTracker::Initialize()
     mvPatchCorners[1] = cv::Point2f(h, -h);   // top right
     mvPatchCorners[2] = cv::Point2f(-h, h);   // bottom left
     mvPatchCorners[3] = cv::Point2f(h, h);    // bottom right
+    mbNCC = true;                                              // :60
+    mRadiusForFindNearNeighbor = 2.0f * (float)mHalfPatchSize;  // :62
     mN = (int)mvKeysRef.size();
+    mvvNearNeighbors.assign(mvKeysRef.size(), std::vector<sMatch>());
+    mvFlowsErrorUn.assign(mvKeysRef.size(), cv::Point2f(0, 0));
     mvPtPredict.assign(mN, cv::Point2f(0, 0));
     mvPtPredictUn.assign(mN, cv::Point2f(0, 0));
     mvFlowsPredictUn.assign(mN, cv::Point2f(0, 0));
@@ -320,6 +324,206 @@ int GyroAidedTracker::TrackFeatures()
         n_predict = GyroPredictFeaturesAndOpticalFlowRefined();
     }
     return n_predict;
+}
+
+// ---- track-to-detection association (reference :788-1136; the definition is in include/pagk.h) ---------------------------
+namespace {
+struct KeyArrays {
+    std::vector<float> ref, pred, affine, cur, cur_un;
+    std::vector<cv::uchar> status;
+};
+
+// the tracker's vectors as the dense arrays of the C ABI (one spare row: no array is empty)
+KeyArrays key_arrays(const GyroAidedTracker &t)
+{
+    const size_t n = (size_t)t.mN, m = t.mvKeysCur.size();
+    KeyArrays a;
+    a.ref.assign(2 * n + 2, 0.f), a.pred.assign(2 * n + 2, 0.f), a.affine.assign(4 * n + 4, 0.f), a.status.assign(n + 1, 0);
+    a.cur.assign(2 * m + 2, 0.f), a.cur_un.assign(2 * m + 2, 0.f);
+    for (size_t i = 0; i < n; i++) {
+        a.ref[2 * i] = t.mvKeysRef[i].pt.x, a.ref[2 * i + 1] = t.mvKeysRef[i].pt.y;
+        a.pred[2 * i] = t.mvPtPredictUn[i].x, a.pred[2 * i + 1] = t.mvPtPredictUn[i].y;
+        a.status[i] = t.mvStatus[i];
+        const cv::Mat &A = t.mvAffineDeformationMatrix[i];  // an empty Mat warps nothing (src/utils.cpp:125)
+        a.affine[4 * i] = A.empty() ? 1.f : A.at<float>(0, 0), a.affine[4 * i + 1] = A.empty() ? 0.f : A.at<float>(0, 1);
+        a.affine[4 * i + 2] = A.empty() ? 0.f : A.at<float>(1, 0), a.affine[4 * i + 3] = A.empty() ? 1.f : A.at<float>(1, 1);
+    }
+    for (size_t j = 0; j < m; j++) {
+        a.cur[2 * j] = t.mvKeysCur[j].pt.x, a.cur[2 * j + 1] = t.mvKeysCur[j].pt.y;
+        a.cur_un[2 * j] = t.mvKeysCurUn[j].pt.x, a.cur_un[2 * j + 1] = t.mvKeysCurUn[j].pt.y;
+    }
+    return a;
+}
+
+pagk_image image_of(const cv::Mat &m) { return pagk_image{m.data, m.cols, m.rows, (int64_t)m.step}; }
+
+[[noreturn]] void fail(const char *what, int rc)
+{
+    throw std::runtime_error(std::string("GyroAidedTracker: ") + what + ": " + pagk_strerror(rc) + " " +
+                             pagk_last_error(PatchMatch::Context()));
+}
+}  // namespace
+
+// reference :788-851 for the features of `range`: the lists of features that have none yet
+void GyroAidedTracker::FindAndSortNearNeighbor(const cv::Range &range, int level)
+{
+    const KeyArrays a = key_arrays(*this);
+    const int m = (int)mvKeysCur.size();
+    std::vector<int32_t> count((size_t)mN + 1, 0);
+    for (int i = 0; i < mN; i++)  // a feature outside the range, or with a list (:793), is skipped
+        count[i] = (i < range.start || i >= range.end) ? 1 : (int32_t)mvvNearNeighbors[i].size();
+    const std::vector<int32_t> before = count;
+    const pagk_image ref = image_of(mImgGrayRef), cur = image_of(mImgGrayCur);
+    int cap = 64;
+    for (;;) {
+        std::vector<int32_t> idx((size_t)mN * cap + 1), cnt = before;
+        std::vector<float> dist((size_t)mN * cap + 1), ncc((size_t)mN * cap + 1);
+        int rc = pagk_find_near_neighbors(PatchMatch::Context(), &ref, &cur, mHalfPatchSize, mN, a.ref.data(), a.pred.data(),
+                                          a.status.data(), a.affine.data(), m, a.cur.data(), a.cur_un.data(), level,
+                                          mRadiusForFindNearNeighbor, mbNCC ? 1 : 0, cap, cnt.data(), idx.data(), dist.data(),
+                                          ncc.data());
+        if (rc == PAGK_E_CAPACITY) {  // cnt holds the sizes needed
+            for (int i = 0; i < mN; i++) cap = cnt[i] > cap ? cnt[i] : cap;
+            continue;
+        }
+        if (rc != PAGK_OK) fail("pagk_find_near_neighbors", rc);
+        for (int i = range.start; i < range.end && i < mN; i++) {
+            if (before[i] > 0 || !mvStatus[i]) continue;
+            std::vector<sMatch> &list = mvvNearNeighbors[i];
+            for (int k = 0; k < cnt[i]; k++)
+                list.push_back(sMatch(i, idx[(size_t)i * cap + k], dist[(size_t)i * cap + k], ncc[(size_t)i * cap + k], level));
+        }
+        return;
+    }
+}
+
+// reference :949-1008
+void GyroAidedTracker::MatchFeatures(std::vector<sMatch> &vMatches, const std::vector<std::vector<sMatch>> &vvNearNeighbors)
+{
+    size_t cap = 1;
+    for (int i = 0; i < mN; i++) cap = vvNearNeighbors[i].size() > cap ? vvNearNeighbors[i].size() : cap;
+    std::vector<int32_t> count((size_t)mN + 1, 0), idx((size_t)mN * cap + 1, -1), q((size_t)mN + 1), t((size_t)mN + 1);
+    std::vector<float> dist((size_t)mN * cap + 1, 0.f), ncc((size_t)mN * cap + 1, 0.f), md((size_t)mN + 1), mc((size_t)mN + 1);
+    for (int i = 0; i < mN; i++) {
+        count[i] = (int32_t)vvNearNeighbors[i].size();
+        for (size_t k = 0; k < vvNearNeighbors[i].size(); k++) {
+            const sMatch &s = vvNearNeighbors[i][k];
+            idx[i * cap + k] = s.trainIdx, dist[i * cap + k] = s.distance, ncc[i * cap + k] = s.ncc;
+        }
+    }
+    const int k = pagk_match_features(mN, (int32_t)cap, count.data(), idx.data(), dist.data(), ncc.data(), mbNCC ? 1 : 0, q.data(),
+                                      t.data(), md.data(), mc.data());
+    if (k < 0) fail("pagk_match_features", k);
+    for (int r = 0; r < k; r++) vMatches.push_back(vvNearNeighbors[q[r]][0]);
+}
+
+// reference :859-939.  Steps 2 and 3 are one call: the searches, both MatchFeatures and the retry run on the device.
+int GyroAidedTracker::SearchByGyroPredict()
+{
+    IntegrateGyroMeasurements();
+    if (mType == GYRO_PREDICT)  // Step 1, :866-905
+        GyroPredictFeatures();
+    else {
+        switch (mType) {
+            case IMAGE_ONLY_OPTICAL_FLOW_CONSIDER_ILLUMINATION:
+                mbHasGyroPredictInitial = false, mbConsiderIllumination = true, mbConsiderAffineDeformation = true,
+                mbRegularizationPenalty = false;
+                break;
+            case GYRO_PREDICT_WITH_OPTICAL_FLOW_REFINED:
+                mbHasGyroPredictInitial = true, mbConsiderIllumination = false, mbConsiderAffineDeformation = false,
+                mbRegularizationPenalty = false;
+                break;
+            case GYRO_PREDICT_WITH_OPTICAL_FLOW_REFINED_CONSIDER_ILLUMINATION:
+                mbHasGyroPredictInitial = true, mbConsiderIllumination = true, mbConsiderAffineDeformation = false,
+                mbRegularizationPenalty = false;
+                break;
+            case GYRO_PREDICT_WITH_OPTICAL_FLOW_REFINED_CONSIDER_ILLUMINATION_DEFORMATION:
+                mbHasGyroPredictInitial = true, mbConsiderIllumination = true, mbConsiderAffineDeformation = true,
+                mbRegularizationPenalty = false;
+                break;
+            case GYRO_PREDICT_WITH_OPTICAL_FLOW_REFINED_CONSIDER_ILLUMINATION_DEFORMATION_REGULAR:
+                mbHasGyroPredictInitial = true, mbConsiderIllumination = true, mbConsiderAffineDeformation = true,
+                mbRegularizationPenalty = true;
+                break;
+            default:
+                return -1;  // :899-902 "Unsupport type" (OPENCV_OPTICAL_FLOW_PYR_LK among them)
+        }
+        GyroPredictFeaturesAndOpticalFlowRefined();
+    }
+    const KeyArrays a = key_arrays(*this);
+    const int m = (int)mvKeysCur.size();
+    const pagk_image ref = image_of(mImgGrayRef), cur = image_of(mImgGrayCur);
+    pagk_assoc_params ap;
+    pagk_assoc_params_default(&ap);
+    ap.th_ncc_high = TH_NCC_HIGH, ap.th_ncc_low = TH_NCC_LOW, ap.th_ratio = TH_RATIO, ap.use_ncc = mbNCC ? 1 : 0;
+    std::vector<int32_t> q((size_t)mN + 1), t((size_t)mN + 1), count((size_t)mN + 1);
+    std::vector<float> md((size_t)mN + 1), mc((size_t)mN + 1), flows(2 * (size_t)mN + 2);
+    int32_t info[PAGK_ASSOC_INFO_WORDS] = {0};
+    int cap = 64, k;
+    std::vector<int32_t> idx;
+    std::vector<float> dist, ncc;
+    for (;;) {
+        idx.assign((size_t)mN * cap + 1, -1), dist.assign((size_t)mN * cap + 1, 0.f), ncc.assign((size_t)mN * cap + 1, 0.f);
+        k = pagk_search_gyro_predict(PatchMatch::Context(), &ap, &ref, &cur, mHalfPatchSize, mN, a.ref.data(), a.pred.data(),
+                                     a.status.data(), a.affine.data(), m, a.cur.data(), a.cur_un.data(),
+                                     mRadiusForFindNearNeighbor, cap, count.data(), idx.data(), dist.data(), ncc.data(), q.data(),
+                                     t.data(), md.data(), mc.data(), flows.data(), info);
+        if (k != PAGK_E_CAPACITY) break;
+        for (int i = 0; i < mN; i++) cap = count[i] > cap ? count[i] : cap;  // count holds the sizes needed
+    }
+    if (k < 0) fail("pagk_search_gyro_predict", k);
+    mvvNearNeighbors.assign(mN, std::vector<sMatch>());
+    const float r1 = 1 * mRadiusForFindNearNeighbor;  // :811
+    for (int i = 0; i < mN; i++)
+        for (int c = 0; c < count[i]; c++) {
+            const int j = idx[(size_t)i * cap + c];
+            // a list found at level 2 was empty at level 1: its entries lie outside the level-1 square (:813-814)
+            const cv::Point2f dpt = mvPtPredictUn[i] - mvKeysCurUn[j].pt;
+            const int level = (std::fabs(dpt.x) > r1 || std::fabs(dpt.y) > r1) ? 2 : 1;
+            mvvNearNeighbors[i].push_back(sMatch(i, j, dist[(size_t)i * cap + c], ncc[(size_t)i * cap + c], level));
+        }
+    mvMatches.clear();
+    for (int r = 0; r < k; r++) mvMatches.push_back(mvvNearNeighbors[q[r]][0]);
+    mvFlowsErrorUn.assign(mN, cv::Point2f(0, 0));  // Step 3, :928-933
+    for (int i = 0; i < mN; i++) mvFlowsErrorUn[i] = cv::Point2f(flows[2 * i], flows[2 * i + 1]);
+    return (int)mvMatches.size();
+}
+
+// reference :1017-1136.  cv::calcOpticalFlowPyrLK and cv::BFMatcher::radiusMatch are the library's definitions
+// (include/pagk.h), not OpenCV's arithmetic.  The reference appends to mvMatches and mvDisparities; on a fresh tracker,
+// which is how it is used, that is what is left here: both are cleared first.
+int GyroAidedTracker::SearchByOpencvKLT()
+{
+    if (mImgGrayRef.empty() || mImgGrayCur.empty()) return -1;  // :1021-1025
+    const size_t n = mvKeysRef.size(), m = mvKeysCur.size();
+    std::vector<float> kr(2 * n + 2, 0.f), kc(2 * m + 2, 0.f), ptOut(2 * n + 2, 0.f), md(n + 1), err(n + 1, 0.f);
+    std::vector<cv::uchar> status(n + 1, 0);
+    std::vector<int32_t> q(n + 1), t(n + 1);
+    std::vector<double> disp(n + 1);
+    for (size_t i = 0; i < n; i++) kr[2 * i] = mvKeysRef[i].pt.x, kr[2 * i + 1] = mvKeysRef[i].pt.y;  // :1028-1030
+    for (size_t j = 0; j < m; j++) kc[2 * j] = mvKeysCur[j].pt.x, kc[2 * j + 1] = mvKeysCur[j].pt.y;  // :1031-1033
+    pagk_lk_params lk;
+    pagk_lk_params_default(&lk);  // maxLevel 2, (COUNT + EPS, 30, 0.01), minEigThreshold 1e-4, 12.0 (:1036-1048)
+    lk.half_patch = mHalfPatchSize;
+    pagk_assoc_params ap;
+    pagk_assoc_params_default(&ap);  // maxDistance 4, ratio 0.7, filterOutFactor 1.5 (:1066, :1081, :1115)
+    const pagk_image ref = image_of(mImgGrayRef), cur = image_of(mImgGrayCur);
+    const int k = pagk_search_klt(PatchMatch::Context(), &lk, &ap, &ref, &cur, (int32_t)n, kr.data(), (int32_t)m, kc.data(),
+                                  ptOut.data(), status.data(), err.data(), q.data(), t.data(), md.data(), disp.data(), nullptr,
+                                  nullptr, nullptr);
+    if (k < 0) fail("pagk_search_klt", k);
+    mvPtPredict.resize(n), mvStatus.resize(n), mvError.resize(n);
+    for (size_t i = 0; i < n; i++) {  // :1041-1057
+        mvPtPredict[i] = cv::Point2f(ptOut[2 * i], ptOut[2 * i + 1]);
+        mvStatus[i] = status[i];
+        mvError[i] = err[i];
+    }
+    mvMatches.clear(), mvDisparities.clear();
+    for (int r = 0; r < k; r++) {
+        mvMatches.push_back(sMatch(q[r], t[r], md[r]));  // :1092
+        mvDisparities.push_back(disp[r]);                // :1100
+    }
+    return (int)mvMatches.size();
 }
 
 // ---- Step 2: geometry validation (reference :429-480) ----------------------------------------------

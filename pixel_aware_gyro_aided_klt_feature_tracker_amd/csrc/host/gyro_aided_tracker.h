@@ -1,9 +1,9 @@
-// gyro_aided_tracker.h -- the hot-path side of the reference's GyroAidedTracker
-// (include/gyro_aided_tracker.h:47-260): data constructor, TrackFeatures() type dispatch,
-// GyroPredictFeatures(), GyroPredictFeaturesAndOpticalFlowRefined() and the public result vectors
-// PatchMatch reads and writes, and GeometryValidation() around externally fitted models (the RANSAC fits
-// are cv::findHomography / cv::findFundamentalMat: third-party, supplied by the application).  The unused
-// matchers, display and logging are out of scope and are not declared.
+// gyro_aided_tracker.h -- the reference's GyroAidedTracker (include/gyro_aided_tracker.h:47-260): data constructor,
+// TrackFeatures() type dispatch, GyroPredictFeatures(), GyroPredictFeaturesAndOpticalFlowRefined() and the public result
+// vectors PatchMatch reads and writes, GeometryValidation() around externally fitted models or the device fits, and the
+// two matchers that tie a tracked point to a detected keypoint, SearchByGyroPredict() and SearchByOpencvKLT(), with
+// FindAndSortNearNeighbor(), MatchFeatures(), struct sMatch and their result vectors.  Display and logging are out of
+// scope and are not declared.
 #pragma once
 #include <functional>
 #include <string>
@@ -36,6 +36,17 @@ public:
         IMAGE_ONLY_OPTICAL_FLOW_CONSIDER_ILLUMINATION = 5
     };
     enum ePredictMethod { PIXEL_AWARE_PREDICTION = 1, SINGLE_HOMOGRAPHY = 2 };
+
+    struct sMatch {  // reference include/gyro_aided_tracker.h:70-105
+        int queryIdx = -1, trainIdx = -1;
+        float distance = -1, ncc = 0.0f;
+        int level = 0;  // search region: level * mRadiusForFindNearNeighbor
+        sMatch() {}
+        sMatch(int queryIdx_, int trainIdx_, float distance_, float ncc_ = 0.0f, int level_ = 0)
+            : queryIdx(queryIdx_), trainIdx(trainIdx_), distance(distance_), ncc(ncc_), level(level_) {}
+        bool operator<(const sMatch &m) const { return distance < m.distance; }  // less is better
+    };
+    static constexpr float TH_NCC_HIGH = 0.6f, TH_NCC_LOW = 0.3f, TH_RATIO = 0.75f;  // src/gyro_aided_tracker.cpp:7-9
 
     // reference include/gyro_aided_tracker.h:109-117
     GyroAidedTracker(double t, double t_ref, const cv::Mat &imgGrayRef_, const cv::Mat &imgGrayCur_,
@@ -109,6 +120,14 @@ public:
     int GyroPredictFeatures();
     int GyroPredictFeaturesAndOpticalFlowRefined();
 
+    // Track-to-detection association (include/pagk.h has the definition; everything behind the prediction runs on the
+    // device).  reference include/gyro_aided_tracker.h:132-141, src/gyro_aided_tracker.cpp:859-939, :1017-1136, :949-1008,
+    // :788-851.  SearchByGyroPredict returns -1 for a type it does not run (type 0 among them), like the reference.
+    int SearchByGyroPredict();
+    int SearchByOpencvKLT();
+    void MatchFeatures(std::vector<sMatch> &vMatches, const std::vector<std::vector<sMatch>> &vvNearNeighbors);
+    void FindAndSortNearNeighbor(const cv::Range &range, int level);
+
     // Step 2 of the tracker, reference include/gyro_aided_tracker.h:134 / src/gyro_aided_tracker.cpp:429-480.
     // The reference fits H21 and F21 inside CheckHomography / CheckFundamental with OpenCV's RANSAC
     // (:596, :699) and inverts H21 with cv::Mat::inv (:597); here an application may supply those three
@@ -153,6 +172,13 @@ public:  // data members keep the reference's names (include/gyro_aided_tracker.
     std::vector<double> mvPixelErrorsOfPatchMatched, mvDistanceBetweenPredictedAndPatchMatched;
     std::vector<float> mvNccAfterPatchMatched;
     std::vector<cv::Point2f> mvFlowsPredictUn;
+
+    std::vector<sMatch> mvMatches;                       // the two Search methods' result
+    std::vector<double> mvDisparities;                   // SearchByOpencvKLT: |keypoint in ref - matched keypoint in cur|
+    std::vector<std::vector<sMatch>> mvvNearNeighbors;   // best first
+    std::vector<cv::Point2f> mvFlowsErrorUn;             // detected - predicted, (0, 0) without a match
+    bool mbNCC = true;                                   // src/gyro_aided_tracker.cpp:60
+    float mRadiusForFindNearNeighbor = 0;                // 2 * mHalfPatchSize (:62), set by Initialize()
 
     float mTimeCostGyroPredict = 0, mTimeCostOptFlow = 0, mTimeCostOptFlowResultFilterOut = 0,
           mTimeCostGeometryValidation = 0, mTImeCostTotalFeatureTrack = 0;

@@ -15,6 +15,7 @@
 
 #include "../../include/pagk.h"
 #include "pagk_kernels.h"
+#include "pagk_associate_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 
@@ -70,6 +71,7 @@ struct pagk_ctx {
         ORB_KEYS,      // ... the matcher's best-match keys: sized by cap_q
         LK_PYR,        // Lucas-Kanade (pagk_lk_kernel.h): the pyrDown levels of slot 0 ...
         LK_PYR_LAST = LK_PYR + kSlots - 1,   // ... to slot kSlots - 1, each sized by W, H and the top level
+        ASSOC,         // track-to-detection association (pagk_associate_kernel.h): choices and claims, sized by n and m
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
@@ -3550,7 +3552,8 @@ static int near_neighbors_launch(pagk_ctx *ctx, const FrameSlot &sr, const Frame
                                  const float *d_keys_ref, const float *d_pt_predict_un, const uint8_t *d_status,
                                  const float *d_affine, int32_t m, const float *d_keys_cur, const float *d_keys_cur_un,
                                  int32_t level, float radius_unit, int32_t use_ncc, int32_t pairs, int32_t cap,
-                                 int32_t *d_count, int32_t *d_nbr_idx, float *d_nbr_dist, float *d_nbr_ncc)
+                                 int32_t *d_count, int32_t *d_nbr_idx, float *d_nbr_dist, float *d_nbr_ncc,
+                                 const int32_t *d_gate = nullptr, int32_t gate_below = 0, const int32_t *d_m = nullptr)
 {
     NeighborArgs a;
     memset(&a, 0, sizeof a);
@@ -3563,6 +3566,7 @@ static int near_neighbors_launch(pagk_ctx *ctx, const FrameSlot &sr, const Frame
     a.keys_ref = d_keys_ref, a.pt_pred = d_pt_predict_un, a.affine = d_affine, a.status = d_status;
     a.keys_cur = d_keys_cur, a.keys_cur_un = d_keys_cur_un;
     a.count = d_count, a.nbr_idx = d_nbr_idx, a.nbr_dist = d_nbr_dist, a.nbr_ncc = d_nbr_ncc;
+    a.gate = d_gate, a.gate_below = gate_below, a.d_m = d_m;
     if (n <= 0) return PAGK_OK;
     const int P = (2 * half_patch + 1) * (2 * half_patch + 1);
     const int nr = (P + 255) / 256, tail = P % 32;
@@ -3809,8 +3813,9 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
     return st.finish();
 }
 
-// GyroAidedTracker::MatchFeatures, src/gyro_aided_tracker.cpp:949-1008.  Host-side: a sequential pass whose
-// decisions depend on the matches accepted so far.
+// GyroAidedTracker::MatchFeatures, src/gyro_aided_tracker.cpp:949-1008, as the reference writes it: a sequential pass
+// over a set and an erase loop.  Its result is a count and a stable compaction (feature i keeps its choice t iff exactly
+// one feature chose t, in increasing i): pagk_match_features_device below computes the same bytes on device lists.
 int pagk_match_features(int32_t n, int32_t cap, const int32_t *count, const int32_t *nbr_idx, const float *nbr_dist,
                         const float *nbr_ncc, int32_t use_ncc, int32_t *match_query, int32_t *match_train,
                         float *match_dist, float *match_ncc)
@@ -3864,6 +3869,278 @@ int pagk_match_features(int32_t n, int32_t cap, const int32_t *count, const int3
     } catch (const std::bad_alloc &) {
         return PAGK_E_NOMEM;
     }
+}
+
+// ---- track-to-detection association (pagk_associate_kernel.h) --------------------------------------------------------
+void pagk_assoc_params_default(pagk_assoc_params *p)
+{
+    if (!p) return;
+    p->th_ncc_high = 0.6f, p->th_ncc_low = 0.3f, p->th_ratio = 0.75f;   // src/gyro_aided_tracker.cpp:7-9
+    p->use_ncc = 1;                     // mbNCC, :60
+    p->min_matches = 100;               // :921
+    p->klt_max_distance = 4.0f;         // :1066
+    p->klt_ratio = 0.7;                 // :1081
+    p->klt_disparity_factor = 1.5;      // :1115
+}
+
+int pagk_assoc_params_check(const pagk_assoc_params *p)
+{
+    if (!p) return PAGK_E_ARG;
+    auto ok = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (!ok(p->th_ncc_high) || !ok(p->th_ncc_low) || !ok(p->th_ratio) || !ok(p->klt_max_distance) || !ok(p->klt_ratio) ||
+        !ok(p->klt_disparity_factor))
+        return PAGK_E_ARG;
+    if ((p->use_ncc != 0 && p->use_ncc != 1) || p->min_matches < 0) return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+namespace {
+
+// buf[ASSOC]: choice (rows) | neighbour counts (rows) | best distances (rows) | claims or owners (m)
+struct AssocWs {
+    int32_t *choice, *nnb, *claims;
+    float *dist0;
+    size_t claims_bytes;
+};
+
+int assoc_reserve(pagk_ctx *ctx, int32_t rows, int32_t m, AssocWs *w)
+{
+    const size_t rr = (size_t)std::max(rows, 1), mm = (size_t)std::max(m, 1);
+    const size_t sizes[4] = {rr * 4, rr * 4, rr * 4, mm * 4};
+    const Layout<4> lay(sizes);
+    DevBuf &b = ctx->buf[pagk_ctx::ASSOC];
+    int rc = reserve(ctx, b, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the association's workspace",
+                     "run the call once with these sizes before capturing");
+    if (rc) return rc;
+    w->choice = lay.at<int32_t>(b.ptr, 0), w->nnb = lay.at<int32_t>(b.ptr, 1), w->dist0 = lay.at<float>(b.ptr, 2);
+    w->claims = lay.at<int32_t>(b.ptr, 3), w->claims_bytes = mm * 4;
+    return PAGK_OK;
+}
+
+// choose and compact on device lists; `a` carries everything but the workspace
+int match_launch(pagk_ctx *ctx, MatchArgs a, const AssocWs &w)
+{
+    a.choice = w.choice, a.claims = w.claims;
+    HIPCHK(ctx, hipMemsetAsync(w.claims, 0, w.claims_bytes, ctx->stream));
+    if (a.n > 0) {
+        hipLaunchKernelGGL(k_match_choose, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_match_compact, dim3(1), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+MatchArgs match_args(const pagk_assoc_params *p, int32_t n, int32_t m, int32_t cap, const int32_t *d_count,
+                     const int32_t *d_nbr_idx, const float *d_nbr_dist, const float *d_nbr_ncc, int32_t *d_match_query,
+                     int32_t *d_match_train, float *d_match_dist, float *d_match_ncc, int32_t *d_n_matches, int32_t *d_info)
+{
+    MatchArgs a = {};
+    a.n = n, a.m = m, a.cap = cap, a.use_ncc = p->use_ncc;
+    a.th_high = p->th_ncc_high, a.th_low = p->th_ncc_low, a.th_ratio = p->th_ratio;
+    a.count = d_count, a.nbr_idx = d_nbr_idx, a.nbr_dist = d_nbr_dist, a.nbr_ncc = d_nbr_ncc;
+    a.match_query = d_match_query, a.match_train = d_match_train, a.match_dist = d_match_dist, a.match_ncc = d_match_ncc;
+    a.n_matches = d_n_matches, a.info = d_info;
+    return a;
+}
+
+int search_gyro_slots(pagk_ctx *ctx, const pagk_assoc_params *p, const FrameSlot &sr, const FrameSlot &sc, int32_t half_patch,
+                      int32_t n, const float *d_keys_ref, const float *d_pt_predict_un, const uint8_t *d_status,
+                      const float *d_affine, int32_t m, const float *d_keys_cur, const float *d_keys_cur_un, const int32_t *d_m,
+                      float radius_unit, int32_t cap, int32_t *d_count, int32_t *d_nbr_idx, float *d_nbr_dist, float *d_nbr_ncc,
+                      int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist, float *d_match_ncc,
+                      int32_t *d_n_matches, float *d_flows_err, int32_t *d_info)
+{
+    AssocWs w;
+    int rc = assoc_reserve(ctx, n, m, &w);
+    if (rc) return rc;
+    MatchArgs a = match_args(p, n, m, cap, d_count, d_nbr_idx, d_nbr_dist, d_nbr_ncc, d_match_query, d_match_train,
+                             d_match_dist, d_match_ncc, d_n_matches, d_info);
+    a.keys_cur_un = d_keys_cur_un, a.pt_pred = d_pt_predict_un, a.flows = d_flows_err;
+    if (n > 0) HIPCHK(ctx, hipMemsetAsync(d_count, 0, (size_t)n * 4, ctx->stream));
+    // Step 2.1 and 2.2 (:912-917)
+    if ((rc = near_neighbors_launch(ctx, sr, sc, half_patch, n, d_keys_ref, d_pt_predict_un, d_status, d_affine, m, d_keys_cur,
+                                    d_keys_cur_un, 1, radius_unit, p->use_ncc, 0, cap, d_count, d_nbr_idx, d_nbr_dist,
+                                    d_nbr_ncc, nullptr, 0, d_m)) ||
+        (rc = match_launch(ctx, a, w)))
+        return rc;
+    // the wider search, decided by the count on the device (:921-925): it fills only the lists that are empty (:793), and
+    // choosing again on unchanged lists gives the same matches, so the second match needs no gate of its own
+    if ((rc = near_neighbors_launch(ctx, sr, sc, half_patch, n, d_keys_ref, d_pt_predict_un, d_status, d_affine, m, d_keys_cur,
+                                    d_keys_cur_un, 2, radius_unit, p->use_ncc, 0, cap, d_count, d_nbr_idx, d_nbr_dist,
+                                    d_nbr_ncc, d_n_matches, p->min_matches, d_m)))
+        return rc;
+    a.gate = d_n_matches, a.gate_below = p->min_matches;
+    return match_launch(ctx, a, w);
+}
+
+int search_klt_slots(pagk_ctx *ctx, const pagk_lk_params *lk, const pagk_assoc_params *p, int32_t slot_ref, int32_t slot_cur,
+                     int32_t cap, const float *d_keys_ref, const int32_t *d_n, int32_t m, const float *d_keys_cur,
+                     const int32_t *d_m, float *d_pt_out, uint8_t *d_status, float *d_err, int32_t *d_match_query,
+                     int32_t *d_match_train, float *d_match_dist, double *d_disparity, int32_t *d_n_matches, double *d_stats,
+                     int32_t *d_info, int32_t *d_lk_info)
+{
+    if (!ctx || pagk_assoc_params_check(p) || m < 0 || (m > 0 && !d_keys_cur) || !d_match_query || !d_match_train ||
+        !d_disparity || !d_n_matches || !d_stats || !d_info || !d_lk_info)
+        return PAGK_E_ARG;
+    // calcOpticalFlowPyrLK and Step 1 (:1041-1057); it checks the rest of the arguments
+    int rc = lk_track_slots(ctx, lk, slot_ref, slot_cur, cap, d_keys_ref, d_n, d_pt_out, d_status, nullptr, d_err, nullptr,
+                            d_lk_info);
+    if (rc) return rc;
+    AssocWs w;
+    if ((rc = assoc_reserve(ctx, cap, m, &w))) return rc;
+    KltArgs a = {};
+    a.cap = cap, a.m = m, a.d_n = d_n, a.d_m = d_m, a.status = d_status, a.pt_lk = d_pt_out, a.pt_ref = d_keys_ref;
+    a.keys_cur = d_keys_cur, a.max_distance = p->klt_max_distance, a.ratio = p->klt_ratio, a.factor = p->klt_disparity_factor;
+    a.choice = w.choice, a.nnb = w.nnb, a.dist0 = w.dist0, a.owner = w.claims;
+    a.match_query = d_match_query, a.match_train = d_match_train, a.match_dist = d_match_dist, a.disparity = d_disparity;
+    a.n_matches = d_n_matches, a.stats = d_stats, a.info = d_info;
+    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)w.claims, 0x7fffffff, w.claims_bytes / 4, ctx->stream));
+    hipLaunchKernelGGL(k_radius_top2, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, a);   // Step 2, :1059-1087
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_klt_finish, dim3(1), dim3(1024), 0, ctx->stream, a);                                // Steps 3 and 4
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+}  // namespace
+
+int pagk_match_features_device(pagk_ctx *ctx, const pagk_assoc_params *params, int32_t n, int32_t m, int32_t cap,
+                               const int32_t *d_count, const int32_t *d_nbr_idx, const float *d_nbr_dist,
+                               const float *d_nbr_ncc, int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist,
+                               float *d_match_ncc, int32_t *d_n_matches, int32_t *d_info)
+{
+    if (!ctx || pagk_assoc_params_check(params) || n < 0 || m < 0 || cap < 1 || !d_n_matches || !d_info) return PAGK_E_ARG;
+    if (n > 0 && (!d_count || !d_nbr_idx || !d_nbr_dist || !d_nbr_ncc || !d_match_query || !d_match_train)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    AssocWs w;
+    int rc = assoc_reserve(ctx, n, m, &w);
+    if (rc) return rc;
+    return match_launch(ctx, match_args(params, n, m, cap, d_count, d_nbr_idx, d_nbr_dist, d_nbr_ncc, d_match_query,
+                                        d_match_train, d_match_dist, d_match_ncc, d_n_matches, d_info), w);
+}
+
+int pagk_search_gyro_predict_device(pagk_ctx *ctx, const pagk_assoc_params *params, int32_t slot_ref, int32_t slot_cur,
+                                    int32_t half_patch, int32_t n, const float *d_keys_ref, const float *d_pt_predict_un,
+                                    const uint8_t *d_status, const float *d_affine, int32_t m, const float *d_keys_cur,
+                                    const float *d_keys_cur_un, const int32_t *d_m, float radius_unit, int32_t cap,
+                                    int32_t *d_count, int32_t *d_nbr_idx, float *d_nbr_dist, float *d_nbr_ncc,
+                                    int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist, float *d_match_ncc,
+                                    int32_t *d_n_matches, float *d_flows_err, int32_t *d_info)
+{
+    if (!ctx || pagk_assoc_params_check(params) || slot_ref < 0 || slot_ref >= kUserSlots || slot_cur < 0 || slot_cur >= kUserSlots)
+        return PAGK_E_ARG;
+    if (half_patch < 1 || half_patch > PAGK_MAX_HALF_PATCH || n < 0 || m < 0 || cap < 1 || !d_n_matches || !d_info) return PAGK_E_ARG;
+    if (n > 0 && (!d_keys_ref || !d_pt_predict_un || !d_status || !d_count || !d_nbr_idx || !d_nbr_dist || !d_nbr_ncc ||
+                  !d_match_query || !d_match_train))
+        return PAGK_E_ARG;
+    if (n > 0 && m > 0 && (!d_keys_cur || !d_keys_cur_un)) return PAGK_E_ARG;
+    const FrameSlot &sr = ctx->slots[slot_ref], &sc = ctx->slots[slot_cur];
+    if (!sr.valid || !sc.valid) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return search_gyro_slots(ctx, params, sr, sc, half_patch, n, d_keys_ref, d_pt_predict_un, d_status, d_affine, m, d_keys_cur,
+                             d_keys_cur_un, d_m, radius_unit, cap, d_count, d_nbr_idx, d_nbr_dist, d_nbr_ncc, d_match_query,
+                             d_match_train, d_match_dist, d_match_ncc, d_n_matches, d_flows_err, d_info);
+}
+
+int pagk_search_gyro_predict(pagk_ctx *ctx, const pagk_assoc_params *params, const pagk_image *ref, const pagk_image *cur,
+                             int32_t half_patch, int32_t n, const float *keys_ref, const float *pt_predict_un,
+                             const uint8_t *status, const float *affine, int32_t m, const float *keys_cur,
+                             const float *keys_cur_un, float radius_unit, int32_t cap, int32_t *count, int32_t *nbr_idx,
+                             float *nbr_dist, float *nbr_ncc, int32_t *match_query, int32_t *match_train, float *match_dist,
+                             float *match_ncc, float *flows_err, int32_t *info)
+{
+    if (!ctx || pagk_assoc_params_check(params)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_search_gyro_predict");
+    if (half_patch < 1 || half_patch > PAGK_MAX_HALF_PATCH || n < 0 || m < 0 || cap < 1) return PAGK_E_ARG;
+    if (n > 0 && (!keys_ref || !pt_predict_un || !status || !count || !nbr_idx || !nbr_dist || !nbr_ncc || !match_query ||
+                  !match_train))
+        return PAGK_E_ARG;
+    if (n > 0 && m > 0 && (!keys_cur || !keys_cur_un)) return PAGK_E_ARG;
+    int rc;
+    if ((rc = check_image(ref)) || (rc = check_image(cur))) return rc;
+    if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
+    const size_t nn = (size_t)(n < 1 ? 1 : n), mm = (size_t)(m < 1 ? 1 : m), cc = (size_t)cap;
+    // keys_ref | pt_predict_un | status | affine | keys_cur | keys_cur_un | count | nbr_idx | nbr_dist | nbr_ncc |
+    // match_query | match_train | match_dist | match_ncc | flows_err | the count and the info words
+    const size_t sizes[16] = {nn * 8, nn * 8, nn, nn * 16, mm * 8, mm * 8, nn * 4, nn * cc * 4, nn * cc * 4, nn * cc * 4,
+                              nn * 4, nn * 4, nn * 4, nn * 4, nn * 8, 256};
+    const size_t fn = (size_t)n, fm = (size_t)m, list = fn * cc * 4;
+    int32_t tail[1 + kAssocInfoWords] = {};   // (in front of the object: copies write it)
+    Staged<16> s(ctx, sizes);
+    if ((rc = s.open(&ctx->buf[pagk_ctx::SCORE], "the neighbour search's scratch")) || (rc = s.in(0, keys_ref, fn * 8)) ||
+        (rc = s.in(1, pt_predict_un, fn * 8)) || (rc = s.in(2, status, fn)) || (rc = s.in(3, affine, fn * 16)) ||
+        (rc = s.in(4, keys_cur, fm * 8)) || (rc = s.in(5, keys_cur_un, fm * 8)) ||
+        // the lists of features that stay empty keep the caller's content
+        (rc = s.in(7, nbr_idx, list)) || (rc = s.in(8, nbr_dist, list)) || (rc = s.in(9, nbr_ncc, list)))
+        return rc;
+    int32_t *d_tail = s.at<int32_t>(15);
+    rc = search_gyro_slots(ctx, params, ctx->slots[4], ctx->slots[5], half_patch, n, s.at<float>(0), s.at<float>(1),
+                           s.at<uint8_t>(2), affine ? s.at<float>(3) : nullptr, m, s.at<float>(4), s.at<float>(5), nullptr,
+                           radius_unit, cap, s.at<int32_t>(6), s.at<int32_t>(7), s.at<float>(8), s.at<float>(9),
+                           s.at<int32_t>(10), s.at<int32_t>(11), s.at<float>(12), s.at<float>(13), d_tail,
+                           flows_err ? s.at<float>(14) : nullptr, d_tail + 1);
+    if (rc || (rc = s.out(6, count, fn * 4)) || (rc = s.out(7, nbr_idx, list)) || (rc = s.out(8, nbr_dist, list)) ||
+        (rc = s.out(9, nbr_ncc, list)) || (rc = s.out(10, match_query, fn * 4)) || (rc = s.out(11, match_train, fn * 4)) ||
+        (rc = s.out(12, match_dist, fn * 4)) || (rc = s.out(13, match_ncc, fn * 4)) || (rc = s.out(14, flows_err, fn * 8)) ||
+        (rc = s.out(15, tail, sizeof tail)) || (rc = s.finish()))
+        return rc;
+    if (info) memcpy(info, tail + 1, kAssocInfoWords * sizeof(int32_t));
+    if (tail[2]) {   // a list did not fit: count[] holds the sizes needed
+        snprintf(ctx->err, sizeof(ctx->err), "%d neighbour lists are longer than the capacity %d", tail[2], cap);
+        return PAGK_E_CAPACITY;
+    }
+    return tail[0];
+}
+
+int pagk_search_klt_device(pagk_ctx *ctx, const pagk_lk_params *lk_params, const pagk_assoc_params *assoc_params,
+                           int32_t slot_ref, int32_t slot_cur, int32_t cap, const float *d_keys_ref, const int32_t *d_n,
+                           int32_t m, const float *d_keys_cur, const int32_t *d_m, float *d_pt_out, uint8_t *d_status,
+                           float *d_err, int32_t *d_match_query, int32_t *d_match_train, float *d_match_dist,
+                           double *d_disparity, int32_t *d_n_matches, double *d_stats, int32_t *d_info, int32_t *d_lk_info)
+{
+    if (slot_ref < 0 || slot_ref >= kUserSlots || slot_cur < 0 || slot_cur >= kUserSlots) return PAGK_E_ARG;
+    return search_klt_slots(ctx, lk_params, assoc_params, slot_ref, slot_cur, cap, d_keys_ref, d_n, m, d_keys_cur, d_m, d_pt_out,
+                            d_status, d_err, d_match_query, d_match_train, d_match_dist, d_disparity, d_n_matches, d_stats,
+                            d_info, d_lk_info);
+}
+
+int pagk_search_klt(pagk_ctx *ctx, const pagk_lk_params *lk_params, const pagk_assoc_params *assoc_params,
+                    const pagk_image *ref, const pagk_image *cur, int32_t n, const float *keys_ref, int32_t m,
+                    const float *keys_cur, float *pt_out, uint8_t *status, float *err, int32_t *match_query,
+                    int32_t *match_train, float *match_dist, double *disparity, double *stats, int32_t *info, int32_t *lk_info)
+{
+    if (!ctx || !ref || !cur || lk_params_check(lk_params) || pagk_assoc_params_check(assoc_params)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_search_klt");
+    if (n < 0 || n > kLkMaxRows || m < 0 || (n && (!keys_ref || !pt_out || !status || !err || !match_query || !match_train || !disparity)))
+        return PAGK_E_ARG;
+    if (m > 0 && !keys_cur) return PAGK_E_ARG;
+    if (ref->width != cur->width || ref->height != cur->height || pagk_lk_levels(ref->width, ref->height, lk_params) < 0)
+        return PAGK_E_ARG;
+    int rc;
+    if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
+    if ((rc = lk_pyramid_slot(ctx, lk_params, 4)) || (rc = lk_pyramid_slot(ctx, lk_params, 5))) return rc;
+    const size_t nc = (size_t)std::max(n, 1), mm = (size_t)std::max(m, 1), nn = (size_t)n;
+    // keys_ref | count | keys_cur | pt_out | status | err | match_query | match_train | match_dist | disparity | stats |
+    // the match count, the info words and Lucas-Kanade's
+    const size_t sizes[12] = {nc * 8, 256, mm * 8, nc * 8, nc, nc * 4, nc * 4, nc * 4, nc * 4, nc * 8, 256, 256};
+    int32_t tail[1 + kAssocInfoWords + kLkInfoWords] = {};
+    Staged<12> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, keys_ref, nn * 8)) || (rc = s.in(1, &n, 4)) ||
+        (rc = s.in(2, keys_cur, (size_t)m * 8)))
+        return rc;
+    int32_t *d_tail = s.at<int32_t>(11);
+    rc = search_klt_slots(ctx, lk_params, assoc_params, 4, 5, (int32_t)nc, s.at<float>(0), s.at<int32_t>(1), m, s.at<float>(2),
+                          nullptr, s.at<float>(3), s.at<uint8_t>(4), s.at<float>(5), s.at<int32_t>(6), s.at<int32_t>(7),
+                          s.at<float>(8), s.at<double>(9), d_tail, s.at<double>(10), d_tail + 1, d_tail + 1 + kAssocInfoWords);
+    if (rc || (rc = s.out(3, pt_out, nn * 8)) || (rc = s.out(4, status, nn)) || (rc = s.out(5, err, nn * 4)) ||
+        (rc = s.out(6, match_query, nn * 4)) || (rc = s.out(7, match_train, nn * 4)) || (rc = s.out(8, match_dist, nn * 4)) ||
+        (rc = s.out(9, disparity, nn * 8)) || (rc = s.out(10, stats, kAssocStatsWords * sizeof(double))) ||
+        (rc = s.out(11, tail, sizeof tail)) || (rc = s.finish()))
+        return rc;
+    if (info) memcpy(info, tail + 1, kAssocInfoWords * sizeof(int32_t));
+    if (lk_info) memcpy(lk_info, tail + 1 + kAssocInfoWords, kLkInfoWords * sizeof(int32_t));
+    return tail[0];
 }
 
 }  // extern "C"

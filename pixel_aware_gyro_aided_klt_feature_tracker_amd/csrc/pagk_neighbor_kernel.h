@@ -33,6 +33,9 @@ struct NeighborArgs {
     int *count;
     int *nbr_idx;
     float *nbr_dist, *nbr_ncc;
+    const int *gate;       // nullptr, or: a workgroup returns at once unless *gate < gate_below (the "fewer than 100 matches"
+    int gate_below;        // retry of SearchByGyroPredict, :921, decided on the device)
+    const int *d_m;        // nullptr, or a device count of the live current keypoints: min(m, max(*d_m, 0))
 };
 
 // GetPixelValue of include/utils.h:32-46 on a quad image.  `pad`: bytes between the end of a row and the next
@@ -87,6 +90,8 @@ __global__ void __launch_bounds__(256) k_near_neighbors(NeighborArgs a)
     float *sh = reinterpret_cast<float *>(order + a.cap);  // 16 floats of scratch
     int *shi = reinterpret_cast<int *>(sh + 8);
 
+    if (a.gate && *a.gate >= a.gate_below) return;
+    if (a.d_m) a.m = min(a.m, max(*a.d_m, 0));
     if (!a.status[i]) return;                 // :791
     if (!a.pairs && a.count[i] > 0) return;   // :793 neighbours already found with a smaller search region
 

@@ -305,3 +305,24 @@ def lk_track(img_ref, img_cur, pts, lk=None, ctx=None) -> dict:
     name: n, raw, kept, top_level, lost_min_eig, lost_out_of_range)."""
     return _device_context(ctx).lk_track(np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8),
                                          pts, lk)
+
+
+# ---- track-to-detection association (src/gyro_aided_tracker.cpp:859-939, :1017-1136), array in, array out ----
+def search_by_gyro_predict(img_ref, img_cur, half_patch, keys_ref, pt_predict_un, status, affine, keys_cur, keys_cur_un,
+                           assoc=None, radius_unit=None, cap=64, ctx=None) -> dict:
+    """Steps 2 and 3 of GyroAidedTracker::SearchByGyroPredict behind a finished prediction (pagk_search_gyro_predict): the
+    neighbour search, MatchFeatures, the wider search when fewer than min_matches came out, the flow error -> dict(rc,
+    n_matches, query, train, dist, ncc, flows_err (n x 2), count, idx, dist_lists, ncc_lists, info and its words by name)."""
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)     # noqa: E731
+    return _device_context(ctx).search_gyro_predict(img_ref, img_cur, int(half_patch), f32(keys_ref).reshape(-1, 2),
+                                                    f32(pt_predict_un).reshape(-1, 2), np.ascontiguousarray(status, np.uint8),
+                                                    f32(affine), f32(keys_cur).reshape(-1, 2), f32(keys_cur_un).reshape(-1, 2),
+                                                    assoc, radius_unit, cap)
+
+
+def search_by_klt(img_ref, img_cur, keys_ref, keys_cur, lk=None, assoc=None, ctx=None) -> dict:
+    """GyroAidedTracker::SearchByOpencvKLT by the library's definition (pagk_search_klt): pyramidal Lucas-Kanade, the err
+    filter, the radius match against the detected keypoints, ratio test, first-come uniqueness, the mean-disparity filter ->
+    dict(n_matches, query, train, dist, disparity, pt_out, status, err, stats, info, lk_info and their fields by name)."""
+    return _device_context(ctx).search_klt(np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8),
+                                           keys_ref, keys_cur, lk, assoc)
