@@ -1002,10 +1002,117 @@ int pagk_geometry_validation_device(pagk_ctx *ctx, const pagk_fit_params *params
  * error.  Equal to pagk_geometry_validation fed with the models of pagk_geometry_fit. */
 int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, int32_t n, const float *pt_ref_un,
                                  const float *pt_predict_un, uint8_t *status, float sigma, float *track_score);
-/* Diagnostic: the drawn index sets of hypotheses first .. first + count - 1 of model (0 = H: 4 indices each, 1 = F: 8)
- * among m points, -1s for a hypothesis whose draws ran out.  Host buffer idx, synchronous. */
+/* Diagnostic: the drawn index sets of hypotheses first .. first + count - 1 of model (0 = H: 4 indices each, 1 = F: 8,
+ * 2 = E: 5, the section below) among m points, -1s for a hypothesis whose draws ran out.  Host buffer idx, synchronous. */
 int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32_t m, int32_t first, int32_t count,
                               int32_t *idx);
+
+/* ---- Two-view pose: the essential matrix, R and t of a frame pair, on the device ------------------------------------ */
+/* ORBDetectAndDespMatcher::PoseEstimation2d2d (src/ORBDetectAndDespMatcher.cpp:84-108), what both front-ends call behind
+ * FindFeatureMatches (Examples/Demo/RealSenseD435i.cpp:282-284): cv::findFundamentalMat(points1, points2, cv::RANSAC) (:93),
+ * cv::findEssentialMat(points1, points2, (mfx + mfy) / 2, cv::Point2d(mcx, mcy), cv::RANSAC) (:97), cv::findHomography(points1,
+ * points2, cv::RANSAC, 3) (:101) and cv::recoverPose(mE, points1, points2, mR, mt, focal, pp) (:105).  H and F are the fits of
+ * the section above (pagk_geometry_fit_device, bit for bit, its "more than 8 points" rule included); E, R and t are defined
+ * here.  Parity contract: NO parity with OpenCV is claimed -- its random generator, its SVD-based five-point solver and
+ * triangulatePoints are third-party.  The contract is this text, bit for bit, restated in plain C in tests/pose_ref.c.  Every
+ * rule below that is not Nister's method or the reference's call is the library's own.  All model arithmetic is f64, one IEEE
+ * rounding per operation, + - * / sqrt and comparisons only (no library call), every loop and sum in the stated order, sums
+ * left to right.
+ *
+ *   points     the m status-true correspondences in index order (all n when status is NULL); a point takes part whatever the
+ *              masks of H and F say (recoverPose is called without a mask, :105).
+ *   normalise  q = ((u - cx) / f, (v - cy) / f, 1) for both images, u and v widened from f32; the pixel threshold becomes
+ *              t = thresh_E / f.
+ *   sampling   hypothesis h draws 5 distinct indices by the rule of the section above with model id k = 2 (the draws of H and F
+ *              do not change); 64 draws without a full sample make the hypothesis invalid.
+ *   null space the 5 x 9 system with rows (x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1) is reduced by Gauss-Jordan with full
+ *              pivoting: step j takes the largest |entry| of rows j.. and columns j.. (the first in row-major order on a tie),
+ *              swaps it to (j, j), divides row j by it and subtracts f * row j from every other row.  A pivot at or below 1e-8
+ *              of the system's largest |entry| makes the sample invalid.  Null vector k = 0 .. 3 has 1 at the k-th free column,
+ *              minus column k of the reduced system at the pivot columns, 0 elsewhere.  The four vectors are orthonormalised by
+ *              modified Gram-Schmidt in index order (dot products over the 9 entries in order): X, Y, Z, W.
+ *   constraints  E = x X + y Y + z Z + W.  The 10 x 20 coefficient matrix, columns in Nister's order x3 y3 x2y xy2 x2z x2 y2z y2
+ *              xyz xy | xz2 xz x yz2 yz y z3 z2 z 1: rows 0 .. 8 are the entries of (E E^T - 1/2 tr(E E^T) I) E in row-major
+ *              order, row 9 is det E = e0 (e4 e8 - e5 e7) + e1 (e5 e6 - e3 e8) + e2 (e3 e7 - e4 e6).  Polynomial products
+ *              accumulate term by term in monomial order (linear: x y z 1; quadratic: x2 y2 xy xz x yz y z2 z 1): of two
+ *              linear factors the left one's monomials run in the outer loop, of a quadratic and a linear factor the
+ *              quadratic's (the 2 x 2 cofactors of det E, the entries of E E^T - 1/2 tr I); a difference of two products adds
+ *              the first and then subtracts the second, term by term; sums over the inner index k = 0, 1, 2 in order.  Gauss-Jordan with partial pivoting on the first
+ *              ten columns (largest |entry| of the column from the diagonal down, the first on a tie; a pivot that is not > 0
+ *              makes the sample invalid); rows 0 .. 3 are not updated after their own step.
+ *   B(z)       rows 4 .. 9 are e (x2z), f (x2), g (y2z), h (y2), i (xyz), j (xy).  The rows e - z f, g - z h, i - z j form the
+ *              3 x 3 matrix B(z) with columns x (degree 3), y (degree 3), 1 (degree 4); p(z) = det B(z), degree 10, by expansion
+ *              along the third column (c0 (x1 y2 - x2 y1) - c1 (x0 y2 - x2 y0) + c2 (x0 y1 - x1 y0)), then divided by its
+ *              largest |coefficient|.  A non-finite coefficient, p = 0 or a degree below 1 (after dropping exactly-zero leading
+ *              coefficients) makes the sample invalid.
+ *   real roots (the library's own algorithm) Cauchy's bound R = 1 + max |c_k / c_d|; the Sturm chain p, p', then the negated
+ *              remainders of the polynomial division, each divided by its largest |coefficient|, exactly-zero leading
+ *              coefficients dropped, ending at a zero remainder or degree 0; every polynomial is evaluated by Horner's rule.
+ *              N = V(-R) - V(R) sign variations (zeros skipped), clamped to 0 .. 10.  Root r = 1 .. N in increasing order: the
+ *              bracket (lo, hi] = (-R, R] is halved 64 times (mid = 0.5 (lo + hi); hi = mid when V(-R) - V(mid) >= r, else
+ *              lo = mid); then x = 0.5 (lo + hi) takes up to 6 Newton steps x - p(x) / p'(x), stopping at the first step that
+ *              leaves [lo, hi] or is not a number.  A companion-matrix eigen solver is not used.
+ *   candidates per root z: of the three row pairs (0,1), (0,2), (1,2) of B(z) the one with the largest |2 x 2 determinant| of its
+ *              x and y columns (the first on a tie) gives x and y by Cramer's rule; E = ((x X + y Y) + z Z) + W is divided by
+ *              its Frobenius norm (sum of squares in index order).  A non-finite candidate is invalid.
+ *   consensus  the Sampson distance without its division: with (a, b, c) = E q1, (d1, d2, .) = E^T q2, r = q2 . (E q1):
+ *              r^2 <= t^2 (((a^2 + b^2) + d1^2) + d2^2).  Candidates are numbered 16 h + root; the highest integer count wins,
+ *              the lowest number on a tie.  The winner is E: there is no refit (findEssentialMat has none).  mask_E holds its
+ *              inliers.
+ *   no model   fewer than 5 points, no valid candidate, or a best count below 5: E, R, t and both masks are 0, status 0.
+ *   pose       Horn's closed form (no SVD, no Jacobi): G = E E^T, D_i = 1/2 tr G - G_ii; with i the largest D_i (the first on a
+ *              tie) b = row i of (1/2 tr G I - G) / sqrt(D_i); (b . b) R1 = cof(E) - [b]x E, (b . b) R2 = cof(E) + [b]x E with
+ *              cof the cofactor matrix; t = b / sqrt(b . b).  For E of Frobenius norm 1 D_i >= 1/6 up to rounding, so the
+ *              division is defined.  det R = +1 and |t| = 1 as far as E satisfies its constraints.
+ *   cheirality for each of (R1, t), (R2, t), (R1, -t), (R2, -t), in that order, and every point: a = R q1, the depths of
+ *              lambda2 q2 = lambda1 a + t from the normal equations, det = (a.a)(q2.q2) - (a.q2)^2, lambda1 = ((a.q2)(q2.t) -
+ *              (a.t)(q2.q2)) / det, lambda2 = ((a.a)(q2.t) - (a.q2)(a.t)) / det; the point is good when 0 < lambda1 < max_depth
+ *              and 0 < lambda2 < max_depth (depths in units of |t|; a NaN is not good).  The pose with the most good points
+ *              wins, the first on a tie; mask_pose holds its good points.
+ * Info words, PAGK_POSE_INFO_WORDS int32: [0] status (1 = E, R, t; 0 = no model), [1] m, [2] the best hypothesis and [3] its
+ * root (-1, -1: no valid candidate), [4] its count, [5] valid samples, [6] valid (finite) candidates, [7] OpenCV's adaptive
+ * iteration count for w = best count / m, s = 5 and conf_E, as in the section above, [8] the chosen pose 0 .. 3, [9] .. [12]
+ * the good counts of the four poses, the rest 0. */
+#define PAGK_POSE_INFO_WORDS 16
+typedef struct pagk_pose_params {
+    uint64_t seed;
+    int32_t iters_E;      /* hypotheses of the essential matrix, default 1000, 1 .. PAGK_FIT_MAX_ITERS                       */
+    int32_t reserved;     /* 0                                                                                              */
+    double thresh_E;      /* px, default 1 (findEssentialMat's threshold argument)                                          */
+    double conf_E;        /* default 0.999 (its prob argument), reported adaptive count only                                 */
+    double max_depth;     /* default 50: the distance threshold of OpenCV 3.4's recoverPose, a parameter so that a host can pin it */
+    pagk_fit_params fit;  /* the H and F of the same call                                                                    */
+} pagk_pose_params;
+void pagk_pose_params_default(pagk_pose_params *p);
+/* PAGK_OK if *p can be run by the entry points below (src/ORBDetectAndDespMatcher.cpp:84-108): iters_E in range, thresh_E and
+ * max_depth finite and > 0, 0 < conf_E < 1, and a `fit` that pagk_geometry_fit_device accepts; PAGK_E_ARG otherwise or for
+ * NULL.  Needs no device. */
+int pagk_pose_params_check(const pagk_pose_params *p);
+/* PoseEstimation2d2d (src/ORBDetectAndDespMatcher.cpp:93-105) on device correspondences.  f > 0, cx, cy: the calibration the
+ * reference passes, (mfx + mfy) / 2 and (mcx, mcy).  d_pts1 / d_pts2: n x 2 float, d_status: n bytes or NULL; d_models: 27
+ * doubles H21 | H12 | F21 and d_fit_info: PAGK_FIT_INFO_WORDS, as pagk_geometry_fit_device writes them; d_pose: 21 doubles
+ * E | R | t (row-major); the four masks: n bytes each or NULL; d_pose_info: PAGK_POSE_INFO_WORDS; d_cand_counts: iters_E x 10
+ * consensus counts (-1: no such root, or not finite) or NULL.  Device pointers, asynchronous on the context stream,
+ * capturable; no count is read on the host (run the same call once before capturing: the workspaces are sized for n and
+ * the budgets by a call outside a capture).  The result does not depend on the order in which the workgroups run. */
+int pagk_pose_2d2d_device(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t n,
+                          const float *d_pts1, const float *d_pts2, const uint8_t *d_status /* or NULL */, double *d_models,
+                          double *d_pose, uint8_t *d_mask_H, uint8_t *d_mask_F, uint8_t *d_mask_E, uint8_t *d_mask_pose,
+                          int32_t *d_fit_info, int32_t *d_pose_info, int32_t *d_cand_counts /* or NULL */);
+/* The input of PoseEstimation2d2d (src/ORBDetectAndDespMatcher.cpp:86-91) gathered on the device in front of the call above,
+ * from what pagk_detect_fast_device and pagk_orb_match_device wrote: for query row q < cap_q, pts1[q] = d_kp_ref[q], pts2[q]
+ * = d_kp_cur[d_train_idx[q]], status[q] = q < nq && d_keep[q] && 0 <= d_train_idx[q] < nt, with the device counts *d_nq and
+ * *d_nt clamped to [0, cap_q] and [0, cap_t].  n = cap_q, and the masks (cap_q bytes each or NULL) are indexed by query row.
+ * Device pointers, asynchronous on the context stream, capturable. */
+int pagk_pose_from_matches_device(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t cap_q,
+                                  const float *d_kp_ref, const int32_t *d_nq, int32_t cap_t, const float *d_kp_cur,
+                                  const int32_t *d_nt, const int32_t *d_train_idx, const uint8_t *d_keep, double *d_models,
+                                  double *d_pose, uint8_t *d_mask_H, uint8_t *d_mask_F, uint8_t *d_mask_E, uint8_t *d_mask_pose,
+                                  int32_t *d_fit_info, int32_t *d_pose_info);
+/* pagk_pose_2d2d_device with host buffers, synchronous.  status, the masks and cand_counts may be NULL. */
+int pagk_pose_2d2d(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t n, const float *pts1,
+                   const float *pts2, const uint8_t *status, double *models, double *pose, uint8_t *mask_H, uint8_t *mask_F,
+                   uint8_t *mask_E, uint8_t *mask_pose, int32_t *fit_info, int32_t *pose_info, int32_t *cand_counts);
 
 /* ---- NCC nearest-neighbour matching ------------------------------ */
 /* GyroAidedTracker::FindAndSortNearNeighbor (src/gyro_aided_tracker.cpp:788-851) for all n reference keypoints

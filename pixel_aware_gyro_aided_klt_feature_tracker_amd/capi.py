@@ -48,6 +48,13 @@ class FitParams(C.Structure):
                 ("thresh_F", C.c_double), ("conf_H", C.c_double), ("conf_F", C.c_double)]
 
 
+class PoseParams(C.Structure):
+    """pagk_pose_params (include/pagk.h): the budget and thresholds of the essential matrix and the pose, and the
+    pagk_fit_params of the H and F of the same call."""
+    _fields_ = [("seed", C.c_uint64), ("iters_E", C.c_int32), ("reserved", C.c_int32), ("thresh_E", C.c_double),
+                ("conf_E", C.c_double), ("max_depth", C.c_double), ("fit", FitParams)]
+
+
 class DetectParams(C.Structure):
     """pagk_detect_params (include/pagk.h): the arguments of the reference's goodFeaturesToTrack call."""
     _fields_ = [("quality_level", C.c_double), ("min_distance", C.c_double), ("harris_k", C.c_double),
@@ -100,6 +107,9 @@ DETECT_INFO_FIELDS = ("n_corners", "raw", "overflow", "rmax_bits", "visited")
 FAST_INFO_FIELDS = ("n_keypoints", "raw", "first_pass_empty", "empty_cells", "nodes", "passes")
 FIT_INFO_WORDS = 12
 FIT_INFO_FIELDS = ("status", "best", "best_count", "refit_count", "valid", "adaptive")
+POSE_INFO_WORDS = 16
+POSE_INFO_FIELDS = ("status", "m", "best_hyp", "best_root", "best_count", "valid_samples", "valid_candidates", "adaptive",
+                    "pose", "good0", "good1", "good2", "good3")
 
 
 class Outputs(C.Structure):
@@ -381,6 +391,17 @@ def declare(lib) -> None:
     lib.pagk_geometry_validation_fit.argtypes = [vp, _P(FitParams), i32, vp, vp, vp, f32, _P(f32)]
     lib.pagk_selftest_fit_samples.restype = C.c_int
     lib.pagk_selftest_fit_samples.argtypes = [vp, C.c_uint64, i32, i32, i32, i32, vp]
+    f64 = C.c_double
+    lib.pagk_pose_params_default.restype = None
+    lib.pagk_pose_params_default.argtypes = [_P(PoseParams)]
+    lib.pagk_pose_params_check.restype = C.c_int
+    lib.pagk_pose_params_check.argtypes = [_P(PoseParams)]
+    lib.pagk_pose_2d2d_device.restype = C.c_int
+    lib.pagk_pose_2d2d_device.argtypes = [vp, _P(PoseParams), f64, f64, f64, i32] + [vp] * 12
+    lib.pagk_pose_from_matches_device.restype = C.c_int
+    lib.pagk_pose_from_matches_device.argtypes = [vp, _P(PoseParams), f64, f64, f64, i32, vp, vp, i32] + [vp] * 12
+    lib.pagk_pose_2d2d.restype = C.c_int
+    lib.pagk_pose_2d2d.argtypes = [vp, _P(PoseParams), f64, f64, f64, i32] + [vp] * 12
     lib.pagk_near_neighbors_device.restype = C.c_int
     lib.pagk_near_neighbors_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, i32, i32,
                                                vp, vp, vp, vp]
@@ -454,6 +475,8 @@ EXPORTED_SYMBOLS = [
     "pagk_multi_comm_count", "pagk_has_variant",
     "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
     "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
+    "pagk_pose_params_default", "pagk_pose_params_check", "pagk_pose_2d2d_device", "pagk_pose_from_matches_device",
+    "pagk_pose_2d2d",
     "pagk_post_filter_device", "pagk_gyro_predict_device_live", "pagk_frame_handover_device", "pagk_frame_handover",
     "pagk_detect_params_default", "pagk_detect_corners_device", "pagk_detect_corners",
     "pagk_frame_handover_detect_device", "pagk_frame_handover_detect", "pagk_selftest_corner_response",
@@ -483,6 +506,22 @@ def fit_params_default(**overrides) -> FitParams:
             raise TypeError(f"pagk_fit_params has no field {k}")
         setattr(p, k, v)
     return p
+
+
+def pose_params_default(**overrides) -> PoseParams:
+    """pagk_pose_params_default() with overrides (seed, iters_E, thresh_E, conf_E, max_depth, fit: a FitParams)."""
+    p = PoseParams()
+    load().pagk_pose_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(PoseParams._fields_):
+            raise TypeError(f"pagk_pose_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def pose_params_check(p: PoseParams) -> int:
+    """pagk_pose_params_check: PAGK_OK or PAGK_E_ARG.  Needs no device."""
+    return load().pagk_pose_params_check(C.byref(p))
 
 
 def detect_params_default(**overrides) -> DetectParams:
@@ -885,11 +924,61 @@ class Context:
                                                              _ptr(d_score)), "pagk_geometry_validation_device")
 
     def selftest_fit_samples(self, seed: int, model: int, m: int, first: int, count: int) -> np.ndarray:
-        """The drawn index sets of hypotheses [first, first + count) of model 0 (H, 4 each) or 1 (F, 8 each)."""
-        out = np.zeros((max(count, 1), 8 if model else 4), np.int32)
+        """The drawn index sets of hypotheses [first, first + count) of model 0 (H, 4 each), 1 (F, 8 each) or 2 (E, 5 each)."""
+        out = np.zeros((max(count, 1), 5 if model == 2 else 8 if model else 4), np.int32)
         self._check(self.lib.pagk_selftest_fit_samples(self.h, seed, model, m, first, count, _ptr(out)),
                     "pagk_selftest_fit_samples")
         return out[:count]
+
+    # the two-view pose (src/ORBDetectAndDespMatcher.cpp:84-108) ----------------------------------------------------
+    pose_params_default = staticmethod(pose_params_default)
+
+    def pose_2d2d(self, pts1, pts2, f: float, cx: float, cy: float, status=None, params: PoseParams | None = None,
+                  cand_counts: bool = False) -> dict:
+        """PoseEstimation2d2d (include/pagk.h pagk_pose_2d2d), host buffers -> dict(models, H21, H12, F21, pose, E, R, t,
+        mask_H, mask_F, mask_E, mask_pose, fit_info, pose_info, info: the pose words by name, cand_counts when asked for)."""
+        params = params if params is not None else pose_params_default()
+        pts1 = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2)
+        pts2 = np.ascontiguousarray(pts2, np.float32).reshape(-1, 2)
+        n = pts1.shape[0]
+        if pts2.shape[0] != n:
+            raise ValueError("pts1 / pts2 differ in length")
+        st = None if status is None else np.ascontiguousarray(status, np.uint8)
+        if st is not None and st.shape[0] != n:
+            raise ValueError("status has the wrong length")
+        models, pose = np.zeros(27, np.float64), np.zeros(21, np.float64)
+        masks = [np.zeros(max(n, 1), np.uint8) for _ in range(4)]
+        fi, pi = np.zeros(FIT_INFO_WORDS, np.int32), np.zeros(POSE_INFO_WORDS, np.int32)
+        cc = np.zeros((params.iters_E, 10), np.int32) if cand_counts else None
+        self._check(self.lib.pagk_pose_2d2d(self.h, C.byref(params), f, cx, cy, n, _ptr(pts1), _ptr(pts2), _ptr(st),
+                                            _ptr(models), _ptr(pose), *[_ptr(m) for m in masks], _ptr(fi), _ptr(pi),
+                                            _ptr(cc)), "pagk_pose_2d2d")
+        out = dict(models=models, H21=models[:9].reshape(3, 3), H12=models[9:18].reshape(3, 3), F21=models[18:].reshape(3, 3),
+                   pose=pose, E=pose[:9].reshape(3, 3), R=pose[9:18].reshape(3, 3), t=pose[18:], mask_H=masks[0][:n],
+                   mask_F=masks[1][:n], mask_E=masks[2][:n], mask_pose=masks[3][:n], fit_info=fi, pose_info=pi,
+                   info=dict(zip(POSE_INFO_FIELDS, pi.tolist())))
+        if cc is not None:
+            out["cand_counts"] = cc
+        return out
+
+    def pose_2d2d_device(self, params: PoseParams, f: float, cx: float, cy: float, n: int, d_pts1, d_pts2, d_status, d_models,
+                         d_pose, d_mask_H, d_mask_F, d_mask_E, d_mask_pose, d_fit_info, d_pose_info, d_cand_counts=None):
+        """pagk_pose_2d2d_device on device arrays (asynchronous, capturable)."""
+        self._check(self.lib.pagk_pose_2d2d_device(self.h, C.byref(params), f, cx, cy, n, _ptr(d_pts1), _ptr(d_pts2),
+                                                   _ptr(d_status), _ptr(d_models), _ptr(d_pose), _ptr(d_mask_H),
+                                                   _ptr(d_mask_F), _ptr(d_mask_E), _ptr(d_mask_pose), _ptr(d_fit_info),
+                                                   _ptr(d_pose_info), _ptr(d_cand_counts)), "pagk_pose_2d2d_device")
+
+    def pose_from_matches_device(self, params: PoseParams, f: float, cx: float, cy: float, cap_q: int, d_kp_ref, d_nq,
+                                 cap_t: int, d_kp_cur, d_nt, d_train_idx, d_keep, d_models, d_pose, d_mask_H, d_mask_F,
+                                 d_mask_E, d_mask_pose, d_fit_info, d_pose_info):
+        """pagk_pose_from_matches_device behind pagk_orb_match_device (asynchronous, capturable)."""
+        self._check(self.lib.pagk_pose_from_matches_device(self.h, C.byref(params), f, cx, cy, cap_q, _ptr(d_kp_ref),
+                                                           _ptr(d_nq), cap_t, _ptr(d_kp_cur), _ptr(d_nt), _ptr(d_train_idx),
+                                                           _ptr(d_keep), _ptr(d_models), _ptr(d_pose), _ptr(d_mask_H),
+                                                           _ptr(d_mask_F), _ptr(d_mask_E), _ptr(d_mask_pose),
+                                                           _ptr(d_fit_info), _ptr(d_pose_info)),
+                    "pagk_pose_from_matches_device")
 
     # NCC nearest-neighbour matching (SURVEY.md section 8 row f3) ------------------------------
     def find_near_neighbors(self, img_ref, img_cur, half_patch, keys_ref, pt_predict_un, status, affine, keys_cur,

@@ -65,10 +65,13 @@ __device__ __forceinline__ int32_t fit_draw(unsigned long long seed, int model, 
     return (int32_t)(((z >> 32) * (unsigned long long)m) >> 32);
 }
 
-// s = 4 (H) or 8 (F) distinct indices; false (and -1s) when kFitMaxDraws draws did not find them
+__device__ __forceinline__ int fit_sample_size(int model) { return model == 2 ? 5 : model ? 8 : 4; }
+
+// s = 4 (H), 8 (F) or 5 (E, model 2: pagk_pose_kernel.h) distinct indices; false (and -1s) when kFitMaxDraws draws did not
+// find them
 __device__ bool fit_sample(unsigned long long seed, int model, uint32_t hyp, uint32_t m, int32_t *idx)
 {
-    const int s = model ? 8 : 4;
+    const int s = fit_sample_size(model);
     uint32_t d = 0;
     for (int j = 0; j < 8; j++) idx[j] = -1;
     for (int j = 0; j < s; j++) {
@@ -600,7 +603,7 @@ __global__ void __launch_bounds__(256) k_fit_samples(unsigned long long seed, in
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    const int s = model ? 8 : 4;
+    const int s = fit_sample_size(model);
     int32_t idx[8];
     fit_sample(seed, model, (uint32_t)(first + i), (uint32_t)m, idx);
     for (int j = 0; j < s; j++) out[(size_t)s * i + j] = idx[j];

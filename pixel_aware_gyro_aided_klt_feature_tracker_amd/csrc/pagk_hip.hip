@@ -16,6 +16,7 @@
 #include "../../include/pagk.h"
 #include "pagk_kernels.h"
 #include "pagk_associate_kernel.h"
+#include "pagk_pose_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 
@@ -72,6 +73,8 @@ struct pagk_ctx {
         LK_PYR,        // Lucas-Kanade (pagk_lk_kernel.h): the pyrDown levels of slot 0 ...
         LK_PYR_LAST = LK_PYR + kSlots - 1,   // ... to slot kSlots - 1, each sized by W, H and the top level
         ASSOC,         // track-to-detection association (pagk_associate_kernel.h): choices and claims, sized by n and m
+        POSE,          // workspace of the two-view pose (pagk_pose_kernel.h): sized for pose_n correspondences and pose_iters hypotheses
+        POSEIO,        // scratch of the host-buffer pose entry point
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
@@ -79,6 +82,7 @@ struct pagk_ctx {
     };
     DevBuf buf[kBufs];
     int fit_n = 0, fit_iters = 0;  // what buf[FIT]'s layout was computed for
+    int pose_n = 0, pose_iters = 0;  // ... and buf[POSE]'s
     int rect_w = 0, rect_h = 0, rect_wp = 0;
     bool orb_pattern_set = false;
     struct LkPyr { int w = 0, h = 0, top = -1; } lk_pyr[kSlots];   // what buf[LK_PYR + slot] holds (top -1: nothing)
@@ -3547,6 +3551,149 @@ int pagk_geometry_validation_fit(pagk_ctx *ctx, const pagk_fit_params *params, i
     return cnt;
 }
 
+// ---- the two-view pose on the device (pagk_pose_kernel.h) ---------------------------------------------------------
+void pagk_pose_params_default(pagk_pose_params *p)
+{
+    if (!p) return;
+    p->seed = 0;
+    p->iters_E = 1000;
+    p->reserved = 0;
+    p->thresh_E = 1.0;    // findEssentialMat's default threshold
+    p->conf_E = 0.999;    // ... and prob
+    p->max_depth = 50.0;  // recoverPose's distance threshold
+    pagk_fit_params_default(&p->fit);
+}
+
+int pagk_pose_params_check(const pagk_pose_params *p)
+{
+    const bool ok = p && p->iters_E >= 1 && p->iters_E <= PAGK_FIT_MAX_ITERS && std::isfinite(p->thresh_E) && p->thresh_E > 0 &&
+                    p->conf_E > 0 && p->conf_E < 1 && std::isfinite(p->max_depth) && p->max_depth > 0 && fit_params_ok(&p->fit);
+    return ok ? PAGK_OK : PAGK_E_ARG;
+}
+
+namespace {
+
+bool pose_camera_ok(double f, double cx, double cy) { return std::isfinite(f) && f > 0 && std::isfinite(cx) && std::isfinite(cy); }
+
+// the pose workspace: PoseHdr | normalised correspondences | the hypotheses' best candidates | E R t | info | and, for
+// pagk_pose_from_matches_device, the gathered pts1 | pts2 | status
+struct PoseWs {
+    PoseHdr *hdr;
+    double *qn, *hyp_E, *pose;
+    int32_t *info;
+    float *g1, *g2;
+    uint8_t *gst;
+};
+
+// Room for n correspondences and `iters` hypotheses; grows like the fit's workspace, outside a capture only.
+int pose_workspace(pagk_ctx *ctx, int32_t n, int32_t iters, PoseWs *w)
+{
+    const int32_t n2 = n > ctx->pose_n ? n : ctx->pose_n, it2 = iters > ctx->pose_iters ? iters : ctx->pose_iters;
+    const size_t nn = (size_t)(n2 < 1 ? 1 : n2), hh = (size_t)it2;
+    const size_t sizes[8] = {sizeof(PoseHdr), nn * 32, hh * 72, 21 * 8, kPoseInfoWords * 4, nn * 8, nn * 8, nn};
+    const Layout<8> lay(sizes);
+    char hint[128];
+    snprintf(hint, sizeof hint, "run the call once with at least %d correspondences and %d hypotheses before capturing", n, iters);
+    int rc = reserve(ctx, ctx->buf[pagk_ctx::POSE], lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the pose estimation's workspace", hint);
+    if (rc) return rc;
+    ctx->pose_n = n2, ctx->pose_iters = it2;
+    void *b = ctx->buf[pagk_ctx::POSE].ptr;
+    *w = PoseWs{lay.at<PoseHdr>(b, 0), lay.at<double>(b, 1), lay.at<double>(b, 2), lay.at<double>(b, 3), lay.at<int32_t>(b, 4),
+                lay.at<float>(b, 5), lay.at<float>(b, 6), lay.at<uint8_t>(b, 7)};   // (in the order of PoseWs' members)
+    return PAGK_OK;
+}
+
+// the fits of H and F (they compact the correspondences), then normalisation + hypotheses + recovery on the context stream
+int pose_launch(pagk_ctx *ctx, const pagk_pose_params *p, double f, double cx, double cy, int32_t n, const float *d_pts1,
+                const float *d_pts2, const uint8_t *d_status, double *d_models, double *d_pose, uint8_t *d_mask_H,
+                uint8_t *d_mask_F, uint8_t *d_mask_E, uint8_t *d_mask_pose, int32_t *d_fit_info, int32_t *d_pose_info,
+                int32_t *d_cand_counts, const PoseWs &w)
+{
+    FitWs fw;
+    int rc = fit_launch(ctx, &p->fit, n, d_pts1, d_pts2, d_status, d_models, d_mask_H, d_mask_F, d_fit_info, nullptr, &fw);
+    if (rc) return rc;
+    PoseArgs a;
+    memset(&a, 0, sizeof a);
+    a.p1 = fw.p1, a.p2 = fw.p2, a.idx = fw.idx, a.fit_hdr = fw.hdr, a.hdr = w.hdr, a.qn = w.qn, a.hyp_E = w.hyp_E;
+    a.cand_counts = d_cand_counts, a.pose = d_pose, a.info = d_pose_info, a.mask_E = d_mask_E, a.mask_pose = d_mask_pose;
+    a.seed = p->seed, a.n = n, a.iters = p->iters_E;
+    a.f = f, a.cx = cx, a.cy = cy;
+    const double tn = p->thresh_E / f;
+    a.t2 = tn * tn, a.conf = p->conf_E, a.max_depth = p->max_depth;
+    hipLaunchKernelGGL(k_pose_prep, dim3(n > 0 ? (n + 255) / 256 : 1), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_pose_hyp, dim3((p->iters_E + kPoseHypPerBlock - 1) / kPoseHypPerBlock), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_pose_recover, dim3(1), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+}  // namespace
+
+int pagk_pose_2d2d_device(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t n,
+                          const float *d_pts1, const float *d_pts2, const uint8_t *d_status, double *d_models, double *d_pose,
+                          uint8_t *d_mask_H, uint8_t *d_mask_F, uint8_t *d_mask_E, uint8_t *d_mask_pose, int32_t *d_fit_info,
+                          int32_t *d_pose_info, int32_t *d_cand_counts)
+{
+    if (!ctx || pagk_pose_params_check(params) || !pose_camera_ok(f, cx, cy) || n < 0) return PAGK_E_ARG;
+    if (!d_models || !d_pose || !d_fit_info || !d_pose_info || (n > 0 && (!d_pts1 || !d_pts2))) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PoseWs w;
+    int rc = pose_workspace(ctx, n, params->iters_E, &w);
+    if (rc) return rc;
+    return pose_launch(ctx, params, f, cx, cy, n, d_pts1, d_pts2, d_status, d_models, d_pose, d_mask_H, d_mask_F, d_mask_E,
+                       d_mask_pose, d_fit_info, d_pose_info, d_cand_counts, w);
+}
+
+int pagk_pose_from_matches_device(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t cap_q,
+                                  const float *d_kp_ref, const int32_t *d_nq, int32_t cap_t, const float *d_kp_cur,
+                                  const int32_t *d_nt, const int32_t *d_train_idx, const uint8_t *d_keep, double *d_models,
+                                  double *d_pose, uint8_t *d_mask_H, uint8_t *d_mask_F, uint8_t *d_mask_E, uint8_t *d_mask_pose,
+                                  int32_t *d_fit_info, int32_t *d_pose_info)
+{
+    if (!ctx || pagk_pose_params_check(params) || !pose_camera_ok(f, cx, cy) || cap_q < 1 || cap_t < 1) return PAGK_E_ARG;
+    if (!d_kp_ref || !d_nq || !d_kp_cur || !d_nt || !d_train_idx || !d_keep || !d_models || !d_pose || !d_fit_info || !d_pose_info)
+        return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PoseWs w;
+    int rc = pose_workspace(ctx, cap_q, params->iters_E, &w);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pose_gather, dim3((cap_q + 255) / 256), dim3(256), 0, ctx->stream, cap_q, d_kp_ref, d_nq, cap_t, d_kp_cur,
+                       d_nt, d_train_idx, d_keep, w.g1, w.g2, w.gst);
+    HIPCHK(ctx, hipGetLastError());
+    return pose_launch(ctx, params, f, cx, cy, cap_q, w.g1, w.g2, w.gst, d_models, d_pose, d_mask_H, d_mask_F, d_mask_E,
+                       d_mask_pose, d_fit_info, d_pose_info, nullptr, w);
+}
+
+int pagk_pose_2d2d(pagk_ctx *ctx, const pagk_pose_params *params, double f, double cx, double cy, int32_t n, const float *pts1,
+                   const float *pts2, const uint8_t *status, double *models, double *pose, uint8_t *mask_H, uint8_t *mask_F,
+                   uint8_t *mask_E, uint8_t *mask_pose, int32_t *fit_info, int32_t *pose_info, int32_t *cand_counts)
+{
+    if (!ctx || pagk_pose_params_check(params) || !pose_camera_ok(f, cx, cy) || n < 0) return PAGK_E_ARG;
+    if (!models || !pose || !fit_info || !pose_info || (n > 0 && (!pts1 || !pts2))) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_pose_2d2d");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nn = (size_t)(n < 1 ? 1 : n), cc = (size_t)params->iters_E * 10 * sizeof(int32_t);
+    // pts1 | pts2 | status | mask_H | mask_F | mask_E | mask_pose | models | pose | fit_info | pose_info | cand_counts
+    const size_t sizes[12] = {nn * 8, nn * 8, nn, nn, nn, nn, nn, 27 * 8, 21 * 8, 256, 256, cand_counts ? cc : 4};
+    Staged<12> s(ctx, sizes);
+    int rc;
+    if ((rc = s.open(&ctx->buf[pagk_ctx::POSEIO], "the host-buffer pose estimation's scratch")) ||
+        (rc = s.in(0, pts1, (size_t)n * 8)) || (rc = s.in(1, pts2, (size_t)n * 8)) || (rc = s.in(2, status, (size_t)n)))
+        return rc;
+    rc = pagk_pose_2d2d_device(ctx, params, f, cx, cy, n, s.at<float>(0), s.at<float>(1), status ? s.at<uint8_t>(2) : nullptr,
+                               s.at<double>(7), s.at<double>(8), s.at<uint8_t>(3), s.at<uint8_t>(4), s.at<uint8_t>(5),
+                               s.at<uint8_t>(6), s.at<int32_t>(9), s.at<int32_t>(10), cand_counts ? s.at<int32_t>(11) : nullptr);
+    if (rc || (rc = s.out(7, models, 27 * sizeof(double))) || (rc = s.out(8, pose, 21 * sizeof(double))) ||
+        (rc = s.out(9, fit_info, PAGK_FIT_INFO_WORDS * sizeof(int32_t))) ||
+        (rc = s.out(10, pose_info, PAGK_POSE_INFO_WORDS * sizeof(int32_t))) || (rc = s.out(3, mask_H, (size_t)n)) ||
+        (rc = s.out(4, mask_F, (size_t)n)) || (rc = s.out(5, mask_E, (size_t)n)) || (rc = s.out(6, mask_pose, (size_t)n)) ||
+        (rc = s.out(11, cand_counts, cc)))
+        return rc;
+    return s.finish();
+}
+
 // ---- NCC nearest-neighbour matching ---------------------------------
 static int near_neighbors_launch(pagk_ctx *ctx, const FrameSlot &sr, const FrameSlot &sc, int32_t half_patch, int32_t n,
                                  const float *d_keys_ref, const float *d_pt_predict_un, const uint8_t *d_status,
@@ -3715,12 +3862,12 @@ int pagk_selftest_divide(pagk_ctx *ctx, int32_t n, const double *num, const doub
 int pagk_selftest_fit_samples(pagk_ctx *ctx, uint64_t seed, int32_t model, int32_t m, int32_t first, int32_t count,
                               int32_t *idx)
 {
-    if (!ctx || (model != 0 && model != 1) || m < 1 || first < 0 || count < 0 || !idx) return PAGK_E_ARG;
+    if (!ctx || model < 0 || model > 2 || m < 1 || first < 0 || count < 0 || !idx) return PAGK_E_ARG;
     if ((int64_t)first + count > (int64_t)PAGK_FIT_MAX_ITERS) return PAGK_E_ARG;
     NOT_WHILE_CAPTURING(ctx, "pagk_selftest_fit_samples");
     if (count == 0) return PAGK_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t sizes[1] = {(size_t)count * (model ? 8 : 4) * sizeof(int32_t)};
+    const size_t sizes[1] = {(size_t)count * (model == 2 ? 5 : model ? 8 : 4) * sizeof(int32_t)};
     Staged<1> s(ctx, sizes);
     int rc = s.open(nullptr, nullptr);
     if (rc) return rc;

@@ -297,6 +297,37 @@ def orb_match_pair(img_ref, img_cur, n_features: int, pattern, fast=None, orb=No
     return out
 
 
+# ---- the two-view pose of a frame pair (src/ORBDetectAndDespMatcher.cpp:84-108), array in, array out ----
+def _focal_and_centre(K):
+    """(mfx + mfy) / 2 and (mcx, mcy) of a 3 x 3 camera matrix, as PoseEstimation2d2d passes them (:97, :105)."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    return (K[0, 0] + K[1, 1]) / 2.0, float(K[0, 2]), float(K[1, 2])
+
+
+def pose_estimation_2d2d(pts1, pts2, K, status=None, params=None, ctx=None) -> dict:
+    """ORBDetectAndDespMatcher::PoseEstimation2d2d by the library's definition (pagk_pose_2d2d): H21, H12, F21 as
+    pagk_geometry_fit fits them, the essential matrix by the deterministic five-point RANSAC, R and t by the cheirality test
+    -> dict(H21, H12, F21, E, R, t, mask_H, mask_F, mask_E, mask_pose, fit_info, pose_info, info: the pose words by name)."""
+    f, cx, cy = _focal_and_centre(K)
+    return _device_context(ctx).pose_2d2d(pts1, pts2, f, cx, cy, status, params)
+
+
+def orb_pose_pair(img_ref, img_cur, n_features: int, pattern, K, fast=None, orb=None, params=None, ctx=None) -> dict:
+    """FindFeatureMatches followed by PoseEstimation2d2d, the two calls both front-ends make per frame pair: orb_match_pair,
+    then pose_estimation_2d2d on points1[q] = ref keypoint q, points2[q] = cur keypoint train_idx[q] with status = keep
+    (:86-91) -> the result of orb_match_pair plus `pose` (the dict of pose_estimation_2d2d), pts1, pts2 and status."""
+    c = _device_context(ctx)
+    out = orb_match_pair(img_ref, img_cur, n_features, pattern, fast, orb, c)
+    kp1, kp2 = out["ref"]["keypoints"], out["cur"]["keypoints"]
+    tr = np.asarray(out["train_idx"], np.int64)
+    st = (np.asarray(out["keep"]) != 0) & (tr >= 0) & (tr < len(kp2))
+    pts2 = np.zeros_like(kp1)
+    pts2[st] = kp2[tr[st]]
+    out.update(pose=pose_estimation_2d2d(kp1, pts2, K, st.astype(np.uint8), params, c), pts1=kp1, pts2=pts2,
+               status=st.astype(np.uint8))
+    return out
+
+
 # ---- pyramidal Lucas-Kanade, the image-only baseline of the comparison (src/gyro_aided_tracker.cpp:353-380), ----
 # ---- array in, array out ----
 def lk_track(img_ref, img_cur, pts, lk=None, ctx=None) -> dict:
