@@ -257,6 +257,27 @@ int pagk_last_handover(pagk_ctx *ctx);
  * iterations per feature and level the context's launches have run.  No counterpart in the reference.  Synchronises the context's stream. */
 int pagk_priority_threshold(pagk_ctx *ctx);
 
+/* The hint of the same priorities (csrc/pagk_prio.h -- no arithmetic effect).  Every launch of the 4-wave kernels stores, per feature
+ * SLOT (index into the arrays of the call), the iterations the feature ran; in the context's next launch a slot whose count exceeded
+ * the threshold outranks its neighbours from its first iteration -- a tracker follows the same patch frame after frame, and last
+ * frame's straggler is the best forecast of this frame's.  The forecast holds only while index i still means the same feature:
+ *   - the host-buffer calls (pagk_track, pagk_track_pyr, pagk_track_sharded) install new arrays: they clear the hints, read none and
+ *     store none;
+ *   - a caller of the *_device calls that writes NEW features into its device arrays calls pagk_prio_hint_reset (stream order,
+ *     capturable); one that keeps a feature at its index from frame to frame (status_in = 0 for the lost ones) calls nothing.
+ * A stale or wrong hint costs issue order, never a bit of a result.  PAGK_PRIO_HINT in the environment of pagk_create sets the
+ * threshold (a whole number; 0 = off; 14 by default).  It is stated for three pyramid levels: a launch of L levels compares with
+ * threshold * L / 3, rounded up; a launch of no more workgroups than the device has CUs stores its counts and boosts nobody.  _get / _set copy the first n hints to / from HOST memory and synchronise (diagnostics, tests).
+ * The array grows with the largest launch, and it may not grow inside a capture or while a graph of the context is alive: run the
+ * largest *_device launch once directly BEFORE capturing (as for the other workspaces) -- a launch that meets too small an array
+ * there is not refused, it runs without reading or storing hints.  A launch that selects another kernel than the 4-wave one at four
+ * workgroups per CU (1025-1280 and 2500+ features, the other variants) leaves the array as it was: the next 4-wave launch reads older counts.
+ * No counterpart in the reference. */
+int pagk_prio_hint_threshold(pagk_ctx *ctx);
+int pagk_prio_hint_reset(pagk_ctx *ctx);
+int pagk_prio_hint_get(pagk_ctx *ctx, int32_t n, int32_t *hints);
+int pagk_prio_hint_set(pagk_ctx *ctx, int32_t n, const int32_t *hints);
+
 /* Concurrency hint for the automatic selection: the caller runs `streams` contexts like this one at the same time on
  * this device (one PatchMatch per camera stream, BASELINE configs[4]: src/patch_match.cpp:79-142 called from several
  * threads).  The launch-size thresholds above are then applied to streams * n: a launch that would get a latency

@@ -415,6 +415,15 @@ def declare(lib) -> None:
         lib.pagk_selftest_divide.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
         lib.pagk_selftest_solve.restype = C.c_int
         lib.pagk_selftest_solve.argtypes = [vp, i32, vp, vp, C.c_uint32, vp, vp, vp, vp]
+    if hasattr(lib, "pagk_prio_hint_reset"):   # (an older build given through PAGK_LIB for an A/B run has no hint)
+        lib.pagk_prio_hint_threshold.restype = C.c_int
+        lib.pagk_prio_hint_threshold.argtypes = [vp]
+        lib.pagk_prio_hint_reset.restype = C.c_int
+        lib.pagk_prio_hint_reset.argtypes = [vp]
+        lib.pagk_prio_hint_get.restype = C.c_int
+        lib.pagk_prio_hint_get.argtypes = [vp, i32, vp]
+        lib.pagk_prio_hint_set.restype = C.c_int
+        lib.pagk_prio_hint_set.argtypes = [vp, i32, vp]
     if hasattr(lib, "pagk_priority_threshold"):
         lib.pagk_priority_threshold.restype = C.c_int
         lib.pagk_priority_threshold.argtypes = [vp]
@@ -473,6 +482,7 @@ EXPORTED_SYMBOLS = [
     "pagk_multi_allgather", "pagk_track_sharded", "pagk_selftest_divide", "pagk_selftest_solve",
     "pagk_selftest_repeat_sum", "pagk_check_launch", "pagk_track_device_batch", "pagk_frame_set_device_batch", "pagk_priority_threshold",
     "pagk_multi_comm_count", "pagk_has_variant",
+    "pagk_prio_hint_threshold", "pagk_prio_hint_reset", "pagk_prio_hint_get", "pagk_prio_hint_set",
     "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
     "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
     "pagk_pose_params_default", "pagk_pose_params_check", "pagk_pose_2d2d_device", "pagk_pose_from_matches_device",
@@ -1550,6 +1560,24 @@ class Context:
         if rc < 0:
             self._check(rc, "pagk_priority_threshold")
         return rc
+
+    def prio_hint_threshold(self) -> int:
+        """Threshold of the 4-wave kernels' hint (csrc/pagk_prio.h; PAGK_PRIO_HINT, 0 = off)."""
+        return int(self.lib.pagk_prio_hint_threshold(self.h))
+
+    def prio_hint_reset(self):
+        """New features were written into the device arrays: forget what the slots' previous features ran (stream order)."""
+        if hasattr(self.lib, "pagk_prio_hint_reset"):   # (an older build through PAGK_LIB: nothing to forget)
+            self._check(self.lib.pagk_prio_hint_reset(self.h), "pagk_prio_hint_reset")
+
+    def prio_hint_get(self, n: int) -> np.ndarray:
+        out = np.zeros(max(n, 0), np.int32)
+        self._check(self.lib.pagk_prio_hint_get(self.h, n, out.ctypes.data_as(C.c_void_p)), "pagk_prio_hint_get")
+        return out
+
+    def prio_hint_set(self, hints) -> None:
+        h = np.ascontiguousarray(hints, np.int32)
+        self._check(self.lib.pagk_prio_hint_set(self.h, int(h.shape[0]), h.ctypes.data_as(C.c_void_p)), "pagk_prio_hint_set")
 
     def last_variant(self) -> int:
         return int(self.lib.pagk_last_variant(self.h))

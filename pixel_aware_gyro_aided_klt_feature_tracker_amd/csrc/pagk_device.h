@@ -107,6 +107,11 @@ struct TrackArgs {
     // workgroups that finish early and read -- one load, consumed a level set-up later -- by every workgroup of the NEXT launches
     unsigned long long *prio_stats;
     const int *prio_kbuf;
+    // the hint (pagk_prio.h): the iterations each feature slot ran in this context's previous 4-wave launch, one int per feature;
+    // a workgroup whose entry exceeds prio_hint_t (0: hint off) is behind from its first iteration.  In and out may be the same array.
+    const int *prio_hint_in;
+    int *prio_hint_out;
+    int prio_hint_t;
     int has_gyro, illum, use_affine, penalty, calc_ncc;
     uint32_t solver;        // pagk_params::solver_variant (SV_* bits)
     float lam_invlog;       // mLambda * mInvLogMaxDist            (f32 product, :305)

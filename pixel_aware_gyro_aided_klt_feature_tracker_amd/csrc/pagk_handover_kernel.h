@@ -142,6 +142,9 @@ struct HandoverArgs {
     int32_t *index_in_last;
     uint8_t *live, *mask;
     int32_t *state;
+    // the tracking launches' per-slot hints (pagk_prio.h), compacted IN PLACE with the survivors; nullptr / 0: none
+    int32_t *prio_hint;
+    int32_t prio_hint_n;
 };
 
 // mMask = ones: 16 bytes per store; `bytes` is a multiple of 16 (the buffer is padded), the tail is stored bytewise
@@ -217,6 +220,9 @@ __global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a)
     for (int c0 = 0; c0 < a.cap; c0 += 1024) {
         const int i = c0 + tid;
         const bool take = i < a.cap && a.status[i] != 0;
+        // (in place: a group's hints are read in front of the scan's barriers and stored behind them, to slots o <= i that no
+        // later group reads)
+        const int32_t hint = (take && i < a.prio_hint_n) ? a.prio_hint[i] : 0;
         int32_t tot;
         const int32_t o = m + handover_scan(take, wtot, lane, wave, tot);
         if (take) {
@@ -225,6 +231,7 @@ __global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a)
             a.keys_un[2 * o] = xu, a.keys_un[2 * o + 1] = yu;
             if (a.keys_normal) a.keys_normal[2 * o] = (xu - a.cx) * a.fx_inv, a.keys_normal[2 * o + 1] = (yu - a.cy) * a.fy_inv;  // :128-129
             a.index_in_last[o] = i;
+            if (o < a.prio_hint_n) a.prio_hint[o] = hint;
         }
         m += tot;
     }
@@ -267,6 +274,7 @@ __global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a)
     const int32_t added = topup ? (seen < n_new ? seen : n_new) : 0;
     const int32_t total = m + added;
     for (int i = tid; i < a.cap; i += 1024) {
+        if (i >= m && i < a.prio_hint_n) a.prio_hint[i] = 0;   // topped-up and unused slots: no forecast
         a.live[i] = i < total ? 1 : 0;
         if (i >= total) {
             a.keys[2 * i] = a.keys[2 * i + 1] = 0.0f;

@@ -19,6 +19,7 @@
 #include "pagk_pose_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
+#include "pagk_prio_env.h"
 
 using namespace pagk;
 
@@ -78,6 +79,7 @@ struct pagk_ctx {
         QUAD_WS,       // k_track_quad: iteration-invariant img1 samples, 4 * NCH * 64 floats per wave
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
+        PRIO_HINT,     // the 4-wave kernels' hint (pagk_prio.h): one int32 per feature slot of the largest launch so far
         kBufs
     };
     DevBuf buf[kBufs];
@@ -163,6 +165,7 @@ struct pagk_ctx {
     int block5_min_features = 2500;      // PAGK_BLOCK5_MIN: the 4-wave kernel in its five-workgroups-per-CU build (h = 10)
     int prio_k = 4;                      // PAGK_PRIO_K: iterations per pyramid level beyond which a 4-wave workgroup counts as behind (pagk_prio.h); 0 = rule off
     unsigned long long *prio_stats = nullptr;  // PAGK_PRIO_K=auto: device block [iterations, feature-levels (u64 each), K (int)]
+    int prio_hint_t = kPrioHintDefault;  // PAGK_PRIO_HINT: a feature slot whose previous launch ran more iterations than this starts behind (pagk_prio.h); 0 = hint off
     bool block5_window = true;           // ... also for launches that only five workgroups per CU hold in one round (off when PAGK_BLOCK5_MIN is set)
     int levels_min_features = 6000;      // PAGK_LEVELS_MIN: ... one level per wave (a context alone on the device)
     int levels_shift = 0;                // PAGK_LEVELS_XCD_SHIFT (tests): waves start with another XCD's ticket sequence
@@ -906,12 +909,39 @@ int launch_block(pagk_ctx *ctx, const TrackKernels &k, bool lean, int n, const T
     return PAGK_OK;
 }
 
+// The hint array of the 4-wave kernels (pagk_prio.h): one int32 per feature slot, what the slot's feature ran in the previous
+// launch.  It grows -- zeroed: no forecast -- with the largest launch; where it may not grow (inside a capture, under a live
+// graph whose nodes hold the old pointer) the launch runs without a hint, which costs it issue order and nothing else.
+int prio_hint_attach(pagk_ctx *ctx, int n, TrackArgs *a)
+{
+    DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    const size_t need = (size_t)n * sizeof(int32_t);
+    if (need > hb.bytes) {
+        if (in_capture(ctx)) return PAGK_OK;
+        for (int k = 0; k < pagk_ctx::kGraphs; k++)
+            if (ctx->graph_execs[k]) return PAGK_OK;
+        if (int rc = reserve(ctx, hb, need, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the priority hints", kLargestLaunchFirst)) return rc;
+        HIPCHK(ctx, hipMemsetAsync(hb.ptr, 0, hb.bytes, ctx->stream));
+    }
+    a->prio_hint_in = a->prio_hint_out = static_cast<int *>(hb.ptr);
+    return PAGK_OK;
+}
+
+// New features in the slots: what the slots' previous features ran says nothing about them (stream order).
+int prio_hint_clear(pagk_ctx *ctx)
+{
+    DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    if (hb.ptr) HIPCHK(ctx, hipMemsetAsync(hb.ptr, 0, hb.bytes, ctx->stream));
+    return PAGK_OK;
+}
+
 // pyr / pyr_blocks / pyr_done: optionally, another slot's pyramid to be built by trailing workgroups of the
 // tracking launch (k_track_block_pyr).  Honoured when the 4-wave kernel is the one selected; *pyr_done tells the
 // caller whether it was (otherwise the caller launches the pyramid itself).
 int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const FrameSlot &sc, int n,
                  const float *d_pt_ref, const float *d_pt_init, const float *d_affine, const uint8_t *d_status,
-                 const pagk_outputs *o, const PyrArgs *pyr = nullptr, int pyr_blocks = 0, bool *pyr_done = nullptr)
+                 const pagk_outputs *o, const PyrArgs *pyr = nullptr, int pyr_blocks = 0, bool *pyr_done = nullptr,
+                 bool hinted = true)
 {
     if (pyr_done) *pyr_done = false;
     TrackArgs a;
@@ -943,6 +973,12 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
     a.prio_stats = ctx->prio_stats;
     a.prio_kbuf = ctx->prio_stats ? reinterpret_cast<const int *>(ctx->prio_stats + 2) : nullptr;
     a.lv_error = ctx->lv_error_dev;   // (the pipelined 4-wave body raises it too: a solve that gave up waiting for its sums)
+    // ... and only where there is somebody to outrank: with a workgroup per CU or fewer, priority 3 throughout merely takes the
+    // by-phase order away from the workgroup's own four waves (250 features: 55.1 -> 55.8 us).  The counts are stored all the same.
+    // The threshold is stated for three pyramid levels, the shape it was chosen on; a feature's count grows with the levels it
+    // runs -- K counts per level entered for the same reason -- so a launch of L levels compares with T L / 3, rounded up
+    // (configs[2], four levels: 14 flags a third of the features, 1.3 per CU, and the boost is diluted; 19 flags 6 %).
+    a.prio_hint_t = n > ctx->cus ? (int)(((long long)ctx->prio_hint_t * p->pyramids + 2) / 3) : 0;
 
     if (ctx->ev_trk[0] && !in_capture(ctx)) HIPCHK(ctx, hipEventRecord(ctx->ev_trk[0], ctx->stream));
     if (n > 0) {
@@ -963,7 +999,12 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
             case 5:
             case 7: rc = launch_quad(ctx, p, k, lean, variant == 7, n, a); break;
             case 6: rc = launch_rows(ctx, k, n, a); break;
-            default: rc = launch_block(ctx, k, lean, n, a, pyr, pyr_blocks, pyr_done); break;
+            default:
+                // (hinted: false for the host-buffer calls -- their arrays are new features in a new order every call, a count
+                // kept for them would forecast nothing, and they clear the array instead: prio_hint_clear)
+                if (hinted && (rc = prio_hint_attach(ctx, n, &a))) break;
+                rc = launch_block(ctx, k, lean, n, a, pyr, pyr_blocks, pyr_done);
+                break;
         }
         if (rc) return rc;
         HIPCHK(ctx, e);
@@ -1043,6 +1084,7 @@ int track_host_common(pagk_ctx *ctx, const pagk_params *p, int n, const float *p
         memcpy(hb + offs[3], status_in, nn);
         HIPCHK(ctx, hipMemcpyAsync(db, hb, fp.in_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
+    if ((rc = prio_hint_clear(ctx))) return rc;   // the arrays above are new features, whatever the slots held
     pagk_outputs dout = fp.out;
     if (!out->pt_dist) dout.pt_dist = nullptr;
     if (!out->pix_err) dout.pix_err = nullptr;
@@ -1050,7 +1092,7 @@ int track_host_common(pagk_ctx *ctx, const pagk_params *p, int n, const float *p
     if (!out->ncc) dout.ncc = nullptr;
     if (!out->iters) dout.iters = nullptr;
     rc = launch_track(ctx, p, sr, sc, n, fp.pt_ref, pt_init ? fp.pt_init : nullptr, affine ? fp.affine : nullptr,
-                      fp.status_in, &dout);
+                      fp.status_in, &dout, nullptr, 0, nullptr, false);
     if (rc) return rc;
     if (n > 0)  // every output array with ONE copy into the pinned mirror, scattered to the caller after the sync
         HIPCHK(ctx, hipMemcpyAsync(hb + fp.in_bytes, db + fp.in_bytes, fp.lay.total - fp.in_bytes, hipMemcpyDeviceToHost,
@@ -1186,6 +1228,7 @@ int pagk_create(pagk_ctx **out, int device)
     } else if (getenv("PAGK_PRIO_K")) {
         ctx->prio_k = atoi(getenv("PAGK_PRIO_K")) < 0 ? 0 : atoi(getenv("PAGK_PRIO_K"));
     }
+    if (getenv("PAGK_PRIO_HINT")) ctx->prio_hint_t = prio_hint_parse(getenv("PAGK_PRIO_HINT"), ctx->prio_hint_t);
     if (getenv("PAGK_LEVELS_XCD_SHIFT")) ctx->levels_shift = atoi(getenv("PAGK_LEVELS_XCD_SHIFT")) & 7;
     if (getenv("PAGK_LEVELS_SHARED")) ctx->levels_shared = atoi(getenv("PAGK_LEVELS_SHARED")) != 0;
     if (getenv("PAGK_QUAD_BUDGET")) ctx->quad_budget = atoi(getenv("PAGK_QUAD_BUDGET"));
@@ -1300,6 +1343,47 @@ int pagk_priority_threshold(pagk_ctx *ctx)
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (int lr = lv_check(ctx)) return lr;
     return k;
+}
+
+// The hint threshold of the 4-wave kernels (csrc/pagk_prio.h; 0 = off).
+int pagk_prio_hint_threshold(pagk_ctx *ctx) { return ctx ? ctx->prio_hint_t : PAGK_E_ARG; }
+
+// The caller wrote NEW features into the device arrays it tracks with: forget what the slots' previous features ran.
+// In stream order, capturable.  (The host-buffer entry points do this themselves.)
+int pagk_prio_hint_reset(pagk_ctx *ctx)
+{
+    if (!ctx) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return prio_hint_clear(ctx);
+}
+
+// The first n hints to host memory (diagnostics, tests; synchronises).  Slots past the array's size read 0.
+int pagk_prio_hint_get(pagk_ctx *ctx, int32_t n, int32_t *hints)
+{
+    if (!ctx || n < 0 || (n > 0 && !hints)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_prio_hint_get");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    const size_t have = hb.bytes / sizeof(int32_t) < (size_t)n ? hb.bytes / sizeof(int32_t) : (size_t)n;
+    memset(hints, 0, (size_t)n * sizeof(int32_t));
+    if (have) HIPCHK(ctx, hipMemcpyAsync(hints, hb.ptr, have * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
+}
+
+// Install n hints from host memory (tests, a host that keeps its own forecast; synchronises).  The array grows as a launch of n
+// features would grow it; slots past n read 0.
+int pagk_prio_hint_set(pagk_ctx *ctx, int32_t n, const int32_t *hints)
+{
+    if (!ctx || n < 0 || (n > 0 && !hints)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_prio_hint_set");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    if (int rc = reserve(ctx, hb, (size_t)n * sizeof(int32_t), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the priority hints", kLargestLaunchFirst)) return rc;
+    if (int rc = prio_hint_clear(ctx)) return rc;
+    if (n) HIPCHK(ctx, hipMemcpyAsync(hb.ptr, hints, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
 }
 
 // The error word of the level-by-level launches without a synchronisation: for callers that synchronise the stream
@@ -2117,6 +2201,15 @@ bool handover_args_ok(const pagk_params *params, int32_t width, int32_t height, 
            cap >= target_n && cand_cap >= 0 && !std::isnan(new_point_threshold);
 }
 
+// The tracking launches' hints (pagk_prio.h) are per feature SLOT: a survivor that moves to a new slot takes its hint along, a
+// new or an unused slot has none.  The array as it stands when the hand-over is issued (none before the first launch).
+void handover_hint_args(pagk_ctx *ctx, HandoverArgs *a)
+{
+    const DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    a->prio_hint = static_cast<int32_t *>(hb.ptr);
+    a->prio_hint_n = (int32_t)(hb.bytes / sizeof(int32_t));
+}
+
 // the sizes, the rule's constants and the camera model of a hand-over; the pointers are the caller's to fill
 void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
                         int32_t target_n, double new_point_threshold)
@@ -2333,6 +2426,7 @@ int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int
     a.n_cand = d_n_cand, a.cand_un = d_cand_un;
     a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
     a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
+    handover_hint_args(ctx, &a);
     hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
@@ -2582,6 +2676,7 @@ int handover_fast_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width
     a.n_cand = d_info, a.cand_un = ws.cand;
     a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
     a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
+    handover_hint_args(ctx, &a);
     hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,

@@ -592,8 +592,14 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
 
     const float *init = a.has_gyro ? a.pt_init : a.pt_ref;  // :85-89
     float p2x = init[2 * i], p2y = init[2 * i + 1];
+    // the hint of pagk_prio.h belongs to the 4-wave DPP kernel at four workgroups per CU: read and written by the launch's own
+    // workgroups (not by a finisher, not by the two-wave, relaxed-order or five-per-CU builds)
+    [[maybe_unused]] const bool hinted = !MFMA && !RELAXED && PIPE && !resume;
     if (!a.status_in[i]) {  // :173 (block-uniform)
-        if (tid == 0) write_outputs(a, i, p2x, p2y, 0, 0.0f, 0, 0.0f, 0);
+        if (tid == 0) {
+            write_outputs(a, i, p2x, p2y, 0, 0.0f, 0, 0.0f, 0);
+            if (hinted) prio_hint_store(a, i, 0);
+        }
         return;
     }
     float A00 = 1, A01 = 0, A10 = 0, A11 = 1;
@@ -683,7 +689,7 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
 
     int succ = 1, iters = 0;
     [[maybe_unused]] constexpr bool kPrioByWork = NR > 1;  // pagk_prio.h
-    PAGK_PRIO_DECL
+    PAGK_PRIO_DECL(hinted)
     float lastCost = 0.0f;
 #ifdef PAGK_STAMPS
     // diagnostic build only: cycles per phase, summed over iterations, written to a.dbg (a buffer
@@ -1145,6 +1151,7 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
         ncc = (float)((double)sh_f[2] / sqrt((double)(sh_f[3] * sh_f[4]) + 1e-10));
     }
     if (tid == 0) write_outputs(a, i, p2x, p2y, succ, lastCost, 1, ncc, iters);
+    if (tid == 0 && hinted) prio_hint_store(a, i, iters);
     if (tid == 0 && kPrioByWork && !resume) prio_account(a, i, iters, a.n_levels);
 #ifdef PAGK_STAMPS
     if (tid == 0 && a.dbg) {

@@ -387,9 +387,15 @@ int pagk_track_sharded(pagk_multi *pm, const pagk_params *params, const pagk_ima
         o.dist_pred = reinterpret_cast<double *>(sl + off[4]);
         o.ncc = reinterpret_cast<float *>(sl + off[5]);
         o.iters = reinterpret_cast<int32_t *>(sl + off[6]);
+        if ((rc = prio_hint_clear(c))) {   // this rank's block of NEW features (pagk_prio.h: hints are per slot)
+            snprintf(pm->err, sizeof pm->err, "rank %d: %s", k, c->err);
+            drain(k);
+            return rc;
+        }
         rc = launch_track(c, params, c->slots[4], c->slots[5], nk, reinterpret_cast<float *>(db + in_off[0]),
                           pt_init_un ? reinterpret_cast<float *>(db + in_off[1]) : nullptr,
-                          affine ? reinterpret_cast<float *>(db + in_off[2]) : nullptr, db + in_off[3], &o);
+                          affine ? reinterpret_cast<float *>(db + in_off[2]) : nullptr, db + in_off[3], &o, nullptr, 0, nullptr,
+                          false);
         if (rc) {
             snprintf(pm->err, sizeof pm->err, "rank %d: %s", k, c->err);
             drain(k);

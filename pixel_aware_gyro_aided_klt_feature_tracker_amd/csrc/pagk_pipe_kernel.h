@@ -73,7 +73,10 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
     const float *init = a.has_gyro ? a.pt_init : a.pt_ref;  // :85-89
     float p2x = init[2 * i], p2y = init[2 * i + 1];
     if (!a.status_in[i]) {  // :173 (block-uniform)
-        if (tid == 0) write_outputs(a, i, p2x, p2y, 0, 0.0f, 0, 0.0f, 0);
+        if (tid == 0) {
+            write_outputs(a, i, p2x, p2y, 0, 0.0f, 0, 0.0f, 0);
+            if (!resume) prio_hint_store(a, i, 0);
+        }
         return;
     }
     float A00 = 1, A01 = 0, A10 = 0, A11 = 1;
@@ -130,7 +133,7 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
 
     int succ = 1, iters = 0, seq = 0;
     [[maybe_unused]] constexpr bool kPrioByWork = true;  // pagk_prio.h
-    PAGK_PRIO_DECL
+    PAGK_PRIO_DECL(!resume)
     float lastCost = 0.0f;
 #ifdef PAGK_STAMPS
     // diagnostic build only (tools/stamps.py): cycles per phase as wave 0 sees them, summed over iterations.
@@ -536,6 +539,7 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
         ncc = (float)((double)sh_f[2] / sqrt((double)(sh_f[3] * sh_f[4]) + 1e-10));
     }
     if (tid == 0) write_outputs(a, i, p2x, p2y, succ, lastCost, 1, ncc, iters);
+    if (tid == 0 && !resume) prio_hint_store(a, i, iters);
     if (tid == 0 && kPrioByWork && !resume) prio_account(a, i, iters, a.n_levels);
 #ifdef PAGK_STAMPS
     if (lane == 0 && a.dbg) {

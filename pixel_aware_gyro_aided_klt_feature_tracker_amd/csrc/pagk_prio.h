@@ -44,9 +44,27 @@ __device__ __forceinline__ void prio_account(const TrackArgs &a, int i, int iter
         }
     }
 }
+
+// The hint: last launch's stragglers are behind from their FIRST iteration.  The rule above cannot tell the feature that
+// will need 26 iterations from its CU-mates before it has run K per level more than they -- iterations it shares four
+// ways (~8 us of a 74 us launch).  A tracker follows the same patches frame after frame, so the
+// iteration count a feature slot needed on the last pair is a forecast for this one: every workgroup stores its total
+// into TrackArgs::prio_hint_out[feature] at its end (0 for a feature that came in with status 0) and the next launch
+// reads it from prio_hint_in (the same array: a workgroup touches its own entry only).  hint > TrackArgs::prio_hint_t
+// adds kPrioBoost -- beyond any iteration count -- to the left side of the test, so the workgroup runs at priority 3
+// throughout (folding the boost into K instead -- K = -1 for a hinted workgroup, no second scalar through the loop -- keeps the
+// headline kernel's spilled SGPRs at the three they were instead of six and measured 0.5-1 us SLOWER at 250 and 1000 features:
+// not kept); prio_hint_t = 0 (PAGK_PRIO_HINT=0 in the environment of pagk_create) switches the hint off.  A wrong hint
+// costs issue slots, never a bit of the result.  The host scales the threshold with the launch's pyramid levels and passes 0
+// for a launch with nobody to outrank (launch_track, pagk_hip.hip).
+constexpr int kPrioBoost = 1 << 20;
+__device__ __forceinline__ void prio_hint_store(const TrackArgs &a, int i, int iters)
+{
+    if (a.prio_hint_out) a.prio_hint_out[i] = iters;
+}
 }  // namespace pagk
 #if PAGK_PRIO_MODE == 0
-#define PAGK_PRIO_DECL
+#define PAGK_PRIO_DECL(hinted)
 #define PAGK_PRIO_TIER
 #define PAGK_PRIO_RESET
 #define PRIO(n) __builtin_amdgcn_s_setprio(n);
@@ -57,9 +75,14 @@ __device__ __forceinline__ void prio_account(const TrackArgs &a, int i, int iter
 #else
 // (one PLAIN load -- the L2 serves a thousand workgroups; an agent-scope load of one line from all of them queues for 60 us -- beside the prologue's other loads -- the feature's points and affine -- and a scalar from then on: a vector register held
 // through the body costs the generic instantiations a spill)
-#define PAGK_PRIO_DECL   \
-    int tier_now = 0;    \
-    const int prio_kv = !kPrioByWork ? 0 : (a.prio_kbuf ? __builtin_amdgcn_readfirstlane(*a.prio_kbuf) : a.prio_k);
+// The hint (TrackArgs::prio_hint_in, above): `hinted` says whether this body reads one -- a finisher does not.  The same
+// shape of load as K's: plain, beside the prologue's other loads, a scalar from then on.  prio_boost is 0 or kPrioBoost
+// and joins the rule's one comparison; a body whose rule is off (kPrioByWork false, K = 0) never looks at it.
+#define PAGK_PRIO_DECL(hinted)                                                                                       \
+    int tier_now = 0;                                                                                                \
+    const int prio_kv = !kPrioByWork ? 0 : (a.prio_kbuf ? __builtin_amdgcn_readfirstlane(*a.prio_kbuf) : a.prio_k);  \
+    const int prio_boost = (kPrioByWork && (hinted) && a.prio_hint_t > 0 && a.prio_hint_in &&                        \
+                            __builtin_amdgcn_readfirstlane(a.prio_hint_in[i]) > a.prio_hint_t) ? kPrioBoost : 0;
 #define PAGK_STR2(x) #x
 #define PAGK_STR(x) PAGK_STR2(x)
 // (wave-uniform: iters, level and the kernel argument are the same in every lane; readfirstlane says so to the compiler, and
@@ -67,7 +90,7 @@ __device__ __forceinline__ void prio_account(const TrackArgs &a, int i, int iter
 // The priority is switched once per transition: two scalar instructions on the path of an iteration without one.
 #define PAGK_PRIO_TIER                                                                                              \
     {                                                                                                               \
-        const int tier = (prio_kv > 0 && __builtin_amdgcn_readfirstlane(iters - prio_kv * (a.n_levels - level)) > 0) ? 3 : 0; \
+        const int tier = (prio_kv > 0 && __builtin_amdgcn_readfirstlane(iters + prio_boost - prio_kv * (a.n_levels - level)) > 0) ? 3 : 0; \
         asm volatile("s_cmp_eq_u32 %0, %1\n\t"                                                                      \
                      "s_cbranch_scc1 2f\n\t"                                                                        \
                      "s_cmp_eq_u32 %1, 0\n\t"                                                                       \

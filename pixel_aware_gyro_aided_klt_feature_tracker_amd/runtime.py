@@ -149,6 +149,7 @@ class ResidentTracker:
                                       (self.d_affine, affine, 4), (self.d_status, status_in, 1)):
                     if hi > lo:
                         dst[:hi - lo].copy_(torch.from_numpy(np.ascontiguousarray(a[lo:hi])).to(self.dev))
+                self.ctx.prio_hint_reset()   # new features in the slots: last launch's iteration counts forecast nothing
             self._settle()
             return
         self.d_pt_ref = up(pt_ref, 2)
@@ -158,6 +159,8 @@ class ResidentTracker:
         self.out = distributed.alloc_device_outputs(m, self.dev)
         self._n_alloc = self.n
         self._drop_graph()
+        with torch.cuda.stream(self.main):
+            self.ctx.prio_hint_reset()
         self._settle()
 
     def rebuild_current_pyramid(self, slot: int = 1):

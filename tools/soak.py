@@ -1,11 +1,13 @@
 """One-off soak: the randomized parity sweep of tests/test_parity_gpu.py over many more seeds.
-Usage: python tools/soak.py [first_seed] [count]"""
+Usage: python tools/soak.py [first_seed] [count]
+PAGK_SOAK_HINTS=1: every case also runs the 4-wave kernels on device-resident features with RANDOM priority hints injected
+(csrc/pagk_prio.h: any hint must leave every bit where it was), twice -- the second launch reads the hints the first one left."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from oracle import pagk_oracle as orc
-from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi
+from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, distributed, runtime
 import test_parity_gpu as T
 from util import assert_parity
 first, count = int(sys.argv[1]) if len(sys.argv) > 1 else 1000, int(sys.argv[2]) if len(sys.argv) > 2 else 300
@@ -39,6 +41,21 @@ for seed in range(first, first + count):
         except AssertionError as e:
             bad += 1
             print("MISMATCH", e, flush=True)
+    if os.environ.get("PAGK_SOAK_HINTS"):
+        rt = runtime.ResidentTracker(p, device=0)
+        rt.load_pair(w.img_ref, w.img_cur)
+        rt.set_features(w.pt_ref, w.pt_init, w.affine, w.status_in)
+        rt.ctx.prio_hint_set(np.random.default_rng(seed ^ 0x41A7).integers(0, 60, w.n).astype(np.int32))
+        for turn in ("random hints", "the hints that launch left"):
+            rt.step(mode="serial")
+            rt.synchronize()
+            got = {name: rt.out[name][:w.n].cpu().numpy() for name, _, _ in distributed.FIELDS}
+            try:
+                assert_parity(got, ref, w.n, exact=True, what=f"seed {seed} resident, variant {rt.ctx.last_variant()}, {turn}")
+            except AssertionError as e:
+                bad += 1
+                print("MISMATCH", e, flush=True)
+        rt.close()
     feats += w.n
     if (seed - first) % 50 == 49:
         print(f"{seed - first + 1} cases, {feats} features, {bad} mismatches", flush=True)

@@ -1,6 +1,8 @@
 """Diagnostic: the slowest features of a launch of the pipelined 4-wave kernel -- when their workgroup started, when it ended, cycles
 per iteration -- and the launch's ramp (when the last workgroup started).  Separate -DPAGK_STAMPS build (inflates every phase; never
-quote its run time).  Usage: PAGK_N=1000 [PAGK_STAMPS_FLAGS="-DPAGK_PRIO_MODE=0"] python tools/stamps_stragglers.py"""
+quote its run time).  Usage: PAGK_N=1000 [PAGK_STAMPS_FLAGS="-DPAGK_PRIO_MODE=0"] python tools/stamps_stragglers.py
+PAGK_STAMPS_RESIDENT=1: the features stay on the device (runtime.ResidentTracker), so the third launch reads the hints the second one left
+(csrc/pagk_prio.h; PAGK_PRIO_HINT=0 for the same launches without) -- the host-buffer call clears them."""
 import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,9 +27,24 @@ for n in [int(v) for v in os.environ.get("PAGK_N", "1000").split(",")]:
     os.environ["PAGK_DBG_PTR"] = str(dbg.data_ptr())
     ctx = capi.Context(0)
     p = capi.make_params(half_patch=10, iterations=30, pyramids=3, has_gyro=w.has_gyro, camera=w.camera)
-    for _ in range(3):
-        dbg.zero_()
-        ctx.track(p, w.img_ref, w.img_cur, w.pt_ref, w.pt_init, w.affine, w.status_in)
+    if os.environ.get("PAGK_STAMPS_RESIDENT"):
+        from pixel_aware_gyro_aided_klt_feature_tracker_amd import runtime
+        ctx.close()
+        rt = runtime.ResidentTracker(p, device=0)
+        ctx = rt.ctx
+        rt.load_pair(w.img_ref, w.img_cur)
+        rt.set_features(w.pt_ref, w.pt_init, w.affine, w.status_in)
+        for _ in range(3):
+            rt.synchronize()
+            dbg.zero_()
+            torch.cuda.synchronize()
+            rt.step(mode="serial")
+        rt.synchronize()
+        print(f"   resident features, PAGK_PRIO_HINT threshold {ctx.prio_hint_threshold()}")
+    else:
+        for _ in range(3):
+            dbg.zero_()
+            ctx.track(p, w.img_ref, w.img_cur, w.pt_ref, w.pt_init, w.affine, w.status_in)
     trk, pyr = ctx.last_kernel_ms()
     d = dbg.cpu().numpy().reshape(n, 16).astype(np.float64)
     it = np.maximum(d[:, 6], 1)
