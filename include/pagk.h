@@ -278,6 +278,26 @@ int pagk_prio_hint_reset(pagk_ctx *ctx);
 int pagk_prio_hint_get(pagk_ctx *ctx, int32_t n, int32_t *hints);
 int pagk_prio_hint_set(pagk_ctx *ctx, int32_t n, const int32_t *hints);
 
+/* The dispatch order of the 4-wave kernels (csrc/pagk_order.h): workgroup b of a launch runs the feature with the b-th largest
+ * hint -- a stable counting sort of the hints clamped to [0, 127], descending, ties in index order -- so that the features that
+ * ran longest last time start first and on different compute units.  It decides when a feature runs and beside whom, never a bit
+ * of a result.  The array is built on the device by one extra workgroup of the pyramid launch (pagk_frame_set_device,
+ * pagk_frame_upload*, pagk_frame_rectify*) that precedes the tracking launch on the same stream, for the n of the context's last
+ * *_device 4-wave launch (or of pagk_prio_hint_set), when that n is above the device's CU count and at most 8192.  A launch uses
+ * it only when such a build for exactly its n was enqueued on its stream since the last 4-wave launch or hint write; otherwise --
+ * hints cleared, host-buffer calls, another stream, a pyramid built by pagk_track_device_fused or pagk_frame_set_device_batch, an
+ * array that could not grow under a live graph -- it runs in index order.  The array is bound to the stream of its last build,
+ * reader or graph replay until the host has waited for that stream (pagk_sync, pagk_graph_destroy, the _get calls): pyramids and
+ * launches on other streams meanwhile leave it alone.  Inside pagk_graph_begin's capture the decision is recorded with the graph; a
+ * replayed [pagk_frame_set_device -> pagk_track_device] graph rebuilds and uses the order on every replay, and a replay on another
+ * stream than the one the array is bound to waits for the device first.  Any other capture of the stream neither builds nor uses it.
+ * PAGK_DISPATCH_ORDER=0 in the environment of pagk_create switches it off (_enabled: 1 / 0).  _get copies the first n entries of
+ * the array as it is on the device to HOST memory and synchronises (diagnostics, tests; not capturable; entries the array does
+ * not hold read as the identity); *in_force (may be NULL) is 1 when a 4-wave *_device launch of n features enqueued next on the
+ * current stream would use the array.  No counterpart in the reference. */
+int pagk_dispatch_order_enabled(pagk_ctx *ctx);
+int pagk_dispatch_order_get(pagk_ctx *ctx, int32_t n, int32_t *order, int32_t *in_force);
+
 /* Concurrency hint for the automatic selection: the caller runs `streams` contexts like this one at the same time on
  * this device (one PatchMatch per camera stream, BASELINE configs[4]: src/patch_match.cpp:79-142 called from several
  * threads).  The launch-size thresholds above are then applied to streams * n: a launch that would get a latency

@@ -424,6 +424,11 @@ def declare(lib) -> None:
         lib.pagk_prio_hint_get.argtypes = [vp, i32, vp]
         lib.pagk_prio_hint_set.restype = C.c_int
         lib.pagk_prio_hint_set.argtypes = [vp, i32, vp]
+    if hasattr(lib, "pagk_dispatch_order_get"):   # (likewise: an older build has no dispatch order)
+        lib.pagk_dispatch_order_enabled.restype = C.c_int
+        lib.pagk_dispatch_order_enabled.argtypes = [vp]
+        lib.pagk_dispatch_order_get.restype = C.c_int
+        lib.pagk_dispatch_order_get.argtypes = [vp, i32, vp, vp]
     if hasattr(lib, "pagk_priority_threshold"):
         lib.pagk_priority_threshold.restype = C.c_int
         lib.pagk_priority_threshold.argtypes = [vp]
@@ -483,6 +488,7 @@ EXPORTED_SYMBOLS = [
     "pagk_selftest_repeat_sum", "pagk_check_launch", "pagk_track_device_batch", "pagk_frame_set_device_batch", "pagk_priority_threshold",
     "pagk_multi_comm_count", "pagk_has_variant",
     "pagk_prio_hint_threshold", "pagk_prio_hint_reset", "pagk_prio_hint_get", "pagk_prio_hint_set",
+    "pagk_dispatch_order_enabled", "pagk_dispatch_order_get",
     "pagk_fit_params_default", "pagk_geometry_fit_device", "pagk_geometry_fit", "pagk_geometry_validation_device",
     "pagk_geometry_validation_fit", "pagk_selftest_fit_samples",
     "pagk_pose_params_default", "pagk_pose_params_check", "pagk_pose_2d2d_device", "pagk_pose_from_matches_device",
@@ -1578,6 +1584,20 @@ class Context:
     def prio_hint_set(self, hints) -> None:
         h = np.ascontiguousarray(hints, np.int32)
         self._check(self.lib.pagk_prio_hint_set(self.h, int(h.shape[0]), h.ctypes.data_as(C.c_void_p)), "pagk_prio_hint_set")
+
+    def dispatch_order_enabled(self) -> bool:
+        """The 4-wave kernels' dispatch order (csrc/pagk_order.h) is on (PAGK_DISPATCH_ORDER=0 in the environment of the context's
+        creation switches it off)."""
+        return bool(self.lib.pagk_dispatch_order_enabled(self.h))
+
+    def dispatch_order_get(self, n: int):
+        """(order, in_force): the first n entries of the order array as they are on the device, and whether a 4-wave launch of n
+        features enqueued next on the current stream would use it.  Synchronises."""
+        out = np.zeros(max(n, 0), np.int32)
+        in_force = C.c_int32(0)
+        self._check(self.lib.pagk_dispatch_order_get(self.h, n, out.ctypes.data_as(C.c_void_p), C.byref(in_force)),
+                    "pagk_dispatch_order_get")
+        return out, bool(in_force.value)
 
     def last_variant(self) -> int:
         return int(self.lib.pagk_last_variant(self.h))

@@ -120,6 +120,10 @@ struct TrackArgs {
     double win_size_inv;    // mWinSizeInv (:57)
     int distort_on;         // mDistCoef(0) != 0 (:410)
     float fx, fy, cx, cy, fx_inv, fy_inv, k1, k2, p1, p2, k3;
+    // the dispatch order (pagk_order.h): workgroup b of a 4-wave launch runs feature order[b], a permutation of [0, n) that lists the
+    // features by prio_hint_in, longest first; null: the identity.  Only the choice of the feature goes through it.  (Last: every
+    // other argument keeps the offset it had.)
+    const int *order;
 };
 
 // A level's description copied out of the kernel-argument segment.  Pinning the fields in scalar registers with

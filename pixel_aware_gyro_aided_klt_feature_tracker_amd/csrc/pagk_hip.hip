@@ -20,6 +20,7 @@
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
+#include "pagk_order.h"
 
 using namespace pagk;
 
@@ -80,6 +81,7 @@ struct pagk_ctx {
         SUSP,          // continuation buffers: int count (256 B) | int list[n] | SuspState state[n]
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
         PRIO_HINT,     // the 4-wave kernels' hint (pagk_prio.h): one int32 per feature slot of the largest launch so far
+        DISPATCH_ORDER,  // ... and their dispatch order (pagk_order.h): one int32 per feature slot, beside the hints
         kBufs
     };
     DevBuf buf[kBufs];
@@ -166,6 +168,8 @@ struct pagk_ctx {
     int prio_k = 4;                      // PAGK_PRIO_K: iterations per pyramid level beyond which a 4-wave workgroup counts as behind (pagk_prio.h); 0 = rule off
     unsigned long long *prio_stats = nullptr;  // PAGK_PRIO_K=auto: device block [iterations, feature-levels (u64 each), K (int)]
     int prio_hint_t = kPrioHintDefault;  // PAGK_PRIO_HINT: a feature slot whose previous launch ran more iterations than this starts behind (pagk_prio.h); 0 = hint off
+    bool graph_order[kGraphs] = {};      // graph k holds a build or a reader of the dispatch order (pagk_order.h: its replays bind the array)
+    OrderState order;                    // PAGK_DISPATCH_ORDER: the 4-wave launches' dispatch order, and when a launch may use it (pagk_order.h)
     bool block5_window = true;           // ... also for launches that only five workgroups per CU hold in one round (off when PAGK_BLOCK5_MIN is set)
     int levels_min_features = 6000;      // PAGK_LEVELS_MIN: ... one level per wave (a context alone on the device)
     int levels_shift = 0;                // PAGK_LEVELS_XCD_SHIFT (tests): waves start with another XCD's ticket sequence
@@ -334,6 +338,7 @@ int capture_split(pagk_ctx *ctx)
         if (e != hipSuccess) {
             (void)hipGraphDestroy(g);
             ctx->capturing = false;
+            (void)ctx->order.capture_ended();
             snprintf(ctx->err, sizeof(ctx->err), "hipGraphInstantiate (segment) -> %s", hipGetErrorString(e));
             return PAGK_E_HIP;
         }
@@ -343,6 +348,7 @@ int capture_split(pagk_ctx *ctx)
     hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) {
         ctx->capturing = false;
+        (void)ctx->order.capture_ended();
         snprintf(ctx->err, sizeof(ctx->err), "hipStreamBeginCapture (next segment) -> %s", hipGetErrorString(e));
         return PAGK_E_HIP;
     }
@@ -450,6 +456,18 @@ int slot_reserve(pagk_ctx *ctx, FrameSlot &s, int w, int h, int L)
     return rc ? rc : slot_alloc(ctx, s, lw, lh, L, NOT_IN_CAPTURE);
 }
 
+// How a launch that is about to be enqueued is recorded, for the order's rule: 0 executed, 1 into pagk_graph_begin's capture (the
+// graph dies in pagk_graph_destroy), 2 into somebody else's capture of the stream (nobody tells us when that graph dies).
+int capture_kind(pagk_ctx *ctx) { return ctx->capturing ? 1 : (in_capture(ctx) ? 2 : 0); }
+
+// The order workgroup of the pyramid launch that is about to be enqueued on ctx->stream: n = 0 for none.
+OrderArgs order_build_args(pagk_ctx *ctx)
+{
+    const DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT], &ob = ctx->buf[pagk_ctx::DISPATCH_ORDER];
+    const int n = ctx->order.build_n(ctx->stream, ctx->cus, (long long)(hb.bytes / sizeof(int32_t)), (long long)(ob.bytes / sizeof(int32_t)), capture_kind(ctx));
+    return {static_cast<const int *>(hb.ptr), static_cast<int *>(ob.ptr), n};
+}
+
 // Arguments of the single-launch pyramid (k_pyramid_fused / the trailing blocks of k_track_block_pyr) for a
 // reserved slot with at most 4 levels and even parents; returns the number of 256-thread blocks.
 int make_pyr_args(const FrameSlot &s, const uint8_t *src0, int64_t pitch0, int wrap0, PyrArgs *out)
@@ -505,8 +523,11 @@ int slot_build(pagk_ctx *ctx, FrameSlot &s, const uint8_t *src0, int64_t pitch0,
     if (s.L <= 4 && !ctx->unfused_pyramid && all_even) {
         PyrArgs pa;
         const int nb = make_pyr_args(s, src0, pitch0, wrap0, &pa);
-        hipLaunchKernelGGL(k_pyramid_fused, dim3(nb), dim3(256), 0, ctx->stream, pa);
+        // ... with the next tracking launch's dispatch order as one leading workgroup, where one is due (pagk_order.h)
+        const OrderArgs oa = order_build_args(ctx);
+        hipLaunchKernelGGL(k_pyramid_fused, dim3(nb + (oa.n > 0 ? 1 : 0)), dim3(256), order_lds_bytes(oa.n), ctx->stream, pa, oa);
         HIPCHK(ctx, hipGetLastError());
+        if (oa.n > 0) ctx->order.built(oa.n, ctx->stream, capture_kind(ctx));
         if (ctx->ev_pyr[1] && !in_capture(ctx)) HIPCHK(ctx, hipEventRecord(ctx->ev_pyr[1], ctx->stream));
         if (!in_capture(ctx)) ctx->pyr_timed = true;
         s.wrap0 = wrap0;
@@ -909,6 +930,18 @@ int launch_block(pagk_ctx *ctx, const TrackKernels &k, bool lean, int n, const T
     return PAGK_OK;
 }
 
+// Room for the dispatch order of n features (pagk_order.h), beside the hints and under the same terms: where the buffer may not grow
+// the launches run the identity.
+int order_reserve(pagk_ctx *ctx, int n)
+{
+    DevBuf &ob = ctx->buf[pagk_ctx::DISPATCH_ORDER];
+    if (!ctx->order.on || !order_serves(n, ctx->cus) || (size_t)n * sizeof(int32_t) <= ob.bytes || in_capture(ctx)) return PAGK_OK;
+    for (int k = 0; k < pagk_ctx::kGraphs; k++)
+        if (ctx->graph_execs[k]) return PAGK_OK;
+    ctx->order.array_replaced();
+    return reserve(ctx, ob, (size_t)n * sizeof(int32_t), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the dispatch order", kLargestLaunchFirst);
+}
+
 // The hint array of the 4-wave kernels (pagk_prio.h): one int32 per feature slot, what the slot's feature ran in the previous
 // launch.  It grows -- zeroed: no forecast -- with the largest launch; where it may not grow (inside a capture, under a live
 // graph whose nodes hold the old pointer) the launch runs without a hint, which costs it issue order and nothing else.
@@ -916,6 +949,7 @@ int prio_hint_attach(pagk_ctx *ctx, int n, TrackArgs *a)
 {
     DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
     const size_t need = (size_t)n * sizeof(int32_t);
+    if (int rc = order_reserve(ctx, n)) return rc;
     if (need > hb.bytes) {
         if (in_capture(ctx)) return PAGK_OK;
         for (int k = 0; k < pagk_ctx::kGraphs; k++)
@@ -932,6 +966,7 @@ int prio_hint_clear(pagk_ctx *ctx)
 {
     DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
     if (hb.ptr) HIPCHK(ctx, hipMemsetAsync(hb.ptr, 0, hb.bytes, ctx->stream));
+    ctx->order.hints_cleared();   // all counts equal: the order they give is the identity, and no launch is handed an older one
     return PAGK_OK;
 }
 
@@ -1003,7 +1038,12 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
                 // (hinted: false for the host-buffer calls -- their arrays are new features in a new order every call, a count
                 // kept for them would forecast nothing, and they clear the array instead: prio_hint_clear)
                 if (hinted && (rc = prio_hint_attach(ctx, n, &a))) break;
+                // the dispatch order, by the conservative rule of pagk_order.h; frozen with the graph inside a capture, like the hint pointer
+                if (a.prio_hint_in && ctx->order.usable(n, ctx->stream, ctx->cus, capture_kind(ctx)) &&
+                    ctx->buf[pagk_ctx::DISPATCH_ORDER].bytes >= (size_t)n * sizeof(int32_t))
+                    a.order = static_cast<const int *>(ctx->buf[pagk_ctx::DISPATCH_ORDER].ptr);
                 rc = launch_block(ctx, k, lean, n, a, pyr, pyr_blocks, pyr_done);
+                if (!rc && hinted) ctx->order.launched(a.prio_hint_out ? n : 0, ctx->stream, a.order != nullptr, capture_kind(ctx));
                 break;
         }
         if (rc) return rc;
@@ -1229,6 +1269,7 @@ int pagk_create(pagk_ctx **out, int device)
         ctx->prio_k = atoi(getenv("PAGK_PRIO_K")) < 0 ? 0 : atoi(getenv("PAGK_PRIO_K"));
     }
     if (getenv("PAGK_PRIO_HINT")) ctx->prio_hint_t = prio_hint_parse(getenv("PAGK_PRIO_HINT"), ctx->prio_hint_t);
+    if (getenv("PAGK_DISPATCH_ORDER")) ctx->order.on = atoi(getenv("PAGK_DISPATCH_ORDER")) != 0;
     if (getenv("PAGK_LEVELS_XCD_SHIFT")) ctx->levels_shift = atoi(getenv("PAGK_LEVELS_XCD_SHIFT")) & 7;
     if (getenv("PAGK_LEVELS_SHARED")) ctx->levels_shared = atoi(getenv("PAGK_LEVELS_SHARED")) != 0;
     if (getenv("PAGK_QUAD_BUDGET")) ctx->quad_budget = atoi(getenv("PAGK_QUAD_BUDGET"));
@@ -1368,6 +1409,28 @@ int pagk_prio_hint_get(pagk_ctx *ctx, int32_t n, int32_t *hints)
     memset(hints, 0, (size_t)n * sizeof(int32_t));
     if (have) HIPCHK(ctx, hipMemcpyAsync(hints, hb.ptr, have * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->order.stream_idle(ctx->stream);
+    return PAGK_OK;
+}
+
+// The dispatch order of the 4-wave launches (csrc/pagk_order.h): 1 unless PAGK_DISPATCH_ORDER=0 was in the environment of pagk_create.
+int pagk_dispatch_order_enabled(pagk_ctx *ctx) { return ctx ? (ctx->order.on ? 1 : 0) : PAGK_E_ARG; }
+
+// The first n entries of the order array as they are on the device (diagnostics, tests; synchronises); entries past the array's size
+// read as the identity.  *in_force (may be NULL): 1 when a hinted 4-wave launch of n features enqueued next on the current stream would
+// be handed the array, 0 when it would run the identity.
+int pagk_dispatch_order_get(pagk_ctx *ctx, int32_t n, int32_t *order, int32_t *in_force)
+{
+    if (!ctx || n < 0 || (n > 0 && !order)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_dispatch_order_get");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const DevBuf &ob = ctx->buf[pagk_ctx::DISPATCH_ORDER];
+    const size_t have = ob.bytes / sizeof(int32_t) < (size_t)n ? ob.bytes / sizeof(int32_t) : (size_t)n;
+    for (int32_t i = 0; i < n; i++) order[i] = i;
+    if (have) HIPCHK(ctx, hipMemcpyAsync(order, ob.ptr, have * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->order.stream_idle(ctx->stream);
+    if (in_force) *in_force = (have == (size_t)n && ctx->order.usable(n, ctx->stream, ctx->cus, 0)) ? 1 : 0;
     return PAGK_OK;
 }
 
@@ -1383,6 +1446,9 @@ int pagk_prio_hint_set(pagk_ctx *ctx, int32_t n, const int32_t *hints)
     if (int rc = prio_hint_clear(ctx)) return rc;
     if (n) HIPCHK(ctx, hipMemcpyAsync(hb.ptr, hints, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = order_reserve(ctx, n)) return rc;
+    ctx->order.stream_idle(ctx->stream);
+    ctx->order.hints_set(n);   // a forecast for n slots: the next pyramid launch sorts it
     return PAGK_OK;
 }
 
@@ -1407,6 +1473,7 @@ int pagk_sync(pagk_ctx *ctx)
     if (!ctx) return PAGK_E_ARG;
     NOT_WHILE_CAPTURING(ctx, "pagk_sync");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->order.stream_idle(ctx->stream);
     return lv_check(ctx);
 }
 
@@ -3314,6 +3381,7 @@ int pagk_graph_end(pagk_ctx *ctx, int32_t *graph_id)
 {
     if (!ctx || !ctx->capturing || !graph_id) return PAGK_E_ARG;
     ctx->capturing = false;
+    const bool carries_order = ctx->order.capture_ended();
     hipGraph_t g = nullptr;
     HIPCHK(ctx, hipStreamEndCapture(ctx->stream, &g));
     int id = -1;
@@ -3340,6 +3408,7 @@ int pagk_graph_end(pagk_ctx *ctx, int32_t *graph_id)
     }
     ctx->graphs[id] = g;
     ctx->graph_execs[id] = ex;
+    ctx->graph_order[id] = carries_order;
     ctx->pre_segs[id] = std::move(ctx->cap_segs);   // (empty for a capture without a live finisher: one graph, as before)
     ctx->cap_segs.clear();
     batch_desc_free(ctx->graph_batch[id]);
@@ -3353,6 +3422,9 @@ int pagk_graph_end(pagk_ctx *ctx, int32_t *graph_id)
 int pagk_graph_launch(pagk_ctx *ctx, int32_t graph_id)
 {
     if (!ctx || ctx->capturing || graph_id < 0 || graph_id >= pagk_ctx::kGraphs || !ctx->graph_execs[graph_id]) return PAGK_E_ARG;
+    // a graph that builds or reads the dispatch order binds the array to the stream it is replayed on; bound to another stream, whose
+    // work the host has not waited for, the array could be rewritten under a reader: wait first (rare: a stream switch without a sync)
+    if (ctx->graph_order[graph_id] && ctx->order.replay(ctx->stream)) HIPCHK(ctx, hipDeviceSynchronize());
     for (pagk_ctx::GraphSeg &sg : ctx->pre_segs[graph_id]) {
         if (sg.kind == pagk_ctx::GraphSeg::GRAPH) {
             HIPCHK(ctx, hipGraphLaunch(sg.ex, ctx->stream));
@@ -3382,6 +3454,11 @@ int pagk_graph_destroy(pagk_ctx *ctx, int32_t graph_id)
     batch_desc_free(ctx->graph_batch[graph_id]);
     ctx->graph_execs[graph_id] = nullptr;
     ctx->graphs[graph_id] = nullptr;
+    ctx->graph_order[graph_id] = false;
+    ctx->order.stream_idle(ctx->stream);
+    bool alive = false;
+    for (int k = 0; k < pagk_ctx::kGraphs; k++) alive = alive || ctx->graph_execs[k];
+    if (!alive) ctx->order.graphs_gone();
     return lv_check(ctx);
 }
 

@@ -19,6 +19,7 @@
 #include "pagk_device.h"
 #include "pagk_chain_asm.h"
 #include "pagk_prio.h"
+#include "pagk_order.h"
 
 namespace pagk {
 
@@ -163,9 +164,95 @@ __device__ __forceinline__ void pyr_block(const PyrArgs &a, int b, int tid)
     }
 }
 
-__global__ void __launch_bounds__(256) k_pyramid_fused(PyrArgs a)
+// The dispatch order of the NEXT 4-wave tracking launch (pagk_order.h), built by one extra workgroup of the pyramid launch that
+// precedes it: the step keeps its two launches, and nothing is added behind the tracking kernel, whose end is the step's end.  The
+// workgroup LEADS the launch (block 0, the pyramid's blocks follow one index up): its chain of dependent steps -- load, count, scan,
+// scatter -- is about 2 us long and a 752 x 480 pyramid 5 us, so started first it ends inside the launch, while as the LAST block it
+// started behind the coarse levels' blocks and the launch measured 0.26 us longer (profiles/dispatch_order/).
+struct OrderArgs {
+    const int *hints;  // the counts the n feature slots ran last (TrackArgs::prio_hint_in of the launch to come)
+    int *order;        // out: the n features, largest count first, ties in index order
+    int n;             // 0: no order block in this launch
+};
+
+// 256 threads.  The hints are read ONCE, clamped and kept as class numbers in LDS (class 0 = the largest key); the histogram and the
+// scatter both work from that copy, so `order` is a permutation of [0, n) whatever is written to the hint array meanwhile (a tracking
+// launch of another stream).  Wave w owns the w-th quarter of the index range: per-wave class counts, one scan over the classes
+// (wave w's part of a class starts behind the parts of the waves below it), then every wave walks its quarter 64 features at a time.
+// Inside a chunk a feature's place among its equals is the number of lower lanes with the same class -- eight ballots, one per bit of
+// the class, intersect to that mask -- which keeps ties in index order without a sort.
+__device__ __forceinline__ void order_block(const OrderArgs &o, int tid)
 {
-    pyr_block(a, (int)blockIdx.x, (int)threadIdx.x);
+    // (dynamic LDS, order_lds_bytes(n) of it: a launch without an order workgroup allocates none for the pyramid's blocks)
+    extern __shared__ __attribute__((aligned(16))) unsigned char order_lds[];
+    int (*s_at)[kOrderClasses] = reinterpret_cast<int (*)[kOrderClasses]>(order_lds);   // [4]: counts, then running start positions, per wave and class
+    uint8_t *s_class = order_lds + 4 * kOrderClasses * sizeof(int);
+    const int n = o.n < kOrderMaxN ? o.n : kOrderMaxN;   // (the host attaches the block for n <= kOrderMaxN only)
+    const int wave = tid >> 6, lane = tid & 63;
+    const int quarter = ((n + 255) >> 8) << 6;           // whole chunks of 64
+    const int lo = wave * quarter, hi = lo + quarter < n ? lo + quarter : n;
+    for (int k = tid; k < 4 * kOrderClasses; k += 256) (&s_at[0][0])[k] = 0;
+    __syncthreads();
+    for (int i = lo + lane; i < hi; i += 64) {
+        const int c = kOrderKeyMax - order_key(o.hints[i]);
+        s_class[i] = (uint8_t)c;
+        atomicAdd(&s_at[wave][c], 1);
+    }
+    __syncthreads();
+    if (wave == 0) {   // lane l: classes 2l and 2l + 1
+        static_assert(kOrderClasses == 128, "two classes per lane of one wave");
+        int cnt[2][4], pair = 0;
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int w = 0; w < 4; w++) pair += cnt[k][w] = s_at[w][2 * lane + k];
+        int incl = pair;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d);
+            incl += lane >= d ? up : 0;
+        }
+        int at = incl - pair;
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                s_at[w][2 * lane + k] = at;
+                at += cnt[k][w];
+            }
+    }
+    __syncthreads();
+    for (int base = lo; base < hi; base += 64) {   // (wave-uniform bounds)
+        const int i = base + lane;
+        const bool valid = i < hi;
+        const int c = valid ? (int)s_class[i] : 255;   // lanes past the end: a class of their own
+        unsigned long long same = ~0ull;
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const bool bit = (c >> b) & 1;
+            const unsigned long long with = __ballot(bit);
+            same &= bit ? with : ~with;
+        }
+        const int below = __popcll(same & ((1ull << lane) - 1ull)), all = __popcll(same);
+        int at = 0;
+        if (valid) {
+            at = s_at[wave][c];
+            o.order[at + below] = i;
+        }
+        __builtin_amdgcn_wave_barrier();   // every lane has read its class's position before the class's last lane moves it on
+        if (valid && below == all - 1) s_at[wave][c] = at + all;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_pyramid_fused(PyrArgs a, OrderArgs o)
+{
+    const int lead = o.n > 0 ? 1 : 0;   // (launched with one workgroup more than the pyramid has)
+    if (lead && blockIdx.x == 0) {
+        order_block(o, (int)threadIdx.x);
+        return;
+    }
+    pyr_block(a, (int)blockIdx.x - lead, (int)threadIdx.x);
 }
 
 // The pyramids of k frames as ONE launch (pagk_frame_set_device_batch: the CreatePyramids of k trackers that are stepped
@@ -1176,7 +1263,10 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
 template <int NR, int TAIL, int WAVES = 4, bool MFMA = false, bool RELAXED = false, bool LEAN = false>
 __global__ void __launch_bounds__(WAVES * 64, 4) k_track_block(TrackArgs a)
 {
-    track_block_body<NR, TAIL, WAVES, MFMA, RELAXED, LEAN>(a, (int)blockIdx.x);
+    if constexpr (MFMA || RELAXED)
+        track_block_body<NR, TAIL, WAVES, MFMA, RELAXED, LEAN>(a, (int)blockIdx.x);
+    else
+        track_block_body<NR, TAIL, WAVES, MFMA, RELAXED, LEAN>(a, dispatch_feature(a));
 }
 
 // The same 4-wave kernel compiled for FIVE waves per SIMD (96 VGPRs, 13 spilled at h = 10): five workgroups per CU
@@ -1186,7 +1276,7 @@ __global__ void __launch_bounds__(WAVES * 64, 4) k_track_block(TrackArgs a)
 template <int NR, int TAIL, bool LEAN = false>
 __global__ void __launch_bounds__(256, 5) k_track_block5(TrackArgs a)
 {
-    track_block_body<NR, TAIL, 4, false, false, LEAN, false>(a, (int)blockIdx.x);
+    track_block_body<NR, TAIL, 4, false, false, LEAN, false>(a, dispatch_feature(a));
 }
 
 // The latency kernel as the second pass of a large launch: finishes the features a throughput kernel suspended
@@ -1269,7 +1359,7 @@ __global__ void __launch_bounds__(256, 4) k_track_block_pyr(TrackArgs a, PyrArgs
         pyr_block(pa, (int)blockIdx.x - a.n, (int)threadIdx.x);
         return;
     }
-    track_block_body<NR, TAIL, 4, false, false, LEAN>(a, (int)blockIdx.x);
+    track_block_body<NR, TAIL, 4, false, false, LEAN>(a, dispatch_feature(a));
 }
 
 }  // namespace pagk

@@ -62,6 +62,14 @@ __device__ __forceinline__ void prio_hint_store(const TrackArgs &a, int i, int i
 {
     if (a.prio_hint_out) a.prio_hint_out[i] = iters;
 }
+
+// The feature a workgroup of a 4-wave launch runs (pagk_order.h): its own index, or -- one scalar load in the prologue -- what the
+// dispatch order lists there.  Everything else indexes by the feature.
+__device__ __forceinline__ int dispatch_feature(const TrackArgs &a)
+{
+    const int b = (int)blockIdx.x;
+    return a.order ? __builtin_amdgcn_readfirstlane(a.order[b]) : b;
+}
 }  // namespace pagk
 #if PAGK_PRIO_MODE == 0
 #define PAGK_PRIO_DECL(hinted)

@@ -4,7 +4,9 @@ gets -- as far as this sequence goes: the REFERENCE frame and the keypoints neve
 affine and the incoming status do), so the reference patches that make a feature slow are the same in every pair, while a real tracker's
 reference frame is new every frame.  An upper bound on what footage would give.  Two trackers, one created with PAGK_PRIO_HINT=0 and one with the default (or PAGK_HINT_T), take turns on every pair; the tracking
 launch is timed by the library's own events (pagk_last_kernel_ms).  For comparison the same pairs with the pair's own counts as the hint
-(the benchmark's situation: a replayed pair).  Usage: python tools/hint_sequence.py [n] [rounds] [config]
+(the benchmark's situation: a replayed pair).  Usage: python tools/hint_sequence.py [n] [rounds] [config] [arm]
+arm = order: the same measurement of the dispatch order of csrc/pagk_order.h -- both trackers keep the default hint threshold, "off" is
+created with PAGK_DISPATCH_ORDER=0 -- so that its two figures (the previous pair's counts, the pair's own) stand beside the hint's.
 Another config than 1 has no sequence (tools/hint_pairs.py varies configs[1]'s motion): its one pair is replayed, both figures are the
 exact-hint case."""
 import os, sys
@@ -24,17 +26,21 @@ w0 = pairs[0]
 p = capi.make_params(half_patch=w0.half_patch, iterations=w0.iterations, pyramids=w0.pyramids, has_gyro=w0.has_gyro, camera=w0.camera)
 
 
-def make(threshold):
-    old = os.environ.get("PAGK_PRIO_HINT")
+arm = sys.argv[4] if len(sys.argv) > 4 else "hint"
+assert arm in ("hint", "order"), arm
+
+
+def make(threshold, name="PAGK_PRIO_HINT"):
+    old = os.environ.get(name)
     if threshold is None:
-        os.environ.pop("PAGK_PRIO_HINT", None)
+        os.environ.pop(name, None)
     else:
-        os.environ["PAGK_PRIO_HINT"] = str(threshold)
+        os.environ[name] = str(threshold)
     rt = runtime.ResidentTracker(p, device=0)
     if old is None:
-        os.environ.pop("PAGK_PRIO_HINT", None)
+        os.environ.pop(name, None)
     else:
-        os.environ["PAGK_PRIO_HINT"] = old
+        os.environ[name] = old
     rt.load_pair(w0.img_ref, w0.img_cur)
     rt.set_features(w0.pt_ref, w0.pt_init, w0.affine, w0.status_in)
     return rt
@@ -57,8 +63,13 @@ def launch(rt):
         return rt.ctx.last_kernel_ms()[0] * 1e3
 
 
-on, off = make(os.environ.get("PAGK_HINT_T")), make(0)
-print(f"configs[{cfg}] scene, {n} features, {len(pairs)} pairs, {rounds} rounds; thresholds: on = {on.ctx.prio_hint_threshold()}, off = {off.ctx.prio_hint_threshold()}")
+if arm == "order":
+    on, off = make(None, "PAGK_DISPATCH_ORDER"), make(0, "PAGK_DISPATCH_ORDER")
+    print(f"configs[{cfg}] scene, {n} features, {len(pairs)} pairs, {rounds} rounds; dispatch order: on = {on.ctx.dispatch_order_enabled()}, "
+          f"off = {off.ctx.dispatch_order_enabled()}; hint threshold of both = {on.ctx.prio_hint_threshold()}")
+else:
+    on, off = make(os.environ.get("PAGK_HINT_T")), make(0)
+    print(f"configs[{cfg}] scene, {n} features, {len(pairs)} pairs, {rounds} rounds; thresholds: on = {on.ctx.prio_hint_threshold()}, off = {off.ctx.prio_hint_threshold()}")
 seq = {"on": [], "off": []}
 exact = {"on": [], "off": []}
 for r in range(rounds + 1):          # (round 0 warms up)
@@ -80,7 +91,7 @@ def per_round(v):
     return a.mean(1)
 
 
-for what, d in (("hint from the previous pair (a tracker)", seq), ("hint = the pair's own counts (a replayed pair)", exact)):
+for what, d in ((f"{arm} from the previous pair's counts (a tracker)", seq), (f"{arm} from the pair's own counts (a replayed pair)", exact)):
     a_on, a_off = per_round(d["on"]), per_round(d["off"])
     print(f"{what}: tracking launch, mean over the pairs, per round (us)")
     print("   on : " + "  ".join(f"{x:.2f}" for x in a_on) + f"   median {np.median(a_on):.2f}")

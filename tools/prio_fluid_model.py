@@ -105,8 +105,58 @@ def hint_tables(out=sys.stdout, K=4, Ts=(10, 12, 14, 15, 16, 17, 18, 19, 20, 22,
     return best, rows, exact, base
 def by_level(s, L): return s["lv"]
 
+def dispatch_order(hint, key_max=127):
+    """csrc/pagk_order.h: the features by clamped hint, descending, ties in index order (workgroup b runs feature order[b])."""
+    return np.argsort(-np.clip(np.asarray(hint, np.int64), 0, key_max), kind="stable")
+
+def simulate_ordered(it, hint, order, K=4, T=14, **kw):
+    """simulate() with workgroup b running feature order[b]: the features and their hints are permuted, the placement rule is untouched."""
+    return simulate(it[order], behind(K), hint=np.asarray(hint)[order], T=T, **kw)
+
+def order_tables(out=sys.stdout, K=4):
+    """`python tools/prio_fluid_model.py order`: the makespan with the workgroups in index order (today) and in hint-descending order,
+    beside the slowest feature's own time -- the replayed pair (own counts), the sequence of tools/hint_pairs.py (the previous pair's
+    counts), other orders on pair 0, and the launches of several rounds."""
+    seq = [np.loadtxt(os.path.join(HERE, "data", f"iters_seq_cfg1_1000_p{j}.txt"), dtype=int, ndmin=2) for j in range(7)]
+    tot = [s.sum(1) for s in seq]
+    alone = lambda it: ((it.sum(1).max() * LONE + it.shape[1] * SETUP) / (GHZ * 1e3))   # noqa: E731
+    ident = np.arange(1000)
+    print(f"K = {K}, T = 14 per three levels, four slots per CU unless stated.  Makespan (us) of the fluid model.", file=out)
+    print("workload, hint                                   identity   hint-descending   slowest feature alone", file=out)
+    def row(name, it, hint, T=14, **kw):
+        a = simulate_ordered(it, hint, np.arange(len(hint)), K, T, **kw)
+        b = simulate_ordered(it, hint, dispatch_order(hint), K, T, **kw)
+        print(f"{name:48s} {a:8.2f}   {b:15.2f}   {alone(it):21.2f}", file=out)
+        return a, b
+    rows = {0: row("configs[1] pair 0, own counts (a replayed pair)", seq[0], tot[0])}
+    for j in range(1, 7):
+        rows[j] = row(f"pair {j}, previous pair's counts", seq[j], tot[j - 1])
+    d = [rows[j][1] - rows[j][0] for j in range(1, 7)]
+    print(f"   pairs 1..6, ordered - identity: mean {np.mean(d):+.2f} us, worst {max(d):+.2f}, best {min(d):+.2f}", file=out)
+    rng = np.random.default_rng(0)
+    print("other orders on pair 0 (own counts):", file=out)
+    for name, order in (("random permutation", rng.permutation(1000)), ("ascending", dispatch_order(tot[0])[::-1].copy()),
+                        ("snake over the layers", _snake(tot[0]))):
+        print(f"   {name:24s} {simulate_ordered(seq[0], tot[0], order, K):8.2f}", file=out)
+    print(f"   {'snake, pair 3 with pair 2 counts':24s} {simulate_ordered(seq[3], tot[2], _snake(tot[2]), K):8.2f}", file=out)
+    print("launches of several rounds (own counts):", file=out)
+    for name, T, slots in (("iters_cfg2_2000.npy", 19, 4), ("iters_cfg1_2000.txt", 14, 4), ("iters_cfg1_1100.txt", 14, 5)):
+        path = os.path.join(HERE, "data", name)
+        it = (np.load(path) if name.endswith(".npy") else np.loadtxt(path, dtype=int, ndmin=2)).astype(int)
+        row(f"{name[:-4]}, T = {T}, {slots} slots per CU", it, it.sum(1), T=T, slots=slots)
+    return rows
+
+def _snake(hint):
+    """hint-descending with every other layer of 256 reversed: the longest features get the shortest CU-mates"""
+    o = dispatch_order(hint).copy()
+    for layer in range(1, (len(o) + 255) // 256, 2):
+        o[layer * 256:(layer + 1) * 256] = o[layer * 256:(layer + 1) * 256][::-1].copy()
+    return o
+
 if __name__ == "__main__" and sys.argv[1:] == ["hint"]:
     hint_tables()
+elif __name__ == "__main__" and sys.argv[1:] == ["order"]:
+    order_tables()
 elif __name__ == "__main__":
     for name in ("iters_cfg1_1000.npy", "iters_cfg2_2000.npy"):
         it = np.load(os.path.join(HERE, "data", name)).astype(int)
