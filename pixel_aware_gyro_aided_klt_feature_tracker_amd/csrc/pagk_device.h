@@ -563,14 +563,21 @@ struct OperandRange {
     }
     __device__ __forceinline__ bool in_range() const { return t <= kSpan; }
 };
-template <bool FAST>
+// A range add that can decide nothing is left out (ROOT_OF_CHECKED below): the denominator is the root that
+// pivot_root_early or an accepting pivot_root formed from a pivot x which the SAME accumulator has already taken.  If x
+// was in range, 2^-400 <= x < 2^401, its root lies in [2^-200, 2^200.5] (the lean root is sqrt(x) to the last bit there,
+// and even an error of many ulps would not leave the range), so its own t is below kSpan and the maximum keeps saying
+// "in range"; if x was not (zero, negative, denormal, huge, inf, NaN), t already says "out of range" and no later
+// operand can take that back.  Either way in_range() is what it would be with the add -- and nothing else reads t.
+// Every other operand (numerators, a rejected pivot's H(k,k)) is still added.
+template <bool FAST, bool ROOT_OF_CHECKED = false>
 __device__ __forceinline__ Den den_prepare(double d, OperandRange &rg)
 {
     Den D;
     D.d = d;
     D.r = 0.0;
     if constexpr (FAST) {
-        rg.add_positive(d);
+        if constexpr (!ROOT_OF_CHECKED) rg.add_positive(d);
         double r = __builtin_amdgcn_rcp(d);
         double e = __builtin_fma(-d, r, 1.0);
         r = __builtin_fma(r, e, r);
@@ -645,6 +652,35 @@ __device__ __forceinline__ double pivot_root_early(bool ok, double x, double hkk
         return ok ? sqrt(x) : hkk;
     }
 }
+// What the four-lane FAST form does with a REJECTED 4th pivot.  H is singular (J = (Ix, Iy, c, 1) with c constant per
+// level: column 3 is column 2 / c), so x3 is rounding noise around zero and the reference's LLT returns at `x <= 0` in
+// most solves, leaving H33 on the diagonal.
+//   Pivot3Select: pivot_root forms the root of a stand-in 1.0 and den_prepare refines 1 / H33 from scratch; selects drop
+//     the one and keep the other.  Branch-free: ~24 instructions in every solve.
+//   Pivot3Known: the solving lanes hold the same x3, so the decision is a scalar branch.  Rejected: D3 = {H33, r} with r
+//     the reciprocal den_prepare<true> refines for H33 and t its range word, both prepared by the caller where H33 is
+//     known -- once per workgroup in a tracking kernel, whose H33 is the patch's pixel count (pivot3_known).  No root, no
+//     reciprocal, no range add on that path.  Accepted (a NaN pivot included: `x <= 0` is false): the root and the
+//     reciprocal as in the select form.  The same bits either way.
+struct Pivot3Select {
+    static constexpr bool kBranch = false;
+};
+struct Pivot3Known {
+    static constexpr bool kBranch = true;
+    double r;    // den_prepare<true>(H33).r
+    uint32_t t;  // OperandRange's word for H33; 0 where H33 is in range by construction
+};
+// H33 = the number of pixels of a patch: in range by construction.  The reciprocal comes from the device's own
+// sequence (v_rcp_f64 and two Newton steps -- the operand is hidden from the compiler, which would otherwise fold the
+// sequence from a correctly rounded 1 / h33) and is wave-uniform: it lives in two scalar registers, not in a VGPR pair.
+__device__ __forceinline__ Pivot3Known pivot3_known(double h33)
+{
+    asm volatile("" : "+v"(h33));
+    OperandRange rg;
+    const double r = den_prepare<true>(h33, rg).r;
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(r)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(r));
+    return Pivot3Known{__hiloint2double(hi, lo), 0u};
+}
 // the lean square root by itself, with the plain one where the operand is out of its range (diagnostics)
 __device__ __forceinline__ double sqrt_one(double x)
 {
@@ -699,7 +735,7 @@ __device__ __forceinline__ double llt4_solve_nsq_form(const double (&M)[4][4], c
     // column 0
     const bool ok0 = FAST || (!(H00 <= 0.0));
     const double d0 = pivot_root_early<FAST>(ok0, H00, H00, rg);
-    const Den D0 = den_prepare<FAST>(d0, rg);
+    const Den D0 = den_prepare<FAST, true>(d0, rg);
     double rx = recip ? div_by<FAST>(1.0, D0, rg) : 0.0;
     const double q10 = scale(H10, D0, rx), q20 = scale(H20, D0, rx), q30 = scale(H30, D0, rx);
     const double r0 = div_by<FAST>(b[0], D0, rg);
@@ -708,7 +744,7 @@ __device__ __forceinline__ double llt4_solve_nsq_form(const double (&M)[4][4], c
     const double x1 = H11 - L10 * L10;
     const bool ok1 = FAST || (ok0 && !(x1 <= 0.0));
     const double d1 = pivot_root_early<FAST>(ok1, x1, H11, rg);
-    const Den D1 = den_prepare<FAST>(d1, rg);
+    const Den D1 = den_prepare<FAST, true>(d1, rg);
     rx = recip ? div_by<FAST>(1.0, D1, rg) : 0.0;
     const double q21 = scale(H21 - L20 * L10, D1, rx), q31 = scale(H31 - L30 * L10, D1, rx);
     const double r1 = div_by<FAST>(b[1] - L10 * r0, D1, rg);
@@ -719,7 +755,7 @@ __device__ __forceinline__ double llt4_solve_nsq_form(const double (&M)[4][4], c
     const double x2 = H22 - s;
     const bool ok2 = FAST || (ok1 && !(x2 <= 0.0));
     const double d2 = pivot_root_early<FAST>(ok2, x2, H22, rg);
-    const Den D2 = den_prepare<FAST>(d2, rg);
+    const Den D2 = den_prepare<FAST, true>(d2, rg);
     s = L30 * L20;
     s += L31 * L21;
     rx = recip ? div_by<FAST>(1.0, D2, rg) : 0.0;
@@ -799,10 +835,11 @@ struct SolveNoLate {
     __device__ __forceinline__ void issue() const {}
     __device__ __forceinline__ void operator()() const {}
 };
-template <bool FAST, bool ROWB = false, class LATE = SolveNoLate>
+// P3: the FAST form's way with a rejected 4th pivot (Pivot3Select / Pivot3Known above); the plain form ignores it.
+template <bool FAST, bool ROWB = false, class LATE = SolveNoLate, class P3 = Pivot3Select>
 __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4][4], const double (&b)[4], int l,
                                                             double (&x)[4], uint32_t sv, OperandRange &rg,
-                                                            const LATE &late = LATE{})
+                                                            const LATE &late = LATE{}, const P3 &p3 = P3{})
 {
     const double H00 = M[0][0], H10 = M[1][0], H20 = M[2][0], H22 = M[2][2];
     const double H30 = M[3][0], H32 = M[3][2], H33 = M[3][3];
@@ -819,7 +856,7 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
     const bool ok0 = FAST || (!(H00 <= 0.0));
     const double d0 = pivot_root_early<FAST>(ok0, H00, H00, rg);
     late.issue();
-    const Den D0 = den_prepare<FAST>(d0, rg);
+    const Den D0 = den_prepare<FAST, true>(d0, rg);
     const double n0 = l == 0 ? b[0] : (l == 1 ? H10 : (l == 2 ? H20 : H30));
     const double q0 = column(n0, D0, l == 0);
     const double own0 = (l == 0 || ok0) ? q0 : n0;
@@ -831,7 +868,7 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
     const double x1 = H11 - L10 * L10;
     const bool ok1 = FAST || (ok0 && !(x1 <= 0.0));
     const double d1 = pivot_root_early<FAST>(ok1, x1, H11, rg);
-    const Den D1 = den_prepare<FAST>(d1, rg);
+    const Den D1 = den_prepare<FAST, true>(d1, rg);
     const double h1 = l == 2 ? H21 : H31;
     const double n1 = l == 1 ? b[1] - L10 * r0 : h1 - (l == 2 ? L20 : L30) * L10;
     const double q1 = column(n1, D1, l == 1);
@@ -844,7 +881,7 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
     const double x2 = H22 - s;
     const bool ok2 = FAST || (ok1 && !(x2 <= 0.0));
     const double d2 = pivot_root_early<FAST>(ok2, x2, H22, rg);
-    const Den D2 = den_prepare<FAST>(d2, rg);
+    const Den D2 = den_prepare<FAST, true>(d2, rg);
     s = L30 * L20;
     s += L31 * L21;
     const double n2 = l == 2 ? b[2] - (L20 * r0 + L21 * r1) : H32 - s;
@@ -856,8 +893,19 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
     const double a0 = L30 * L30, a1 = L31 * L31, a2 = L32 * L32;
     const double x3 = H33 - ((sv & SV_PIVOT_TREE) ? a0 + (a1 + a2) : (a0 + a1) + a2);
     const bool ok3 = ok2 && !(x3 <= 0.0);
-    const double d3 = pivot_root<FAST>(ok3, x3, H33, rg);
-    const Den D3 = den_prepare<FAST>(d3, rg);
+    Den D3;
+    if constexpr (FAST && P3::kBranch) {
+        // lanes 0..3 hold the same x3 and the others follow them: one scalar branch, nothing computed to be dropped
+        if (__builtin_amdgcn_ballot_w64(ok3 && l < 4) != 0) {
+            D3 = den_prepare<true, true>(pivot_root<true>(true, x3, H33, rg), rg);
+        } else {
+            D3.d = H33;
+            D3.r = p3.r;
+            rg.t = p3.t > rg.t ? p3.t : rg.t;
+        }
+    } else {
+        D3 = den_prepare<FAST>(pivot_root<FAST>(ok3, x3, H33, rg), rg);
+    }
     const double c0 = L30 * r0, c1 = L31 * r1, c2 = L32 * r2;
     const double r3 = div_by<FAST, true>(b[3] - ((sv & SV_LOWER_SEQ) ? (c0 + c1) + c2 : c0 + (c1 + c2)), D3, rg);
     // L^T x = y  (sequential by nature; every lane computes it)
@@ -867,12 +915,13 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes_form(const double (&M)[4]
 // (the calling lanes -- four, or a whole wave whose lanes 0..3 matter -- take the decision together: the form
 // broadcasts between them)
 // With a LATE hook (see the form) the plain-division redo reads M and b as the hook completed them.
-template <bool ROWB = false, class LATE = SolveNoLate>
+template <bool ROWB = false, class LATE = SolveNoLate, class P3 = Pivot3Select>
 __device__ __forceinline__ double llt4_solve_nsq_lanes(const double (&M)[4][4], const double (&b)[4], int l,
-                                                       double (&x)[4], uint32_t sv, const LATE &late = LATE{})
+                                                       double (&x)[4], uint32_t sv, const LATE &late = LATE{},
+                                                       const P3 &p3 = P3{})
 {
     OperandRange rg;
-    double nsq = llt4_solve_nsq_lanes_form<true, ROWB>(M, b, l, x, sv, rg, late);
+    double nsq = llt4_solve_nsq_lanes_form<true, ROWB>(M, b, l, x, sv, rg, late, p3);
 #ifndef PAGK_EXPERIMENT_NO_REDO
     if (__builtin_amdgcn_ballot_w64(!rg.in_range() && l < 4) != 0) nsq = llt4_solve_nsq_lanes_form<false, ROWB>(M, b, l, x, sv, rg);
 #endif

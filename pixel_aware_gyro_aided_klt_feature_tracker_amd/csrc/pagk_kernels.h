@@ -774,6 +774,9 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
         }
     }
 
+    // H33 = P in every solve of the DPP-row body: the reciprocal a rejected 4th pivot divides by, once (pagk_device.h)
+    [[maybe_unused]] const Pivot3Known pivot3 = MFMA ? Pivot3Known{0.0, 0u} : pivot3_known((double)P);
+
     int succ = 1, iters = 0;
     [[maybe_unused]] constexpr bool kPrioByWork = NR > 1;  // pagk_prio.h
     PAGK_PRIO_DECL(hinted)
@@ -1119,7 +1122,11 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
                     if (a.penalty) add_penalty(a, dx, dy, H, b, cost);
                 }
                 // four lanes share the divides of each Cholesky column (pagk_device.h); all end with the result
-                double unorm = llt4_solve_nsq_lanes(H, b, tid, upd, LEAN ? 0u : a.solver);  // update.squaredNorm()
+                double unorm;  // update.squaredNorm()
+                if constexpr (MFMA)  // (H33 is a sum there)
+                    unorm = llt4_solve_nsq_lanes(H, b, tid, upd, LEAN ? 0u : a.solver);
+                else
+                    unorm = llt4_solve_nsq_lanes(H, b, tid, upd, LEAN ? 0u : a.solver, SolveNoLate{}, pivot3);
 #ifdef PAGK_COUNT_REDO
                 if (a.dbg) {
                     OperandRange rg;

@@ -131,6 +131,9 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
     // result is one masked store.  Wave 0 publishes nothing: its sums stay in registers.
     const int acc_slot = wave == 1 ? (lr == 0 ? (cid == 7 ? 4 : cid - 4) : ((lr == 1 && cid >= 6) ? 2 * cid - 9 : -1)) : -1;
 
+    // H33 = P in every solve of this body: the reciprocal a rejected 4th pivot divides by, once (pagk_device.h)
+    const Pivot3Known pivot3 = pivot3_known((double)P);
+
     int succ = 1, iters = 0, seq = 0;
     [[maybe_unused]] constexpr bool kPrioByWork = true;  // pagk_prio.h
     PAGK_PRIO_DECL(!resume)
@@ -376,13 +379,13 @@ __device__ __forceinline__ void track_pipe_body(const TrackArgs &a, const int i,
                         // four lanes share the divides of each Cholesky column (pagk_device.h); all end with the result,
                         // update.squaredNorm()
                         if constexpr (LEAN) {
-                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, 0u, take_late);
+                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, 0u, take_late, pivot3);
                         } else {
                             // the generic instantiations take wave 1's sums before the solve: the penalty adds to them,
                             // and the late form's live ranges cost these kernels spills
                             take_late();
                             if (a.penalty) epsq = add_penalty_hb(a, dx, dy, Hm, b);
-                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, a.solver);
+                            unorm = llt4_solve_nsq_lanes<true>(Hm, b, tid, upd, a.solver, SolveNoLate{}, pivot3);
                         }
                         if (tid == 0) {
                             sh_upd[0] = upd[0];

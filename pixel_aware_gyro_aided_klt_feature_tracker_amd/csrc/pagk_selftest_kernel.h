@@ -59,7 +59,13 @@ __global__ void __launch_bounds__(64) k_selftest_solve(int n, const double *H, c
             const int sys = blockIdx.x * 16 + g;
             double M[4][4], rhs[4], x[4];
             load(sys, M, rhs);
-            const double nsq = llt4_solve_nsq_lanes(M, rhs, t & 3, x, sv);  // every lane holds the same system
+            // the form the 4-wave kernels' DPP-row bodies run: a rejected 4th pivot branches to a reciprocal of H33 prepared
+            // outside the solve (pagk_device.h: Pivot3Known).  H33 is arbitrary here, so its range word goes along.
+            OperandRange rg33;
+            const Den D33 = den_prepare<true>(M[3][3], rg33);
+            const Pivot3Known p3{D33.r, rg33.t};
+            // every lane holds the same system
+            const double nsq = llt4_solve_nsq_lanes(M, rhs, t & 3, x, sv, SolveNoLate{}, p3);
             if (t == 0 && sys < n) {
                 for (int k = 0; k < 4; k++) x_lanes[(size_t)sys * 4 + k] = x[k];
                 nsq_lanes[sys] = nsq;
