@@ -25,6 +25,9 @@
 // loop then feeds those raw frames: pagk_frame_rectify_device (maps from pagk_undistort_maps, set once) replaces
 // pagk_frame_set_device inside each graph.  The same lines are printed.  --detect / --detect-fast and --rectify combine.
 //
+// --inverse tracks in the template-Jacobian mode (pagk_params::inverse = PAGK_INVERSE_TEMPLATE, include/pagk.h): the same loop
+// and the same lines, with that mode's results.  Combines with every other flag.
+//
 // Input: the file of stream_resident.cpp.
 // Build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I /opt/rocm/include -I include examples/stream_graph_loop.cpp
 //        -L <pkg> -l:libpagk_hip.so -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,<pkg> -Wl,-rpath,/opt/rocm/lib
@@ -64,16 +67,17 @@ struct KeySet {
 
 int main(int argc, char **argv)
 {
-    bool detect = false, rectify = false, fast = false;   // fast: the detector of --detect is the FAST one
+    bool detect = false, rectify = false, fast = false, inverse = false;   // fast: the detector of --detect is the FAST one
     for (int k = 1; k < argc; k++)
-        if (!std::strcmp(argv[k], "--detect") || !std::strcmp(argv[k], "--rectify") || !std::strcmp(argv[k], "--detect-fast")) {
-            (argv[k][2] == 'd' ? detect : rectify) = true;
+        if (!std::strcmp(argv[k], "--detect") || !std::strcmp(argv[k], "--rectify") || !std::strcmp(argv[k], "--detect-fast") ||
+            !std::strcmp(argv[k], "--inverse")) {
+            (argv[k][2] == 'd' ? detect : (argv[k][2] == 'i' ? inverse : rectify)) = true;
             if (!std::strcmp(argv[k], "--detect-fast")) fast = true;
             for (int j = k; j + 1 < argc; j++) argv[j] = argv[j + 1];
             argc--, k--;
         }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s [--detect | --detect-fast] [--rectify] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--detect | --detect-fast] [--rectify] [--inverse] sequence.bin [half_patch iterations pyramids]\n", argv[0]);
         return 2;
     }
     const int half = argc > 2 ? std::atoi(argv[2]) : 5, iters = argc > 3 ? std::atoi(argv[3]) : 10,
@@ -107,6 +111,7 @@ int main(int argc, char **argv)
     pagk_params_default(&p);
     p.half_patch = half, p.iterations = iters, p.pyramids = pyr;
     p.has_gyro_predict_initial = 1, p.consider_illumination = 1, p.consider_affine = 1, p.regularization_penalty = 0;
+    if (inverse) p.inverse = PAGK_INVERSE_TEMPLATE;
     p.fx = K[0], p.fy = K[4], p.cx = K[2], p.cy = K[5];
     p.n_dist_coef = 4;
     for (int k = 0; k < 4; k++) p.dist_coef[k] = dist[k];

@@ -35,7 +35,8 @@ enum {
     PAGK_E_ARG = -1,         /* null pointer / out-of-range parameter                     */
     PAGK_E_HIP = -2,         /* a HIP runtime call failed (see pagk_last_error)           */
     PAGK_E_NOMEM = -3,       /* device or host allocation failed                          */
-    PAGK_E_UNSUPPORTED = -4, /* inverse-compositional mode (reference: "not support yet") */
+    PAGK_E_UNSUPPORTED = -4, /* pagk_params::inverse other than 0 and PAGK_INVERSE_TEMPLATE (1 is the reference's
+                                bInverse_: "not support yet"); a variant or mode this build does not carry */
     PAGK_E_NODEVICE = -5,    /* no HIP device / HIP library could not initialise          */
     PAGK_E_NCCL = -6,        /* an RCCL call of the sharded path failed (see pagk_last_error) */
     PAGK_E_CAPACITY = -7     /* a caller-sized output array is too small (neighbour lists)  */
@@ -59,7 +60,9 @@ typedef struct pagk_params {
     int32_t iterations; /* iterations_     (reference call site: 10; BASELINE: 30)       */
     int32_t pyramids;   /* pyramids_       (reference call site: 3)                      */
     uint8_t has_gyro_predict_initial; /* bHasGyroPredictInitial_: 0 => pt_init ignored   */
-    uint8_t inverse;                  /* bInverse_: must be 0 (PAGK_E_UNSUPPORTED)        */
+    uint8_t inverse;                  /* 0 = forward mode (the reference's path).  1 = bInverse_, the reference's own
+                                         branch: PAGK_E_UNSUPPORTED, as there.  2 = PAGK_INVERSE_TEMPLATE, the library's
+                                         template-Jacobian mode defined below.  Others: PAGK_E_UNSUPPORTED.          */
     uint8_t consider_illumination;    /* bConsiderIllumination_                           */
     uint8_t consider_affine;          /* bConsiderAffineDeformation_                      */
     uint8_t regularization_penalty;   /* bRegularizationPenalty_                          */
@@ -82,6 +85,50 @@ typedef struct pagk_params {
     float dist_coef[5];      /* k1 k2 p1 p2 k3                                            */
     int32_t n_dist_coef;     /* 4 or 5 (mDistCoef.total()); k3 ignored unless 5           */
 } pagk_params;
+
+/* ---- Template-Jacobian mode: pagk_params::inverse == PAGK_INVERSE_TEMPLATE ---------------------------------------------
+ * The Gauss-Newton loop with the Jacobian taken from the REFERENCE image, once per pyramid level: what the reference's
+ * bInverse_ branch (src/patch_match.cpp:216-222, :265-275, :286-297) sets out to do and refuses ("not support yet", :220).
+ * Everything around the loop is the forward path unchanged: the level loop and its initial points (:177-183), dg = db = 0
+ * per level, warp_patch (:198-209), the member GetPixelValue, the residual (:252-253) with its association, the penalty
+ * (:302-314), solver_variant, the termination rules (:319-344), :348-353, NCC (:356-366), DistortPoints and SetMatcher.
+ *
+ * Per feature and level, with pt the reference point at the level, h = half_patch, pixel k = (y + h)(2h + 1) + (x + h) for
+ * y (outer) and x in -h .. h, I1 / I2 = GetPixelValue on the level of the reference / current image:
+ *   set-up, once, before iteration 0:
+ *     T_k  = I1(pt.x + x, pt.y + y)
+ *     Ix_k = (float)(0.5 * (I1(pt.x + x + 1, pt.y + y) - I1(pt.x + x - 1, pt.y + y)))      (:269-270)
+ *     Iy_k = (float)(0.5 * (I1(pt.x + x, pt.y + y + 1) - I1(pt.x + x, pt.y + y - 1)))      (:271-272)
+ *            coordinate sums left to right in f32; the f32 difference is widened, halved and narrowed
+ *     c    = I1(pt.x, pt.y);   J_k = (Ix_k, Iy_k, -c, 1) widened to f64                    (:273-274)
+ *     Hp   = sum_k J_k J_k^T:  ten f64 sums of exact products
+ *   every iteration:
+ *     e_k  = I2(pt.x + dx + wx_k, pt.y + dy + wy_k) + db - (1 + dg) * T_k                  (:252-253, (wx, wy) = warp_patch)
+ *     b    = sum_k (-J_k) (double)e_k      cost = sum_k e_k * e_k in f32      H = Hp
+ *     then the penalty (if set) on this fresh H, b and cost, the solve, and :319-344, as in the forward path.
+ * The sums.  Each of the fifteen sums over the patch is taken in one order that depends on half_patch alone -- not on the
+ * launch size, the entry point or any hardware state: pixel k belongs to slot k mod 64; a slot starts at +0.0 and adds its
+ * pixels in ascending k (a slot without pixels stays +0.0); then six steps v[s] = v[s] + v[s ^ m] over all 64 slots at
+ * once, m = 1, 2, 4, 8, 16, 32; the sum is v[0].  Accumulators are f64 for Hp and b, f32 for the cost.
+ * tests/inverse_ref.c restates the mode sequentially; every entry point returns its bits.
+ *
+ * Departures from the reference's branch: (1) the Jacobians are kept per pixel (the reference overwrites vJ[i] with an unset
+ * local from iteration 1 on and accumulates with the last pixel's Jacobian); (2) H is rebuilt from Hp in every iteration, so
+ * the penalty term does not pile up as :295-297 with :311 would have it; (3) the summation order is the library's own.
+ * Kept on purpose: -I1(pt), the patch CENTRE, as the gain column -- in exact arithmetic a singular H, as in the forward
+ * mode -- so that both modes fit the same model.
+ *
+ * A launch of this mode runs one kernel (csrc/pagk_inverse_kernel.h; every half_patch 1 .. 15) and pagk_last_variant reports
+ * 8 after it; pagk_has_variant(8) == 1.  pagk_set_kernel (1, 3, 5 and 7 included), the issue-priority hint, the dispatch
+ * order and the hand-over do not apply to such a launch.  pagk_track_device_fused runs pyramid and tracking as two launches,
+ * pagk_track_device_batch as k launches.  Accuracy is claimed where the coarsest level holds the patch (DESIGN.md,
+ * "Template-Jacobian mode"); the results are defined and reproducible everywhere. */
+#define PAGK_INVERSE_TEMPLATE 2
+
+/* check of a pagk_params as every tracking entry point applies it: PAGK_OK, PAGK_E_ARG (NULL, half_patch outside
+ * 1 .. PAGK_MAX_HALF_PATCH, iterations < 0, pyramids outside 1 .. PAGK_MAX_PYRAMIDS, an unknown solver_variant bit) or
+ * PAGK_E_UNSUPPORTED (inverse other than 0 and PAGK_INVERSE_TEMPLATE).  Needs no device. */
+int pagk_params_check(const pagk_params *params);
 
 /* Outputs == the six vectors PatchMatch::SetMatcher fills on the tracker
  * (src/patch_match.cpp:370-388, include/gyro_aided_tracker.h:214-219) plus an
@@ -189,8 +236,8 @@ int pagk_track_device_fused(pagk_ctx *ctx, const pagk_params *params, int32_t sl
  * in the device arrays d_pt_ref_un[j], d_pt_init_un[j], d_affine[j], d_status_in[j], results to d_out[j]; `params` is
  * common to all (the trackers of one application are configured alike).  Results per stream are bit-identical to its own
  * pagk_track_device.  From 6000 features in total (or pagk_set_kernel(ctxs[0], 7)) the streams are served by one launch
- * of variant 7 whose four-feature groups carry their stream; smaller batches, calculate_ncc and one-level pyramids run
- * as k launches.  The launch is issued on ctxs[0]'s stream: it waits for what the other contexts' streams have enqueued
+ * of variant 7 whose four-feature groups carry their stream; smaller batches, calculate_ncc, one-level pyramids and
+ * inverse == PAGK_INVERSE_TEMPLATE run as k launches.  The launch is issued on ctxs[0]'s stream: it waits for what the other contexts' streams have enqueued
  * so far, and their later work waits for it (contexts switched to one common stream with pagk_set_stream need neither,
  * and can be captured together: pagk_graph_begin(ctxs[0]) ... pagk_graph_end -- after the same call has been issued once
  * directly, at most four batched calls (of this kind and of pagk_frame_set_device_batch together) per capture: the stream descriptors a captured launch reads are buffers that
@@ -241,10 +288,11 @@ int pagk_set_stream(pagk_ctx *ctx, void *hip_stream);
 int pagk_set_kernel(pagk_ctx *ctx, int32_t which);
 /* Variants 2 and 6 no longer win at any launch size and nothing selects them automatically; the product's build leaves
  * them out (pagk_set_kernel returns PAGK_E_UNSUPPORTED for them) and a library compiled with -DPAGK_ALL_VARIANTS carries
- * them for cross-checks.  1 = `which` can be selected in this build. */
+ * them for cross-checks.  1 = `which` can be selected in this build; also for 8, the kernel of PAGK_INVERSE_TEMPLATE, which
+ * the parameters select and pagk_set_kernel does not. */
 int pagk_has_variant(int32_t which);
-/* The variant (numbering above; 0 = the 4-wave kernel) the last tracking launch of this context actually used;
- * -1 before the first launch. */
+/* The variant (numbering above; 0 = the 4-wave kernel; 8 = the kernel of PAGK_INVERSE_TEMPLATE) the last tracking launch
+ * of this context actually used; -1 before the first launch. */
 int pagk_last_variant(const pagk_ctx *ctx);
 
 /* Number of features the last tracking launch of this context handed from the throughput kernel to the latency

@@ -22,6 +22,7 @@ PAGK_E_UNSUPPORTED = -4
 PAGK_E_NODEVICE = -5
 PAGK_E_NCCL = -6
 PAGK_E_CAPACITY = -7
+PAGK_INVERSE_TEMPLATE = 2   # pagk_params::inverse: the template-Jacobian mode (include/pagk.h)
 
 
 class Image(C.Structure):
@@ -146,6 +147,11 @@ def make_params(*, half_patch=5, iterations=10, pyramids=3, has_gyro=True, illum
     return p
 
 
+def params_check(p: Params) -> int:
+    """pagk_params_check: the code every tracking entry point returns for these parameters (no device needed)."""
+    return int(load().pagk_params_check(C.byref(p)))
+
+
 def image_view(a: np.ndarray) -> Image:
     assert a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1
     return Image(a.ctypes.data, a.shape[1], a.shape[0], a.strides[0])
@@ -203,6 +209,9 @@ def declare(lib) -> None:
     lib.pagk_last_error.argtypes = [vp]
     lib.pagk_params_default.restype = None
     lib.pagk_params_default.argtypes = [_P(Params)]
+    if hasattr(lib, "pagk_params_check"):   # (an older build given through PAGK_LIB for an A/B run has no such check)
+        lib.pagk_params_check.restype = C.c_int
+        lib.pagk_params_check.argtypes = [_P(Params)]
     lib.pagk_inv_log_max_dist.restype = C.c_float
     lib.pagk_inv_log_max_dist.argtypes = [C.c_float, i32]
     lib.pagk_create.restype = C.c_int
@@ -474,7 +483,7 @@ def declare(lib) -> None:
 
 
 EXPORTED_SYMBOLS = [
-    "pagk_version", "pagk_strerror", "pagk_last_error", "pagk_params_default", "pagk_inv_log_max_dist",
+    "pagk_version", "pagk_strerror", "pagk_last_error", "pagk_params_default", "pagk_params_check", "pagk_inv_log_max_dist",
     "pagk_create", "pagk_destroy", "pagk_track", "pagk_track_pyr", "pagk_frame_upload", "pagk_frame_upload_pinned",
     "pagk_frame_set_device", "pagk_frame_download_level", "pagk_track_device", "pagk_track_device_fused", "pagk_sync",
     "pagk_set_stream", "pagk_set_kernel", "pagk_last_variant", "pagk_set_concurrency", "pagk_last_handover", "pagk_last_kernel_ms", "pagk_post_filter", "pagk_gyro_predict_device",

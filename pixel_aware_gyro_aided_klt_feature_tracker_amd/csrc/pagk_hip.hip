@@ -15,6 +15,7 @@
 
 #include "../../include/pagk.h"
 #include "pagk_kernels.h"
+#include "pagk_inverse_kernel.h"
 #include "pagk_associate_kernel.h"
 #include "pagk_pose_kernel.h"
 #include "pagk_layout.h"
@@ -564,7 +565,8 @@ int check_params(const pagk_params *p)
     if (!p) return PAGK_E_ARG;
     if (p->half_patch < 1 || p->half_patch > PAGK_MAX_HALF_PATCH) return PAGK_E_ARG;
     if (p->iterations < 0 || p->pyramids < 1 || p->pyramids > PAGK_MAX_PYRAMIDS) return PAGK_E_ARG;
-    if (p->inverse) return PAGK_E_UNSUPPORTED;        // src/patch_match.cpp:220 "not support yet"
+    // 1 is the reference's own bInverse_ (src/patch_match.cpp:220 "not support yet"); 2 the library's template-Jacobian mode
+    if (p->inverse != 0 && p->inverse != PAGK_INVERSE_TEMPLATE) return PAGK_E_UNSUPPORTED;
     if (p->solver_variant & ~(SV_LOWER_SEQ | SV_UPPER_TREE | SV_NORM_SEQ | SV_LLT_RECIP | SV_PIVOT_TREE)) return PAGK_E_ARG;
     return PAGK_OK;
 }
@@ -653,6 +655,26 @@ constexpr std::array<TrackKernels, sizeof...(H0)> track_table(std::integer_seque
 }
 constexpr auto kTrackTable = track_table(std::make_integer_sequence<int, PAGK_MAX_HALF_PATCH>{});
 const TrackKernels &track_kernels_of(int half) { return kTrackTable[(size_t)half - 1]; }   // half: 1..15 (check_params)
+
+// PAGK_INVERSE_TEMPLATE (pagk_inverse_kernel.h): one kernel, instantiated for every half patch, [lean] as above.
+struct InverseKernels {
+    TrackFn wave[2] = {};
+};
+template <int H>
+constexpr InverseKernels inverse_kernels()
+{
+    constexpr PatchShape s = patch_shape(H);
+    InverseKernels k;
+    k.wave[0] = k_inv_wave<s.nch, s.tail>;
+    k.wave[1] = k_inv_wave<s.nch, s.tail, true>;
+    return k;
+}
+template <int... H0>
+constexpr std::array<InverseKernels, sizeof...(H0)> inverse_table(std::integer_sequence<int, H0...>)
+{
+    return {inverse_kernels<H0 + 1>()...};
+}
+constexpr auto kInverseTable = inverse_table(std::make_integer_sequence<int, PAGK_MAX_HALF_PATCH>{});
 
 #ifdef PAGK_ALL_VARIANTS
 constexpr bool kAllVariants = true;
@@ -1022,10 +1044,15 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
         // compile-time facts (LEAN); everything else runs the generic instantiations
         const bool lean = !a.penalty && a.solver == 0;
         const TrackKernels &k = track_kernels_of(a.half);
-        const int variant = ctx->last_variant = select_variant(select_in(ctx, p, n));
+        // the template-Jacobian mode has one kernel: pagk_set_kernel, the priority hint, the dispatch order and the hand-over do
+        // not apply to such a launch, and a pyramid offered for fusing is left to the caller (*pyr_done stays false)
+        const int variant = ctx->last_variant = p->inverse == PAGK_INVERSE_TEMPLATE ? 8 : select_variant(select_in(ctx, p, n));
         int rc = PAGK_OK;
         hipError_t e = hipSuccess;
         switch (variant) {
+            case 8:   // pagk_inverse_kernel.h
+                e = launch(kInverseTable[(size_t)a.half - 1].wave[lean], n, 64, inv_wave_lds_bytes(a.half, a.calc_ncc != 0), ctx->stream, a);
+                break;
             case 1: e = launch(k_track_thread, (n + 63) / 64, 64, 0, ctx->stream, a); break;
             case 2: e = launch(k.mfma[lean], n, 128, track_mfma_lds_bytes(a.half), ctx->stream, a); break;
             case 3: e = launch(k.wave[lean], n, 64, track_wave_lds_bytes(a.half), ctx->stream, a); break;   // pagk_wave_kernel.h
@@ -1345,6 +1372,7 @@ int pagk_set_stream(pagk_ctx *ctx, void *hip_stream)
 // instantiations.
 int pagk_has_variant(int32_t which)
 {
+    if (which == 8) return 1;   // what pagk_last_variant reports after a PAGK_INVERSE_TEMPLATE launch; no pagk_set_kernel value
     return which >= 0 && which <= 7 && (kAllVariants || (which != 2 && which != 6));
 }
 
@@ -1358,6 +1386,8 @@ int pagk_set_kernel(pagk_ctx *ctx, int32_t which)
     ctx->kernel = which;
     return PAGK_OK;
 }
+
+int pagk_params_check(const pagk_params *params) { return check_params(params); }
 
 int pagk_last_variant(const pagk_ctx *ctx) { return ctx ? ctx->last_variant : PAGK_E_ARG; }
 
@@ -1940,7 +1970,8 @@ int pagk_track_device_batch(pagk_ctx *const *ctxs, int32_t k, const pagk_params 
         total_q += (n[j] + 3) / 4;
     }
     HIPCHK(lead, hipSetDevice(lead->device));
-    const bool batched = select_batched(select_in(lead, params, 0), total_n, total_q);
+    // (the template-Jacobian mode has no batched kernel: k launches)
+    const bool batched = params->inverse == 0 && select_batched(select_in(lead, params, 0), total_n, total_q);
     if (!batched) {
         // every stream as its own launch on its own context (small batches, NCC launches, a forced variant)
         for (int j = 0; j < k; j++) {
