@@ -712,6 +712,38 @@ class PagkError(RuntimeError):
         super().__init__(f"{where}: {msg} ({code}){': ' + detail if detail else ''}")
 
 
+def _handover_args(h, params: Params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un,
+                   *outs, device: bool = True):
+    """(head, tail) of the arguments of every pagk_frame_handover* entry point; the candidates' source goes between them.
+    outs: keys, keys_un, keys_normal, index_in_last, live, mask, state and, for a detecting form, info.  The device forms
+    share one guard."""
+    if device and cap < target_n:
+        raise ValueError("cap must be at least target_n")
+    head = (h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(status), _ptr(pt_predict),
+            _ptr(pt_predict_un))
+    return head, tuple(_ptr(a) for a in outs)
+
+
+def _handover_host_arrays(width, height, cap, status, pt_predict, pt_predict_un, state, with_info: bool):
+    """The host forms' shared part -> ((status, pt_predict, pt_predict_un) padded to cap, the dictionary that the call fills
+    and returns: its values in the order of _handover_args' outs, `state` a copy)."""
+    def pad(a, dtype, width_):
+        out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
+        a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
+        if a.shape[0] > cap:
+            raise ValueError("more entries than cap")
+        out[:a.shape[0]] = a
+        return out
+    ins = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
+    state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+    out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
+               keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
+               live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state)
+    if with_info:
+        out["info"] = np.zeros(DETECT_INFO_WORDS, np.int32)
+    return ins, out
+
+
 class Context:
     """pagk_ctx owner.  One per GPU / host thread."""
 
@@ -1117,27 +1149,17 @@ class Context:
                               d_n_cand, d_cand_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
                               d_state):
         """pagk_frame_handover_device on device arrays (asynchronous, capturable)."""
-        if cap < target_n:
-            raise ValueError("cap must be at least target_n")
-        self._check(self.lib.pagk_frame_handover_device(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
-            _ptr(d_pt_predict), _ptr(d_pt_predict_un), cand_cap, _ptr(d_n_cand), _ptr(d_cand_un), _ptr(d_keys),
-            _ptr(d_keys_un), _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state)),
-            "pagk_frame_handover_device")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                                    d_pt_predict_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask, d_state)
+        self._check(self.lib.pagk_frame_handover_device(*head, cand_cap, _ptr(d_n_cand), _ptr(d_cand_un), *tail),
+                    "pagk_frame_handover_device")
 
     def frame_handover(self, params: Params, width: int, height: int, cap: int, target_n: int,
                        new_point_threshold: float, status, pt_predict, pt_predict_un, candidates, state=None,
                        cand_cap: int | None = None) -> dict:
         """pagk_frame_handover, host buffers -> dict(keys, keys_un, keys_normal, index_in_last, live, mask, state).
         `state` (8 int32, reach_flag in [1]) is copied, not updated in place; status / points are padded to cap."""
-        def pad(a, dtype, width_):
-            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
-            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
-            if a.shape[0] > cap:
-                raise ValueError("more entries than cap")
-            out[:a.shape[0]] = a
-            return out
-        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
+        ins, out = _handover_host_arrays(width, height, cap, status, pt_predict, pt_predict_un, state, False)
         cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 2)
         cc = cand.shape[0] if cand_cap is None else int(cand_cap)
         if cc < cand.shape[0]:
@@ -1145,14 +1167,9 @@ class Context:
         cbuf = np.zeros((max(cc, 1), 2), np.float32)
         cbuf[:cand.shape[0]] = cand
         ncand = np.array([cand.shape[0]], np.int32)
-        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
-        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
-                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
-                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state)
-        self._check(self.lib.pagk_frame_handover(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
-            _ptr(ppu), cc, _ptr(ncand), _ptr(cbuf), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
-            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state)), "pagk_frame_handover")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, *ins, *out.values(),
+                                    device=False)
+        self._check(self.lib.pagk_frame_handover(*head, cc, _ptr(ncand), _ptr(cbuf), *tail), "pagk_frame_handover")
         return out
 
     # the corner detector (reference src/frame.cpp:156-218: goodFeaturesToTrack with the Harris response) -------
@@ -1195,13 +1212,11 @@ class Context:
                                      d_live, d_mask, d_state, d_info):
         """pagk_frame_handover_detect_device on device arrays (asynchronous, capturable): the hand-over with the
         candidates detected on level 0 of frame slot `slot` under the mask the call builds."""
-        if cap < target_n:
-            raise ValueError("cap must be at least target_n")
-        self._check(self.lib.pagk_frame_handover_detect_device(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
-            _ptr(d_pt_predict), _ptr(d_pt_predict_un), C.byref(det), slot, _ptr(d_keys), _ptr(d_keys_un),
-            _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state), _ptr(d_info)),
-            "pagk_frame_handover_detect_device")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                                    d_pt_predict_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask, d_state,
+                                    d_info)
+        self._check(self.lib.pagk_frame_handover_detect_device(*head, C.byref(det), slot, *tail),
+                    "pagk_frame_handover_detect_device")
 
     def frame_handover_detect(self, params: Params, img: np.ndarray, cap: int, target_n: int, new_point_threshold: float,
                               status, pt_predict, pt_predict_un, det: DetectParams | None = None, state=None) -> dict:
@@ -1209,26 +1224,11 @@ class Context:
         info).  `state` is copied, not updated in place; status / points are padded to cap."""
         det = det if det is not None else detect_params_default()
         height, width = img.shape
-
-        def pad(a, dtype, width_):
-            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
-            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
-            if a.shape[0] > cap:
-                raise ValueError("more entries than cap")
-            out[:a.shape[0]] = a
-            return out
-        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
-        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+        ins, out = _handover_host_arrays(width, height, cap, status, pt_predict, pt_predict_un, state, True)
         iv = image_view(img)
-        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
-                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
-                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state,
-                   info=np.zeros(DETECT_INFO_WORDS, np.int32))
-        self._check(self.lib.pagk_frame_handover_detect(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
-            _ptr(ppu), C.byref(det), C.byref(iv), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
-            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
-            "pagk_frame_handover_detect")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, *ins, *out.values(),
+                                    device=False)
+        self._check(self.lib.pagk_frame_handover_detect(*head, C.byref(det), C.byref(iv), *tail), "pagk_frame_handover_detect")
         return out
 
     # the detector of the reference's front-ends (src/ORBextractor.cc:1148-1205: FAST in cells, then the quadtree) ----
@@ -1279,13 +1279,11 @@ class Context:
                                    d_info):
         """pagk_frame_handover_fast_device on device arrays (asynchronous, capturable): the hand-over with the
         candidates = the FAST-and-quadtree detector's output on level 0 of frame slot `slot`."""
-        if cap < target_n:
-            raise ValueError("cap must be at least target_n")
-        self._check(self.lib.pagk_frame_handover_fast_device(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(d_status),
-            _ptr(d_pt_predict), _ptr(d_pt_predict_un), C.byref(fast), slot, _ptr(d_keys), _ptr(d_keys_un),
-            _ptr(d_keys_normal), _ptr(d_index_in_last), _ptr(d_live), _ptr(d_mask), _ptr(d_state), _ptr(d_info)),
-            "pagk_frame_handover_fast_device")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
+                                    d_pt_predict_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask, d_state,
+                                    d_info)
+        self._check(self.lib.pagk_frame_handover_fast_device(*head, C.byref(fast), slot, *tail),
+                    "pagk_frame_handover_fast_device")
 
     def frame_handover_fast(self, params: Params, img: np.ndarray, cap: int, target_n: int, new_point_threshold: float,
                             status, pt_predict, pt_predict_un, fast: FastParams | None = None, state=None) -> dict:
@@ -1293,26 +1291,11 @@ class Context:
         info).  `state` is copied, not updated in place; status / points are padded to cap."""
         fast = fast if fast is not None else fast_params_default()
         height, width = img.shape
-
-        def pad(a, dtype, width_):
-            out = np.zeros((cap, width_) if width_ > 1 else (cap,), dtype)
-            a = np.asarray(a, dtype).reshape((-1, width_) if width_ > 1 else (-1,))
-            if a.shape[0] > cap:
-                raise ValueError("more entries than cap")
-            out[:a.shape[0]] = a
-            return out
-        st, pp, ppu = pad(status, np.uint8, 1), pad(pt_predict, np.float32, 2), pad(pt_predict_un, np.float32, 2)
-        state = np.zeros(HANDOVER_STATE_WORDS, np.int32) if state is None else np.array(state, np.int32, copy=True)
+        ins, out = _handover_host_arrays(width, height, cap, status, pt_predict, pt_predict_un, state, True)
         iv = image_view(img)
-        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
-                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32),
-                   live=np.zeros(cap, np.uint8), mask=np.zeros((height, width), np.uint8), state=state,
-                   info=np.zeros(DETECT_INFO_WORDS, np.int32))
-        self._check(self.lib.pagk_frame_handover_fast(
-            self.h, C.byref(params), width, height, cap, target_n, float(new_point_threshold), _ptr(st), _ptr(pp),
-            _ptr(ppu), C.byref(fast), C.byref(iv), _ptr(out["keys"]), _ptr(out["keys_un"]), _ptr(out["keys_normal"]),
-            _ptr(out["index_in_last"]), _ptr(out["live"]), _ptr(out["mask"]), _ptr(state), _ptr(out["info"])),
-            "pagk_frame_handover_fast")
+        head, tail = _handover_args(self.h, params, width, height, cap, target_n, new_point_threshold, *ins, *out.values(),
+                                    device=False)
+        self._check(self.lib.pagk_frame_handover_fast(*head, C.byref(fast), C.byref(iv), *tail), "pagk_frame_handover_fast")
         return out
 
     # rectification: a raw camera frame (distorted, 1 / 3 / 4 channels) into a frame slot ----

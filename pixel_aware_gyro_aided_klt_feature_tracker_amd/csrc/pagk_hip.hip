@@ -2288,98 +2288,6 @@ int pagk_post_filter_device(pagk_ctx *ctx, int32_t n, int32_t half_patch, const 
     return PAGK_OK;
 }
 
-// ---- frame hand-over (pagk_handover_kernel.h) ------------------------------------------------------------------
-namespace {
-
-bool handover_args_ok(const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
-                      double new_point_threshold, int32_t cand_cap)
-{
-    // 14 = the mask's hole (src/frame.cpp:117-119): a smaller image has no place for one
-    return params && width >= 14 && height >= 14 && (int64_t)width * height <= 0x7fffffff && cap >= 1 && target_n >= 0 &&
-           cap >= target_n && cand_cap >= 0 && !std::isnan(new_point_threshold);
-}
-
-// The tracking launches' hints (pagk_prio.h) are per feature SLOT: a survivor that moves to a new slot takes its hint along, a
-// new or an unused slot has none.  The array as it stands when the hand-over is issued (none before the first launch).
-void handover_hint_args(pagk_ctx *ctx, HandoverArgs *a)
-{
-    const DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
-    a->prio_hint = static_cast<int32_t *>(hb.ptr);
-    a->prio_hint_n = (int32_t)(hb.bytes / sizeof(int32_t));
-}
-
-// the sizes, the rule's constants and the camera model of a hand-over; the pointers are the caller's to fill
-void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                        int32_t target_n, double new_point_threshold)
-{
-    HandoverArgs a;
-    memset(&a, 0, sizeof a);
-    a.cap = cap, a.width = width, a.height = height, a.target_n = target_n;
-    a.new_point_threshold = new_point_threshold;
-    a.fx = params->fx, a.fy = params->fy, a.cx = params->cx, a.cy = params->cy;
-    a.fx_inv = (float)(1.0 / (double)params->fx);  // src/frame.cpp:70
-    a.fy_inv = (float)(1.0 / (double)params->fy);
-    a.k1 = params->dist_coef[0], a.k2 = params->dist_coef[1], a.p1 = params->dist_coef[2], a.p2 = params->dist_coef[3];
-    a.k3 = params->n_dist_coef == 5 ? params->dist_coef[4] : 0.0f;
-    a.distort_on = params->dist_coef[0] != 0.0f;
-    *out = a;
-}
-
-// The hand-over's launches on the context's stream: fill -> holes -> [plan -> detector] -> keys.  Without d_mask the
-// context's own mask is used.  With the detector leg (det, the frame's slot s, d_info) the candidates are not the
-// caller's but the corners found under the mask: at most n_new <= target_n <= cap of them, counted in d_info[0].
-int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
-                    double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
-                    const float *d_pt_predict_un, int32_t cand_cap, const int32_t *d_n_cand, const float *d_cand_un,
-                    float *d_keys, float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live,
-                    uint8_t *d_mask, int32_t *d_state, const pagk_detect_params *det = nullptr,
-                    const FrameSlot *s = nullptr, int32_t *d_info = nullptr);
-
-// The host-buffer hand-overs: the caller's arrays through one device block around the device step.  The candidates are the
-// caller's list (neither det nor fast), or the corners (det) or FAST keypoints (fast) found on scratch slot 4 and counted
-// in info.
-int handover_host(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
-                  double new_point_threshold, const uint8_t *status, const float *pt_predict, const float *pt_predict_un,
-                  int32_t cand_cap, const int32_t *n_cand, const float *cand_un, const pagk_detect_params *det,
-                  const pagk_fast_params *fast, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
-                  uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info);
-
-}  // namespace
-
-int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                               int32_t target_n, double new_point_threshold, const uint8_t *d_status,
-                               const float *d_pt_predict, const float *d_pt_predict_un, int32_t cand_cap,
-                               const int32_t *d_n_cand, const float *d_cand_un, float *d_keys, float *d_keys_un,
-                               float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
-                               int32_t *d_state)
-{
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, cand_cap)) return PAGK_E_ARG;
-    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_n_cand || (cand_cap > 0 && !d_cand_un) || !d_keys ||
-        !d_keys_un || !d_index_in_last || !d_live || !d_state)
-        return PAGK_E_ARG;
-    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
-    return handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
-                           d_pt_predict_un, cand_cap, d_n_cand, d_cand_un, d_keys, d_keys_un, d_keys_normal, d_index_in_last,
-                           d_live, d_mask, d_state);
-}
-
-int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                        int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
-                        const float *pt_predict_un, int32_t cand_cap, const int32_t *n_cand, const float *cand_un,
-                        float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live,
-                        uint8_t *mask, int32_t *state)
-{
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, cand_cap)) return PAGK_E_ARG;
-    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover");
-    if (!status || !pt_predict || !pt_predict_un || !n_cand || (cand_cap > 0 && !cand_un) || !keys || !keys_un ||
-        !index_in_last || !live || !state)
-        return PAGK_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un,
-                         cand_cap, n_cand, cand_un, nullptr, nullptr, keys, keys_un, keys_normal, index_in_last, live, mask, state,
-                         nullptr);
-}
-
 // ---- corner detection (pagk_detect_kernel.h) -------------------------------------------------------------------
 namespace {
 
@@ -2498,50 +2406,6 @@ int detect_corners_slot(pagk_ctx *ctx, const pagk_detect_params *det, int32_t sl
     return detect_launch(ctx, det, s, d_mask, cap, d_max_corners, nullptr, d_corners, d_info, ws);
 }
 
-int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
-                    double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
-                    const float *d_pt_predict_un, int32_t cand_cap, const int32_t *d_n_cand, const float *d_cand_un,
-                    float *d_keys, float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live,
-                    uint8_t *d_mask, int32_t *d_state, const pagk_detect_params *det, const FrameSlot *s, int32_t *d_info)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int64_t bytes = (int64_t)width * height;
-    DevBuf &hand = ctx->buf[pagk_ctx::HAND];   // the context's own mask, for a caller that passes none
-    int rc = d_mask ? PAGK_OK
-                    : reserve(ctx, hand, align_up((size_t)bytes, kPartAlign), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the hand-over's mask",
-                              "run the call once with this image size before capturing, or pass d_mask");
-    if (rc) return rc;
-    uint8_t *mask = d_mask ? d_mask : static_cast<uint8_t *>(hand.ptr);
-    DetectWs ws;
-    if (det) {
-        if ((rc = detect_workspace(ctx, det, width, height, cap, &ws))) return rc;
-        cand_cap = cap, d_n_cand = d_info, d_cand_un = ws.cand;
-    }
-    HandoverArgs a;
-    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
-    a.cand_cap = cand_cap;
-    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
-    a.n_cand = d_n_cand, a.cand_un = d_cand_un;
-    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
-    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
-    handover_hint_args(ctx, &a);
-    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
-                       width, height, d_status, d_pt_predict_un, mask);
-    HIPCHK(ctx, hipGetLastError());
-    if (det) {
-        hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
-                           (const int32_t *)d_state, ws.ctl);
-        HIPCHK(ctx, hipGetLastError());
-        if ((rc = detect_launch(ctx, det, *s, mask, cap, ws.ctl + kDetCtlLimit, ws.ctl + kDetCtlSkip, ws.cand, d_info, ws)))
-            return rc;
-    }
-    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
-    HIPCHK(ctx, hipGetLastError());
-    return PAGK_OK;
-}
-
 }  // namespace
 
 void pagk_detect_params_default(pagk_detect_params *p)
@@ -2594,45 +2458,6 @@ int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R
     HIPCHK(ctx, hipMemcpyAsync(R, ws.R, (size_t)img->width * img->height * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PAGK_OK;
-}
-
-int pagk_frame_handover_detect_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
-                                      int32_t cap, int32_t target_n, double new_point_threshold, const uint8_t *d_status,
-                                      const float *d_pt_predict, const float *d_pt_predict_un,
-                                      const pagk_detect_params *det, int32_t slot, float *d_keys, float *d_keys_un,
-                                      float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
-                                      int32_t *d_state, int32_t *d_info)
-{
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0) || !detect_params_ok(det) ||
-        slot < 0 || slot >= kUserSlots)
-        return PAGK_E_ARG;
-    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_keys || !d_keys_un || !d_index_in_last || !d_live || !d_state ||
-        !d_info)
-        return PAGK_E_ARG;
-    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
-    const FrameSlot &s = ctx->slots[slot];
-    if (!detect_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
-    return handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
-                           d_pt_predict_un, 0, nullptr, nullptr, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live,
-                           d_mask, d_state, det, &s, d_info);
-}
-
-int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                               int32_t target_n, double new_point_threshold, const uint8_t *status,
-                               const float *pt_predict, const float *pt_predict_un, const pagk_detect_params *det,
-                               const pagk_image *img, float *keys, float *keys_un, float *keys_normal,
-                               int32_t *index_in_last, uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info)
-{
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0) || !detect_params_ok(det))
-        return PAGK_E_ARG;
-    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover_detect");
-    if (!status || !pt_predict || !pt_predict_un || !img || img->width != width || img->height != height || !keys || !keys_un ||
-        !index_in_last || !live || !state)
-        return PAGK_E_ARG;
-    int rc = frame_upload_any(ctx, 4, img, 1);
-    if (rc) return rc;
-    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, 0,
-                         nullptr, nullptr, det, nullptr, keys, keys_un, keys_normal, index_in_last, live, mask, state, info);
 }
 
 // ---- the FAST detector: cells and quadtree (pagk_fast_kernel.h) --------------------------------------------------
@@ -2745,51 +2570,6 @@ int fast_launch(pagk_ctx *ctx, const pagk_fast_params *fp, int32_t n_features, c
 
 bool fast_slot_ok(const FrameSlot &s) { return s.valid && s.img0; }
 
-// pagk_frame_handover_device with the candidate list = the FAST detector's output on slot `s`, no mask: fill -> holes ->
-// plan -> detector -> keys.  The acceptance test of k_handover_keys is the reference's mask test (:1199-1203).
-int handover_fast_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                         int32_t target_n, double new_point_threshold, const uint8_t *d_status, const float *d_pt_predict,
-                         const float *d_pt_predict_un, const pagk_fast_params *fp, const FrameSlot &s, float *d_keys,
-                         float *d_keys_un, float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
-                         int32_t *d_state, int32_t *d_info)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    FastGrid g;
-    if (!fast_grid(width, height, &g)) return PAGK_E_ARG;
-    const int32_t n_features = fp->n_features ? fp->n_features : target_n;
-    if (n_features < 1) return PAGK_E_ARG;
-    const int64_t bytes = (int64_t)width * height;
-    DevBuf &hand = ctx->buf[pagk_ctx::HAND];   // the context's own mask, for a caller that passes none
-    int rc = d_mask ? PAGK_OK
-                    : reserve(ctx, hand, align_up((size_t)bytes, kPartAlign), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the hand-over's mask",
-                              "run the call once with this image size before capturing, or pass d_mask");
-    if (rc) return rc;
-    uint8_t *mask = d_mask ? d_mask : static_cast<uint8_t *>(hand.ptr);
-    FastWs ws;
-    if ((rc = fast_workspace(ctx, g, n_features, &ws))) return rc;
-    HandoverArgs a;
-    handover_fill_args(&a, params, width, height, cap, target_n, new_point_threshold);
-    a.cand_cap = ws.out_bound;
-    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
-    a.n_cand = d_info, a.cand_un = ws.cand;
-    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
-    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = mask, a.state = d_state;
-    handover_hint_args(ctx, &a);
-    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
-                       width, height, d_status, d_pt_predict_un, mask);
-    HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, d_status,
-                       (const int32_t *)d_state, ws.ctl);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = fast_launch(ctx, fp, n_features, s, g, nullptr, ws.out_bound, ws.cand, nullptr, d_info, ws.ctl + kFastCtlSkip, ws)))
-        return rc;
-    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, a);
-    HIPCHK(ctx, hipGetLastError());
-    return PAGK_OK;
-}
-
 }  // namespace
 
 void pagk_fast_params_default(pagk_fast_params *p)
@@ -2885,73 +2665,278 @@ int pagk_selftest_fast_cells(pagk_ctx *ctx, const pagk_fast_params *params, cons
     return PAGK_OK;
 }
 
-static int handover_fast_slot(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
-                              int32_t target_n, double new_point_threshold, const uint8_t *d_status,
-                              const float *d_pt_predict, const float *d_pt_predict_un, const pagk_fast_params *fast,
-                              int32_t slot, float *d_keys, float *d_keys_un, float *d_keys_normal,
-                              int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask, int32_t *d_state,
-                              int32_t *d_info)
-{
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0)) return PAGK_E_ARG;
-    int rc = fast_params_check(fast);
-    if (rc) return rc;
-    if (slot < 0 || slot >= kSlots) return PAGK_E_ARG;
-    if (!d_status || !d_pt_predict || !d_pt_predict_un || !d_keys || !d_keys_un || !d_index_in_last || !d_live || !d_state ||
-        !d_info)
-        return PAGK_E_ARG;
-    if (d_keys == d_pt_predict || d_keys_un == d_pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
-    const FrameSlot &s = ctx->slots[slot];
-    if (!fast_slot_ok(s) || s.w != width || s.h != height) return PAGK_E_ARG;
-    return handover_fast_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
-                                d_pt_predict_un, fast, s, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
-                                d_state, d_info);
-}
-
+// ---- frame hand-over (pagk_handover_kernel.h) ------------------------------------------------------------------
+// Behind the two detectors, whose workspaces and launches it uses.
 namespace {
 
-int handover_host(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
-                  double new_point_threshold, const uint8_t *status, const float *pt_predict, const float *pt_predict_un,
-                  int32_t cand_cap, const int32_t *n_cand, const float *cand_un, const pagk_detect_params *det,
-                  const pagk_fast_params *fast, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
-                  uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info)
+// The hand-over's arrays: the device's for the check and the launch, the caller's for handover_host.  keys_normal may be
+// NULL; without a mask the device forms use the context's own and the host forms copy none out.
+struct HandoverArrays {
+    const uint8_t *status = nullptr;
+    const float *pt_predict = nullptr, *pt_predict_un = nullptr;
+    float *keys = nullptr, *keys_un = nullptr, *keys_normal = nullptr;
+    int32_t *index_in_last = nullptr;
+    uint8_t *live = nullptr, *mask = nullptr;
+    int32_t *state = nullptr;
+};
+
+// Where the candidates come from: the caller's list, or what a detector finds on level 0 of a frame slot and counts in info.
+struct HandoverSource {
+    enum Kind { GIVEN, CORNERS, FAST } kind = GIVEN;
+    int32_t cand_cap = 0;                    // GIVEN
+    const int32_t *n_cand = nullptr;
+    const float *cand_un = nullptr;
+    const pagk_detect_params *det = nullptr; // CORNERS
+    const pagk_fast_params *fast = nullptr;  // FAST
+    int32_t slot = 4;                        // CORNERS, FAST (the host forms detect on scratch slot 4)
+    int32_t *info = nullptr;
+};
+
+bool handover_args_ok(const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                      double new_point_threshold, int32_t cand_cap)
 {
-    const bool given = !det && !fast;   // the caller's candidates: a count and a list go in, no info comes out
-    const size_t nc = (size_t)cap, cc = (size_t)(cand_cap > 0 ? cand_cap : 1), px = (size_t)width * height;
+    // 14 = the mask's hole (src/frame.cpp:117-119): a smaller image has no place for one
+    return params && width >= 14 && height >= 14 && (int64_t)width * height <= 0x7fffffff && cap >= 1 && target_n >= 0 &&
+           cap >= target_n && cand_cap >= 0 && !std::isnan(new_point_threshold);
+}
+
+// What every form refuses first: the geometry, then the source's parameter block (whose code may be PAGK_E_UNSUPPORTED).
+int handover_geometry_check(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                            int32_t target_n, double new_point_threshold, const HandoverSource &src)
+{
+    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, src.cand_cap)) return PAGK_E_ARG;
+    switch (src.kind) {
+    case HandoverSource::GIVEN: return PAGK_OK;
+    case HandoverSource::CORNERS: return detect_params_ok(src.det) ? PAGK_OK : PAGK_E_ARG;
+    case HandoverSource::FAST: return fast_params_check(src.fast);
+    }
+    return PAGK_E_ARG;
+}
+
+// the arrays no form does without, the device's or the caller's
+bool handover_required(const HandoverArrays &a, const HandoverSource &src)
+{
+    if (src.kind == HandoverSource::GIVEN && (!src.n_cand || (src.cand_cap > 0 && !src.cand_un))) return false;
+    return a.status && a.pt_predict && a.pt_predict_un && a.keys && a.keys_un && a.index_in_last && a.live && a.state;
+}
+
+// Everything a device form refuses, in front of handover_launch.
+int handover_check(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                   double new_point_threshold, const HandoverArrays &a, const HandoverSource &src)
+{
+    const bool given = src.kind == HandoverSource::GIVEN;
+    if (!given && (src.slot < 0 || src.slot >= kUserSlots)) return PAGK_E_ARG;   // (slots 4 and 5 are the host-buffer forms' own)
+    int rc = handover_geometry_check(ctx, params, width, height, cap, target_n, new_point_threshold, src);
+    if (rc) return rc;
+    if (!handover_required(a, src) || (!given && !src.info)) return PAGK_E_ARG;
+    if (a.keys == a.pt_predict || a.keys_un == a.pt_predict_un) return PAGK_E_ARG;  // the caller ping-pongs two sets
+    if (given) return PAGK_OK;
+    const FrameSlot &s = ctx->slots[src.slot];
+    const bool slot_ok = src.kind == HandoverSource::CORNERS ? detect_slot_ok(s) : fast_slot_ok(s);
+    return slot_ok && s.w == width && s.h == height ? PAGK_OK : PAGK_E_ARG;
+}
+
+// The tracking launches' hints (pagk_prio.h) are per feature SLOT: a survivor that moves to a new slot takes its hint along, a
+// new or an unused slot has none.  The array as it stands when the hand-over is issued (none before the first launch).
+void handover_hint_args(pagk_ctx *ctx, HandoverArgs *a)
+{
+    const DevBuf &hb = ctx->buf[pagk_ctx::PRIO_HINT];
+    a->prio_hint = static_cast<int32_t *>(hb.ptr);
+    a->prio_hint_n = (int32_t)(hb.bytes / sizeof(int32_t));
+}
+
+// the sizes, the rule's constants and the camera model of a hand-over; the pointers are the caller's to fill
+void handover_fill_args(HandoverArgs *out, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                        int32_t target_n, double new_point_threshold)
+{
+    HandoverArgs a;
+    memset(&a, 0, sizeof a);
+    a.cap = cap, a.width = width, a.height = height, a.target_n = target_n;
+    a.new_point_threshold = new_point_threshold;
+    a.fx = params->fx, a.fy = params->fy, a.cx = params->cx, a.cy = params->cy;
+    a.fx_inv = (float)(1.0 / (double)params->fx);  // src/frame.cpp:70
+    a.fy_inv = (float)(1.0 / (double)params->fy);
+    a.k1 = params->dist_coef[0], a.k2 = params->dist_coef[1], a.p1 = params->dist_coef[2], a.p2 = params->dist_coef[3];
+    a.k3 = params->n_dist_coef == 5 ? params->dist_coef[4] : 0.0f;
+    a.distort_on = params->dist_coef[0] != 0.0f;
+    *out = a;
+}
+
+// The hand-over's launches on the context's stream: fill -> holes -> [plan -> detector] -> keys.  Without a.mask the
+// context's own mask is used.  A detecting source's candidates are not the caller's but what its detector finds on the
+// frame's slot, counted in info[0]: the corners under the mask the call has just built (at most n_new <= target_n <= cap),
+// or the FAST keypoints of the whole frame (no mask: the acceptance test of k_handover_keys is the reference's mask test,
+// src/ORBextractor.cc:1199-1203).
+int handover_launch(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                    double new_point_threshold, const HandoverArrays &a, const HandoverSource &src)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    FastGrid g;
+    int32_t n_features = 0;
+    if (src.kind == HandoverSource::FAST) {   // (refused before anything is reserved)
+        if (!fast_grid(width, height, &g)) return PAGK_E_ARG;
+        n_features = src.fast->n_features ? src.fast->n_features : target_n;
+        if (n_features < 1) return PAGK_E_ARG;
+    }
+    const int64_t bytes = (int64_t)width * height;
+    DevBuf &hand = ctx->buf[pagk_ctx::HAND];   // the context's own mask, for a caller that passes none
+    int rc = a.mask ? PAGK_OK
+                    : reserve(ctx, hand, align_up((size_t)bytes, kPartAlign), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the hand-over's mask",
+                              "run the call once with this image size before capturing, or pass d_mask");
+    if (rc) return rc;
+    uint8_t *mask = a.mask ? a.mask : static_cast<uint8_t *>(hand.ptr);
+    HandoverArgs k;
+    handover_fill_args(&k, params, width, height, cap, target_n, new_point_threshold);
+    DetectWs dws;
+    FastWs fws;
+    int32_t *plan = nullptr;   // the detector's control words, which k_handover_plan writes
+    switch (src.kind) {
+    case HandoverSource::GIVEN:
+        k.cand_cap = src.cand_cap, k.n_cand = src.n_cand, k.cand_un = src.cand_un;
+        break;
+    case HandoverSource::CORNERS:
+        if ((rc = detect_workspace(ctx, src.det, width, height, cap, &dws))) return rc;
+        k.cand_cap = cap, k.n_cand = src.info, k.cand_un = dws.cand, plan = dws.ctl;
+        break;
+    case HandoverSource::FAST:
+        if ((rc = fast_workspace(ctx, g, n_features, &fws))) return rc;
+        k.cand_cap = fws.out_bound, k.n_cand = src.info, k.cand_un = fws.cand, plan = fws.ctl;
+        break;
+    }
+    k.status = a.status, k.pt_predict = a.pt_predict, k.pt_predict_un = a.pt_predict_un;
+    k.keys = a.keys, k.keys_un = a.keys_un, k.keys_normal = a.keys_normal;
+    k.index_in_last = a.index_in_last, k.live = a.live, k.mask = mask, k.state = a.state;
+    handover_hint_args(ctx, &k);
+    hipLaunchKernelGGL(k_handover_fill, dim3((unsigned)((bytes + 4095) / 4096)), dim3(256), 0, ctx->stream, mask, bytes);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_handover_holes, dim3((unsigned)(((int64_t)cap * 14 + 255) / 256)), dim3(256), 0, ctx->stream, cap,
+                       width, height, a.status, a.pt_predict_un, mask);
+    HIPCHK(ctx, hipGetLastError());
+    if (plan) {
+        hipLaunchKernelGGL(k_handover_plan, dim3(1), dim3(1024), 0, ctx->stream, cap, target_n, new_point_threshold, a.status,
+                           (const int32_t *)a.state, plan);
+        HIPCHK(ctx, hipGetLastError());
+        const FrameSlot &s = ctx->slots[src.slot];
+        rc = src.kind == HandoverSource::CORNERS
+                 ? detect_launch(ctx, src.det, s, mask, cap, dws.ctl + kDetCtlLimit, dws.ctl + kDetCtlSkip, dws.cand, src.info, dws)
+                 : fast_launch(ctx, src.fast, n_features, s, g, nullptr, fws.out_bound, fws.cand, nullptr, src.info,
+                               fws.ctl + kFastCtlSkip, fws);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_handover_keys, dim3(1), dim3(1024), 0, ctx->stream, k);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// The host-buffer hand-overs: the caller's arrays `host` through one device block around handover_launch.  Of `src` the
+// list, its count and info are the caller's too; the detecting sources find their candidates on `img`, uploaded into
+// scratch slot 4.
+int handover_host(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap, int32_t target_n,
+                  double new_point_threshold, const HandoverArrays &host, const HandoverSource &src, const pagk_image *img)
+{
+    static const char *const kNames[] = {"pagk_frame_handover", "pagk_frame_handover_detect", "pagk_frame_handover_fast"};
+    int rc = handover_geometry_check(ctx, params, width, height, cap, target_n, new_point_threshold, src);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, kNames[src.kind]);
+    const bool given = src.kind == HandoverSource::GIVEN;   // a count and a list go in, no info comes out
+    if (!handover_required(host, src) || (!given && (!img || img->width != width || img->height != height))) return PAGK_E_ARG;
+    if (given)
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+    else if ((rc = frame_upload_any(ctx, 4, img, 1)))
+        return rc;
+    const size_t nc = (size_t)cap, cc = (size_t)(src.cand_cap > 0 ? src.cand_cap : 1), px = (size_t)width * height;
     enum { STATUS, PREDICT, PREDICT_UN, N_CAND, CAND, KEYS, KEYS_UN, KEYS_NORMAL, INDEX, LIVE, STATE, INFO, MASK, PARTS };
     const size_t sizes[PARTS] = {nc,     nc * 8, nc * 8, given ? 4 : 0u, given ? cc * 8 : 0u,     nc * 8,
                                  nc * 8, nc * 8, nc * 4, nc,             kHandoverStateWords * 4, given ? 0u : kDetectInfoWords * 4,
                                  px};
     Staged<PARTS> s(ctx, sizes);
     // (the form with the caller's candidates keeps its block in the context; the detecting forms take one per call)
-    int rc = s.open(given ? &ctx->buf[pagk_ctx::HANDIO] : nullptr, "the host-buffer hand-over's scratch");
+    rc = s.open(given ? &ctx->buf[pagk_ctx::HANDIO] : nullptr, "the host-buffer hand-over's scratch");
     if (rc) return rc;
-    const void *src[] = {status, pt_predict, pt_predict_un, n_cand, cand_cap > 0 ? cand_un : nullptr};
+    const void *in[] = {host.status, host.pt_predict, host.pt_predict_un, src.n_cand, src.cand_cap > 0 ? src.cand_un : nullptr};
     for (int k = STATUS; k <= CAND; k++)
-        if ((rc = s.in(k, src[k], sizes[k]))) return rc;
-    if ((rc = s.in(STATE, state, sizes[STATE]))) return rc;   // reach_flag persists
-    uint8_t *d_status = s.at<uint8_t>(STATUS), *d_live = s.at<uint8_t>(LIVE), *d_mask = s.at<uint8_t>(MASK);
-    float *d_predict = s.at<float>(PREDICT), *d_predict_un = s.at<float>(PREDICT_UN), *d_keys = s.at<float>(KEYS);
-    float *d_keys_un = s.at<float>(KEYS_UN), *d_keys_normal = keys_normal ? s.at<float>(KEYS_NORMAL) : nullptr;
-    int32_t *d_index = s.at<int32_t>(INDEX), *d_state = s.at<int32_t>(STATE), *d_info = s.at<int32_t>(INFO);
-    if (given)
-        rc = pagk_frame_handover_device(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict,
-                                        d_predict_un, cand_cap, s.at<int32_t>(N_CAND), s.at<float>(CAND), d_keys, d_keys_un,
-                                        d_keys_normal, d_index, d_live, d_mask, d_state);
-    else if (det)
-        rc = handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict, d_predict_un, 0,
-                             nullptr, nullptr, d_keys, d_keys_un, d_keys_normal, d_index, d_live, d_mask, d_state, det,
-                             &ctx->slots[4], d_info);
-    else
-        rc = handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_predict, d_predict_un,
-                                fast, 4, d_keys, d_keys_un, d_keys_normal, d_index, d_live, d_mask, d_state, d_info);
-    if (rc) return rc;
-    void *dst[] = {keys, keys_un, keys_normal, index_in_last, live, state, info, mask};
+        if ((rc = s.in(k, in[k], sizes[k]))) return rc;
+    if ((rc = s.in(STATE, host.state, sizes[STATE]))) return rc;   // reach_flag persists
+    HandoverArrays d;
+    d.status = s.at<uint8_t>(STATUS), d.pt_predict = s.at<float>(PREDICT), d.pt_predict_un = s.at<float>(PREDICT_UN);
+    d.keys = s.at<float>(KEYS), d.keys_un = s.at<float>(KEYS_UN);
+    d.keys_normal = host.keys_normal ? s.at<float>(KEYS_NORMAL) : nullptr;
+    d.index_in_last = s.at<int32_t>(INDEX), d.live = s.at<uint8_t>(LIVE), d.mask = s.at<uint8_t>(MASK);
+    d.state = s.at<int32_t>(STATE);
+    HandoverSource dsrc = src;
+    dsrc.n_cand = s.at<int32_t>(N_CAND), dsrc.cand_un = s.at<float>(CAND), dsrc.info = s.at<int32_t>(INFO);
+    if ((rc = handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, d, dsrc))) return rc;
+    void *out[] = {host.keys, host.keys_un, host.keys_normal, host.index_in_last, host.live, host.state, src.info, host.mask};
     for (int k = KEYS; k <= MASK; k++)
-        if ((rc = s.out(k, dst[k - KEYS], sizes[k]))) return rc;
+        if ((rc = s.out(k, out[k - KEYS], sizes[k]))) return rc;
     return s.finish();
 }
 
 }  // namespace
+
+int pagk_frame_handover_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                               const float *d_pt_predict, const float *d_pt_predict_un, int32_t cand_cap,
+                               const int32_t *d_n_cand, const float *d_cand_un, float *d_keys, float *d_keys_un,
+                               float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                               int32_t *d_state)
+{
+    HandoverArrays a;
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = d_mask, a.state = d_state;
+    HandoverSource src;
+    src.cand_cap = cand_cap, src.n_cand = d_n_cand, src.cand_un = d_cand_un;
+    int rc = handover_check(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
+    return rc ? rc : handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
+}
+
+int pagk_frame_handover(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                        int32_t target_n, double new_point_threshold, const uint8_t *status, const float *pt_predict,
+                        const float *pt_predict_un, int32_t cand_cap, const int32_t *n_cand, const float *cand_un,
+                        float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live,
+                        uint8_t *mask, int32_t *state)
+{
+    HandoverArrays a;
+    a.status = status, a.pt_predict = pt_predict, a.pt_predict_un = pt_predict_un;
+    a.keys = keys, a.keys_un = keys_un, a.keys_normal = keys_normal;
+    a.index_in_last = index_in_last, a.live = live, a.mask = mask, a.state = state;
+    HandoverSource src;
+    src.cand_cap = cand_cap, src.n_cand = n_cand, src.cand_un = cand_un;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, a, src, nullptr);
+}
+
+int pagk_frame_handover_detect_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                                      int32_t cap, int32_t target_n, double new_point_threshold, const uint8_t *d_status,
+                                      const float *d_pt_predict, const float *d_pt_predict_un,
+                                      const pagk_detect_params *det, int32_t slot, float *d_keys, float *d_keys_un,
+                                      float *d_keys_normal, int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask,
+                                      int32_t *d_state, int32_t *d_info)
+{
+    HandoverArrays a;
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = d_mask, a.state = d_state;
+    HandoverSource src;
+    src.kind = HandoverSource::CORNERS, src.det = det, src.slot = slot, src.info = d_info;
+    int rc = handover_check(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
+    return rc ? rc : handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
+}
+
+int pagk_frame_handover_detect(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
+                               int32_t target_n, double new_point_threshold, const uint8_t *status,
+                               const float *pt_predict, const float *pt_predict_un, const pagk_detect_params *det,
+                               const pagk_image *img, float *keys, float *keys_un, float *keys_normal,
+                               int32_t *index_in_last, uint8_t *live, uint8_t *mask, int32_t *state, int32_t *info)
+{
+    HandoverArrays a;
+    a.status = status, a.pt_predict = pt_predict, a.pt_predict_un = pt_predict_un;
+    a.keys = keys, a.keys_un = keys_un, a.keys_normal = keys_normal;
+    a.index_in_last = index_in_last, a.live = live, a.mask = mask, a.state = state;
+    HandoverSource src;
+    src.kind = HandoverSource::CORNERS, src.det = det, src.info = info;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, a, src, img);
+}
 
 int pagk_frame_handover_fast_device(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
                                     int32_t target_n, double new_point_threshold, const uint8_t *d_status,
@@ -2960,10 +2945,14 @@ int pagk_frame_handover_fast_device(pagk_ctx *ctx, const pagk_params *params, in
                                     int32_t *d_index_in_last, uint8_t *d_live, uint8_t *d_mask, int32_t *d_state,
                                     int32_t *d_info)
 {
-    if (slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
-    return handover_fast_slot(ctx, params, width, height, cap, target_n, new_point_threshold, d_status, d_pt_predict,
-                              d_pt_predict_un, fast, slot, d_keys, d_keys_un, d_keys_normal, d_index_in_last, d_live, d_mask,
-                              d_state, d_info);
+    HandoverArrays a;
+    a.status = d_status, a.pt_predict = d_pt_predict, a.pt_predict_un = d_pt_predict_un;
+    a.keys = d_keys, a.keys_un = d_keys_un, a.keys_normal = d_keys_normal;
+    a.index_in_last = d_index_in_last, a.live = d_live, a.mask = d_mask, a.state = d_state;
+    HandoverSource src;
+    src.kind = HandoverSource::FAST, src.fast = fast, src.slot = slot, src.info = d_info;
+    int rc = handover_check(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
+    return rc ? rc : handover_launch(ctx, params, width, height, cap, target_n, new_point_threshold, a, src);
 }
 
 int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height, int32_t cap,
@@ -2972,16 +2961,13 @@ int pagk_frame_handover_fast(pagk_ctx *ctx, const pagk_params *params, int32_t w
                              float *keys_un, float *keys_normal, int32_t *index_in_last, uint8_t *live, uint8_t *mask,
                              int32_t *state, int32_t *info)
 {
-    if (!ctx || !handover_args_ok(params, width, height, cap, target_n, new_point_threshold, 0)) return PAGK_E_ARG;
-    int rc = fast_params_check(fast);
-    if (rc) return rc;
-    NOT_WHILE_CAPTURING(ctx, "pagk_frame_handover_fast");
-    if (!status || !pt_predict || !pt_predict_un || !img || img->width != width || img->height != height || !keys || !keys_un ||
-        !index_in_last || !live || !state)
-        return PAGK_E_ARG;
-    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
-    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, status, pt_predict, pt_predict_un, 0,
-                         nullptr, nullptr, nullptr, fast, keys, keys_un, keys_normal, index_in_last, live, mask, state, info);
+    HandoverArrays a;
+    a.status = status, a.pt_predict = pt_predict, a.pt_predict_un = pt_predict_un;
+    a.keys = keys, a.keys_un = keys_un, a.keys_normal = keys_normal;
+    a.index_in_last = index_in_last, a.live = live, a.mask = mask, a.state = state;
+    HandoverSource src;
+    src.kind = HandoverSource::FAST, src.fast = fast, src.info = info;
+    return handover_host(ctx, params, width, height, cap, target_n, new_point_threshold, a, src, img);
 }
 
 // ---- ORB descriptors and matching (pagk_orb_kernel.h) ----------------------------------------------------------

@@ -1,6 +1,7 @@
 """GPU tests of the device-side frame hand-over: pagk_post_filter_device against the host function, pagk_frame_handover
 against the plain-C restatement (tests/frame_handover_ref.c), pagk_gyro_predict_device_live, runtime.SequenceTracker
-against a host loop built from the older entry points, and examples/stream_graph_loop.cpp against stream_resident."""
+against a host loop built from the older entry points, the codes with which the six pagk_frame_handover* forms refuse a
+mistake, and examples/stream_graph_loop.cpp against stream_resident."""
 import os
 import struct
 import subprocess
@@ -357,6 +358,138 @@ def test_sequence_tracker_against_a_host_loop(ctx, ref):
     for k in range(NF):
         for name in runtime.FrameResult.FIELDS:
             assert results["graph"][k][name].tobytes() == results["direct"][k][name].tobytes(), (k, name)
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------
+# What each of the six entry points returns for which mistake, and which code wins when two mistakes meet.  Every row is
+# refused on the host, in front of the hand-over's first launch; the calls go to the C functions, because capi.Context
+# raises ValueError on its own for some of them.
+RW, RH, RCAP, RTARGET = 97, 80, 16, 8
+R_ALL = ("given_dev", "given_host", "detect_dev", "detect_host", "fast_dev", "fast_host")
+R_DEV, R_HOST = R_ALL[0::2], R_ALL[1::2]
+R_GIVEN, R_DETECT, R_FAST = R_ALL[0:2], R_ALL[2:4], R_ALL[4:6]
+R_NAMES = dict(given_dev="pagk_frame_handover_device", given_host="pagk_frame_handover",
+               detect_dev="pagk_frame_handover_detect_device", detect_host="pagk_frame_handover_detect",
+               fast_dev="pagk_frame_handover_fast_device", fast_host="pagk_frame_handover_fast")
+
+
+def _refusal_rows(img61):
+    """(mistake, forms, overrides of the valid call's arguments, code)"""
+    A, U, nan = capi.PAGK_E_ARG, capi.PAGK_E_UNSUPPORTED, float("nan")
+    fast8 = capi.fast_params_default(n_levels=8)
+    low = dict(height=61, slot=0, img=img61, mask=None)   # (slot 0 and img61 are 97 x 61: too low for the FAST cell grid)
+    rows = [("cap < target_n", R_ALL, dict(cap=RTARGET - 1), A),
+            ("width 13", R_ALL, dict(width=13), A),
+            ("height 13", R_ALL, dict(height=13), A),
+            ("NaN threshold", R_ALL, dict(thr=nan), A),
+            ("params NULL", R_ALL, dict(params=None), A),
+            ("cand_cap > 0 with a NULL list", R_GIVEN, dict(cand_un=None), A),
+            ("cand_cap < 0", R_GIVEN, dict(cand_cap=-1), A),
+            ("n_cand NULL", R_GIVEN, dict(n_cand=None), A)]
+    rows += [(name + " NULL", R_ALL, {name: None}, A)
+             for name in ("status", "pt_predict", "pt_predict_un", "keys", "keys_un", "index_in_last", "live", "state")]
+    rows += [("info NULL", ("detect_dev", "fast_dev"), dict(info=None), A),
+             ("img NULL", ("detect_host", "fast_host"), dict(img=None), A),
+             ("img of another size", ("detect_host", "fast_host"), dict(img=img61), A),
+             ("keys == pt_predict", R_DEV, dict(keys="pt_predict"), A),
+             ("keys_un == pt_predict_un", R_DEV, dict(keys_un="pt_predict_un"), A),
+             ("slot -1", ("detect_dev", "fast_dev"), dict(slot=-1), A),
+             ("slot 4", ("detect_dev", "fast_dev"), dict(slot=4), A),
+             ("empty slot", ("detect_dev", "fast_dev"), dict(slot=2), A),
+             ("slot of another size", ("detect_dev", "fast_dev"), dict(slot=0), A),
+             ("det NULL", R_DETECT, dict(detect=None), A),
+             ("quality_level NaN", R_DETECT, dict(detect=capi.detect_params_default(quality_level=nan)), A),
+             ("fast NULL", R_FAST, dict(fast=None), A),
+             ("ini_threshold 256", R_FAST, dict(fast=capi.fast_params_default(ini_threshold=256)), A),
+             ("n_levels 8", R_FAST, dict(fast=fast8), U),
+             ("61-pixel-high frame", R_FAST, low, A),
+             ("n_features 0 with target_n 0", R_FAST, dict(target_n=0), A),
+             # two at once: the parameter block is looked at after the geometry and the slot's range, before the rest
+             ("n_levels 8 and a NaN threshold", R_FAST, dict(fast=fast8, thr=nan), A),
+             ("n_levels 8 and slot -1", ("fast_dev",), dict(fast=fast8, slot=-1), A),
+             ("n_levels 8 and keys NULL", R_FAST, dict(fast=fast8, keys=None), U),
+             ("n_levels 8 and keys == pt_predict", ("fast_dev",), dict(fast=fast8, keys="pt_predict"), U),
+             ("n_levels 8 and an empty slot", ("fast_dev",), dict(fast=fast8, slot=2), U),
+             ("n_levels 8 and a 61-pixel-high frame", R_FAST, dict(low, fast=fast8), U)]
+    return rows
+
+
+def _refusal_args(form, img):
+    """The arguments of a valid call: device tensors for the device forms, numpy arrays for the host forms."""
+    if form in R_HOST:
+        z, u8, f32, i32 = np.zeros, np.uint8, np.float32, np.int32
+    else:
+        z, u8, f32, i32 = (lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:0")), torch.uint8, torch.float32, torch.int32
+    return dict(params=capi.make_params(camera=synth.D435I), width=RW, height=RH, cap=RCAP, target_n=RTARGET, thr=6.0,
+                status=z(RCAP, u8), pt_predict=z((RCAP, 2), f32), pt_predict_un=z((RCAP, 2), f32), cand_cap=4,
+                n_cand=z(1, i32), cand_un=z((4, 2), f32), detect=capi.detect_params_default(), fast=capi.fast_params_default(),
+                slot=1, img=img, keys=z((RCAP, 2), f32), keys_un=z((RCAP, 2), f32), keys_normal=z((RCAP, 2), f32),
+                index_in_last=z(RCAP, i32), live=z(RCAP, u8), mask=z((RH, RW), u8), state=z(8, i32), info=z(8, i32))
+
+
+def _refusal_call(c, form, a):
+    import ctypes as C
+    ptr = lambda k: capi._ptr(a[k])                          # noqa: E731
+    ref = lambda s: None if s is None else C.byref(s)        # noqa: E731
+    head = [c.h, ref(a["params"]), a["width"], a["height"], a["cap"], a["target_n"], a["thr"], ptr("status"), ptr("pt_predict"),
+            ptr("pt_predict_un")]
+    tail = [ptr(k) for k in ("keys", "keys_un", "keys_normal", "index_in_last", "live", "mask", "state")]
+    fn = getattr(c.lib, R_NAMES[form])
+    if form in R_GIVEN:
+        return fn(*head, a["cand_cap"], ptr("n_cand"), ptr("cand_un"), *tail)
+    frame = a["slot"] if form in R_DEV else None if a["img"] is None else C.byref(capi.image_view(a["img"]))
+    return fn(*head, ref(a["detect" if form in R_DETECT else "fast"]), frame, *tail, ptr("info"))
+
+
+def test_handover_refusals(built):
+    rng = np.random.default_rng(97)
+    img, img61 = rng.integers(0, 256, (RH, RW), dtype=np.uint8), rng.integers(0, 256, (61, RW), dtype=np.uint8)
+    c = capi.Context(0)
+    stream = torch.cuda.Stream()
+    bad = []
+
+    def expect(what, form, over, code):
+        a = base[form]
+        a = dict(a, **{k: a[v] if isinstance(v, str) else v for k, v in over.items()})
+        got = _refusal_call(c, form, a)
+        print(f"{what} | {form} | {got}")
+        if got != code:
+            bad.append((what, form, got, code))
+        return got
+
+    try:
+        with torch.cuda.stream(stream):
+            c.set_stream(stream.cuda_stream)
+            c.frame_upload(0, img61, 1)
+            c.frame_upload(1, img, 1)                          # (slot 2 stays empty)
+            base = {form: _refusal_args(form, img) for form in R_ALL}
+            torch.cuda.synchronize()
+            for form in R_ALL:                                 # the arguments that the rows spoil are good ones
+                expect("a valid call", form, {}, capi.PAGK_OK)
+            c.sync()
+            for what, forms, over, code in _refusal_rows(img61):
+                for form in forms:
+                    expect(what, form, over, code)
+            c.graph_begin()
+            try:
+                for form in R_HOST:
+                    if expect("under capture", form, {}, capi.PAGK_E_ARG) == capi.PAGK_E_ARG:
+                        text = c.lib.pagk_last_error(c.h).decode()
+                        print(f"    {text}")
+                        if not text.startswith(R_NAMES[form] + " is not capturable"):
+                            bad.append(("under capture: the message", form, text, R_NAMES[form]))
+                expect("under capture: n_levels 8", "fast_host", dict(fast=capi.fast_params_default(n_levels=8)),
+                       capi.PAGK_E_UNSUPPORTED)
+                expect("under capture: width 13", "given_host", dict(width=13), capi.PAGK_E_ARG)
+                for form in R_DEV:                             # (sized by the valid calls above)
+                    expect("under capture: a valid call", form, {}, capi.PAGK_OK)
+            finally:
+                c.graph_destroy(c.graph_end())
+            c.sync()
+    finally:
+        c.set_stream(None)
+        c.close()
+    assert bad == [], "(mistake, form, returned, expected): " + repr(bad)
 
 
 # ---- examples ------------------------------------------------------------------------------------------------------
