@@ -13,6 +13,10 @@
  *   - affine is n x 4 float32, row-major 2x2 per feature      (cv::Mat CV_32F 2x2,
  *     reference src/gyro_aided_tracker.cpp:166-168)
  *   - status bytes are 0 / 1                                   (std::vector<uchar>)
+ *   - an image given as data, width, height and step (a pagk_image, or the d_data / d_next / d_raw of the *_device
+ *     calls) is (height - 1) * step + width bytes long (d_raw: src_width * channels in place of width): the bytes of a
+ *     row beyond its last pixel and everything after the last row's last pixel are not part of it: they are
+ *     never written and no result depends on them
  *   - return value: 0 = PAGK_OK, negative = error (never throws, never aborts)
  */
 #ifndef PAGK_H
@@ -215,7 +219,8 @@ int pagk_frame_download_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_
 
 /* Track with every per-feature array in DEVICE memory (all pointers are device
  * pointers; same layouts as pagk_track). Asynchronous on the context stream;
- * call pagk_sync before reading results on the host. */
+ * call pagk_sync before reading results on the host.  Every array is n elements (n x 2, n x 4) long: nothing is
+ * written beyond it and no result depends on what lies beyond it.  n = 0 is valid and leaves every output untouched. */
 int pagk_track_device(pagk_ctx *ctx, const pagk_params *params, int32_t slot_ref,
                       int32_t slot_cur, int32_t n, const float *d_pt_ref_un,
                       const float *d_pt_init_un, const float *d_affine,
