@@ -967,6 +967,18 @@ int pagk_selftest_repeat_sum(pagk_ctx *ctx, int32_t n, const float *c, int32_t c
  * 0 <= x < cols - 1 and 0 <= y < rows - 1 (mode 1) or 1 <= x < cols - 2 and 1 <= y < rows - 2 (mode 3) hold for all of them
  * (NaN fails).  Host pointers, synchronous, not between pagk_graph_begin and pagk_graph_end. */
 int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mode, int32_t n, const float *xy, float *out);
+/* Selftest: overwrite the scratch this context owns with the 32-bit `word`, on the context's stream (the call waits for the
+ * context's queued work first): every workspace and staging buffer the library has allocated for this context so far, the
+ * row queue, the Lucas-Kanade pyramids of all slots and the blocks of all frame slots.  Afterwards NO frame slot is valid
+ * and no slot has a Lucas-Kanade pyramid: the caller uploads its frames (and calls pagk_lk_pyramid_device) again before the
+ * next call that reads them, and pagk_last_handover returns 0 until the next launch.  Left as they are: what has set / reset
+ * calls of its own (the maps of pagk_rectify_set_maps, the pattern of pagk_orb_set_pattern, the priority hints and the
+ * dispatch order) and the descriptors of the batched launches.
+ * also_new != 0: from now on every block the library allocates for this context is filled with `word` before its first
+ * use; also_new == 0 switches that off again.
+ * PAGK_E_ARG inside a graph capture and while a graph of this context is alive.  No result of the library may depend on
+ * `word`: that is what the call is for (tests/test_workspace_content_gpu.py). */
+int pagk_selftest_fill_workspaces(pagk_ctx *ctx, uint32_t word, int32_t also_new);
 
 /* hipGraph capture of the per-frame work (BASELINE configs[4], "hipGraph-captured iterate").  A camera
  * stream issues the same launches on the same device pointers every frame; between pagk_graph_begin and

@@ -450,6 +450,9 @@ def declare(lib) -> None:
     if hasattr(lib, "pagk_selftest_sample"):
         lib.pagk_selftest_sample.restype = C.c_int
         lib.pagk_selftest_sample.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    if hasattr(lib, "pagk_selftest_fill_workspaces"):
+        lib.pagk_selftest_fill_workspaces.restype = C.c_int
+        lib.pagk_selftest_fill_workspaces.argtypes = [vp, C.c_uint32, i32]
     lib.pagk_match_features.restype = C.c_int
     lib.pagk_match_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     # the sharded path
@@ -511,7 +514,7 @@ EXPORTED_SYMBOLS = [
     "pagk_frame_rectify_pinned", "pagk_rectify", "pagk_undistort_maps",
     "pagk_orb_params_default", "pagk_orb_params_check", "pagk_orb_pattern_check", "pagk_orb_set_pattern",
     "pagk_orb_describe_device", "pagk_orb_describe", "pagk_orb_match_device", "pagk_orb_match",
-    "pagk_selftest_sample",
+    "pagk_selftest_sample", "pagk_selftest_fill_workspaces",
     "pagk_lk_params_default", "pagk_lk_params_check", "pagk_lk_levels", "pagk_lk_pyramid_device", "pagk_lk_track_device",
     "pagk_lk_track", "pagk_selftest_lk_level",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
@@ -1103,6 +1106,12 @@ class Context:
         self._check(self.lib.pagk_selftest_sample(self.h, int(slot), int(level), int(mode), n, _ptr(xy), _ptr(out)),
                     "pagk_selftest_sample")
         return out[:n]
+
+    def selftest_fill_workspaces(self, word: int, also_new: bool = False) -> None:
+        """pagk_selftest_fill_workspaces: the scratch this context owns becomes the 32-bit `word` (no frame slot is valid and no
+        slot has a Lucas-Kanade pyramid afterwards); also_new: so does every block the library allocates from now on."""
+        self._check(self.lib.pagk_selftest_fill_workspaces(self.h, int(word) & 0xFFFFFFFF, int(bool(also_new))),
+                    "pagk_selftest_fill_workspaces")
 
     def selftest_solve(self, H: np.ndarray, b: np.ndarray, solver_variant: int = 0):
         """H.llt().solve(b) and the update's norm for n 4x4 systems: (x, norm) of the one-lane form and

@@ -36,6 +36,7 @@ struct DevBuf {
     size_t bytes = 0;
     void *host = nullptr;   // `mirrored` buffers: pinned host memory of the same size (one copy in, one copy out)
     bool mirrored = false;
+    bool state = false;     // holds state with set / reset calls of its own, not scratch: pagk_selftest_fill_workspaces leaves it alone
 };
 
 struct FrameSlot {
@@ -130,6 +131,9 @@ struct pagk_ctx {
     // hipGraph capture of the per-frame work (pagk_graph_*): while capturing, nothing may allocate and the
     // timing events are left out (an event recorded into a graph cannot be read back)
     bool capturing = false;
+    // pagk_selftest_fill_workspaces(word, also_new != 0): every block allocated from now on starts as `fill_word`
+    bool fill_new = false;
+    uint32_t fill_word = 0;
     static constexpr int kGraphs = 8;
     hipGraph_t graphs[kGraphs] = {};
     hipGraphExec_t graph_execs[kGraphs] = {};
@@ -257,6 +261,21 @@ int release(pagk_ctx *ctx, DevBuf &b)
     return PAGK_OK;
 }
 
+// `bytes` at p become the 32-bit `word` (a tail that is no whole word: its low byte), in stream order
+int fill_words(pagk_ctx *ctx, void *p, size_t bytes, uint32_t word)
+{
+    const size_t words = bytes / 4, tail = bytes % 4;
+    if (p && words) HIPCHK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, words, ctx->stream));
+    if (p && tail) HIPCHK(ctx, hipMemsetAsync(static_cast<uint8_t *>(p) + 4 * words, (int)(word & 0xff), tail, ctx->stream));
+    return PAGK_OK;
+}
+// ... and of a pinned mirror, by the host (nothing is queued on a mirror when this is called)
+void fill_words_host(void *p, size_t bytes, uint32_t word)
+{
+    uint8_t *b = static_cast<uint8_t *>(p);
+    for (size_t i = 0; p && i < bytes; i++) b[i] = i < bytes / 4 * 4 ? (uint8_t)(word >> (8 * (i % 4))) : (uint8_t)word;
+}
+
 // Room for `bytes` in `b`: a buffer that is too small is freed and allocated anew (its content is scratch), and is left
 // empty when that fails.  `what` names the buffer in ctx->err, `hint` is what the caller does instead of growing it here.
 int reserve(pagk_ctx *ctx, DevBuf &b, size_t bytes, GrowPolicy policy, const char *what, const char *hint = "")
@@ -271,6 +290,10 @@ int reserve(pagk_ctx *ctx, DevBuf &b, size_t bytes, GrowPolicy policy, const cha
     HIPCHK(ctx, hipMalloc(&b.ptr, bytes));
     if (b.mirrored) HIPCHK(ctx, hipHostMalloc(&b.host, bytes, hipHostMallocDefault));
     b.bytes = bytes;
+    if (ctx->fill_new) {   // (selftest only: the new block does not start as the allocator left it)
+        fill_words_host(b.host, bytes, ctx->fill_word);
+        return fill_words(ctx, b.ptr, bytes, ctx->fill_word);
+    }
     return PAGK_OK;
 }
 
@@ -299,7 +322,7 @@ public:
         }
         HIPCHK(ctx_, hipMalloc(&own_, lay_.total));
         base_ = own_;
-        return PAGK_OK;
+        return ctx_->fill_new ? fill_words(ctx_, own_, lay_.total, ctx_->fill_word) : PAGK_OK;
     }
     template <class T>
     T *at(int k) const { return lay_.template at<T>(base_, k); }
@@ -1250,6 +1273,7 @@ int pagk_create(pagk_ctx **out, int device)
     }
     ctx->stream = ctx->own_stream;
     ctx->buf[pagk_ctx::FEAT].mirrored = true;
+    for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER}) ctx->buf[b].state = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
         pagk_destroy(ctx);
@@ -4147,6 +4171,44 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
     HIPCHK(ctx, hipGetLastError());
     if ((rc = st.out(1, out, sizes[1]))) return rc;
     return st.finish();
+}
+
+// What the context owns as scratch becomes `word`: every buf[] entry that is no state (DevBuf::state), the row queue, the
+// Lucas-Kanade pyramids and the frame slots -- and what described their content is withdrawn (no slot is valid, no slot has a
+// Lucas-Kanade pyramid, no hand-over count to read).  The descriptor ring of the batched launches is rewritten whole by
+// every launch that uses it and stays as it is.
+int pagk_selftest_fill_workspaces(pagk_ctx *ctx, uint32_t word, int32_t also_new)
+{
+    if (!ctx) return PAGK_E_ARG;
+    if (in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "the workspaces would have to be overwritten inside a graph capture: fill them before pagk_graph_begin");
+        return PAGK_E_ARG;
+    }
+    for (int k = 0; k < pagk_ctx::kGraphs; k++)
+        if (ctx->graph_execs[k]) {
+            snprintf(ctx->err, sizeof(ctx->err), "the workspaces would have to be overwritten while graph %d of this context is alive (its nodes "
+                     "read the slots and buffers as they were captured): destroy the graph first", k);
+            return PAGK_E_ARG;
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (the pinned mirror is written by the host)
+    if (ctx->aux_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->aux_stream));
+    ctx->fill_word = word;
+    ctx->fill_new = also_new != 0;
+    int rc = PAGK_OK;
+    for (DevBuf &b : ctx->buf) {
+        if (b.state) continue;
+        fill_words_host(b.host, b.bytes, word);
+        if ((rc = fill_words(ctx, b.ptr, b.bytes, word))) return rc;
+    }
+    if ((rc = fill_words(ctx, ctx->queue, 256, word))) return rc;
+    for (auto &p : ctx->lk_pyr) p.top = -1;
+    for (FrameSlot &s : ctx->slots) {
+        s.valid = false;
+        if ((rc = fill_words(ctx, s.block.ptr, s.block.bytes, word))) return rc;
+    }
+    ctx->last_handover = false;
+    return PAGK_OK;
 }
 
 // GyroAidedTracker::MatchFeatures, src/gyro_aided_tracker.cpp:949-1008, as the reference writes it: a sequential pass

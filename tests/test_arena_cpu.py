@@ -209,9 +209,14 @@ def test_lengths_evaluate():
 
 
 def test_every_row_has_a_gpu_case():
-    """Every function of the table is called by tests/test_device_bounds_gpu.py through its capi.Context method (the test's
-    own source is the record)."""
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_device_bounds_gpu.py")).read()
+    """Every function of the table is called through its capi.Context method by a scenario of tests/device_plans.py, and
+    tests/test_device_bounds_gpu.py runs that scenario (the sources are the record)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    plans = open(os.path.join(here, "device_plans.py")).read()
+    test = open(os.path.join(here, "test_device_bounds_gpu.py")).read()
+    scenarios = re.split(r"^def ", plans, flags=re.M)[1:]
     for f in df.FORMS:
         short = f.function[len("pagk_"):]
-        assert re.search(r"\.%s\b" % short, src), f"{f.function} has a row and no case"
+        users = [s.split("(")[0] for s in scenarios if re.search(r"\.%s\b" % short, s)]
+        assert users, f"{f.function} has a row and no scenario"
+        assert any(re.search(r"check\(dp\.%s\(" % u, test) for u in users), f"{f.function}: no case runs its scenario"
