@@ -554,8 +554,8 @@ int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R
  * ORBextractor::DetectFeatures (src/ORBextractor.cc:1148-1205), ComputeKeyPointsOctTree (:789-871), DistributeOctTree
  * (:563-787), ExtractorNode::DivideNode (:505-561).  This section is that branch for nlevels = 1.  Parity with OpenCV's
  * cv::FAST is NOT claimed (it cannot be built here); the contract is this definition, bit for bit (restated in plain C in
- * tests/fast_detect_ref.c).  It is integer arithmetic throughout, so a host with OpenCV can pin it.  Multi-level ORB
- * (cv::resize at 1 / 1.2) is not provided; computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and the
+ * tests/fast_detect_ref.c).  It is integer arithmetic throughout, so a host with OpenCV can pin it.  More than one
+ * level is "ORB over a scale pyramid" below (pagk_orb_extractor); computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and the
  * descriptors are pagk_orb_describe_device below ("ORB descriptors and matching").
  *   input      an 8-bit image W x H (level 0 of a frame slot, read through its pitch).  At level 0 without orientation
  *              every FAST window lies inside the image: the border image of ComputePyramid is never read.  EDGE_THRESHOLD
@@ -740,7 +740,8 @@ int pagk_undistort_maps(double fx, double fy, double cx, double cy, const double
  * images -- ComputeKeyPointsOctTree, computeOrientation / IC_Angle (src/ORBextractor.cc:101-128, 496-503), a 7 x 7 Gaussian
  * blur and the steered rBRIEF descriptors (:131-171, 1057-1064, 1113-1130) --, then BruteForce-Hamming matching and a
  * distance filter.  The detector half is pagk_detect_fast_device with mask = NULL (ComputeKeyPointsOctTree for the one
- * level the front-ends construct); this section is the describe and the match half, for nlevels = 1.
+ * level the front-ends construct); this section is the describe and the match half, for nlevels = 1 (more
+ * levels: "ORB over a scale pyramid" below, which runs this section's definition on every level).
  * Parity contract: parity with OpenCV's own arithmetic (GaussianBlur, fastAtan2, cvRound, BFMatcher) is NOT claimed (it
  * cannot be built here); the contract is this definition, bit for bit (restated in plain C in tests/orb_ref.c).  It follows
  * OpenCV 3.4's scalar code paths step by step and says where it is the library's own rule.
@@ -838,6 +839,116 @@ int pagk_orb_match_device(pagk_ctx *ctx, const pagk_orb_params *params, int32_t 
  * PAGK_ORB_MAX_ROWS. */
 int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, const uint8_t *desc_q, int32_t nt,
                    const uint8_t *desc_t, int32_t *train_idx, int32_t *distance, uint8_t *keep, int32_t *info);
+
+/* ---- ORB over a scale pyramid ----------------------------------------------------------------------------------------- */
+/* ORBextractor is general in nlevels (src/ORBextractor.cc:434-470 the constructor, :1207-1230 ComputePyramid, :789-875
+ * ComputeKeyPointsOctTree, :1066-1146 operator(), :1148-1205 DetectFeatures); both front-ends write the alternative next to
+ * the value they ship ("int nLevels = 1;    // 8", Examples/Demo/RealSenseD435i.cpp:187).  This section is the extractor for
+ * 1 <= nlevels <= PAGK_ORB_MAX_LEVELS.  The two n_levels fields of pagk_fast_params and pagk_orb_params describe the
+ * one-level calls above and keep refusing anything but 1; the levels of this section come from pagk_orb_extractor.
+ * Parity contract: parity with OpenCV (cv::resize, cv::FAST, GaussianBlur) is NOT claimed; the contract is this definition,
+ * bit for bit (restated in plain C in tests/orb_levels_ref.c, on top of tests/fast_detect_ref.c and tests/orb_ref.c).
+ *   scales     (:439-455) sc[0] = 1.0f, sc[l] = sc[l - 1] * scale_factor (one f32 rounding per level), inv[l] = 1.0f / sc[l].
+ *   sizes      (:1211-1212) W_l = cvRound((float)W * inv[l]), H_l = cvRound((float)H * inv[l]), ties to even; W and H are
+ *              always the ORIGINAL image's.  Every level must be a legal input of the one-level detector: 62 <= W_l, H_l <=
+ *              32767 and nIni >= 1 (PAGK_E_ARG otherwise: the reference divides by zero there).
+ *   quotas     (:459-470) factor = 1.0f / scale_factor; nd = ((float)n_features * (1.0f - factor)) / (1.0f - (float)p), one
+ *              f32 rounding per operation, where p is (double)factor multiplied n_levels times, starting from 1.0, in f64
+ *              (the library's stated rule in place of pow).  quota[l] = cvRound(nd), then nd *= factor, for l < n_levels - 1;
+ *              the last level gets max(n_features - sum, 0).  A quota of 0 is legal and reachable (10 features over 8 levels:
+ *              2 2 2 1 1 1 1 0; one feature over 3 levels: 0 0 1).  The tree of a level with quota 0 runs with N = 1, which is
+ *              identical to the reference's N = 0: the first splitting round runs unconditionally (:618-689), and the finish
+ *              test size >= N || size == prevSize (:693) is then true for both values.
+ *   pyramid    (:1207-1230) level 0 is the image, level l is the resize of level l - 1 to W_l x H_l: OpenCV 3.4's 8-bit
+ *              INTER_LINEAR restated.  With src, dst the two extents of an axis: scale = 1 / ((double)dst / src); for
+ *              destination index d: f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s.  Columns: s < 0 gives
+ *              (f, s) = (0, 0); s + 1 >= src makes the column a single tap S = 2048 I[s], and s >= src - 1 first gives
+ *              (f, s) = (0, src - 1).  Rows: the two rows s and s + 1 are each clipped into [0, src - 1]; f stays.
+ *              Coefficients in Q11 by cvRound: a0 = rne((1.f - fx) * 2048.f), a1 = rne(fx * 2048.f), b0, b1 likewise from
+ *              fy.  Horizontal pass in int: S = I[s] a0 + I[s + 1] a1 per row.  Vertical pass: the low byte of
+ *              (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Since scale_factor <= 1.5 a level is never
+ *              exactly half its parent: at that ratio OpenCV switches to another kernel, which is not restated here.  The
+ *              border image of copyMakeBorder (:1222-1228) is never read: the FAST windows and the orientation disc lie
+ *              inside the level, as the one-level sections argue (cells start at minBorder = 16 with a ring of 3; the disc
+ *              of radius 15 and the taps of reach 18 are only used for centres in [19, W_l - 19) x [19, H_l - 19)).
+ *   per level  (:789-875) the one-level definition ("FAST in cells, then the quadtree") runs unchanged on the level image
+ *              with N = max(quota[l], 1) and no mask.  Orientation runs on the unblurred level, the blur and the descriptor
+ *              on the blurred level ("ORB descriptors and matching").  The centre rule [19, W_l - 19) x [19, H_l - 19) uses
+ *              the LEVEL's size; a keypoint outside it gets a zero descriptor and angle -1, and is counted.
+ *   packing    (:1113-1142) levels in ascending order, inside a level the tree's list order.  pt = pt_level * sc[l], one f32
+ *              multiplication per coordinate, for l != 0; octave = l; the keypoint size size_l = (int)(31 * sc[l]) comes
+ *              from the level table, not per keypoint.  Entries beyond the count are zeroed.
+ *   detect     DetectFeatures (:1148-1205) is the same without orientation and descriptors, and a keypoint is dropped when
+ *              mask[int(y) * W + int(x)] == 0 at the SCALED coordinates, W x H bytes of the original image (NULL: all ones;
+ *              a scaled coordinate lies inside the image, because x_level <= W_l - 17 and W_l <= W inv[l] + 0.5).
+ *              operator() never reads its mask (:1066-1146): the extract form has none.
+ * Info, PAGK_ORB_LEVELS_INFO_WORDS int32: [0] keypoints returned, [1] keypoints outside the descriptor border, [2] levels,
+ * [8 + l] keypoints of level l, [16 + l] raw FAST keypoints of level l, [24 + l] quota of level l, the rest 0.
+ * None of the entry points takes an array in device memory from the caller: the device form works on a frame slot and
+ * writes a keypoint set the context owns for that slot (the number of keypoints depends on the data and spans levels); the
+ * results are read with the synchronous host-buffer calls. */
+#define PAGK_ORB_MAX_LEVELS 8
+#define PAGK_ORB_LEVELS_INFO_WORDS 32
+typedef struct pagk_orb_extractor {
+    int32_t n_features;    /* nfeatures 1000 */
+    float scale_factor;    /* scaleFactor 1.2; 1 < scale_factor <= 1.5 */
+    int32_t n_levels;      /* nlevels 8; 1 .. PAGK_ORB_MAX_LEVELS */
+    int32_t ini_threshold; /* iniThFAST 20 */
+    int32_t min_threshold; /* minThFAST 7 */
+} pagk_orb_extractor;
+/* 1000, 1.2f, 8, 20, 7: the five constructor arguments (src/ORBextractor.cc:434-437) as ORB is normally run */
+void pagk_orb_extractor_default(pagk_orb_extractor *ex);
+/* PAGK_OK if *ex can be run by the entry points below (the constructor, src/ORBextractor.cc:434-470): 1 <= n_levels <=
+ * PAGK_ORB_MAX_LEVELS, 1 < scale_factor <= 1.5, thresholds in [0, 255], 1 <= n_features <= 1 << 24; PAGK_E_ARG otherwise or
+ * for NULL.  Needs no device. */
+int pagk_orb_extractor_check(const pagk_orb_extractor *ex);
+/* The level table of a width x height image (src/ORBextractor.cc:439-470, 1211-1212): per level its size, sc[l], quota and
+ * keypoint size; *out_bound = the sum over the levels of the one-level out_bound (pagk_detect_fast_bounds) with N =
+ * max(quota[l], 1): the rows a keypoint set can hold.  Host arrays of PAGK_ORB_MAX_LEVELS entries (entries at or beyond
+ * n_levels are zeroed); any pointer may be NULL.  PAGK_E_ARG for parameters the check refuses or a level the definition
+ * excludes.  Needs no device. */
+int pagk_orb_extractor_levels(const pagk_orb_extractor *ex, int32_t width, int32_t height, int32_t *level_width,
+                              int32_t *level_height, float *scale, int32_t *quota, int32_t *size, int32_t *out_bound);
+/* ORBextractor::operator() (src/ORBextractor.cc:1066-1146) on level 0 of frame slot `slot` (for how long a slot can be read
+ * see pagk_detect_corners_device): pyramid, per-level detection, orientation, blur, descriptors, packing.  The result goes
+ * into the keypoint set the context owns for that slot.  Asynchronous on the context stream, capturable; nothing is read on
+ * the host.  Run it once outside a capture first (the pyramid, the set and the workspace are buffers of the context).
+ * PAGK_E_ARG without a pattern, for an empty slot, for a size the level table refuses, or where a buffer would have to grow
+ * inside a capture or under a live graph.  orb->n_levels stays 1: it describes the one-level calls; the levels are
+ * ex->n_levels. */
+int pagk_orb_extract_slot(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_orb_params *orb, int32_t slot);
+/* The keypoint set of `slot` (what src/ORBextractor.cc:1113-1142 packs) into host arrays, synchronous: keypoints cap x 2
+ * floats, octave cap int32, response cap floats, angle cap floats, desc cap x 32 bytes, info PAGK_ORB_LEVELS_INFO_WORDS
+ * words; any array but keypoints may be NULL.  cap >= out_bound of the call that wrote the set (PAGK_E_ARG otherwise, or
+ * for a slot without a set). */
+int pagk_orb_slot_read(pagk_ctx *ctx, int32_t slot, int32_t cap, float *keypoints, int32_t *octave, float *response,
+                       float *angle, uint8_t *desc, int32_t *info);
+/* matcher->match and the distance filter of FindFeatureMatches (src/ORBDetectAndDespMatcher.cpp:61-81) between the sets of
+ * slot_q (query) and slot_t (train), both written by pagk_orb_extract_slot: the launches of pagk_orb_match_device on the
+ * context's own arrays and counts, the result kept by the context for slot_q.  Asynchronous on the context stream,
+ * capturable; run it once outside a capture first.  Two pagk_orb_extract_slot calls and one pagk_orb_match_slots call are
+ * FindFeatureMatches as one capturable chain. */
+int pagk_orb_match_slots(pagk_ctx *ctx, const pagk_orb_params *orb, int32_t slot_q, int32_t slot_t);
+/* The result of the last pagk_orb_match_slots with slot_q as the query (src/ORBDetectAndDespMatcher.cpp:61-81), synchronous:
+ * train_idx, distance cap int32 each, keep cap bytes, info (or NULL) PAGK_ORB_INFO_WORDS words (the match info).  cap >= the
+ * query set's out_bound; rows at or beyond the query count hold -1 / 257 / 0. */
+int pagk_orb_match_slots_read(pagk_ctx *ctx, int32_t slot_q, int32_t cap, int32_t *train_idx, int32_t *distance,
+                              uint8_t *keep, int32_t *info);
+/* ORBextractor::operator() with host buffers, synchronous (src/ORBextractor.cc:1066-1146): the image is uploaded into a
+ * scratch slot, pagk_orb_extract_slot's launches run, the set is read back as by pagk_orb_slot_read. */
+int pagk_orb_extract_levels(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_orb_params *orb, const pagk_image *img,
+                            int32_t cap, float *keypoints, int32_t *octave, float *response, float *angle, uint8_t *desc,
+                            int32_t *info);
+/* ORBextractor::DetectFeatures with host buffers, synchronous (src/ORBextractor.cc:1148-1205): mask (or NULL)
+ * img->width * img->height bytes; keypoints cap x 2 floats, octave (or NULL) cap int32, response (or NULL) cap floats, info
+ * (or NULL) PAGK_ORB_LEVELS_INFO_WORDS words ([1] is 0).  The output is a candidate list in the reference's order: an
+ * application copies it into the candidate array of pagk_frame_handover_device. */
+int pagk_orb_detect_levels(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_image *img, const uint8_t *mask,
+                           int32_t cap, float *keypoints, int32_t *octave, float *response, int32_t *info);
+/* Diagnostic, never on the per-frame path: level `level` (0 .. n_levels - 1) of the scale pyramid that the last
+ * pagk_orb_extract_slot built for `slot` (ComputePyramid, src/ORBextractor.cc:1207-1230), into dst with rows of `pitch`
+ * bytes.  Host pointer, synchronous, not between pagk_graph_begin and pagk_graph_end.  Localises a mismatch to the resize. */
+int pagk_selftest_orb_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int64_t pitch);
 
 /* ---- Pyramidal Lucas-Kanade: tracker type 0, the image-only baseline of the reference's comparison ------------------ */
 /* GyroAidedTracker::TrackFeatures with mType == OPENCV_OPTICAL_FLOW_PYR_LK (src/gyro_aided_tracker.cpp:353-380) calls
@@ -987,7 +1098,7 @@ int pagk_selftest_fill_workspaces(pagk_ctx *ctx, uint32_t word, int32_t also_new
  * pagk_geometry_fit_device, pagk_geometry_validation_device, pagk_frame_handover_device, pagk_detect_corners_device,
  * pagk_frame_handover_detect_device, pagk_detect_fast_device,
  * pagk_frame_handover_fast_device, pagk_frame_rectify_device, pagk_orb_describe_device, pagk_orb_match_device,
- * pagk_lk_pyramid_device, pagk_lk_track_device, pagk_match_features_device, pagk_search_gyro_predict_device,
+ * pagk_orb_extract_slot, pagk_orb_match_slots, pagk_lk_pyramid_device, pagk_lk_track_device, pagk_match_features_device, pagk_search_gyro_predict_device,
  * pagk_search_klt_device; and the
  * pinned-memory forms pagk_frame_upload_pinned,
  * pagk_frame_rectify_pinned) are recorded on the context stream instead of executed,

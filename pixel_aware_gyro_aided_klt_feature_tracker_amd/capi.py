@@ -78,6 +78,12 @@ class OrbParams(C.Structure):
     _fields_ = [("blur_weights", C.c_int32 * 4), ("match_floor", C.c_int32), ("n_levels", C.c_int32)]
 
 
+class OrbExtractor(C.Structure):
+    """pagk_orb_extractor (include/pagk.h): the five constructor arguments of ORBextractor (src/ORBextractor.cc:434-437)."""
+    _fields_ = [("n_features", C.c_int32), ("scale_factor", C.c_float), ("n_levels", C.c_int32),
+                ("ini_threshold", C.c_int32), ("min_threshold", C.c_int32)]
+
+
 class LkParams(C.Structure):
     """pagk_lk_params (include/pagk.h): the constants of the reference's calcOpticalFlowPyrLK call and its error filter."""
     _fields_ = [("half_patch", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double),
@@ -101,6 +107,8 @@ ASSOC_STATS_FIELDS = ("avg1", "avg2", "max1", "max2", "threshold", "sum1", "sum2
 DETECT_INFO_WORDS = 8
 ORB_INFO_WORDS = 8
 LK_INFO_WORDS = 8
+ORB_MAX_LEVELS = 8
+ORB_LEVELS_INFO_WORDS = 32
 LK_INFO_FIELDS = ("n", "raw", "kept", "top_level", "lost_min_eig", "lost_out_of_range")
 ORB_DESCRIBE_INFO_FIELDS = ("described", "outside")
 ORB_MATCH_INFO_FIELDS = ("nq", "matches", "kept", "min_dist", "max_dist", "threshold")
@@ -337,6 +345,27 @@ def declare(lib) -> None:
         lib.pagk_orb_match_device.argtypes = [vp, _P(OrbParams), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         lib.pagk_orb_match.restype = C.c_int
         lib.pagk_orb_match.argtypes = [vp, _P(OrbParams), i32, vp, i32, vp, vp, vp, vp, vp]
+    if hasattr(lib, "pagk_orb_extract_slot"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
+        lib.pagk_orb_extractor_default.restype = None
+        lib.pagk_orb_extractor_default.argtypes = [_P(OrbExtractor)]
+        lib.pagk_orb_extractor_check.restype = C.c_int
+        lib.pagk_orb_extractor_check.argtypes = [_P(OrbExtractor)]
+        lib.pagk_orb_extractor_levels.restype = C.c_int
+        lib.pagk_orb_extractor_levels.argtypes = [_P(OrbExtractor), i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.pagk_orb_extract_slot.restype = C.c_int
+        lib.pagk_orb_extract_slot.argtypes = [vp, _P(OrbExtractor), _P(OrbParams), i32]
+        lib.pagk_orb_slot_read.restype = C.c_int
+        lib.pagk_orb_slot_read.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.pagk_orb_match_slots.restype = C.c_int
+        lib.pagk_orb_match_slots.argtypes = [vp, _P(OrbParams), i32, i32]
+        lib.pagk_orb_match_slots_read.restype = C.c_int
+        lib.pagk_orb_match_slots_read.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+        lib.pagk_orb_extract_levels.restype = C.c_int
+        lib.pagk_orb_extract_levels.argtypes = [vp, _P(OrbExtractor), _P(OrbParams), _P(Image), i32, vp, vp, vp, vp, vp, vp]
+        lib.pagk_orb_detect_levels.restype = C.c_int
+        lib.pagk_orb_detect_levels.argtypes = [vp, _P(OrbExtractor), _P(Image), vp, i32, vp, vp, vp, vp]
+        lib.pagk_selftest_orb_level.restype = C.c_int
+        lib.pagk_selftest_orb_level.argtypes = [vp, i32, i32, vp, C.c_int64]
     if hasattr(lib, "pagk_lk_track_device"):   # (absent from older builds that tools/ab_lib.py loads for A/B runs)
         lib.pagk_lk_params_default.restype = None
         lib.pagk_lk_params_default.argtypes = [_P(LkParams)]
@@ -515,6 +544,9 @@ EXPORTED_SYMBOLS = [
     "pagk_orb_params_default", "pagk_orb_params_check", "pagk_orb_pattern_check", "pagk_orb_set_pattern",
     "pagk_orb_describe_device", "pagk_orb_describe", "pagk_orb_match_device", "pagk_orb_match",
     "pagk_selftest_sample", "pagk_selftest_fill_workspaces",
+    "pagk_orb_extractor_default", "pagk_orb_extractor_check", "pagk_orb_extractor_levels", "pagk_orb_extract_slot",
+    "pagk_orb_slot_read", "pagk_orb_match_slots", "pagk_orb_match_slots_read", "pagk_orb_extract_levels",
+    "pagk_orb_detect_levels", "pagk_selftest_orb_level",
     "pagk_lk_params_default", "pagk_lk_params_check", "pagk_lk_levels", "pagk_lk_pyramid_device", "pagk_lk_track_device",
     "pagk_lk_track", "pagk_selftest_lk_level",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
@@ -616,6 +648,48 @@ def _orb_pattern(pattern) -> np.ndarray:
 def orb_pattern_check(pattern) -> int:
     """pagk_orb_pattern_check: PAGK_OK if every coordinate lies in [-13, 13] (needs no device)."""
     return int(load().pagk_orb_pattern_check(_orb_pattern(pattern).ctypes.data))
+
+
+def orb_extractor_default(**overrides) -> OrbExtractor:
+    """pagk_orb_extractor_default() with overrides (n_features, scale_factor, n_levels, ini_threshold, min_threshold)."""
+    e = OrbExtractor()
+    load().pagk_orb_extractor_default(C.byref(e))
+    for k, v in overrides.items():
+        if k not in dict(OrbExtractor._fields_):
+            raise TypeError(f"pagk_orb_extractor has no field {k}")
+        setattr(e, k, v)
+    return e
+
+
+def orb_extractor_check(e: OrbExtractor) -> int:
+    """pagk_orb_extractor_check: PAGK_OK or PAGK_E_ARG (needs no device)."""
+    return int(load().pagk_orb_extractor_check(C.byref(e)))
+
+
+def orb_extractor_levels(e: OrbExtractor, width: int, height: int):
+    """pagk_orb_extractor_levels (needs no device) -> dict(rc, and for rc == 0: n_levels, width, height, scale, quota, size
+    (arrays of n_levels entries) and out_bound)."""
+    lw, lh = np.zeros(ORB_MAX_LEVELS, np.int32), np.zeros(ORB_MAX_LEVELS, np.int32)
+    sc, quota, size = np.zeros(ORB_MAX_LEVELS, np.float32), np.zeros(ORB_MAX_LEVELS, np.int32), np.zeros(ORB_MAX_LEVELS, np.int32)
+    ob = C.c_int32(0)
+    rc = int(load().pagk_orb_extractor_levels(C.byref(e), int(width), int(height), lw.ctypes.data, lh.ctypes.data,
+                                              sc.ctypes.data, quota.ctypes.data, size.ctypes.data, C.addressof(ob)))
+    if rc:
+        return dict(rc=rc)
+    n = int(e.n_levels)
+    return dict(rc=0, n_levels=n, width=lw[:n], height=lh[:n], scale=sc[:n], quota=quota[:n], size=size[:n],
+                out_bound=int(ob.value))
+
+
+def _orb_set_dict(cap, kp, octave, resp, ang, desc, info) -> dict:
+    """The arrays of a keypoint set cut to its count, with the whole-capacity arrays under full_*."""
+    n = int(info[0])
+    out = dict(n=n, cap=cap, keypoints=kp[:n], octave=octave[:n], response=resp[:n], info=info,
+               full_keypoints=kp, full_octave=octave, full_response=resp, outside=int(info[1]), n_levels=int(info[2]),
+               level_counts=info[8:16].copy(), level_raw=info[16:24].copy(), level_quota=info[24:32].copy())
+    if ang is not None:
+        out.update(angle=ang[:n], desc=desc[:n], full_angle=ang, full_desc=desc)
+    return out
 
 
 def lk_params_default(**overrides) -> LkParams:
@@ -1396,6 +1470,79 @@ class Context:
         out = dict(train_idx=idx[:nq], distance=dist[:nq], keep=keep[:nq], info=info)
         out.update(zip(ORB_MATCH_INFO_FIELDS, (int(v) for v in info[:6])))
         return out
+
+    # ORB over a scale pyramid (src/ORBextractor.cc:434-470, 789-875, 1066-1232) --------------------------------------
+    orb_extractor_default = staticmethod(orb_extractor_default)
+
+    def orb_extract_slot(self, ex: OrbExtractor, slot: int, orb: OrbParams | None = None):
+        """pagk_orb_extract_slot: ORBextractor::operator() on frame slot `slot` into the slot's keypoint set (asynchronous,
+        capturable)."""
+        orb = orb if orb is not None else orb_params_default()
+        self._check(self.lib.pagk_orb_extract_slot(self.h, C.byref(ex), C.byref(orb), slot), "pagk_orb_extract_slot")
+
+    def orb_slot_read(self, slot: int, cap: int) -> dict:
+        """pagk_orb_slot_read (synchronous) -> dict(n, keypoints, octave, response, angle, desc (cut to n), info and its
+        words by name, full_* (cap rows))."""
+        cap = int(cap)
+        kp, octave = np.full((max(cap, 1), 2), 7, np.float32), np.full(max(cap, 1), 7, np.int32)
+        resp, ang = np.full(max(cap, 1), 7, np.float32), np.full(max(cap, 1), 7, np.float32)
+        desc, info = np.full((max(cap, 1), 32), 7, np.uint8), np.zeros(ORB_LEVELS_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_slot_read(self.h, slot, cap, _ptr(kp), _ptr(octave), _ptr(resp), _ptr(ang), _ptr(desc),
+                                                _ptr(info)), "pagk_orb_slot_read")
+        return _orb_set_dict(cap, kp, octave, resp, ang, desc, info)
+
+    def orb_match_slots(self, slot_q: int, slot_t: int, orb: OrbParams | None = None):
+        """pagk_orb_match_slots: the matcher and the distance filter between two slots' sets (asynchronous, capturable)."""
+        orb = orb if orb is not None else orb_params_default()
+        self._check(self.lib.pagk_orb_match_slots(self.h, C.byref(orb), slot_q, slot_t), "pagk_orb_match_slots")
+
+    def orb_match_slots_read(self, slot_q: int, cap: int) -> dict:
+        """pagk_orb_match_slots_read (synchronous) -> dict(train_idx, distance, keep (cap rows), info and its words by name)."""
+        cap = int(cap)
+        idx, dist = np.full(max(cap, 1), 7, np.int32), np.full(max(cap, 1), 7, np.int32)
+        keep, info = np.full(max(cap, 1), 7, np.uint8), np.zeros(ORB_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_match_slots_read(self.h, slot_q, cap, _ptr(idx), _ptr(dist), _ptr(keep), _ptr(info)),
+                    "pagk_orb_match_slots_read")
+        out = dict(train_idx=idx, distance=dist, keep=keep, info=info)
+        out.update(zip(ORB_MATCH_INFO_FIELDS, (int(v) for v in info[:6])))
+        return out
+
+    def orb_extract_levels(self, img: np.ndarray, ex: OrbExtractor, orb: OrbParams | None = None, cap: int | None = None) -> dict:
+        """pagk_orb_extract_levels, host buffers -> the dict of orb_slot_read.  cap defaults to the table's out_bound."""
+        orb = orb if orb is not None else orb_params_default()
+        iv = image_view(img)
+        if cap is None:
+            cap = orb_extractor_levels(ex, iv.width, iv.height).get("out_bound", 1)
+        cap = int(cap)
+        kp, octave = np.full((max(cap, 1), 2), 7, np.float32), np.full(max(cap, 1), 7, np.int32)
+        resp, ang = np.full(max(cap, 1), 7, np.float32), np.full(max(cap, 1), 7, np.float32)
+        desc, info = np.full((max(cap, 1), 32), 7, np.uint8), np.zeros(ORB_LEVELS_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_extract_levels(self.h, C.byref(ex), C.byref(orb), C.byref(iv), cap, _ptr(kp), _ptr(octave),
+                                                     _ptr(resp), _ptr(ang), _ptr(desc), _ptr(info)), "pagk_orb_extract_levels")
+        return _orb_set_dict(cap, kp, octave, resp, ang, desc, info)
+
+    def orb_detect_levels(self, img: np.ndarray, ex: OrbExtractor, mask=None, cap: int | None = None) -> dict:
+        """pagk_orb_detect_levels, host buffers -> dict(n, keypoints, octave, response (cut to n), info and its words by name,
+        full_* (cap rows)).  mask: height x width bytes or None."""
+        iv = image_view(img)
+        if cap is None:
+            cap = orb_extractor_levels(ex, iv.width, iv.height).get("out_bound", 1)
+        cap = int(cap)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (iv.height, iv.width):
+            raise ValueError("mask must be height x width")
+        kp, octave = np.full((max(cap, 1), 2), 7, np.float32), np.full(max(cap, 1), 7, np.int32)
+        resp, info = np.full(max(cap, 1), 7, np.float32), np.zeros(ORB_LEVELS_INFO_WORDS, np.int32)
+        self._check(self.lib.pagk_orb_detect_levels(self.h, C.byref(ex), C.byref(iv), _ptr(m), cap, _ptr(kp), _ptr(octave),
+                                                    _ptr(resp), _ptr(info)), "pagk_orb_detect_levels")
+        return _orb_set_dict(cap, kp, octave, resp, None, None, info)
+
+    def selftest_orb_level(self, slot: int, level: int, width: int, height: int, pitch: int | None = None) -> np.ndarray:
+        """pagk_selftest_orb_level: level `level` of the slot's ORB scale pyramid, height x width."""
+        pitch = width if pitch is None else int(pitch)
+        buf = np.zeros((height, pitch), np.uint8)
+        self._check(self.lib.pagk_selftest_orb_level(self.h, slot, level, buf.ctypes.data, pitch), "pagk_selftest_orb_level")
+        return buf[:, :width]
 
     # pyramidal Lucas-Kanade, tracker type 0 (src/gyro_aided_tracker.cpp:353-380) -------------------------------------
     lk_params_default = staticmethod(lk_params_default)

@@ -103,7 +103,8 @@ __device__ __forceinline__ int fast_m(const uint8_t (*s)[kFastWinPitch], int y, 
 // S_t: the score of a corner at threshold t, 0 for everything else
 __device__ __forceinline__ int fast_score(int m, int t) { return m > t ? m - 1 : 0; }
 
-__global__ void __launch_bounds__(256) k_fast_cells(FastCellArgs a)
+// (the body is a function of its own so that pagk_orb_levels_kernel.h can run it on one of several levels per launch)
+__device__ __forceinline__ void fast_cells_body(const FastCellArgs &a)
 {
     __shared__ uint8_t s_img[kFastWin][kFastWinPitch];
     __shared__ uint8_t s_m[kFastWin][kFastWinPitch];   // max(m, 0); 0 outside the cell's detection region
@@ -168,6 +169,8 @@ __global__ void __launch_bounds__(256) k_fast_cells(FastCellArgs a)
         a.cell_cnt[cell] = (total < g.seg ? total : g.seg) | (pass >= 1 ? kFastCellFirstEmpty : 0) | (pass >= 2 ? kFastCellEmpty : 0);
 }
 
+__global__ void __launch_bounds__(256) k_fast_cells(FastCellArgs a) { fast_cells_body(a); }
+
 // exclusive prefix of v over the workgroup's 1024 in thread order, and the workgroup's total
 __device__ __forceinline__ int32_t fast_scan1024(int32_t v, int32_t *wtot, int lane, int wave, int32_t &tot)
 {
@@ -190,8 +193,8 @@ __device__ __forceinline__ int32_t fast_scan1024(int32_t v, int32_t *wtot, int l
 }
 
 // One workgroup: cell_off[c] = the keys of the cells in front of c; the control words.
-__global__ void __launch_bounds__(1024) k_fast_offsets(int32_t n_cells, const int32_t *cell_cnt, int32_t *cell_off, int32_t *ctl,
-                                                       const int32_t *skip)
+__device__ __forceinline__ void fast_offsets_body(int32_t n_cells, const int32_t *cell_cnt, int32_t *cell_off, int32_t *ctl,
+                                                  const int32_t *skip)
 {
     __shared__ int32_t s_wtot[16];
     if (skip && *skip) return;
@@ -210,16 +213,29 @@ __global__ void __launch_bounds__(1024) k_fast_offsets(int32_t n_cells, const in
     if (tid == 0) ctl[kFastCtlCount] = base, ctl[kFastCtlFirstEmpty] = first, ctl[kFastCtlEmpty] = empty;
 }
 
+__global__ void __launch_bounds__(1024) k_fast_offsets(int32_t n_cells, const int32_t *cell_cnt, int32_t *cell_off, int32_t *ctl,
+                                                       const int32_t *skip)
+{
+    fast_offsets_body(n_cells, cell_cnt, cell_off, ctl, skip);
+}
+
 // one workgroup per cell: its segment to its place in the raw list
-__global__ void __launch_bounds__(256) k_fast_gather(int32_t seg, const int32_t *cell_cnt, const int32_t *cell_off,
-                                                     const uint32_t *seg_xy, const int32_t *seg_score, uint32_t *kxy,
-                                                     int32_t *kscore, const int32_t *skip)
+__device__ __forceinline__ void fast_gather_body(int32_t seg, const int32_t *cell_cnt, const int32_t *cell_off,
+                                                 const uint32_t *seg_xy, const int32_t *seg_score, uint32_t *kxy,
+                                                 int32_t *kscore, const int32_t *skip)
 {
     if (skip && *skip) return;
     const int cell = blockIdx.x;
     const int32_t cnt = cell_cnt[cell] & kFastCellCountMask, off = cell_off[cell];
     const size_t seg0 = (size_t)cell * seg;
     for (int r = threadIdx.x; r < cnt && r < seg; r += 256) kxy[off + r] = seg_xy[seg0 + r], kscore[off + r] = seg_score[seg0 + r];
+}
+
+__global__ void __launch_bounds__(256) k_fast_gather(int32_t seg, const int32_t *cell_cnt, const int32_t *cell_off,
+                                                     const uint32_t *seg_xy, const int32_t *seg_score, uint32_t *kxy,
+                                                     int32_t *kscore, const int32_t *skip)
+{
+    fast_gather_body(seg, cell_cnt, cell_off, seg_xy, seg_score, kxy, kscore, skip);
 }
 
 struct FastTreeArgs {
@@ -257,7 +273,7 @@ __device__ __forceinline__ int4 fast_child_box(const int4 b, int q)
     return make_int4(q & 1 ? mx : b.x, q & 2 ? my : b.y, q & 1 ? b.z : mx, q & 2 ? b.w : my);
 }
 
-__global__ void __launch_bounds__(1024) k_fast_tree(FastTreeArgs a)
+__device__ __forceinline__ void fast_tree_body(const FastTreeArgs &a)
 {
     __shared__ int32_t s_wtot[16];
     __shared__ int32_t s_nexp;
@@ -468,5 +484,7 @@ __global__ void __launch_bounds__(1024) k_fast_tree(FastTreeArgs a)
         a.info[7] = bad ? -1 : 0;
     }
 }
+
+__global__ void __launch_bounds__(1024) k_fast_tree(FastTreeArgs a) { fast_tree_body(a); }
 
 }  // namespace pagk

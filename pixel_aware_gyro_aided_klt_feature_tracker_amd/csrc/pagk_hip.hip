@@ -18,6 +18,7 @@
 #include "pagk_inverse_kernel.h"
 #include "pagk_associate_kernel.h"
 #include "pagk_pose_kernel.h"
+#include "pagk_orb_levels_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
@@ -76,6 +77,13 @@ struct pagk_ctx {
         ORB_KEYS,      // ... the matcher's best-match keys: sized by cap_q
         LK_PYR,        // Lucas-Kanade (pagk_lk_kernel.h): the pyrDown levels of slot 0 ...
         LK_PYR_LAST = LK_PYR + kSlots - 1,   // ... to slot kSlots - 1, each sized by W, H and the top level
+        ORBL_WS,       // ORB over a scale pyramid (pagk_orb_levels_kernel.h): a slice per level -- the FAST workspace, the blurred level, the level's keypoint segment
+        ORBL_PYR,      // ... the resized levels 1 .. of slot 0 ...
+        ORBL_PYR_LAST = ORBL_PYR + kSlots - 1,   // ... to slot kSlots - 1, each sized by the level table
+        ORBL_SET,      // ... the packed keypoint set of slot 0 ...
+        ORBL_SET_LAST = ORBL_SET + kSlots - 1,   // ... to slot kSlots - 1, each sized by the table's out_bound
+        ORBL_MATCH,    // ... the match result of query slot 0 ...
+        ORBL_MATCH_LAST = ORBL_MATCH + kSlots - 1,   // ... to slot kSlots - 1, each sized by the query set's capacity
         ASSOC,         // track-to-detection association (pagk_associate_kernel.h): choices and claims, sized by n and m
         POSE,          // workspace of the two-view pose (pagk_pose_kernel.h): sized for pose_n correspondences and pose_iters hypotheses
         POSEIO,        // scratch of the host-buffer pose entry point
@@ -92,6 +100,14 @@ struct pagk_ctx {
     int rect_w = 0, rect_h = 0, rect_wp = 0;
     bool orb_pattern_set = false;
     struct LkPyr { int w = 0, h = 0, top = -1; } lk_pyr[kSlots];   // what buf[LK_PYR + slot] holds (top -1: nothing)
+    // what buf[ORBL_PYR + slot], buf[ORBL_SET + slot] and buf[ORBL_MATCH + slot] hold (n_levels 0, cap 0: nothing)
+    struct OrbLevelsSlot {
+        int w = 0, h = 0, n_levels = 0;
+        int lw[kOrbMaxLevels] = {}, lh[kOrbMaxLevels] = {};
+        int cap = 0;             // rows of the keypoint set
+        bool described = false;  // the set has angles and descriptors (pagk_orb_extract_slot, not the detect form)
+        int match_cap = 0;       // rows of the match result with this slot as the query
+    } orbl[kSlots];
     void *queue = nullptr;    // k_track_rows: the work-queue counter (256 B)
     // per half patch (0 = not asked yet), the resident waves (occupancy x CUs) on this device of ...
     int quad_capacity[PAGK_MAX_HALF_PATCH + 1] = {};  // ... the generic whole-feature k_track_quad: the hand-over rule's "round"
@@ -2526,30 +2542,49 @@ struct FastWs {
     int32_t raw_bound = 0, out_bound = 0, n_cells = 0;
 };
 
-int fast_workspace(pagk_ctx *ctx, const FastGrid &g, int32_t n_features, FastWs *ws)
+// the parts of the detector's workspace for grid g and target n_features (false: a raw list beyond 2^30 keys)
+constexpr int kFastWsParts = 20;
+bool fast_ws_sizes(const FastGrid &g, int32_t n_features, size_t *sizes, uint32_t *sort_slots)
 {
     const int64_t rb64 = fast_raw_bound(g);
-    if (rb64 > (1 << 30)) return PAGK_E_ARG;
+    if (rb64 > (1 << 30)) return false;
     const size_t rb = (size_t)rb64, ob = (size_t)fast_out_bound(g, n_features), nc = (size_t)g.n_rows * g.n_cols;
     uint32_t slots = 2;
     while (slots < ob) slots <<= 1;
-    const size_t sizes[20] = {256,    nc * 4, nc * 4, rb * 4, rb * 4, rb * 4, rb * 4,  rb * 4, ob * 16,           ob * 16,
-                              ob * 4, ob * 4, ob * 4, ob * 4, ob * 16, ob * 4, ob * 4, (size_t)slots * 8, ob * 8, ob * 8};
-    const Layout<20> lay(sizes);
+    const size_t v[kFastWsParts] = {256,    nc * 4, nc * 4, rb * 4, rb * 4, rb * 4, rb * 4,  rb * 4, ob * 16,           ob * 16,
+                                    ob * 4, ob * 4, ob * 4, ob * 4, ob * 16, ob * 4, ob * 4, (size_t)slots * 8, ob * 8, ob * 8};
+    std::copy(v, v + kFastWsParts, sizes);
+    *sort_slots = slots;
+    return true;
+}
+
+// ... and their addresses: part k of the workspace lies off[k] bytes into the block at b
+void fast_ws_carve(const size_t *off, void *b, const FastGrid &g, int32_t n_features, uint32_t slots, FastWs *ws)
+{
+    auto part = [&](int k) { return static_cast<uint8_t *>(b) + off[k]; };
+    auto i32 = [&](int k) { return reinterpret_cast<int32_t *>(part(k)); };
+    ws->ctl = i32(0), ws->cell_cnt = i32(1), ws->cell_off = i32(2);
+    ws->seg_xy = reinterpret_cast<uint32_t *>(part(3)), ws->seg_score = i32(4);
+    ws->kxy = reinterpret_cast<uint32_t *>(part(5)), ws->kscore = i32(6), ws->knode = i32(7);
+    ws->box[0] = reinterpret_cast<int4 *>(part(8)), ws->box[1] = reinterpret_cast<int4 *>(part(9));
+    ws->ncnt[0] = i32(10), ws->ncnt[1] = i32(11), ws->ncand[0] = i32(12), ws->ncand[1] = i32(13);
+    ws->cnt4 = i32(14), ws->cbase = i32(15), ws->split = i32(16);
+    ws->sortk = reinterpret_cast<unsigned long long *>(part(17)), ws->best = reinterpret_cast<unsigned long long *>(part(18));
+    ws->cand = reinterpret_cast<float *>(part(19));
+    ws->sort_slots = slots, ws->raw_bound = (int32_t)fast_raw_bound(g), ws->out_bound = fast_out_bound(g, n_features);
+    ws->n_cells = g.n_rows * g.n_cols;
+}
+
+int fast_workspace(pagk_ctx *ctx, const FastGrid &g, int32_t n_features, FastWs *ws)
+{
+    size_t sizes[kFastWsParts];
+    uint32_t slots;
+    if (!fast_ws_sizes(g, n_features, sizes, &slots)) return PAGK_E_ARG;
+    const Layout<kFastWsParts> lay(sizes);
     int rc = reserve(ctx, ctx->buf[pagk_ctx::FAST], lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the FAST detector's workspace",
                      "run the call once with this image size and n_features before capturing");
     if (rc) return rc;
-    void *b = ctx->buf[pagk_ctx::FAST].ptr;
-    ws->ctl = lay.at<int32_t>(b, 0), ws->cell_cnt = lay.at<int32_t>(b, 1), ws->cell_off = lay.at<int32_t>(b, 2);
-    ws->seg_xy = lay.at<uint32_t>(b, 3), ws->seg_score = lay.at<int32_t>(b, 4);
-    ws->kxy = lay.at<uint32_t>(b, 5), ws->kscore = lay.at<int32_t>(b, 6), ws->knode = lay.at<int32_t>(b, 7);
-    ws->box[0] = lay.at<int4>(b, 8), ws->box[1] = lay.at<int4>(b, 9);
-    ws->ncnt[0] = lay.at<int32_t>(b, 10), ws->ncnt[1] = lay.at<int32_t>(b, 11);
-    ws->ncand[0] = lay.at<int32_t>(b, 12), ws->ncand[1] = lay.at<int32_t>(b, 13);
-    ws->cnt4 = lay.at<int32_t>(b, 14), ws->cbase = lay.at<int32_t>(b, 15), ws->split = lay.at<int32_t>(b, 16);
-    ws->sortk = lay.at<unsigned long long>(b, 17), ws->best = lay.at<unsigned long long>(b, 18);
-    ws->cand = lay.at<float>(b, 19);
-    ws->sort_slots = slots, ws->raw_bound = (int32_t)rb, ws->out_bound = (int32_t)ob, ws->n_cells = (int32_t)nc;
+    fast_ws_carve(lay.off, ctx->buf[pagk_ctx::FAST].ptr, g, n_features, slots, ws);
     return PAGK_OK;
 }
 
@@ -3180,6 +3215,416 @@ int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, con
         (rc = s.out(5, keep, (size_t)nq)) || (rc = s.out(6, info, kOrbInfoWords * 4)))
         return rc;
     return s.finish();
+}
+
+// ---- ORB over a scale pyramid (pagk_orb_levels_kernel.h) ----------------------------------------------------------
+namespace {
+
+int orb_extractor_check(const pagk_orb_extractor *e)
+{
+    if (!e || e->n_levels < 1 || e->n_levels > kOrbMaxLevels || !(e->scale_factor > 1.0f) || !(e->scale_factor <= 1.5f) ||
+        e->ini_threshold < 0 || e->ini_threshold > 255 || e->min_threshold < 0 || e->min_threshold > 255 || e->n_features < 1 ||
+        e->n_features > (1 << 24))
+        return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+// The level table of src/ORBextractor.cc:439-470 and :1211-1212 for a W x H image.
+struct OrbLevelTable {
+    int L = 0;
+    int w[kOrbMaxLevels], h[kOrbMaxLevels], quota[kOrbMaxLevels], N[kOrbMaxLevels], size[kOrbMaxLevels], ob[kOrbMaxLevels];
+    float sc[kOrbMaxLevels], inv[kOrbMaxLevels];
+    FastGrid g[kOrbMaxLevels];
+    int64_t cap = 0;   // the sum of the levels' out_bound
+};
+
+int orb_level_table(const pagk_orb_extractor *e, int W, int H, OrbLevelTable *t)
+{
+    if (orb_extractor_check(e) || W < 1 || H < 1 || W > 32767 || H > 32767) return PAGK_E_ARG;
+    const int L = t->L = e->n_levels;
+    t->sc[0] = 1.0f, t->inv[0] = 1.0f;   // :446-455
+    for (int l = 1; l < L; l++) t->sc[l] = t->sc[l - 1] * e->scale_factor, t->inv[l] = 1.0f / t->sc[l];
+    const float factor = 1.0f / e->scale_factor;   // :459-470
+    double p = 1.0;
+    for (int l = 0; l < L; l++) p *= (double)factor;   // (the library's rule in place of pow)
+    float nd = ((float)e->n_features * (1.0f - factor)) / (1.0f - (float)p);
+    int sum = 0;
+    for (int l = 0; l < L - 1; l++) {
+        t->quota[l] = (int)std::lrint(nd);   // cvRound: ties to even
+        sum += t->quota[l];
+        nd *= factor;
+    }
+    t->quota[L - 1] = std::max(e->n_features - sum, 0);
+    t->cap = 0;
+    for (int l = 0; l < L; l++) {
+        t->w[l] = (int)std::lrint((float)W * t->inv[l]), t->h[l] = (int)std::lrint((float)H * t->inv[l]);   // :1211-1212
+        t->N[l] = std::max(t->quota[l], 1);
+        t->size[l] = (int)(31.0f * t->sc[l]);
+        if (!fast_grid(t->w[l], t->h[l], &t->g[l]) || fast_raw_bound(t->g[l]) > (1 << 30)) return PAGK_E_ARG;
+        t->ob[l] = fast_out_bound(t->g[l], t->N[l]);
+        t->cap += t->ob[l];
+    }
+    return t->cap > (1ll << 30) ? PAGK_E_ARG : PAGK_OK;
+}
+
+int orbl_pitch(int w) { return (w + 3) & ~3; }
+
+// where the levels 1 .. L - 1 lie in buf[ORBL_PYR + slot] (part l - 1 is level l, rows of orbl_pitch(w[l]) bytes)
+Layout<kOrbMaxLevels> orbl_pyr_layout(const int *lw, const int *lh, int L)
+{
+    size_t sizes[kOrbMaxLevels] = {};
+    for (int l = 1; l < L; l++) sizes[l - 1] = (size_t)orbl_pitch(lw[l]) * lh[l];
+    return Layout<kOrbMaxLevels>(sizes, std::max(L - 1, 1));
+}
+
+// the keypoint set of a slot: keypoints | octave | response | angle | descriptors | info ([0] is the set's device count)
+struct OrbSet {
+    float *kp, *resp, *angle;
+    int32_t *octave, *info;
+    uint8_t *desc;
+};
+Layout<6> orbl_set_layout(size_t cap)
+{
+    const size_t sizes[6] = {cap * 8, cap * 4, cap * 4, cap * 4, cap * 32, kOrbLevelsInfoWords * sizeof(int32_t)};
+    return Layout<6>(sizes);
+}
+OrbSet orbl_set_at(void *b, size_t cap)
+{
+    const Layout<6> lay = orbl_set_layout(cap);
+    return {lay.at<float>(b, 0), lay.at<float>(b, 2), lay.at<float>(b, 3), lay.at<int32_t>(b, 1), lay.at<int32_t>(b, 5),
+            lay.at<uint8_t>(b, 4)};
+}
+
+// the match result of a query slot: train_idx | distance | keep | info
+Layout<4> orbl_match_layout(size_t cap)
+{
+    const size_t sizes[4] = {cap * 4, cap * 4, cap, kOrbInfoWords * sizeof(int32_t)};
+    return Layout<4>(sizes);
+}
+
+// a level's slice of buf[ORBL_WS]: the detector's parts, then the blurred level | keypoints | response | angle | descriptors |
+// the detector's info | the describer's info
+constexpr int kOrblParts = kFastWsParts + 7;
+
+// ORBextractor::operator() (orb != nullptr) or DetectFeatures (orb == nullptr, d_mask or nullptr) on frame slot `slot`, into
+// the slot's keypoint set; arguments checked here.  (slots 4 and 5 are the host-buffer forms' own)
+int orb_levels_slot(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_orb_params *orb, int32_t slot, const uint8_t *d_mask,
+                    const char *what)
+{
+    if (!ctx || slot < 0 || slot >= kSlots) return PAGK_E_ARG;
+    int rc = orb ? orb_params_check(orb) : PAGK_OK;
+    if (rc) return rc;
+    if (orb && !ctx->orb_pattern_set) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: no sampling pattern set (pagk_orb_set_pattern)", what);
+        return PAGK_E_ARG;
+    }
+    const FrameSlot &s = ctx->slots[slot];
+    if (!fast_slot_ok(s)) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: frame slot %d holds no image", what, slot);
+        return PAGK_E_ARG;
+    }
+    OrbLevelTable t;
+    if (orb_level_table(ex, s.w, s.h, &t)) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: the extractor's parameters, or a level of a %d x %d image, are outside the definition "
+                 "(pagk_orb_extractor_levels)", what, s.w, s.h);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int L = t.L;
+    const char *hint = "run the call once with this image size and these parameters before capturing";
+    // the three buffers: workspace, the slot's pyramid, the slot's set
+    size_t sizes[kOrbMaxLevels * kOrblParts];
+    uint32_t sort_slots[kOrbMaxLevels];
+    for (int l = 0; l < L; l++) {
+        size_t *z = sizes + l * kOrblParts;
+        if (!fast_ws_sizes(t.g[l], t.N[l], z, &sort_slots[l])) return PAGK_E_ARG;
+        const size_t ob = (size_t)t.ob[l];
+        z[kFastWsParts + 0] = (size_t)orbl_pitch(t.w[l]) * t.h[l];
+        z[kFastWsParts + 1] = ob * 8, z[kFastWsParts + 2] = ob * 4, z[kFastWsParts + 3] = ob * 4, z[kFastWsParts + 4] = ob * 32;
+        z[kFastWsParts + 5] = 256, z[kFastWsParts + 6] = 256;
+    }
+    const Layout<kOrbMaxLevels * kOrblParts> wlay(sizes, L * kOrblParts);
+    const Layout<kOrbMaxLevels> play = orbl_pyr_layout(t.w, t.h, L);
+    const size_t cap = (size_t)t.cap;
+    DevBuf &wsb = ctx->buf[pagk_ctx::ORBL_WS], &pyr = ctx->buf[pagk_ctx::ORBL_PYR + slot], &setb = ctx->buf[pagk_ctx::ORBL_SET + slot];
+    pagk_ctx::OrbLevelsSlot &st = ctx->orbl[slot];
+    if ((rc = reserve(ctx, wsb, wlay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the workspace of ORB over a scale pyramid", hint)))
+        return rc;
+    rc = reserve(ctx, pyr, play.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the ORB scale pyramid of a slot", hint);
+    if (!rc) rc = reserve(ctx, setb, orbl_set_layout(cap).total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the ORB keypoint set of a slot", hint);
+    if (rc) {
+        if (!pyr.ptr) st.n_levels = 0;   // (a failed allocation left the buffer empty: the slot has no pyramid / no set)
+        if (!setb.ptr) st.cap = 0;
+        return rc;
+    }
+    st.n_levels = 0, st.cap = 0;   // nothing valid until everything has been enqueued
+    // the pyramid (:1207-1230): level l from level l - 1
+    const uint8_t *img[kOrbMaxLevels];
+    long long pitch[kOrbMaxLevels];
+    img[0] = s.img0, pitch[0] = (long long)s.pitch0;
+    for (int l = 1; l < L; l++) {
+        OrbResizeArgs r;
+        r.src = img[l - 1], r.spitch = pitch[l - 1], r.dst = play.at<uint8_t>(pyr.ptr, l - 1);
+        r.sw = t.w[l - 1], r.sh = t.h[l - 1], r.dw = t.w[l], r.dh = t.h[l], r.dpitch = orbl_pitch(t.w[l]);
+        r.scale_x = 1.0 / ((double)r.dw / r.sw), r.scale_y = 1.0 / ((double)r.dh / r.sh);
+        hipLaunchKernelGGL(k_orb_resize, dim3((unsigned)((r.dpitch / 4 + 63) / 64), (unsigned)((r.dh + 3) / 4)), dim3(256), 0,
+                           ctx->stream, r);
+        HIPCHK(ctx, hipGetLastError());
+        img[l] = r.dst, pitch[l] = r.dpitch;
+    }
+    // the stages of the one-level definition, one launch each, the level as a grid dimension
+    FastCellLevels cells;
+    FastListLevels lists;
+    FastTreeLevels trees;
+    OrbBlurLevels blurs;
+    OrbDescLevels descs;
+    OrbPackArgs pk;
+    memset(&cells, 0, sizeof cells), memset(&lists, 0, sizeof lists), memset(&trees, 0, sizeof trees);
+    memset(&blurs, 0, sizeof blurs), memset(&descs, 0, sizeof descs), memset(&pk, 0, sizeof pk);
+    int max_cells = 0, max_bx = 0, max_by = 0, max_db = 0;
+    pagk_fast_params fp;
+    fp.ini_threshold = ex->ini_threshold, fp.min_threshold = ex->min_threshold, fp.n_features = 0, fp.n_levels = 1;
+    for (int l = 0; l < L; l++) {
+        FastWs ws;
+        fast_ws_carve(wlay.off + l * kOrblParts, wsb.ptr, t.g[l], t.N[l], sort_slots[l], &ws);
+        const int first = l * kOrblParts + kFastWsParts;
+        uint8_t *blur = wlay.at<uint8_t>(wsb.ptr, first);
+        float *kp = wlay.at<float>(wsb.ptr, first + 1), *resp = wlay.at<float>(wsb.ptr, first + 2);
+        float *angle = wlay.at<float>(wsb.ptr, first + 3);
+        uint8_t *desc = wlay.at<uint8_t>(wsb.ptr, first + 4);
+        int32_t *finfo = wlay.at<int32_t>(wsb.ptr, first + 5), *oinfo = wlay.at<int32_t>(wsb.ptr, first + 6);
+        FastCellArgs &c = cells.a[l];
+        c.img = img[l], c.pitch = pitch[l], c.g = t.g[l], c.t_ini = fp.ini_threshold, c.t_min = fp.min_threshold;
+        c.seg_xy = ws.seg_xy, c.seg_score = ws.seg_score, c.cell_cnt = ws.cell_cnt, c.skip = nullptr;
+        cells.n_cells[l] = ws.n_cells;
+        max_cells = std::max(max_cells, ws.n_cells);
+        FastListArgs &li = lists.a[l];
+        li.n_cells = ws.n_cells, li.seg = t.g[l].seg, li.cell_cnt = ws.cell_cnt, li.cell_off = ws.cell_off, li.ctl = ws.ctl;
+        li.seg_xy = ws.seg_xy, li.seg_score = ws.seg_score, li.kxy = ws.kxy, li.kscore = ws.kscore;
+        FastTreeArgs &tr = trees.a[l];
+        tr.g = t.g[l], tr.n_features = t.N[l], tr.cap = t.ob[l], tr.out_bound = ws.out_bound, tr.raw_bound = ws.raw_bound;
+        tr.sort_slots = ws.sort_slots, tr.ctl = ws.ctl, tr.kxy = ws.kxy, tr.kscore = ws.kscore, tr.knode = ws.knode;
+        for (int k = 0; k < 2; k++) tr.box[k] = ws.box[k], tr.ncnt[k] = ws.ncnt[k], tr.ncand[k] = ws.ncand[k];
+        tr.cnt4 = ws.cnt4, tr.cbase = ws.cbase, tr.split = ws.split, tr.sortk = ws.sortk, tr.best = ws.best;
+        tr.mask = nullptr, tr.out_xy = kp, tr.out_resp = resp, tr.info = finfo, tr.skip = nullptr;
+        OrbBlurArgs &b = blurs.a[l];
+        b.img = img[l], b.pitch = pitch[l], b.blur = blur, b.info = oinfo, b.W = t.w[l], b.H = t.h[l], b.wp = orbl_pitch(t.w[l]);
+        if (orb) b.w0 = orb->blur_weights[0], b.w1 = orb->blur_weights[1], b.w2 = orb->blur_weights[2], b.w3 = orb->blur_weights[3];
+        blurs.nbx[l] = (t.w[l] + kOrbBlurTx - 1) / kOrbBlurTx, blurs.nby[l] = (t.h[l] + kOrbBlurTy - 1) / kOrbBlurTy;
+        max_bx = std::max(max_bx, blurs.nbx[l]), max_by = std::max(max_by, blurs.nby[l]);
+        OrbDescArgs &d = descs.a[l];
+        d.img = img[l], d.pitch = pitch[l], d.blur = blur;
+        d.pattern = static_cast<const int32_t *>(ctx->buf[pagk_ctx::ORB_PATTERN].ptr);
+        d.keypoints = kp, d.n = finfo, d.angle = angle, d.desc = desc, d.info = oinfo;
+        d.W = t.w[l], d.H = t.h[l], d.wp = b.wp, d.cap = t.ob[l];
+        descs.n_blocks[l] = (t.ob[l] + 3) / 4;
+        max_db = std::max(max_db, descs.n_blocks[l]);
+        OrbPackLevel &v = pk.lv[l];
+        v.kp = kp, v.resp = resp, v.angle = orb ? angle : nullptr, v.desc = orb ? desc : nullptr, v.fast_info = finfo;
+        v.orb_info = orb ? oinfo : nullptr, v.seg_cap = t.ob[l], v.quota = t.quota[l], v.scale = t.sc[l];
+    }
+    hipLaunchKernelGGL(k_fast_cells_levels, dim3((unsigned)max_cells, (unsigned)L), dim3(256), 0, ctx->stream, cells);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_offsets_levels, dim3((unsigned)L), dim3(1024), 0, ctx->stream, lists);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_gather_levels, dim3((unsigned)max_cells, (unsigned)L), dim3(256), 0, ctx->stream, lists);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_fast_tree_levels, dim3((unsigned)L), dim3(1024), 0, ctx->stream, trees);
+    HIPCHK(ctx, hipGetLastError());
+    if (orb) {
+        hipLaunchKernelGGL(k_orb_blur_levels, dim3((unsigned)max_bx, (unsigned)max_by, (unsigned)L), dim3(256), 0, ctx->stream, blurs);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_orb_describe_levels, dim3((unsigned)max_db, (unsigned)L), dim3(256), 0, ctx->stream, descs);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    const OrbSet set = orbl_set_at(setb.ptr, cap);
+    pk.n_levels = L, pk.cap = (int32_t)cap, pk.W = s.w, pk.H = s.h, pk.mask = d_mask;
+    pk.kp = set.kp, pk.octave = set.octave, pk.resp = set.resp, pk.angle = set.angle, pk.desc = set.desc, pk.info = set.info;
+    hipLaunchKernelGGL(k_orb_pack, dim3(1), dim3(1024), 0, ctx->stream, pk);
+    HIPCHK(ctx, hipGetLastError());
+    st.w = s.w, st.h = s.h, st.n_levels = L, st.cap = (int)cap, st.described = orb != nullptr;
+    std::copy(t.w, t.w + L, st.lw), std::copy(t.h, t.h + L, st.lh);
+    return PAGK_OK;
+}
+
+// the slot's set into host arrays (cap rows each; rows at or beyond the set's capacity are zeroed here)
+int orb_slot_read(pagk_ctx *ctx, int32_t slot, int32_t cap, float *keypoints, int32_t *octave, float *response, float *angle,
+                  uint8_t *desc, int32_t *info)
+{
+    if (!ctx || slot < 0 || slot >= kSlots || !keypoints) return PAGK_E_ARG;
+    const pagk_ctx::OrbLevelsSlot &st = ctx->orbl[slot];
+    if (st.cap < 1 || cap < st.cap) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_orb_slot_read: slot %d has %s (cap %d)", slot,
+                 st.cap < 1 ? "no keypoint set" : "a set of more rows than cap", cap);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)st.cap, rest = (size_t)cap - n;
+    const OrbSet set = orbl_set_at(ctx->buf[pagk_ctx::ORBL_SET + slot].ptr, n);
+    hipStream_t q = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(keypoints, set.kp, n * 8, hipMemcpyDeviceToHost, q));
+    if (octave) HIPCHK(ctx, hipMemcpyAsync(octave, set.octave, n * 4, hipMemcpyDeviceToHost, q));
+    if (response) HIPCHK(ctx, hipMemcpyAsync(response, set.resp, n * 4, hipMemcpyDeviceToHost, q));
+    if (angle && st.described) HIPCHK(ctx, hipMemcpyAsync(angle, set.angle, n * 4, hipMemcpyDeviceToHost, q));
+    if (desc && st.described) HIPCHK(ctx, hipMemcpyAsync(desc, set.desc, n * 32, hipMemcpyDeviceToHost, q));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, set.info, kOrbLevelsInfoWords * sizeof(int32_t), hipMemcpyDeviceToHost, q));
+    HIPCHK(ctx, hipStreamSynchronize(q));
+    memset(keypoints + 2 * n, 0, rest * 8);
+    if (octave) memset(octave + n, 0, rest * 4);
+    if (response) memset(response + n, 0, rest * 4);
+    if (angle) memset(angle + (st.described ? n : 0), 0, (st.described ? rest : (size_t)cap) * 4);
+    if (desc) memset(desc + (st.described ? n * 32 : 0), 0, (st.described ? rest : (size_t)cap) * 32);
+    return PAGK_OK;
+}
+
+}  // namespace
+
+void pagk_orb_extractor_default(pagk_orb_extractor *e)
+{
+    if (!e) return;
+    e->n_features = 1000;      // the arguments ORB is normally run with (src/ORBextractor.cc:434-437)
+    e->scale_factor = 1.2f;
+    e->n_levels = 8;           // "int nLevels = 1;    // 8", Examples/Demo/RealSenseD435i.cpp:187
+    e->ini_threshold = 20;
+    e->min_threshold = 7;
+}
+
+int pagk_orb_extractor_check(const pagk_orb_extractor *e) { return orb_extractor_check(e); }
+
+int pagk_orb_extractor_levels(const pagk_orb_extractor *ex, int32_t width, int32_t height, int32_t *level_width,
+                              int32_t *level_height, float *scale, int32_t *quota, int32_t *size, int32_t *out_bound)
+{
+    OrbLevelTable t;
+    if (orb_level_table(ex, width, height, &t)) return PAGK_E_ARG;
+    for (int l = 0; l < kOrbMaxLevels; l++) {
+        const bool in = l < t.L;
+        if (level_width) level_width[l] = in ? t.w[l] : 0;
+        if (level_height) level_height[l] = in ? t.h[l] : 0;
+        if (scale) scale[l] = in ? t.sc[l] : 0.0f;
+        if (quota) quota[l] = in ? t.quota[l] : 0;
+        if (size) size[l] = in ? t.size[l] : 0;
+    }
+    if (out_bound) *out_bound = (int32_t)t.cap;
+    return PAGK_OK;
+}
+
+int pagk_orb_extract_slot(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_orb_params *orb, int32_t slot)
+{
+    if (!ctx || !orb || slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    return orb_levels_slot(ctx, ex, orb, slot, nullptr, "pagk_orb_extract_slot");
+}
+
+int pagk_orb_slot_read(pagk_ctx *ctx, int32_t slot, int32_t cap, float *keypoints, int32_t *octave, float *response,
+                       float *angle, uint8_t *desc, int32_t *info)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_slot_read");
+    return orb_slot_read(ctx, slot, cap, keypoints, octave, response, angle, desc, info);
+}
+
+int pagk_orb_match_slots(pagk_ctx *ctx, const pagk_orb_params *orb, int32_t slot_q, int32_t slot_t)
+{
+    if (!ctx || slot_q < 0 || slot_q >= kUserSlots || slot_t < 0 || slot_t >= kUserSlots) return PAGK_E_ARG;
+    int rc = orb_params_check(orb);
+    if (rc) return rc;
+    pagk_ctx::OrbLevelsSlot &q = ctx->orbl[slot_q];
+    const pagk_ctx::OrbLevelsSlot &t = ctx->orbl[slot_t];
+    if (q.cap < 1 || t.cap < 1 || !q.described || !t.described) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_orb_match_slots: slots %d and %d need a described keypoint set each "
+                 "(pagk_orb_extract_slot)", slot_q, slot_t);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf &mb = ctx->buf[pagk_ctx::ORBL_MATCH + slot_q];
+    const Layout<4> lay = orbl_match_layout((size_t)q.cap);
+    if ((rc = reserve(ctx, mb, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the ORB match result of a slot",
+                      "run the call once with these sets before capturing"))) {
+        if (!mb.ptr) q.match_cap = 0;
+        return rc;
+    }
+    q.match_cap = 0;
+    const OrbSet sq = orbl_set_at(ctx->buf[pagk_ctx::ORBL_SET + slot_q].ptr, (size_t)q.cap);
+    const OrbSet stt = orbl_set_at(ctx->buf[pagk_ctx::ORBL_SET + slot_t].ptr, (size_t)t.cap);
+    rc = pagk_orb_match_device(ctx, orb, q.cap, sq.desc, sq.info, t.cap, stt.desc, stt.info, lay.at<int32_t>(mb.ptr, 0),
+                               lay.at<int32_t>(mb.ptr, 1), lay.at<uint8_t>(mb.ptr, 2), lay.at<int32_t>(mb.ptr, 3));
+    if (!rc) q.match_cap = q.cap;
+    return rc;
+}
+
+int pagk_orb_match_slots_read(pagk_ctx *ctx, int32_t slot_q, int32_t cap, int32_t *train_idx, int32_t *distance, uint8_t *keep,
+                              int32_t *info)
+{
+    if (!ctx || slot_q < 0 || slot_q >= kUserSlots || !train_idx || !distance || !keep) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_match_slots_read");
+    const pagk_ctx::OrbLevelsSlot &q = ctx->orbl[slot_q];
+    if (q.match_cap < 1 || q.match_cap != q.cap || cap < q.match_cap) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_orb_match_slots_read: slot %d has no match result of at most cap = %d rows "
+                 "(pagk_orb_match_slots)", slot_q, cap);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)q.match_cap;
+    const Layout<4> lay = orbl_match_layout(n);
+    void *b = ctx->buf[pagk_ctx::ORBL_MATCH + slot_q].ptr;
+    HIPCHK(ctx, hipMemcpyAsync(train_idx, lay.at<void>(b, 0), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(distance, lay.at<void>(b, 1), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(keep, lay.at<void>(b, 2), n, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, lay.at<void>(b, 3), kOrbInfoWords * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = n; i < (size_t)cap; i++) train_idx[i] = -1, distance[i] = 257, keep[i] = 0;   // as rows at or beyond nq
+    return PAGK_OK;
+}
+
+int pagk_orb_extract_levels(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_orb_params *orb, const pagk_image *img,
+                            int32_t cap, float *keypoints, int32_t *octave, float *response, float *angle, uint8_t *desc,
+                            int32_t *info)
+{
+    if (!ctx || !img || !orb || !keypoints) return PAGK_E_ARG;
+    int rc = orb_params_check(orb);
+    if (rc) return rc;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_extract_levels");
+    OrbLevelTable t;
+    if (check_image(img) || orb_level_table(ex, img->width, img->height, &t) || cap < t.cap) return PAGK_E_ARG;
+    if ((rc = frame_upload_any(ctx, 4, img, 1))) return rc;
+    if ((rc = orb_levels_slot(ctx, ex, orb, 4, nullptr, "pagk_orb_extract_levels"))) return rc;
+    return orb_slot_read(ctx, 4, cap, keypoints, octave, response, angle, desc, info);
+}
+
+int pagk_orb_detect_levels(pagk_ctx *ctx, const pagk_orb_extractor *ex, const pagk_image *img, const uint8_t *mask, int32_t cap,
+                           float *keypoints, int32_t *octave, float *response, int32_t *info)
+{
+    if (!ctx || !img || !keypoints) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_orb_detect_levels");
+    OrbLevelTable t;
+    if (check_image(img) || orb_level_table(ex, img->width, img->height, &t) || cap < t.cap) return PAGK_E_ARG;
+    int rc = frame_upload_any(ctx, 4, img, 1);
+    if (rc) return rc;
+    const size_t px = (size_t)img->width * img->height;
+    const size_t sizes[1] = {px};
+    Staged<1> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, mask, px))) return rc;
+    if ((rc = orb_levels_slot(ctx, ex, nullptr, 4, mask ? s.at<uint8_t>(0) : nullptr, "pagk_orb_detect_levels"))) return rc;
+    if ((rc = orb_slot_read(ctx, 4, cap, keypoints, octave, response, nullptr, nullptr, info))) return rc;
+    return s.finish();
+}
+
+int pagk_selftest_orb_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t *dst, int64_t pitch)
+{
+    if (!ctx || slot < 0 || slot >= kUserSlots || !dst) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_selftest_orb_level");
+    const FrameSlot &s = ctx->slots[slot];
+    const pagk_ctx::OrbLevelsSlot &st = ctx->orbl[slot];
+    if (!fast_slot_ok(s) || st.n_levels < 1 || st.w != s.w || st.h != s.h || level < 0 || level >= st.n_levels ||
+        pitch < st.lw[level])
+        return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const Layout<kOrbMaxLevels> lay = orbl_pyr_layout(st.lw, st.lh, st.n_levels);
+    const uint8_t *src = level ? lay.at<uint8_t>(ctx->buf[pagk_ctx::ORBL_PYR + slot].ptr, level - 1) : s.img0;
+    const size_t spitch = level ? (size_t)orbl_pitch(st.lw[level]) : (size_t)s.pitch0;
+    HIPCHK(ctx, hipMemcpy2DAsync(dst, (size_t)pitch, src, spitch, (size_t)st.lw[level], (size_t)st.lh[level], hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PAGK_OK;
 }
 
 // ---- pyramidal Lucas-Kanade, tracker type 0 (pagk_lk_kernel.h) ---------------------------------------------------
@@ -4203,6 +4648,7 @@ int pagk_selftest_fill_workspaces(pagk_ctx *ctx, uint32_t word, int32_t also_new
     }
     if ((rc = fill_words(ctx, ctx->queue, 256, word))) return rc;
     for (auto &p : ctx->lk_pyr) p.top = -1;
+    for (auto &o : ctx->orbl) o = pagk_ctx::OrbLevelsSlot();
     for (FrameSlot &s : ctx->slots) {
         s.valid = false;
         if ((rc = fill_words(ctx, s.block.ptr, s.block.bytes, word))) return rc;

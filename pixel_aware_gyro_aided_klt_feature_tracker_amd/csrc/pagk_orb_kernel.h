@@ -97,13 +97,15 @@ struct OrbBlurArgs {
     int w0, w1, w2, w3;   // Q8 taps for offsets 0, +-1, +-2, +-3
 };
 
-__global__ __launch_bounds__(256) void k_orb_blur(OrbBlurArgs a)
+// (the bodies of the blur and the describe kernel are functions of their own so that pagk_orb_levels_kernel.h can run them on
+// one of several levels per launch; bx, by / block: the workgroup's place in the level's own grid)
+__device__ __forceinline__ void orb_blur_body(const OrbBlurArgs &a, int bx, int by)
 {
     constexpr int SW = kOrbBlurTx + 6, SH = kOrbBlurTy + 6, SP = 72;
     __shared__ uint8_t src[SH * SP];
     __shared__ __attribute__((aligned(16))) uint32_t hor[SH * kOrbBlurTx];
-    const int tid = threadIdx.x, x0 = blockIdx.x * kOrbBlurTx, y0 = blockIdx.y * kOrbBlurTy;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < kOrbInfoWords) a.info[tid] = 0;
+    const int tid = threadIdx.x, x0 = bx * kOrbBlurTx, y0 = by * kOrbBlurTy;
+    if (bx == 0 && by == 0 && tid < kOrbInfoWords) a.info[tid] = 0;
     for (int i = tid; i < SW * SH; i += 256) {
         const int ry = i / SW, rx = i - ry * SW;
         const int gy = orb_reflect(y0 + ry - 3, a.H), gx = orb_reflect(x0 + rx - 3, a.W);
@@ -131,6 +133,8 @@ __global__ __launch_bounds__(256) void k_orb_blur(OrbBlurArgs a)
         (s0 >> 16) | ((s1 >> 16) << 8) | ((s2 >> 16) << 16) | ((s3 >> 16) << 24);
 }
 
+__global__ __launch_bounds__(256) void k_orb_blur(OrbBlurArgs a) { orb_blur_body(a, blockIdx.x, blockIdx.y); }
+
 // ---- orientation and descriptor -------------------------------------------------------------------------------------
 struct OrbDescArgs {
     const uint8_t *img;       // the unblurred image (orientation)
@@ -145,10 +149,10 @@ struct OrbDescArgs {
     int W, H, wp, cap;
 };
 
-__global__ __launch_bounds__(256) void k_orb_describe(OrbDescArgs a)
+__device__ __forceinline__ void orb_describe_body(const OrbDescArgs &a, int block)
 {
     const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);   // the wave's keypoint
+    const int k = block * 4 + (threadIdx.x >> 6);   // the wave's keypoint
     if (k >= a.cap) return;
     const int n = min(max(*a.n, 0), a.cap);
     uint4 *out = reinterpret_cast<uint4 *>(a.desc + (size_t)k * 32);
@@ -223,6 +227,8 @@ __global__ __launch_bounds__(256) void k_orb_describe(OrbDescArgs a)
         atomicAdd(a.info, 1);
     }
 }
+
+__global__ __launch_bounds__(256) void k_orb_describe(OrbDescArgs a) { orb_describe_body(a, blockIdx.x); }
 
 // ---- matching -------------------------------------------------------------------------------------------------------
 struct OrbMatchArgs {

@@ -297,6 +297,43 @@ def orb_match_pair(img_ref, img_cur, n_features: int, pattern, fast=None, orb=No
     return out
 
 
+# ---- ORB over a scale pyramid (src/ORBextractor.cc:434-470, 789-875, 1066-1232), array in, array out ----
+def orb_extract_levels(img, extractor, pattern, orb=None, ctx=None) -> dict:
+    """ORBextractor::operator() with extractor.n_levels levels (pagk_orb_extract_levels) -> dict(n, keypoints (n x 2
+    float32, original-image coordinates), octave (n), response (n), angle (n), desc (n x 32 uint8), info and its words by
+    name).  `pattern` is the host's sampling table (1024 integers); it is uploaded to the context on every call."""
+    c = _device_context(ctx)
+    c.orb_set_pattern(pattern)
+    return c.orb_extract_levels(np.ascontiguousarray(img, np.uint8), extractor, orb)
+
+
+def orb_detect_levels(img, extractor, mask=None, ctx=None) -> dict:
+    """ORBextractor::DetectFeatures with extractor.n_levels levels (pagk_orb_detect_levels) -> dict(n, keypoints, octave,
+    response, info): the candidate list of the hand-over, in the reference's order."""
+    return _device_context(ctx).orb_detect_levels(np.ascontiguousarray(img, np.uint8), extractor, mask)
+
+
+def orb_match_pair_levels(img_ref, img_cur, extractor, pattern, orb=None, ctx=None) -> dict:
+    """ORBDetectAndDespMatcher::FindFeatureMatches with extractor.n_levels levels, as one chain on the device: both images
+    into frame slots 0 and 1, pagk_orb_extract_slot on each, pagk_orb_match_slots with the reference image as the query ->
+    dict(ref, cur (the two sets), train_idx, distance, keep (nq rows), info and its words by name)."""
+    c = _device_context(ctx)
+    c.orb_set_pattern(pattern)
+    ref_img, cur_img = np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8)
+    c.frame_upload(0, ref_img, 1)
+    c.frame_upload(1, cur_img, 1)
+    c.orb_extract_slot(extractor, 0, orb)
+    c.orb_extract_slot(extractor, 1, orb)
+    c.orb_match_slots(0, 1, orb)
+    cap_r = capi.orb_extractor_levels(extractor, ref_img.shape[1], ref_img.shape[0])["out_bound"]
+    cap_c = capi.orb_extractor_levels(extractor, cur_img.shape[1], cur_img.shape[0])["out_bound"]
+    ref, cur = c.orb_slot_read(0, cap_r), c.orb_slot_read(1, cap_c)
+    out = c.orb_match_slots_read(0, cap_r)
+    nq = ref["n"]
+    out.update(train_idx=out["train_idx"][:nq], distance=out["distance"][:nq], keep=out["keep"][:nq], ref=ref, cur=cur)
+    return out
+
+
 # ---- the two-view pose of a frame pair (src/ORBDetectAndDespMatcher.cpp:84-108), array in, array out ----
 def _focal_and_centre(K):
     """(mfx + mfy) / 2 and (mcx, mcy) of a 3 x 3 camera matrix, as PoseEstimation2d2d passes them (:97, :105)."""
