@@ -134,66 +134,16 @@ struct TrackArgs {
 __device__ __forceinline__ DevLevel pin_level(const DevLevel &src) { return src; }
 
 // ---- bilinear sampler ---------------------------------------------------------------------------
-// One coordinate of PatchMatch::GetPixelValue (src/patch_match.cpp:394-401): clamp, integer
-// part, fraction and its complement.
-struct Coord {
-    int i;      // int(x)
-    float f;    // xx = x - floor(x)
-    float omf;  // 1.0f - xx
-};
-
-template <bool CLAMP>
-__device__ __forceinline__ Coord prep_coord(float x, float fmax, float fmax_m1)
-{
-    if (CLAMP) {
-        // `if (x < 0) x = 0;` -- fmaxf also maps NaN to 0 (defined behaviour of this
-        // implementation; the reference's int(NaN) is undefined).  -0.0 vs +0.0 is
-        // immaterial: both give i = 0, xx = 0.
-        x = fmaxf(x, 0.0f);
-        x = (x >= fmax) ? fmax_m1 : x;  // `if (x >= img.cols) x = img.cols - 1;`
-    }
-    Coord c;
-    c.i = (int)x;  // truncation == floor for x >= 0
-    // xx = x - floor(x) (:400).  For x >= 0 (guaranteed: the clamp, or the interior test) the subtraction
-    // is exact and v_fract_f32 returns exactly that value; its only deviation from x - floor(x) is a
-    // clamp below 1.0 for tiny negative x, which cannot occur here.  One instruction instead of two.
-    c.f = __builtin_amdgcn_fractf(x);
-    c.omf = 1.0f - c.f;
-    return c;
-}
-
-// b*(a*d0 + xx*d1) + yy*(a*d2 + xx*d3), src/patch_match.cpp:402-403, this association.
-__device__ __forceinline__ float bilerp(uint32_t q, const Coord &cx, const Coord &cy)
-{
-    float d0 = (float)(q & 0xffu);
-    float d1 = (float)((q >> 8) & 0xffu);
-    float d2 = (float)((q >> 16) & 0xffu);
-    float d3 = (float)(q >> 24);
-    float top = cx.omf * d0 + cx.f * d1;
-    float bot = cx.omf * d2 + cx.f * d3;
-    return cy.omf * top + cy.f * bot;
-}
-
-// ---- the sampler's two hardware-specific forms -------------------------------------------------------------------
-// Default build: tap loads through a typed buffer resource (the texture addresser converts the four bytes to floats)
-// and the interpolation in packed f32 (the quad's two rows side by side in v_pk_mul_f32 / v_pk_add_f32).  Both are
-// bit-identical to the classic form (byte unpacking with v_cvt_f32_ubyte, scalar f32 arithmetic), which
-// -DPAGK_CLASSIC_SAMPLER builds for A/B runs.  Measured on MI355X (same-session A/B, profiles/r02_ab_runs.md): 53
-// instead of 135 VALU instructions per patch pixel; -1.6 % launch time at 1000 features (the launch is latency-bound
-// there), -5 % at 20000 (four features per wave), -7.5 % at 8000.
-#if !defined(PAGK_CLASSIC_SAMPLER)
-#ifndef PAGK_PK_BILERP
-#define PAGK_PK_BILERP
-#endif
-#ifndef PAGK_TYPED_TAPS
-#define PAGK_TYPED_TAPS
-#endif
-#endif
+// Tap loads go through a typed buffer resource (the texture addresser converts the four bytes to floats) and the
+// interpolation runs in packed f32 (the quad's two rows side by side in v_pk_mul_f32 / v_pk_add_f32).  Both are
+// bit-identical to the classic form (byte unpacking with v_cvt_f32_ubyte, scalar f32 arithmetic), which this one
+// replaced after a same-session A/B on MI355X (profiles/r02_ab_runs.md): 53 instead of 135 VALU instructions per patch
+// pixel; -1.6 % launch time at 1000 features (the launch is latency-bound there), -5 % at 20000 (four features per
+// wave), -7.5 % at 8000.
 typedef float pagk_f32x4 __attribute__((ext_vector_type(4)));
 typedef float pagk_f32x2 __attribute__((ext_vector_type(2)));
 typedef int pagk_i32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef PAGK_TYPED_TAPS
 // The four taps of a quad arrive as four floats: the texture addresser converts them.  A quad dword is read
 // through a buffer resource whose element format is 8_8_8_8 / USCALED (unsigned byte -> float, exact), so
 // `buffer_load_format_xyzw` returns (float)byte0..3 and the 4 x v_cvt_f32_ubyte per sample disappear from the
@@ -221,24 +171,6 @@ __device__ __forceinline__ TapSrc tap_src(const DevLevel &L)
 typedef pagk_f32x4 Taps;   // (d0, d2, d1, d3) as floats
 __device__ __forceinline__ Taps load_taps(const TapSrc &t, int idx) { return pagk_buffer_load_format_xyzw(t.rs, idx, 0, 0, 0); }
 __device__ __forceinline__ pagk_f32x4 taps_f32(Taps q) { return q; }
-#else
-struct TapSrc {
-    const uint32_t *quad;
-};
-__device__ __forceinline__ TapSrc tap_src(const DevLevel &L) { return TapSrc{L.quad}; }
-typedef uint32_t Taps;     // the packed quad dword; converted when consumed
-// unsigned 32-bit element offsets: SGPR base + VGPR offset addressing, no 64-bit pointer math
-__device__ __forceinline__ Taps load_taps(const TapSrc &t, int idx) { return t.quad[(uint32_t)idx]; }
-__device__ __forceinline__ pagk_f32x4 taps_f32(Taps q)
-{
-    pagk_f32x4 d;   // (d0, d2, d1, d3): v_cvt_f32_ubyte0/2/1/3 straight into the two register pairs
-    d.x = (float)(q & 0xffu);
-    d.y = (float)((q >> 16) & 0xffu);
-    d.z = (float)((q >> 8) & 0xffu);
-    d.w = (float)(q >> 24);
-    return d;
-}
-#endif
 
 // b*(a*d0 + xx*d1) + yy*(a*d2 + xx*d3) (:402-403) on the pairs (d0, d2), (d1, d3): the same seven roundings in
 // the same association, the two rows of the quad side by side in v_pk_mul_f32 / v_pk_add_f32 (IEEE per component,
@@ -250,6 +182,8 @@ __device__ __forceinline__ float bilerp_pk(pagk_f32x4 d, pagk_f32x2 cx, pagk_f32
     return t.x + t.y;
 }
 
+// One coordinate of PatchMatch::GetPixelValue (src/patch_match.cpp:394-401): clamp, integer part, fraction and its
+// complement.
 struct CoordPk {
     int i;            // int(x)
     pagk_f32x2 w;     // (1 - xx, xx)
@@ -259,11 +193,16 @@ template <bool CLAMP>
 __device__ __forceinline__ CoordPk prep_coord_pk(float x, float fmax, float fmax_m1)
 {
     if (CLAMP) {
+        // `if (x < 0) x = 0;` -- fmaxf also maps NaN to 0 (defined behaviour of this implementation; the reference's
+        // int(NaN) is undefined).  -0.0 vs +0.0 is immaterial: both give i = 0, xx = 0.
         x = fmaxf(x, 0.0f);
-        x = (x >= fmax) ? fmax_m1 : x;
+        x = (x >= fmax) ? fmax_m1 : x;  // `if (x >= img.cols) x = img.cols - 1;`
     }
     CoordPk c;
-    c.i = (int)x;
+    c.i = (int)x;  // truncation == floor for x >= 0
+    // xx = x - floor(x) (:400).  For x >= 0 (guaranteed: the clamp, or the interior test) the subtraction is exact and
+    // v_fract_f32 returns exactly that value; its only deviation from x - floor(x) is a clamp below 1.0 for tiny
+    // negative x, which cannot occur here.  One instruction instead of two.
     const float f = __builtin_amdgcn_fractf(x);
     c.w.y = f;
     c.w.x = 1.0f - f;
@@ -273,15 +212,9 @@ __device__ __forceinline__ CoordPk prep_coord_pk(float x, float fmax, float fmax
 template <bool CLAMP>
 __device__ __forceinline__ float sample(const DevLevel &L, float x, float y)
 {
-#ifdef PAGK_PK_BILERP
     const CoordPk cx = prep_coord_pk<CLAMP>(x, L.fcols, L.fcols_m1);
     const CoordPk cy = prep_coord_pk<CLAMP>(y, L.frows, L.frows_m1);
     return bilerp_pk(taps_f32(load_taps(tap_src(L), __mul24(cy.i, L.cols) + cx.i)), cx.w, cy.w);
-#else
-    Coord cx = prep_coord<CLAMP>(x, L.fcols, L.fcols_m1);
-    Coord cy = prep_coord<CLAMP>(y, L.frows, L.frows_m1);
-    return bilerp(L.quad[(uint32_t)(__mul24(cy.i, L.cols) + cx.i)], cx, cy);
-#endif
 }
 
 // One sample in two halves (tap load requested / interpolated), so that a batch of independent samples has all its
@@ -293,33 +226,19 @@ struct OneTap {
 template <bool CLAMP>
 __device__ __forceinline__ OneTap sample_issue(const DevLevel &L, float x, float y)
 {
-#ifdef PAGK_PK_BILERP
     const CoordPk cx = prep_coord_pk<CLAMP>(x, L.fcols, L.fcols_m1);
     const CoordPk cy = prep_coord_pk<CLAMP>(y, L.frows, L.frows_m1);
     OneTap t;
     t.q = load_taps(tap_src(L), __mul24(cy.i, L.cols) + cx.i);
     t.fx = cx.w.y, t.fy = cy.w.y;
     return t;
-#else
-    const Coord cx = prep_coord<CLAMP>(x, L.fcols, L.fcols_m1);
-    const Coord cy = prep_coord<CLAMP>(y, L.frows, L.frows_m1);
-    OneTap t;
-    t.q = L.quad[(uint32_t)(__mul24(cy.i, L.cols) + cx.i)];
-    t.fx = cx.f, t.fy = cy.f;
-    return t;
-#endif
 }
 __device__ __forceinline__ float sample_finish(const OneTap &t)
 {
-#ifdef PAGK_PK_BILERP
     pagk_f32x2 wx, wy;
     wx.x = 1.0f - t.fx, wx.y = t.fx;
     wy.x = 1.0f - t.fy, wy.y = t.fy;
     return bilerp_pk(taps_f32(t.q), wx, wy);
-#else
-    const Coord cx{0, t.fx, 1.0f - t.fx}, cy{0, t.fy, 1.0f - t.fy};
-    return bilerp(t.q, cx, cy);
-#endif
 }
 
 // The five img2 samples one pixel of the GN loop needs (src/patch_match.cpp:252,259-262):
@@ -352,7 +271,6 @@ struct Five {
 // contracted into an fma, whose single rounding the bound on |wx| does not cover.
 // pagk_selftest_sample refuses a clamp-free call outside [1, cols - 2) x [1, rows - 2).
 // The clamped form prepares all six coordinates: its clamp acts on X - 1 itself.
-#ifdef PAGK_PK_BILERP
 // five tap loads in flight and the six fractions; the (1 - xx, xx) pairs are formed at use.  In the clamp-free form
 // fxm, fym are fx, fy themselves: no register of their own, and sample5_finish forms four weight pairs, not six
 struct FiveTaps {
@@ -411,59 +329,6 @@ __device__ __forceinline__ Five sample5_finish(const FiveTaps &t)
     r.ym = bilerp_pk(taps_f32(t.q4), cx, cym);
     return r;
 }
-#else
-// five packed quads and the six fractions: 11 registers between issue and use (1 - xx is recomputed at use: the
-// same single rounding)
-struct FiveTaps {
-    uint32_t q0, q1, q2, q3, q4;
-    float fx, fxp, fxm, fy, fyp, fym;
-};
-template <bool CLAMP>
-__device__ __forceinline__ FiveTaps sample5_issue(const DevLevel &L, float X, float Y)
-{
-    const Coord cx = prep_coord<CLAMP>(X, L.fcols, L.fcols_m1);
-    const Coord cxp = prep_coord<CLAMP>(X + 1.0f, L.fcols, L.fcols_m1);
-    const Coord cy = prep_coord<CLAMP>(Y, L.frows, L.frows_m1);
-    const Coord cyp = prep_coord<CLAMP>(Y + 1.0f, L.frows, L.frows_m1);
-    const int rc = __mul24(cy.i, L.cols), rp = __mul24(cyp.i, L.cols);
-    const int ic = rc + cx.i;
-    int im, iu;  // the quads of (X - 1, Y) and (X, Y - 1)
-    FiveTaps t;
-    if constexpr (CLAMP) {
-        const Coord cxm = prep_coord<true>(X - 1.0f, L.fcols, L.fcols_m1);
-        const Coord cym = prep_coord<true>(Y - 1.0f, L.frows, L.frows_m1);
-        im = rc + cxm.i;
-        iu = __mul24(cym.i, L.cols) + cx.i;
-        t.fxm = cxm.f, t.fym = cym.f;
-    } else {
-        // X, Y >= 1: the centre's left and upper neighbours, with the centre's fractions (above)
-        im = ic - 1;
-        iu = ic - L.cols;
-        t.fxm = cx.f, t.fym = cy.f;
-    }
-    const uint32_t *q = L.quad;
-    // unsigned 32-bit element offsets: SGPR base + VGPR offset addressing, no 64-bit pointer math
-    t.q0 = q[(uint32_t)ic];
-    t.q1 = q[(uint32_t)(rc + cxp.i)];
-    t.q2 = q[(uint32_t)im];
-    t.q3 = q[(uint32_t)(rp + cx.i)];
-    t.q4 = q[(uint32_t)iu];
-    t.fx = cx.f, t.fxp = cxp.f, t.fy = cy.f, t.fyp = cyp.f;
-    return t;
-}
-__device__ __forceinline__ Five sample5_finish(const FiveTaps &t)
-{
-    const Coord cx{0, t.fx, 1.0f - t.fx}, cxp{0, t.fxp, 1.0f - t.fxp}, cxm{0, t.fxm, 1.0f - t.fxm};
-    const Coord cy{0, t.fy, 1.0f - t.fy}, cyp{0, t.fyp, 1.0f - t.fyp}, cym{0, t.fym, 1.0f - t.fym};
-    Five r;
-    r.c = bilerp(t.q0, cx, cy);
-    r.xp = bilerp(t.q1, cxp, cy);
-    r.xm = bilerp(t.q2, cxm, cy);
-    r.yp = bilerp(t.q3, cx, cyp);
-    r.ym = bilerp(t.q4, cx, cym);
-    return r;
-}
-#endif
 
 template <bool CLAMP>
 __device__ __forceinline__ Five sample5(const DevLevel &L, float X, float Y)
@@ -813,9 +678,6 @@ __device__ __forceinline__ double row_bcast(double v)
     return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + K, 0xf, 0xf, false);  // row_newbcast:K
 }
 
-#ifdef PAGK_COUNT_REDO
-static __device__ uint32_t g_redo_lo, g_redo_hi;   // (diagnostic build: racy by design, last writer wins)
-#endif
 // ROWB: the lane-to-lane results travel by row_bcast (one DPP instruction, the value stays in a vector register) instead
 // of lane_bcast (two v_readlane, the value in scalar registers): fewer instructions, ~20 more live VGPRs -- for kernels
 // that have them (the pipelined 4-wave kernel; the others sit at their register limit and would spill).
@@ -922,12 +784,7 @@ __device__ __forceinline__ double llt4_solve_nsq_lanes(const double (&M)[4][4], 
 {
     OperandRange rg;
     double nsq = llt4_solve_nsq_lanes_form<true, ROWB>(M, b, l, x, sv, rg, late, p3);
-#ifndef PAGK_EXPERIMENT_NO_REDO
     if (__builtin_amdgcn_ballot_w64(!rg.in_range() && l < 4) != 0) nsq = llt4_solve_nsq_lanes_form<false, ROWB>(M, b, l, x, sv, rg);
-#endif
-#ifdef PAGK_COUNT_REDO
-    g_redo_lo = rg.t;
-#endif
     return nsq;
 }
 

@@ -1061,7 +1061,7 @@ int launch_track(pagk_ctx *ctx, const pagk_params *p, const FrameSlot &sr, const
     a.dist_pred = o->dist_pred;
     a.ncc = o->ncc;
     a.iters = o->iters;
-#if defined(PAGK_STAMPS) || defined(PAGK_COUNT_REDO) || defined(PAGK_TIC)
+#if defined(PAGK_STAMPS) || defined(PAGK_TIC)
     a.dbg = reinterpret_cast<unsigned long long *>(getenv("PAGK_DBG_PTR") ? strtoull(getenv("PAGK_DBG_PTR"), nullptr, 0) : 0ull);
 #endif
     fill_param_args(a, p);
@@ -3270,7 +3270,8 @@ int orb_level_table(const pagk_orb_extractor *e, int W, int H, OrbLevelTable *t)
 int orbl_pitch(int w) { return (w + 3) & ~3; }
 
 // where the levels 1 .. L - 1 lie in buf[ORBL_PYR + slot] (part l - 1 is level l, rows of orbl_pitch(w[l]) bytes)
-Layout<kOrbMaxLevels> orbl_pyr_layout(const int *lw, const int *lh, int L)
+// (extern "C++": a class template cannot be returned with the C linkage of the block around these helpers)
+extern "C++" Layout<kOrbMaxLevels> orbl_pyr_layout(const int *lw, const int *lh, int L)
 {
     size_t sizes[kOrbMaxLevels] = {};
     for (int l = 1; l < L; l++) sizes[l - 1] = (size_t)orbl_pitch(lw[l]) * lh[l];
@@ -3283,7 +3284,7 @@ struct OrbSet {
     int32_t *octave, *info;
     uint8_t *desc;
 };
-Layout<6> orbl_set_layout(size_t cap)
+extern "C++" Layout<6> orbl_set_layout(size_t cap)
 {
     const size_t sizes[6] = {cap * 8, cap * 4, cap * 4, cap * 4, cap * 32, kOrbLevelsInfoWords * sizeof(int32_t)};
     return Layout<6>(sizes);
@@ -3296,7 +3297,7 @@ OrbSet orbl_set_at(void *b, size_t cap)
 }
 
 // the match result of a query slot: train_idx | distance | keep | info
-Layout<4> orbl_match_layout(size_t cap)
+extern "C++" Layout<4> orbl_match_layout(size_t cap)
 {
     const size_t sizes[4] = {cap * 4, cap * 4, cap, kOrbInfoWords * sizeof(int32_t)};
     return Layout<4>(sizes);
@@ -3656,7 +3657,7 @@ int lk_levels(int w, int h, const pagk_lk_params *p, int *lw, int *lh)
 }
 
 // where the levels 1 .. top lie in buf[LK_PYR + slot] (part l - 1 is level l, rows of lw[l] bytes)
-Layout<kLkMaxLevels> lk_layout(const int *lw, const int *lh, int top)
+extern "C++" Layout<kLkMaxLevels> lk_layout(const int *lw, const int *lh, int top)
 {
     size_t sizes[kLkMaxLevels] = {};
     for (int l = 1; l <= top; l++) sizes[l - 1] = (size_t)lw[l] * lh[l];

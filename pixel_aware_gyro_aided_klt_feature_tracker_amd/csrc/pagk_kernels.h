@@ -551,9 +551,6 @@ __host__ __device__ inline size_t track_block_lds_bytes(int half)
     size_t PP = (size_t)track_block_pp(half);
     size_t bytes = kStreams * (PP + 1) * 8 + PP * 4 + 2 * 8 + 16 * 8 + 5 * 8 + 2 * 4 + 8;  // streams PP + 1 doubles apart
     bytes += 16 + 16 + 8;  // the pipelined body (pagk_pipe_kernel.h): int flags[4], double h22[2], double pen
-#ifdef PAGK_EXPERIMENT_LDS_WINDOW
-    bytes += 32 * 32 * 4;  // the staged img2 window (experiment build only, see track_block_body)
-#endif
     return bytes;
 }
 // MFMA variant: three f64 streams of PP + 8 (the +8 staggers the banks of neighbouring arrays),
@@ -647,14 +644,11 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
     // two-round patches: (NR, TAIL) determine the patch size (h = 8, 9, 10 <-> P mod 32 = 1, 9, 25), so every LDS
     // address below is a compile-time constant (immediate offsets instead of address registers)
     constexpr int HC = (NR == 2 && !MFMA) ? (TAIL == 1 ? 8 : (TAIL == 9 ? 9 : 10)) : 0;
-#ifndef PAGK_NO_PIPE
-    // ... and their iteration is the pipelined one (pagk_pipe_kernel.h; -DPAGK_NO_PIPE builds the serial phases below
-    // for A/B runs: the same bits)
+    // ... and their iteration is the pipelined one (pagk_pipe_kernel.h); the serial phases below compute the same bits
     if constexpr (HC != 0 && !RELAXED && PIPE) {
         track_pipe_body<HC, LEAN>(a, i, resume);
         return;
     }
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -673,9 +667,6 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
     double *acc = cslot + 2;
     double *sh_upd = acc + kAcc;
     float *sh_cost = reinterpret_cast<float *>(sh_upd + 5);
-#ifdef PAGK_EXPERIMENT_LDS_WINDOW
-    uint32_t *win = reinterpret_cast<uint32_t *>(sh_cost + 2);  // 32 x 32 quads of img2 around the patch (experiment)
-#endif
 
     const float *init = a.has_gyro ? a.pt_init : a.pt_ref;  // :85-89
     float p2x = init[2 * i], p2y = init[2 * i + 1];
@@ -933,48 +924,6 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
                 }
             }
             };
-#ifdef PAGK_EXPERIMENT_LDS_WINDOW
-            // EXPERIMENT (never the product; BASELINE.json's north_star prescribes "pyramid levels staged into LDS tiles"):
-            // the 32 x 32 quads of img2 that contain every tap of this iteration are staged in LDS with coalesced row
-            // loads, and the five samples per pixel read their quad with ds_read_b32 and unpack the bytes (the typed
-            // buffer load's free conversion is not available for LDS).  Same arithmetic, same bits; measured against
-            // the product's gathers in profiles/r03_lds_window_experiment.log.
-            bool staged = false;
-            if constexpr (NR == 2 && !MFMA) {
-                if (interior && ext_x <= 14.0f && ext_y <= 14.0f) {   // (block-uniform)
-                    const int ox = (int)(bx - ext_x), oy = (int)(by - ext_y);
-                    for (int k = tid; k < 32 * 32; k += kBlock) {
-                        const int r = oy + (k >> 5), c = ox + (k & 31);
-                        win[k] = (r < L2.rows && c < L2.cols) ? L2.quad[(uint32_t)(__mul24(r, L2.cols) + c)] : 0u;
-                    }
-                    __syncthreads();
-                    auto tap = [&](float X, float Y) {
-                        const Coord cx = prep_coord<false>(X, L2.fcols, L2.fcols_m1), cy = prep_coord<false>(Y, L2.frows, L2.frows_m1);
-                        return bilerp(win[((cy.i - oy) << 5) + (cx.i - ox)], cx, cy);
-                    };
-#pragma unroll
-                    for (int r = 0; r < NR; r++) {
-                        const float X = bx + wx[r], Y = by + wy[r];
-                        Five sv;
-                        sv.c = tap(X, Y), sv.xp = tap(X + 1.0f, Y), sv.xm = tap(X - 1.0f, Y);
-                        sv.yp = tap(X, Y + 1.0f), sv.ym = tap(X, Y - 1.0f);
-                        const int p = tid + kBlock * r;
-                        if (p < P) {
-                            float e = sv.c + db - gain * s1[r];
-                            float Ix = 0.5f * (sv.xp - sv.xm), Iy = 0.5f * (sv.yp - sv.ym);
-                            double dIx = (double)Ix, dIy = (double)Iy, de = (double)e;
-                            stream[0 * PS + p] = dIx * dIx, stream[1 * PS + p] = dIy * dIx, stream[2 * PS + p] = dIy * dIy;
-                            stream[3 * PS + p] = dIx * de, stream[4 * PS + p] = dIy * de;
-                            stream[5 * PS + p] = dIx, stream[6 * PS + p] = dIy, stream[7 * PS + p] = de;
-                            esq[p] = e * e;
-                        }
-                    }
-                    staged = true;
-                }
-            }
-            if (staged) {
-            } else
-#endif
             using AllRounds = std::integral_constant<int, NR>;
             if constexpr (MFMA) {
                 sampling(std::integral_constant<int, 2>{}, AllRounds{});
@@ -1127,24 +1076,6 @@ __device__ __forceinline__ void track_block_body(const TrackArgs &a, const int i
                     unorm = llt4_solve_nsq_lanes(H, b, tid, upd, LEAN ? 0u : a.solver);
                 else
                     unorm = llt4_solve_nsq_lanes(H, b, tid, upd, LEAN ? 0u : a.solver, SolveNoLate{}, pivot3);
-#ifdef PAGK_COUNT_REDO
-                if (a.dbg) {
-                    OperandRange rg;
-                    double xx[4];
-                    llt4_solve_nsq_lanes_form<true>(H, b, tid, xx, a.solver, rg);
-                    if (tid == 0) {
-                        atomicAdd(a.dbg, 1ull);
-                        if (!rg.in_range()) {
-                            atomicAdd(a.dbg + 1, 1ull);
-                            a.dbg[4] = rg.t;
-                            for (int r = 0; r < 4; r++) {
-                                for (int c = 0; c <= r; c++) a.dbg[8 + r * 4 + c] = __double_as_longlong(H[r][c]);
-                                a.dbg[24 + r] = __double_as_longlong(b[r]);
-                            }
-                        }
-                    }
-                }
-#endif
                 if (tid == 0) {
                     sh_upd[0] = upd[0];
                     sh_upd[1] = upd[1];

@@ -12,12 +12,7 @@
 // 500: 75.4 -> 72.1, configs[2] 2000 x 4 levels 208 -> 199.5, 250 (nothing to outrank) 69.5 -> 69.9.
 // A body states with `constexpr bool kPrioByWork` whether the rule applies to it: not for one-round patches (h <= 7: five
 // workgroups of 96 VGPRs per CU, short iterations -- 0..+1.7 % there).
-// -DPAGK_PRIO_MODE=0 is the by-phase rule alone (rounds 1-4: chains 3, sampling 2, cost 1).
 #pragma once
-
-#ifndef PAGK_PRIO_MODE
-#define PAGK_PRIO_MODE 1
-#endif
 
 namespace pagk {
 // PAGK_PRIO_K=auto (TrackArgs::prio_stats / prio_kbuf non-null): K = the mean number of iterations per feature and level that this
@@ -71,16 +66,6 @@ __device__ __forceinline__ int dispatch_feature(const TrackArgs &a)
     return a.order ? __builtin_amdgcn_readfirstlane(a.order[b]) : b;
 }
 }  // namespace pagk
-#if PAGK_PRIO_MODE == 0
-#define PAGK_PRIO_DECL(hinted)
-#define PAGK_PRIO_TIER
-#define PAGK_PRIO_RESET
-#define PRIO(n) __builtin_amdgcn_s_setprio(n);
-#define PAGK_PRIO_N_CHAIN 3
-#define PAGK_PRIO_N_SAMP 2
-#define PAGK_PRIO_N_COST 1
-#define PAGK_PRIO_N_REST 0
-#else
 // (one PLAIN load -- the L2 serves a thousand workgroups; an agent-scope load of one line from all of them queues for 60 us -- beside the prologue's other loads -- the feature's points and affine -- and a scalar from then on: a vector register held
 // through the body costs the generic instantiations a spill)
 // The hint (TrackArgs::prio_hint_in, above): `hinted` says whether this body reads one -- a finisher does not.  The same
@@ -124,4 +109,3 @@ __device__ __forceinline__ int dispatch_feature(const TrackArgs &a)
 #define PAGK_PRIO_N_SAMP 1
 #define PAGK_PRIO_N_COST 1
 #define PAGK_PRIO_N_REST 0
-#endif

@@ -245,10 +245,6 @@ __global__ void __launch_bounds__(64, 4) k_track_quad(TrackArgs a)
             // address-dependent on the entry and a wave's loads return in order -- that dependency is the consumer's
             // ordering; do not index the state by the ticket)
             quad = __builtin_amdgcn_readfirstlane(e) - 1;
-#ifdef PAGK_EXPERIMENT_ACQUIRE_ONCE
-            // A/B build: ONE agent-scope acquire per wave, behind the look that found the entry -- not one per look
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
         }
     }
     // LEVELS: this wave's quad is through with its level -- the next level's consumers may have it
@@ -459,12 +455,8 @@ __global__ void __launch_bounds__(64, 4) k_track_quad(TrackArgs a)
                 const bool valid = 64 * c + lane < P;
                 auto issue = [&](int f, FiveTaps &tp, float &s1v) {
                     const int src = 16 * f;
-#ifndef PAGK_EXPERIMENT_RECOMPUTE_I1
                     // the feature's img1 sample of this pixel first: loads return in order, so it is there when the taps are
                     s1v = ws[(f * NCH + c) * 64];
-#else
-                    s1v = sample<true>(L1, rl(ptx, src) + x, rl(pty, src) + y);
-#endif
                     float wx = x, wy = y;
                     if (a.use_affine) {  // :203-204
                         wx = rl(A00, src) * x + rl(A01, src) * y;

@@ -1,6 +1,6 @@
 """Diagnostic: the slowest features of a launch of the pipelined 4-wave kernel -- when their workgroup started, when it ended, cycles
 per iteration -- and the launch's ramp (when the last workgroup started).  Separate -DPAGK_STAMPS build (inflates every phase; never
-quote its run time).  Usage: PAGK_N=1000 [PAGK_STAMPS_FLAGS="-DPAGK_PRIO_MODE=0"] python tools/stamps_stragglers.py
+quote its run time).  Usage: PAGK_N=1000 [PAGK_PRIO_K=0] [PAGK_STAMPS_FLAGS="-D..."] python tools/stamps_stragglers.py
 PAGK_STAMPS_RESIDENT=1: the features stay on the device (runtime.ResidentTracker), so the third launch reads the hints the second one left
 (csrc/pagk_prio.h; PAGK_PRIO_HINT=0 for the same launches without) -- the host-buffer call clears them."""
 import os, sys, subprocess
