@@ -1002,7 +1002,30 @@ int pagk_selftest_orb_level(pagk_ctx *ctx, int32_t slot, int32_t level, uint8_t 
  *   filter     (:371-375) kept = status_raw && !(err >= err_threshold); flow = pt_out - pt_ref.
  * Info, PAGK_LK_INFO_WORDS int32: [0] n, [1] features with raw status 1, [2] kept, [3] the effective top level, [4] lost to
  * the min-eigenvalue test at level 0, [5] lost out of range at level 0, the rest 0.
- * Not provided: OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, images with more than one channel. */
+ * Not provided: OPTFLOW_LK_GET_MIN_EIGENVALS, images with more than one channel.  OPTFLOW_USE_INITIAL_FLOW is provided by
+ * pagk_lk_track_flow (the addendum below); pagk_lk_track_device and pagk_lk_track are flags = 0.
+ *
+ * Addendum: the flow form (pagk_lk_track_flow; kernel k_lk_flow, restated in plain C in tests/lk_flow_ref.c).  The reference
+ * carries the flag as its own open experiment ("TODO: test OPTFLOW_USE_INITIAL_FLOW", "int flags = 0;
+ * //cv::OPTFLOW_USE_INITIAL_FLOW;", src/gyro_aided_tracker.cpp:364-365).  Everything above holds; the changes are:
+ *   1 start    at the top level next = pt_init 2^-L, the same exact f32 scaling as prev, in place of next = prev (OpenCV 3.4's
+ *              OPTFLOW_USE_INITIAL_FLOW branch).  prev, the template, the tests, the iteration and the error are unchanged;
+ *              flow = pt_out - pt_ref.  pt_init may be non-finite or far outside the image: the range rule of step 6 decides.
+ *   status_in  the library's own rule: a row k below the count with status_in[k] == 0 is not tracked and is written like a row
+ *              at or beyond the count: point, distorted point, err and flow 0, status and raw status 0.  It is counted in info
+ *              [6] and in none of [1], [2], [4], [5]; [0] stays the count.  With the flag OpenCV would track such a row from
+ *              whatever nextPts holds, which after GyroPredictFeatures is (0, 0) for a prediction that left the image
+ *              (src/gyro_aided_tracker.cpp:131-139): a search started in the image's corner, which this rule leaves out.
+ *   distorted  pt_out_dist = DistortVecPoints(pt_out) (src/utils.cpp:49-76; mvPtPredict = DistortVecPoints(mvPtPredictUn),
+ *              src/gyro_aided_tracker.cpp:379) with the camera of a pagk_params: x = (u - cx) (float)(1.0 / fx), y likewise,
+ *              r2 = x x + y y, r4 = r2 r2, r6 = r4 r2, xd = x (1 + k1 r2 + k2 r4 + k3 r6) + 2 p1 x y + p2 (r2 + 2 x x),
+ *              yd = y (1 + k1 r2 + k2 r4 + k3 r6) + p1 (r2 + 2 y y) + 2 p2 x y, out = (fx xd + cx, fy yd + cy): f32, left to
+ *              right, one rounding per operation, no contraction.  With dist_coef[0] == 0 it is a copy, as in the PatchMatch
+ *              epilogue and the frame hand-over.  It is written for every tracked row whatever its status (:379 distorts all
+ *              of them); zeroed rows get (0, 0).
+ *   identity   with pt_init bit-equal to pt_ref (or NULL) and every status_in set (or NULL), every output equals
+ *              pagk_lk_track's byte for byte.
+ * Info word [6]: rows below the count that status_in switched off (0 from pagk_lk_track_device and pagk_lk_track). */
 typedef struct pagk_lk_params {
     int32_t half_patch;        /* mHalfPatchSize: 10; winSize = 2 half_patch + 1 (:361) */
     int32_t max_level;         /* maxLevel 2 (:362) */
@@ -1044,6 +1067,17 @@ int pagk_lk_track_device(pagk_ctx *ctx, const pagk_lk_params *params, int32_t sl
 int pagk_lk_track(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_image *ref, const pagk_image *cur, int32_t n,
                   const float *pt_ref, float *pt_out, uint8_t *status, uint8_t *status_raw, float *err, float *flow,
                   int32_t *info);
+/* The flow form of the addendum above with host buffers, synchronous (src/gyro_aided_tracker.cpp:353-380 with the flag of
+ * :364-365 and the distortion of :379): both images are uploaded and their pyramids built.  cam (or NULL: no pt_out_dist)
+ * must pass pagk_params_check; only its camera model is read.  pt_ref, pt_out n x 2 floats; pt_init n x 2 floats or NULL for
+ * pt_ref; status_in n bytes or NULL for all 1; pt_out_dist (or NULL) n x 2 floats; status n bytes; status_raw (or NULL) n
+ * bytes; err n floats; flow (or NULL) n x 2 floats; info (or NULL) PAGK_LK_INFO_WORDS words.  0 <= n <= PAGK_LK_MAX_ROWS.  Not
+ * between pagk_graph_begin and pagk_graph_end. */
+int pagk_lk_track_flow(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam /* or NULL: no pt_out_dist */,
+                       const pagk_image *ref, const pagk_image *cur, int32_t n, const float *pt_ref,
+                       const float *pt_init /* or NULL: pt_ref */, const uint8_t *status_in /* or NULL: all 1 */,
+                       float *pt_out, float *pt_out_dist /* or NULL */, uint8_t *status, uint8_t *status_raw /* or NULL */,
+                       float *err, float *flow /* or NULL */, int32_t *info /* or NULL */);
 /* Diagnostic, never on the tracking path: level `level` (1 .. the top level built) of the pyramid that
  * pagk_lk_pyramid_device built for `slot` (the pyrDown levels behind src/gyro_aided_tracker.cpp:353-380), into dst with
  * rows of `pitch` bytes.  Host pointer, synchronous, not between pagk_graph_begin and pagk_graph_end. */
@@ -1082,7 +1116,8 @@ int pagk_selftest_sample(pagk_ctx *ctx, int32_t slot, int32_t level, int32_t mod
  * context's queued work first): every workspace and staging buffer the library has allocated for this context so far, the
  * row queue, the Lucas-Kanade pyramids of all slots and the blocks of all frame slots.  Afterwards NO frame slot is valid
  * and no slot has a Lucas-Kanade pyramid: the caller uploads its frames (and calls pagk_lk_pyramid_device) again before the
- * next call that reads them, and pagk_last_handover returns 0 until the next launch.  Left as they are: what has set / reset
+ * next call that reads them, and pagk_last_handover returns 0 until the next launch.  A sequence of the context
+ * (pagk_sequence_create) is invalid until the next pagk_sequence_start, as frame slots are.  Left as they are: what has set / reset
  * calls of its own (the maps of pagk_rectify_set_maps, the pattern of pagk_orb_set_pattern, the priority hints and the
  * dispatch order) and the descriptors of the batched launches.
  * also_new != 0: from now on every block the library allocates for this context is filled with `word` before its first
@@ -1532,6 +1567,94 @@ int pagk_multi_allgather(pagk_multi *pm, const void *const *d_send, void *const 
 int pagk_track_sharded(pagk_multi *pm, const pagk_params *params, const pagk_image *ref, const pagk_image *cur,
                        int32_t n, const float *pt_ref_un, const float *pt_init_un, const float *affine,
                        const uint8_t *status_in, const pagk_outputs *out);
+
+/* ---- The sequence the context owns: the frame loop behind the C ABI --------------------------------------------------- */
+/* The reference's main loop (Examples/Demo/RealSenseD435i.cpp:199-321: grab a frame and the gyro rotation, track, hand the
+ * result over to the next pair) with everything between two frames on the device and every buffer owned by the context:
+ * the caller hands in host frames and nine rotation floats and reads host arrays back.  One sequence per context.  The
+ * tracker is PatchMatch behind the gyro prediction (tracker type 4, src/gyro_aided_tracker.cpp:381-392), pyramidal
+ * Lucas-Kanade (type 0, :353-380), or Lucas-Kanade started from the gyro prediction (the flow form of the section
+ * "Pyramidal Lucas-Kanade", the reference's open experiment at :364-365).
+ * A step enqueues on the context stream, in the reference's order (the copy of the inputs into the fixed input block of the
+ * sequence stands in front of it, outside the graph):
+ *   PatchMatch  frame -> pyramid (pagk_frame_set_device); pagk_gyro_predict_device_live when has_gyro_predict_initial;
+ *               pagk_track_device; pagk_post_filter_device (Step 3, :289-341); pagk_geometry_validation_device when
+ *               `validate`; the hand-over of the chosen detector (:97-111, src/frame.cpp:115-218).
+ *   LK          frame -> pyramid -> pagk_lk_pyramid_device (the other slot's was built one frame earlier); with
+ *               lk_initial_flow pagk_gyro_predict_device_live, whose pt_predict_un becomes pt_init and whose status becomes
+ *               status_in; the flow kernel with the live count on the device (its status_in is the live mask otherwise);
+ *               pagk_geometry_validation_device on Lucas-Kanade's status when `validate`; the hand-over.  There is no
+ *               Step-3 post-filter: it belongs to GyroPredictFeaturesAndOpticalFlowRefined, which type 0 does not enter.
+ * With PAGK_SEQ_GRAPH the first step of each parity runs directly (allocations happen outside a capture), the next one of
+ * that parity is captured, and later steps replay one of the two graphs; the context stream must then not be the legacy
+ * default stream (pagk_graph_begin).  Every sequence call returns PAGK_E_ARG between pagk_graph_begin and pagk_graph_end.
+ * After pagk_selftest_fill_workspaces a sequence is invalid until the next pagk_sequence_start, as frame slots are.
+ * Out of scope: raw-frame rectification inside the sequence, k cameras batched, sharding, tracker type GYRO_PREDICT, the
+ * C++ shell classes, mvFlowVelocityInNormalPlane. */
+#define PAGK_SEQ_PATCHMATCH 0
+#define PAGK_SEQ_LK 1
+#define PAGK_SEQ_GRAPH 0
+#define PAGK_SEQ_DIRECT 1
+#define PAGK_SEQ_STATUS_WORDS 4
+typedef struct pagk_sequence_params {
+    pagk_params track;           /* the PatchMatch configuration and the camera model (both trackers read the camera) */
+    pagk_lk_params lk;           /* PAGK_SEQ_LK: the constants of src/gyro_aided_tracker.cpp:353-380 */
+    pagk_fit_params fit;         /* the fits of the geometry validation (:429-480), read when `validate` */
+    pagk_detect_params harris;   /* detector 1: src/frame.cpp:181-184 */
+    pagk_fast_params fast;       /* detector 2: src/ORBextractor.cc:1148-1205 */
+    double new_point_threshold;  /* mThresholdOfPredictNewKeyPoint = mN * th (src/frame.cpp:79) */
+    int32_t tracker;             /* PAGK_SEQ_PATCHMATCH or PAGK_SEQ_LK */
+    int32_t lk_initial_flow;     /* PAGK_SEQ_LK: 0 = flags 0, 1 = started from the gyro prediction */
+    int32_t width, height;       /* of every frame */
+    int32_t cap;                 /* rows of every key array; >= target_n */
+    int32_t target_n;            /* Frame::mN */
+    int32_t detector;            /* 0 the caller's candidate list, 1 Harris (goodFeaturesToTrack), 2 FAST cells and quadtree */
+    int32_t cand_cap;            /* detector 0: the longest candidate list, >= 1 */
+    int32_t validate;            /* 0 or 1: GeometryValidation behind the tracker */
+    float sigma;                 /* its sigma (1.0 in the reference) */
+} pagk_sequence_params;
+/* The reference's demo configuration (Examples/Demo/RealSenseD435i.cpp:199-321): pagk_params_default, pagk_lk_params_default,
+ * pagk_fit_params_default, both detectors' defaults, PatchMatch, 640 x 480, cap 448, target_n 400, threshold 320, the
+ * caller's candidate list (cand_cap 1024), validation on, sigma 1. */
+void pagk_sequence_params_default(pagk_sequence_params *p);
+/* PAGK_OK if pagk_sequence_create accepts *p (Examples/Demo/RealSenseD435i.cpp:199-321): each nested block passes its own
+ * check; tracker, lk_initial_flow, validate in {0, 1}; detector in {0, 1, 2}; width, height >= 14; cap >= target_n >= 1,
+ * cap <= PAGK_LK_MAX_ROWS; cand_cap >= 1 for detector 0; new_point_threshold and sigma finite, sigma > 0; for PAGK_SEQ_LK
+ * a frame larger than the window (pagk_lk_levels).  PAGK_E_ARG (or the nested check's code) otherwise.  Needs no device. */
+int pagk_sequence_params_check(const pagk_sequence_params *p);
+/* The sequence of this context (Examples/Demo/RealSenseD435i.cpp:199-321, the objects the loop keeps between frames):
+ * reserves two key sets, the work arrays, the state and info words and the fixed input block in one buffer of the
+ * context, and a ring of four pinned input blocks.  PAGK_E_ARG for a second sequence, inside a capture, or for parameters
+ * the check refuses.  pagk_destroy destroys a live sequence. */
+int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params);
+/* Ends the sequence (Examples/Demo/RealSenseD435i.cpp:199-321, leaving the loop): waits for its queued work, destroys its
+ * graphs, frees its blocks.  PAGK_E_ARG without a sequence or inside a capture. */
+int pagk_sequence_destroy(pagk_ctx *ctx);
+/* The first frame (Examples/Demo/RealSenseD435i.cpp:221-235): its pyramid into slot 0 and the first-frame hand-over, an
+ * all-zero status, into key set 0.  frame: a host image of the sequence's size.  cand: host, n_cand x 2 floats
+ * (0 <= n_cand <= cand_cap), required for detector 0 (non-NULL also when n_cand is 0) and refused (non-NULL or n_cand != 0) otherwise.  Runs directly, never
+ * as a graph; may be called again to restart (graphs are kept).  Invalid after pagk_selftest_fill_workspaces until called. */
+int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *cand, int32_t n_cand);
+/* Frame k >= 1 (Examples/Demo/RealSenseD435i.cpp:237-321): tracks pair (k - 1, k) and hands over to pair (k, k + 1).  rot9:
+ * nine host floats, rows 0 and 1 of K R K^-1 followed by the third row of R, as pagk_gyro_predict_device_rot defines them
+ * (NULL: nine zeros are NOT substituted -- PAGK_E_ARG when the tracker predicts).  mode: PAGK_SEQ_GRAPH or PAGK_SEQ_DIRECT.
+ * Nothing is synchronised except the flow control of the pinned ring (a block is rewritten only after the copy that read
+ * it, four frames earlier, has run).  PAGK_E_ARG before pagk_sequence_start. */
+int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand,
+                       int32_t mode);
+/* The current key set (Examples/Demo/RealSenseD435i.cpp:199-321, what the next pair starts from), synchronous: the first
+ * `cap` rows (1 <= cap <= the sequence's cap) of keys, keys_un, keys_normal (x 2 floats), index_in_last (int32), live
+ * (bytes); state: PAGK_HANDOVER_STATE_WORDS int32; info: PAGK_DETECT_INFO_WORDS int32 of the detector (zeros for detector
+ * 0).  Any array but keys_un may be NULL. */
+int pagk_sequence_read(pagk_ctx *ctx, int32_t cap, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
+                       uint8_t *live, int32_t *state, int32_t *info);
+/* What SetBackToFrame (src/gyro_aided_tracker.cpp:97-111; Examples/Demo/RealSenseD435i.cpp:199-321) hands over for the last
+ * pair, synchronous: status (the mask after validation), pt_predict, pt_predict_un (x 2 floats), err (Lucas-Kanade's error;
+ * 0 for PatchMatch), the first `cap` rows each.  Any array may be NULL.  PAGK_E_ARG before the first pagk_sequence_step. */
+int pagk_sequence_read_pair(pagk_ctx *ctx, int32_t cap, uint8_t *status, float *pt_predict, float *pt_predict_un, float *err);
+/* Host-side words, nothing synchronised (Examples/Demo/RealSenseD435i.cpp:199-321 has no counterpart), PAGK_SEQ_STATUS_WORDS
+ * int32: [0] frames handed in, [1] 1 if the last step was a graph replay, [2] graphs held, [3] 0. */
+int pagk_sequence_status(pagk_ctx *ctx, int32_t *words);
 
 #ifdef __cplusplus
 }

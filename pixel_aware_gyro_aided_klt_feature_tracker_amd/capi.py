@@ -107,6 +107,19 @@ ASSOC_STATS_FIELDS = ("avg1", "avg2", "max1", "max2", "threshold", "sum1", "sum2
 DETECT_INFO_WORDS = 8
 ORB_INFO_WORDS = 8
 LK_INFO_WORDS = 8
+
+
+class SequenceParams(C.Structure):
+    """pagk_sequence_params (include/pagk.h): the configuration of the sequence a context owns."""
+    _fields_ = [("track", Params), ("lk", LkParams), ("fit", FitParams), ("harris", DetectParams), ("fast", FastParams),
+                ("new_point_threshold", C.c_double), ("tracker", C.c_int32), ("lk_initial_flow", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("cap", C.c_int32), ("target_n", C.c_int32),
+                ("detector", C.c_int32), ("cand_cap", C.c_int32), ("validate", C.c_int32), ("sigma", C.c_float)]
+
+
+SEQ_PATCHMATCH, SEQ_LK = 0, 1
+SEQ_GRAPH, SEQ_DIRECT = 0, 1
+SEQ_STATUS_WORDS = 4
 ORB_MAX_LEVELS = 8
 ORB_LEVELS_INFO_WORDS = 32
 LK_INFO_FIELDS = ("n", "raw", "kept", "top_level", "lost_min_eig", "lost_out_of_range")
@@ -381,6 +394,21 @@ def declare(lib) -> None:
         lib.pagk_lk_track.argtypes = [vp, _P(LkParams), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp]
         lib.pagk_selftest_lk_level.restype = C.c_int
         lib.pagk_selftest_lk_level.argtypes = [vp, i32, i32, vp, C.c_int64]
+    if hasattr(lib, "pagk_sequence_create"):
+        sp = _P(SequenceParams)
+        lib.pagk_sequence_params_default.restype = None
+        lib.pagk_sequence_params_default.argtypes = [sp]
+        for name, args in (("pagk_sequence_params_check", [sp]), ("pagk_sequence_create", [vp, sp]),
+                           ("pagk_sequence_destroy", [vp]), ("pagk_sequence_start", [vp, _P(Image), vp, i32]),
+                           ("pagk_sequence_step", [vp, _P(Image), vp, vp, i32, i32]),
+                           ("pagk_sequence_read", [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+                           ("pagk_sequence_read_pair", [vp, i32, vp, vp, vp, vp]), ("pagk_sequence_status", [vp, vp])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_lk_track_flow"):
+        lib.pagk_lk_track_flow.restype = C.c_int
+        lib.pagk_lk_track_flow.argtypes = [vp, _P(LkParams), _P(Params), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp]
     f32 = C.c_float
     for name in ("pagk_graph_begin",):
         getattr(lib, name).restype = C.c_int
@@ -548,7 +576,9 @@ EXPORTED_SYMBOLS = [
     "pagk_orb_slot_read", "pagk_orb_match_slots", "pagk_orb_match_slots_read", "pagk_orb_extract_levels",
     "pagk_orb_detect_levels", "pagk_selftest_orb_level",
     "pagk_lk_params_default", "pagk_lk_params_check", "pagk_lk_levels", "pagk_lk_pyramid_device", "pagk_lk_track_device",
-    "pagk_lk_track", "pagk_selftest_lk_level",
+    "pagk_lk_track", "pagk_selftest_lk_level", "pagk_lk_track_flow",
+    "pagk_sequence_params_default", "pagk_sequence_params_check", "pagk_sequence_create", "pagk_sequence_destroy",
+    "pagk_sequence_start", "pagk_sequence_step", "pagk_sequence_read", "pagk_sequence_read_pair", "pagk_sequence_status",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
@@ -701,6 +731,22 @@ def lk_params_default(**overrides) -> LkParams:
             raise TypeError(f"pagk_lk_params has no field {k}")
         setattr(p, k, v)
     return p
+
+
+def sequence_params_default(**overrides) -> SequenceParams:
+    """pagk_sequence_params_default() with overrides (any field of pagk_sequence_params; nested blocks as their structures)."""
+    p = SequenceParams()
+    load().pagk_sequence_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(SequenceParams._fields_):
+            raise TypeError(f"pagk_sequence_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def sequence_params_check(p: SequenceParams) -> int:
+    """pagk_sequence_params_check: PAGK_OK, or the code pagk_sequence_create refuses these parameters with (needs no device)."""
+    return int(load().pagk_sequence_params_check(C.byref(p)))
 
 
 def lk_params_check(p: LkParams) -> int:
@@ -1578,6 +1624,95 @@ class Context:
         out["info"] = info
         out.update(zip(LK_INFO_FIELDS, (int(v) for v in info[:6])))
         return out
+
+    def lk_track_flow(self, img_ref: np.ndarray, img_cur: np.ndarray, pts, lk: LkParams | None = None, cam: Params | None = None,
+                      pt_init=None, status_in=None) -> dict:
+        """pagk_lk_track_flow, host buffers: Lucas-Kanade started from pt_init (None: pts), rows with status_in == 0 (None:
+        all 1) left out, the distorted point with the camera of `cam` (None: no pt_out_dist) -> the dict of lk_track plus
+        pt_out_dist (n x 2, with cam) and the info word `skipped`."""
+        lk = lk if lk is not None else lk_params_default()
+        pt = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = int(pt.shape[0])
+        nn = max(n, 1)
+        init = None if pt_init is None else np.ascontiguousarray(pt_init, np.float32).reshape(-1, 2)
+        live = None if status_in is None else np.ascontiguousarray(status_in, np.uint8).reshape(-1)
+        if (init is not None and init.shape[0] != n) or (live is not None and live.shape[0] != n):
+            raise ValueError("pt_init and status_in have one row per point")
+        ir, ic = image_view(img_ref), image_view(img_cur)
+        out = dict(pt_out=np.zeros((nn, 2), np.float32), status=np.zeros(nn, np.uint8), status_raw=np.zeros(nn, np.uint8),
+                   err=np.zeros(nn, np.float32), flow=np.zeros((nn, 2), np.float32))
+        if cam is not None:
+            out["pt_out_dist"] = np.zeros((nn, 2), np.float32)
+        info = np.zeros(LK_INFO_WORDS, np.int32)
+        opt = lambda a: _ptr(a) if (a is not None and n) else None     # noqa: E731
+        self._check(self.lib.pagk_lk_track_flow(self.h, C.byref(lk), C.byref(cam) if cam is not None else None, C.byref(ir),
+                                                C.byref(ic), n, opt(pt), opt(init), opt(live), _ptr(out["pt_out"]),
+                                                _ptr(out["pt_out_dist"]) if cam is not None else None, _ptr(out["status"]),
+                                                _ptr(out["status_raw"]), _ptr(out["err"]), _ptr(out["flow"]), _ptr(info)),
+                    "pagk_lk_track_flow")
+        out = {k: v[:n] for k, v in out.items()}
+        out["info"] = info
+        out.update(zip(LK_INFO_FIELDS, (int(v) for v in info[:6])))
+        out["skipped"] = int(info[6])
+        return out
+
+    # the sequence the context owns (Examples/Demo/RealSenseD435i.cpp:199-321) -------------------------------------------
+    def sequence_create(self, sp: SequenceParams):
+        """pagk_sequence_create: one sequence per context; its buffers are the context's."""
+        self._check(self.lib.pagk_sequence_create(self.h, C.byref(sp)), "pagk_sequence_create")
+        self._seq_params = sp
+
+    def sequence_destroy(self):
+        self._check(self.lib.pagk_sequence_destroy(self.h), "pagk_sequence_destroy")
+
+    @staticmethod
+    def _seq_cand(candidates):
+        if candidates is None:
+            return None, None, 0
+        cand = np.ascontiguousarray(candidates, np.float32).reshape(-1, 2)
+        n = int(cand.shape[0])
+        if n == 0:
+            cand = np.zeros((1, 2), np.float32)   # (an empty list is still a list: the pointer is required)
+        return cand, cand.ctypes.data, n
+
+    def sequence_start(self, frame: np.ndarray, candidates=None):
+        """pagk_sequence_start: the first frame (host image); candidates (n x 2) for a sequence without a detector."""
+        iv = image_view(frame)
+        keep, ptr, n = self._seq_cand(candidates)
+        self._check(self.lib.pagk_sequence_start(self.h, C.byref(iv), ptr, n), "pagk_sequence_start")
+
+    def sequence_step(self, frame: np.ndarray, rot9=None, candidates=None, mode: int = SEQ_GRAPH):
+        """pagk_sequence_step: frame k >= 1 with its nine rotation floats; nothing is synchronised."""
+        iv = image_view(frame)
+        rot = None if rot9 is None else np.ascontiguousarray(rot9, np.float32).reshape(9)
+        keep, ptr, n = self._seq_cand(candidates)
+        self._check(self.lib.pagk_sequence_step(self.h, C.byref(iv), _ptr(rot), ptr, n, int(mode)), "pagk_sequence_step")
+
+    def sequence_read(self, cap: int) -> dict:
+        """pagk_sequence_read -> dict(keys, keys_un, keys_normal, index_in_last, live (cap rows), state, info and the state
+        words by name)."""
+        out = dict(keys=np.zeros((cap, 2), np.float32), keys_un=np.zeros((cap, 2), np.float32),
+                   keys_normal=np.zeros((cap, 2), np.float32), index_in_last=np.zeros(cap, np.int32), live=np.zeros(cap, np.uint8),
+                   state=np.zeros(HANDOVER_STATE_WORDS, np.int32), info=np.zeros(DETECT_INFO_WORDS, np.int32))
+        self._check(self.lib.pagk_sequence_read(self.h, cap, *(_ptr(out[k]) for k in ("keys", "keys_un", "keys_normal",
+                                                                                       "index_in_last", "live", "state", "info"))),
+                    "pagk_sequence_read")
+        out.update(zip(HANDOVER_STATE_FIELDS, (int(v) for v in out["state"][:5])))
+        return out
+
+    def sequence_read_pair(self, cap: int) -> dict:
+        """pagk_sequence_read_pair -> dict(status, pt_predict, pt_predict_un, err), cap rows: what the last pair handed over."""
+        out = dict(status=np.zeros(cap, np.uint8), pt_predict=np.zeros((cap, 2), np.float32),
+                   pt_predict_un=np.zeros((cap, 2), np.float32), err=np.zeros(cap, np.float32))
+        self._check(self.lib.pagk_sequence_read_pair(self.h, cap, *(_ptr(out[k]) for k in ("status", "pt_predict", "pt_predict_un",
+                                                                                            "err"))), "pagk_sequence_read_pair")
+        return out
+
+    def sequence_status(self) -> dict:
+        """pagk_sequence_status -> dict(frames, last_was_graph, graphs); nothing is synchronised."""
+        w = np.zeros(SEQ_STATUS_WORDS, np.int32)
+        self._check(self.lib.pagk_sequence_status(self.h, _ptr(w)), "pagk_sequence_status")
+        return dict(frames=int(w[0]), last_was_graph=bool(w[1]), graphs=int(w[2]))
 
     def selftest_lk_level(self, slot: int, level: int, width: int, height: int, pitch: int | None = None) -> np.ndarray:
         """pagk_selftest_lk_level: level `level` (>= 1) of the slot's Lucas-Kanade pyramid, height x width."""

@@ -52,6 +52,34 @@ struct FrameSlot {
     bool valid = false;
 };
 
+// The sequence a context owns (pagk_sequence_*): its parameters, typed views into buf[SEQ], the pinned input ring and where
+// the loop stands.  Everything the steps launch on is in buf[SEQ]; the pointers below are fixed from create to destroy.
+struct SeqState {
+    pagk_sequence_params p;
+    size_t in_bytes = 0, off_rot = 0, off_ncand = 0, off_cand = 0;   // the input block: image | rot9 | n_cand | candidates
+    uint8_t *in = nullptr;        // the fixed device input block
+    uint8_t *img[2] = {};         // Lucas-Kanade: each parity's own copy of its frame (level 0 is read in place)
+    struct KeySet {
+        float *keys, *keys_un, *keys_normal;
+        int32_t *index_in_last;
+        uint8_t *live;
+    } set[2] = {};
+    uint8_t *work = nullptr;      // the work arrays, zeroed by start
+    size_t work_bytes = 0;
+    float *pu = nullptr, *pd = nullptr, *aff = nullptr, *pt_un = nullptr, *pt_dist = nullptr, *pp = nullptr, *ppu = nullptr;
+    float *score = nullptr, *lk_err = nullptr;
+    uint8_t *st_in = nullptr, *status = nullptr, *st = nullptr, *zero = nullptr;
+    double *pix_err = nullptr, *dist_pred = nullptr, *th = nullptr;
+    int32_t *kept = nullptr, *cnt = nullptr, *state = nullptr, *info = nullptr, *lk_info = nullptr;
+    static constexpr int kRing = 4;   // pinned input blocks: one is rewritten only after the copy that read it has run
+    void *pinned[kRing] = {};
+    hipEvent_t read_done[kRing] = {};
+    bool recorded[kRing] = {};
+    int turn = 0, frames = 0;
+    bool started = false, stepped = false, last_graph = false, direct_done[2] = {};
+    int graph[2] = {-1, -1};
+};
+
 }  // namespace
 
 struct pagk_ctx {
@@ -92,6 +120,7 @@ struct pagk_ctx {
         LV,            // one-level-per-wave launches: levels_layout (pagk_layout.h)
         PRIO_HINT,     // the 4-wave kernels' hint (pagk_prio.h): one int32 per feature slot of the largest launch so far
         DISPATCH_ORDER,  // ... and their dispatch order (pagk_order.h): one int32 per feature slot, beside the hints
+        SEQ,           // the sequence the context owns (pagk_sequence_*): input block, two key sets, work arrays, state and info words
         kBufs
     };
     DevBuf buf[kBufs];
@@ -196,6 +225,7 @@ struct pagk_ctx {
     int levels_shift = 0;                // PAGK_LEVELS_XCD_SHIFT (tests): waves start with another XCD's ticket sequence
     bool levels_shared = false;          // PAGK_LEVELS_SHARED=1 (measurement): ... also for contexts that share the device
     bool unfused_pyramid = false;  // PAGK_UNFUSED_PYRAMID=1: level-by-level launches (cross-check)
+    SeqState *seq = nullptr;       // pagk_sequence_create .. pagk_sequence_destroy
     char err[256] = {0};
 };
 
@@ -1366,6 +1396,10 @@ void pagk_destroy(pagk_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    if (ctx->seq) {   // a live sequence goes with its context
+        ctx->capturing = false;
+        (void)pagk_sequence_destroy(ctx);
+    }
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
     if (ctx->aux_stream) {
         (void)hipStreamSynchronize(ctx->aux_stream);
@@ -3698,21 +3732,10 @@ int lk_pyramid_slot(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot)
     return PAGK_OK;
 }
 
-using LkKernel = void (*)(LkTrackArgs);
-LkKernel lk_kernel(int win)
-{
-    switch (lk_npix(win)) {
-        case 1: return k_lk_track<1>;
-        case 2: return k_lk_track<2>;
-        case 4: return k_lk_track<4>;
-        case 8: return k_lk_track<8>;
-        default: return k_lk_track<16>;
-    }
-}
-
-int lk_track_slots(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
-                   const float *d_pt_ref, const int32_t *d_n, float *d_pt_out, uint8_t *d_status, uint8_t *d_status_raw,
-                   float *d_err, float *d_flow, int32_t *d_info)
+// What both trackers check and the launch arguments they share: the levels of both slots, the arrays, the constants.
+int lk_track_args(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
+                  const float *d_pt_ref, const int32_t *d_n, float *d_pt_out, uint8_t *d_status, uint8_t *d_status_raw,
+                  float *d_err, float *d_flow, int32_t *d_info, LkTrackArgs *out)
 {
     if (!ctx || lk_params_check(params) || slot_ref < 0 || slot_ref >= kSlots || slot_cur < 0 || slot_cur >= kSlots ||
         cap < 1 || cap > kLkMaxRows || !d_pt_ref || !d_pt_out || !d_status || !d_err || !d_info)
@@ -3752,8 +3775,71 @@ int lk_track_slots(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref
     a.flow = d_flow, a.info = d_info;
     a.eps2 = params->epsilon * params->epsilon, a.min_eig = params->min_eig_threshold, a.err_threshold = params->err_threshold;
     a.cap = cap, a.win = 2 * params->half_patch + 1, a.top = top, a.max_count = params->max_count;
+    *out = a;
+    return PAGK_OK;
+}
+
+using LkKernel = void (*)(LkTrackArgs);
+LkKernel lk_kernel(int win)
+{
+    switch (lk_npix(win)) {
+        case 1: return k_lk_track<1>;
+        case 2: return k_lk_track<2>;
+        case 4: return k_lk_track<4>;
+        case 8: return k_lk_track<8>;
+        default: return k_lk_track<16>;
+    }
+}
+
+int lk_track_slots(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot_ref, int32_t slot_cur, int32_t cap,
+                   const float *d_pt_ref, const int32_t *d_n, float *d_pt_out, uint8_t *d_status, uint8_t *d_status_raw,
+                   float *d_err, float *d_flow, int32_t *d_info)
+{
+    LkTrackArgs a;
+    int rc = lk_track_args(ctx, params, slot_ref, slot_cur, cap, d_pt_ref, d_n, d_pt_out, d_status, d_status_raw, d_err, d_flow,
+                           d_info, &a);
+    if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(d_info, 0, kLkInfoWords * sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(lk_kernel(a.win), dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// Lucas-Kanade from an initial point, live rows only, with the distorted output (k_lk_flow): the chooser mirrors lk_kernel
+using LkFlowKernel = void (*)(LkFlowArgs);
+LkFlowKernel lk_flow_kernel(int win)
+{
+    switch (lk_npix(win)) {
+        case 1: return k_lk_flow<1>;
+        case 2: return k_lk_flow<2>;
+        case 4: return k_lk_flow<4>;
+        case 8: return k_lk_flow<8>;
+        default: return k_lk_flow<16>;
+    }
+}
+
+// cam: the camera of d_pt_out_dist (required with it); d_pt_init, d_status_in, d_pt_out_dist may be nullptr
+int lk_flow_slots(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam, int32_t slot_ref, int32_t slot_cur,
+                  int32_t cap, const float *d_pt_ref, const float *d_pt_init, const uint8_t *d_status_in, const int32_t *d_n,
+                  float *d_pt_out, float *d_pt_out_dist, uint8_t *d_status, uint8_t *d_status_raw, float *d_err, float *d_flow,
+                  int32_t *d_info)
+{
+    if (d_pt_out_dist && !cam) return PAGK_E_ARG;
+    LkFlowArgs f = {};
+    int rc = lk_track_args(ctx, params, slot_ref, slot_cur, cap, d_pt_ref, d_n, d_pt_out, d_status, d_status_raw, d_err, d_flow,
+                           d_info, &f.t);
+    if (rc) return rc;
+    f.pt_init = d_pt_init, f.status_in = d_status_in, f.pt_out_dist = d_pt_out_dist;
+    if (cam) {   // as fill_param_args takes the camera for the PatchMatch epilogue
+        f.distort_on = cam->dist_coef[0] != 0.0f;
+        f.fx = cam->fx, f.fy = cam->fy, f.cx = cam->cx, f.cy = cam->cy;
+        f.fx_inv = (float)(1.0 / (double)cam->fx);  // src/utils.cpp:53
+        f.fy_inv = (float)(1.0 / (double)cam->fy);
+        f.k1 = cam->dist_coef[0], f.k2 = cam->dist_coef[1], f.p1 = cam->dist_coef[2], f.p2 = cam->dist_coef[3];
+        f.k3 = cam->n_dist_coef == 5 ? cam->dist_coef[4] : 0.0f;
+    }
+    HIPCHK(ctx, hipMemsetAsync(d_info, 0, kLkInfoWords * sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(lk_flow_kernel(f.t.win), dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, ctx->stream, f);
     HIPCHK(ctx, hipGetLastError());
     return PAGK_OK;
 }
@@ -3817,6 +3903,38 @@ int pagk_lk_track(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_image 
                         s.at<uint8_t>(4), s.at<float>(5), s.at<float>(6), s.at<int32_t>(7));
     if (rc || (rc = s.out(2, pt_out, nn * 8)) || (rc = s.out(3, status, nn)) || (rc = s.out(4, status_raw, nn)) ||
         (rc = s.out(5, err, nn * 4)) || (rc = s.out(6, flow, nn * 8)) || (rc = s.out(7, info, kLkInfoWords * 4)))
+        return rc;
+    return s.finish();
+}
+
+int pagk_lk_track_flow(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam, const pagk_image *ref,
+                       const pagk_image *cur, int32_t n, const float *pt_ref, const float *pt_init, const uint8_t *status_in,
+                       float *pt_out, float *pt_out_dist, uint8_t *status, uint8_t *status_raw, float *err, float *flow,
+                       int32_t *info)
+{
+    if (!ctx || !ref || !cur || lk_params_check(params) || (cam && check_params(cam)) || (pt_out_dist && !cam)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_lk_track_flow");
+    if (n < 0 || n > kLkMaxRows || (n && (!pt_ref || !pt_out || !status || !err))) return PAGK_E_ARG;
+    if (ref->width != cur->width || ref->height != cur->height || pagk_lk_levels(ref->width, ref->height, params) < 0)
+        return PAGK_E_ARG;
+    int rc;
+    if ((rc = frame_upload_any(ctx, 4, ref, 1)) || (rc = frame_upload_any(ctx, 5, cur, 1))) return rc;
+    if ((rc = lk_pyramid_slot(ctx, params, 4)) || (rc = lk_pyramid_slot(ctx, params, 5))) return rc;
+    const size_t nc = (size_t)std::max(n, 1);
+    // points in | count | initial points | live mask | points out | distorted | status | raw status | err | flow | info
+    const size_t sizes[11] = {nc * 8, 256, nc * 8, nc, nc * 8, nc * 8, nc, nc, nc * 4, nc * 8, 256};
+    const size_t nn = (size_t)n;
+    Staged<11> s(ctx, sizes);
+    if ((rc = s.open(nullptr, nullptr)) || (rc = s.in(0, pt_ref, nn * 8)) || (rc = s.in(1, &n, 4)) ||
+        (rc = s.in(2, pt_init, nn * 8)) || (rc = s.in(3, status_in, nn)))
+        return rc;
+    rc = lk_flow_slots(ctx, params, cam, 4, 5, (int32_t)nc, s.at<float>(0), pt_init ? s.at<float>(2) : nullptr,
+                       status_in ? s.at<uint8_t>(3) : nullptr, s.at<int32_t>(1), s.at<float>(4),
+                       pt_out_dist ? s.at<float>(5) : nullptr, s.at<uint8_t>(6), s.at<uint8_t>(7), s.at<float>(8), s.at<float>(9),
+                       s.at<int32_t>(10));
+    if (rc || (rc = s.out(4, pt_out, nn * 8)) || (rc = s.out(5, pt_out_dist, nn * 8)) || (rc = s.out(6, status, nn)) ||
+        (rc = s.out(7, status_raw, nn)) || (rc = s.out(8, err, nn * 4)) || (rc = s.out(9, flow, nn * 8)) ||
+        (rc = s.out(10, info, kLkInfoWords * 4)))
         return rc;
     return s.finish();
 }
@@ -4655,6 +4773,7 @@ int pagk_selftest_fill_workspaces(pagk_ctx *ctx, uint32_t word, int32_t also_new
         if ((rc = fill_words(ctx, s.block.ptr, s.block.bytes, word))) return rc;
     }
     ctx->last_handover = false;
+    if (ctx->seq) ctx->seq->started = ctx->seq->stepped = false;   // (its key sets and work arrays are scratch too)
     return PAGK_OK;
 }
 
@@ -4986,6 +5105,356 @@ int pagk_search_klt(pagk_ctx *ctx, const pagk_lk_params *lk_params, const pagk_a
     if (info) memcpy(info, tail + 1, kAssocInfoWords * sizeof(int32_t));
     if (lk_info) memcpy(lk_info, tail + 1 + kAssocInfoWords, kLkInfoWords * sizeof(int32_t));
     return tail[0];
+}
+
+// ---- the sequence the context owns (Examples/Demo/RealSenseD435i.cpp:199-321) ---------------------------------------------
+namespace {
+
+constexpr int kSeqParts = 34;
+
+// This frame's inputs into the next pinned block, then one asynchronous copy into the fixed device block.
+int seq_feed(pagk_ctx *ctx, SeqState &q, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand)
+{
+    const int k = q.turn;
+    q.turn = (k + 1) % SeqState::kRing;
+    if (q.recorded[k]) HIPCHK(ctx, hipEventSynchronize(q.read_done[k]));   // flow control only: the copy four frames ago
+    uint8_t *pin = static_cast<uint8_t *>(q.pinned[k]);
+    for (int y = 0; y < q.p.height; y++)
+        memcpy(pin + (size_t)y * q.p.width, frame->data + (int64_t)y * frame->step, (size_t)q.p.width);
+    if (rot9) memcpy(pin + q.off_rot, rot9, 9 * sizeof(float));
+    if (q.p.detector == 0) {
+        memcpy(pin + q.off_ncand, &n_cand, sizeof n_cand);
+        if (n_cand) memcpy(pin + q.off_cand, cand, (size_t)n_cand * 8);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(q.in, pin, q.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(q.read_done[k], ctx->stream));
+    q.recorded[k] = true;
+    return PAGK_OK;
+}
+
+// what every start / step checks of its frame and candidate list
+int seq_inputs_check(const SeqState &q, const pagk_image *frame, const float *cand, int32_t n_cand)
+{
+    if (!frame || !frame->data || frame->width != q.p.width || frame->height != q.p.height || frame->step < frame->width)
+        return PAGK_E_ARG;
+    if (q.p.detector == 0) return cand && n_cand >= 0 && n_cand <= q.p.cand_cap ? PAGK_OK : PAGK_E_ARG;   // (required, even when empty)
+    return !cand && n_cand == 0 ? PAGK_OK : PAGK_E_ARG;   // a detecting sequence takes no list
+}
+
+// the frame in the input block into frame slot `slot` (Lucas-Kanade: through the parity's own copy, with its pyrDown levels)
+int seq_frame(pagk_ctx *ctx, SeqState &q, int slot)
+{
+    const pagk_sequence_params &p = q.p;
+    if (p.tracker != PAGK_SEQ_LK) return pagk_frame_set_device(ctx, slot, q.in, p.width, p.height, p.width, p.track.pyramids);
+    HIPCHK(ctx, hipMemcpyAsync(q.img[slot], q.in, (size_t)p.width * p.height, hipMemcpyDeviceToDevice, ctx->stream));
+    int rc = pagk_frame_set_device(ctx, slot, q.img[slot], p.width, p.height, p.width, p.track.pyramids);
+    return rc ? rc : lk_pyramid_slot(ctx, &p.lk, slot);
+}
+
+int seq_handover(pagk_ctx *ctx, SeqState &q, const uint8_t *status, int slot)
+{
+    const pagk_sequence_params &p = q.p;
+    const SeqState::KeySet &d = q.set[slot];
+    if (p.detector == 2)
+        return pagk_frame_handover_fast_device(ctx, &p.track, p.width, p.height, p.cap, p.target_n, p.new_point_threshold, status,
+                                               q.pp, q.ppu, &p.fast, slot, d.keys, d.keys_un, d.keys_normal, d.index_in_last,
+                                               d.live, nullptr, q.state, q.info);
+    if (p.detector == 1)
+        return pagk_frame_handover_detect_device(ctx, &p.track, p.width, p.height, p.cap, p.target_n, p.new_point_threshold,
+                                                 status, q.pp, q.ppu, &p.harris, slot, d.keys, d.keys_un, d.keys_normal,
+                                                 d.index_in_last, d.live, nullptr, q.state, q.info);
+    return pagk_frame_handover_device(ctx, &p.track, p.width, p.height, p.cap, p.target_n, p.new_point_threshold, status, q.pp,
+                                      q.ppu, p.cand_cap, reinterpret_cast<const int32_t *>(q.in + q.off_ncand),
+                                      reinterpret_cast<const float *>(q.in + q.off_cand), d.keys, d.keys_un, d.keys_normal,
+                                      d.index_in_last, d.live, nullptr, q.state);
+}
+
+// The work of a frame of parity c: frame slot c is the current frame, slot 1 - c the reference; key set 1 - c holds the
+// reference keypoints, set c receives the next pair's.
+int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
+{
+    const pagk_sequence_params &p = q.p;
+    const SeqState::KeySet &ref = q.set[1 - c];
+    const float *rot = reinterpret_cast<const float *>(q.in + q.off_rot);
+    int rc = seq_frame(ctx, q, c);
+    if (rc) return rc;
+    if (p.tracker == PAGK_SEQ_LK) {   // :353-380
+        const float *init = nullptr;
+        const uint8_t *live = ref.live;
+        if (p.lk_initial_flow) {
+            rc = pagk_gyro_predict_device_live(ctx, &p.track, p.width, p.height, rot, p.cap, ref.keys_un, ref.live, q.pu, q.pd,
+                                               q.st_in, q.aff);
+            if (rc) return rc;
+            init = q.pu, live = q.st_in;
+        }
+        rc = lk_flow_slots(ctx, &p.lk, &p.track, 1 - c, c, p.cap, ref.keys_un, init, live, q.state, q.ppu, q.pp, q.st, nullptr,
+                           q.lk_err, nullptr, q.lk_info);
+        if (rc) return rc;
+    } else {
+        const pagk_outputs out = {q.pt_un, q.pt_dist, q.status, q.pix_err, q.dist_pred, nullptr, nullptr};
+        if (p.track.has_gyro_predict_initial) {
+            rc = pagk_gyro_predict_device_live(ctx, &p.track, p.width, p.height, rot, p.cap, ref.keys_un, ref.live, q.pu, q.pd,
+                                               q.st_in, q.aff);
+            if (!rc) rc = pagk_track_device(ctx, &p.track, 1 - c, c, p.cap, ref.keys_un, q.pu, q.aff, q.st_in, &out);
+        } else {   // no prediction: the live mask is the tracking kernels' status_in
+            rc = pagk_track_device(ctx, &p.track, 1 - c, c, p.cap, ref.keys_un, ref.keys_un, q.aff, ref.live, &out);
+        }
+        if (rc) return rc;
+        rc = pagk_post_filter_device(ctx, p.cap, p.track.half_patch, q.status, q.pix_err, q.dist_pred, q.pt_dist, q.pt_un, q.st,
+                                     q.pp, q.ppu, q.kept, q.th);
+        if (rc) return rc;
+    }
+    if (p.validate) {
+        rc = pagk_geometry_validation_device(ctx, &p.fit, p.cap, ref.keys_un, q.ppu, q.st, p.sigma, q.cnt, q.score);
+        if (rc) return rc;
+    }
+    return seq_handover(ctx, q, q.st, c);
+}
+
+// the sequence of a call, or nullptr with the reason in ctx->err
+SeqState *seq_of(pagk_ctx *ctx, const char *what)
+{
+    if (!ctx) return nullptr;
+    if (ctx->capturing) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s between pagk_graph_begin and pagk_graph_end: the sequence captures its own graphs", what);
+        return nullptr;
+    }
+    if (!ctx->seq) snprintf(ctx->err, sizeof(ctx->err), "%s: the context has no sequence (pagk_sequence_create)", what);
+    return ctx->seq;
+}
+
+}  // namespace
+
+void pagk_sequence_params_default(pagk_sequence_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    pagk_params_default(&p->track);
+    pagk_lk_params_default(&p->lk);
+    pagk_fit_params_default(&p->fit);
+    pagk_detect_params_default(&p->harris);
+    pagk_fast_params_default(&p->fast);
+    p->tracker = PAGK_SEQ_PATCHMATCH, p->lk_initial_flow = 0;
+    p->width = 640, p->height = 480, p->cap = 448, p->target_n = 400, p->new_point_threshold = 320.0;
+    p->detector = 0, p->cand_cap = 1024, p->validate = 1, p->sigma = 1.0f;
+}
+
+int pagk_sequence_params_check(const pagk_sequence_params *p)
+{
+    if (!p) return PAGK_E_ARG;
+    int rc = check_params(&p->track);
+    if (rc || (rc = lk_params_check(&p->lk))) return rc;
+    if (!fit_params_ok(&p->fit) || !detect_params_ok(&p->harris)) return PAGK_E_ARG;
+    if ((rc = fast_params_check(&p->fast))) return rc;
+    if ((p->tracker != PAGK_SEQ_PATCHMATCH && p->tracker != PAGK_SEQ_LK) || (p->lk_initial_flow & ~1) || (p->validate & ~1) ||
+        p->detector < 0 || p->detector > 2 || p->width < 14 || p->height < 14 || p->target_n < 1 || p->cap < p->target_n ||
+        p->cap > kLkMaxRows || (p->detector == 0 && p->cand_cap < 1) || p->cand_cap < 0 || p->cand_cap > kLkMaxRows ||
+        !std::isfinite(p->new_point_threshold) || !std::isfinite(p->sigma) || !(p->sigma > 0.0f) ||
+        (int64_t)p->width * p->height > (int64_t)1 << 28)
+        return PAGK_E_ARG;
+    if (p->tracker == PAGK_SEQ_LK && pagk_lk_levels(p->width, p->height, &p->lk) < 0) return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params)
+{
+    if (!ctx || pagk_sequence_params_check(params)) return PAGK_E_ARG;
+    if (ctx->seq || in_capture(ctx)) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_create: %s", ctx->seq ? "the context has a sequence already" : "inside a graph capture");
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SeqState *q = new (std::nothrow) SeqState();
+    if (!q) return PAGK_E_NOMEM;
+    q->p = *params;
+    const size_t n = (size_t)params->cap, px = (size_t)params->width * params->height;
+    q->off_rot = align_up(px, kPartAlign);
+    q->off_ncand = q->off_rot + kPartAlign;
+    q->off_cand = q->off_ncand + kPartAlign;
+    q->in_bytes = q->off_cand + align_up((size_t)(params->detector == 0 ? params->cand_cap : 0) * 8, kPartAlign);
+    const bool lk = params->tracker == PAGK_SEQ_LK;
+    // input | 2 frame copies (LK) | 2 x (keys keys_un keys_normal index_in_last live) | state | info | the work arrays:
+    // pu pd aff pt_un pt_dist pp ppu score lk_err st_in status st zero pix_err dist_pred th kept cnt lk_info
+    const size_t sizes[kSeqParts] = {q->in_bytes, lk ? px : 0, lk ? px : 0,
+                                     n * 8, n * 8, n * 8, n * 4, n, n * 8, n * 8, n * 8, n * 4, n, 256, 256,
+                                     n * 8, n * 8, n * 16, n * 8, n * 8, n * 8, n * 8, 256, n * 4, n, n, n, n, n * 8, n * 8, 256, 256,
+                                     256, 256};
+    const Layout<kSeqParts> lay(sizes);
+    DevBuf &b = ctx->buf[pagk_ctx::SEQ];
+    int rc = reserve(ctx, b, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the sequence's block", "destroy the graphs first");
+    for (int k = 0; !rc && k < SeqState::kRing; k++) {
+        if (hipHostMalloc(&q->pinned[k], q->in_bytes, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&q->read_done[k], hipEventDisableTiming) != hipSuccess) {
+            snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_create: no pinned input block of %zu bytes", q->in_bytes);
+            rc = PAGK_E_NOMEM;
+        } else {
+            memset(q->pinned[k], 0, q->in_bytes);
+        }
+    }
+    if (rc) {
+        for (int k = 0; k < SeqState::kRing; k++) {
+            if (q->pinned[k]) (void)hipHostFree(q->pinned[k]);
+            if (q->read_done[k]) (void)hipEventDestroy(q->read_done[k]);
+        }
+        delete q;
+        return rc;
+    }
+    int k = 0;
+    void *base = b.ptr;
+    q->in = lay.at<uint8_t>(base, k++);
+    for (int s = 0; s < 2; s++) q->img[s] = lay.at<uint8_t>(base, k++);
+    for (int s = 0; s < 2; s++) {
+        q->set[s].keys = lay.at<float>(base, k++), q->set[s].keys_un = lay.at<float>(base, k++);
+        q->set[s].keys_normal = lay.at<float>(base, k++), q->set[s].index_in_last = lay.at<int32_t>(base, k++);
+        q->set[s].live = lay.at<uint8_t>(base, k++);
+    }
+    q->state = lay.at<int32_t>(base, k++), q->info = lay.at<int32_t>(base, k++);
+    q->work = lay.at<uint8_t>(base, k);
+    q->work_bytes = lay.total - lay.off[k];
+    q->pu = lay.at<float>(base, k++), q->pd = lay.at<float>(base, k++), q->aff = lay.at<float>(base, k++);
+    q->pt_un = lay.at<float>(base, k++), q->pt_dist = lay.at<float>(base, k++), q->pp = lay.at<float>(base, k++);
+    q->ppu = lay.at<float>(base, k++), q->score = lay.at<float>(base, k++), q->lk_err = lay.at<float>(base, k++);
+    q->st_in = lay.at<uint8_t>(base, k++), q->status = lay.at<uint8_t>(base, k++), q->st = lay.at<uint8_t>(base, k++);
+    q->zero = lay.at<uint8_t>(base, k++), q->pix_err = lay.at<double>(base, k++), q->dist_pred = lay.at<double>(base, k++);
+    q->th = lay.at<double>(base, k++), q->kept = lay.at<int32_t>(base, k++), q->cnt = lay.at<int32_t>(base, k++);
+    q->lk_info = lay.at<int32_t>(base, k++);
+    static_assert(kSeqParts == 34, "the carving above names every part");
+    if (k != kSeqParts) {
+        delete q;
+        return PAGK_E_ARG;
+    }
+    ctx->seq = q;
+    return PAGK_OK;
+}
+
+int pagk_sequence_destroy(pagk_ctx *ctx)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_destroy");
+    if (!q) return PAGK_E_ARG;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (int &g : q->graph) {
+        if (g >= 0) (void)pagk_graph_destroy(ctx, g);
+        g = -1;
+    }
+    for (int k = 0; k < SeqState::kRing; k++) {
+        if (q->pinned[k]) (void)hipHostFree(q->pinned[k]);
+        if (q->read_done[k]) (void)hipEventDestroy(q->read_done[k]);
+    }
+    ctx->seq = nullptr;
+    delete q;
+    bool alive = false;
+    for (int k = 0; k < pagk_ctx::kGraphs; k++) alive = alive || ctx->graph_execs[k];
+    return alive ? PAGK_OK : release(ctx, ctx->buf[pagk_ctx::SEQ]);   // (a graph of the caller's cannot point into it, but stay safe)
+}
+
+int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *cand, int32_t n_cand)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_start");
+    if (!q || seq_inputs_check(*q, frame, cand, n_cand)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const pagk_sequence_params &p = q->p;
+    // what the loop reads before it has written it: the reach flag, the all-zero status, the identity affine
+    HIPCHK(ctx, hipMemsetAsync(q->state, 0, 512, ctx->stream));   // (state and info: two parts of 256 bytes)
+    HIPCHK(ctx, hipMemsetAsync(q->work, 0, q->work_bytes, ctx->stream));
+    try {
+        std::vector<float> eye((size_t)p.cap * 4);
+        for (size_t i = 0; i < eye.size(); i += 4) eye[i] = 1.f, eye[i + 1] = 0.f, eye[i + 2] = 0.f, eye[i + 3] = 1.f;
+        HIPCHK(ctx, hipMemcpyAsync(q->aff, eye.data(), eye.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (eye is a local)
+    } catch (const std::bad_alloc &) {
+        return PAGK_E_NOMEM;
+    }
+    q->started = q->stepped = false;
+    int rc = seq_feed(ctx, *q, frame, nullptr, cand, n_cand);
+    if (rc || (rc = seq_frame(ctx, *q, 0)) || (rc = seq_handover(ctx, *q, q->zero, 0))) return rc;
+    q->started = true, q->frames = 1, q->last_graph = false;
+    return PAGK_OK;
+}
+
+int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand, int32_t mode)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_step");
+    if (!q || seq_inputs_check(*q, frame, cand, n_cand) || (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT)) return PAGK_E_ARG;
+    const pagk_sequence_params &p = q->p;
+    const bool predicts = p.tracker == PAGK_SEQ_LK ? p.lk_initial_flow != 0 : p.track.has_gyro_predict_initial != 0;
+    if (!q->started || (predicts && !rot9)) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step: %s", q->started ? "this tracker predicts: rot9 is required"
+                                                                                  : "pagk_sequence_start hands in the first frame");
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int c = q->frames & 1;
+    int rc = seq_feed(ctx, *q, frame, rot9, cand, n_cand);
+    if (rc) return rc;
+    if (mode == PAGK_SEQ_GRAPH && q->direct_done[c]) {
+        if (q->graph[c] < 0) {
+            if ((rc = pagk_graph_begin(ctx))) return rc;
+            rc = seq_issue(ctx, *q, c);
+            int32_t id = -1;
+            const int rc_end = pagk_graph_end(ctx, &id);
+            if (rc || rc_end) {
+                if (!rc_end && id >= 0) (void)pagk_graph_destroy(ctx, id);
+                return rc ? rc : rc_end;
+            }
+            q->graph[c] = id;
+        }
+        if ((rc = pagk_graph_launch(ctx, q->graph[c]))) return rc;
+        q->last_graph = true;
+    } else {   // also the first step of each parity in graph mode: allocations happen outside a capture
+        if ((rc = seq_issue(ctx, *q, c))) return rc;
+        q->direct_done[c] = true;
+        q->last_graph = false;
+    }
+    q->frames++;
+    q->stepped = true;
+    return PAGK_OK;
+}
+
+int pagk_sequence_read(pagk_ctx *ctx, int32_t cap, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,
+                       uint8_t *live, int32_t *state, int32_t *info)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_read");
+    if (!q || !q->started || !keys_un || cap < 1 || cap > q->p.cap) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const SeqState::KeySet &s = q->set[(q->frames - 1) & 1];
+    const size_t n = (size_t)cap;
+    const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // (then plain copies: the arrays are the caller's, pinned or not)
+    if (keys) HIPCHK(ctx, hipMemcpy(keys, s.keys, n * 8, d2h));
+    HIPCHK(ctx, hipMemcpy(keys_un, s.keys_un, n * 8, d2h));
+    if (keys_normal) HIPCHK(ctx, hipMemcpy(keys_normal, s.keys_normal, n * 8, d2h));
+    if (index_in_last) HIPCHK(ctx, hipMemcpy(index_in_last, s.index_in_last, n * 4, d2h));
+    if (live) HIPCHK(ctx, hipMemcpy(live, s.live, n, d2h));
+    if (state) HIPCHK(ctx, hipMemcpy(state, q->state, PAGK_HANDOVER_STATE_WORDS * 4, d2h));
+    if (info) HIPCHK(ctx, hipMemcpy(info, q->info, PAGK_DETECT_INFO_WORDS * 4, d2h));
+    return lv_check(ctx);
+}
+
+int pagk_sequence_read_pair(pagk_ctx *ctx, int32_t cap, uint8_t *status, float *pt_predict, float *pt_predict_un, float *err)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_read_pair");
+    if (!q || !q->started || !q->stepped || cap < 1 || cap > q->p.cap) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)cap;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (status) HIPCHK(ctx, hipMemcpy(status, q->st, n, hipMemcpyDeviceToHost));
+    if (pt_predict) HIPCHK(ctx, hipMemcpy(pt_predict, q->pp, n * 8, hipMemcpyDeviceToHost));
+    if (pt_predict_un) HIPCHK(ctx, hipMemcpy(pt_predict_un, q->ppu, n * 8, hipMemcpyDeviceToHost));
+    if (err) HIPCHK(ctx, hipMemcpy(err, q->lk_err, n * 4, hipMemcpyDeviceToHost));
+    return lv_check(ctx);
+}
+
+int pagk_sequence_status(pagk_ctx *ctx, int32_t *words)
+{
+    SeqState *sq = seq_of(ctx, "pagk_sequence_status");
+    if (!sq || !words) return PAGK_E_ARG;
+    const SeqState &q = *sq;
+    words[0] = q.started ? q.frames : 0;
+    words[1] = q.last_graph ? 1 : 0;
+    words[2] = (q.graph[0] >= 0) + (q.graph[1] >= 0);
+    words[3] = 0;
+    return PAGK_OK;
 }
 
 }  // extern "C"

@@ -14,6 +14,11 @@
 //                 the same integers and runs the same f32 tail, one rounding per operation -- every branch of the level
 //                 loop is uniform over the wave.  The tile is private to the wave, whose LDS accesses complete in program
 //                 order: the kernel has no workgroup barrier at all.  The counters are integer atomics.
+//   k_lk_flow     the same wavefront per feature started from an initial point (OpenCV 3.4's OPTFLOW_USE_INITIAL_FLOW
+//                 branch, the reference's open experiment at :364-365), live rows only (status_in), the distorted point
+//                 (:379, DistortVecPoints) written by lane 0 in the epilogue.  Both kernels are the text of pagk_lk_body.h:
+//                 one body, so the two cannot drift; with pt_init bit-equal to pt_ref and every status_in set the outputs
+//                 are those of k_lk_track byte for byte.
 // No launch is sized by a count: the grid comes from the capacity, the count is read on the device.
 #pragma once
 
@@ -83,6 +88,17 @@ struct LkTrackArgs {
     int cap, win, top, max_count;
 };
 
+// what k_lk_flow takes on top of LkTrackArgs
+struct LkFlowArgs {
+    LkTrackArgs t;
+    const float *pt_init;      // cap x 2, or nullptr: pt_ref
+    const uint8_t *status_in;  // cap, or nullptr: every row below the count is live
+    float *pt_out_dist;        // cap x 2, or nullptr
+    // the camera of DistortVecPoints (src/utils.cpp:49-76), as fill_param_args takes it from pagk_params
+    float fx, fy, cx, cy, fx_inv, fy_inv, k1, k2, p1, p2, k3;
+    int distort_on;            // dist_coef[0] != 0
+};
+
 // the largest window an instantiation serves, and the bytes of its tile
 __host__ __device__ constexpr int lk_max_win(int npix) { return npix == 1 ? 7 : npix == 2 ? 11 : npix == 4 ? 15 : npix == 8 ? 21 : 31; }
 __host__ __device__ constexpr int lk_tile_bytes(int npix) { return ((lk_max_win(npix) + 3) * (lk_max_win(npix) + 3) + 15) & ~15; }
@@ -150,160 +166,40 @@ __device__ __forceinline__ int lk_sample(const uint8_t *tile, int off, int side,
     return (tile[off] * w00 + tile[off + 1] * w01 + tile[off + side] * w10 + tile[off + side + 1] * w11 + 256) >> 9;
 }
 
+// DistortVecPoints, src/utils.cpp:49-76, one point: the arithmetic of distort_point (pagk_device.h), f32, uncontracted
+__device__ __forceinline__ void lk_distort_point(const LkFlowArgs &a, float ux, float uy, float &ox, float &oy)
+{
+    if (!a.distort_on) {
+        ox = ux;
+        oy = uy;
+        return;
+    }
+    float x = (ux - a.cx) * a.fx_inv;
+    float y = (uy - a.cy) * a.fy_inv;
+    float r2 = x * x + y * y;
+    float r4 = r2 * r2;
+    float r6 = r4 * r2;
+    float xd = x * (1 + a.k1 * r2 + a.k2 * r4 + a.k3 * r6) + 2 * a.p1 * x * y + a.p2 * (r2 + 2 * x * x);
+    float yd = y * (1 + a.k1 * r2 + a.k2 * r4 + a.k3 * r6) + a.p1 * (r2 + 2 * y * y) + 2 * a.p2 * x * y;
+    ox = a.fx * xd + a.cx;
+    oy = a.fy * yd + a.cy;
+}
+
 template <int NPIX>
 __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * lk_tile_bytes(NPIX)];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k = blockIdx.x * 4 + wave;   // the wave's feature
-    if (k >= a.cap) return;
-    const int n = a.n ? min(max(*a.n, 0), a.cap) : a.cap;
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.info[0] = n, a.info[3] = a.top;
-    if (k >= n) {   // rows at or beyond the count are zeroed
-        if (lane == 0) {
-            a.pt_out[2 * k] = 0.f, a.pt_out[2 * k + 1] = 0.f, a.status[k] = 0, a.err[k] = 0.f;
-            if (a.status_raw) a.status_raw[k] = 0;
-            if (a.flow) a.flow[2 * k] = 0.f, a.flow[2 * k + 1] = 0.f;
-        }
-        return;
-    }
-    uint8_t *tile = tiles + wave * lk_tile_bytes(NPIX);
-    const int win = a.win, npx = win * win, side_i = win + 3, side_j = win + 1;
-    const unsigned magic_win = lk_magic(win);
-    const float half = (float)(win - 1) * 0.5f;
-    const float rx = a.pt_ref[2 * k], ry = a.pt_ref[2 * k + 1];
-    int st = 1, lost_eig = 0, lost_range = 0;
-    float e = 0.f, nx = 0.f, ny = 0.f;
-    int tI[NPIX], tG[NPIX];   // Ival; ix in the low, iy in the high half
+#define PAGK_LK_FLOW 0
+#include "pagk_lk_body.h"
+#undef PAGK_LK_FLOW
+}
 
-    for (int l = a.top; l >= 0; l--) {
-        const LkLevel &L = a.lv[l];
-        const float sc = __int_as_float((127 - l) << 23);   // 2^-l
-        const float px = rx * sc - half, py = ry * sc - half;
-        if (l == a.top)
-            nx = rx * sc, ny = ry * sc;
-        else
-            nx = 2.f * nx, ny = 2.f * ny;
-        const float fx = floorf(px), fy = floorf(py);
-        if (lk_out_of_range(fx, fy, win, L.w, L.h)) {
-            if (l == 0) st = 0, e = 0.f, lost_range = 1;
-            continue;
-        }
-        const int ipx = (int)fx, ipy = (int)fy;
-        int w00, w01, w10, w11;
-        lk_weights(px - fx, py - fy, w00, w01, w10, w11);
-        // the template: gray tile from (ipx - 1, ipy - 1), derivatives formed from it
-        lk_tile_handover();   // (the reads of the level above are done)
-        lk_stage(tile, L.I, L.pitch_i, L.w, L.h, ipx - 1, ipy - 1, side_i, lane);
-        lk_tile_handover();
-        int s11 = 0, s12 = 0, s22 = 0;
-#pragma unroll
-        for (int c = 0; c < NPIX; c++) {
-            const int p = lane + 64 * c;
-            tI[c] = 0, tG[c] = 0;
-            if (p < npx) {
-                const int y = (int)(((unsigned)p * magic_win) >> 16), x = p - y * win;
-                int g[4][4];
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) g[r][q] = tile[(y + r) * side_i + x + q];
-                int dxs = 8192, dys = 8192;
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int r = 1 + (t >> 1), q = 1 + (t & 1);   // the tap's centre in g
-                    const int gx = ipx + x + (t & 1), gy = ipy + y + (t >> 1);
-                    const int wt = t == 0 ? w00 : (t == 1 ? w01 : (t == 2 ? w10 : w11));
-                    int dx = 3 * (g[r - 1][q + 1] + g[r + 1][q + 1]) + 10 * g[r][q + 1] -
-                             (3 * (g[r - 1][q - 1] + g[r + 1][q - 1]) + 10 * g[r][q - 1]);
-                    int dy = 3 * ((g[r + 1][q - 1] - g[r - 1][q - 1]) + (g[r + 1][q + 1] - g[r - 1][q + 1])) +
-                             10 * (g[r + 1][q] - g[r - 1][q]);
-                    if (gx < 0 || gx >= L.w || gy < 0 || gy >= L.h) dx = 0, dy = 0;   // the constant border of the derivatives
-                    dxs += dx * wt, dys += dy * wt;
-                }
-                const int ix = dxs >> 14, iy = dys >> 14;
-                tI[c] = (g[1][1] * w00 + g[1][2] * w01 + g[2][1] * w10 + g[2][2] * w11 + 256) >> 9;
-                tG[c] = (int)((unsigned)(ix & 0xffff) | ((unsigned)iy << 16));
-                s11 += ix * ix, s12 += ix * iy, s22 += iy * iy;
-            }
-        }
-        const long long S11 = lk_wave_sum(s11), S12 = lk_wave_sum(s12), S22 = lk_wave_sum(s22);
-        const float A11 = (float)S11 * 0x1p-20f, A12 = (float)S12 * 0x1p-20f, A22 = (float)S22 * 0x1p-20f;
-        float D = A11 * A22 - A12 * A12;
-        const float min_eig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
-        if ((double)min_eig < a.min_eig || D < 0x1p-23f) {   // FLT_EPSILON
-            if (l == 0) st = 0, lost_eig = 1;
-            continue;
-        }
-        D = 1.f / D;
-        float qx = nx - half, qy = ny - half, pdx = 0.f, pdy = 0.f;
-        for (int j = 0; j < a.max_count; j++) {
-            const float gx = floorf(qx), gy = floorf(qy);
-            if (lk_out_of_range(gx, gy, win, L.w, L.h)) {
-                if (l == 0) st = 0, lost_range = 1;
-                break;
-            }
-            lk_weights(qx - gx, qy - gy, w00, w01, w10, w11);
-            lk_tile_handover();   // (the reads of the tile before this one are done)
-            lk_stage(tile, L.J, L.pitch_j, L.w, L.h, (int)gx, (int)gy, side_j, lane);
-            lk_tile_handover();
-            int b1 = 0, b2 = 0;
-#pragma unroll
-            for (int c = 0; c < NPIX; c++) {
-                const int p = lane + 64 * c;
-                if (p < npx) {
-                    const int y = (int)(((unsigned)p * magic_win) >> 16), x = p - y * win;
-                    const int diff = lk_sample(tile, y * side_j + x, side_j, w00, w01, w10, w11) - tI[c];
-                    b1 += diff * (int)(short)(tG[c] & 0xffff), b2 += diff * (tG[c] >> 16);
-                }
-            }
-            const long long B1 = lk_wave_sum(b1), B2 = lk_wave_sum(b2);
-            const float fb1 = (float)B1 * 0x1p-20f, fb2 = (float)B2 * 0x1p-20f;
-            const float ddx = (A12 * fb2 - A22 * fb1) * D, ddy = (A12 * fb1 - A11 * fb2) * D;
-            qx += ddx, qy += ddy;
-            nx = qx + half, ny = qy + half;
-            if ((double)ddx * (double)ddx + (double)ddy * (double)ddy <= a.eps2) break;
-            if (j > 0 && (double)fabsf(ddx + pdx) < 0.01 && (double)fabsf(ddy + pdy) < 0.01) {
-                nx -= ddx * 0.5f, ny -= ddy * 0.5f;
-                break;
-            }
-            pdx = ddx, pdy = ddy;
-        }
-        if (l == 0 && st) {   // step 7
-            const float ex = nx - half, ey = ny - half, gx = floorf(ex), gy = floorf(ey);
-            if (lk_out_of_range(gx, gy, win, L.w, L.h)) {
-                st = 0, lost_range = 1;
-            } else {
-                lk_weights(ex - gx, ey - gy, w00, w01, w10, w11);
-                lk_tile_handover();
-                lk_stage(tile, L.J, L.pitch_j, L.w, L.h, (int)gx, (int)gy, side_j, lane);
-                lk_tile_handover();
-                int es = 0;
-#pragma unroll
-                for (int c = 0; c < NPIX; c++) {
-                    const int p = lane + 64 * c;
-                    if (p < npx) {
-                        const int y = (int)(((unsigned)p * magic_win) >> 16), x = p - y * win;
-                        es += abs(lk_sample(tile, y * side_j + x, side_j, w00, w01, w10, w11) - tI[c]);
-                    }
-                }
-                const long long E = lk_wave_sum(es);
-                e = (float)E / (float)(32 * win * win);
-            }
-        }
-    }
-    if (lane == 0) {
-        const int kept = st && !(e >= a.err_threshold);
-        a.pt_out[2 * k] = nx, a.pt_out[2 * k + 1] = ny;
-        a.err[k] = e;
-        a.status[k] = (uint8_t)kept;
-        if (a.status_raw) a.status_raw[k] = (uint8_t)st;
-        if (a.flow) a.flow[2 * k] = nx - rx, a.flow[2 * k + 1] = ny - ry;
-        if (st) atomicAdd(a.info + 1, 1);
-        if (kept) atomicAdd(a.info + 2, 1);
-        if (lost_eig) atomicAdd(a.info + 4, 1);
-        if (lost_range) atomicAdd(a.info + 5, 1);
-    }
+template <int NPIX>
+__global__ __launch_bounds__(256) void k_lk_flow(LkFlowArgs f)
+{
+    const LkTrackArgs &a = f.t;
+#define PAGK_LK_FLOW 1
+#include "pagk_lk_body.h"
+#undef PAGK_LK_FLOW
 }
 
 }  // namespace pagk

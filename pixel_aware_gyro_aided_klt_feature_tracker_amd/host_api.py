@@ -375,6 +375,15 @@ def lk_track(img_ref, img_cur, pts, lk=None, ctx=None) -> dict:
                                          pts, lk)
 
 
+def lk_track_flow(img_ref, img_cur, pts, lk=None, cam=None, pt_init=None, status_in=None, ctx=None) -> dict:
+    """Lucas-Kanade started from an initial point (OPTFLOW_USE_INITIAL_FLOW, the reference's open experiment at
+    src/gyro_aided_tracker.cpp:364-365) by the library's definition (pagk_lk_track_flow): rows with status_in == 0 are left
+    out, pt_out_dist = DistortVecPoints(pt_out) with the camera of `cam` (a capi.Params) -> the dict of lk_track plus
+    pt_out_dist and `skipped`."""
+    return _device_context(ctx).lk_track_flow(np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8),
+                                              pts, lk, cam, pt_init, status_in)
+
+
 # ---- track-to-detection association (src/gyro_aided_tracker.cpp:859-939, :1017-1136), array in, array out ----
 def search_by_gyro_predict(img_ref, img_cur, half_patch, keys_ref, pt_predict_un, status, affine, keys_cur, keys_cur_un,
                            assoc=None, radius_unit=None, cap=64, ctx=None) -> dict:

@@ -744,3 +744,49 @@ class SequenceTracker:
         self.main.synchronize()
         self.side.synchronize()
         self.ctx.check_launch()
+
+
+
+class DeviceSequence:
+    """The frame loop behind the C ABI (pagk_sequence_*, reference Examples/Demo/RealSenseD435i.cpp:199-321) on numpy arrays:
+    the context owns the key sets, the work arrays, the pinned input ring and the two per-parity graphs, so this class keeps
+    nothing but the context.  `sp` is a capi.SequenceParams (capi.sequence_params_default(...)): tracker PatchMatch,
+    Lucas-Kanade or gyro-started Lucas-Kanade; detector 0 (the caller's candidate lists), 1 (Harris) or 2 (FAST).
+    SequenceTracker is the same loop for a Python host that keeps its results on the device."""
+
+    def __init__(self, sp: "capi.SequenceParams", device: int = 0, ctx: "capi.Context | None" = None):
+        self._own = ctx is None
+        self.ctx = capi.Context(device) if ctx is None else ctx
+        self.sp = sp
+        try:
+            self.ctx.sequence_create(sp)
+        except Exception:
+            if self._own:
+                self.ctx.close()
+            raise
+        self._open = True
+
+    def start(self, frame, candidates=None):
+        self.ctx.sequence_start(np.ascontiguousarray(frame, np.uint8), candidates)
+
+    def step(self, frame, rot9=None, candidates=None, mode: str = "graph"):
+        if mode not in ("graph", "direct"):
+            raise ValueError(mode)
+        self.ctx.sequence_step(np.ascontiguousarray(frame, np.uint8), rot9, candidates,
+                               capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT)
+
+    def read(self, cap: "int | None" = None) -> dict:
+        return self.ctx.sequence_read(int(self.sp.cap if cap is None else cap))
+
+    def read_pair(self, cap: "int | None" = None) -> dict:
+        return self.ctx.sequence_read_pair(int(self.sp.cap if cap is None else cap))
+
+    def status(self) -> dict:
+        return self.ctx.sequence_status()
+
+    def close(self):
+        if self._open:
+            self._open = False
+            self.ctx.sequence_destroy()
+            if self._own:
+                self.ctx.close()

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Frame time of the sequence the context owns (pagk_sequence_*, runtime.DeviceSequence) for its three arms -- PatchMatch,
+Lucas-Kanade, Lucas-Kanade started from the gyro prediction -- against runtime.SequenceTracker in the same process, on
+synth.config(1)-sized frames (752 x 480, 1000 keypoints).
+
+Method: a rotating sequence of 9 frames is run once through every loop and the PatchMatch arm's key sets and state words
+are compared with SequenceTracker's, byte for byte, before anything is reported (a mismatch is exit code 20).  Then every
+loop steps through the frames again and again in graph mode; a window is `steps` steps between two host clock readings with
+a synchronisation at both ends (the step calls themselves synchronise nothing), the loops take turns window by window, and
+the figure is the median of seven windows with their minimum and maximum.  The process runs under a time limit of its own
+(--limit seconds, a watchdog thread ends it with exit code 124).
+
+    python tools/sequence_time.py --out profiles/sequence_time.json
+"""
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+W, H, N, NF = 752, 480, 1000, 9
+CAP, RATIO = 1024, 0.8
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--limit", type=float, default=240.0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    threading.Timer(a.limit, lambda: os._exit(124)).start()
+
+    import torch
+    import handover_ref_util as hu
+    from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, runtime, synth
+    if not torch.cuda.is_available():
+        print("no HIP device: nothing is measured", file=sys.stderr)
+        os._exit(3)
+    cam, imgs, Rs, KRKs, rot9, rng = hu.rotating_sequence(synth, NF, W, H, 0x5EED0B20, (0.004, -0.005, 0.006))
+    u = rng.uniform(2 * 4 * N)
+    cand = np.stack([8 + u[0::2] * (W - 16), 8 + u[1::2] * (H - 16)], axis=1).astype(np.float32)
+    cands = [np.roll(cand, 97 * k, axis=0) for k in range(NF)]
+    p = capi.make_params(half_patch=10, iterations=30, pyramids=3, has_gyro=True, camera=cam)
+    fitp = capi.fit_params_default(seed=0x5EED0F17)
+
+    def sp(tracker, flow):
+        return capi.sequence_params_default(track=p, lk=capi.lk_params_default(), fit=fitp, tracker=tracker, lk_initial_flow=flow,
+                                            width=W, height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0,
+                                            cand_cap=len(cand), validate=1, sigma=1.0)
+    arms = {"sequence PatchMatch": sp(capi.SEQ_PATCHMATCH, 0), "sequence LK": sp(capi.SEQ_LK, 0),
+            "sequence LK gyro-started": sp(capi.SEQ_LK, 1)}
+
+    # 1. results first
+    st = runtime.SequenceTracker(p, W, H, CAP, N, RATIO, fitp, cand_cap=len(cand))
+    want = [st.start(imgs[0], cands[0]).to_numpy()]
+    for k in range(1, NF):
+        want.append(st.step(imgs[k], rot9[k - 1], cands[k], mode="graph").to_numpy())
+    st.synchronize()
+    seqs = {name: runtime.DeviceSequence(s) for name, s in arms.items()}
+    kept = {}
+    for name, sq in seqs.items():
+        sq.start(imgs[0], cands[0])
+        got = [sq.read()]
+        for k in range(1, NF):
+            sq.step(imgs[k], rot9[k - 1], cands[k], mode="graph")
+            got.append(sq.read())
+        kept[name] = [int(g["state"][2]) for g in got[1:]]
+        if name == "sequence PatchMatch":
+            for k in range(NF):
+                for key in ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state"):
+                    if np.asarray(got[k][key]).tobytes() != np.asarray(want[k][key]).tobytes():
+                        print(f"frame {k}: {key} differs from SequenceTracker: nothing is reported", file=sys.stderr)
+                        os._exit(20)
+    print("results: the PatchMatch arm equals SequenceTracker on all", NF, "frames; survivors per frame:", kept)
+
+    # 2. windows taking turns (frame k of a window is frame 1 + k mod (NF - 1): both parities, every graph replayed)
+    def window(step, sync):
+        sync()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            k = 1 + i % (NF - 1)
+            step(k)
+        sync()
+        return (time.perf_counter() - t0) / a.steps * 1e6
+
+    loops = {"SequenceTracker": (lambda k: st.step(imgs[k], rot9[k - 1], cands[k], mode="graph", snapshot=False), st.synchronize)}
+    for name, sq in seqs.items():
+        loops[name] = ((lambda k, sq=sq: sq.step(imgs[k], rot9[k - 1], cands[k], mode="graph")), sq.ctx.sync)
+    times = {name: [] for name in loops}
+    for name, (step, sync) in loops.items():
+        window(step, sync)                                     # warm-up
+    for _ in range(a.windows):
+        for name, (step, sync) in loops.items():
+            times[name].append(window(step, sync))
+    res = {"workload": f"{W}x{H}, {N} keypoints, h = 10, {a.steps} steps a window, {a.windows} windows taking turns",
+           "unit": "us per frame (host clock around a window, synchronised at both ends)", "survivors_per_frame": kept, "loops": {}}
+    for name, v in times.items():
+        res["loops"][name] = dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))
+        print(f"{name:28s} {res['loops'][name]['median']:8.1f} us ({res['loops'][name]['min']:.1f} - {res['loops'][name]['max']:.1f})")
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    for sq in seqs.values():
+        sq.close()
+    st.close()
+    os._exit(0)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
