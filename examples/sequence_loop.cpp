@@ -9,6 +9,16 @@
 // (n_cand x 2 floats) | n_frames - 1 rotations (9 floats: rows 0 and 1 of K R K^-1, the third row of R).
 // Prints one line per frame: the hand-over's state words [total reach_flag survivors added rejected].
 // Build: g++ -std=c++17 -I include examples/sequence_loop.cpp -L <pkg> -l:libpagk_hip.so -Wl,-rpath,<pkg>
+//
+//   sequence_loop <dir> <target_n> <cap> --sensor [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]
+//
+// The sensor form: what the demo reads from disk (Examples/Demo/RealSenseD435i.cpp:74-141) goes into the sequence as it is,
+// with no arithmetic in this file.  <dir>/image_file_list.txt and <dir>/imu.txt are read through csrc/host/sequence_io.h
+// (LoadImageList, LoadImu, ImuWindow); image decoding is the application's, so each listed name "<stamp_ns>.png" stands for
+// the headerless raw frame <dir>/<stamp_ns>.raw (src_height rows of src_width x channels bytes).  <dir>/sensor.bin: int32
+// width, height, src_width, src_height, channels, n_cand | float K[9] | dist[4] | Rbc[9] | bias[3] | map_x, map_y (height x
+// width floats each) | one candidate list (n_cand x 2 floats) per frame.  Prints the same state words.
+// Build: add -DPAGK_EXAMPLE_SENSOR -I <pkg>/csrc/host -l:libpagk_tracker.so
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +26,9 @@
 #include <vector>
 
 #include "pagk.h"
+#ifdef PAGK_EXAMPLE_SENSOR
+#include "sequence_io.h"
+#endif
 
 #define CHECK(call)                                                                                        \
     do {                                                                                                   \
@@ -33,10 +46,89 @@ static bool read_n(FILE *f, std::vector<T> &v, size_t n)
     return fread(v.data(), sizeof(T), n, f) == n;
 }
 
+#ifdef PAGK_EXAMPLE_SENSOR
+// :199-321 on a sensor sequence: a raw frame and the IMU samples since the last frame in, the next pair's keypoints out
+static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode)
+{
+    pagk_ctx *ctx = nullptr;
+    std::vector<std::pair<double, std::string>> frames;
+    std::vector<IMU::Point> imu;
+    if (!pagk_seq::LoadImageList(dir + "/image_file_list.txt", frames) || !pagk_seq::LoadImu(dir + "/imu.txt", imu) || frames.empty())
+        return fprintf(stderr, "cannot read image_file_list.txt / imu.txt in %s\n", dir.c_str()), 1;
+    FILE *f = fopen((dir + "/sensor.bin").c_str(), "rb");
+    int32_t hdr[6];
+    std::vector<float> K, dist, Rbc, bias, map_x, map_y;
+    if (!f || fread(hdr, 4, 6, f) != 6 || !read_n(f, K, 9) || !read_n(f, dist, 4) || !read_n(f, Rbc, 9) || !read_n(f, bias, 3))
+        return fprintf(stderr, "cannot read sensor.bin\n"), 1;
+    const int w = hdr[0], h = hdr[1], ws = hdr[2], hs = hdr[3], cn = hdr[4], nc = hdr[5], nf = (int)frames.size();
+    std::vector<std::vector<float>> cand(nf);
+    bool ok = read_n(f, map_x, (size_t)w * h) && read_n(f, map_y, (size_t)w * h);
+    for (int k = 0; ok && k < nf; k++) ok = read_n(f, cand[k], (size_t)nc * 2);
+    fclose(f);
+    if (!ok) return fprintf(stderr, "sensor.bin is short\n"), 1;
+    sp.track.half_patch = 5, sp.track.iterations = 10, sp.track.pyramids = 3, sp.track.has_gyro_predict_initial = 1;
+    sp.track.fx = K[0], sp.track.fy = K[4], sp.track.cx = K[2], sp.track.cy = K[5];
+    for (int i = 0; i < 4; i++) sp.track.dist_coef[i] = dist[i];
+    sp.track.n_dist_coef = 4;
+    sp.lk.half_patch = 5;
+    sp.width = w, sp.height = h, sp.new_point_threshold = 0.8 * sp.target_n;
+    sp.cand_cap = nc > 0 ? nc : 1;
+    pagk_sequence_sensor ss;
+    pagk_sequence_sensor_default(&ss);
+    ss.rectify.channels = cn, ss.raw = 1, ss.src_width = ws, ss.src_height = hs;
+    memcpy(ss.Rbc, Rbc.data(), sizeof ss.Rbc);
+    if (pagk_sequence_params_check(&sp) != PAGK_OK || pagk_sequence_sensor_check(&ss) != PAGK_OK)
+        return fprintf(stderr, "the parameters are refused\n"), 1;
+    int rc = pagk_create(&ctx, 0);
+    if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
+    CHECK(pagk_rectify_set_maps(ctx, map_x.data(), map_y.data(), w, h, (int64_t)w * 4));
+    CHECK(pagk_sequence_create_sensor(ctx, &sp, &ss));
+    const bool list = sp.detector == 0;
+    pagk_seq::ImuWindow windows(imu);
+    std::vector<uint8_t> raw((size_t)ws * hs * cn);
+    std::vector<float> keys_un((size_t)sp.cap * 2);
+    std::vector<double> t;
+    std::vector<float> rates;
+    int32_t state[PAGK_HANDOVER_STATE_WORDS];
+    double t_prev = 0;
+    for (int k = 0; k < nf; k++) {
+        std::string name = frames[k].second;
+        const size_t slash = name.rfind('/'), dot = name.rfind(".png");
+        name = dir + "/" + name.substr(slash == std::string::npos ? 0 : slash + 1, dot - (slash == std::string::npos ? 0 : slash + 1)) + ".raw";
+        FILE *fi = fopen(name.c_str(), "rb");
+        if (!fi || fread(raw.data(), 1, raw.size(), fi) != raw.size()) return fprintf(stderr, "cannot read %s\n", name.c_str()), 1;
+        fclose(fi);
+        const pagk_image frame = {raw.data(), ws, hs, (int64_t)ws * cn};
+        const float *c = list ? cand[k].data() : nullptr;
+        const std::vector<IMU::Point> samples = windows.Next(t_prev, frames[k].first);   // :207-218
+        if (k == 0) {
+            CHECK(pagk_sequence_start_sensor(ctx, &frame, frames[k].first, c, list ? nc : 0));
+        } else {
+            t.clear(), rates.clear();
+            for (const IMU::Point &s : samples) {
+                t.push_back(s.t);
+                rates.push_back(s.w.x), rates.push_back(s.w.y), rates.push_back(s.w.z);
+            }
+            const pagk_imu_window win = {t_prev, frames[k].first, (int32_t)samples.size(), t.data(), rates.data(), {bias[0], bias[1], bias[2]}};
+            CHECK(pagk_sequence_step_sensor(ctx, &frame, &win, c, list ? nc : 0, mode));
+        }
+        t_prev = frames[k].first;
+        CHECK(pagk_sequence_read(ctx, sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr));
+        printf("frame %d: %d %d %d %d %d\n", k, state[0], state[1], state[2], state[3], state[4]);
+    }
+    int32_t words[PAGK_SEQ_STATUS_WORDS];
+    CHECK(pagk_sequence_status(ctx, words));
+    fprintf(stderr, "%d frames, %d graphs\n", words[0], words[2]);
+    CHECK(pagk_sequence_destroy(ctx));
+    pagk_destroy(ctx);
+    return 0;
+}
+#endif
+
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s seq.bin target_n cap [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
+        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
         return 1;
     }
     pagk_ctx *ctx = nullptr;
@@ -44,6 +136,7 @@ int main(int argc, char **argv)
     pagk_sequence_params_default(&sp);
     sp.target_n = atoi(argv[2]), sp.cap = atoi(argv[3]);
     int mode = PAGK_SEQ_GRAPH;
+    bool sensor = false;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lk") sp.tracker = PAGK_SEQ_LK, sp.lk_initial_flow = 0;
@@ -51,7 +144,15 @@ int main(int argc, char **argv)
         else if (a == "--detect") sp.detector = 1;
         else if (a == "--detect-fast") sp.detector = 2;
         else if (a == "--direct") mode = PAGK_SEQ_DIRECT;
+        else if (a == "--sensor") sensor = true;
         else return fprintf(stderr, "unknown flag %s\n", argv[i]), 1;
+    }
+    if (sensor) {
+#ifdef PAGK_EXAMPLE_SENSOR
+        return sensor_loop(argv[1], sp, mode);
+#else
+        return fprintf(stderr, "--sensor: build with -DPAGK_EXAMPLE_SENSOR against csrc/host/sequence_io.h and libpagk_tracker.so\n"), 1;
+#endif
     }
     FILE *f = fopen(argv[1], "rb");
     int32_t hdr[4];

@@ -1568,6 +1568,56 @@ int pagk_track_sharded(pagk_multi *pm, const pagk_params *params, const pagk_ima
                        int32_t n, const float *pt_ref_un, const float *pt_init_un, const float *affine,
                        const uint8_t *status_in, const pagk_outputs *out);
 
+/* ---- Gyro integration: the IMU window of a frame pair -> Rcl and K Rcl K^-1 ------------------------------------------- */
+/* GyroAidedTracker::IntegrateGyroMeasurements, IntegrateOneGyroMeasurement and SetRcl (src/gyro_aided_tracker.cpp:511-587)
+ * turn the gyroscope samples between two frames into the rotation Rcl and into K Rcl K^-1.  Parity contract: parity with
+ * OpenCV's MatExpr evaluation and with a C library's sin / cos is NOT claimed (neither can be pinned here); the contract is
+ * this definition, bit for bit, restated in plain C in tests/gyro_integrate_ref.c.  It follows the reference's expressions
+ * step by step; f32 and f64 operations round once each (no contraction).
+ *   window     samples (t_i, w_i), i = 0 .. samples - 1: f64 time stamps, f32 rates in rad/s; t_ref and t_cur are the two
+ *              frames' time stamps, bias the gyroscope bias.  n = samples - 1 steps; 0 or 1 samples give dR = I.
+ *   time steps every time difference is the f64 difference of two time stamps, rounded once to f32 (tab, tini, tend, tstep).
+ *   step i     (:530-555, the four cases in the reference's order; w0 = w_i, w1 = w_(i+1), per component in f32)
+ *              i == 0 and i < n - 1:  tab = t1 - t0, tini = t0 - t_ref, angVel = ((w0 + w1) - (w1 - w0) * (tini / tab)) * 0.5f,
+ *                                     tstep = t1 - t_ref
+ *              else i < n - 1:        angVel = (w0 + w1) * 0.5f, tstep = t1 - t0
+ *              else i > 0 (the last): tab = t1 - t0, tend = t1 - t_cur, angVel = ((w0 + w1) - (w1 - w0) * (tend / tab)) * 0.5f,
+ *                                     tstep = t_cur - t0
+ *              else (n == 1):         angVel = w0, tstep = t_cur - t_ref
+ *   deltaR     (IntegrateOneGyroMeasurement, :564-587) x = (float)((double)(angVel.x - bias.x) * (double)tstep), y and z alike;
+ *              d2 = x * x + y * y + z * z in f32, left to right; d = sqrtf(d2), correctly rounded; W = the skew matrix
+ *              0 -z y / z 0 -x / -y x 0.  If (double)d < 1e-4: R = I + W in f32.  Otherwise WW = W * W (a product as below),
+ *              s = (double)(float)sin, c = (double)(1.0f - (float)cos) -- the reference's std::sin(float) and
+ *              std::cos(float) return float, so each result is rounded once to f32, and 1.0f - cos is an f32 difference --
+ *              with sin and cos the f64 ALGORITHM of the ORB "steering" paragraph above applied to (double)d (no library
+ *              sin or cos is called; its k = (int)v saturates at 2147483647), and
+ *              R[k] = (float)(((double)I[k] + (double)W[k] * s / (double)d) + (double)WW[k] * c / (double)d2).
+ *   products   every 3 x 3 product: f32 factors, an f64 accumulator starting at 0, k ascending, one rounding to f32.
+ *              dR = dR * deltaR_i for i = 0 .. n - 1, left to right from dR = I; Rcl = (Rbc^T * dR^T) * Rbc (:560);
+ *              KRKinv = (K * Rcl) * inv3(K) (:518) with K = fx 0 cx / 0 fy cy / 0 0 1 and inv3 the f64 cofactor inverse:
+ *              det expanded along the first row, each cofactor times (det != 0 ? 1 / det : 0), rounded once to f32.
+ *   output     Rcl (9 floats, row-major) and rot9: rows 0 and 1 of KRKinv followed by the third row of Rcl, exactly what
+ *              pagk_gyro_predict_device_rot reads.
+ * A window is refused on the host with PAGK_E_ARG and never reaches the device when it has more than imu_cap samples, a
+ * non-finite time, rate or bias, sample times that do not increase strictly, or t_cur <= t_ref. */
+#define PAGK_IMU_MAX_SAMPLES 64
+typedef struct pagk_imu_window {
+    double t_ref, t_cur; /* mTimeStampRef, mTimeStamp: the two frames' time stamps, t_cur > t_ref */
+    int32_t n;           /* samples (mvImuFromLastFrame.size()), 0 .. imu_cap                    */
+    const double *t;     /* host: n time stamps, strictly increasing                             */
+    const float *w;      /* host: n x 3 angular rates, rad/s                                     */
+    float bias[3];       /* mBias                                                                */
+} pagk_imu_window;
+/* The window checks above (src/gyro_aided_tracker.cpp:521-562 makes none): PAGK_OK, or PAGK_E_ARG for NULL, imu_cap outside
+ * 1 .. PAGK_IMU_MAX_SAMPLES, or a window the list above refuses.  Needs no device. */
+int pagk_imu_window_check(const pagk_imu_window *window, int32_t imu_cap);
+/* The definition above on the device (src/gyro_aided_tracker.cpp:511-587; one launch of one wavefront, csrc/pagk_gyro_kernel.h),
+ * host buffers, synchronous: Rbc = the top-left 3 x 3 of Tbc, row-major; camera: fx, fy, cx, cy are read; Rcl and rot9: 9
+ * floats each, either may be NULL.  PAGK_E_ARG for a window the check refuses (imu_cap = PAGK_IMU_MAX_SAMPLES) and inside a
+ * capture. */
+int pagk_gyro_integrate(pagk_ctx *ctx, const float Rbc[9], const pagk_params *camera, const pagk_imu_window *window,
+                        float *Rcl, float *rot9);
+
 /* ---- The sequence the context owns: the frame loop behind the C ABI --------------------------------------------------- */
 /* The reference's main loop (Examples/Demo/RealSenseD435i.cpp:199-321: grab a frame and the gyro rotation, track, hand the
  * result over to the next pair) with everything between two frames on the device and every buffer owned by the context:
@@ -1589,8 +1639,9 @@ int pagk_track_sharded(pagk_multi *pm, const pagk_params *params, const pagk_ima
  * that parity is captured, and later steps replay one of the two graphs; the context stream must then not be the legacy
  * default stream (pagk_graph_begin).  Every sequence call returns PAGK_E_ARG between pagk_graph_begin and pagk_graph_end.
  * After pagk_selftest_fill_workspaces a sequence is invalid until the next pagk_sequence_start, as frame slots are.
- * Out of scope: raw-frame rectification inside the sequence, k cameras batched, sharding, tracker type GYRO_PREDICT, the
- * C++ shell classes, mvFlowVelocityInNormalPlane. */
+ * Out of scope: raw-frame rectification, gyro integration and mvFlowVelocityInNormalPlane in a sequence made by
+ * pagk_sequence_create (they are what "The sensor form of the sequence" below adds); in both forms: k cameras batched,
+ * sharding, tracker type GYRO_PREDICT, the C++ shell classes. */
 #define PAGK_SEQ_PATCHMATCH 0
 #define PAGK_SEQ_LK 1
 #define PAGK_SEQ_GRAPH 0
@@ -1655,6 +1706,57 @@ int pagk_sequence_read_pair(pagk_ctx *ctx, int32_t cap, uint8_t *status, float *
 /* Host-side words, nothing synchronised (Examples/Demo/RealSenseD435i.cpp:199-321 has no counterpart), PAGK_SEQ_STATUS_WORDS
  * int32: [0] frames handed in, [1] 1 if the last step was a graph replay, [2] graphs held, [3] 0. */
 int pagk_sequence_status(pagk_ctx *ctx, int32_t *words);
+
+/* ---- The sensor form of the sequence: raw frames and the IMU window in, tracked features out --------------------------- */
+/* What a camera and an IMU deliver, instead of a rectified gray frame and nine rotation floats: both front-ends of the
+ * reference remap every frame (Examples/Demo/RealSenseD435i.cpp:202), convert it to gray (src/frame.cpp:81-87) and integrate
+ * the gyroscope samples between two frames (src/gyro_aided_tracker.cpp:511-587).  A sensor sequence does the three inside
+ * the step.  The raw frame's rows, the window (times, rates, bias, t_ref, t_cur, n) and the candidates go into the pinned
+ * ring block and with one asynchronous copy into the fixed input block; the issue order behind it is: rectification into
+ * the parity's frame slot and its pyramid ("Rectification" above; Lucas-Kanade reads the rectified level 0 of the slot),
+ * k_gyro_integrate ("Gyro integration" above) writing the nine floats the prediction reads, the chain of the chosen tracker
+ * as for a plain sequence, then k_flow_velocity.  Graph mode follows the plain sequence's rule; so does everything the plain
+ * section says about captures and pagk_selftest_fill_workspaces.  pagk_sequence_read, pagk_sequence_read_pair,
+ * pagk_sequence_status and pagk_sequence_destroy serve both kinds; pagk_sequence_start and pagk_sequence_step return
+ * PAGK_E_ARG on a sensor sequence, the _sensor calls on a plain one.  The results are those of a plain sequence fed the
+ * rectified frames (pagk_rectify) and the rot9 of the window (pagk_gyro_integrate), bit for bit.
+ *   flow velocity  (mvFlowVelocityInNormalPlane, src/frame.cpp:139-143) row j of the new key set with i = index_in_last[j] >= 0:
+ *                  ((keys_normal_cur[j] - keys_normal_last[i]) in f32) / (t_cur - t_last), the divisor the f64 difference of
+ *                  the two time stamps, the division as OpenCV's Point2f / double: an f64 quotient rounded once to f32.
+ *                  Rows with index_in_last < 0 and rows at or beyond the live count get (0, 0); so does every row of the
+ *                  first frame.  The reference indexes this vector by the compacted count (:143): that is row j. */
+typedef struct pagk_sequence_sensor {
+    pagk_rectify_params rectify; /* raw = 1: the gray step of the raw frames; raw = 0: channels must be 1        */
+    int32_t raw;                 /* 0: frames arrive gray, at the sequence's size; 1: raw, through the context's maps */
+    int32_t src_width, src_height; /* raw = 1: the size of a raw frame, 1 .. 32767 each                           */
+    int32_t imu_cap;             /* the longest window, 1 .. PAGK_IMU_MAX_SAMPLES                                 */
+    float Rbc[9];                /* the top-left 3 x 3 of Tbc (mRbc), row-major                                   */
+    int32_t flow_velocity;       /* 0 or 1: mvFlowVelocityInNormalPlane behind the hand-over                      */
+} pagk_sequence_sensor;
+/* pagk_rectify_params_default, frames that arrive gray, imu_cap PAGK_IMU_MAX_SAMPLES, Rbc = I, flow_velocity 1
+ * (src/frame.cpp:139-143 always computes it). */
+void pagk_sequence_sensor_default(pagk_sequence_sensor *s);
+/* PAGK_OK if pagk_sequence_create_sensor accepts *s (Examples/Demo/RealSenseD435i.cpp:199-321): the rectify block passes
+ * its check; raw, flow_velocity in {0, 1}; the sizes and imu_cap in the ranges above; Rbc finite.  PAGK_E_ARG otherwise or for
+ * NULL.  Needs no device. */
+int pagk_sequence_sensor_check(const pagk_sequence_sensor *s);
+/* pagk_sequence_create for a sensor sequence (Examples/Demo/RealSenseD435i.cpp:199-321): the same block with the window in
+ * the input block and the sensor parts (rot9, Rcl, velocities) behind it; a plain sequence's layout does not change.  With
+ * raw = 1 the maps must have been set (pagk_rectify_set_maps) with the sequence's width x height: PAGK_E_ARG otherwise, with
+ * a text in pagk_last_error. */
+int pagk_sequence_create_sensor(pagk_ctx *ctx, const pagk_sequence_params *params, const pagk_sequence_sensor *sensor);
+/* pagk_sequence_start for a sensor sequence (Examples/Demo/RealSenseD435i.cpp:221-235).  raw: a host image; with raw = 1
+ * width and height are the raw frame's, in pixels of `channels` bytes, and step >= width * channels.  t: the frame's time
+ * stamp, finite. */
+int pagk_sequence_start_sensor(pagk_ctx *ctx, const pagk_image *raw, double t, const float *cand, int32_t n_cand);
+/* pagk_sequence_step for a sensor sequence (Examples/Demo/RealSenseD435i.cpp:237-321).  window: the samples between the
+ * previous frame and this one; PAGK_E_ARG, with nothing enqueued, for a window pagk_imu_window_check refuses with the
+ * sequence's imu_cap and for a t_ref that is not the previous frame's time (t of the start, t_cur of the last step). */
+int pagk_sequence_step_sensor(pagk_ctx *ctx, const pagk_image *raw, const pagk_imu_window *window, const float *cand,
+                              int32_t n_cand, int32_t mode);
+/* The flow velocities of the current key set (src/frame.cpp:139-143), synchronous: the first `cap` rows x 2 floats.
+ * PAGK_E_ARG on a plain sequence, with flow_velocity = 0, or before pagk_sequence_start_sensor. */
+int pagk_sequence_read_velocity(pagk_ctx *ctx, int32_t cap, float *v);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,19 @@ class SequenceParams(C.Structure):
                 ("detector", C.c_int32), ("cand_cap", C.c_int32), ("validate", C.c_int32), ("sigma", C.c_float)]
 
 
+class ImuWindow(C.Structure):
+    """pagk_imu_window (include/pagk.h "Gyro integration"): the gyroscope samples between two frames."""
+    _fields_ = [("t_ref", C.c_double), ("t_cur", C.c_double), ("n", C.c_int32), ("t", C.c_void_p), ("w", C.c_void_p),
+                ("bias", C.c_float * 3)]
+
+
+class SequenceSensor(C.Structure):
+    """pagk_sequence_sensor (include/pagk.h): what a sensor sequence adds to pagk_sequence_params."""
+    _fields_ = [("rectify", RectifyParams), ("raw", C.c_int32), ("src_width", C.c_int32), ("src_height", C.c_int32),
+                ("imu_cap", C.c_int32), ("Rbc", C.c_float * 9), ("flow_velocity", C.c_int32)]
+
+
+IMU_MAX_SAMPLES = 64
 SEQ_PATCHMATCH, SEQ_LK = 0, 1
 SEQ_GRAPH, SEQ_DIRECT = 0, 1
 SEQ_STATUS_WORDS = 4
@@ -405,6 +418,17 @@ def declare(lib) -> None:
                            ("pagk_sequence_read_pair", [vp, i32, vp, vp, vp, vp]), ("pagk_sequence_status", [vp, vp])):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_sequence_create_sensor"):
+        sp, ss, iw = _P(SequenceParams), _P(SequenceSensor), _P(ImuWindow)
+        lib.pagk_sequence_sensor_default.restype = None
+        lib.pagk_sequence_sensor_default.argtypes = [ss]
+        for name, args in (("pagk_sequence_sensor_check", [ss]), ("pagk_sequence_create_sensor", [vp, sp, ss]),
+                           ("pagk_sequence_start_sensor", [vp, _P(Image), C.c_double, vp, i32]),
+                           ("pagk_sequence_step_sensor", [vp, _P(Image), iw, vp, i32, i32]),
+                           ("pagk_sequence_read_velocity", [vp, i32, vp]), ("pagk_imu_window_check", [iw, i32]),
+                           ("pagk_gyro_integrate", [vp, vp, _P(Params), iw, vp, vp])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
     if hasattr(lib, "pagk_lk_track_flow"):
         lib.pagk_lk_track_flow.restype = C.c_int
         lib.pagk_lk_track_flow.argtypes = [vp, _P(LkParams), _P(Params), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp,
@@ -579,6 +603,8 @@ EXPORTED_SYMBOLS = [
     "pagk_lk_track", "pagk_selftest_lk_level", "pagk_lk_track_flow",
     "pagk_sequence_params_default", "pagk_sequence_params_check", "pagk_sequence_create", "pagk_sequence_destroy",
     "pagk_sequence_start", "pagk_sequence_step", "pagk_sequence_read", "pagk_sequence_read_pair", "pagk_sequence_status",
+    "pagk_imu_window_check", "pagk_gyro_integrate", "pagk_sequence_sensor_default", "pagk_sequence_sensor_check",
+    "pagk_sequence_create_sensor", "pagk_sequence_start_sensor", "pagk_sequence_step_sensor", "pagk_sequence_read_velocity",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
@@ -747,6 +773,41 @@ def sequence_params_default(**overrides) -> SequenceParams:
 def sequence_params_check(p: SequenceParams) -> int:
     """pagk_sequence_params_check: PAGK_OK, or the code pagk_sequence_create refuses these parameters with (needs no device)."""
     return int(load().pagk_sequence_params_check(C.byref(p)))
+
+
+def sequence_sensor_default(**overrides) -> SequenceSensor:
+    """pagk_sequence_sensor_default() with overrides (rectify as a RectifyParams, Rbc as nine numbers, the scalars)."""
+    s = SequenceSensor()
+    load().pagk_sequence_sensor_default(C.byref(s))
+    for k, v in overrides.items():
+        if k not in dict(SequenceSensor._fields_):
+            raise TypeError(f"pagk_sequence_sensor has no field {k}")
+        if k == "Rbc":
+            v = (C.c_float * 9)(*[float(x) for x in np.asarray(v, np.float32).reshape(9)])
+        setattr(s, k, v)
+    return s
+
+
+def sequence_sensor_check(s: SequenceSensor) -> int:
+    """pagk_sequence_sensor_check: PAGK_OK or PAGK_E_ARG (needs no device)."""
+    return int(load().pagk_sequence_sensor_check(C.byref(s)))
+
+
+def imu_window(t_ref: float, t_cur: float, t, w, bias=(0.0, 0.0, 0.0)):
+    """A pagk_imu_window over host arrays: t (n doubles), w (n x 3 floats, rad/s).  Returns (window, keep): `keep` holds the
+    arrays the window points into and must live as long as the window is used."""
+    tt = np.ascontiguousarray(t, np.float64).reshape(-1)
+    ww = np.ascontiguousarray(w, np.float32).reshape(-1, 3)
+    if ww.shape[0] != tt.shape[0]:
+        raise ValueError("one rate per time stamp")
+    win = ImuWindow(float(t_ref), float(t_cur), int(tt.shape[0]), tt.ctypes.data if tt.size else None,
+                    ww.ctypes.data if ww.size else None, (C.c_float * 3)(*[float(b) for b in bias]))
+    return win, (tt, ww)
+
+
+def imu_window_check(win: ImuWindow, imu_cap: int = IMU_MAX_SAMPLES) -> int:
+    """pagk_imu_window_check: PAGK_OK or PAGK_E_ARG (needs no device)."""
+    return int(load().pagk_imu_window_check(C.byref(win), int(imu_cap)))
 
 
 def lk_params_check(p: LkParams) -> int:
@@ -1713,6 +1774,46 @@ class Context:
         w = np.zeros(SEQ_STATUS_WORDS, np.int32)
         self._check(self.lib.pagk_sequence_status(self.h, _ptr(w)), "pagk_sequence_status")
         return dict(frames=int(w[0]), last_was_graph=bool(w[1]), graphs=int(w[2]))
+
+    # the sensor form of the sequence and the gyro integration (src/gyro_aided_tracker.cpp:511-587) ------------------------
+    def gyro_integrate(self, Rbc, camera: Params, window: ImuWindow):
+        """pagk_gyro_integrate -> (Rcl (3 x 3), rot9): the window's rotation by k_gyro_integrate."""
+        rbc = np.ascontiguousarray(Rbc, np.float32).reshape(9)
+        rcl, rot9 = np.zeros(9, np.float32), np.zeros(9, np.float32)
+        self._check(self.lib.pagk_gyro_integrate(self.h, _ptr(rbc), C.byref(camera), C.byref(window), _ptr(rcl), _ptr(rot9)),
+                    "pagk_gyro_integrate")
+        return rcl.reshape(3, 3), rot9
+
+    def sequence_create_sensor(self, sp: SequenceParams, sensor: SequenceSensor):
+        """pagk_sequence_create_sensor: a sequence fed raw frames and IMU windows."""
+        self._check(self.lib.pagk_sequence_create_sensor(self.h, C.byref(sp), C.byref(sensor)), "pagk_sequence_create_sensor")
+        self._seq_params = sp
+
+    @staticmethod
+    def _raw_view(frame: np.ndarray) -> Image:
+        """height x width (x channels) bytes, rows possibly padded: width and height in pixels, step in bytes"""
+        assert frame.dtype == np.uint8 and frame.ndim in (2, 3) and frame.strides[-1] == 1
+        assert frame.ndim == 2 or frame.strides[1] == frame.shape[2]
+        return Image(frame.ctypes.data, frame.shape[1], frame.shape[0], frame.strides[0])
+
+    def sequence_start_sensor(self, raw: np.ndarray, t: float, candidates=None):
+        """pagk_sequence_start_sensor: the first raw frame and its time stamp."""
+        iv = self._raw_view(raw)
+        keep, ptr, n = self._seq_cand(candidates)
+        self._check(self.lib.pagk_sequence_start_sensor(self.h, C.byref(iv), float(t), ptr, n), "pagk_sequence_start_sensor")
+
+    def sequence_step_sensor(self, raw: np.ndarray, window: ImuWindow, candidates=None, mode: int = SEQ_GRAPH):
+        """pagk_sequence_step_sensor: raw frame k >= 1 with the samples since the previous frame; nothing is synchronised."""
+        iv = self._raw_view(raw)
+        keep, ptr, n = self._seq_cand(candidates)
+        self._check(self.lib.pagk_sequence_step_sensor(self.h, C.byref(iv), C.byref(window), ptr, n, int(mode)),
+                    "pagk_sequence_step_sensor")
+
+    def sequence_read_velocity(self, cap: int) -> np.ndarray:
+        """pagk_sequence_read_velocity -> cap x 2 floats: mvFlowVelocityInNormalPlane of the current key set."""
+        v = np.zeros((cap, 2), np.float32)
+        self._check(self.lib.pagk_sequence_read_velocity(self.h, cap, _ptr(v)), "pagk_sequence_read_velocity")
+        return v
 
     def selftest_lk_level(self, slot: int, level: int, width: int, height: int, pitch: int | None = None) -> np.ndarray:
         """pagk_selftest_lk_level: level `level` (>= 1) of the slot's Lucas-Kanade pyramid, height x width."""

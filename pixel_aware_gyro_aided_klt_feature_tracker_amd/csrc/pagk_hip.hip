@@ -19,6 +19,7 @@
 #include "pagk_associate_kernel.h"
 #include "pagk_pose_kernel.h"
 #include "pagk_orb_levels_kernel.h"
+#include "pagk_gyro_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
@@ -78,6 +79,15 @@ struct SeqState {
     int turn = 0, frames = 0;
     bool started = false, stepped = false, last_graph = false, direct_done[2] = {};
     int graph[2] = {-1, -1};
+    // the sensor form (pagk_sequence_create_sensor): raw frames and the IMU window are parts of the input block
+    bool sensor = false;
+    pagk_sequence_sensor s = {};
+    size_t row_bytes = 0;         // bytes of a frame row in the input block (raw: src_width * channels), and ...
+    int rows = 0;                 // ... its rows
+    size_t off_win = 0;           // the window in the input block (kImuWindowBytes)
+    const float *rot = nullptr;   // what the prediction reads: the caller's nine floats in the input block, or k_gyro_integrate's
+    float *rot_out = nullptr, *rcl = nullptr, *vel = nullptr;   // sensor parts: rot9 | Rcl, the flow velocities
+    double t_last = 0.0;          // the previous frame's time
 };
 
 }  // namespace
@@ -5113,15 +5123,26 @@ namespace {
 constexpr int kSeqParts = 34;
 
 // This frame's inputs into the next pinned block, then one asynchronous copy into the fixed device block.
-int seq_feed(pagk_ctx *ctx, SeqState &q, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand)
+// (a sensor sequence: the frame's rows as they arrive, and the IMU window -- `win`, or for the first frame t_ref = t_cur = t0
+// and no sample)
+int seq_feed(pagk_ctx *ctx, SeqState &q, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand,
+             const pagk_imu_window *win = nullptr, double t0 = 0.0)
 {
     const int k = q.turn;
     q.turn = (k + 1) % SeqState::kRing;
     if (q.recorded[k]) HIPCHK(ctx, hipEventSynchronize(q.read_done[k]));   // flow control only: the copy four frames ago
     uint8_t *pin = static_cast<uint8_t *>(q.pinned[k]);
-    for (int y = 0; y < q.p.height; y++)
-        memcpy(pin + (size_t)y * q.p.width, frame->data + (int64_t)y * frame->step, (size_t)q.p.width);
+    for (int y = 0; y < q.rows; y++)
+        memcpy(pin + (size_t)y * q.row_bytes, frame->data + (int64_t)y * frame->step, q.row_bytes);
     if (rot9) memcpy(pin + q.off_rot, rot9, 9 * sizeof(float));
+    if (q.sensor) {
+        uint8_t *w = pin + q.off_win;
+        const double t_ref = win ? win->t_ref : t0, t_cur = win ? win->t_cur : t0;
+        const int32_t n = win ? win->n : 0;
+        memcpy(w, &t_ref, 8), memcpy(w + 8, &t_cur, 8), memcpy(w + kImuOffN, &n, 4);
+        if (win) memcpy(w + kImuOffBias, win->bias, 12);
+        if (n) memcpy(w + kImuOffT, win->t, (size_t)n * 8), memcpy(w + kImuOffW, win->w, (size_t)n * 12);
+    }
     if (q.p.detector == 0) {
         memcpy(pin + q.off_ncand, &n_cand, sizeof n_cand);
         if (n_cand) memcpy(pin + q.off_cand, cand, (size_t)n_cand * 8);
@@ -5135,7 +5156,9 @@ int seq_feed(pagk_ctx *ctx, SeqState &q, const pagk_image *frame, const float *r
 // what every start / step checks of its frame and candidate list
 int seq_inputs_check(const SeqState &q, const pagk_image *frame, const float *cand, int32_t n_cand)
 {
-    if (!frame || !frame->data || frame->width != q.p.width || frame->height != q.p.height || frame->step < frame->width)
+    const bool raw = q.sensor && q.s.raw;   // a raw frame: src_width x src_height pixels of `channels` bytes
+    if (!frame || !frame->data || frame->width != (raw ? q.s.src_width : q.p.width) ||
+        frame->height != (raw ? q.s.src_height : q.p.height) || frame->step < (int64_t)q.row_bytes)
         return PAGK_E_ARG;
     if (q.p.detector == 0) return cand && n_cand >= 0 && n_cand <= q.p.cand_cap ? PAGK_OK : PAGK_E_ARG;   // (required, even when empty)
     return !cand && n_cand == 0 ? PAGK_OK : PAGK_E_ARG;   // a detecting sequence takes no list
@@ -5145,6 +5168,17 @@ int seq_inputs_check(const SeqState &q, const pagk_image *frame, const float *ca
 int seq_frame(pagk_ctx *ctx, SeqState &q, int slot)
 {
     const pagk_sequence_params &p = q.p;
+    if (q.sensor && q.s.raw) {   // through the context's maps into the slot (Examples/Demo/RealSenseD435i.cpp:202, src/frame.cpp:81-87)
+        if (ctx->rect_w != p.width || ctx->rect_h != p.height) {
+            snprintf(ctx->err, sizeof(ctx->err), "the sequence is %d x %d, the maps are now %d x %d (pagk_rectify_set_maps)", p.width,
+                     p.height, ctx->rect_w, ctx->rect_h);
+            return PAGK_E_ARG;
+        }
+        int rc = rect_into_slot(ctx, slot, &q.s.rectify, q.in, false, q.s.src_width, q.s.src_height, (int64_t)q.row_bytes,
+                                p.track.pyramids, "the sensor sequence");
+        // Lucas-Kanade reads the rectified level 0 of the slot in place
+        return rc || p.tracker != PAGK_SEQ_LK ? rc : lk_pyramid_slot(ctx, &p.lk, slot);
+    }
     if (p.tracker != PAGK_SEQ_LK) return pagk_frame_set_device(ctx, slot, q.in, p.width, p.height, p.width, p.track.pyramids);
     HIPCHK(ctx, hipMemcpyAsync(q.img[slot], q.in, (size_t)p.width * p.height, hipMemcpyDeviceToDevice, ctx->stream));
     int rc = pagk_frame_set_device(ctx, slot, q.img[slot], p.width, p.height, p.width, p.track.pyramids);
@@ -5175,9 +5209,18 @@ int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
 {
     const pagk_sequence_params &p = q.p;
     const SeqState::KeySet &ref = q.set[1 - c];
-    const float *rot = reinterpret_cast<const float *>(q.in + q.off_rot);
+    const float *rot = q.rot;
     int rc = seq_frame(ctx, q, c);
     if (rc) return rc;
+    if (q.sensor) {   // the window of this pair -> the nine floats the prediction reads (:511-587)
+        GyroArgs g;
+        g.win = q.in + q.off_win;
+        memcpy(g.Rbc, q.s.Rbc, sizeof g.Rbc);
+        g.fx = p.track.fx, g.fy = p.track.fy, g.cx = p.track.cx, g.cy = p.track.cy;
+        g.Rcl = q.rcl, g.rot9 = q.rot_out;
+        hipLaunchKernelGGL(k_gyro_integrate, dim3(1), dim3(64), 0, ctx->stream, g);
+        HIPCHK(ctx, hipGetLastError());
+    }
     if (p.tracker == PAGK_SEQ_LK) {   // :353-380
         const float *init = nullptr;
         const uint8_t *live = ref.live;
@@ -5208,7 +5251,14 @@ int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
         rc = pagk_geometry_validation_device(ctx, &p.fit, p.cap, ref.keys_un, q.ppu, q.st, p.sigma, q.cnt, q.score);
         if (rc) return rc;
     }
-    return seq_handover(ctx, q, q.st, c);
+    rc = seq_handover(ctx, q, q.st, c);
+    if (rc || !q.sensor || !q.s.flow_velocity) return rc;
+    FlowVelocityArgs f;   // src/frame.cpp:139-143, on the key set just written
+    f.normal_cur = q.set[c].keys_normal, f.normal_last = ref.keys_normal, f.index_in_last = q.set[c].index_in_last;
+    f.state = q.state, f.win = q.in + q.off_win, f.v = q.vel, f.cap = p.cap;
+    hipLaunchKernelGGL(k_flow_velocity, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, ctx->stream, f);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
 }
 
 // the sequence of a call, or nullptr with the reason in ctx->err
@@ -5256,7 +5306,8 @@ int pagk_sequence_params_check(const pagk_sequence_params *p)
     return PAGK_OK;
 }
 
-int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params)
+// (sensor: NULL for a plain sequence, whose block is carved exactly as before the sensor form existed)
+static int seq_create(pagk_ctx *ctx, const pagk_sequence_params *params, const pagk_sequence_sensor *sensor)
 {
     if (!ctx || pagk_sequence_params_check(params)) return PAGK_E_ARG;
     if (ctx->seq || in_capture(ctx)) {
@@ -5268,10 +5319,19 @@ int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params)
     if (!q) return PAGK_E_NOMEM;
     q->p = *params;
     const size_t n = (size_t)params->cap, px = (size_t)params->width * params->height;
-    q->off_rot = align_up(px, kPartAlign);
+    q->row_bytes = (size_t)params->width, q->rows = params->height;
+    if (sensor) {
+        q->sensor = true, q->s = *sensor;
+        if (sensor->raw) q->row_bytes = (size_t)sensor->src_width * sensor->rectify.channels, q->rows = sensor->src_height;
+    }
+    q->off_rot = align_up(q->row_bytes * q->rows, kPartAlign);
     q->off_ncand = q->off_rot + kPartAlign;
     q->off_cand = q->off_ncand + kPartAlign;
     q->in_bytes = q->off_cand + align_up((size_t)(params->detector == 0 ? params->cand_cap : 0) * 8, kPartAlign);
+    if (sensor) {   // the IMU window: one more part of the input block
+        q->off_win = q->in_bytes;
+        q->in_bytes += align_up(kImuWindowBytes, kPartAlign);
+    }
     const bool lk = params->tracker == PAGK_SEQ_LK;
     // input | 2 frame copies (LK) | 2 x (keys keys_un keys_normal index_in_last live) | state | info | the work arrays:
     // pu pd aff pt_un pt_dist pp ppu score lk_err st_in status st zero pix_err dist_pred th kept cnt lk_info
@@ -5280,8 +5340,12 @@ int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params)
                                      n * 8, n * 8, n * 16, n * 8, n * 8, n * 8, n * 8, 256, n * 4, n, n, n, n, n * 8, n * 8, 256, 256,
                                      256, 256};
     const Layout<kSeqParts> lay(sizes);
+    // the sensor parts lie behind the plain sequence's: rot9 and Rcl (k_gyro_integrate), the flow velocities
+    const size_t sensor_sizes[2] = {256, n * 8};
+    const Layout<2> slay(sensor_sizes);
     DevBuf &b = ctx->buf[pagk_ctx::SEQ];
-    int rc = reserve(ctx, b, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the sequence's block", "destroy the graphs first");
+    int rc = reserve(ctx, b, lay.total + (sensor ? slay.total : 0), NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the sequence's block",
+                     "destroy the graphs first");
     for (int k = 0; !rc && k < SeqState::kRing; k++) {
         if (hipHostMalloc(&q->pinned[k], q->in_bytes, hipHostMallocDefault) != hipSuccess ||
             hipEventCreateWithFlags(&q->read_done[k], hipEventDisableTiming) != hipSuccess) {
@@ -5323,8 +5387,51 @@ int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params)
         delete q;
         return PAGK_E_ARG;
     }
+    q->rot = reinterpret_cast<const float *>(q->in + q->off_rot);
+    if (sensor) {
+        void *sbase = static_cast<uint8_t *>(base) + lay.total;
+        q->rot_out = slay.at<float>(sbase, 0), q->rcl = q->rot_out + 16, q->vel = slay.at<float>(sbase, 1);
+        q->rot = q->rot_out;
+    }
     ctx->seq = q;
     return PAGK_OK;
+}
+
+int pagk_sequence_create(pagk_ctx *ctx, const pagk_sequence_params *params) { return seq_create(ctx, params, nullptr); }
+
+void pagk_sequence_sensor_default(pagk_sequence_sensor *s)
+{
+    if (!s) return;
+    memset(s, 0, sizeof *s);
+    pagk_rectify_params_default(&s->rectify);
+    s->raw = 0, s->src_width = s->src_height = 0, s->imu_cap = PAGK_IMU_MAX_SAMPLES;
+    s->Rbc[0] = s->Rbc[4] = s->Rbc[8] = 1.0f;
+    s->flow_velocity = 1;
+}
+
+int pagk_sequence_sensor_check(const pagk_sequence_sensor *s)
+{
+    if (!s || pagk_rectify_params_check(&s->rectify)) return PAGK_E_ARG;
+    if ((s->raw & ~1) || (s->flow_velocity & ~1) || s->imu_cap < 1 || s->imu_cap > PAGK_IMU_MAX_SAMPLES) return PAGK_E_ARG;
+    if (s->raw ? (s->src_width < 1 || s->src_height < 1 || s->src_width > 32767 || s->src_height > 32767)
+               : (s->rectify.channels != 1)) return PAGK_E_ARG;   // (a frame that is not raw is gray)
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(s->Rbc[k])) return PAGK_E_ARG;
+    return PAGK_OK;
+}
+
+int pagk_sequence_create_sensor(pagk_ctx *ctx, const pagk_sequence_params *params, const pagk_sequence_sensor *sensor)
+{
+    if (!ctx || pagk_sequence_params_check(params) || pagk_sequence_sensor_check(sensor)) return PAGK_E_ARG;
+    if (sensor->raw && (!ctx->buf[pagk_ctx::RECT_ENTRIES].ptr || ctx->rect_w != params->width || ctx->rect_h != params->height)) {
+        if (!ctx->buf[pagk_ctx::RECT_ENTRIES].ptr)
+            snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_create_sensor: raw frames need maps (pagk_rectify_set_maps)");
+        else
+            snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_create_sensor: the maps are %d x %d, the sequence is %d x %d", ctx->rect_w,
+                     ctx->rect_h, params->width, params->height);
+        return PAGK_E_ARG;
+    }
+    return seq_create(ctx, params, sensor);
 }
 
 int pagk_sequence_destroy(pagk_ctx *ctx)
@@ -5348,11 +5455,27 @@ int pagk_sequence_destroy(pagk_ctx *ctx)
     return alive ? PAGK_OK : release(ctx, ctx->buf[pagk_ctx::SEQ]);   // (a graph of the caller's cannot point into it, but stay safe)
 }
 
-int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *cand, int32_t n_cand)
+// the sequence of a call of the plain (`sensor` false) or the sensor form; the other kind is refused with a text
+static SeqState *seq_of_kind(pagk_ctx *ctx, const char *what, bool sensor)
 {
-    SeqState *q = seq_of(ctx, "pagk_sequence_start");
-    if (!q || seq_inputs_check(*q, frame, cand, n_cand)) return PAGK_E_ARG;
+    SeqState *q = seq_of(ctx, what);
+    if (q && q->sensor != sensor) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: the context's sequence is %s", what,
+                 q->sensor ? "a sensor sequence (pagk_sequence_start_sensor, pagk_sequence_step_sensor)"
+                           : "a plain sequence (pagk_sequence_start, pagk_sequence_step)");
+        return nullptr;
+    }
+    return q;
+}
+
+static int seq_start(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const float *cand, int32_t n_cand, double t0)
+{
+    if (seq_inputs_check(*q, frame, cand, n_cand)) return PAGK_E_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (q->sensor) {   // (the first frame has no pair: its velocities are zero)
+        HIPCHK(ctx, hipMemsetAsync(q->rot_out, 0, 256, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(q->vel, 0, (size_t)q->p.cap * 8, ctx->stream));
+    }
     const pagk_sequence_params &p = q->p;
     // what the loop reads before it has written it: the reach flag, the all-zero status, the identity affine
     HIPCHK(ctx, hipMemsetAsync(q->state, 0, 512, ctx->stream));   // (state and info: two parts of 256 bytes)
@@ -5366,27 +5489,42 @@ int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *can
         return PAGK_E_NOMEM;
     }
     q->started = q->stepped = false;
-    int rc = seq_feed(ctx, *q, frame, nullptr, cand, n_cand);
+    int rc = seq_feed(ctx, *q, frame, nullptr, cand, n_cand, nullptr, t0);
     if (rc || (rc = seq_frame(ctx, *q, 0)) || (rc = seq_handover(ctx, *q, q->zero, 0))) return rc;
-    q->started = true, q->frames = 1, q->last_graph = false;
+    q->started = true, q->frames = 1, q->last_graph = false, q->t_last = t0;
     return PAGK_OK;
 }
 
-int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand, int32_t mode)
+int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *cand, int32_t n_cand)
 {
-    SeqState *q = seq_of(ctx, "pagk_sequence_step");
-    if (!q || seq_inputs_check(*q, frame, cand, n_cand) || (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT)) return PAGK_E_ARG;
+    SeqState *q = seq_of_kind(ctx, "pagk_sequence_start", false);
+    return q ? seq_start(ctx, q, frame, cand, n_cand, 0.0) : PAGK_E_ARG;
+}
+
+int pagk_sequence_start_sensor(pagk_ctx *ctx, const pagk_image *raw, double t, const float *cand, int32_t n_cand)
+{
+    SeqState *q = seq_of_kind(ctx, "pagk_sequence_start_sensor", true);
+    if (!q || !std::isfinite(t)) return PAGK_E_ARG;
+    return seq_start(ctx, q, raw, cand, n_cand, t);
+}
+
+// rot9: the plain form's nine floats; win: the sensor form's window (checked by the caller)
+static int seq_step(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const float *rot9, const pagk_imu_window *win,
+                    const float *cand, int32_t n_cand, int32_t mode)
+{
+    if (seq_inputs_check(*q, frame, cand, n_cand) || (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT)) return PAGK_E_ARG;
     const pagk_sequence_params &p = q->p;
     const bool predicts = p.tracker == PAGK_SEQ_LK ? p.lk_initial_flow != 0 : p.track.has_gyro_predict_initial != 0;
-    if (!q->started || (predicts && !rot9)) {
+    if (!q->started || (predicts && !rot9 && !win)) {
         snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step: %s", q->started ? "this tracker predicts: rot9 is required"
                                                                                   : "pagk_sequence_start hands in the first frame");
         return PAGK_E_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int c = q->frames & 1;
-    int rc = seq_feed(ctx, *q, frame, rot9, cand, n_cand);
+    int rc = seq_feed(ctx, *q, frame, rot9, cand, n_cand, win);
     if (rc) return rc;
+    if (win) q->t_last = win->t_cur;
     if (mode == PAGK_SEQ_GRAPH && q->direct_done[c]) {
         if (q->graph[c] < 0) {
             if ((rc = pagk_graph_begin(ctx))) return rc;
@@ -5409,6 +5547,81 @@ int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9
     q->frames++;
     q->stepped = true;
     return PAGK_OK;
+}
+
+int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand, int32_t mode)
+{
+    SeqState *q = seq_of_kind(ctx, "pagk_sequence_step", false);
+    return q ? seq_step(ctx, q, frame, rot9, nullptr, cand, n_cand, mode) : PAGK_E_ARG;
+}
+
+int pagk_imu_window_check(const pagk_imu_window *w, int32_t imu_cap)
+{
+    if (!w || imu_cap < 1 || imu_cap > PAGK_IMU_MAX_SAMPLES || w->n < 0 || w->n > imu_cap) return PAGK_E_ARG;
+    if (!std::isfinite(w->t_ref) || !std::isfinite(w->t_cur) || !(w->t_cur > w->t_ref)) return PAGK_E_ARG;
+    if (w->n > 0 && (!w->t || !w->w)) return PAGK_E_ARG;
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(w->bias[k])) return PAGK_E_ARG;
+    for (int32_t i = 0; i < w->n; i++) {
+        if (!std::isfinite(w->t[i]) || !std::isfinite(w->w[3 * i]) || !std::isfinite(w->w[3 * i + 1]) || !std::isfinite(w->w[3 * i + 2]))
+            return PAGK_E_ARG;
+        if (i > 0 && !(w->t[i] > w->t[i - 1])) return PAGK_E_ARG;
+    }
+    return PAGK_OK;
+}
+
+int pagk_sequence_step_sensor(pagk_ctx *ctx, const pagk_image *raw, const pagk_imu_window *window, const float *cand,
+                              int32_t n_cand, int32_t mode)
+{
+    SeqState *q = seq_of_kind(ctx, "pagk_sequence_step_sensor", true);
+    if (!q) return PAGK_E_ARG;
+    if (pagk_imu_window_check(window, q->s.imu_cap)) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step_sensor: the window fails pagk_imu_window_check (imu_cap %d)", q->s.imu_cap);
+        return PAGK_E_ARG;
+    }
+    if (q->started && window->t_ref != q->t_last) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step_sensor: t_ref %.9f is not the previous frame's time %.9f", window->t_ref, q->t_last);
+        return PAGK_E_ARG;
+    }
+    return seq_step(ctx, q, raw, nullptr, window, cand, n_cand, mode);
+}
+
+int pagk_sequence_read_velocity(pagk_ctx *ctx, int32_t cap, float *v)
+{
+    SeqState *q = seq_of_kind(ctx, "pagk_sequence_read_velocity", true);
+    if (!q || !q->started || !q->s.flow_velocity || !v || cap < 1 || cap > q->p.cap) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(v, q->vel, (size_t)cap * 8, hipMemcpyDeviceToHost));
+    return lv_check(ctx);
+}
+
+int pagk_gyro_integrate(pagk_ctx *ctx, const float Rbc[9], const pagk_params *camera, const pagk_imu_window *window, float *Rcl,
+                        float *rot9)
+{
+    if (!ctx || !Rbc || !camera || pagk_imu_window_check(window, PAGK_IMU_MAX_SAMPLES)) return PAGK_E_ARG;
+    NOT_WHILE_CAPTURING(ctx, "pagk_gyro_integrate");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    alignas(8) uint8_t win[kImuWindowBytes] = {};   // (declared in front of the staging object: a queued copy reads it)
+    memcpy(win, &window->t_ref, 8), memcpy(win + 8, &window->t_cur, 8), memcpy(win + kImuOffN, &window->n, 4);
+    memcpy(win + kImuOffBias, window->bias, 12);
+    if (window->n) {
+        memcpy(win + kImuOffT, window->t, (size_t)window->n * 8);
+        memcpy(win + kImuOffW, window->w, (size_t)window->n * 12);
+    }
+    const size_t sizes[3] = {kImuWindowBytes, 9 * sizeof(float), 9 * sizeof(float)};
+    Staged<3> s(ctx, sizes);
+    int rc = s.open(nullptr, "the staging block of pagk_gyro_integrate");
+    if (rc || (rc = s.in(0, win, sizeof win))) return rc;
+    GyroArgs g;
+    g.win = s.at<uint8_t>(0);
+    memcpy(g.Rbc, Rbc, sizeof g.Rbc);
+    g.fx = camera->fx, g.fy = camera->fy, g.cx = camera->cx, g.cy = camera->cy;
+    g.Rcl = s.at<float>(1), g.rot9 = s.at<float>(2);
+    hipLaunchKernelGGL(k_gyro_integrate, dim3(1), dim3(64), 0, ctx->stream, g);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = s.out(1, Rcl, 9 * sizeof(float))) || (rc = s.out(2, rot9, 9 * sizeof(float)))) return rc;
+    return s.finish();
 }
 
 int pagk_sequence_read(pagk_ctx *ctx, int32_t cap, float *keys, float *keys_un, float *keys_normal, int32_t *index_in_last,

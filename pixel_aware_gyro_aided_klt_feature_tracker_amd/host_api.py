@@ -403,3 +403,17 @@ def search_by_klt(img_ref, img_cur, keys_ref, keys_cur, lk=None, assoc=None, ctx
     dict(n_matches, query, train, dist, disparity, pt_out, status, err, stats, info, lk_info and their fields by name)."""
     return _device_context(ctx).search_klt(np.ascontiguousarray(img_ref, np.uint8), np.ascontiguousarray(img_cur, np.uint8),
                                            keys_ref, keys_cur, lk, assoc)
+
+
+# ---- gyro integration (src/gyro_aided_tracker.cpp:511-587), array in, array out ----
+def gyro_integrate(Rbc, K, t_ref: float, t_cur: float, t, w, bias=(0.0, 0.0, 0.0), ctx=None) -> dict:
+    """GyroAidedTracker::IntegrateGyroMeasurements and SetRcl by the library's definition (pagk_gyro_integrate, include/pagk.h
+    "Gyro integration"): the samples (t: n time stamps, w: n x 3 rates in rad/s) between the frames at t_ref and t_cur ->
+    dict(Rcl (3 x 3), rot9 (rows 0 and 1 of K Rcl K^-1, then the third row of Rcl: what the sequence's prediction reads))."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    cam = capi.make_params()
+    cam.fx, cam.fy, cam.cx, cam.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    win, keep = capi.imu_window(t_ref, t_cur, t, w, bias)
+    rcl, rot9 = _device_context(ctx).gyro_integrate(Rbc, cam, win)
+    del keep
+    return dict(Rcl=rcl, rot9=rot9)

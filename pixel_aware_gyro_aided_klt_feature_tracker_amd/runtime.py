@@ -752,28 +752,47 @@ class DeviceSequence:
     the context owns the key sets, the work arrays, the pinned input ring and the two per-parity graphs, so this class keeps
     nothing but the context.  `sp` is a capi.SequenceParams (capi.sequence_params_default(...)): tracker PatchMatch,
     Lucas-Kanade or gyro-started Lucas-Kanade; detector 0 (the caller's candidate lists), 1 (Harris) or 2 (FAST).
-    SequenceTracker is the same loop for a Python host that keeps its results on the device."""
+    SequenceTracker is the same loop for a Python host that keeps its results on the device.
+    With `sensor` (a capi.SequenceSensor) it is the sensor form: start(raw, t=...) and step(raw, window=...) take what the
+    camera and the IMU deliver (raw frames through the context's maps, set with ctx.rectify_set_maps before; a
+    capi.imu_window), and read_velocity() returns mvFlowVelocityInNormalPlane."""
 
-    def __init__(self, sp: "capi.SequenceParams", device: int = 0, ctx: "capi.Context | None" = None):
+    def __init__(self, sp: "capi.SequenceParams", device: int = 0, ctx: "capi.Context | None" = None,
+                 sensor: "capi.SequenceSensor | None" = None):
         self._own = ctx is None
         self.ctx = capi.Context(device) if ctx is None else ctx
         self.sp = sp
+        self.sensor = sensor
         try:
-            self.ctx.sequence_create(sp)
+            if sensor is None:
+                self.ctx.sequence_create(sp)
+            else:
+                self.ctx.sequence_create_sensor(sp, sensor)
         except Exception:
             if self._own:
                 self.ctx.close()
             raise
         self._open = True
 
-    def start(self, frame, candidates=None):
+    def start(self, frame, candidates=None, t: "float | None" = None):
+        if self.sensor is not None:
+            if t is None:
+                raise ValueError("a sensor sequence starts with the frame's time stamp")
+            return self.ctx.sequence_start_sensor(frame, t, candidates)   # (a raw frame is taken as it is: rows may be padded)
         self.ctx.sequence_start(np.ascontiguousarray(frame, np.uint8), candidates)
 
-    def step(self, frame, rot9=None, candidates=None, mode: str = "graph"):
+    def step(self, frame, rot9=None, candidates=None, mode: str = "graph", window=None):
         if mode not in ("graph", "direct"):
             raise ValueError(mode)
-        self.ctx.sequence_step(np.ascontiguousarray(frame, np.uint8), rot9, candidates,
-                               capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT)
+        m = capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT
+        if self.sensor is not None:
+            if window is None or rot9 is not None:
+                raise ValueError("a sensor sequence steps with an IMU window, not with rot9")
+            return self.ctx.sequence_step_sensor(frame, window, candidates, m)
+        self.ctx.sequence_step(np.ascontiguousarray(frame, np.uint8), rot9, candidates, m)
+
+    def read_velocity(self, cap: "int | None" = None):
+        return self.ctx.sequence_read_velocity(int(self.sp.cap if cap is None else cap))
 
     def read(self, cap: "int | None" = None) -> dict:
         return self.ctx.sequence_read(int(self.sp.cap if cap is None else cap))

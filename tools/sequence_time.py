@@ -11,6 +11,12 @@ the figure is the median of seven windows with their minimum and maximum.  The p
 (--limit seconds, a watchdog thread ends it with exit code 124).
 
     python tools/sequence_time.py --out profiles/sequence_time.json
+
+With --sensor two more loops take their turns on the same frames: the sensor form of the sequence (pagk_sequence_*_sensor)
+fed raw three-channel frames and IMU windows of eight samples, and a plain PatchMatch sequence fed the same frames rectified
+in advance (tests/rectify_ref.c) with the rot9 of tests/gyro_integrate_ref.c; the two are compared byte for byte first.
+
+    python tools/sequence_time.py --sensor --out profiles/sensor_sequence_time.json
 """
 import argparse
 import json
@@ -35,6 +41,7 @@ def main() -> int:
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--limit", type=float, default=240.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sensor", action="store_true", help="add the sensor sequence and its plain counterpart")
     a = ap.parse_args()
     threading.Timer(a.limit, lambda: os._exit(124)).start()
 
@@ -81,6 +88,51 @@ def main() -> int:
                         os._exit(20)
     print("results: the PatchMatch arm equals SequenceTracker on all", NF, "frames; survivors per frame:", kept)
 
+    sensor_loops = {}
+    if a.sensor:
+        import tempfile
+        import gyro_integrate_ref_util as gu
+        import rectify_ref_util as ru
+        tmp = tempfile.mkdtemp(prefix="pagk_sequence_time_")
+        rref, gref = ru.build_ref(tmp), gu.build_ref(tmp)
+        mx, my = ru.lens_maps(ru.MILD, W, H)
+        raws = [np.ascontiguousarray(np.stack([im, np.roll(im, 1, axis=1), 255 - np.roll(im, 2, axis=0)], axis=2)) for im in imgs]
+        rect = [ru.ref_rectify(rref, mx, my, r) for r in raws]
+        dt = 1.0 / 30.0
+        wins = [dict(gu.constant_rate_window((0.004, -0.005, 0.006), 50.0 + (k - 1) * dt, 50.0 + k * dt), camera=(p.fx, p.fy, p.cx, p.cy))
+                for k in range(1, NF)]
+        rot9_w = [gu.ref_integrate(gref, w)[1] for w in wins]
+        cwin = [capi.imu_window(w["t_ref"], w["t_cur"], w["t"], w["w"], w["bias"]) for w in wins]
+        sensor = capi.sequence_sensor_default(rectify=capi.rectify_params_default(channels=3), raw=1, src_width=W, src_height=H)
+        c_sensor = capi.Context(0)
+        c_sensor.rectify_set_maps(mx, my)
+        sq_s = runtime.DeviceSequence(sp(capi.SEQ_PATCHMATCH, 0), ctx=c_sensor, sensor=sensor)
+        sq_p = runtime.DeviceSequence(sp(capi.SEQ_PATCHMATCH, 0))
+        sq_s.start(raws[0], cands[0], t=50.0)
+        sq_p.start(rect[0], cands[0])
+        for k in range(1, NF):
+            sq_s.step(raws[k], None, cands[k], mode="graph", window=cwin[k - 1][0])
+            sq_p.step(rect[k], rot9_w[k - 1], cands[k], mode="graph")
+            gs, gp = sq_s.read(), sq_p.read()
+            for key in ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state"):
+                if np.asarray(gs[key]).tobytes() != np.asarray(gp[key]).tobytes():
+                    print(f"frame {k}: {key} of the sensor sequence differs from the plain one: nothing is reported", file=sys.stderr)
+                    os._exit(20)
+        print("results: the sensor sequence equals the plain sequence on rectified frames on all", NF, "frames")
+
+        # a window restarts the sensor sequence: its time stamps go on from one frame to the next, the plain loop has none
+        def sensor_step(k):
+            if k == 1:
+                sq_s.start(raws[0], cands[0], t=50.0)
+            sq_s.step(raws[k], None, cands[k], mode="graph", window=cwin[k - 1][0])
+
+        def plain_step(k):
+            if k == 1:
+                sq_p.start(rect[0], cands[0])
+            sq_p.step(rect[k], rot9_w[k - 1], cands[k], mode="graph")
+        sensor_loops = {"sensor sequence, raw RGB frames": (sensor_step, c_sensor.sync),
+                        "plain sequence, frames rectified in advance": (plain_step, sq_p.ctx.sync)}
+
     # 2. windows taking turns (frame k of a window is frame 1 + k mod (NF - 1): both parities, every graph replayed)
     def window(step, sync):
         sync()
@@ -94,6 +146,7 @@ def main() -> int:
     loops = {"SequenceTracker": (lambda k: st.step(imgs[k], rot9[k - 1], cands[k], mode="graph", snapshot=False), st.synchronize)}
     for name, sq in seqs.items():
         loops[name] = ((lambda k, sq=sq: sq.step(imgs[k], rot9[k - 1], cands[k], mode="graph")), sq.ctx.sync)
+    loops.update(sensor_loops)
     times = {name: [] for name in loops}
     for name, (step, sync) in loops.items():
         window(step, sync)                                     # warm-up
@@ -102,6 +155,9 @@ def main() -> int:
             times[name].append(window(step, sync))
     res = {"workload": f"{W}x{H}, {N} keypoints, h = 10, {a.steps} steps a window, {a.windows} windows taking turns",
            "unit": "us per frame (host clock around a window, synchronised at both ends)", "survivors_per_frame": kept, "loops": {}}
+    if a.sensor:
+        res["sensor_note"] = ("the two sensor loops restart at the first frame every 8 steps (one start per 8 steps is inside "
+                              "their figures): a sensor sequence's time stamps must go on from frame to frame")
     for name, v in times.items():
         res["loops"][name] = dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))
         print(f"{name:28s} {res['loops'][name]['median']:8.1f} us ({res['loops'][name]['min']:.1f} - {res['loops'][name]['max']:.1f})")
