@@ -10,6 +10,12 @@
 // Prints one line per frame: the hand-over's state words [total reach_flag survivors added rejected].
 // Build: g++ -std=c++17 -I include examples/sequence_loop.cpp -L <pkg> -l:libpagk_hip.so -Wl,-rpath,<pkg>
 //
+//   sequence_loop <seq.bin> <target_n> <cap> --cameras K [--direct]
+//
+// A rig: K copies of the loop stepped together through a sequence group (pagk_sequence_group_*), every stage of a frame one
+// launch for all cameras.  Camera j sees the file's frames and rotations and, so that the cameras differ, the candidate
+// list of frame (k + j) mod n_frames.  Prints "camera j frame k: ..." with the same state words, camera by camera per frame.
+//
 //   sequence_loop <dir> <target_n> <cap> --sensor [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]
 //
 // The sensor form: what the demo reads from disk (Examples/Demo/RealSenseD435i.cpp:74-141) goes into the sequence as it is,
@@ -44,6 +50,50 @@ static bool read_n(FILE *f, std::vector<T> &v, size_t n)
 {
     v.resize(n);
     return fread(v.data(), sizeof(T), n, f) == n;
+}
+
+// :199-321 for K cameras at once: K contexts with one sequence each, grouped; the lead's calls step them all
+static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int nf, int w, int h, int nc,
+                    const std::vector<std::vector<uint8_t>> &img, const std::vector<std::vector<float>> &cand,
+                    const std::vector<std::vector<float>> &rot)
+{
+    pagk_ctx *ctx = nullptr;   // (the lead: CHECK reports its text)
+    std::vector<pagk_ctx *> ctxs(K, nullptr);
+    for (int j = 0; j < K; j++) {
+        int rc = pagk_create(&ctxs[j], 0);
+        if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
+        if (j == 0) ctx = ctxs[0];
+        rc = pagk_sequence_create(ctxs[j], &sp);
+        if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_create -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
+    }
+    CHECK(pagk_sequence_group_create(ctxs.data(), K));
+    std::vector<pagk_image> frames(K);
+    std::vector<const float *> lists(K);
+    std::vector<int32_t> counts(K, nc);
+    std::vector<float> rot9((size_t)K * 9), keys_un((size_t)sp.cap * 2);
+    int32_t state[PAGK_HANDOVER_STATE_WORDS];
+    for (int k = 0; k < nf; k++) {
+        for (int j = 0; j < K; j++) {
+            frames[j] = pagk_image{img[k].data(), w, h, w};
+            lists[j] = cand[(k + j) % nf].data();
+            if (k) memcpy(&rot9[(size_t)j * 9], rot[k - 1].data(), 9 * sizeof(float));
+        }
+        if (k == 0)
+            CHECK(pagk_sequence_group_start(ctx, frames.data(), lists.data(), counts.data()));
+        else
+            CHECK(pagk_sequence_group_step(ctx, frames.data(), rot9.data(), lists.data(), counts.data(), mode));
+        for (int j = 0; j < K; j++) {   // a member's reads keep working while it is grouped
+            int rc = pagk_sequence_read(ctxs[j], sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr);
+            if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_read -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
+            printf("camera %d frame %d: %d %d %d %d %d\n", j, k, state[0], state[1], state[2], state[3], state[4]);
+        }
+    }
+    int32_t words[PAGK_SEQ_STATUS_WORDS];
+    CHECK(pagk_sequence_group_status(ctx, words));
+    fprintf(stderr, "%d cameras, %d frames, %d graphs\n", words[3], words[0], words[2]);
+    CHECK(pagk_sequence_group_destroy(ctx));
+    for (int j = K - 1; j >= 0; j--) pagk_destroy(ctxs[j]);   // (each with its sequence)
+    return 0;
 }
 
 #ifdef PAGK_EXAMPLE_SENSOR
@@ -128,7 +178,7 @@ static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
+        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor | --cameras K] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
         return 1;
     }
     pagk_ctx *ctx = nullptr;
@@ -137,6 +187,7 @@ int main(int argc, char **argv)
     sp.target_n = atoi(argv[2]), sp.cap = atoi(argv[3]);
     int mode = PAGK_SEQ_GRAPH;
     bool sensor = false;
+    int cameras = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lk") sp.tracker = PAGK_SEQ_LK, sp.lk_initial_flow = 0;
@@ -145,6 +196,7 @@ int main(int argc, char **argv)
         else if (a == "--detect-fast") sp.detector = 2;
         else if (a == "--direct") mode = PAGK_SEQ_DIRECT;
         else if (a == "--sensor") sensor = true;
+        else if (a == "--cameras" && i + 1 < argc) cameras = atoi(argv[++i]);
         else return fprintf(stderr, "unknown flag %s\n", argv[i]), 1;
     }
     if (sensor) {
@@ -177,6 +229,11 @@ int main(int argc, char **argv)
     sp.width = w, sp.height = h, sp.new_point_threshold = 0.8 * sp.target_n;
     sp.cand_cap = nc > 0 ? nc : 1;
     if (pagk_sequence_params_check(&sp) != PAGK_OK) return fprintf(stderr, "the parameters are refused\n"), 1;
+    if (cameras) {
+        if (cameras < 1 || cameras > 64 || pagk_sequence_group_check(&sp) != PAGK_OK)
+            return fprintf(stderr, "--cameras: 1 .. 64 cameras, PatchMatch with the file's candidate lists\n"), 1;
+        return rig_loop(sp, cameras, mode, nf, w, h, nc, img, cand, rot);
+    }
 
     int rc = pagk_create(&ctx, 0);
     if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;

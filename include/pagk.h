@@ -1758,6 +1758,63 @@ int pagk_sequence_step_sensor(pagk_ctx *ctx, const pagk_image *raw, const pagk_i
  * PAGK_E_ARG on a plain sequence, with flow_velocity = 0, or before pagk_sequence_start_sensor. */
 int pagk_sequence_read_velocity(pagk_ctx *ctx, int32_t cap, float *v);
 
+/* ---- The sequence group: k cameras stepped together -------------------------------------------------------------------- */
+/* A rig runs the reference's loop (Examples/Demo/RealSenseD435i.cpp:199-321) once per camera.  A sequence group is k contexts
+ * on one device, each holding a plain sequence made by pagk_sequence_create, stepped together: it lifts the first item of
+ * the plain section's "Out of scope" list, k cameras batched.  Per camera the results are, byte for byte, those of the same
+ * sequence stepped alone with the same frames, rot9 and candidates.
+ * A frame of one camera is twelve launches, ten of them kernels of one or two workgroups whose cost is launch and
+ * dependent-load latency.  A group step issues every stage ONCE for all cameras, on the stream of ctxs[0], the lead:
+ *   1. the lead's stream waits for what every member's stream has enqueued;
+ *   2. every member's inputs go into the next block of its own pinned ring and from there, one asynchronous copy per member,
+ *      into its own fixed input block (these copies stand in front of the graph; each ring keeps its own flow control);
+ *   3. pagk_frame_set_device_batch; the prediction when has_gyro_predict_initial; pagk_track_device_batch (which keeps its
+ *      rule: small totals run as k launches); Step 3; the five kernels of the validation when `validate`; the three of the
+ *      hand-over -- each a launch with the camera as the grid's second dimension, reading its camera's arguments from a table
+ *      the lead owns;
+ *   4. every member's stream waits for the last launch, so that a member's synchronous reads see the step.
+ * The first step after pagk_sequence_group_create runs member by member (every member's workspaces get their final size),
+ * the next one as batched launches outside a capture (so do the lead's); from then on graph mode follows the plain
+ * sequence's rule per parity: the first step of a parity runs directly, the next is captured, later ones replay one of the
+ * group's two graphs.  A captured group step is one linear chain of nodes on the lead's stream, which must not be the
+ * legacy default stream.
+ * The group serves PatchMatch with the caller's candidate lists (tracker PAGK_SEQ_PATCHMATCH, detector 0), with or without
+ * the gyro prediction and the validation.  Out of scope of the group: Lucas-Kanade, the Harris and FAST detectors, sensor
+ * sequences (pagk_sequence_create_sensor), cameras that are configured differently, contexts on different devices. */
+/* PAGK_OK iff pagk_sequence_group_create accepts sequences of these parameters (Examples/Demo/RealSenseD435i.cpp:199-321, one
+ * loop per camera): pagk_sequence_params_check passes, tracker == PAGK_SEQ_PATCHMATCH and detector == 0; validate and
+ * track.has_gyro_predict_initial may each be 0 or 1.  PAGK_E_ARG (or the nested check's code) otherwise.  Needs no device. */
+int pagk_sequence_group_check(const pagk_sequence_params *p);
+/* Makes ctxs[0 .. k-1] a group (Examples/Demo/RealSenseD435i.cpp:199-321, the objects k loops keep between frames); ctxs[0]
+ * is the lead and owns it.  PAGK_E_ARG, with a text in pagk_last_error(ctxs[0]), for NULL arguments, k outside 1 .. 64,
+ * contexts on different devices, a context listed twice, a context without a sequence, with a sensor sequence or in a
+ * group already, a call inside a capture, parameters that are not byte-equal across the members (the trackers of one
+ * application are configured alike, as for pagk_track_device_batch) or that pagk_sequence_group_check refuses.  While
+ * grouped a member's own pagk_sequence_start, pagk_sequence_step and pagk_sequence_destroy return PAGK_E_ARG;
+ * pagk_sequence_read, pagk_sequence_read_pair and pagk_sequence_status keep working and see the group's results.  Other
+ * calls on a member that make its fit workspace, its hand-over mask or its hints grow invalidate the group's table: the
+ * next step returns PAGK_E_ARG and the group has to be destroyed. */
+int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k);
+/* Ends the group (Examples/Demo/RealSenseD435i.cpp:199-321, leaving the loops): waits for the queued work of every member,
+ * destroys the group's graphs and table, and leaves every member an ordinary sequence that can be stepped alone from where
+ * it stands.  pagk_destroy of the lead destroys the group first; pagk_destroy of another member dissolves it first.
+ * PAGK_E_ARG when `lead` leads no group or inside a capture. */
+int pagk_sequence_group_destroy(pagk_ctx *lead);
+/* The k first frames (Examples/Demo/RealSenseD435i.cpp:221-235): k times pagk_sequence_start, frames[j], cand[j] and
+ * n_cand[j] being camera j's; not a hot path.  Checks every camera's inputs first: PAGK_E_ARG with nothing enqueued if one
+ * would be refused.  May be called again to restart; the group's graphs are kept. */
+int pagk_sequence_group_start(pagk_ctx *lead, const pagk_image *frames, const float *const *cand, const int32_t *n_cand);
+/* Frame k >= 1 of every camera (Examples/Demo/RealSenseD435i.cpp:237-321), in the issue order above.  frames: k host images;
+ * rot9: k x 9 host floats, camera j's at rot9 + 9 j (NULL only when nothing predicts); cand, n_cand: k host lists and their
+ * lengths; mode: PAGK_SEQ_GRAPH or PAGK_SEQ_DIRECT.  PAGK_E_ARG, with nothing enqueued, if any camera's frame, list or
+ * rot9 would be refused by pagk_sequence_step, before pagk_sequence_group_start, or when the members do not stand at the
+ * same frame. */
+int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const float *rot9, const float *const *cand,
+                             const int32_t *n_cand, int32_t mode);
+/* Host-side words, nothing synchronised (Examples/Demo/RealSenseD435i.cpp:199-321 has no counterpart), PAGK_SEQ_STATUS_WORDS
+ * int32: [0] frames handed in per camera, [1] 1 if the last step was a graph replay, [2] graphs held by the group, [3] k. */
+int pagk_sequence_group_status(pagk_ctx *lead, int32_t *words);
+
 #ifdef __cplusplus
 }
 #endif

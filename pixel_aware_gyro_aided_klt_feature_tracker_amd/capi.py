@@ -429,6 +429,13 @@ def declare(lib) -> None:
                            ("pagk_gyro_integrate", [vp, vp, _P(Params), iw, vp, vp])):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_sequence_group_create"):
+        sp = _P(SequenceParams)
+        for name, args in (("pagk_sequence_group_check", [sp]), ("pagk_sequence_group_create", [vp, i32]),
+                           ("pagk_sequence_group_destroy", [vp]), ("pagk_sequence_group_start", [vp, vp, vp, vp]),
+                           ("pagk_sequence_group_step", [vp, vp, vp, vp, vp, i32]), ("pagk_sequence_group_status", [vp, vp])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
     if hasattr(lib, "pagk_lk_track_flow"):
         lib.pagk_lk_track_flow.restype = C.c_int
         lib.pagk_lk_track_flow.argtypes = [vp, _P(LkParams), _P(Params), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp,
@@ -605,6 +612,8 @@ EXPORTED_SYMBOLS = [
     "pagk_sequence_start", "pagk_sequence_step", "pagk_sequence_read", "pagk_sequence_read_pair", "pagk_sequence_status",
     "pagk_imu_window_check", "pagk_gyro_integrate", "pagk_sequence_sensor_default", "pagk_sequence_sensor_check",
     "pagk_sequence_create_sensor", "pagk_sequence_start_sensor", "pagk_sequence_step_sensor", "pagk_sequence_read_velocity",
+    "pagk_sequence_group_check", "pagk_sequence_group_create", "pagk_sequence_group_destroy", "pagk_sequence_group_start",
+    "pagk_sequence_group_step", "pagk_sequence_group_status",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
@@ -773,6 +782,58 @@ def sequence_params_default(**overrides) -> SequenceParams:
 def sequence_params_check(p: SequenceParams) -> int:
     """pagk_sequence_params_check: PAGK_OK, or the code pagk_sequence_create refuses these parameters with (needs no device)."""
     return int(load().pagk_sequence_params_check(C.byref(p)))
+
+
+def sequence_group_check(p: SequenceParams) -> int:
+    """pagk_sequence_group_check: PAGK_OK if sequences of these parameters can form a group (needs no device)."""
+    return int(load().pagk_sequence_group_check(C.byref(p)))
+
+
+class SequenceGroup:
+    """pagk_sequence_group_*: k contexts, each with a plain sequence of the same parameters, stepped together.  contexts[0] is
+    the lead; per camera the results are those of its sequence stepped alone (Context.sequence_read / sequence_read_pair)."""
+
+    def __init__(self, contexts):
+        self.ctxs = list(contexts)
+        self.lib = load()
+        self.lead = self.ctxs[0]
+        self.k = len(self.ctxs)
+        handles = (C.c_void_p * self.k)(*(c.h for c in self.ctxs))
+        self.lead._check(self.lib.pagk_sequence_group_create(handles, self.k), "pagk_sequence_group_create")
+        self.alive = True
+
+    def _inputs(self, frames, candidates):
+        if len(frames) != self.k or len(candidates) != self.k:
+            raise ValueError("one frame and one candidate list per camera")
+        views = (Image * self.k)(*(image_view(f) for f in frames))
+        lists = [Context._seq_cand(c if c is not None else np.zeros((0, 2), np.float32)) for c in candidates]
+        ptrs = (C.c_void_p * self.k)(*(l[1] for l in lists))
+        counts = (C.c_int32 * self.k)(*(l[2] for l in lists))
+        return (frames, lists), views, ptrs, counts
+
+    def start(self, frames, candidates):
+        """pagk_sequence_group_start: the k first frames (host images) and candidate lists."""
+        keep, views, ptrs, counts = self._inputs(frames, candidates)
+        self.lead._check(self.lib.pagk_sequence_group_start(self.lead.h, views, ptrs, counts), "pagk_sequence_group_start")
+
+    def step(self, frames, rot9s=None, candidates=None, mode: int = SEQ_GRAPH):
+        """pagk_sequence_group_step: frame k >= 1 of every camera; rot9s is k x 9 floats or None; nothing is synchronised."""
+        keep, views, ptrs, counts = self._inputs(frames, candidates if candidates is not None else [None] * self.k)
+        rot = None if rot9s is None else np.ascontiguousarray(rot9s, np.float32).reshape(self.k, 9)
+        self.lead._check(self.lib.pagk_sequence_group_step(self.lead.h, views, _ptr(rot), ptrs, counts, int(mode)),
+                         "pagk_sequence_group_step")
+
+    def status(self) -> dict:
+        """pagk_sequence_group_status -> dict(frames, last_was_graph, graphs, k); nothing is synchronised."""
+        w = np.zeros(SEQ_STATUS_WORDS, np.int32)
+        self.lead._check(self.lib.pagk_sequence_group_status(self.lead.h, _ptr(w)), "pagk_sequence_group_status")
+        return dict(frames=int(w[0]), last_was_graph=bool(w[1]), graphs=int(w[2]), k=int(w[3]))
+
+    def destroy(self):
+        """pagk_sequence_group_destroy: every member is an ordinary sequence again."""
+        if self.alive:
+            self.alive = False
+            self.lead._check(self.lib.pagk_sequence_group_destroy(self.lead.h), "pagk_sequence_group_destroy")
 
 
 def sequence_sensor_default(**overrides) -> SequenceSensor:

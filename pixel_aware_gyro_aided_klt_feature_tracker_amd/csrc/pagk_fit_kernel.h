@@ -401,10 +401,9 @@ __device__ __forceinline__ int fit_wave_isum(int v)
 
 // ---- kernels ------------------------------------------------------------------------------------------------------
 // k_fit_compact: one workgroup of 1024; n may be 0.  status may be null.
-__global__ void __launch_bounds__(1024) k_fit_compact(int32_t n, const float *pts1, const float *pts2,
-                                                      const uint8_t *status, float *p1, float *p2, int32_t *idx,
-                                                      FitHdr *hdr, double *models, int32_t *info, uint8_t *mask_H,
-                                                      uint8_t *mask_F)
+__device__ __forceinline__ void fit_compact_body(int32_t n, const float *pts1, const float *pts2, const uint8_t *status,
+                                                 float *p1, float *p2, int32_t *idx, FitHdr *hdr, double *models,
+                                                 int32_t *info, uint8_t *mask_H, uint8_t *mask_F)
 {
     __shared__ int32_t wtot[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -439,7 +438,16 @@ __global__ void __launch_bounds__(1024) k_fit_compact(int32_t n, const float *pt
     if (tid == 0) hdr->m = base;
 }
 
-__global__ void __launch_bounds__(256) k_fit_hyp(FitArgs a)
+__global__ void __launch_bounds__(1024) k_fit_compact(int32_t n, const float *pts1, const float *pts2,
+                                                      const uint8_t *status, float *p1, float *p2, int32_t *idx,
+                                                      FitHdr *hdr, double *models, int32_t *info, uint8_t *mask_H,
+                                                      uint8_t *mask_F)
+{
+    fit_compact_body(n, pts1, pts2, status, p1, p2, idx, hdr, models, info, mask_H, mask_F);
+}
+
+// (workgroup blockIdx.x of a fit's hypotheses: the same numbering in k_fit_hyp and in every camera of its batched form)
+__device__ __forceinline__ void fit_hyp_body(const FitArgs &a)
 {
     __shared__ double mdl[kFitHypPerBlock][9];
     __shared__ int32_t ok[kFitHypPerBlock];
@@ -487,7 +495,9 @@ __global__ void __launch_bounds__(256) k_fit_hyp(FitArgs a)
     }
 }
 
-__global__ void __launch_bounds__(256) k_fit_refit(FitArgs a)
+__global__ void __launch_bounds__(256) k_fit_hyp(FitArgs a) { fit_hyp_body(a); }
+
+__device__ __forceinline__ void fit_refit_body(const FitArgs &a)
 {
     __shared__ double red[4][45];
     __shared__ int32_t ired[4];
@@ -597,6 +607,8 @@ __global__ void __launch_bounds__(256) k_fit_refit(FitArgs a)
     if (tid < (model ? 9 : 18)) a.models[(model ? 18 : 0) + tid] = res[tid];
 }
 
+__global__ void __launch_bounds__(256) k_fit_refit(FitArgs a) { fit_refit_body(a); }
+
 // the drawn index sets of hypotheses [first, first + count) (pagk_selftest_fit_samples)
 __global__ void __launch_bounds__(256) k_fit_samples(unsigned long long seed, int model, int32_t m, int32_t first,
                                                      int32_t count, int32_t *out)
@@ -612,9 +624,9 @@ __global__ void __launch_bounds__(256) k_fit_samples(unsigned long long seed, in
 // the device end of GeometryValidation (:462-480) after k_geometry_scores_fit: model choice (pagk_geometry_select), the
 // chosen model's outliers cleared in the caller's status, cnt_inlier and the chosen score.  Nothing happens unless
 // m > 8 and at least one model was fitted.
-__global__ void __launch_bounds__(1024) k_fit_select(const FitHdr *hdr, const int32_t *info, const float *scores,
-                                                     const uint8_t *inl_H, const uint8_t *inl_F, const int32_t *idx,
-                                                     uint8_t *status, int32_t *d_cnt, float *d_score)
+__device__ __forceinline__ void fit_select_body(const FitHdr *hdr, const int32_t *info, const float *scores,
+                                                const uint8_t *inl_H, const uint8_t *inl_F, const int32_t *idx,
+                                                uint8_t *status, int32_t *d_cnt, float *d_score)
 {
     __shared__ int32_t part[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -643,6 +655,13 @@ __global__ void __launch_bounds__(1024) k_fit_select(const FitHdr *hdr, const in
         *d_cnt = t;
         *d_score = useH ? sH : sF;
     }
+}
+
+__global__ void __launch_bounds__(1024) k_fit_select(const FitHdr *hdr, const int32_t *info, const float *scores,
+                                                     const uint8_t *inl_H, const uint8_t *inl_F, const int32_t *idx,
+                                                     uint8_t *status, int32_t *d_cnt, float *d_score)
+{
+    fit_select_body(hdr, info, scores, inl_H, inl_F, idx, status, d_cnt, d_score);
 }
 
 }  // namespace pagk

@@ -62,10 +62,11 @@ __device__ __forceinline__ double pf_chain256(double s, const double2 *b)
     return s;
 }
 
-__global__ void __launch_bounds__(1024) k_post_filter(int32_t n, int32_t half_patch, const uint8_t *status_pm,
-                                                      const double *pix_err, const double *dist_pred, const float *pt_pm,
-                                                      const float *pt_pm_un, uint8_t *status_out, float *pt_predict,
-                                                      float *pt_predict_un, int32_t *kept_out, double *thresholds)
+// (the body of k_post_filter, and of one camera's workgroup of its batched form in pagk_group_kernel.h)
+__device__ __forceinline__ void post_filter_body(int32_t n, int32_t half_patch, const uint8_t *status_pm,
+                                                 const double *pix_err, const double *dist_pred, const float *pt_pm,
+                                                 const float *pt_pm_un, uint8_t *status_out, float *pt_predict,
+                                                 float *pt_predict_un, int32_t *kept_out, double *thresholds)
 {
     __shared__ double s_sum;
     __shared__ __align__(16) double s_stage[2][kPfRound];
@@ -128,6 +129,15 @@ __global__ void __launch_bounds__(1024) k_post_filter(int32_t n, int32_t half_pa
     }
 }
 
+__global__ void __launch_bounds__(1024) k_post_filter(int32_t n, int32_t half_patch, const uint8_t *status_pm,
+                                                      const double *pix_err, const double *dist_pred, const float *pt_pm,
+                                                      const float *pt_pm_un, uint8_t *status_out, float *pt_predict,
+                                                      float *pt_predict_un, int32_t *kept_out, double *thresholds)
+{
+    post_filter_body(n, half_patch, status_pm, pix_err, dist_pred, pt_pm, pt_pm_un, status_out, pt_predict, pt_predict_un,
+                     kept_out, thresholds);
+}
+
 // ---- frame hand-over -----------------------------------------------------------------------------------------------
 struct HandoverArgs {
     int32_t cap, cand_cap, width, height, target_n;
@@ -149,7 +159,7 @@ struct HandoverArgs {
 
 // mMask = ones: 16 bytes per store; `bytes` is a multiple of 16 (the buffer is padded), the tail is stored bytewise
 // when the caller's own mask is not
-__global__ void __launch_bounds__(256) k_handover_fill(uint8_t *mask, int64_t bytes)
+__device__ __forceinline__ void handover_fill_body(uint8_t *mask, int64_t bytes)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, o = t * 16;
     if (o + 16 <= bytes) {
@@ -163,6 +173,8 @@ __global__ void __launch_bounds__(256) k_handover_fill(uint8_t *mask, int64_t by
     }
 }
 
+__global__ void __launch_bounds__(256) k_handover_fill(uint8_t *mask, int64_t bytes) { handover_fill_body(mask, bytes); }
+
 // int(x) - 7 clamped so that the 14-wide block lies in the image (src/frame.cpp:148-149)
 __device__ __forceinline__ int handover_hole_origin(float x, int extent)
 {
@@ -173,8 +185,8 @@ __device__ __forceinline__ int handover_hole_origin(float x, int extent)
 }
 
 // one thread per (feature, row of its hole): 14 zero bytes.  Holes overlap; every writer stores 0.
-__global__ void __launch_bounds__(256) k_handover_holes(int32_t cap, int32_t width, int32_t height, const uint8_t *status,
-                                                        const float *pt_predict_un, uint8_t *mask)
+__device__ __forceinline__ void handover_holes_body(int32_t cap, int32_t width, int32_t height, const uint8_t *status,
+                                                    const float *pt_predict_un, uint8_t *mask)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int i = t / (2 * kHandoverHalf), r = t - i * (2 * kHandoverHalf);
@@ -183,6 +195,12 @@ __global__ void __launch_bounds__(256) k_handover_holes(int32_t cap, int32_t wid
     const int y0 = handover_hole_origin(pt_predict_un[2 * i + 1], height);
     uint8_t *row = mask + (int64_t)(y0 + r) * width + x0;
     for (int k = 0; k < 2 * kHandoverHalf; k++) row[k] = 0;
+}
+
+__global__ void __launch_bounds__(256) k_handover_holes(int32_t cap, int32_t width, int32_t height, const uint8_t *status,
+                                                        const float *pt_predict_un, uint8_t *mask)
+{
+    handover_holes_body(cap, width, height, status, pt_predict_un, mask);
 }
 
 // exclusive rank of this lane's `take` among the workgroup's 1024 in thread order, and the workgroup's total
@@ -211,7 +229,7 @@ __device__ __forceinline__ bool handover_accepts(const HandoverArgs &a, float x,
 
 // One workgroup of 1024, behind k_handover_fill and k_handover_holes on the stream: two stable compactions (ballot
 // scans over coalesced groups of 1024 entries), the survivors' and the accepted candidates'.
-__global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a)
+__device__ __forceinline__ void handover_keys_body(const HandoverArgs &a)
 {
     __shared__ int32_t wtot[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -292,5 +310,7 @@ __global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a)
         a.state[5] = a.state[6] = a.state[7] = 0;
     }
 }
+
+__global__ void __launch_bounds__(1024) k_handover_keys(HandoverArgs a) { handover_keys_body(a); }
 
 }  // namespace pagk

@@ -20,6 +20,7 @@
 #include "pagk_pose_kernel.h"
 #include "pagk_orb_levels_kernel.h"
 #include "pagk_gyro_kernel.h"
+#include "pagk_group_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
@@ -90,6 +91,23 @@ struct SeqState {
     double t_last = 0.0;          // the previous frame's time
 };
 
+// The sequence group of k contexts (pagk_sequence_group_*): every member's ctx->group points here, members[0] is the lead and
+// owns it -- its stream carries the steps, its graph slots hold the group's two graphs, its buf[GROUP] the argument table of
+// the batched small kernels (pagk_group_kernel.h): record [parity * k + camera].
+struct GroupState {
+    std::vector<pagk_ctx *> members;
+    bool members_done = false;   // one step has run member by member: every member's workspaces have their final size
+    bool batched_done = false;   // one step has run as batched launches outside a capture: so have the lead's
+    bool direct_done[2] = {}, last_graph = false, table_built = false;
+    int graph[2] = {-1, -1};
+    // what the table was built from, per member: a workspace that moved since then invalidates it
+    struct Held {
+        const void *fit, *hand, *hint;
+        size_t hint_bytes;
+    };
+    std::vector<Held> held;
+};
+
 }  // namespace
 
 struct pagk_ctx {
@@ -131,6 +149,7 @@ struct pagk_ctx {
         PRIO_HINT,     // the 4-wave kernels' hint (pagk_prio.h): one int32 per feature slot of the largest launch so far
         DISPATCH_ORDER,  // ... and their dispatch order (pagk_order.h): one int32 per feature slot, beside the hints
         SEQ,           // the sequence the context owns (pagk_sequence_*): input block, two key sets, work arrays, state and info words
+        GROUP,         // the sequence group this context leads (pagk_sequence_group_*): the argument table of its batched kernels, 2 k records
         kBufs
     };
     DevBuf buf[kBufs];
@@ -236,6 +255,7 @@ struct pagk_ctx {
     bool levels_shared = false;          // PAGK_LEVELS_SHARED=1 (measurement): ... also for contexts that share the device
     bool unfused_pyramid = false;  // PAGK_UNFUSED_PYRAMID=1: level-by-level launches (cross-check)
     SeqState *seq = nullptr;       // pagk_sequence_create .. pagk_sequence_destroy
+    GroupState *group = nullptr;   // pagk_sequence_group_create .. pagk_sequence_group_destroy: the group this context is a member of
     char err[256] = {0};
 };
 
@@ -1329,7 +1349,7 @@ int pagk_create(pagk_ctx **out, int device)
     }
     ctx->stream = ctx->own_stream;
     ctx->buf[pagk_ctx::FEAT].mirrored = true;
-    for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER}) ctx->buf[b].state = true;
+    for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER, pagk_ctx::GROUP}) ctx->buf[b].state = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
         pagk_destroy(ctx);
@@ -1406,6 +1426,10 @@ void pagk_destroy(pagk_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    if (ctx->group) {   // a group goes with any of its members: the others stay ordinary sequences
+        ctx->group->members[0]->capturing = false;
+        (void)pagk_sequence_group_destroy(ctx->group->members[0]);
+    }
     if (ctx->seq) {   // a live sequence goes with its context
         ctx->capturing = false;
         (void)pagk_sequence_destroy(ctx);
@@ -2251,15 +2275,12 @@ int pagk_track_pyr(pagk_ctx *ctx, const pagk_params *params, int32_t n_levels, c
                              ctx->slots[5]);
 }
 
-static int gyro_predict_any(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
-                            const float *KRKinv, const float *r3, const float *d_rot, int32_t n,
-                            const float *d_pt_ref_un, float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status,
-                            float *d_affine, const uint8_t *d_live = nullptr)
+// the arguments of k_gyro_predict: of one launch, or of one camera's record of a sequence group
+static PredictArgs gyro_predict_args(const pagk_params *params, int32_t width, int32_t height, const float *KRKinv,
+                                     const float *r3, const float *d_rot, int32_t n, const float *d_pt_ref_un,
+                                     float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status, float *d_affine,
+                                     const uint8_t *d_live)
 {
-    if (!ctx || !params || (!d_rot && (!KRKinv || !r3)) || n < 0 || width < 1 || height < 1) return PAGK_E_ARG;
-    if (params->half_patch < 1 || params->half_patch > PAGK_MAX_HALF_PATCH) return PAGK_E_ARG;
-    if (n > 0 && (!d_pt_ref_un || !d_pt_predict_un || !d_pt_predict || !d_status)) return PAGK_E_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     PredictArgs a;
     memset(&a, 0, sizeof a);
     a.n = n, a.width = width, a.height = height;
@@ -2288,6 +2309,20 @@ static int gyro_predict_any(pagk_ctx *ctx, const pagk_params *params, int32_t wi
     a.status = d_status;
     a.affine = d_affine;
     a.live = d_live;
+    return a;
+}
+
+static int gyro_predict_any(pagk_ctx *ctx, const pagk_params *params, int32_t width, int32_t height,
+                            const float *KRKinv, const float *r3, const float *d_rot, int32_t n,
+                            const float *d_pt_ref_un, float *d_pt_predict_un, float *d_pt_predict, uint8_t *d_status,
+                            float *d_affine, const uint8_t *d_live = nullptr)
+{
+    if (!ctx || !params || (!d_rot && (!KRKinv || !r3)) || n < 0 || width < 1 || height < 1) return PAGK_E_ARG;
+    if (params->half_patch < 1 || params->half_patch > PAGK_MAX_HALF_PATCH) return PAGK_E_ARG;
+    if (n > 0 && (!d_pt_ref_un || !d_pt_predict_un || !d_pt_predict || !d_status)) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const PredictArgs a = gyro_predict_args(params, width, height, KRKinv, r3, d_rot, n, d_pt_ref_un, d_pt_predict_un,
+                                            d_pt_predict, d_status, d_affine, d_live);
     if (n > 0) {
         hipLaunchKernelGGL(k_gyro_predict, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
         HIPCHK(ctx, hipGetLastError());
@@ -4224,6 +4259,28 @@ int fit_workspace(pagk_ctx *ctx, int32_t n, int32_t iters, FitWs *w)
     return PAGK_OK;
 }
 
+// the arguments of k_fit_hyp and k_fit_refit on workspace w (models, info: the caller's or the workspace's)
+FitArgs fit_args(const pagk_fit_params *p, const FitWs &w, double *models, int32_t *info, int32_t *d_hyp_counts, uint8_t *d_mask_H,
+                 uint8_t *d_mask_F)
+{
+    FitArgs a;
+    memset(&a, 0, sizeof a);
+    a.p1 = w.p1, a.p2 = w.p2, a.idx = w.idx, a.hdr = w.hdr, a.hyp_models = w.hyp_models;
+    a.hyp_counts = d_hyp_counts ? d_hyp_counts : w.hyp_counts;
+    a.models = models, a.info = info, a.mask_H = d_mask_H, a.mask_F = d_mask_F;
+    a.seed = p->seed;
+    a.iters[0] = p->iters_H, a.iters[1] = p->iters_F;
+    a.nblk_H = (p->iters_H + kFitHypPerBlock - 1) / kFitHypPerBlock;
+    a.t2[0] = p->thresh_H * p->thresh_H, a.t2[1] = p->thresh_F * p->thresh_F;
+    a.conf[0] = p->conf_H, a.conf[1] = p->conf_F;
+    return a;
+}
+// ... and the workgroups of k_fit_hyp
+int fit_hyp_blocks(const pagk_fit_params *p)
+{
+    return (p->iters_H + kFitHypPerBlock - 1) / kFitHypPerBlock + (p->iters_F + kFitHypPerBlock - 1) / kFitHypPerBlock;
+}
+
 // compaction + hypotheses + refit on the context stream
 int fit_launch(pagk_ctx *ctx, const pagk_fit_params *p, int32_t n, const float *d_pts1, const float *d_pts2,
                const uint8_t *d_status, double *d_models, uint8_t *d_mask_H, uint8_t *d_mask_F, int32_t *d_info,
@@ -4236,18 +4293,8 @@ int fit_launch(pagk_ctx *ctx, const pagk_fit_params *p, int32_t n, const float *
     hipLaunchKernelGGL(k_fit_compact, dim3(1), dim3(1024), 0, ctx->stream, n, d_pts1, d_pts2, d_status, w->p1, w->p2,
                        w->idx, w->hdr, models, info, d_mask_H, d_mask_F);
     HIPCHK(ctx, hipGetLastError());
-    FitArgs a;
-    memset(&a, 0, sizeof a);
-    a.p1 = w->p1, a.p2 = w->p2, a.idx = w->idx, a.hdr = w->hdr, a.hyp_models = w->hyp_models;
-    a.hyp_counts = d_hyp_counts ? d_hyp_counts : w->hyp_counts;
-    a.models = models, a.info = info, a.mask_H = d_mask_H, a.mask_F = d_mask_F;
-    a.seed = p->seed;
-    a.iters[0] = p->iters_H, a.iters[1] = p->iters_F;
-    a.nblk_H = (p->iters_H + kFitHypPerBlock - 1) / kFitHypPerBlock;
-    a.t2[0] = p->thresh_H * p->thresh_H, a.t2[1] = p->thresh_F * p->thresh_F;
-    a.conf[0] = p->conf_H, a.conf[1] = p->conf_F;
-    const int nblk = a.nblk_H + (p->iters_F + kFitHypPerBlock - 1) / kFitHypPerBlock;
-    hipLaunchKernelGGL(k_fit_hyp, dim3(nblk), dim3(256), 0, ctx->stream, a);
+    const FitArgs a = fit_args(p, *w, models, info, d_hyp_counts, d_mask_H, d_mask_F);
+    hipLaunchKernelGGL(k_fit_hyp, dim3(fit_hyp_blocks(p)), dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_fit_refit, dim3(2), dim3(256), 0, ctx->stream, a);
     HIPCHK(ctx, hipGetLastError());
@@ -5273,6 +5320,14 @@ SeqState *seq_of(pagk_ctx *ctx, const char *what)
     return ctx->seq;
 }
 
+// a member of a sequence group is stepped, started and destroyed through its group only
+bool seq_grouped(pagk_ctx *ctx, const char *what)
+{
+    if (!ctx->group) return false;
+    snprintf(ctx->err, sizeof(ctx->err), "%s: the context is a member of a sequence group (pagk_sequence_group_step, pagk_sequence_group_destroy)", what);
+    return true;
+}
+
 }  // namespace
 
 void pagk_sequence_params_default(pagk_sequence_params *p)
@@ -5437,7 +5492,7 @@ int pagk_sequence_create_sensor(pagk_ctx *ctx, const pagk_sequence_params *param
 int pagk_sequence_destroy(pagk_ctx *ctx)
 {
     SeqState *q = seq_of(ctx, "pagk_sequence_destroy");
-    if (!q) return PAGK_E_ARG;
+    if (!q || seq_grouped(ctx, "pagk_sequence_destroy")) return PAGK_E_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (int &g : q->graph) {
@@ -5498,7 +5553,7 @@ static int seq_start(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const 
 int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *cand, int32_t n_cand)
 {
     SeqState *q = seq_of_kind(ctx, "pagk_sequence_start", false);
-    return q ? seq_start(ctx, q, frame, cand, n_cand, 0.0) : PAGK_E_ARG;
+    return q && !seq_grouped(ctx, "pagk_sequence_start") ? seq_start(ctx, q, frame, cand, n_cand, 0.0) : PAGK_E_ARG;
 }
 
 int pagk_sequence_start_sensor(pagk_ctx *ctx, const pagk_image *raw, double t, const float *cand, int32_t n_cand)
@@ -5552,7 +5607,7 @@ static int seq_step(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const f
 int pagk_sequence_step(pagk_ctx *ctx, const pagk_image *frame, const float *rot9, const float *cand, int32_t n_cand, int32_t mode)
 {
     SeqState *q = seq_of_kind(ctx, "pagk_sequence_step", false);
-    return q ? seq_step(ctx, q, frame, rot9, nullptr, cand, n_cand, mode) : PAGK_E_ARG;
+    return q && !seq_grouped(ctx, "pagk_sequence_step") ? seq_step(ctx, q, frame, rot9, nullptr, cand, n_cand, mode) : PAGK_E_ARG;
 }
 
 int pagk_imu_window_check(const pagk_imu_window *w, int32_t imu_cap)
@@ -5667,6 +5722,388 @@ int pagk_sequence_status(pagk_ctx *ctx, int32_t *words)
     words[1] = q.last_graph ? 1 : 0;
     words[2] = (q.graph[0] >= 0) + (q.graph[1] >= 0);
     words[3] = 0;
+    return PAGK_OK;
+}
+
+// ---- the sequence group: k cameras stepped together (Examples/Demo/RealSenseD435i.cpp:199-321, one loop per camera) -----------
+namespace {
+
+// the group `lead` leads, or nullptr with the reason in lead->err
+GroupState *group_of(pagk_ctx *lead, const char *what)
+{
+    if (!lead) return nullptr;
+    if (lead->capturing) {
+        snprintf(lead->err, sizeof(lead->err), "%s between pagk_graph_begin and pagk_graph_end: the group captures its own graphs", what);
+        return nullptr;
+    }
+    if (!lead->group || lead->group->members[0] != lead) {
+        snprintf(lead->err, sizeof(lead->err), "%s: the context leads no sequence group (pagk_sequence_group_create)", what);
+        return nullptr;
+    }
+    return lead->group;
+}
+
+// While a group step is issued every member works on the lead's stream: the batched calls then have nothing to order
+// between streams (no event crosses into a capture), and what falls back to k launches lands in the same chain.
+struct GroupStreams {
+    explicit GroupStreams(GroupState &g) : g_(g)
+    {
+        for (pagk_ctx *c : g.members) saved_.push_back(c->stream), c->stream = g.members[0]->stream;
+    }
+    ~GroupStreams()
+    {
+        for (size_t j = 0; j < g_.members.size(); j++) g_.members[j]->stream = saved_[j];
+    }
+    GroupStreams(const GroupStreams &) = delete;
+    GroupStreams &operator=(const GroupStreams &) = delete;
+    GroupState &g_;
+    std::vector<hipStream_t> saved_;
+};
+
+GroupState::Held group_held(pagk_ctx *c)
+{
+    const DevBuf &hint = c->buf[pagk_ctx::PRIO_HINT];
+    return {c->buf[pagk_ctx::FIT].ptr, c->buf[pagk_ctx::HAND].ptr, hint.ptr, hint.bytes};
+}
+
+// Camera j's record of parity c: the arguments its own launches of seq_issue would carry.
+int group_record(pagk_ctx *ctx, int c, GroupRec *out)
+{
+    SeqState &q = *ctx->seq;
+    const pagk_sequence_params &p = q.p;
+    const SeqState::KeySet &ref = q.set[1 - c], &dst = q.set[c];
+    GroupRec r;
+    memset(&r, 0, sizeof r);
+    r.predict = gyro_predict_args(&p.track, p.width, p.height, nullptr, nullptr, q.rot, p.cap, ref.keys_un, q.pu, q.pd, q.st_in, q.aff,
+                                  ref.live);
+    r.n = p.cap, r.half_patch = p.track.half_patch;
+    r.pf_status_pm = q.status, r.pf_pix_err = q.pix_err, r.pf_dist_pred = q.dist_pred, r.pf_pt_pm = q.pt_dist, r.pf_pt_pm_un = q.pt_un;
+    r.pf_status_out = q.st, r.pf_pt_predict = q.pp, r.pf_pt_predict_un = q.ppu, r.pf_kept = q.kept, r.pf_thresholds = q.th;
+    if (p.validate) {   // pagk_geometry_validation_device(ref.keys_un, q.ppu, q.st, sigma, q.cnt, q.score)
+        FitWs w;
+        int rc = fit_workspace(ctx, p.cap, p.fit.iters_H + p.fit.iters_F, &w);
+        if (rc) return rc;
+        r.fit_pts1 = ref.keys_un, r.fit_pts2 = q.ppu, r.fit_status = q.st;
+        r.fit_p1 = w.p1, r.fit_p2 = w.p2, r.fit_idx = w.idx;
+        r.fit = fit_args(&p.fit, w, w.models, w.info, nullptr, nullptr, nullptr);
+        r.sigma = p.sigma, r.inl_H = w.inl_H, r.inl_F = w.inl_F, r.scores = w.scores;
+        r.val_cnt = q.cnt, r.val_score = q.score;
+    }
+    // pagk_frame_handover_device(q.st, q.pp, q.ppu, the list in the input block, key set c, the context's own mask, q.state)
+    const DevBuf &hand = ctx->buf[pagk_ctx::HAND];
+    r.mask_bytes = (int64_t)p.width * p.height;
+    if (!hand.ptr || hand.bytes < (size_t)r.mask_bytes) {
+        snprintf(ctx->err, sizeof(ctx->err), "the hand-over's mask has not been reserved");
+        return PAGK_E_ARG;
+    }
+    handover_fill_args(&r.hand, &p.track, p.width, p.height, p.cap, p.target_n, p.new_point_threshold);
+    r.hand.cand_cap = p.cand_cap;
+    r.hand.n_cand = reinterpret_cast<const int32_t *>(q.in + q.off_ncand);
+    r.hand.cand_un = reinterpret_cast<const float *>(q.in + q.off_cand);
+    r.hand.status = q.st, r.hand.pt_predict = q.pp, r.hand.pt_predict_un = q.ppu;
+    r.hand.keys = dst.keys, r.hand.keys_un = dst.keys_un, r.hand.keys_normal = dst.keys_normal;
+    r.hand.index_in_last = dst.index_in_last, r.hand.live = dst.live, r.hand.mask = static_cast<uint8_t *>(hand.ptr);
+    r.hand.state = q.state;
+    handover_hint_args(ctx, &r.hand);
+    *out = r;
+    return PAGK_OK;
+}
+
+// The table, once per group: after the member-by-member step every buffer a record points into has its final size.
+int group_table(pagk_ctx *lead, GroupState &g)
+{
+    const int k = (int)g.members.size();
+    if (g.table_built) {
+        for (int j = 0; j < k; j++) {
+            const GroupState::Held h = group_held(g.members[j]);
+            if (h.fit != g.held[j].fit || h.hand != g.held[j].hand || h.hint != g.held[j].hint || h.hint_bytes != g.held[j].hint_bytes) {
+                snprintf(lead->err, sizeof(lead->err), "a workspace of member %d moved under the group's table (a call outside the group made it "
+                         "grow): destroy the group (pagk_sequence_group_destroy)", j);
+                return PAGK_E_ARG;
+            }
+        }
+        return PAGK_OK;
+    }
+    try {
+        std::vector<GroupRec> host((size_t)2 * k);
+        for (int c = 0; c < 2; c++)
+            for (int j = 0; j < k; j++) {
+                pagk_ctx *m = g.members[j];
+                int rc = group_record(m, c, &host[(size_t)c * k + j]);
+                if (rc) {
+                    if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
+                    return rc;
+                }
+            }
+        g.held.clear();
+        for (int j = 0; j < k; j++) g.held.push_back(group_held(g.members[j]));
+        HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP].ptr, host.data(), host.size() * sizeof(GroupRec), hipMemcpyHostToDevice,
+                                    lead->stream));
+        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host is a local)
+    } catch (const std::bad_alloc &) {
+        return PAGK_E_NOMEM;
+    }
+    g.table_built = true;
+    return PAGK_OK;
+}
+
+// The stage launches of a frame of parity c for all cameras, on the lead's stream (which every member works on: GroupStreams).
+int group_issue(pagk_ctx *lead, GroupState &g, int c)
+{
+    const int k = (int)g.members.size();
+    const pagk_sequence_params &p = lead->seq->p;
+    pagk_ctx *const *ctxs = g.members.data();
+    constexpr int K = pagk_ctx::kBatchMaxStreams;
+    int32_t slot_cur[K], slot_ref[K], width[K], height[K], n[K];
+    int64_t step[K];
+    const void *data[K];
+    const float *pt_ref[K], *pt_init[K], *affine[K];
+    const uint8_t *status_in[K];
+    pagk_outputs out[K];
+    const bool predicts = p.track.has_gyro_predict_initial != 0;
+    for (int j = 0; j < k; j++) {
+        const SeqState &q = *ctxs[j]->seq;
+        const SeqState::KeySet &ref = q.set[1 - c];
+        slot_cur[j] = c, slot_ref[j] = 1 - c, width[j] = p.width, height[j] = p.height, step[j] = p.width, n[j] = p.cap;
+        data[j] = q.in;
+        pt_ref[j] = ref.keys_un, affine[j] = q.aff;
+        pt_init[j] = predicts ? q.pu : ref.keys_un;              // (as seq_issue hands them to pagk_track_device)
+        status_in[j] = predicts ? q.st_in : ref.live;
+        out[j] = pagk_outputs{q.pt_un, q.pt_dist, q.status, q.pix_err, q.dist_pred, nullptr, nullptr};
+    }
+    const GroupRec *table = static_cast<const GroupRec *>(lead->buf[pagk_ctx::GROUP].ptr) + (size_t)c * k;
+    const unsigned kk = (unsigned)k;
+    hipStream_t s = lead->stream;
+    int rc = pagk_frame_set_device_batch(ctxs, k, slot_cur, data, width, height, step, p.track.pyramids);
+    if (rc) return rc;
+    if (predicts) hipLaunchKernelGGL(k_group_gyro_predict, dim3((unsigned)((p.cap + 255) / 256), kk), dim3(256), 0, s, table);
+    HIPCHK(lead, hipGetLastError());
+    if ((rc = pagk_track_device_batch(ctxs, k, &p.track, slot_ref, slot_cur, n, pt_ref, pt_init, affine, status_in, out))) return rc;
+    hipLaunchKernelGGL(k_group_post_filter, dim3(1, kk), dim3(1024), 0, s, table);
+    HIPCHK(lead, hipGetLastError());
+    if (p.validate) {
+        hipLaunchKernelGGL(k_group_fit_compact, dim3(1, kk), dim3(1024), 0, s, table);
+        hipLaunchKernelGGL(k_group_fit_hyp, dim3((unsigned)fit_hyp_blocks(&p.fit), kk), dim3(256), 0, s, table);
+        hipLaunchKernelGGL(k_group_fit_refit, dim3(2, kk), dim3(256), 0, s, table);
+        hipLaunchKernelGGL(k_group_scores_fit, dim3(2, kk), dim3(256), 0, s, table);
+        hipLaunchKernelGGL(k_group_fit_select, dim3(1, kk), dim3(1024), 0, s, table);
+        HIPCHK(lead, hipGetLastError());
+    }
+    const int64_t bytes = (int64_t)p.width * p.height;
+    hipLaunchKernelGGL(k_group_handover_fill, dim3((unsigned)((bytes + 4095) / 4096), kk), dim3(256), 0, s, table);
+    hipLaunchKernelGGL(k_group_handover_holes, dim3((unsigned)(((int64_t)p.cap * 14 + 255) / 256), kk), dim3(256), 0, s, table);
+    hipLaunchKernelGGL(k_group_handover_keys, dim3(1, kk), dim3(1024), 0, s, table);
+    HIPCHK(lead, hipGetLastError());
+    return PAGK_OK;
+}
+
+// every camera's frame and list as pagk_sequence_start / pagk_sequence_step would check them
+int group_inputs_check(pagk_ctx *lead, const GroupState &g, const char *what, const pagk_image *frames, const float *const *cand,
+                       const int32_t *n_cand)
+{
+    if (!frames || !cand || !n_cand) return PAGK_E_ARG;
+    for (size_t j = 0; j < g.members.size(); j++)
+        if (seq_inputs_check(*g.members[j]->seq, &frames[j], cand[j], n_cand[j])) {
+            snprintf(lead->err, sizeof(lead->err), "%s: camera %zu's frame or candidate list is refused", what, j);
+            return PAGK_E_ARG;
+        }
+    return PAGK_OK;
+}
+
+void group_drop(GroupState *g)
+{
+    pagk_ctx *lead = g->members[0];
+    (void)hipSetDevice(lead->device);
+    for (pagk_ctx *m : g->members) (void)hipStreamSynchronize(m->stream);
+    for (int &id : g->graph) {
+        if (id >= 0) (void)pagk_graph_destroy(lead, id);
+        id = -1;
+    }
+    (void)release(lead, lead->buf[pagk_ctx::GROUP]);
+    for (pagk_ctx *m : g->members) m->group = nullptr;
+    delete g;
+}
+
+}  // namespace
+
+int pagk_sequence_group_check(const pagk_sequence_params *p)
+{
+    int rc = pagk_sequence_params_check(p);
+    if (rc) return rc;
+    return p->tracker == PAGK_SEQ_PATCHMATCH && p->detector == 0 ? PAGK_OK : PAGK_E_ARG;
+}
+
+int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k)
+{
+    if (!ctxs || !ctxs[0]) return PAGK_E_ARG;
+    pagk_ctx *lead = ctxs[0];
+    auto refuse = [&](const char *why, int j) {
+        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: context %d %s", j, why);
+        return PAGK_E_ARG;
+    };
+    if (k < 1 || k > pagk_ctx::kBatchMaxStreams) {
+        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: k = %d is outside 1 .. %d", k, pagk_ctx::kBatchMaxStreams);
+        return PAGK_E_ARG;
+    }
+    for (int j = 0; j < k; j++) {
+        pagk_ctx *c = ctxs[j];
+        if (!c) return refuse("is NULL", j);
+        if (c->device != lead->device) return refuse("lives on another device than the lead", j);
+        for (int i = 0; i < j; i++)
+            if (ctxs[i] == c) return refuse("is listed twice", j);
+        if (!c->seq) return refuse("has no sequence (pagk_sequence_create)", j);
+        if (c->seq->sensor) return refuse("holds a sensor sequence: out of scope of the group", j);
+        if (c->group) return refuse("is a member of a group already", j);
+        if (in_capture(c)) return refuse("is inside a graph capture", j);
+        if (memcmp(&c->seq->p, &lead->seq->p, sizeof(pagk_sequence_params)) != 0)
+            return refuse("is configured differently from the lead: the parameters of a group are byte-equal", j);
+    }
+    if (pagk_sequence_group_check(&lead->seq->p)) {
+        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: the group serves PatchMatch with the caller's candidate lists "
+                 "(pagk_sequence_group_check)");
+        return PAGK_E_ARG;
+    }
+    HIPCHK(lead, hipSetDevice(lead->device));
+    // (no graph of the group exists yet: whatever graphs the lead holds do not point into the table)
+    int rc = reserve(lead, lead->buf[pagk_ctx::GROUP], align_up((size_t)2 * k * sizeof(GroupRec), kPartAlign), NOT_IN_CAPTURE,
+                     "the sequence group's table");
+    if (rc) return rc;
+    GroupState *g = new (std::nothrow) GroupState();
+    if (!g) return PAGK_E_NOMEM;
+    try {
+        g->members.assign(ctxs, ctxs + k);
+    } catch (const std::bad_alloc &) {
+        delete g;
+        return PAGK_E_NOMEM;
+    }
+    for (int j = 0; j < k; j++) ctxs[j]->group = g;
+    return PAGK_OK;
+}
+
+int pagk_sequence_group_destroy(pagk_ctx *lead)
+{
+    GroupState *g = group_of(lead, "pagk_sequence_group_destroy");
+    if (!g) return PAGK_E_ARG;
+    group_drop(g);
+    return PAGK_OK;
+}
+
+int pagk_sequence_group_start(pagk_ctx *lead, const pagk_image *frames, const float *const *cand, const int32_t *n_cand)
+{
+    GroupState *g = group_of(lead, "pagk_sequence_group_start");
+    if (!g || group_inputs_check(lead, *g, "pagk_sequence_group_start", frames, cand, n_cand)) return PAGK_E_ARG;
+    for (size_t j = 0; j < g->members.size(); j++) {
+        pagk_ctx *m = g->members[j];
+        int rc = seq_start(m, m->seq, &frames[j], cand[j], n_cand[j], 0.0);
+        if (rc) {
+            if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %zu: %s", j, m->err);
+            return rc;
+        }
+    }
+    g->last_graph = false;
+    return PAGK_OK;
+}
+
+int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const float *rot9, const float *const *cand,
+                             const int32_t *n_cand, int32_t mode)
+{
+    const char *what = "pagk_sequence_group_step";
+    GroupState *gp = group_of(lead, what);
+    if (!gp || group_inputs_check(lead, *gp, what, frames, cand, n_cand) || (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT))
+        return PAGK_E_ARG;
+    GroupState &g = *gp;
+    const int k = (int)g.members.size();
+    const pagk_sequence_params &p = lead->seq->p;
+    for (int j = 0; j < k; j++) {
+        const SeqState &q = *g.members[j]->seq;
+        if (!q.started || q.frames != lead->seq->frames) {
+            snprintf(lead->err, sizeof(lead->err), "%s: %s (pagk_sequence_group_start)", what,
+                     q.started ? "the members do not stand at the same frame" : "a member has not been started");
+            return PAGK_E_ARG;
+        }
+    }
+    if (p.track.has_gyro_predict_initial && !rot9) {
+        snprintf(lead->err, sizeof(lead->err), "%s: this tracker predicts: rot9 is required", what);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(lead, hipSetDevice(lead->device));
+    const int c = lead->seq->frames & 1;
+    int rc = PAGK_OK;
+    if (g.members_done && (rc = group_table(lead, g))) return rc;   // (in front of everything that enqueues)
+    // 1. what the members' streams have enqueued (reads, a step alone before the group was made) comes first
+    for (int j = 1; j < k; j++)
+        if (g.members[j]->stream != lead->stream) {
+            HIPCHK(lead, hipEventRecord(g.members[j]->ev_batch, g.members[j]->stream));
+            HIPCHK(lead, hipStreamWaitEvent(lead->stream, g.members[j]->ev_batch, 0));
+        }
+    {
+        GroupStreams on_lead(g);
+        // 2. the inputs: each member's ring, each member's fixed block
+        for (int j = 0; j < k && !rc; j++) {
+            pagk_ctx *m = g.members[j];
+            rc = seq_feed(m, *m->seq, &frames[j], rot9 ? rot9 + 9 * j : nullptr, cand[j], n_cand[j]);
+            if (rc && m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
+        }
+        if (rc) return rc;
+        // 3. the stages
+        bool replay = false;
+        if (!g.members_done) {   // every member's own launches: its fit workspace, its mask, its hints get their size
+            for (int j = 0; j < k; j++) {
+                pagk_ctx *m = g.members[j];
+                if ((rc = seq_issue(m, *m->seq, c))) {
+                    if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
+                    return rc;
+                }
+                m->seq->direct_done[c] = true;
+            }
+            g.members_done = true;
+            g.direct_done[c] = true;
+        } else if (mode == PAGK_SEQ_GRAPH && g.direct_done[c] && g.batched_done) {
+            if (g.graph[c] < 0) {
+                if ((rc = pagk_graph_begin(lead))) return rc;
+                rc = group_issue(lead, g, c);
+                int32_t id = -1;
+                const int rc_end = pagk_graph_end(lead, &id);
+                if (rc || rc_end) {
+                    if (!rc_end && id >= 0) (void)pagk_graph_destroy(lead, id);
+                    return rc ? rc : rc_end;
+                }
+                g.graph[c] = id;
+            }
+            if ((rc = pagk_graph_launch(lead, g.graph[c]))) return rc;
+            replay = true;
+        } else {   // also the first batched step, and the first step of each parity, in graph mode: allocations happen outside a capture
+            if ((rc = group_issue(lead, g, c))) return rc;
+            g.batched_done = true;
+            g.direct_done[c] = true;
+        }
+        g.last_graph = replay;
+        for (pagk_ctx *m : g.members) {
+            m->seq->frames++;
+            m->seq->stepped = true;
+            m->seq->last_graph = replay;
+        }
+    }
+    // 4. a member's synchronous reads wait for its own stream: that stream sees the step
+    bool others = false;
+    for (int j = 1; j < k; j++) others = others || g.members[j]->stream != lead->stream;
+    if (others) {
+        HIPCHK(lead, hipEventRecord(lead->ev_batch, lead->stream));
+        for (int j = 1; j < k; j++)
+            if (g.members[j]->stream != lead->stream) HIPCHK(lead, hipStreamWaitEvent(g.members[j]->stream, lead->ev_batch, 0));
+    }
+    return PAGK_OK;
+}
+
+int pagk_sequence_group_status(pagk_ctx *lead, int32_t *words)
+{
+    GroupState *g = group_of(lead, "pagk_sequence_group_status");
+    if (!g || !words) return PAGK_E_ARG;
+    const SeqState &q = *lead->seq;
+    words[0] = q.started ? q.frames : 0;
+    words[1] = g->last_graph ? 1 : 0;
+    words[2] = (g->graph[0] >= 0) + (g->graph[1] >= 0);
+    words[3] = (int32_t)g->members.size();
     return PAGK_OK;
 }
 

@@ -310,9 +310,9 @@ __device__ __forceinline__ void predict_one(const PredictArgs &a, float rx, floa
     dyo = a.fy * yd + a.cy;
 }
 
-__global__ void __launch_bounds__(256) k_gyro_predict(PredictArgs a)
+// feature i of one launch (k_gyro_predict), or of one camera of a batched launch (pagk_group_kernel.h)
+__device__ __forceinline__ void gyro_predict_body(PredictArgs a, int i)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     if (a.d_rot) {
         for (int k = 0; k < 6; k++) a.K[k] = a.d_rot[k];
@@ -354,6 +354,11 @@ __global__ void __launch_bounds__(256) k_gyro_predict(PredictArgs a)
     a.affine[4 * i + 1] = (float)((double)t00 * a.inv01 + (double)t01 * a.inv00);
     a.affine[4 * i + 2] = (float)((double)t10 * a.inv00 + (double)t11 * a.inv01);
     a.affine[4 * i + 3] = (float)((double)t10 * a.inv01 + (double)t11 * a.inv00);
+}
+
+__global__ void __launch_bounds__(256) k_gyro_predict(PredictArgs a)
+{
+    gyro_predict_body(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---- shared epilogue: SetMatcher + DistortPoints for one feature --------------------------------

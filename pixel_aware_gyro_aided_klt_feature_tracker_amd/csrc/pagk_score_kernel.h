@@ -138,12 +138,12 @@ __global__ void __launch_bounds__(256) k_geometry_scores(ScoreArgs a)
 // The same loops on the output of a device fit (pagk_fit_kernel.h): models (H21 | H12 | F21), the correspondence count
 // and whether each model exists are read from device memory, so that a captured graph replays them with each frame's
 // fit.  A model that was not fitted has no inliers and scores 0; with m <= 8 nothing is scored (:445).
-__global__ void __launch_bounds__(256) k_geometry_scores_fit(const double *models, const int32_t *info,
-                                                             const int32_t *d_n, const float *pts1, const float *pts2,
-                                                             float sigma, uint8_t *inl_H, uint8_t *inl_F, float *scores)
+// (n: the count as the workgroup read it from device memory, the same value in every lane)
+__device__ __forceinline__ void geometry_scores_fit_body(const double *models, const int32_t *info, const int n,
+                                                         const float *pts1, const float *pts2, float sigma,
+                                                         uint8_t *inl_H, uint8_t *inl_F, float *scores)
 {
     const int model = blockIdx.x;
-    const int n = *d_n;
     if (n <= 8) return;
     uint8_t *inl = model == 0 ? inl_H : inl_F;
     if (info[6 * model] == 0) {
@@ -152,6 +152,13 @@ __global__ void __launch_bounds__(256) k_geometry_scores_fit(const double *model
         return;
     }
     score_model(model, models, models + 9, models + 18, pts1, pts2, n, sigma, inl, scores);
+}
+
+__global__ void __launch_bounds__(256) k_geometry_scores_fit(const double *models, const int32_t *info,
+                                                             const int32_t *d_n, const float *pts1, const float *pts2,
+                                                             float sigma, uint8_t *inl_H, uint8_t *inl_F, float *scores)
+{
+    geometry_scores_fit_body(models, info, *d_n, pts1, pts2, sigma, inl_H, inl_F, scores);
 }
 
 }  // namespace pagk

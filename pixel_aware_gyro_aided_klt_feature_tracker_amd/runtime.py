@@ -809,3 +809,54 @@ class DeviceSequence:
             self.ctx.sequence_destroy()
             if self._own:
                 self.ctx.close()
+
+
+class DeviceSequenceGroup:
+    """k cameras stepped together (pagk_sequence_group_*): k contexts on one device, each with a plain sequence of the
+    parameters `sp` (PatchMatch, the caller's candidate lists; with or without the gyro prediction and the validation), every
+    stage of a frame issued once for the whole rig.  Per camera the results are, byte for byte, those of a DeviceSequence
+    fed the same frames, rot9 and candidates.  frames, rot9s and cands are sequences of k numpy arrays (rot9s may be None
+    when nothing predicts); read(j) and read_pair(j) return camera j's arrays."""
+
+    def __init__(self, sp: "capi.SequenceParams", k: int, device: int = 0):
+        if capi.sequence_group_check(sp) != capi.PAGK_OK:
+            raise ValueError("pagk_sequence_group_check refuses these parameters")
+        self.sp, self.k = sp, int(k)
+        self.seqs, self.group = [], None
+        try:
+            for _ in range(self.k):
+                self.seqs.append(DeviceSequence(sp, device))
+            self.group = capi.SequenceGroup([s.ctx for s in self.seqs])
+        except Exception:
+            self.close()
+            raise
+
+    def start(self, frames, cands):
+        self.group.start([np.ascontiguousarray(f, np.uint8) for f in frames], cands)
+
+    def step(self, frames, rot9s=None, cands=None, mode: str = "graph"):
+        if mode not in ("graph", "direct"):
+            raise ValueError(mode)
+        self.group.step([np.ascontiguousarray(f, np.uint8) for f in frames], rot9s, cands,
+                        capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT)
+
+    def read(self, j: int, cap: "int | None" = None) -> dict:
+        return self.seqs[j].read(cap)
+
+    def read_pair(self, j: int, cap: "int | None" = None) -> dict:
+        return self.seqs[j].read_pair(cap)
+
+    def status(self) -> dict:
+        return self.group.status()
+
+    def dissolve(self):
+        """pagk_sequence_group_destroy: the members (self.seqs) are ordinary sequences again and can be stepped alone."""
+        if self.group is not None:
+            self.group.destroy()
+            self.group = None
+
+    def close(self):
+        self.dissolve()
+        for s in self.seqs:
+            s.close()
+        self.seqs = []

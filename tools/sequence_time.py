@@ -17,6 +17,14 @@ fed raw three-channel frames and IMU windows of eight samples, and a plain Patch
 in advance (tests/rectify_ref.c) with the rot9 of tests/gyro_integrate_ref.c; the two are compared byte for byte first.
 
     python tools/sequence_time.py --sensor --out profiles/sensor_sequence_time.json
+
+With --cameras K the script measures a rig instead (runtime.DeviceSequenceGroup, pagk_sequence_group_*): (a) a group of K
+cameras, (b) K sequences of the same configuration stepped one after another, each on its own context and replaying its own
+graphs -- what a rig does without the group -- and (c) one of those sequences alone.  Camera j sees the frames and its own
+rotation of the candidate list.  (a) and (b) are compared byte for byte on every array of every camera and frame first (a
+mismatch is exit code 20); a step of (a) or (b) is one frame of the whole rig, and (b) is synchronised on all its contexts.
+
+    python tools/sequence_time.py --cameras 8 --out profiles/sequence_group_time_k8.json
 """
 import argparse
 import json
@@ -42,6 +50,7 @@ def main() -> int:
     ap.add_argument("--limit", type=float, default=240.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sensor", action="store_true", help="add the sensor sequence and its plain counterpart")
+    ap.add_argument("--cameras", type=int, default=0, help="measure a rig of K cameras: the group against K sequences in turn")
     a = ap.parse_args()
     threading.Timer(a.limit, lambda: os._exit(124)).start()
 
@@ -62,6 +71,8 @@ def main() -> int:
         return capi.sequence_params_default(track=p, lk=capi.lk_params_default(), fit=fitp, tracker=tracker, lk_initial_flow=flow,
                                             width=W, height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0,
                                             cand_cap=len(cand), validate=1, sigma=1.0)
+    if a.cameras:
+        return rig(a, runtime, sp(capi.SEQ_PATCHMATCH, 0), imgs, rot9, cands)
     arms = {"sequence PatchMatch": sp(capi.SEQ_PATCHMATCH, 0), "sequence LK": sp(capi.SEQ_LK, 0),
             "sequence LK gyro-started": sp(capi.SEQ_LK, 1)}
 
@@ -168,6 +179,93 @@ def main() -> int:
     for sq in seqs.values():
         sq.close()
     st.close()
+    os._exit(0)
+
+
+def rig(a, runtime, sp, imgs, rot9, cands) -> int:
+    """--cameras K: the group, K sequences one after another, one sequence."""
+    K = a.cameras
+    lists = [[np.roll(c, 13 * j, axis=0) for c in cands] for j in range(K)]      # camera j's candidate list of frame k
+    group = runtime.DeviceSequenceGroup(sp, K)
+    singles = [runtime.DeviceSequence(sp) for _ in range(K)]
+    names = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state", "info")
+    pair = ("status", "pt_predict", "pt_predict_un", "err")
+
+    # 1. results first: every array of every camera after every frame
+    group.start([imgs[0]] * K, [lists[j][0] for j in range(K)])
+    for j, sq in enumerate(singles):
+        sq.start(imgs[0], lists[j][0])
+    kept = []
+    for k in range(NF):
+        if k:
+            group.step([imgs[k]] * K, [rot9[k - 1]] * K, [lists[j][k] for j in range(K)], mode="graph")
+            for j, sq in enumerate(singles):
+                sq.step(imgs[k], rot9[k - 1], lists[j][k], mode="graph")
+        for j, sq in enumerate(singles):
+            got, want = group.read(j), sq.read()
+            both = [(n, got[n], want[n]) for n in names]
+            if k:
+                gp, wp = group.read_pair(j), sq.read_pair()
+                both += [(n, gp[n], wp[n]) for n in pair]
+            for n, g, w in both:
+                if np.asarray(g).tobytes() != np.asarray(w).tobytes():
+                    print(f"camera {j} frame {k}: {n} of the group differs from the sequence alone: nothing is reported", file=sys.stderr)
+                    os._exit(20)
+        kept.append(int(group.read(0)["state"][2]))
+    print(f"results: the group of {K} equals {K} sequences alone on all {NF} frames; camera 0's survivors per frame: {kept[1:]}")
+
+    # 2. windows taking turns; a step is one frame of the whole rig (arm c: of one camera)
+    def window(step, sync):
+        sync()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            step(1 + i % (NF - 1))
+        sync()
+        return (time.perf_counter() - t0) / a.steps * 1e6
+
+    def step_group(k):
+        group.step([imgs[k]] * K, [rot9[k - 1]] * K, [lists[j][k] for j in range(K)], mode="graph")
+
+    def step_singles(k):
+        for j, sq in enumerate(singles):
+            sq.step(imgs[k], rot9[k - 1], lists[j][k], mode="graph")
+
+    def sync_singles():
+        for sq in singles:
+            sq.ctx.sync()
+
+    def sync_group():
+        for sq in group.seqs:
+            sq.ctx.sync()
+    loops = {f"(a) group of {K}": (step_group, sync_group), f"(b) {K} sequences one after another": (step_singles, sync_singles),
+             "(c) one sequence": (lambda k: singles[0].step(imgs[k], rot9[k - 1], lists[0][k], mode="graph"), singles[0].ctx.sync)}
+    times = {name: [] for name in loops}
+    for step, sync in loops.values():
+        window(step, sync)                                     # warm-up
+    for _ in range(a.windows):
+        for name, (step, sync) in loops.items():
+            times[name].append(window(step, sync))
+    res = {"workload": f"{K} cameras, each {W}x{H}, {N} keypoints, h = 10, validation on, graph mode, {a.steps} steps a window, "
+                       f"{a.windows} windows taking turns",
+           "unit": "us per rig frame for (a) and (b), per frame for (c) (host clock around a window, synchronised at both ends)",
+           "group_status": group.status(), "loops": {}}
+    for name, v in times.items():
+        res["loops"][name] = dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))
+        print(f"{name:36s} {res['loops'][name]['median']:8.1f} us ({res['loops'][name]['min']:.1f} - {res['loops'][name]['max']:.1f})")
+    ga, gb = res["loops"][f"(a) group of {K}"], res["loops"][f"(b) {K} sequences one after another"]
+    res["a_range_below_b_range"] = bool(ga["max"] < gb["min"])
+    try:   # the single path as the parent commit recorded it
+        with open(os.path.join(ROOT, "profiles", "sequence_time.json")) as f:
+            res["parent_one_sequence"] = json.load(f)["loops"]["sequence PatchMatch"]
+    except (OSError, KeyError, ValueError):
+        pass
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    group.close()
+    for sq in singles:
+        sq.close()
     os._exit(0)
 
 
