@@ -7,6 +7,7 @@ import torch
 
 import detect_ref_util as du
 import handover_ref_util as hu
+from sequence_model import restated_handover_detect as _restated_handover_detect
 from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, distributed, host_api, runtime, synth
 
 pytestmark = pytest.mark.gpu
@@ -156,24 +157,6 @@ def test_arguments_are_checked():
 
 
 # ---- the fused hand-over -----------------------------------------------------------------------------------------------
-def _restated_handover_detect(href, dref, p, img, cap, target_n, thr, status, pp, ppu, state, **det):
-    """The composition that defines the fused call, made of the two restatements."""
-    h, w = img.shape
-    cam = hu.camera_of(p)
-    none = np.zeros((0, 2), np.float32)
-    state = np.zeros(8, np.int32) if state is None else np.asarray(state, np.int32)
-    first = hu.ref_handover(href, cam, w, h, cap, target_n, thr, status, pp, ppu, none, state=state)   # its mask, its survivors
-    m, reach = int(first["state"][2]), int(state[1])
-    n_new = target_n - m
-    if (m < thr or not reach) and n_new > 0:
-        d = du.ref_detect(dref, img, first["mask"], n_new, cap=cap, **det)
-    else:
-        d = dict(corners=np.zeros((cap, 2), np.float32), info=np.zeros(8, np.int32), n=0)
-    out = hu.ref_handover(href, cam, w, h, cap, target_n, thr, status, pp, ppu, d["corners"][:d["n"]], state=state)
-    out["info"] = d["info"]
-    return out
-
-
 def _handover_cases(img):
     """(what, status, points, state in): survivors with the top-up running; the top-up not running; the first frame."""
     rng = np.random.default_rng(17)

@@ -7,6 +7,7 @@ import torch
 
 import fast_ref_util as fu
 import handover_ref_util as hu
+from sequence_model import restated_handover_fast as _restated_handover_fast
 from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, distributed, host_api, runtime, synth
 
 pytestmark = pytest.mark.gpu
@@ -172,25 +173,6 @@ def test_arguments_are_checked():
 
 
 # ---- the fused hand-over -----------------------------------------------------------------------------------------------
-def _restated_handover_fast(href, fref, p, img, cap, target_n, thr, status, pp, ppu, state, n_features=0):
-    """The composition that defines the fused call, made of the two restatements: the detector without a mask, then the
-    hand-over on its list."""
-    h, w = img.shape
-    cam = hu.camera_of(p)
-    none = np.zeros((0, 2), np.float32)
-    state = np.zeros(8, np.int32) if state is None else np.asarray(state, np.int32)
-    first = hu.ref_handover(href, cam, w, h, cap, target_n, thr, status, pp, ppu, none, state=state)   # its survivors
-    m, reach = int(first["state"][2]), int(state[1])
-    if (m < thr or not reach) and target_n - m > 0:
-        d = fu.ref_detect(fref, img, None, n_features or target_n)
-        cand, info = d["keypoints"][:d["n"]], d["info"]
-    else:
-        cand, info = none, np.zeros(8, np.int32)
-    out = hu.ref_handover(href, cam, w, h, cap, target_n, thr, status, pp, ppu, cand, state=state)
-    out["info"] = info
-    return out
-
-
 def _handover_cases(img):
     """(what, status, points, state in): the cases of test_detect_gpu.py's _handover_cases."""
     rng = np.random.default_rng(17)
