@@ -1,9 +1,12 @@
 /*
  * pagk_oracle.c -- CPU restatement of the reference's PatchMatch hot path.
  *
- * TEST INFRASTRUCTURE ONLY (see pagk_oracle.h).  PARITY UNPINNED (see pagk_oracle.h
- * and oracle/README.md): written from the reference's source text, not checked
- * against reference outputs, because the reference cannot be built here.
+ * TEST INFRASTRUCTURE ONLY (see pagk_oracle.h).  Written from the reference's source
+ * text.  The PatchMatch path and the free NCC are held bit for bit to that text itself,
+ * compiled unchanged against stand-in headers (oracle/ref_shim,
+ * tests/test_reference_build_cpu.py); the third-party arithmetic -- Eigen's
+ * associations, cv::resize, libm's log -- and everything restated from
+ * gyro_aided_tracker.cpp stay UNPINNED (pagk_oracle.h, oracle/README.md).
  *
  * Build: gcc -O2 -ffp-contract=off -fno-fast-math (oracle/Makefile).  The reference
  * is built with g++ -O3 for baseline x86-64 (CMakeLists.txt:10-11, no -march), i.e.

@@ -6,13 +6,15 @@
  * only as the checker / the timed CPU baseline.  The product (libpagk_hip.so) never
  * links, loads or falls back to this code.
  *
- * PARITY UNPINNED: the reference (C++ on OpenCV + Eigen + glog) cannot be built in
- * this environment and ships no tests or golden vectors, so this restatement could
- * not be checked against reference outputs.  It follows the reference's own source
- * type-for-type (citations on every function); the arithmetic that lives in absent
- * third-party code is restated from the published algorithms and listed in
- * oracle/README.md (cv::resize 2x decimation, Eigen 3.3 fixed-size LLT / triangular
- * solves / norm reduction order, libm log).
+ * PARITY: the reference (C++ on OpenCV + Eigen + glog) cannot be built as a whole and
+ * ships no tests or golden vectors.  Its own text for the PatchMatch path and the free
+ * NCC -- src/patch_match.cpp and src/utils.cpp, compiled unchanged against the stand-in
+ * headers of oracle/ref_shim -- is what this restatement is held to bit for bit
+ * (tests/test_reference_build_cpu.py).  UNPINNED remain the arithmetic that lives in
+ * absent third-party code, restated from the published algorithms and listed in
+ * oracle/README.md (cv::resize, Eigen 3.3 fixed-size LLT / triangular solves / norm
+ * reduction order, libm log) -- the stand-ins call the definitions below for it --
+ * and every function restated from src/gyro_aided_tracker.cpp.
  */
 #ifndef PAGK_ORACLE_H
 #define PAGK_ORACLE_H

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: import this from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg, nowhere else.  The product never loads it.
-PARITY UNPINNED: see pagk_oracle.h.
+What is pinned to the reference and what is not: see pagk_oracle.h.
 """
 from __future__ import annotations
 

@@ -3,7 +3,8 @@
 What these fixtures pin: the CPU oracle's own outputs (oracle/pagk_oracle.c) on small seeded
 cases, one per flag / edge-case combination of the path.  They guard the oracle against
 regressions and give the GPU tests fixed expected outputs.  They do NOT pin the oracle to the
-reference: the reference cannot be built here and ships no vectors (PARITY UNPINNED, see
+reference; the files of tests/golden/ref_shim/ do that for the reference's own text (outputs of its
+compiled PatchMatch sources, generator make_ref_shim.py next to this file; what stays unpinned:
 oracle/pagk_oracle.h).  Run:  python tests/golden/make_golden.py
 """
 import os

@@ -1,7 +1,11 @@
 """The pinning kit (tools/ref_dump/): oracle and HIP path against outputs of the REAL reference.
 
-Nothing under /root/reference can be built or run in the image this repository is developed in (OpenCV, Eigen, glog
-absent), and the reference ships no vectors: parity is unpinned (oracle/README.md).  A maintainer with a working
+The reference as a whole cannot be built in the image this repository is developed in (OpenCV, Eigen, glog absent), and it
+ships no vectors.  Its own text for the PatchMatch path is pinned all the same: src/patch_match.cpp and src/utils.cpp compile
+unchanged against the stand-ins of oracle/ref_shim, and tests/test_reference_build_cpu.py / _gpu.py hold the oracle and the
+HIP path to that binary (fixtures: tests/golden/ref_shim/).  What those tests cannot pin -- the stand-ins take it from the
+oracle's own definitions -- is what THIS file waits for: the Eigen associations, cv::resize on odd parents, libm's log
+(oracle/README.md).  tests/golden/ref/ stays reserved for outputs of a real OpenCV + Eigen build.  A maintainer with a working
 checkout closes that in three commands (tools/ref_dump/dump_patchmatch.cpp, header): the reference itself runs
 PatchMatch::OpticalFlowMultiLevel() (src/patch_match.cpp:79-142) over the committed golden inputs, the results land in
 tests/golden/ref/<case>.npz, and the tests below -- skipped until that directory exists -- then

@@ -8,6 +8,10 @@
 //     python tools/ref_dump/import_ref.py out/ tests/golden/ref/  # -> tests/golden/ref/<case>.npz
 //     python -m pytest tests/test_reference_pin.py                # oracle and HIP against the REFERENCE's outputs
 //
+// (oracle/ref_shim/ref_patchmatch.cpp is this program grown for the stand-in build that IS made in this repository: the
+// reference's two PatchMatch sources against project headers, which pins the reference's own text but none of the Eigen /
+// OpenCV arithmetic.  This file stays the kit for the real libraries.)
+//
 // What it runs is the path itself: PatchMatch::OpticalFlowMultiLevel() (reference src/patch_match.cpp:79-142) on a
 // GyroAidedTracker (ctor #1, include/gyro_aided_tracker.h:109-117) whose public prediction state -- mvPtPredictUn,
 // mvStatus, mvAffineDeformationMatrix -- is filled from the case file, exactly what GyroPredictFeatures() leaves
