@@ -800,18 +800,11 @@ int pagk_oracle_gyro_predict(const pagk_params *cam, int32_t width, int32_t heig
 
     const float hh = (float)half_patch;
     const float cornx[4] = {-hh, hh, -hh, hh}, corny[4] = {-hh, -hh, hh, hh}; /* :73-77 */
-    /* (B B^T): entries are sums of 4 products of small integers: exact */
-    double bbt00 = 0, bbt01 = 0, bbt11 = 0;
-    for (int j = 0; j < 4; j++) {
-        bbt00 += (double)cornx[j] * cornx[j];
-        bbt01 += (double)cornx[j] * corny[j];
-        bbt11 += (double)corny[j] * corny[j];
-    }
-    float m00 = (float)bbt00, m01 = (float)bbt01, m11 = (float)bbt11;
-    double det = (double)m00 * m11 - (double)m01 * m01;
-    double dinv = det != 0 ? 1. / det : 0;
-    float inv00 = (float)(m11 * dinv), inv11 = (float)(m00 * dinv);
-    float inv01 = (float)(-m01 * dinv), inv10 = inv01;
+    /* mMatPatchCorners (2 x 4), its transpose, and (B B^T)^-1 (:77, :167) */
+    float B[8], Bt[8], BBt[4], inv[4];
+    for (int j = 0; j < 4; j++) B[j] = Bt[2 * j] = cornx[j], B[4 + j] = Bt[2 * j + 1] = corny[j];
+    pagk_oracle_mat_mul(2, 4, 2, B, Bt, BBt);
+    pagk_oracle_mat_inv2(BBt, inv);
 
     int n_predict = 0;
     for (int i = 0; i < n; i++) {
@@ -838,20 +831,11 @@ int pagk_oracle_gyro_predict(const pagk_params *cam, int32_t width, int32_t heig
             Cx[j] = cux - ux;
             Cy[j] = cuy - uy;
         }
-        /* matC * B^T (2x4 * 4x2) */
-        double s00 = 0, s01 = 0, s10 = 0, s11 = 0;
-        for (int j = 0; j < 4; j++) {
-            s00 += (double)Cx[j] * cornx[j];
-            s01 += (double)Cx[j] * corny[j];
-            s10 += (double)Cy[j] * cornx[j];
-            s11 += (double)Cy[j] * corny[j];
-        }
-        float t00 = (float)s00, t01 = (float)s01, t10 = (float)s10, t11 = (float)s11;
-        /* (...) * inv  (2x2 * 2x2) */
-        affine[4 * i + 0] = (float)((double)t00 * inv00 + (double)t01 * inv10);
-        affine[4 * i + 1] = (float)((double)t00 * inv01 + (double)t01 * inv11);
-        affine[4 * i + 2] = (float)((double)t10 * inv00 + (double)t11 * inv10);
-        affine[4 * i + 3] = (float)((double)t10 * inv01 + (double)t11 * inv11);
+        /* matC * B^T (2x4 * 4x2), then (...) * inv (2x2 * 2x2) */
+        float Cm[8], CBt[4];
+        for (int j = 0; j < 4; j++) Cm[j] = Cx[j], Cm[4 + j] = Cy[j];
+        pagk_oracle_mat_mul(2, 4, 2, Cm, Bt, CBt);
+        pagk_oracle_mat_mul(2, 2, 2, CBt, inv, &affine[4 * i]);
     }
     return n_predict;
 }
@@ -1221,4 +1205,86 @@ int pagk_oracle_match_features(int32_t n, int32_t cap, const int32_t *count, con
     }
     free(seen);
     return out;
+}
+
+/* ---- the cv::Mat algebra and the sine / cosine next to the path: ONE definition --------------------------------------
+ * Third-party arithmetic (OpenCV gemm / transpose / inv, libm sinf / cosf) as this project defines it; the plain-C
+ * restatement tests/gyro_integrate_ref.c, pagk_oracle_gyro_predict's affine chain and the stand-in cv::Mat of
+ * oracle/ref_shim (under the reference's own src/gyro_aided_tracker.cpp) all call these. */
+
+/* the f64 sine and cosine of the header's ORB "steering" paragraph, for x >= 0 */
+void pagk_oracle_sin_cos(double x, double *sn, double *cs)
+{
+    static const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                        S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    static const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                        C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    double v = x * 0x1.45f306dc9c883p-1 + 0.5;
+    if (!(v < 2147483647.0)) v = 2147483647.0;   /* the conversion saturates (a meaningless angle stays defined) */
+    const int k = (int)v;
+    const double kd = (double)k;
+    const double t = (x - kd * 0x1.921fb544p+0) - kd * 0x1.0b4611a626331p-34;
+    const double z = t * t;
+    const double s = t + t * (z * (S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))))));
+    const double c = 1.0 - z * (0.5 - z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))))));
+    const int q = k & 3;
+    *cs = q == 0 ? c : (q == 1 ? -s : (q == 2 ? -c : s));
+    *sn = q == 0 ? s : (q == 1 ? c : (q == 2 ? -s : -c));
+}
+
+/* (rows x inner) * (inner x cols), row-major f32: f32 factors, an f64 accumulator starting at 0, k ascending, one
+ * rounding to f32 per element.  o may alias a or b. */
+int pagk_oracle_mat_mul(int32_t rows, int32_t inner, int32_t cols, const float *a, const float *b, float *o)
+{
+    if (rows < 1 || inner < 1 || cols < 1 || !a || !b || !o) return PAGK_E_ARG;
+    float *m = (float *)malloc(sizeof(float) * (size_t)rows * (size_t)cols);
+    if (!m) return PAGK_E_NOMEM;
+    for (int r = 0; r < rows; r++)
+        for (int c = 0; c < cols; c++) {
+            double s = 0.0;
+            for (int k = 0; k < inner; k++) s += (double)a[r * inner + k] * (double)b[k * cols + c];
+            m[r * cols + c] = (float)s;
+        }
+    memcpy(o, m, sizeof(float) * (size_t)rows * (size_t)cols);
+    free(m);
+    return PAGK_OK;
+}
+
+/* 3x3 f32 inverse: the f64 cofactor inverse, each element rounded once to f32; a zero determinant gives zeros */
+void pagk_oracle_mat_inv3(const float *m, float *o)
+{
+    double a[9], inv[9];
+    for (int k = 0; k < 9; k++) a[k] = (double)m[k];
+    pagk_oracle_mat_inv3d(a, inv);
+    for (int k = 0; k < 9; k++) o[k] = (float)inv[k];
+}
+
+/* 3x3 f64 inverse (H21.inv(), src/gyro_aided_tracker.cpp:598): cofactors times 1 / det, det expanded along row 0; a zero
+ * determinant gives zeros (what cv::Mat::inv leaves for a singular matrix) */
+void pagk_oracle_mat_inv3d(const double *m, double *o)
+{
+    double a[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) a[r][c] = m[r * 3 + c];
+    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+    const double d = det != 0.0 ? 1.0 / det : 0.0;
+    o[0] = (a[1][1] * a[2][2] - a[1][2] * a[2][1]) * d;
+    o[1] = (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * d;
+    o[2] = (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * d;
+    o[3] = (a[1][2] * a[2][0] - a[1][0] * a[2][2]) * d;
+    o[4] = (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * d;
+    o[5] = (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * d;
+    o[6] = (a[1][0] * a[2][1] - a[1][1] * a[2][0]) * d;
+    o[7] = (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * d;
+    o[8] = (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * d;
+}
+
+/* 2x2 f32 inverse through the f64 determinant (the "gemm / inv() 2x2" row of oracle/README.md) */
+void pagk_oracle_mat_inv2(const float *m, float *o)
+{
+    const double det = (double)m[0] * m[3] - (double)m[1] * m[2];
+    const double dinv = det != 0 ? 1. / det : 0;
+    const float i00 = (float)(m[3] * dinv), i01 = (float)(-m[1] * dinv), i10 = (float)(-m[2] * dinv), i11 = (float)(m[0] * dinv);
+    o[0] = i00, o[1] = i01, o[2] = i10, o[3] = i11;
 }

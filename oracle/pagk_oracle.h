@@ -7,14 +7,15 @@
  * links, loads or falls back to this code.
  *
  * PARITY: the reference (C++ on OpenCV + Eigen + glog) cannot be built as a whole and
- * ships no tests or golden vectors.  Its own text for the PatchMatch path and the free
- * NCC -- src/patch_match.cpp and src/utils.cpp, compiled unchanged against the stand-in
- * headers of oracle/ref_shim -- is what this restatement is held to bit for bit
- * (tests/test_reference_build_cpu.py).  UNPINNED remain the arithmetic that lives in
- * absent third-party code, restated from the published algorithms and listed in
- * oracle/README.md (cv::resize, Eigen 3.3 fixed-size LLT / triangular solves / norm
- * reduction order, libm log) -- the stand-ins call the definitions below for it --
- * and every function restated from src/gyro_aided_tracker.cpp.
+ * ships no tests or golden vectors.  Its own text -- src/patch_match.cpp, src/utils.cpp
+ * and src/gyro_aided_tracker.cpp, compiled unchanged against the stand-in headers of
+ * oracle/ref_shim -- is what this restatement is held to bit for bit
+ * (tests/test_reference_build_cpu.py, tests/test_reference_tracker_cpu.py).  UNPINNED
+ * remain the arithmetic that lives in absent third-party code, restated from the
+ * published algorithms and listed in oracle/README.md (cv::resize, Eigen 3.3 fixed-size
+ * LLT / triangular solves / norm reduction order, libm log, sinf and cosf, the cv::Mat
+ * products and inverses) -- the stand-ins call the definitions below for it -- and the
+ * RANSAC fits and Lucas-Kanade, which the compiled reference takes as inputs.
  */
 #ifndef PAGK_ORACLE_H
 #define PAGK_ORACLE_H
@@ -126,6 +127,18 @@ int pagk_oracle_find_near_neighbors(const pagk_image *ref, const pagk_image *cur
 int pagk_oracle_match_features(int32_t n, int32_t cap, const int32_t *count, const int32_t *nbr_idx,
                                const float *nbr_dist, const float *nbr_ncc, int32_t use_ncc, int32_t *match_query,
                                int32_t *match_train, float *match_dist, float *match_ncc);
+
+/* ---- the cv::Mat algebra and sine / cosine next to the path (third-party arithmetic: this project's definition, oracle/README.md);
+ * one definition for tests/gyro_integrate_ref.c, the affine chain of pagk_oracle_gyro_predict and the stand-in cv::Mat under the
+ * reference's own src/gyro_aided_tracker.cpp -------------------------------------------------------------------------------- */
+/* f64 sine and cosine for x >= 0 (std::sin(float) / std::cos(float) narrow the result to float) */
+void pagk_oracle_sin_cos(double x, double *sn, double *cs);
+/* row-major f32 product: f64 accumulator from 0, k ascending, one rounding per element; o may alias an input */
+int pagk_oracle_mat_mul(int32_t rows, int32_t inner, int32_t cols, const float *a, const float *b, float *o);
+/* f64 cofactor inverses (zero determinant: zeros); the f32 forms round each element once */
+void pagk_oracle_mat_inv3(const float *m, float *o);
+void pagk_oracle_mat_inv3d(const double *m, double *o);
+void pagk_oracle_mat_inv2(const float *m, float *o);
 
 #ifdef __cplusplus
 }

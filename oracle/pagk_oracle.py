@@ -70,6 +70,8 @@ def load():
                                                         i32, i32, vp, vp, vp, vp]
         lib.pagk_oracle_match_features.restype = C.c_int
         lib.pagk_oracle_match_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        lib.pagk_oracle_mat_inv3d.restype = None
+        lib.pagk_oracle_mat_inv3d.argtypes = [vp, vp]
         _lib = lib
     return _lib
 
@@ -260,3 +262,10 @@ def match_features(count, idx, dist, ncc, use_ncc=True):
     if k < 0:
         raise RuntimeError(f"pagk_oracle_match_features: {k}")
     return q[:k], t[:k], d[:k], c[:k]
+
+
+def mat_inv3d(M) -> np.ndarray:
+    """The 3 x 3 f64 inverse the stand-in cv::Mat::inv() uses for H21.inv() (reference src/gyro_aided_tracker.cpp:598) -> 9 doubles."""
+    M, out = _mat3(M), np.zeros(9, np.float64)
+    load().pagk_oracle_mat_inv3d(M.ctypes.data, out.ctypes.data)
+    return out

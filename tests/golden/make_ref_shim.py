@@ -3,6 +3,10 @@ parameters and the six outputs that oracle/_ref/ref_patchmatch wrote -- the refe
 src/utils.cpp, compiled unchanged against the project's stand-ins (oracle/ref_shim), with the oracle's llt / resize / log
 (the `built_with` string of every file says so).  Data the reference's program wrote while running; no program text.
 
+tests/golden/ref_shim/tracker/<case>.npz holds the same for oracle/_ref/ref_tracker -- the reference's own
+src/gyro_aided_tracker.cpp, compiled unchanged under its own header -- over reference_cases.TRACKER_CASES: every input array as
+in_<name>, every array the binary wrote as out_<name> (oracle/ref_shim/ref_tracker.cpp lists them).  Arrays only.
+
 Kept apart from tests/golden/ref/, which stays reserved for a real OpenCV + Eigen build (tools/ref_dump/).
 
 Needs the binary (`make -C oracle ref` where the reference's sources are).  The files are written with fixed zip timestamps:
@@ -59,10 +63,18 @@ def ncc_arrays(c, workdir):
                 out_by_images=by_images, out_by_values=by_values)
 
 
+def tracker_arrays(c, workdir, binary=None):
+    inp = rc.make_tracker_inputs(c)
+    out, proc = rc.run_tracker(c.mode, inp, workdir, c.name, **({"binary": binary} if binary else {}))
+    if out is None:
+        raise RuntimeError(f"{c.name}: ref_tracker --{c.mode} exited with {proc.returncode}: {proc.stderr}")
+    return {**{"in_" + k: v for k, v in inp.items()}, **{"out_" + k: v for k, v in out.items()}}
+
+
 def main():
-    if not os.path.exists(rc.REF_BIN):
-        sys.exit(f"{rc.REF_BIN} is missing: make -C oracle ref (needs the reference's sources)")
-    os.makedirs(rc.FIXTURE_DIR, exist_ok=True)
+    if not os.path.exists(rc.REF_BIN) or not os.path.exists(rc.TRK_BIN):
+        sys.exit(f"{rc.REF_BIN} or {rc.TRK_BIN} is missing: make -C oracle ref (needs the reference's sources)")
+    os.makedirs(rc.TRK_FIXTURE_DIR, exist_ok=True)
     with tempfile.TemporaryDirectory() as workdir:
         for name in rc.committed_cases():
             a = patchmatch_arrays(rc.case(name), workdir)
@@ -74,6 +86,10 @@ def main():
             path = os.path.join(rc.FIXTURE_DIR, c.name + ".npz")
             save_npz(path, **a)
             print(f"{c.name}: n={a['pt_ref'].shape[0]}, {os.path.getsize(path)} bytes")
+        for c in rc.TRACKER_CASES:
+            path = os.path.join(rc.TRK_FIXTURE_DIR, c.name + ".npz")
+            save_npz(path, **tracker_arrays(c, workdir))
+            print(f"tracker/{c.name}: {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

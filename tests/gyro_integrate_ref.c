@@ -1,44 +1,20 @@
 /* gyro_integrate_ref.c -- the "Gyro integration" section of include/pagk.h restated in plain C: the window checks, the
  * window-to-rotation arithmetic (reference src/gyro_aided_tracker.cpp:511-587) and the flow velocity of the sensor sequence
  * (src/frame.cpp:139-143).  Sequential, one rounding per operation (build with -ffp-contract=off); no libm call but sqrtf,
- * which IEEE 754 rounds correctly.  tests/gyro_integrate_ref_util.py builds and loads it. */
+ * which IEEE 754 rounds correctly.  tests/gyro_integrate_ref_util.py builds it against oracle/libpagk_oracle.so and loads it. */
 #include <math.h>
 #include <stdint.h>
 
+#include "../oracle/pagk_oracle.h"
+
 #define GI_MAX_SAMPLES 64
 
-/* the f64 sine and cosine of the header's ORB "steering" paragraph, for x >= 0 */
-static void gi_sin_cos(double x, double *sn, double *cs)
-{
-    static const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
-                        S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    static const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
-                        C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    double v = x * 0x1.45f306dc9c883p-1 + 0.5;
-    if (!(v < 2147483647.0)) v = 2147483647.0;   /* the conversion saturates (a meaningless angle stays defined) */
-    const int k = (int)v;
-    const double kd = (double)k;
-    const double t = (x - kd * 0x1.921fb544p+0) - kd * 0x1.0b4611a626331p-34;
-    const double z = t * t;
-    const double s = t + t * (z * (S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))))));
-    const double c = 1.0 - z * (0.5 - z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))))));
-    const int q = k & 3;
-    *cs = q == 0 ? c : (q == 1 ? -s : (q == 2 ? -c : s));
-    *sn = q == 0 ? s : (q == 1 ? c : (q == 2 ? -s : -c));
-}
-
-/* f32 factors, an f64 accumulator starting at 0, k ascending, one rounding to f32 */
-static void gi_mul3(const float *a, const float *b, float *o)
-{
-    float m[9];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            double s = 0.0;
-            for (int k = 0; k < 3; k++) s += (double)a[r * 3 + k] * (double)b[k * 3 + c];
-            m[r * 3 + c] = (float)s;
-        }
-    for (int k = 0; k < 9; k++) o[k] = m[k];
-}
+/* The f64 sine and cosine, the 3x3 f32 product (f32 factors, an f64 accumulator starting at 0, k ascending, one rounding to
+ * f32) and the f64 cofactor inverse are defined once, in oracle/pagk_oracle.c: the stand-in cv::Mat under the reference's own
+ * src/gyro_aided_tracker.cpp (oracle/ref_shim) calls the same functions. */
+#define gi_sin_cos pagk_oracle_sin_cos
+#define gi_inv3 pagk_oracle_mat_inv3
+static void gi_mul3(const float *a, const float *b, float *o) { pagk_oracle_mat_mul(3, 3, 3, a, b, o); }
 
 static void gi_transpose(const float *a, float *o)
 {
@@ -46,26 +22,6 @@ static void gi_transpose(const float *a, float *o)
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) m[c * 3 + r] = a[r * 3 + c];
     for (int k = 0; k < 9; k++) o[k] = m[k];
-}
-
-/* the f64 cofactor inverse, each element rounded once to f32 */
-static void gi_inv3(const float *m, float *o)
-{
-    double a[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) a[r][c] = (double)m[r * 3 + c];
-    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
-                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
-    const double d = det != 0.0 ? 1.0 / det : 0.0;
-    o[0] = (float)((a[1][1] * a[2][2] - a[1][2] * a[2][1]) * d);
-    o[1] = (float)((a[0][2] * a[2][1] - a[0][1] * a[2][2]) * d);
-    o[2] = (float)((a[0][1] * a[1][2] - a[0][2] * a[1][1]) * d);
-    o[3] = (float)((a[1][2] * a[2][0] - a[1][0] * a[2][2]) * d);
-    o[4] = (float)((a[0][0] * a[2][2] - a[0][2] * a[2][0]) * d);
-    o[5] = (float)((a[0][2] * a[1][0] - a[0][0] * a[1][2]) * d);
-    o[6] = (float)((a[1][0] * a[2][1] - a[1][1] * a[2][0]) * d);
-    o[7] = (float)((a[0][1] * a[2][0] - a[0][0] * a[2][1]) * d);
-    o[8] = (float)((a[0][0] * a[1][1] - a[0][1] * a[1][0]) * d);
 }
 
 /* IntegrateOneGyroMeasurement (:564-587) */

@@ -14,6 +14,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF_SRC = os.path.join(HERE, "gyro_integrate_ref.c")
 SANITIZE_SRC = os.path.join(HERE, "gyro_integrate_sanitize.c")
+ORACLE_DIR = os.path.join(HERE, "..", "oracle")
+# the matrix product, the inverse and the sine / cosine live in the oracle library (one definition, oracle/pagk_oracle.h)
+ORACLE_LINK = ["-L", ORACLE_DIR, "-l:libpagk_oracle.so", f"-Wl,-rpath,{os.path.abspath(ORACLE_DIR)}"]
 F, D = np.float32, np.float64
 MAX_SAMPLES = 64
 CAMERA = (382.613, 382.1, 320.183, 236.455)          # fx fy cx cy
@@ -21,9 +24,11 @@ EYE = np.eye(3, dtype=np.float32)
 
 
 def build_ref(out_dir):
+    from oracle import pagk_oracle
+    pagk_oracle.build()   # the oracle library, when it is missing or older than its source
     so = os.path.join(str(out_dir), "gyro_integrate_ref.so")
     subprocess.run(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so,
-                    REF_SRC, "-lm"], check=True)
+                    REF_SRC, *ORACLE_LINK, "-lm"], check=True)
     lib = C.CDLL(so)
     vp, i32, f32, f64 = C.c_void_p, C.c_int32, C.c_float, C.c_double
     lib.gyro_ref_one_step.restype = None

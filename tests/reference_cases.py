@@ -1,4 +1,5 @@
-"""The case table of the compiled-reference pin: what oracle/_ref/ref_patchmatch -- the reference's own
+"""The case table of the compiled-reference pin, for both binaries (the tracker's part, oracle/_ref/ref_tracker, is the second
+half of this file): what oracle/_ref/ref_patchmatch -- the reference's own
 src/patch_match.cpp and src/utils.cpp, compiled unchanged against the stand-ins of oracle/ref_shim -- is run on, and the
 helpers that run it.  tests/test_reference_build_cpu.py holds the oracle to the binary on these cases,
 tests/golden/make_ref_shim.py writes the binary's outputs to tests/golden/ref_shim/<case>.npz, and
@@ -303,3 +304,316 @@ def load_ncc_fixture(name):
     inp = dict(img_ref=_padded(z["img_ref"], step), img_cur=_padded(z["img_cur"], step), pt_ref=z["pt_ref"], pt_cur=z["pt_cur"],
                affine=z["affine"])
     return inp, z["out_by_images"], z["out_by_values"], str(z["built_with"])
+
+
+# ==== the tracker: oracle/_ref/ref_tracker, the reference's own src/gyro_aided_tracker.cpp compiled unchanged ================
+# One row per statement of the reference that branches (the `what` of every row says which).  Four modes, as ref_tracker.cpp
+# lists them; third-party algorithms (the RANSAC fits, Lucas-Kanade) are inputs of a case.  tests/test_reference_tracker_cpu.py
+# holds the project's CPU side to the binary on this table, tests/golden/make_ref_shim.py writes the binary's outputs to
+# tests/golden/ref_shim/tracker/<case>.npz, tests/test_reference_tracker_gpu.py holds the device entry points to those files.
+TRK_BIN = os.path.join(ROOT, "oracle", "_ref", "ref_tracker")
+TRK_BIN_SAN = os.path.join(ROOT, "oracle", "_ref", "ref_tracker_san")
+TRK_FIXTURE_DIR = os.path.join(FIXTURE_DIR, "tracker")
+TRK_MAX_EXCLUDED_SHARE = 0.10
+_DTYPES = (np.uint8, np.int32, np.float32, np.float64)
+T_REF, T_CUR = 100.0, 100.05
+EXACT_CAMERA = (128.0, 128.0, 80.0, 60.0)   # K * K^-1 is the identity in f32: with a zero rotation a prediction IS its reference point
+RBC_TILTED = synth.rodrigues(np.array([0.3, -0.2, 0.5])).astype(np.float32)
+
+
+def write_arrays(path, arrays):
+    """The array container ref_tracker reads and writes (oracle/ref_shim/ref_tracker.cpp)."""
+    with open(path, "wb") as f:
+        f.write(b"PAGKARR1" + struct.pack("<i", len(arrays)))
+        for name, a in arrays.items():
+            a = np.ascontiguousarray(a)
+            code = next(k for k, t in enumerate(_DTYPES) if a.dtype == t)
+            dims = list(a.shape) + [1] * (3 - a.ndim)
+            f.write(name.encode().ljust(24, b"\0") + struct.pack("<5i", code, a.ndim, *dims) + a.tobytes())
+
+
+def read_arrays(path):
+    raw = open(path, "rb").read()
+    assert raw[:8] == b"PAGKARR1"
+    count, pos, out = struct.unpack_from("<i", raw, 8)[0], 12, {}
+    for _ in range(count):
+        name = raw[pos:pos + 24].rstrip(b"\0").decode()
+        code, ndim, d0, d1, d2 = struct.unpack_from("<5i", raw, pos + 24)
+        shape = (d0, d1, d2)[:ndim]
+        size = int(np.prod(shape, dtype=np.int64)) * np.dtype(_DTYPES[code]).itemsize
+        out[name] = np.frombuffer(raw, _DTYPES[code], int(np.prod(shape, dtype=np.int64)), pos + 44).reshape(shape).copy()
+        pos += 44 + size
+    assert pos == len(raw)
+    return out
+
+
+def run_tracker(mode, inputs, workdir, name, binary=TRK_BIN):
+    """The compiled reference tracker on one case -> (its outputs or None, the finished process).  Its log files
+    (trackFeatures.txt, timeCost.txt) go to a scratch directory under workdir, never into the tree."""
+    fin, fout = os.path.join(str(workdir), name + ".trk"), os.path.join(str(workdir), name + ".out")
+    scratch = os.path.join(str(workdir), name + ".scratch") + "/"
+    write_arrays(fin, inputs)
+    if os.path.exists(fout):
+        os.remove(fout)
+    proc = subprocess.run([binary, "--" + mode, fin, fout, scratch], capture_output=True, text=True)
+    return (read_arrays(fout) if proc.returncode == 0 else None), proc
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackerCase:
+    name: str
+    mode: str          # track | validate | search | klt
+    what: str          # the statements of src/gyro_aided_tracker.cpp the row exists for
+    make: str          # the builder below
+    args: dict = dataclasses.field(default_factory=dict)
+    branches: dict = dataclasses.field(default_factory=dict)   # branch counts seen in the compiled reference's outputs
+
+
+def _window(kind, rng, rate=0.6):
+    """Sample times and rates between T_REF and T_CUR.  `exact`: the first and last sample ON the frame times (tini = tend = 0)."""
+    n = int(kind[1])
+    lo, hi = (T_REF, T_CUR) if kind.endswith("exact") else (T_REF - 0.0013, T_CUR + 0.0021)
+    t = np.linspace(lo, hi, n)
+    w = ((rng.uniform(3 * n).reshape(n, 3) - 0.5) * 2 * rate).astype(np.float32)
+    if "small" in kind:   # the step between samples 1 and 2 turns by d just below / just above 1e-4 (:579)
+        d = 0.99e-4 if "below" in kind else 1.01e-4
+        w[1] = w[2] = np.float32(d / (t[2] - t[1])) * np.array([0.6, 0.0, 0.8], np.float32)
+    if kind.startswith("z"):
+        w[:] = 0
+    return t, w
+
+
+def _frames(width, height, rng, content="texture"):
+    if content == "gray":
+        img = np.full((height, width), 128, np.uint8)
+        return img, img.copy()
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    if content == "period8":   # both frames the same image of period 8 in x and y: patches 8 px apart are equal, NCC and all
+        cell = (rng.uniform(64).reshape(8, 8) * 200 + 20).astype(np.uint8)
+        img = cell[(yy.astype(int) % 8), (xx.astype(int) % 8)]
+        return img, img.copy()
+    tex = synth.Texture(rng)
+    ref = synth._to_u8(tex(xx, yy))
+    if content == "same":
+        return ref, ref.copy()
+    return ref, synth._to_u8(1.05 * tex(xx - SHIFT[0], yy - SHIFT[1]) + 4.0)
+
+
+def _base(width, height, seed, keys_ref, keys_cur=None, *, type_=4, method=1, half=5, ncc=1, dist=(0.0, 0.0, 0.0, 0.0),
+          camera=None, window="w5_offset", rbc=None, bias=(0.0, 0.0, 0.0), content="texture", rate=0.6):
+    rng = synth.SplitMix64(seed)
+    img_ref, img_cur = _frames(width, height, rng, content)
+    cam = camera if camera is not None else (0.6 * width, 0.6 * width, width / 2.0 - 0.5, height / 2.0 - 0.5)
+    t, w = _window(window, rng, rate)
+    keys_ref = np.ascontiguousarray(keys_ref, np.float32).reshape(-1, 2)
+    keys_cur = np.zeros((0, 2), np.float32) if keys_cur is None else np.ascontiguousarray(keys_cur, np.float32).reshape(-1, 2)
+    return dict(img_ref=img_ref, img_cur=img_cur, cam=np.array(list(cam) + list(dist) + [0.0] * (5 - len(dist)), np.float32),
+                cfg=np.array([len(dist), half, type_, method, ncc], np.int32), times=np.array([T_REF, T_CUR]), imu_t=t, imu_w=w,
+                bias=np.array(bias, np.float32), rbc=np.ascontiguousarray(np.eye(3) if rbc is None else rbc, np.float32).reshape(9),
+                keys_ref=keys_ref, keys_ref_un=keys_ref.copy(), keys_cur=keys_cur, keys_cur_un=keys_cur.copy())
+
+
+def _spread(width, height, n, rng, margin=0.0):
+    u = rng.uniform(2 * n)
+    return np.c_[margin + u[0::2] * (width - 1 - 2 * margin), margin + u[1::2] * (height - 1 - 2 * margin)]
+
+
+def make_track(width=160, height=120, n=64, seed=0, borders=True, **kw):
+    """TrackFeatures(): features anywhere in the frame, the border set of the PatchMatch table in front."""
+    rng = synth.SplitMix64(seed ^ 0x7AC)
+    pts = _spread(width, height, n, rng)
+    if borders:
+        b = border_points(width, height)
+        pts[:len(b)] = b
+    return _base(width, height, seed, pts, **kw)
+
+
+def make_track_exact(seed=0, **kw):
+    """A zero rotation under EXACT_CAMERA and no distortion: the predicted and the distorted point equal the reference point,
+    so the border tests of :131 and :134 see exactly 0, the last float below width / height, width / height and beyond."""
+    w, h = 160.0, 120.0
+    below_w, below_h = float(np.nextafter(np.float32(w), np.float32(0))), float(np.nextafter(np.float32(h), np.float32(0)))
+    pts = [(0, 0), (0, 50), (50, 0), (below_w, 50), (50, below_h), (below_w, below_h), (w, 50), (50, h), (w, h), (-0.0, 30),
+           (float(-np.finfo(np.float32).tiny), 30), (30, -0.25), (w + 1, 50), (50, h + 2), (80, 60), (159, 119), (159.5, 60), (80, 119.5)]
+    return _base(160, 120, seed, np.array(pts, np.float64), camera=EXACT_CAMERA, window="z2_exact", **kw)
+
+
+def make_validate(n=64, seed=0, scene="plane", active="all", h21="true", f21="true", noise=0.3, outliers=6, span=10.0):
+    """GeometryValidation(): correspondences of a plane (a homography moves them) or of a sideways translation (the epipolar
+    lines are the image rows; the disparities spread over `span` px, and h21 = "shift" is the translation by their middle); H21 and F21 -- what the RANSAC fits would return -- are the case's inputs."""
+    rng = synth.SplitMix64(seed)
+    p1 = _spread(160, 120, n, rng)
+    H = np.array([[1.02, 0.01, 2.0], [-0.015, 0.99, -1.5], [1e-4, -5e-5, 1.0]])
+    F = np.array([[0.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])   # x2 = x1 + (d, 0): y2 == y1
+    if scene == "plane":
+        q = np.c_[p1, np.ones(n)] @ H.T
+        p2 = q[:, :2] / q[:, 2:]
+    else:
+        p2 = p1 + np.c_[2.0 + span * rng.uniform(n), np.zeros(n)]
+    p2 = p2 + noise * np.c_[_normal(rng, n), _normal(rng, n)]
+    p2[:outliers] += 25.0 * (rng.uniform(2 * outliers).reshape(-1, 2) - 0.5)
+    status = np.ones(n, np.uint8)
+    if active != "all":       # `active` rows on, spread over the table with inactive rows between them (:434-440)
+        status[:] = 0
+        status[np.linspace(0, n - 1, int(active)).round().astype(int)] = 1
+        assert int(status.sum()) == int(active)
+    h_of = dict(true=H, identity=np.eye(3), shift=np.array([[1.0, 0, 2.0 + span / 2], [0, 1.0, 0], [0, 0, 1.0]]), far=np.array([[1.0, 0, 300.0], [0, 1.0, 300.0], [0, 0, 1.0]]),
+                singular=np.array([[1.0, 0, 0], [0, 1.0, 0], [0, 0, 0.0]]), rank1=np.outer([1.0, 2.0, 0.5], [0.5, -1.0, 2.0]))
+    f_of = dict(true=F, zero=np.zeros((3, 3)), far=np.array([[0.0, 0, 0], [0, 0, 0], [0, 0, 1.0]]) + 1e-9 * np.eye(3),
+                tilted=np.array([[0.0, 0.0, 0.02], [0.0, 0.0, -1.0], [-0.02, 1.0, 0.0]]))
+    inp = _base(160, 120, seed, p1, window="w2_exact")
+    inp.update(status=status, pt_predict_un=p2.astype(np.float32), H21=np.ascontiguousarray(h_of[h21]).reshape(9),
+               F21=np.ascontiguousarray(f_of[f21]).reshape(9))
+    return inp
+
+
+def make_search_lists(seed=0, ncc=1):
+    """SearchByGyroPredict() under EXACT_CAMERA with a zero rotation (a prediction is its reference point) on a frame of period
+    8 that both images share: detections 8 px from a query see the query's own patch, so NCC values tie exactly, and so do
+    distances.  Lists of 0, 1, 2 and many neighbours; two and three queries that claim one detection (:993-1007); queries whose
+    neighbours come only with level 2 (:921-925) next to lists found at level 1, which level 2 must leave alone (:793)."""
+    q, d = [], []
+    def add(query, dets):
+        q.append(query), d.extend(dets)
+    add((20, 20), [])                                            # no neighbour at either level
+    add((60, 20), [(60, 20)])                                    # one neighbour, the query's own patch
+    add((100, 20), [(100, 20), (104, 23)])                       # two
+    add((140, 20), [(148, 20), (132, 20), (140, 28), (140, 12), (140, 20), (143, 22), (137, 19)])   # many; four tie in NCC and distance
+    add((20, 60), [(35, 60)])                                    # level 2 only (|dx| = 15 > 10)
+    add((60, 60), [(60, 60), (76, 60)])                          # found at level 1; (76, 60) is in reach of level 2 and must not join
+    add((100, 60), [(108, 60)])                                  # claimed by this query and the next one: erased (:997-1007)
+    add((116, 60), [])
+    add((20, 100), [(28, 100)])                                  # claimed by three: the third finds the set entry and erases nothing
+    add((36, 100), [])
+    add((28, 92), [])
+    add((80, 100), [(83, 101), (78, 97)])                        # two neighbours of other patches: the ratio and the low-NCC rules
+    add((120, 100), [(123, 103)])                                # one neighbour of another patch: rejected unless NCC > TH_NCC_HIGH (:973)
+    add((5, 117), [(5, 117), (2, 119)])                                # within half a patch of the border: the free sampler's `>` clamp
+    add((157, 117), [(157, 117), (159, 119)])
+    return _base(160, 120, seed, np.array(q, np.float64), np.array(d, np.float64), type_=1, camera=EXACT_CAMERA, window="z2_exact",
+                 content="period8", ncc=ncc)
+
+
+def make_search_texture(n=64, seed=0, ncc=1, type_=1, spacing=None, **kw):
+    """SearchByGyroPredict() on a textured pair with a gyro window: detections scattered around the true motion of every
+    feature, so NCC values and distances of every size meet the rules of MatchFeatures (:959-989).  With `spacing` the features
+    lie on a grid wider than the level-1 radius with one detection each on the same image: every feature matches."""
+    rng = synth.SplitMix64(seed ^ 0x5EA)
+    if spacing:
+        gx, gy = np.meshgrid(np.arange(6, 160 - 5, spacing), np.arange(6, 120 - 5, spacing))
+        pts = np.c_[gx.ravel(), gy.ravel()][:n].astype(np.float64)
+        det = pts.copy()
+        det[-6:] += (15.0, 0.0)   # out of reach of level 1, in reach of level 2 -- which must not run (:921)
+        return _base(160, 120, seed, pts, det, type_=type_, camera=EXACT_CAMERA, window="z2_exact", content="same", ncc=ncc, **kw)
+    pts = _spread(160, 120, n, rng)
+    pts[:8] = [(3, 3), (157, 4), (2, 116), (158, 117), (5, 60), (155, 60), (80, 4), (80, 116)]   # within half a patch of the border
+    k = np.array([1, 2, 3, 1, 2, 0, 1, 5] * (n // 8 + 1))[:n]
+    det = np.concatenate([pts[i] + np.array(SHIFT) + 6.0 * np.c_[_normal(rng, k[i]), _normal(rng, k[i])] for i in range(n) if k[i]])
+    det[::5] = np.round(det[::5])
+    return _base(160, 120, seed, pts, det, type_=type_, ncc=ncc, rate=0.15, **kw)
+
+
+def make_klt(n=48, seed=0):
+    """TrackFeatures() type 0 and SearchByOpencvKLT() with Lucas-Kanade's result as an input: errors on both sides of 12 and
+    exactly 12 (>= at :372, < at :1048), status 0 rows, detections 0, 1, 2 and more within the radius of 4 px, distance ratios on
+    both sides of 0.7, a detection two tracks claim (:1089), and disparities beyond 1.5 times the average (:1119)."""
+    rng = synth.SplitMix64(seed ^ 0x417)
+    pts = _spread(160, 120, n, rng, margin=6.0)
+    lk = pts + np.array(SHIFT) + 0.4 * np.c_[_normal(rng, n), _normal(rng, n)]
+    lk[5] = lk[4] + (0.5, 0.0)                # two tracks end next to each other: both claim the detection at lk[4]
+    lk[40:44] += (14.0, 9.0)                  # large disparities
+    status = np.ones(n, np.uint8)
+    status[7::11] = 0
+    err = (rng.uniform(n) * 11.0).astype(np.float32)
+    err[3], err[9], err[13] = 12.0, 12.5, np.float32(np.nextafter(np.float32(12.0), np.float32(0)))
+    k = np.array([1, 2, 1, 0, 1, 0, 3, 1] * (n // 8 + 1))[:n]
+    det = [lk[i] + 0.8 * np.c_[_normal(rng, k[i]), _normal(rng, k[i])] for i in range(n) if k[i]]
+    det += [lk[16:20] + (2.0, 0.0), lk[16:20] + (-2.5, 0.0), lk[20:24] + (0.0, 1.0), lk[20:24] + (0.0, -3.9), lk[24:26] + (4.0, 0.0),
+            lk[26:28] + (2.0, 0.0), lk[26:28] + (-2.0, 0.0)]   # ratios 0.8, 0.26, distance exactly 4, equal distances
+    inp = _base(160, 120, seed, pts, np.concatenate(det), type_=0, window="w3_offset", dist=synth.D435I.dist)
+    lk32 = lk.astype(np.float32)
+    inp.update(lk_pt=lk32, lk_status=status, lk_err=err, lk2_pt=lk32, lk2_status=status, lk2_err=err)
+    return inp
+
+
+TRACKER_CASES = (
+    # ---- integration windows (:521-587) with the prediction (:118-256) and, for types 2-6, PatchMatch and Step 3 (:289-341)
+    TrackerCase("track_t4_w5_offset", "track", "five samples off the frame times: first, middle and last branch of :530-555, tini and tend "
+                "non-zero; tilted Rbc, bias; type 4", "make_track",
+                dict(seed=0x7AC00001, type_=4, window="w5_offset", rbc=RBC_TILTED, bias=(0.01, -0.02, 0.005), dist=synth.D435I.dist)),
+    TrackerCase("track_t1_exact_borders", "track", "type 1; predictions exactly on 0, the last float below width / height, on them "
+                "and outside (:131, :134); two samples on the frame times: the i == 0 && i == n-1 branch, tini = tend = 0",
+                "make_track_exact", dict(seed=0x7AC00002, type_=1)),
+    TrackerCase("track_t1_m2_k1pos_h7", "track", "SINGLE_HOMOGRAPHY (:235-255); k1 = +0.3 pushes distorted points over the border "
+                "where the undistorted one is inside (:134); three samples off the frame times: first and last branch only; half "
+                "patch 7", "make_track", dict(seed=0x7AC00003, type_=1, method=2, half=7, window="w3_offset", dist=(0.3, 0.0, 0.0, 0.0))),
+    TrackerCase("track_t2_w2_offset_odd", "track", "type 2 (no illumination, no affine); two samples off the frame times; 161 x 121",
+                "make_track", dict(width=161, height=121, seed=0x7AC00004, type_=2, window="w2_offset", dist=synth.D435I.dist)),
+    TrackerCase("track_t3_w3_exact_k3", "track", "type 3; three samples on the frame times; five distortion coefficients (:70)",
+                "make_track", dict(seed=0x7AC00005, type_=3, window="w3_exact", dist=(-0.28, 0.07, 0.0002, -0.0003, 0.05), rbc=RBC_TILTED)),
+    TrackerCase("track_t5_nogyro_odd", "track", "type 5: no prediction, the identity affine and copied points of :263-271; 97 x 81",
+                "make_track", dict(width=97, height=81, seed=0x7AC00006, type_=5, window="w5_exact", dist=synth.D435I.dist)),
+    TrackerCase("track_t6_small_below", "track", "type 6 (penalty); one step with d just below 1e-4: deltaR = I + W (:579-580)",
+                "make_track", dict(seed=0x7AC00007, type_=6, window="w5_small_below_offset", bias=(0.002, 0.0, -0.001))),
+    TrackerCase("track_t4_m2_small_above", "track", "type 4 with SINGLE_HOMOGRAPHY; the same step with d just above 1e-4 (:583)",
+                "make_track", dict(seed=0x7AC00008, type_=4, method=2, window="w5_small_above_offset", bias=(0.002, 0.0, -0.001))),
+    TrackerCase("track_t4_none_survive", "track", "constant frames: no feature survives PatchMatch, cnt == 0, the 0/0 average, the "
+                "threshold falls back to the half patch (:305-308)", "make_track",
+                dict(seed=0x7AC00009, type_=4, content="gray", n=32), dict(pm_survivors=0, kept=0)),
+    TrackerCase("track_t4_h1_filters", "track", "half patch 1 under a rotation the images do not follow: rows fail the status, the pixel-"
+                "error and the distance condition of :322", "make_track", dict(seed=0x7AC0000A, type_=4, half=1, rate=2.5, window="w5_offset"),
+                dict(pm_survivors=51, fail_pix_err=1, fail_dist=22, kept=28)),
+    # ---- geometry validation (:429-508, :589-768)
+    TrackerCase("val_8_active", "validate", "8 active rows among 64: skipped, status untouched, returns 0 (:445)", "make_validate",
+                dict(seed=0x7AC00101, active=8, outliers=0)),
+    TrackerCase("val_9_active", "validate", "9 active rows among 64: runs; compaction and vIndeces (:434-440, :473-481)", "make_validate",
+                dict(seed=0x7AC00102, active=9, outliers=0)),
+    TrackerCase("val_select_h", "validate", "a plane with the true H21 and an F21 that fits nothing: RH > 0.45, H's inliers kept", "make_validate",
+                dict(seed=0x7AC00103, scene="plane", f21="tilted", active=40), dict(model="H")),
+    TrackerCase("val_select_f", "validate", "a sideways translation with the true F21 and the identity as H21: RH <= 0.45, F's inliers kept",
+                "make_validate", dict(seed=0x7AC00104, scene="sideways", h21="identity"), dict(model="F")),
+    TrackerCase("val_rh_above", "validate", "disparities within 3.4 px and the translation by their middle as H21: RH = 0.4525 > 0.45 (:463), "
+                "H's inliers kept -- one row fewer than F's", "make_validate",
+                dict(seed=0x7AC00105, scene="sideways", h21="shift", span=3.4), dict(model="H")),
+    TrackerCase("val_rh_below", "validate", "the same scene with the disparities within 3.5 px: RH = 0.4498, F's inliers kept", "make_validate",
+                dict(seed=0x7AC00105, scene="sideways", h21="shift", span=3.5), dict(model="F")),
+    TrackerCase("val_both_zero", "validate", "no row within either threshold: both scores 0, RH = 0/0, F chosen, every row an outlier",
+                "make_validate", dict(seed=0x7AC00107, h21="far", f21="far", n=32), dict(model="F")),
+    TrackerCase("val_zero_f", "validate", "F21 = 0: 0/0 distances, NaN score, no row fails a NaN comparison (:731-739)", "make_validate",
+                dict(seed=0x7AC00108, f21="zero", n=32)),
+    TrackerCase("val_singular_h", "validate", "H21 with a zero last row: H12 = 0, 1/0 and 0 * inf in the transfer errors (:641-662)",
+                "make_validate", dict(seed=0x7AC00109, h21="singular", n=32)),
+    TrackerCase("val_rank1_h", "validate", "H21 of rank 1: the inverse's zero-determinant rule", "make_validate",
+                dict(seed=0x7AC0010A, h21="rank1", n=32)),
+    # ---- SearchByGyroPredict (:859-1009)
+    TrackerCase("search_lists_ncc", "search", "lists of 0, 1, 2 and many neighbours with tied NCC values and distances: the two-stack "
+                "order (:826-842); two and three claims of one detection; level 2 after under 100 matches", "make_search_lists",
+                dict(seed=0x7AC00201, ncc=1)),
+    TrackerCase("search_lists_dist", "search", "the same lists ordered and matched by distance (mbNCC false, :831-836, :977-989)",
+                "make_search_lists", dict(seed=0x7AC00202, ncc=0)),
+    TrackerCase("search_texture_ncc", "search", "every branch of the NCC rule (:961-974) on scattered detections; border patches", "make_search_texture",
+                dict(seed=0x7AC00203, ncc=1, rbc=RBC_TILTED)),
+    TrackerCase("search_texture_dist", "search", "every branch of the distance rule (:978-988)", "make_search_texture",
+                dict(seed=0x7AC00204, ncc=0)),
+    TrackerCase("search_t4_texture", "search", "type 4: the lists are searched around the PatchMatch result with the predicted affine",
+                "make_search_texture", dict(seed=0x7AC00205, ncc=1, type_=4, n=48)),
+    TrackerCase("search_128_matches", "search", "128 features, 122 matches at level 1: at least 100, level 2 does not run (:921)",
+                "make_search_texture", dict(seed=0x7AC00206, n=128, spacing=11)),
+    # ---- TrackFeatures type 0 and SearchByOpencvKLT (:353-380, :1017-1136)
+    TrackerCase("klt_basic", "klt", "Lucas-Kanade's result as an input: the error filters, radiusMatch lists of 0, 1, 2 and more, the "
+                "ratio test, a detection claimed twice, the disparity filter", "make_klt", dict(seed=0x7AC00301)),
+)
+
+
+def tracker_case(name):
+    return next(c for c in TRACKER_CASES if c.name == name)
+
+
+def make_tracker_inputs(c):
+    return globals()[c.make](**c.args)
+
+
+def load_tracker_fixture(name):
+    """-> (inputs, the compiled reference's outputs) of tests/golden/ref_shim/tracker/<name>.npz"""
+    z = np.load(os.path.join(TRK_FIXTURE_DIR, name + ".npz"), allow_pickle=False)
+    return ({k[3:]: z[k] for k in z.files if k.startswith("in_")}, {k[4:]: z[k] for k in z.files if k.startswith("out_")})

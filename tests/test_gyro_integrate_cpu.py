@@ -206,7 +206,8 @@ def test_restatement_under_the_sanitizers(ref, table, restated, tmp_path):
             f.write(c["t"].tobytes() + c["w"].tobytes() + np.asarray(c["bias"], np.float32).tobytes())
     exe = str(tmp_path / "gyro_integrate_sanitize")
     subprocess.run(["gcc", "-std=c99", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-Wall", "-Werror", gu.SANITIZE_SRC, gu.REF_SRC, "-o", exe, "-lm"], check=True)
+                    "-fno-sanitize-recover=all", "-Wall", "-Werror", gu.SANITIZE_SRC, gu.REF_SRC, "-o", exe, *gu.ORACLE_LINK, "-lm"],
+                   check=True)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
     lines = r.stdout.strip().splitlines()
