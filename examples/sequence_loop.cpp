@@ -25,6 +25,12 @@
 // width, height, src_width, src_height, channels, n_cand | float K[9] | dist[4] | Rbc[9] | bias[3] | map_x, map_y (height x
 // width floats each) | one candidate list (n_cand x 2 floats) per frame.  Prints the same state words.
 // Build: add -DPAGK_EXAMPLE_SENSOR -I <pkg>/csrc/host -l:libpagk_tracker.so
+//
+//   sequence_loop <dir> <target_n> <cap> --sensor --cameras K [--detect-fast] [--direct]
+//
+// A rig of sensor sequences (pagk_sequence_group_*_sensor): K contexts, each with the file's maps and Rbc, stepped together
+// with the raw frames and the IMU window as they come from disk.  So that the cameras differ, camera j sees the raw frame
+// (k + j) mod n_frames and (without --detect-fast) the candidate list of that frame.  Prints "camera j frame k: ...".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -97,72 +103,100 @@ static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int nf, int
 }
 
 #ifdef PAGK_EXAMPLE_SENSOR
+// what the sensor forms read from <dir>: the two lists through csrc/host/sequence_io.h, sensor.bin, the raw frames
+struct SensorFiles {
+    std::string dir;
+    std::vector<std::pair<double, std::string>> frames;
+    std::vector<IMU::Point> imu;
+    std::vector<float> K, dist, Rbc, bias, map_x, map_y;
+    std::vector<std::vector<float>> cand;
+    int w = 0, h = 0, ws = 0, hs = 0, cn = 0, nc = 0, nf = 0;
+
+    int load(const std::string &d)
+    {
+        dir = d;
+        if (!pagk_seq::LoadImageList(dir + "/image_file_list.txt", frames) || !pagk_seq::LoadImu(dir + "/imu.txt", imu) || frames.empty())
+            return fprintf(stderr, "cannot read image_file_list.txt / imu.txt in %s\n", dir.c_str()), 1;
+        FILE *f = fopen((dir + "/sensor.bin").c_str(), "rb");
+        int32_t hdr[6];
+        if (!f || fread(hdr, 4, 6, f) != 6 || !read_n(f, K, 9) || !read_n(f, dist, 4) || !read_n(f, Rbc, 9) || !read_n(f, bias, 3))
+            return fprintf(stderr, "cannot read sensor.bin\n"), 1;
+        w = hdr[0], h = hdr[1], ws = hdr[2], hs = hdr[3], cn = hdr[4], nc = hdr[5], nf = (int)frames.size();
+        cand.resize(nf);
+        bool ok = read_n(f, map_x, (size_t)w * h) && read_n(f, map_y, (size_t)w * h);
+        for (int k = 0; ok && k < nf; k++) ok = read_n(f, cand[k], (size_t)nc * 2);
+        fclose(f);
+        return ok ? 0 : (fprintf(stderr, "sensor.bin is short\n"), 1);
+    }
+    // the demo's configuration with the file's camera; the sensor block of the file's frames
+    bool configure(pagk_sequence_params &sp, pagk_sequence_sensor &ss) const
+    {
+        sp.track.half_patch = 5, sp.track.iterations = 10, sp.track.pyramids = 3, sp.track.has_gyro_predict_initial = 1;
+        sp.track.fx = K[0], sp.track.fy = K[4], sp.track.cx = K[2], sp.track.cy = K[5];
+        for (int i = 0; i < 4; i++) sp.track.dist_coef[i] = dist[i];
+        sp.track.n_dist_coef = 4;
+        sp.lk.half_patch = 5;
+        sp.width = w, sp.height = h, sp.new_point_threshold = 0.8 * sp.target_n;
+        sp.cand_cap = nc > 0 ? nc : 1;
+        pagk_sequence_sensor_default(&ss);
+        ss.rectify.channels = cn, ss.raw = 1, ss.src_width = ws, ss.src_height = hs;
+        memcpy(ss.Rbc, Rbc.data(), sizeof ss.Rbc);
+        return pagk_sequence_params_check(&sp) == PAGK_OK && pagk_sequence_sensor_check(&ss) == PAGK_OK;
+    }
+    // "<stamp_ns>.png" of the list stands for the headerless raw frame <dir>/<stamp_ns>.raw
+    bool raw(int k, std::vector<uint8_t> &buf) const
+    {
+        std::string name = frames[k].second;
+        const size_t slash = name.rfind('/'), dot = name.rfind(".png");
+        name = dir + "/" + name.substr(slash == std::string::npos ? 0 : slash + 1, dot - (slash == std::string::npos ? 0 : slash + 1)) + ".raw";
+        buf.resize((size_t)ws * hs * cn);
+        FILE *fi = fopen(name.c_str(), "rb");
+        const bool ok = fi && fread(buf.data(), 1, buf.size(), fi) == buf.size();
+        if (fi) fclose(fi);
+        if (!ok) fprintf(stderr, "cannot read %s\n", name.c_str());
+        return ok;
+    }
+};
+
 // :199-321 on a sensor sequence: a raw frame and the IMU samples since the last frame in, the next pair's keypoints out
 static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode)
 {
     pagk_ctx *ctx = nullptr;
-    std::vector<std::pair<double, std::string>> frames;
-    std::vector<IMU::Point> imu;
-    if (!pagk_seq::LoadImageList(dir + "/image_file_list.txt", frames) || !pagk_seq::LoadImu(dir + "/imu.txt", imu) || frames.empty())
-        return fprintf(stderr, "cannot read image_file_list.txt / imu.txt in %s\n", dir.c_str()), 1;
-    FILE *f = fopen((dir + "/sensor.bin").c_str(), "rb");
-    int32_t hdr[6];
-    std::vector<float> K, dist, Rbc, bias, map_x, map_y;
-    if (!f || fread(hdr, 4, 6, f) != 6 || !read_n(f, K, 9) || !read_n(f, dist, 4) || !read_n(f, Rbc, 9) || !read_n(f, bias, 3))
-        return fprintf(stderr, "cannot read sensor.bin\n"), 1;
-    const int w = hdr[0], h = hdr[1], ws = hdr[2], hs = hdr[3], cn = hdr[4], nc = hdr[5], nf = (int)frames.size();
-    std::vector<std::vector<float>> cand(nf);
-    bool ok = read_n(f, map_x, (size_t)w * h) && read_n(f, map_y, (size_t)w * h);
-    for (int k = 0; ok && k < nf; k++) ok = read_n(f, cand[k], (size_t)nc * 2);
-    fclose(f);
-    if (!ok) return fprintf(stderr, "sensor.bin is short\n"), 1;
-    sp.track.half_patch = 5, sp.track.iterations = 10, sp.track.pyramids = 3, sp.track.has_gyro_predict_initial = 1;
-    sp.track.fx = K[0], sp.track.fy = K[4], sp.track.cx = K[2], sp.track.cy = K[5];
-    for (int i = 0; i < 4; i++) sp.track.dist_coef[i] = dist[i];
-    sp.track.n_dist_coef = 4;
-    sp.lk.half_patch = 5;
-    sp.width = w, sp.height = h, sp.new_point_threshold = 0.8 * sp.target_n;
-    sp.cand_cap = nc > 0 ? nc : 1;
+    SensorFiles in;
+    if (in.load(dir)) return 1;
+    const int ws = in.ws, hs = in.hs, cn = in.cn, nc = in.nc, nf = in.nf;
     pagk_sequence_sensor ss;
-    pagk_sequence_sensor_default(&ss);
-    ss.rectify.channels = cn, ss.raw = 1, ss.src_width = ws, ss.src_height = hs;
-    memcpy(ss.Rbc, Rbc.data(), sizeof ss.Rbc);
-    if (pagk_sequence_params_check(&sp) != PAGK_OK || pagk_sequence_sensor_check(&ss) != PAGK_OK)
-        return fprintf(stderr, "the parameters are refused\n"), 1;
+    if (!in.configure(sp, ss)) return fprintf(stderr, "the parameters are refused\n"), 1;
     int rc = pagk_create(&ctx, 0);
     if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
-    CHECK(pagk_rectify_set_maps(ctx, map_x.data(), map_y.data(), w, h, (int64_t)w * 4));
+    CHECK(pagk_rectify_set_maps(ctx, in.map_x.data(), in.map_y.data(), in.w, in.h, (int64_t)in.w * 4));
     CHECK(pagk_sequence_create_sensor(ctx, &sp, &ss));
     const bool list = sp.detector == 0;
-    pagk_seq::ImuWindow windows(imu);
-    std::vector<uint8_t> raw((size_t)ws * hs * cn);
+    pagk_seq::ImuWindow windows(in.imu);
+    std::vector<uint8_t> raw;
     std::vector<float> keys_un((size_t)sp.cap * 2);
     std::vector<double> t;
     std::vector<float> rates;
     int32_t state[PAGK_HANDOVER_STATE_WORDS];
     double t_prev = 0;
     for (int k = 0; k < nf; k++) {
-        std::string name = frames[k].second;
-        const size_t slash = name.rfind('/'), dot = name.rfind(".png");
-        name = dir + "/" + name.substr(slash == std::string::npos ? 0 : slash + 1, dot - (slash == std::string::npos ? 0 : slash + 1)) + ".raw";
-        FILE *fi = fopen(name.c_str(), "rb");
-        if (!fi || fread(raw.data(), 1, raw.size(), fi) != raw.size()) return fprintf(stderr, "cannot read %s\n", name.c_str()), 1;
-        fclose(fi);
+        if (!in.raw(k, raw)) return 1;
         const pagk_image frame = {raw.data(), ws, hs, (int64_t)ws * cn};
-        const float *c = list ? cand[k].data() : nullptr;
-        const std::vector<IMU::Point> samples = windows.Next(t_prev, frames[k].first);   // :207-218
+        const float *c = list ? in.cand[k].data() : nullptr;
+        const std::vector<IMU::Point> samples = windows.Next(t_prev, in.frames[k].first);   // :207-218
         if (k == 0) {
-            CHECK(pagk_sequence_start_sensor(ctx, &frame, frames[k].first, c, list ? nc : 0));
+            CHECK(pagk_sequence_start_sensor(ctx, &frame, in.frames[k].first, c, list ? nc : 0));
         } else {
             t.clear(), rates.clear();
             for (const IMU::Point &s : samples) {
                 t.push_back(s.t);
                 rates.push_back(s.w.x), rates.push_back(s.w.y), rates.push_back(s.w.z);
             }
-            const pagk_imu_window win = {t_prev, frames[k].first, (int32_t)samples.size(), t.data(), rates.data(), {bias[0], bias[1], bias[2]}};
+            const pagk_imu_window win = {t_prev, in.frames[k].first, (int32_t)samples.size(), t.data(), rates.data(),
+                                         {in.bias[0], in.bias[1], in.bias[2]}};
             CHECK(pagk_sequence_step_sensor(ctx, &frame, &win, c, list ? nc : 0, mode));
         }
-        t_prev = frames[k].first;
+        t_prev = in.frames[k].first;
         CHECK(pagk_sequence_read(ctx, sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr));
         printf("frame %d: %d %d %d %d %d\n", k, state[0], state[1], state[2], state[3], state[4]);
     }
@@ -173,12 +207,81 @@ static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode
     pagk_destroy(ctx);
     return 0;
 }
+
+// ... and for K cameras at once: K sensor sequences, grouped; the lead's calls step them all, nothing is computed outside
+static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int K, int mode)
+{
+    pagk_ctx *ctx = nullptr;   // (the lead: CHECK reports its text)
+    SensorFiles in;
+    if (in.load(dir)) return 1;
+    const int ws = in.ws, hs = in.hs, cn = in.cn, nc = in.nc, nf = in.nf;
+    pagk_sequence_sensor ss;
+    if (!in.configure(sp, ss) || pagk_sequence_group_sensor_check(&sp, &ss) != PAGK_OK)
+        return fprintf(stderr, "--sensor --cameras: PatchMatch with the file's candidate lists or --detect-fast\n"), 1;
+    std::vector<pagk_ctx *> ctxs(K, nullptr);
+    for (int j = 0; j < K; j++) {
+        int rc = pagk_create(&ctxs[j], 0);
+        if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
+        if (j == 0) ctx = ctxs[0];
+        if ((rc = pagk_rectify_set_maps(ctxs[j], in.map_x.data(), in.map_y.data(), in.w, in.h, (int64_t)in.w * 4)) != PAGK_OK ||
+            (rc = pagk_sequence_create_sensor(ctxs[j], &sp, &ss)) != PAGK_OK)
+            return fprintf(stderr, "camera %d -> %s (%s)\n", j, pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
+    }
+    CHECK(pagk_sequence_group_create_sensor(ctxs.data(), K));
+    const bool list = sp.detector == 0;
+    pagk_seq::ImuWindow windows(in.imu);
+    std::vector<std::vector<uint8_t>> raw(K);
+    std::vector<pagk_image> frames(K);
+    std::vector<pagk_imu_window> wins(K);
+    std::vector<const float *> lists(K);
+    std::vector<int32_t> counts(K, nc);
+    std::vector<double> stamps(K), t;
+    std::vector<float> rates, keys_un((size_t)sp.cap * 2);
+    int32_t state[PAGK_HANDOVER_STATE_WORDS];
+    double t_prev = 0;
+    for (int k = 0; k < nf; k++) {
+        for (int j = 0; j < K; j++) {
+            if (!in.raw((k + j) % nf, raw[j])) return 1;
+            frames[j] = pagk_image{raw[j].data(), ws, hs, (int64_t)ws * cn};
+            lists[j] = in.cand[(k + j) % nf].data();
+            stamps[j] = in.frames[k].first;
+        }
+        const std::vector<IMU::Point> samples = windows.Next(t_prev, in.frames[k].first);   // :207-218, one IMU for the rig
+        if (k == 0) {
+            CHECK(pagk_sequence_group_start_sensor(ctx, frames.data(), stamps.data(), list ? lists.data() : nullptr,
+                                                   list ? counts.data() : nullptr));
+        } else {
+            t.clear(), rates.clear();
+            for (const IMU::Point &s : samples) {
+                t.push_back(s.t);
+                rates.push_back(s.w.x), rates.push_back(s.w.y), rates.push_back(s.w.z);
+            }
+            for (int j = 0; j < K; j++)
+                wins[j] = pagk_imu_window{t_prev, in.frames[k].first, (int32_t)samples.size(), t.data(), rates.data(),
+                                          {in.bias[0], in.bias[1], in.bias[2]}};
+            CHECK(pagk_sequence_group_step_sensor(ctx, frames.data(), wins.data(), list ? lists.data() : nullptr,
+                                                  list ? counts.data() : nullptr, mode));
+        }
+        t_prev = in.frames[k].first;
+        for (int j = 0; j < K; j++) {   // a member's reads keep working while it is grouped
+            int rc = pagk_sequence_read(ctxs[j], sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr);
+            if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_read -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
+            printf("camera %d frame %d: %d %d %d %d %d\n", j, k, state[0], state[1], state[2], state[3], state[4]);
+        }
+    }
+    int32_t words[PAGK_SEQ_STATUS_WORDS];
+    CHECK(pagk_sequence_group_status(ctx, words));
+    fprintf(stderr, "%d cameras, %d frames, %d graphs\n", words[3], words[0], words[2]);
+    CHECK(pagk_sequence_group_destroy(ctx));
+    for (int j = K - 1; j >= 0; j--) pagk_destroy(ctxs[j]);   // (each with its sequence)
+    return 0;
+}
 #endif
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor | --cameras K] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
+        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor] [--cameras K] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
         return 1;
     }
     pagk_ctx *ctx = nullptr;
@@ -201,7 +304,8 @@ int main(int argc, char **argv)
     }
     if (sensor) {
 #ifdef PAGK_EXAMPLE_SENSOR
-        return sensor_loop(argv[1], sp, mode);
+        if (cameras < 0 || cameras > 64) return fprintf(stderr, "--cameras: 1 .. 64 cameras\n"), 1;
+        return cameras ? sensor_rig_loop(argv[1], sp, cameras, mode) : sensor_loop(argv[1], sp, mode);
 #else
         return fprintf(stderr, "--sensor: build with -DPAGK_EXAMPLE_SENSOR against csrc/host/sequence_io.h and libpagk_tracker.so\n"), 1;
 #endif

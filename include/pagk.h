@@ -1815,6 +1815,63 @@ int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const flo
  * int32: [0] frames handed in per camera, [1] 1 if the last step was a graph replay, [2] graphs held by the group, [3] k. */
 int pagk_sequence_group_status(pagk_ctx *lead, int32_t *words);
 
+/* ---- The sensor form of the sequence group: k raw frames and k IMU windows in ------------------------------------------ */
+/* What a rig's cameras and IMU deliver.  Every front-end of the reference remaps and grays its frame
+ * (Examples/Demo/RealSenseD435i.cpp:202, src/frame.cpp:81-87), integrates the gyro window (src/gyro_aided_tracker.cpp:511-587)
+ * and tops up with ORBextractor::DetectFeatures (src/frame.cpp:172-179).  A sensor group is k contexts on one device, each
+ * holding a sensor sequence made by pagk_sequence_create_sensor, stepped together: it lifts two items of the plain group's
+ * "Out of scope" list, sensor sequences and the FAST detector.  Per camera every array of pagk_sequence_read,
+ * pagk_sequence_read_pair and pagk_sequence_read_velocity is, after every frame, byte for byte that of the same sensor
+ * sequence stepped alone with the same raw frames, windows and lists.
+ * The stages a sensor step adds are launches of one or a few workgroups, and a group step issues each of them ONCE for all
+ * cameras, the camera being the grid's second dimension, from a second table the lead owns.  The issue order on the lead's
+ * stream is that of one sensor sequence, stage by stage:
+ *   1. the lead's stream waits for what every member's stream has enqueued;
+ *   2. every member's raw rows, window and list go into its own pinned ring block and, one asynchronous copy per member,
+ *      into its own fixed input block;
+ *   3. with raw = 1 the rectification of all cameras, each through its own maps into its own frame slot; then
+ *      pagk_frame_set_device_batch on the slots' own level 0 (with raw = 0 on the input blocks);
+ *   4. the gyro integration of all windows (always, also when nothing predicts), each with its camera's Rbc; the
+ *      prediction when has_gyro_predict_initial; pagk_track_device_batch; Step 3; the validation when `validate`;
+ *   5. the hand-over: fill and holes; with detector 2 the plan and the four kernels of the FAST detector, every camera under
+ *      its own skip word (in one step the top-up may run for one camera and not for another); the keys;
+ *   6. the flow velocities when flow_velocity; then every member's stream waits for the last launch.
+ * Graph mode follows the plain group's rule: the first step runs member by member (that sizes every member's FAST
+ * workspace), the second as batched launches outside a capture, then a parity is captured at its next step once it has run
+ * directly, and replayed afterwards; a captured step is one linear chain.
+ * The sensor group serves PatchMatch with the caller's candidate lists (detector 0) or the FAST detector (detector 2), with
+ * or without the prediction, the validation, raw frames and the flow velocities.  What stays out: the Harris detector,
+ * Lucas-Kanade, cameras whose parameters differ (anything but Rbc and the maps), contexts on different devices. */
+/* PAGK_OK iff pagk_sequence_group_create_sensor accepts sensor sequences of these blocks (Examples/Demo/RealSenseD435i.cpp:
+ * 199-321, one loop per camera): pagk_sequence_params_check and pagk_sequence_sensor_check pass, tracker ==
+ * PAGK_SEQ_PATCHMATCH and detector is 0 or 2; validate, track.has_gyro_predict_initial, raw and flow_velocity may each be 0
+ * or 1.  PAGK_E_ARG (or the nested check's code) otherwise, so for the Harris detector and Lucas-Kanade.  Needs no device. */
+int pagk_sequence_group_sensor_check(const pagk_sequence_params *p, const pagk_sequence_sensor *s);
+/* pagk_sequence_group_create for sensor sequences (Examples/Demo/RealSenseD435i.cpp:199-321, the objects k loops keep between
+ * frames); ctxs[0] is the lead.  Refuses, with a text in pagk_last_error(ctxs[0]), everything pagk_sequence_group_create
+ * refuses, a plain sequence among the members, pagk_sequence_params that are not byte-equal, and pagk_sequence_sensor
+ * blocks that differ in anything but Rbc (every camera has its own extrinsic rotation).  Every member keeps its own maps
+ * (pagk_rectify_set_maps: every camera has its own lens).  pagk_sequence_group_status, pagk_sequence_group_destroy and
+ * pagk_destroy of a member serve both kinds of group; pagk_sequence_group_start and pagk_sequence_group_step return
+ * PAGK_E_ARG on a sensor group, the _sensor calls on a plain one.  While grouped a member's own
+ * pagk_sequence_start_sensor, pagk_sequence_step_sensor and pagk_sequence_destroy return PAGK_E_ARG; its
+ * pagk_sequence_read, pagk_sequence_read_pair, pagk_sequence_read_velocity and pagk_sequence_status keep working.  Calls
+ * outside the group that move a member's FAST workspace, its map entries, its frame slots or its sequence invalidate
+ * the tables like those the plain group names. */
+int pagk_sequence_group_create_sensor(pagk_ctx *const *ctxs, int32_t k);
+/* The k first raw frames (Examples/Demo/RealSenseD435i.cpp:221-235): k times pagk_sequence_start_sensor, raws[j], t[j],
+ * cand[j] and n_cand[j] being camera j's (cand and n_cand NULL with detector 2).  All inputs are checked first: PAGK_E_ARG
+ * with nothing enqueued if one is refused.  May be called again to restart; the group's graphs are kept. */
+int pagk_sequence_group_start_sensor(pagk_ctx *lead, const pagk_image *raws, const double *t, const float *const *cand,
+                                     const int32_t *n_cand);
+/* Raw frame k >= 1 of every camera with its window (Examples/Demo/RealSenseD435i.cpp:237-321), in the issue order above.
+ * raws: k host images; windows: k windows, camera j's the samples between its previous frame and this one; cand, n_cand: k
+ * host lists and their lengths, both NULL with detector 2; mode: PAGK_SEQ_GRAPH or PAGK_SEQ_DIRECT.  Every camera's window
+ * is checked on the host (pagk_imu_window_check with the sequence's imu_cap; t_ref must equal that camera's previous time)
+ * before anything is enqueued: a refusal of any camera's frame, window or list returns PAGK_E_ARG and changes nothing. */
+int pagk_sequence_group_step_sensor(pagk_ctx *lead, const pagk_image *raws, const pagk_imu_window *windows,
+                                    const float *const *cand, const int32_t *n_cand, int32_t mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -436,6 +436,13 @@ def declare(lib) -> None:
                            ("pagk_sequence_group_step", [vp, vp, vp, vp, vp, i32]), ("pagk_sequence_group_status", [vp, vp])):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_sequence_group_create_sensor"):
+        sp, ss = _P(SequenceParams), _P(SequenceSensor)
+        for name, args in (("pagk_sequence_group_sensor_check", [sp, ss]), ("pagk_sequence_group_create_sensor", [vp, i32]),
+                           ("pagk_sequence_group_start_sensor", [vp, vp, vp, vp, vp]),
+                           ("pagk_sequence_group_step_sensor", [vp, vp, vp, vp, vp, i32])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
     if hasattr(lib, "pagk_lk_track_flow"):
         lib.pagk_lk_track_flow.restype = C.c_int
         lib.pagk_lk_track_flow.argtypes = [vp, _P(LkParams), _P(Params), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp,
@@ -614,6 +621,8 @@ EXPORTED_SYMBOLS = [
     "pagk_sequence_create_sensor", "pagk_sequence_start_sensor", "pagk_sequence_step_sensor", "pagk_sequence_read_velocity",
     "pagk_sequence_group_check", "pagk_sequence_group_create", "pagk_sequence_group_destroy", "pagk_sequence_group_start",
     "pagk_sequence_group_step", "pagk_sequence_group_status",
+    "pagk_sequence_group_sensor_check", "pagk_sequence_group_create_sensor", "pagk_sequence_group_start_sensor",
+    "pagk_sequence_group_step_sensor",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
@@ -789,23 +798,36 @@ def sequence_group_check(p: SequenceParams) -> int:
     return int(load().pagk_sequence_group_check(C.byref(p)))
 
 
+def sequence_group_sensor_check(p: SequenceParams, s: "SequenceSensor") -> int:
+    """pagk_sequence_group_sensor_check: PAGK_OK if sensor sequences of these blocks can form a sensor group (needs no device)."""
+    return int(load().pagk_sequence_group_sensor_check(C.byref(p), C.byref(s)))
+
+
 class SequenceGroup:
     """pagk_sequence_group_*: k contexts, each with a plain sequence of the same parameters, stepped together.  contexts[0] is
-    the lead; per camera the results are those of its sequence stepped alone (Context.sequence_read / sequence_read_pair)."""
+    the lead; per camera the results are those of its sequence stepped alone (Context.sequence_read / sequence_read_pair).
+    With sensor=True the contexts hold sensor sequences (pagk_sequence_group_*_sensor): start_sensor and step_sensor take the
+    raw frames, time stamps and IMU windows; with detector 2 candidates is None."""
 
-    def __init__(self, contexts):
+    def __init__(self, contexts, sensor: bool = False):
         self.ctxs = list(contexts)
         self.lib = load()
         self.lead = self.ctxs[0]
         self.k = len(self.ctxs)
+        self.sensor = bool(sensor)
         handles = (C.c_void_p * self.k)(*(c.h for c in self.ctxs))
-        self.lead._check(self.lib.pagk_sequence_group_create(handles, self.k), "pagk_sequence_group_create")
+        if self.sensor:
+            self.lead._check(self.lib.pagk_sequence_group_create_sensor(handles, self.k), "pagk_sequence_group_create_sensor")
+        else:
+            self.lead._check(self.lib.pagk_sequence_group_create(handles, self.k), "pagk_sequence_group_create")
         self.alive = True
 
-    def _inputs(self, frames, candidates):
-        if len(frames) != self.k or len(candidates) != self.k:
+    def _inputs(self, frames, candidates, view=None):
+        if len(frames) != self.k or (candidates is not None and len(candidates) != self.k):
             raise ValueError("one frame and one candidate list per camera")
-        views = (Image * self.k)(*(image_view(f) for f in frames))
+        views = (Image * self.k)(*((view or image_view)(f) for f in frames))
+        if candidates is None:                     # (a detecting sensor group takes no lists)
+            return (frames, None), views, None, None
         lists = [Context._seq_cand(c if c is not None else np.zeros((0, 2), np.float32)) for c in candidates]
         ptrs = (C.c_void_p * self.k)(*(l[1] for l in lists))
         counts = (C.c_int32 * self.k)(*(l[2] for l in lists))
@@ -813,7 +835,7 @@ class SequenceGroup:
 
     def start(self, frames, candidates):
         """pagk_sequence_group_start: the k first frames (host images) and candidate lists."""
-        keep, views, ptrs, counts = self._inputs(frames, candidates)
+        keep, views, ptrs, counts = self._inputs(frames, candidates if candidates is not None else [None] * self.k)
         self.lead._check(self.lib.pagk_sequence_group_start(self.lead.h, views, ptrs, counts), "pagk_sequence_group_start")
 
     def step(self, frames, rot9s=None, candidates=None, mode: int = SEQ_GRAPH):
@@ -822,6 +844,24 @@ class SequenceGroup:
         rot = None if rot9s is None else np.ascontiguousarray(rot9s, np.float32).reshape(self.k, 9)
         self.lead._check(self.lib.pagk_sequence_group_step(self.lead.h, views, _ptr(rot), ptrs, counts, int(mode)),
                          "pagk_sequence_group_step")
+
+    def start_sensor(self, raws, times, candidates=None):
+        """pagk_sequence_group_start_sensor: the k first raw frames, their time stamps and (detector 0) candidate lists."""
+        keep, views, ptrs, counts = self._inputs(raws, candidates, Context._raw_view)
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        if t.shape[0] != self.k:
+            raise ValueError("one time stamp per camera")
+        self.lead._check(self.lib.pagk_sequence_group_start_sensor(self.lead.h, views, _ptr(t), ptrs, counts),
+                         "pagk_sequence_group_start_sensor")
+
+    def step_sensor(self, raws, windows, candidates=None, mode: int = SEQ_GRAPH):
+        """pagk_sequence_group_step_sensor: raw frame k >= 1 of every camera with its ImuWindow; nothing is synchronised."""
+        keep, views, ptrs, counts = self._inputs(raws, candidates, Context._raw_view)
+        if len(windows) != self.k:
+            raise ValueError("one window per camera")
+        wins = (ImuWindow * self.k)(*windows)
+        self.lead._check(self.lib.pagk_sequence_group_step_sensor(self.lead.h, views, wins, ptrs, counts, int(mode)),
+                         "pagk_sequence_group_step_sensor")
 
     def status(self) -> dict:
         """pagk_sequence_group_status -> dict(frames, last_was_graph, graphs, k); nothing is synchronised."""

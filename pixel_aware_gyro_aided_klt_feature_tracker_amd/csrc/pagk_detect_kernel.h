@@ -38,8 +38,9 @@ __device__ __forceinline__ int det_reflect(int i, int n)
 }
 
 // The hand-over's decision in front of the detector: num_predicted, the top-up rule (src/frame.cpp:164-169), n_new (:168).
-__global__ void __launch_bounds__(1024) k_handover_plan(int32_t cap, int32_t target_n, double new_point_threshold,
-                                                        const uint8_t *status, const int32_t *state, int32_t *ctl)
+// (the body is a function of its own so that pagk_group_sensor_kernel.h can run it for one of several cameras per launch)
+__device__ __forceinline__ void handover_plan_body(int32_t cap, int32_t target_n, double new_point_threshold,
+                                                   const uint8_t *status, const int32_t *state, int32_t *ctl)
 {
     __shared__ int32_t s_cnt[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -56,6 +57,12 @@ __global__ void __launch_bounds__(1024) k_handover_plan(int32_t cap, int32_t tar
         ctl[kDetCtlLimit] = topup ? n_new : 0;
         ctl[kDetCtlSkip] = topup ? 0 : 1;
     }
+}
+
+__global__ void __launch_bounds__(1024) k_handover_plan(int32_t cap, int32_t target_n, double new_point_threshold,
+                                                        const uint8_t *status, const int32_t *state, int32_t *ctl)
+{
+    handover_plan_body(cap, target_n, new_point_threshold, status, state, ctl);
 }
 
 // One tile of 64 x 16 pixels per workgroup.  The u8 tile is staged with a halo of 2, the reflection taken there; the

@@ -93,7 +93,8 @@ __device__ __forceinline__ float gyro_dot3(float a0, float a1, float a2, float b
     return (float)s;
 }
 
-__global__ void __launch_bounds__(64) k_gyro_integrate(GyroArgs a)
+// (the body is a function of its own so that pagk_group_sensor_kernel.h can run it for one of several cameras per launch)
+__device__ __forceinline__ void gyro_integrate_body(const GyroArgs &a)
 {
     __shared__ float s_delta[kImuMaxSamples * 9];
     __shared__ float s_mat[3 * 9];   // Rbc | K | K^-1
@@ -185,6 +186,8 @@ __global__ void __launch_bounds__(64) k_gyro_integrate(GyroArgs a)
     }
 }
 
+__global__ void __launch_bounds__(64) k_gyro_integrate(GyroArgs a) { gyro_integrate_body(a); }
+
 struct FlowVelocityArgs {
     const float *normal_cur, *normal_last;   // cap x 2
     const int32_t *index_in_last;            // cap
@@ -196,7 +199,7 @@ struct FlowVelocityArgs {
 
 // Row j of the new key set: ((normal_cur[j] - normal_last[i]) in f32) / (t_cur - t_last) as Point2f / double divides (an f64
 // quotient rounded once); (0, 0) for a row the top-up added and for rows at or beyond the live count.
-__global__ void __launch_bounds__(256) k_flow_velocity(FlowVelocityArgs a)
+__device__ __forceinline__ void flow_velocity_body(const FlowVelocityArgs &a)
 {
     const int j = (int)(blockIdx.x * 256 + threadIdx.x);
     if (j >= a.cap) return;
@@ -210,5 +213,7 @@ __global__ void __launch_bounds__(256) k_flow_velocity(FlowVelocityArgs a)
     }
     reinterpret_cast<float2 *>(a.v)[j] = o;
 }
+
+__global__ void __launch_bounds__(256) k_flow_velocity(FlowVelocityArgs a) { flow_velocity_body(a); }
 
 }  // namespace pagk

@@ -21,6 +21,7 @@
 #include "pagk_orb_levels_kernel.h"
 #include "pagk_gyro_kernel.h"
 #include "pagk_group_kernel.h"
+#include "pagk_group_sensor_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
@@ -100,10 +101,17 @@ struct GroupState {
     bool batched_done = false;   // one step has run as batched launches outside a capture: so have the lead's
     bool direct_done[2] = {}, last_graph = false, table_built = false;
     int graph[2] = {-1, -1};
-    // what the table was built from, per member: a workspace that moved since then invalidates it
+    // The group's kind: k sensor sequences (pagk_sequence_group_create_sensor).  The lead's buf[GROUP_SENSOR] then holds a
+    // second table, of the stages a sensor step adds (pagk_group_sensor_kernel.h): record [parity * k + camera].
+    bool sensor = false;
+    int n_cells = 0;             // (detector 2) the cells of the FAST grid, the same for every member
+    // what the tables were built from, per member: a workspace that moved since then invalidates them
     struct Held {
         const void *fit, *hand, *hint;
         size_t hint_bytes;
+        // the sensor group's: the FAST workspace, the map entries, both frame slots' level 0, the sequence's block
+        const void *fast, *entries, *level0[2], *seq;
+        int rect_w, rect_h, rect_wp;
     };
     std::vector<Held> held;
 };
@@ -150,6 +158,7 @@ struct pagk_ctx {
         DISPATCH_ORDER,  // ... and their dispatch order (pagk_order.h): one int32 per feature slot, beside the hints
         SEQ,           // the sequence the context owns (pagk_sequence_*): input block, two key sets, work arrays, state and info words
         GROUP,         // the sequence group this context leads (pagk_sequence_group_*): the argument table of its batched kernels, 2 k records
+        GROUP_SENSOR,  // ... of k sensor sequences (pagk_sequence_group_*_sensor): the table of the stages they add, 2 k records
         kBufs
     };
     DevBuf buf[kBufs];
@@ -1349,7 +1358,9 @@ int pagk_create(pagk_ctx **out, int device)
     }
     ctx->stream = ctx->own_stream;
     ctx->buf[pagk_ctx::FEAT].mirrored = true;
-    for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER, pagk_ctx::GROUP}) ctx->buf[b].state = true;
+    for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER, pagk_ctx::GROUP,
+                  pagk_ctx::GROUP_SENSOR})
+        ctx->buf[b].state = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
         pagk_destroy(ctx);
@@ -1865,16 +1876,24 @@ int rect_check_src(pagk_ctx *ctx, const pagk_rectify_params *params, int32_t sw,
 }
 
 // the kernel: d_raw -> dst (rect_w x rect_h bytes, pitch rect_w); arguments checked by the caller
-int rect_launch(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_raw, int32_t sw, int32_t sh, int64_t sstep,
-                uint8_t *dst)
+RectArgs rect_args(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_raw, int32_t sw, int32_t sh, int64_t sstep,
+                   uint8_t *dst)
 {
     RectArgs a;
+    memset(&a, 0, sizeof a);
     a.entries = static_cast<const RectEntry *>(ctx->buf[pagk_ctx::RECT_ENTRIES].ptr);
     a.src = static_cast<const uint8_t *>(d_raw);
     a.dst = dst;
     a.src_step = sstep;
     a.W = ctx->rect_w, a.H = ctx->rect_h, a.wp = ctx->rect_wp, a.Ws = sw, a.Hs = sh;
     a.gw0 = params->gray_weight[0], a.gw1 = params->gray_weight[1], a.gw2 = params->gray_weight[2], a.gshift = params->gray_shift;
+    return a;
+}
+
+int rect_launch(pagk_ctx *ctx, const pagk_rectify_params *params, const void *d_raw, int32_t sw, int32_t sh, int64_t sstep,
+                uint8_t *dst)
+{
+    const RectArgs a = rect_args(ctx, params, d_raw, sw, sh, sstep, dst);
     const long long threads = (long long)(a.wp >> 2) * a.H;
     const dim3 grd((unsigned)((threads + 255) / 256)), blk(256);
     const bool pair = sw >= 2;   // the two-taps-per-load form needs a second pixel in every source row
@@ -2668,13 +2687,33 @@ int fast_workspace(pagk_ctx *ctx, const FastGrid &g, int32_t n_features, FastWs 
 }
 
 // FAST in cells and the raw list (step 3 of the definition) of frame slot `s`; d_skip: a device word or NULL.
-int fast_cells_launch(pagk_ctx *ctx, const pagk_fast_params *fp, const FrameSlot &s, const FastGrid &g, const FastWs &ws,
-                      const int32_t *d_skip)
+FastCellArgs fast_cell_args(const pagk_fast_params *fp, const uint8_t *img, int64_t pitch, const FastGrid &g, const FastWs &ws,
+                            const int32_t *d_skip)
 {
     FastCellArgs c;
     memset(&c, 0, sizeof c);
-    c.img = s.img0, c.pitch = s.pitch0, c.g = g, c.t_ini = fp->ini_threshold, c.t_min = fp->min_threshold;
+    c.img = img, c.pitch = pitch, c.g = g, c.t_ini = fp->ini_threshold, c.t_min = fp->min_threshold;
     c.seg_xy = ws.seg_xy, c.seg_score = ws.seg_score, c.cell_cnt = ws.cell_cnt, c.skip = d_skip;
+    return c;
+}
+
+FastTreeArgs fast_tree_args(int32_t n_features, const FastGrid &g, const uint8_t *d_mask, int32_t cap, float *d_keypoints,
+                            float *d_response, int32_t *d_info, const int32_t *d_skip, const FastWs &ws)
+{
+    FastTreeArgs t;
+    memset(&t, 0, sizeof t);
+    t.g = g, t.n_features = n_features, t.cap = cap, t.out_bound = ws.out_bound, t.raw_bound = ws.raw_bound;
+    t.sort_slots = ws.sort_slots, t.ctl = ws.ctl, t.kxy = ws.kxy, t.kscore = ws.kscore, t.knode = ws.knode;
+    for (int k = 0; k < 2; k++) t.box[k] = ws.box[k], t.ncnt[k] = ws.ncnt[k], t.ncand[k] = ws.ncand[k];
+    t.cnt4 = ws.cnt4, t.cbase = ws.cbase, t.split = ws.split, t.sortk = ws.sortk, t.best = ws.best;
+    t.mask = d_mask, t.out_xy = d_keypoints, t.out_resp = d_response, t.info = d_info, t.skip = d_skip;
+    return t;
+}
+
+int fast_cells_launch(pagk_ctx *ctx, const pagk_fast_params *fp, const FrameSlot &s, const FastGrid &g, const FastWs &ws,
+                      const int32_t *d_skip)
+{
+    const FastCellArgs c = fast_cell_args(fp, s.img0, s.pitch0, g, ws, d_skip);
     hipLaunchKernelGGL(k_fast_cells, dim3(ws.n_cells), dim3(256), 0, ctx->stream, c);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_fast_offsets, dim3(1), dim3(1024), 0, ctx->stream, ws.n_cells, (const int32_t *)ws.cell_cnt, ws.cell_off,
@@ -2694,13 +2733,7 @@ int fast_launch(pagk_ctx *ctx, const pagk_fast_params *fp, int32_t n_features, c
 {
     int rc = fast_cells_launch(ctx, fp, s, g, ws, d_skip);
     if (rc) return rc;
-    FastTreeArgs t;
-    memset(&t, 0, sizeof t);
-    t.g = g, t.n_features = n_features, t.cap = cap, t.out_bound = ws.out_bound, t.raw_bound = ws.raw_bound;
-    t.sort_slots = ws.sort_slots, t.ctl = ws.ctl, t.kxy = ws.kxy, t.kscore = ws.kscore, t.knode = ws.knode;
-    for (int k = 0; k < 2; k++) t.box[k] = ws.box[k], t.ncnt[k] = ws.ncnt[k], t.ncand[k] = ws.ncand[k];
-    t.cnt4 = ws.cnt4, t.cbase = ws.cbase, t.split = ws.split, t.sortk = ws.sortk, t.best = ws.best;
-    t.mask = d_mask, t.out_xy = d_keypoints, t.out_resp = d_response, t.info = d_info, t.skip = d_skip;
+    const FastTreeArgs t = fast_tree_args(n_features, g, d_mask, cap, d_keypoints, d_response, d_info, d_skip, ws);
     hipLaunchKernelGGL(k_fast_tree, dim3(1), dim3(1024), 0, ctx->stream, t);
     HIPCHK(ctx, hipGetLastError());
     return PAGK_OK;
@@ -5250,6 +5283,29 @@ int seq_handover(pagk_ctx *ctx, SeqState &q, const uint8_t *status, int slot)
                                       d.index_in_last, d.live, nullptr, q.state);
 }
 
+// the arguments of a sensor sequence's own two kernels: the integration of the window in the input block ...
+GyroArgs seq_gyro_args(const SeqState &q)
+{
+    const pagk_sequence_params &p = q.p;
+    GyroArgs g;
+    memset(&g, 0, sizeof g);
+    g.win = q.in + q.off_win;
+    memcpy(g.Rbc, q.s.Rbc, sizeof g.Rbc);
+    g.fx = p.track.fx, g.fy = p.track.fy, g.cx = p.track.cx, g.cy = p.track.cy;
+    g.Rcl = q.rcl, g.rot9 = q.rot_out;
+    return g;
+}
+
+// ... and the flow velocities of key set c against set 1 - c
+FlowVelocityArgs seq_flow_args(const SeqState &q, int c)
+{
+    FlowVelocityArgs f;
+    memset(&f, 0, sizeof f);
+    f.normal_cur = q.set[c].keys_normal, f.normal_last = q.set[1 - c].keys_normal, f.index_in_last = q.set[c].index_in_last;
+    f.state = q.state, f.win = q.in + q.off_win, f.v = q.vel, f.cap = q.p.cap;
+    return f;
+}
+
 // The work of a frame of parity c: frame slot c is the current frame, slot 1 - c the reference; key set 1 - c holds the
 // reference keypoints, set c receives the next pair's.
 int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
@@ -5260,11 +5316,7 @@ int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
     int rc = seq_frame(ctx, q, c);
     if (rc) return rc;
     if (q.sensor) {   // the window of this pair -> the nine floats the prediction reads (:511-587)
-        GyroArgs g;
-        g.win = q.in + q.off_win;
-        memcpy(g.Rbc, q.s.Rbc, sizeof g.Rbc);
-        g.fx = p.track.fx, g.fy = p.track.fy, g.cx = p.track.cx, g.cy = p.track.cy;
-        g.Rcl = q.rcl, g.rot9 = q.rot_out;
+        const GyroArgs g = seq_gyro_args(q);
         hipLaunchKernelGGL(k_gyro_integrate, dim3(1), dim3(64), 0, ctx->stream, g);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -5300,9 +5352,7 @@ int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
     }
     rc = seq_handover(ctx, q, q.st, c);
     if (rc || !q.sensor || !q.s.flow_velocity) return rc;
-    FlowVelocityArgs f;   // src/frame.cpp:139-143, on the key set just written
-    f.normal_cur = q.set[c].keys_normal, f.normal_last = ref.keys_normal, f.index_in_last = q.set[c].index_in_last;
-    f.state = q.state, f.win = q.in + q.off_win, f.v = q.vel, f.cap = p.cap;
+    const FlowVelocityArgs f = seq_flow_args(q, c);   // src/frame.cpp:139-143, on the key set just written
     hipLaunchKernelGGL(k_flow_velocity, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, ctx->stream, f);
     HIPCHK(ctx, hipGetLastError());
     return PAGK_OK;
@@ -5326,6 +5376,20 @@ bool seq_grouped(pagk_ctx *ctx, const char *what)
     if (!ctx->group) return false;
     snprintf(ctx->err, sizeof(ctx->err), "%s: the context is a member of a sequence group (pagk_sequence_group_step, pagk_sequence_group_destroy)", what);
     return true;
+}
+
+// what every sensor step checks of its window, on the host and before anything is enqueued; the text goes to `to`
+int seq_window_check(pagk_ctx *to, const SeqState &q, const char *what, const pagk_imu_window *window)
+{
+    if (pagk_imu_window_check(window, q.s.imu_cap)) {
+        snprintf(to->err, sizeof(to->err), "%s: the window fails pagk_imu_window_check (imu_cap %d)", what, q.s.imu_cap);
+        return PAGK_E_ARG;
+    }
+    if (q.started && window->t_ref != q.t_last) {
+        snprintf(to->err, sizeof(to->err), "%s: t_ref %.9f is not the previous frame's time %.9f", what, window->t_ref, q.t_last);
+        return PAGK_E_ARG;
+    }
+    return PAGK_OK;
 }
 
 }  // namespace
@@ -5559,7 +5623,7 @@ int pagk_sequence_start(pagk_ctx *ctx, const pagk_image *frame, const float *can
 int pagk_sequence_start_sensor(pagk_ctx *ctx, const pagk_image *raw, double t, const float *cand, int32_t n_cand)
 {
     SeqState *q = seq_of_kind(ctx, "pagk_sequence_start_sensor", true);
-    if (!q || !std::isfinite(t)) return PAGK_E_ARG;
+    if (!q || seq_grouped(ctx, "pagk_sequence_start_sensor") || !std::isfinite(t)) return PAGK_E_ARG;
     return seq_start(ctx, q, raw, cand, n_cand, t);
 }
 
@@ -5629,15 +5693,7 @@ int pagk_sequence_step_sensor(pagk_ctx *ctx, const pagk_image *raw, const pagk_i
                               int32_t n_cand, int32_t mode)
 {
     SeqState *q = seq_of_kind(ctx, "pagk_sequence_step_sensor", true);
-    if (!q) return PAGK_E_ARG;
-    if (pagk_imu_window_check(window, q->s.imu_cap)) {
-        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step_sensor: the window fails pagk_imu_window_check (imu_cap %d)", q->s.imu_cap);
-        return PAGK_E_ARG;
-    }
-    if (q->started && window->t_ref != q->t_last) {
-        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_step_sensor: t_ref %.9f is not the previous frame's time %.9f", window->t_ref, q->t_last);
-        return PAGK_E_ARG;
-    }
+    if (!q || seq_grouped(ctx, "pagk_sequence_step_sensor") || seq_window_check(ctx, *q, "pagk_sequence_step_sensor", window)) return PAGK_E_ARG;
     return seq_step(ctx, q, raw, nullptr, window, cand, n_cand, mode);
 }
 
@@ -5743,6 +5799,19 @@ GroupState *group_of(pagk_ctx *lead, const char *what)
     return lead->group;
 }
 
+// the group of a call of the plain (`sensor` false) or the sensor form; the other kind is refused with a text
+GroupState *group_of_kind(pagk_ctx *lead, const char *what, bool sensor)
+{
+    GroupState *g = group_of(lead, what);
+    if (g && g->sensor != sensor) {
+        snprintf(lead->err, sizeof(lead->err), "%s: the group is %s", what,
+                 g->sensor ? "one of sensor sequences (pagk_sequence_group_start_sensor, pagk_sequence_group_step_sensor)"
+                           : "one of plain sequences (pagk_sequence_group_start, pagk_sequence_group_step)");
+        return nullptr;
+    }
+    return g;
+}
+
 // While a group step is issued every member works on the lead's stream: the batched calls then have nothing to order
 // between streams (no event crosses into a capture), and what falls back to k launches lands in the same chain.
 struct GroupStreams {
@@ -5763,7 +5832,24 @@ struct GroupStreams {
 GroupState::Held group_held(pagk_ctx *c)
 {
     const DevBuf &hint = c->buf[pagk_ctx::PRIO_HINT];
-    return {c->buf[pagk_ctx::FIT].ptr, c->buf[pagk_ctx::HAND].ptr, hint.ptr, hint.bytes};
+    return {c->buf[pagk_ctx::FIT].ptr, c->buf[pagk_ctx::HAND].ptr, hint.ptr, hint.bytes, c->buf[pagk_ctx::FAST].ptr,
+            c->buf[pagk_ctx::RECT_ENTRIES].ptr, {c->slots[0].u8[0], c->slots[1].u8[0]}, c->buf[pagk_ctx::SEQ].ptr,
+            c->rect_w, c->rect_h, c->rect_wp};
+}
+
+bool group_held_equal(const GroupState::Held &a, const GroupState::Held &b, bool sensor)
+{
+    if (a.fit != b.fit || a.hand != b.hand || a.hint != b.hint || a.hint_bytes != b.hint_bytes) return false;
+    return !sensor || (a.fast == b.fast && a.entries == b.entries && a.level0[0] == b.level0[0] && a.level0[1] == b.level0[1] &&
+                       a.seq == b.seq && a.rect_w == b.rect_w && a.rect_h == b.rect_h && a.rect_wp == b.rect_wp);
+}
+
+// the FAST grid and workspace of a detecting member, as handover_launch takes them (reserved by the member's own first step)
+int group_fast(pagk_ctx *ctx, const pagk_sequence_params &p, FastGrid *g, FastWs *fws, int32_t *n_features)
+{
+    if (!fast_grid(p.width, p.height, g)) return PAGK_E_ARG;
+    *n_features = p.fast.n_features ? p.fast.n_features : p.target_n;
+    return *n_features < 1 ? PAGK_E_ARG : fast_workspace(ctx, *g, *n_features, fws);
 }
 
 // Camera j's record of parity c: the arguments its own launches of seq_issue would carry.
@@ -5797,9 +5883,18 @@ int group_record(pagk_ctx *ctx, int c, GroupRec *out)
         return PAGK_E_ARG;
     }
     handover_fill_args(&r.hand, &p.track, p.width, p.height, p.cap, p.target_n, p.new_point_threshold);
-    r.hand.cand_cap = p.cand_cap;
-    r.hand.n_cand = reinterpret_cast<const int32_t *>(q.in + q.off_ncand);
-    r.hand.cand_un = reinterpret_cast<const float *>(q.in + q.off_cand);
+    if (p.detector == 2) {   // (a sensor group's) the detector's list, as handover_launch fills it for one camera
+        FastGrid g;
+        FastWs fws;
+        int32_t n_features;
+        int rc = group_fast(ctx, p, &g, &fws, &n_features);
+        if (rc) return rc;
+        r.hand.cand_cap = fws.out_bound, r.hand.n_cand = q.info, r.hand.cand_un = fws.cand;
+    } else {
+        r.hand.cand_cap = p.cand_cap;
+        r.hand.n_cand = reinterpret_cast<const int32_t *>(q.in + q.off_ncand);
+        r.hand.cand_un = reinterpret_cast<const float *>(q.in + q.off_cand);
+    }
     r.hand.status = q.st, r.hand.pt_predict = q.pp, r.hand.pt_predict_un = q.ppu;
     r.hand.keys = dst.keys, r.hand.keys_un = dst.keys_un, r.hand.keys_normal = dst.keys_normal;
     r.hand.index_in_last = dst.index_in_last, r.hand.live = dst.live, r.hand.mask = static_cast<uint8_t *>(hand.ptr);
@@ -5809,14 +5904,51 @@ int group_record(pagk_ctx *ctx, int c, GroupRec *out)
     return PAGK_OK;
 }
 
-// The table, once per group: after the member-by-member step every buffer a record points into has its final size.
+// Camera j's record of parity c of the stages a sensor step adds: the arguments its own launches of seq_issue would carry
+// (rect_into_slot, k_gyro_integrate, handover_launch's plan and detector, k_flow_velocity).
+int rig_record(pagk_ctx *ctx, int c, RigRec *out)
+{
+    SeqState &q = *ctx->seq;
+    const pagk_sequence_params &p = q.p;
+    RigRec r;
+    memset(&r, 0, sizeof r);
+    const FrameSlot &s = ctx->slots[c];
+    if (q.s.raw) {
+        if (!ctx->buf[pagk_ctx::RECT_ENTRIES].ptr || ctx->rect_w != p.width || ctx->rect_h != p.height || !s.u8[0] || s.w != p.width ||
+            s.h != p.height) {
+            snprintf(ctx->err, sizeof(ctx->err), "the sequence is %d x %d, the maps are now %d x %d (pagk_rectify_set_maps)", p.width,
+                     p.height, ctx->rect_w, ctx->rect_h);
+            return PAGK_E_ARG;
+        }
+        r.rect = rect_args(ctx, &q.s.rectify, q.in, q.s.src_width, q.s.src_height, (int64_t)q.row_bytes, s.u8[0]);
+    }
+    r.gyro = seq_gyro_args(q);
+    if (p.detector == 2) {
+        FastGrid g;
+        FastWs fws;
+        int32_t n_features;
+        int rc = group_fast(ctx, p, &g, &fws, &n_features);
+        if (rc) return rc;
+        r.cap = p.cap, r.target_n = p.target_n, r.new_point_threshold = p.new_point_threshold;
+        r.plan_status = q.st, r.plan_state = q.state, r.plan_ctl = fws.ctl;
+        // level 0 as the pyramid of this parity reads it: the rectified slot, or the gray frame in the input block
+        const uint8_t *img0 = q.s.raw ? s.u8[0] : q.in;
+        r.cells = fast_cell_args(&p.fast, img0, p.width, g, fws, fws.ctl + kFastCtlSkip);
+        r.n_cells = fws.n_cells, r.cell_off = fws.cell_off, r.ctl = fws.ctl, r.kxy = fws.kxy, r.kscore = fws.kscore;
+        r.tree = fast_tree_args(n_features, g, nullptr, fws.out_bound, fws.cand, nullptr, q.info, fws.ctl + kFastCtlSkip, fws);
+    }
+    r.flow = seq_flow_args(q, c);
+    *out = r;
+    return PAGK_OK;
+}
+
+// The tables, once per group: after the member-by-member step every buffer a record points into has its final size.
 int group_table(pagk_ctx *lead, GroupState &g)
 {
     const int k = (int)g.members.size();
     if (g.table_built) {
         for (int j = 0; j < k; j++) {
-            const GroupState::Held h = group_held(g.members[j]);
-            if (h.fit != g.held[j].fit || h.hand != g.held[j].hand || h.hint != g.held[j].hint || h.hint_bytes != g.held[j].hint_bytes) {
+            if (!group_held_equal(group_held(g.members[j]), g.held[j], g.sensor)) {
                 snprintf(lead->err, sizeof(lead->err), "a workspace of member %d moved under the group's table (a call outside the group made it "
                          "grow): destroy the group (pagk_sequence_group_destroy)", j);
                 return PAGK_E_ARG;
@@ -5826,10 +5958,12 @@ int group_table(pagk_ctx *lead, GroupState &g)
     }
     try {
         std::vector<GroupRec> host((size_t)2 * k);
+        std::vector<RigRec> rig(g.sensor ? (size_t)2 * k : 0);
         for (int c = 0; c < 2; c++)
             for (int j = 0; j < k; j++) {
                 pagk_ctx *m = g.members[j];
                 int rc = group_record(m, c, &host[(size_t)c * k + j]);
+                if (!rc && g.sensor) rc = rig_record(m, c, &rig[(size_t)c * k + j]);
                 if (rc) {
                     if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
                     return rc;
@@ -5837,9 +5971,19 @@ int group_table(pagk_ctx *lead, GroupState &g)
             }
         g.held.clear();
         for (int j = 0; j < k; j++) g.held.push_back(group_held(g.members[j]));
+        if (g.sensor) {
+            for (int j = 1; j < k; j++)   // (one launch of the rectification: one grid, one row pitch of the entries)
+                if (g.held[j].rect_wp != g.held[0].rect_wp) {
+                    snprintf(lead->err, sizeof(lead->err), "camera %d's map entries are laid out differently from the lead's", j);
+                    return PAGK_E_ARG;
+                }
+            g.n_cells = rig[0].n_cells;   // (the detector's grid is the size's: one for the group)
+            HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_SENSOR].ptr, rig.data(), rig.size() * sizeof(RigRec),
+                                        hipMemcpyHostToDevice, lead->stream));
+        }
         HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP].ptr, host.data(), host.size() * sizeof(GroupRec), hipMemcpyHostToDevice,
                                     lead->stream));
-        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host is a local)
+        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host and rig are locals)
     } catch (const std::bad_alloc &) {
         return PAGK_E_NOMEM;
     }
@@ -5861,11 +6005,14 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
     const uint8_t *status_in[K];
     pagk_outputs out[K];
     const bool predicts = p.track.has_gyro_predict_initial != 0;
+    const pagk_sequence_sensor &sn = lead->seq->s;
+    const bool raw = g.sensor && sn.raw;
     for (int j = 0; j < k; j++) {
         const SeqState &q = *ctxs[j]->seq;
         const SeqState::KeySet &ref = q.set[1 - c];
         slot_cur[j] = c, slot_ref[j] = 1 - c, width[j] = p.width, height[j] = p.height, step[j] = p.width, n[j] = p.cap;
-        data[j] = q.in;
+        // raw frames: the slot's own level 0, in place, as rect_into_slot builds one camera's pyramid
+        data[j] = raw ? ctxs[j]->slots[c].u8[0] : q.in;
         pt_ref[j] = ref.keys_un, affine[j] = q.aff;
         pt_init[j] = predicts ? q.pu : ref.keys_un;              // (as seq_issue hands them to pagk_track_device)
         status_in[j] = predicts ? q.st_in : ref.live;
@@ -5874,8 +6021,26 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
     const GroupRec *table = static_cast<const GroupRec *>(lead->buf[pagk_ctx::GROUP].ptr) + (size_t)c * k;
     const unsigned kk = (unsigned)k;
     hipStream_t s = lead->stream;
+    const RigRec *rig = g.sensor ? static_cast<const RigRec *>(lead->buf[pagk_ctx::GROUP_SENSOR].ptr) + (size_t)c * k : nullptr;
+    if (raw) {   // every camera's raw frame through its own maps into its own slot (rect_launch's grid and instantiation)
+        const long long threads = (long long)(lead->rect_wp >> 2) * lead->rect_h;
+        const dim3 grd((unsigned)((threads + 255) / 256), kk), blk(256);
+        const bool pair = sn.src_width >= 2;
+        if (sn.rectify.channels == 1) {
+            if (pair) hipLaunchKernelGGL((k_rig_rectify<1, true>), grd, blk, 0, s, rig);
+            else hipLaunchKernelGGL((k_rig_rectify<1, false>), grd, blk, 0, s, rig);
+        } else if (sn.rectify.channels == 3) {
+            if (pair) hipLaunchKernelGGL((k_rig_rectify<3, true>), grd, blk, 0, s, rig);
+            else hipLaunchKernelGGL((k_rig_rectify<3, false>), grd, blk, 0, s, rig);
+        } else {
+            if (pair) hipLaunchKernelGGL((k_rig_rectify<4, true>), grd, blk, 0, s, rig);
+            else hipLaunchKernelGGL((k_rig_rectify<4, false>), grd, blk, 0, s, rig);
+        }
+        HIPCHK(lead, hipGetLastError());
+    }
     int rc = pagk_frame_set_device_batch(ctxs, k, slot_cur, data, width, height, step, p.track.pyramids);
     if (rc) return rc;
+    if (g.sensor) hipLaunchKernelGGL(k_rig_gyro_integrate, dim3(1, kk), dim3(64), 0, s, rig);   // (always, as seq_issue does)
     if (predicts) hipLaunchKernelGGL(k_group_gyro_predict, dim3((unsigned)((p.cap + 255) / 256), kk), dim3(256), 0, s, table);
     HIPCHK(lead, hipGetLastError());
     if ((rc = pagk_track_device_batch(ctxs, k, &p.track, slot_ref, slot_cur, n, pt_ref, pt_init, affine, status_in, out))) return rc;
@@ -5892,7 +6057,18 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
     const int64_t bytes = (int64_t)p.width * p.height;
     hipLaunchKernelGGL(k_group_handover_fill, dim3((unsigned)((bytes + 4095) / 4096), kk), dim3(256), 0, s, table);
     hipLaunchKernelGGL(k_group_handover_holes, dim3((unsigned)(((int64_t)p.cap * 14 + 255) / 256), kk), dim3(256), 0, s, table);
+    if (p.detector == 2) {   // the plan and the detector in front of the keys, every camera under its own skip word
+        const unsigned n_cells = (unsigned)g.n_cells;
+        hipLaunchKernelGGL(k_rig_handover_plan, dim3(1, kk), dim3(1024), 0, s, rig);
+        hipLaunchKernelGGL(k_rig_fast_cells, dim3(n_cells, kk), dim3(256), 0, s, rig);
+        hipLaunchKernelGGL(k_rig_fast_offsets, dim3(1, kk), dim3(1024), 0, s, rig);
+        hipLaunchKernelGGL(k_rig_fast_gather, dim3(n_cells, kk), dim3(256), 0, s, rig);
+        hipLaunchKernelGGL(k_rig_fast_tree, dim3(1, kk), dim3(1024), 0, s, rig);
+        HIPCHK(lead, hipGetLastError());
+    }
     hipLaunchKernelGGL(k_group_handover_keys, dim3(1, kk), dim3(1024), 0, s, table);
+    if (g.sensor && sn.flow_velocity)
+        hipLaunchKernelGGL(k_rig_flow_velocity, dim3((unsigned)((p.cap + 255) / 256), kk), dim3(256), 0, s, rig);
     HIPCHK(lead, hipGetLastError());
     return PAGK_OK;
 }
@@ -5901,9 +6077,10 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
 int group_inputs_check(pagk_ctx *lead, const GroupState &g, const char *what, const pagk_image *frames, const float *const *cand,
                        const int32_t *n_cand)
 {
-    if (!frames || !cand || !n_cand) return PAGK_E_ARG;
+    const bool lists = g.members[0]->seq->p.detector == 0;   // (a detecting group takes no lists, as a detecting sequence)
+    if (!frames || (lists ? !cand || !n_cand : cand || n_cand)) return PAGK_E_ARG;
     for (size_t j = 0; j < g.members.size(); j++)
-        if (seq_inputs_check(*g.members[j]->seq, &frames[j], cand[j], n_cand[j])) {
+        if (seq_inputs_check(*g.members[j]->seq, &frames[j], lists ? cand[j] : nullptr, lists ? n_cand[j] : 0)) {
             snprintf(lead->err, sizeof(lead->err), "%s: camera %zu's frame or candidate list is refused", what, j);
             return PAGK_E_ARG;
         }
@@ -5920,6 +6097,7 @@ void group_drop(GroupState *g)
         id = -1;
     }
     (void)release(lead, lead->buf[pagk_ctx::GROUP]);
+    if (g->sensor) (void)release(lead, lead->buf[pagk_ctx::GROUP_SENSOR]);
     for (pagk_ctx *m : g->members) m->group = nullptr;
     delete g;
 }
@@ -5933,16 +6111,17 @@ int pagk_sequence_group_check(const pagk_sequence_params *p)
     return p->tracker == PAGK_SEQ_PATCHMATCH && p->detector == 0 ? PAGK_OK : PAGK_E_ARG;
 }
 
-int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k)
+// pagk_sequence_group_create (`sensor` false) and pagk_sequence_group_create_sensor: one list of refusals, one GroupState
+static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const char *what)
 {
     if (!ctxs || !ctxs[0]) return PAGK_E_ARG;
     pagk_ctx *lead = ctxs[0];
     auto refuse = [&](const char *why, int j) {
-        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: context %d %s", j, why);
+        snprintf(lead->err, sizeof(lead->err), "%s: context %d %s", what, j, why);
         return PAGK_E_ARG;
     };
     if (k < 1 || k > pagk_ctx::kBatchMaxStreams) {
-        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: k = %d is outside 1 .. %d", k, pagk_ctx::kBatchMaxStreams);
+        snprintf(lead->err, sizeof(lead->err), "%s: k = %d is outside 1 .. %d", what, k, pagk_ctx::kBatchMaxStreams);
         return PAGK_E_ARG;
     }
     for (int j = 0; j < k; j++) {
@@ -5952,15 +6131,24 @@ int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k)
         for (int i = 0; i < j; i++)
             if (ctxs[i] == c) return refuse("is listed twice", j);
         if (!c->seq) return refuse("has no sequence (pagk_sequence_create)", j);
-        if (c->seq->sensor) return refuse("holds a sensor sequence: out of scope of the group", j);
+        if (!sensor && c->seq->sensor)
+            return refuse("holds a sensor sequence: out of scope of the group (pagk_sequence_group_create_sensor)", j);
+        if (sensor && !c->seq->sensor) return refuse("holds a plain sequence (pagk_sequence_group_create)", j);
         if (c->group) return refuse("is a member of a group already", j);
         if (in_capture(c)) return refuse("is inside a graph capture", j);
         if (memcmp(&c->seq->p, &lead->seq->p, sizeof(pagk_sequence_params)) != 0)
             return refuse("is configured differently from the lead: the parameters of a group are byte-equal", j);
+        if (sensor) {   // everything of the sensor block but Rbc: every camera has its own extrinsic rotation
+            pagk_sequence_sensor a = c->seq->s;
+            memcpy(a.Rbc, lead->seq->s.Rbc, sizeof a.Rbc);
+            if (memcmp(&a, &lead->seq->s, sizeof a) != 0)
+                return refuse("is configured differently from the lead: the sensor blocks of a group differ in Rbc only", j);
+        }
     }
-    if (pagk_sequence_group_check(&lead->seq->p)) {
-        snprintf(lead->err, sizeof(lead->err), "pagk_sequence_group_create: the group serves PatchMatch with the caller's candidate lists "
-                 "(pagk_sequence_group_check)");
+    if (sensor ? pagk_sequence_group_sensor_check(&lead->seq->p, &lead->seq->s) : pagk_sequence_group_check(&lead->seq->p)) {
+        snprintf(lead->err, sizeof(lead->err), "%s: the group serves PatchMatch with %s", what,
+                 sensor ? "the caller's candidate lists or the FAST detector (pagk_sequence_group_sensor_check)"
+                        : "the caller's candidate lists (pagk_sequence_group_check)");
         return PAGK_E_ARG;
     }
     HIPCHK(lead, hipSetDevice(lead->device));
@@ -5968,8 +6156,12 @@ int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k)
     int rc = reserve(lead, lead->buf[pagk_ctx::GROUP], align_up((size_t)2 * k * sizeof(GroupRec), kPartAlign), NOT_IN_CAPTURE,
                      "the sequence group's table");
     if (rc) return rc;
+    if (sensor && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_SENSOR], align_up((size_t)2 * k * sizeof(RigRec), kPartAlign),
+                                NOT_IN_CAPTURE, "the sensor group's table")))
+        return rc;
     GroupState *g = new (std::nothrow) GroupState();
     if (!g) return PAGK_E_NOMEM;
+    g->sensor = sensor;
     try {
         g->members.assign(ctxs, ctxs + k);
     } catch (const std::bad_alloc &) {
@@ -5980,6 +6172,20 @@ int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k)
     return PAGK_OK;
 }
 
+int pagk_sequence_group_create(pagk_ctx *const *ctxs, int32_t k) { return group_create(ctxs, k, false, "pagk_sequence_group_create"); }
+
+int pagk_sequence_group_sensor_check(const pagk_sequence_params *p, const pagk_sequence_sensor *s)
+{
+    int rc = pagk_sequence_params_check(p);
+    if (rc || (rc = pagk_sequence_sensor_check(s))) return rc;
+    return p->tracker == PAGK_SEQ_PATCHMATCH && (p->detector == 0 || p->detector == 2) ? PAGK_OK : PAGK_E_ARG;
+}
+
+int pagk_sequence_group_create_sensor(pagk_ctx *const *ctxs, int32_t k)
+{
+    return group_create(ctxs, k, true, "pagk_sequence_group_create_sensor");
+}
+
 int pagk_sequence_group_destroy(pagk_ctx *lead)
 {
     GroupState *g = group_of(lead, "pagk_sequence_group_destroy");
@@ -5988,13 +6194,21 @@ int pagk_sequence_group_destroy(pagk_ctx *lead)
     return PAGK_OK;
 }
 
-int pagk_sequence_group_start(pagk_ctx *lead, const pagk_image *frames, const float *const *cand, const int32_t *n_cand)
+// pagk_sequence_group_start (t NULL) and pagk_sequence_group_start_sensor: k times the member's own start
+static int group_start(pagk_ctx *lead, const char *what, bool sensor, const pagk_image *frames, const double *t,
+                       const float *const *cand, const int32_t *n_cand)
 {
-    GroupState *g = group_of(lead, "pagk_sequence_group_start");
-    if (!g || group_inputs_check(lead, *g, "pagk_sequence_group_start", frames, cand, n_cand)) return PAGK_E_ARG;
-    for (size_t j = 0; j < g->members.size(); j++) {
+    GroupState *g = group_of_kind(lead, what, sensor);
+    if (!g || (sensor && !t) || group_inputs_check(lead, *g, what, frames, cand, n_cand)) return PAGK_E_ARG;
+    const size_t k = g->members.size();
+    for (size_t j = 0; sensor && j < k; j++)
+        if (!std::isfinite(t[j])) {
+            snprintf(lead->err, sizeof(lead->err), "%s: camera %zu's time stamp is not finite", what, j);
+            return PAGK_E_ARG;
+        }
+    for (size_t j = 0; j < k; j++) {
         pagk_ctx *m = g->members[j];
-        int rc = seq_start(m, m->seq, &frames[j], cand[j], n_cand[j], 0.0);
+        int rc = seq_start(m, m->seq, &frames[j], cand ? cand[j] : nullptr, n_cand ? n_cand[j] : 0, sensor ? t[j] : 0.0);
         if (rc) {
             if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %zu: %s", j, m->err);
             return rc;
@@ -6004,12 +6218,24 @@ int pagk_sequence_group_start(pagk_ctx *lead, const pagk_image *frames, const fl
     return PAGK_OK;
 }
 
-int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const float *rot9, const float *const *cand,
-                             const int32_t *n_cand, int32_t mode)
+int pagk_sequence_group_start(pagk_ctx *lead, const pagk_image *frames, const float *const *cand, const int32_t *n_cand)
 {
-    const char *what = "pagk_sequence_group_step";
-    GroupState *gp = group_of(lead, what);
-    if (!gp || group_inputs_check(lead, *gp, what, frames, cand, n_cand) || (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT))
+    return group_start(lead, "pagk_sequence_group_start", false, frames, nullptr, cand, n_cand);
+}
+
+int pagk_sequence_group_start_sensor(pagk_ctx *lead, const pagk_image *raws, const double *t, const float *const *cand,
+                                     const int32_t *n_cand)
+{
+    return group_start(lead, "pagk_sequence_group_start_sensor", true, raws, t, cand, n_cand);
+}
+
+// pagk_sequence_group_step (rot9, no windows) and pagk_sequence_group_step_sensor (windows, no rot9): one issue order
+static int group_step(pagk_ctx *lead, const char *what, bool sensor, const pagk_image *frames, const float *rot9,
+                      const pagk_imu_window *windows, const float *const *cand, const int32_t *n_cand, int32_t mode)
+{
+    GroupState *gp = group_of_kind(lead, what, sensor);
+    if (!gp || (sensor && !windows) || group_inputs_check(lead, *gp, what, frames, cand, n_cand) ||
+        (mode != PAGK_SEQ_GRAPH && mode != PAGK_SEQ_DIRECT))
         return PAGK_E_ARG;
     GroupState &g = *gp;
     const int k = (int)g.members.size();
@@ -6022,10 +6248,17 @@ int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const flo
             return PAGK_E_ARG;
         }
     }
-    if (p.track.has_gyro_predict_initial && !rot9) {
+    if (!sensor && p.track.has_gyro_predict_initial && !rot9) {
         snprintf(lead->err, sizeof(lead->err), "%s: this tracker predicts: rot9 is required", what);
         return PAGK_E_ARG;
     }
+    for (int j = 0; sensor && j < k; j++)   // every camera's window, on the host, before anything is enqueued
+        if (seq_window_check(lead, *g.members[j]->seq, what, &windows[j])) {
+            char text[sizeof lead->err];
+            memcpy(text, lead->err, sizeof text);
+            snprintf(lead->err, sizeof(lead->err), "camera %d: %.*s", j, (int)sizeof(text) - 16, text);
+            return PAGK_E_ARG;
+        }
     HIPCHK(lead, hipSetDevice(lead->device));
     const int c = lead->seq->frames & 1;
     int rc = PAGK_OK;
@@ -6041,7 +6274,9 @@ int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const flo
         // 2. the inputs: each member's ring, each member's fixed block
         for (int j = 0; j < k && !rc; j++) {
             pagk_ctx *m = g.members[j];
-            rc = seq_feed(m, *m->seq, &frames[j], rot9 ? rot9 + 9 * j : nullptr, cand[j], n_cand[j]);
+            rc = seq_feed(m, *m->seq, &frames[j], rot9 ? rot9 + 9 * j : nullptr, cand ? cand[j] : nullptr, n_cand ? n_cand[j] : 0,
+                          sensor ? &windows[j] : nullptr);
+            if (!rc && sensor) m->seq->t_last = windows[j].t_cur;
             if (rc && m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
         }
         if (rc) return rc;
@@ -6093,6 +6328,18 @@ int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const flo
             if (g.members[j]->stream != lead->stream) HIPCHK(lead, hipStreamWaitEvent(g.members[j]->stream, lead->ev_batch, 0));
     }
     return PAGK_OK;
+}
+
+int pagk_sequence_group_step(pagk_ctx *lead, const pagk_image *frames, const float *rot9, const float *const *cand,
+                             const int32_t *n_cand, int32_t mode)
+{
+    return group_step(lead, "pagk_sequence_group_step", false, frames, rot9, nullptr, cand, n_cand, mode);
+}
+
+int pagk_sequence_group_step_sensor(pagk_ctx *lead, const pagk_image *raws, const pagk_imu_window *windows, const float *const *cand,
+                                    const int32_t *n_cand, int32_t mode)
+{
+    return group_step(lead, "pagk_sequence_group_step_sensor", true, raws, nullptr, windows, cand, n_cand, mode);
 }
 
 int pagk_sequence_group_status(pagk_ctx *lead, int32_t *words)

@@ -102,8 +102,9 @@ __device__ __forceinline__ uint32_t rectify_pixel(const RectArgs &a, uint32_t lo
         return (uint32_t)((v[0] * a.gw0 + v[1] * a.gw1 + v[2] * a.gw2 + (1 << (a.gshift - 1))) >> a.gshift);
 }
 
+// (the body is a function of its own so that pagk_group_sensor_kernel.h can run it for one of several cameras per launch)
 template <int CN, bool PAIR>
-__global__ __launch_bounds__(256) void k_rectify(RectArgs a)
+__device__ __forceinline__ void rectify_body(const RectArgs &a)
 {
     const int quads = a.wp >> 2;                                    // threads per destination row
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -123,6 +124,12 @@ __global__ __launch_bounds__(256) void k_rectify(RectArgs a)
     if (left > 1) d[1] = (uint8_t)g1;
     if (left > 2) d[2] = (uint8_t)g2;
     if (left > 3) d[3] = (uint8_t)g3;
+}
+
+template <int CN, bool PAIR>
+__global__ __launch_bounds__(256) void k_rectify(RectArgs a)
+{
+    rectify_body<CN, PAIR>(a);
 }
 
 }  // namespace pagk

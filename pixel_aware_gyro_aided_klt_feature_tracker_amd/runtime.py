@@ -816,29 +816,68 @@ class DeviceSequenceGroup:
     parameters `sp` (PatchMatch, the caller's candidate lists; with or without the gyro prediction and the validation), every
     stage of a frame issued once for the whole rig.  Per camera the results are, byte for byte, those of a DeviceSequence
     fed the same frames, rot9 and candidates.  frames, rot9s and cands are sequences of k numpy arrays (rot9s may be None
-    when nothing predicts); read(j) and read_pair(j) return camera j's arrays."""
+    when nothing predicts); read(j) and read_pair(j) return camera j's arrays.
+    With `sensor` (a capi.SequenceSensor) it is the sensor form (pagk_sequence_group_*_sensor): k sensor sequences, detector 0
+    or 2 (FAST); `rbc` gives every camera its own Rbc (k arrays of nine numbers; default: the block's), `maps` its own
+    rectification maps (k pairs (map_x, map_y), required with raw = 1).  start(frames, cands, t=[...]) takes the raw frames and
+    their time stamps, step(frames, windows=[...], cands=...) one capi.ImuWindow per camera; cands is None with detector 2;
+    read_velocity(j) returns camera j's flow velocities."""
 
-    def __init__(self, sp: "capi.SequenceParams", k: int, device: int = 0):
-        if capi.sequence_group_check(sp) != capi.PAGK_OK:
-            raise ValueError("pagk_sequence_group_check refuses these parameters")
-        self.sp, self.k = sp, int(k)
+    def __init__(self, sp: "capi.SequenceParams", k: int, device: int = 0, sensor: "capi.SequenceSensor | None" = None,
+                 rbc=None, maps=None):
+        ok = capi.sequence_group_check(sp) if sensor is None else capi.sequence_group_sensor_check(sp, sensor)
+        if ok != capi.PAGK_OK:
+            raise ValueError("pagk_sequence_group_check refuses these parameters" if sensor is None else
+                             "pagk_sequence_group_sensor_check refuses these parameters")
+        if sensor is None and (rbc is not None or maps is not None):
+            raise ValueError("rbc and maps belong to the sensor form")
+        if (rbc is not None and len(rbc) != k) or (maps is not None and len(maps) != k):
+            raise ValueError("one Rbc and one pair of maps per camera")
+        self.sp, self.k, self.sensor = sp, int(k), sensor
         self.seqs, self.group = [], None
         try:
-            for _ in range(self.k):
-                self.seqs.append(DeviceSequence(sp, device))
-            self.group = capi.SequenceGroup([s.ctx for s in self.seqs])
+            for j in range(self.k):
+                if sensor is None:
+                    self.seqs.append(DeviceSequence(sp, device))
+                    continue
+                ctx = capi.Context(device)
+                try:
+                    if maps is not None:
+                        ctx.rectify_set_maps(*maps[j])
+                    own = sensor
+                    if rbc is not None:
+                        own = capi.SequenceSensor.from_buffer_copy(sensor)
+                        own.Rbc = (capi.C.c_float * 9)(*[float(x) for x in np.asarray(rbc[j], np.float32).reshape(9)])
+                    seq = DeviceSequence(sp, ctx=ctx, sensor=own)
+                except Exception:
+                    ctx.close()
+                    raise
+                seq._own = True          # (the context was made here: close() closes it)
+                self.seqs.append(seq)
+            self.group = capi.SequenceGroup([s.ctx for s in self.seqs], sensor=sensor is not None)
         except Exception:
             self.close()
             raise
 
-    def start(self, frames, cands):
+    def start(self, frames, cands=None, t=None):
+        if self.sensor is not None:
+            if t is None:
+                raise ValueError("a sensor group starts with the frames' time stamps")
+            return self.group.start_sensor(list(frames), t, cands)       # (raw frames are taken as they are: rows may be padded)
         self.group.start([np.ascontiguousarray(f, np.uint8) for f in frames], cands)
 
-    def step(self, frames, rot9s=None, cands=None, mode: str = "graph"):
+    def step(self, frames, rot9s=None, cands=None, mode: str = "graph", windows=None):
         if mode not in ("graph", "direct"):
             raise ValueError(mode)
-        self.group.step([np.ascontiguousarray(f, np.uint8) for f in frames], rot9s, cands,
-                        capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT)
+        m = capi.SEQ_GRAPH if mode == "graph" else capi.SEQ_DIRECT
+        if self.sensor is not None:
+            if windows is None or rot9s is not None:
+                raise ValueError("a sensor group steps with IMU windows, not with rot9")
+            return self.group.step_sensor(list(frames), windows, cands, m)
+        self.group.step([np.ascontiguousarray(f, np.uint8) for f in frames], rot9s, cands, m)
+
+    def read_velocity(self, j: int, cap: "int | None" = None):
+        return self.seqs[j].read_velocity(cap)
 
     def read(self, j: int, cap: "int | None" = None) -> dict:
         return self.seqs[j].read(cap)

@@ -25,6 +25,10 @@ rotation of the candidate list.  (a) and (b) are compared byte for byte on every
 mismatch is exit code 20); a step of (a) or (b) is one frame of the whole rig, and (b) is synchronised on all its contexts.
 
     python tools/sequence_time.py --cameras 8 --out profiles/sequence_group_time_k8.json
+
+With --cameras K --sensor [--detect-fast] the rig is one of sensor sequences (pagk_sequence_group_*_sensor): raw RGB frames,
+IMU windows and, with --detect-fast, the FAST top-up instead of the lists; the same three arms.
+    python tools/sequence_time.py --cameras 8 --sensor --detect-fast
 """
 import argparse
 import json
@@ -51,6 +55,7 @@ def main() -> int:
     ap.add_argument("--out", default=None)
     ap.add_argument("--sensor", action="store_true", help="add the sensor sequence and its plain counterpart")
     ap.add_argument("--cameras", type=int, default=0, help="measure a rig of K cameras: the group against K sequences in turn")
+    ap.add_argument("--detect-fast", action="store_true", help="with --cameras K --sensor: the FAST top-up instead of the lists")
     a = ap.parse_args()
     threading.Timer(a.limit, lambda: os._exit(124)).start()
 
@@ -71,6 +76,8 @@ def main() -> int:
         return capi.sequence_params_default(track=p, lk=capi.lk_params_default(), fit=fitp, tracker=tracker, lk_initial_flow=flow,
                                             width=W, height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0,
                                             cand_cap=len(cand), validate=1, sigma=1.0)
+    if a.cameras and a.sensor:
+        return rig_sensor(a, capi, runtime, sp(capi.SEQ_PATCHMATCH, 0), p, imgs, cands)
     if a.cameras:
         return rig(a, runtime, sp(capi.SEQ_PATCHMATCH, 0), imgs, rot9, cands)
     arms = {"sequence PatchMatch": sp(capi.SEQ_PATCHMATCH, 0), "sequence LK": sp(capi.SEQ_LK, 0),
@@ -265,6 +272,131 @@ def rig(a, runtime, sp, imgs, rot9, cands) -> int:
             json.dump(res, f, indent=1)
     group.close()
     for sq in singles:
+        sq.close()
+    os._exit(0)
+
+
+def rig_sensor(a, capi, runtime, sp, p, imgs, cands) -> int:
+    """--cameras K --sensor [--detect-fast]: the sensor group, K sensor sequences one after another on their own streams, one
+    sensor sequence.  Raw RGB frames of 752 x 480 through the mild lens maps; camera j sees the frames rolled by 3 j columns, its
+    own Rbc (a roll of 0.01 j about the optical axis) and, without --detect-fast, its own lists."""
+    import gyro_integrate_ref_util as gu
+    import rectify_ref_util as ru
+    K = a.cameras
+    if a.detect_fast:
+        sp.detector, sp.cand_cap = 2, 0
+    mx, my = ru.lens_maps(ru.MILD, W, H)
+    raws = [[np.ascontiguousarray(np.stack([im, np.roll(im, 1, axis=1), 255 - np.roll(im, 2, axis=0)], axis=2))
+             for im in (np.roll(im, 3 * j, axis=1) for im in imgs)] for j in range(K)]
+    lists = [[np.roll(c, 13 * j, axis=0) for c in cands] for j in range(K)]
+    rbc = [gu.rodrigues64((0.0, 0.0, 0.01 * j)).astype(np.float32) for j in range(K)]
+    dt, t0 = 1.0 / 30.0, 50.0
+    wins = [[capi.imu_window(w["t_ref"], w["t_cur"], w["t"], w["w"], w["bias"])
+             for w in (gu.constant_rate_window(rbc[j].astype(np.float64) @ np.array((0.004, -0.005, 0.006)), t0 + (k - 1) * dt, t0 + k * dt)
+                       for k in range(1, NF))] for j in range(K)]
+    sensor = capi.sequence_sensor_default(rectify=capi.rectify_params_default(channels=3), raw=1, src_width=W, src_height=H)
+    group = runtime.DeviceSequenceGroup(sp, K, sensor=sensor, rbc=rbc, maps=[(mx, my)] * K)
+    singles = []
+    for j in range(K):
+        c = capi.Context(0)
+        c.rectify_set_maps(mx, my)
+        own = capi.SequenceSensor.from_buffer_copy(sensor)
+        own.Rbc = (capi.C.c_float * 9)(*[float(x) for x in rbc[j].reshape(9)])
+        singles.append(runtime.DeviceSequence(sp, ctx=c, sensor=own))
+    names = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state", "info")
+    pair = ("status", "pt_predict", "pt_predict_un", "err")
+    cand = (lambda j, k: None) if a.detect_fast else (lambda j, k: lists[j][k])
+
+    def group_frame(k):
+        cs = None if a.detect_fast else [lists[j][k] for j in range(K)]
+        if k == 0:
+            group.start([raws[j][0] for j in range(K)], cs, t=[t0] * K)
+        else:
+            group.step([raws[j][k] for j in range(K)], windows=[wins[j][k - 1][0] for j in range(K)], cands=cs, mode="graph")
+
+    def single_frame(j, k):
+        if k == 0:
+            singles[j].start(raws[j][0], cand(j, 0), t=t0)
+        else:
+            singles[j].step(raws[j][k], None, cand(j, k), mode="graph", window=wins[j][k - 1][0])
+
+    # 1. results first: every array of every camera after every frame
+    kept = []
+    for k in range(NF):
+        group_frame(k)
+        for j in range(K):
+            single_frame(j, k)
+            got, want = group.read(j), singles[j].read()
+            both = [(n, got[n], want[n]) for n in names] + [("velocity", group.read_velocity(j), singles[j].read_velocity())]
+            if k:
+                gp, wp = group.read_pair(j), singles[j].read_pair()
+                both += [(n, gp[n], wp[n]) for n in pair]
+            for n, g, w in both:
+                if np.asarray(g).tobytes() != np.asarray(w).tobytes():
+                    print(f"camera {j} frame {k}: {n} of the group differs from the sequence alone: nothing is reported", file=sys.stderr)
+                    os._exit(20)
+        kept.append([int(v) for v in group.read(0)["state"][:5]])
+    print(f"results: the sensor group of {K} equals {K} sensor sequences alone on all {NF} frames; camera 0's state words: {kept}")
+
+    # 2. windows taking turns; a step is one frame of the whole rig (arm c: of one camera).  A loop restarts at the first frame
+    # every NF - 1 steps: a sensor sequence's time stamps go on from one frame to the next
+    def window(step, sync):
+        sync()
+        t_0 = time.perf_counter()
+        for i in range(a.steps):
+            step(1 + i % (NF - 1))
+        sync()
+        return (time.perf_counter() - t_0) / a.steps * 1e6
+
+    def step_group(k):
+        if k == 1:
+            group_frame(0)
+        group_frame(k)
+
+    def step_singles(k):
+        for j in range(K):
+            if k == 1:
+                single_frame(j, 0)
+            single_frame(j, k)
+
+    def step_one(k):
+        if k == 1:
+            single_frame(0, 0)
+        single_frame(0, k)
+
+    def sync_singles():
+        for sq in singles:
+            sq.ctx.sync()
+
+    def sync_group():
+        for sq in group.seqs:
+            sq.ctx.sync()
+    loops = {f"(a) sensor group of {K}": (step_group, sync_group),
+             f"(b) {K} sensor sequences one after another": (step_singles, sync_singles),
+             "(c) one sensor sequence": (step_one, singles[0].ctx.sync)}
+    times = {name: [] for name in loops}
+    for step, sync in loops.values():
+        window(step, sync)                                     # warm-up
+    for _ in range(a.windows):
+        for name, (step, sync) in loops.items():
+            times[name].append(window(step, sync))
+    res = {"workload": f"{K} cameras, each {W}x{H} maps from 3-channel raw frames, {N} keypoints, h = 10, validation on, "
+                       f"{'FAST top-up' if a.detect_fast else 'candidate lists'}, graph mode, {a.steps} steps a window, {a.windows} windows "
+                       "taking turns; one start per 8 steps is inside every figure",
+           "unit": "us per rig frame for (a) and (b), per frame for (c) (host clock around a window, synchronised at both ends)",
+           "group_status": group.status(), "camera_0_state_words": kept, "loops": {}}
+    for name, v in times.items():
+        res["loops"][name] = dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))
+        print(f"{name:44s} {res['loops'][name]['median']:8.1f} us ({res['loops'][name]['min']:.1f} - {res['loops'][name]['max']:.1f})")
+    ga, gb = res["loops"][f"(a) sensor group of {K}"], res["loops"][f"(b) {K} sensor sequences one after another"]
+    res["a_range_below_b_range"] = bool(ga["max"] < gb["min"])
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    group.close()
+    for sq in singles:
+        sq._own = True
         sq.close()
     os._exit(0)
 
