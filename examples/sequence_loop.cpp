@@ -31,6 +31,13 @@
 // A rig of sensor sequences (pagk_sequence_group_*_sensor): K contexts, each with the file's maps and Rbc, stepped together
 // with the raw frames and the IMU window as they come from disk.  So that the cameras differ, camera j sees the raw frame
 // (k + j) mod n_frames and (without --detect-fast) the candidate list of that frame.  Prints "camera j frame k: ...".
+//
+//   ... --pipeline DEPTH  (every form above; DEPTH 2 .. 8)
+//
+// The pipelined loop: the sequence gets a result ring of DEPTH pinned blocks (pagk_sequence_results_create), frames are handed
+// in without waiting, and the record of frame k is fetched (pagk_sequence_fetch: it waits for that frame's copy only) after
+// frame k + DEPTH - 1 was handed in.  Prints the same lines as the lock-step loop, from the records: a diff of the two outputs
+// is empty.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +58,27 @@
         }                                                                                                  \
     } while (0)
 
+// --pipeline: the line of frame k of a camera (-1: the only one), from its record in the ring
+static int print_fetched(pagk_ctx *c, int k, int camera)
+{
+    pagk_sequence_result r;
+    const int rc = pagk_sequence_fetch(c, k, &r);
+    if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_fetch -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(c)), rc;
+    if (camera >= 0) printf("camera %d ", camera);
+    printf("frame %d: %d %d %d %d %d\n", r.frame, r.state[0], r.state[1], r.state[2], r.state[3], r.state[4]);
+    return PAGK_OK;
+}
+
+// the frames whose records are due once frame k has been handed in: k - depth + 1, and behind the last frame the rest
+static int fetch_due(pagk_ctx *const *ctxs, int K, bool rig, int k, int nf, int depth)
+{
+    const int first = k - depth + 1 < 0 ? 0 : k - depth + 1, last = k == nf - 1 ? k : k - depth + 1;
+    for (int f = first; f <= last; f++)
+        for (int j = 0; j < K; j++)
+            if (print_fetched(ctxs[j], f, rig ? j : -1) != PAGK_OK) return 2;
+    return 0;
+}
+
 template <class T>
 static bool read_n(FILE *f, std::vector<T> &v, size_t n)
 {
@@ -59,7 +87,7 @@ static bool read_n(FILE *f, std::vector<T> &v, size_t n)
 }
 
 // :199-321 for K cameras at once: K contexts with one sequence each, grouped; the lead's calls step them all
-static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int nf, int w, int h, int nc,
+static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int depth, int nf, int w, int h, int nc,
                     const std::vector<std::vector<uint8_t>> &img, const std::vector<std::vector<float>> &cand,
                     const std::vector<std::vector<float>> &rot)
 {
@@ -70,6 +98,7 @@ static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int nf, int
         if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
         if (j == 0) ctx = ctxs[0];
         rc = pagk_sequence_create(ctxs[j], &sp);
+        if (rc == PAGK_OK && depth) rc = pagk_sequence_results_create(ctxs[j], depth);
         if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_create -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
     }
     CHECK(pagk_sequence_group_create(ctxs.data(), K));
@@ -88,6 +117,10 @@ static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int nf, int
             CHECK(pagk_sequence_group_start(ctx, frames.data(), lists.data(), counts.data()));
         else
             CHECK(pagk_sequence_group_step(ctx, frames.data(), rot9.data(), lists.data(), counts.data(), mode));
+        if (depth) {   // a member's fetches keep working while it is grouped
+            if (fetch_due(ctxs.data(), K, true, k, nf, depth)) return 2;
+            continue;
+        }
         for (int j = 0; j < K; j++) {   // a member's reads keep working while it is grouped
             int rc = pagk_sequence_read(ctxs[j], sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr);
             if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_read -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
@@ -159,7 +192,7 @@ struct SensorFiles {
 };
 
 // :199-321 on a sensor sequence: a raw frame and the IMU samples since the last frame in, the next pair's keypoints out
-static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode)
+static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode, int depth)
 {
     pagk_ctx *ctx = nullptr;
     SensorFiles in;
@@ -171,6 +204,7 @@ static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode
     if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
     CHECK(pagk_rectify_set_maps(ctx, in.map_x.data(), in.map_y.data(), in.w, in.h, (int64_t)in.w * 4));
     CHECK(pagk_sequence_create_sensor(ctx, &sp, &ss));
+    if (depth) CHECK(pagk_sequence_results_create(ctx, depth));
     const bool list = sp.detector == 0;
     pagk_seq::ImuWindow windows(in.imu);
     std::vector<uint8_t> raw;
@@ -197,6 +231,10 @@ static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode
             CHECK(pagk_sequence_step_sensor(ctx, &frame, &win, c, list ? nc : 0, mode));
         }
         t_prev = in.frames[k].first;
+        if (depth) {
+            if (fetch_due(&ctx, 1, false, k, nf, depth)) return 2;
+            continue;
+        }
         CHECK(pagk_sequence_read(ctx, sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr));
         printf("frame %d: %d %d %d %d %d\n", k, state[0], state[1], state[2], state[3], state[4]);
     }
@@ -209,7 +247,7 @@ static int sensor_loop(const std::string &dir, pagk_sequence_params sp, int mode
 }
 
 // ... and for K cameras at once: K sensor sequences, grouped; the lead's calls step them all, nothing is computed outside
-static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int K, int mode)
+static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int K, int mode, int depth)
 {
     pagk_ctx *ctx = nullptr;   // (the lead: CHECK reports its text)
     SensorFiles in;
@@ -224,7 +262,8 @@ static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int 
         if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
         if (j == 0) ctx = ctxs[0];
         if ((rc = pagk_rectify_set_maps(ctxs[j], in.map_x.data(), in.map_y.data(), in.w, in.h, (int64_t)in.w * 4)) != PAGK_OK ||
-            (rc = pagk_sequence_create_sensor(ctxs[j], &sp, &ss)) != PAGK_OK)
+            (rc = pagk_sequence_create_sensor(ctxs[j], &sp, &ss)) != PAGK_OK ||
+            (depth && (rc = pagk_sequence_results_create(ctxs[j], depth)) != PAGK_OK))
             return fprintf(stderr, "camera %d -> %s (%s)\n", j, pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
     }
     CHECK(pagk_sequence_group_create_sensor(ctxs.data(), K));
@@ -263,6 +302,10 @@ static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int 
                                                   list ? counts.data() : nullptr, mode));
         }
         t_prev = in.frames[k].first;
+        if (depth) {   // a member's fetches keep working while it is grouped
+            if (fetch_due(ctxs.data(), K, true, k, nf, depth)) return 2;
+            continue;
+        }
         for (int j = 0; j < K; j++) {   // a member's reads keep working while it is grouped
             int rc = pagk_sequence_read(ctxs[j], sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr);
             if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_read -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
@@ -281,7 +324,7 @@ static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor] [--cameras K] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]\n", argv[0]);
+        fprintf(stderr, "usage: %s seq.bin|dir target_n cap [--sensor] [--cameras K] [--lk | --lk-gyro] [--detect | --detect-fast] [--direct] [--pipeline DEPTH]\n", argv[0]);
         return 1;
     }
     pagk_ctx *ctx = nullptr;
@@ -290,7 +333,7 @@ int main(int argc, char **argv)
     sp.target_n = atoi(argv[2]), sp.cap = atoi(argv[3]);
     int mode = PAGK_SEQ_GRAPH;
     bool sensor = false;
-    int cameras = 0;
+    int cameras = 0, depth = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lk") sp.tracker = PAGK_SEQ_LK, sp.lk_initial_flow = 0;
@@ -300,12 +343,14 @@ int main(int argc, char **argv)
         else if (a == "--direct") mode = PAGK_SEQ_DIRECT;
         else if (a == "--sensor") sensor = true;
         else if (a == "--cameras" && i + 1 < argc) cameras = atoi(argv[++i]);
+        else if (a == "--pipeline" && i + 1 < argc) depth = atoi(argv[++i]);
         else return fprintf(stderr, "unknown flag %s\n", argv[i]), 1;
     }
+    if (depth && (depth < 2 || depth > 8)) return fprintf(stderr, "--pipeline: a ring of 2 .. 8 blocks\n"), 1;
     if (sensor) {
 #ifdef PAGK_EXAMPLE_SENSOR
         if (cameras < 0 || cameras > 64) return fprintf(stderr, "--cameras: 1 .. 64 cameras\n"), 1;
-        return cameras ? sensor_rig_loop(argv[1], sp, cameras, mode) : sensor_loop(argv[1], sp, mode);
+        return cameras ? sensor_rig_loop(argv[1], sp, cameras, mode, depth) : sensor_loop(argv[1], sp, mode, depth);
 #else
         return fprintf(stderr, "--sensor: build with -DPAGK_EXAMPLE_SENSOR against csrc/host/sequence_io.h and libpagk_tracker.so\n"), 1;
 #endif
@@ -336,12 +381,13 @@ int main(int argc, char **argv)
     if (cameras) {
         if (cameras < 1 || cameras > 64 || pagk_sequence_group_check(&sp) != PAGK_OK)
             return fprintf(stderr, "--cameras: 1 .. 64 cameras, PatchMatch with the file's candidate lists\n"), 1;
-        return rig_loop(sp, cameras, mode, nf, w, h, nc, img, cand, rot);
+        return rig_loop(sp, cameras, mode, depth, nf, w, h, nc, img, cand, rot);
     }
 
     int rc = pagk_create(&ctx, 0);
     if (rc != PAGK_OK) return fprintf(stderr, "pagk_create: %s, no fallback\n", pagk_strerror(rc)), 3;
     CHECK(pagk_sequence_create(ctx, &sp));
+    if (depth) CHECK(pagk_sequence_results_create(ctx, depth));
     const bool list = sp.detector == 0;
     std::vector<float> keys_un((size_t)sp.cap * 2);
     int32_t state[PAGK_HANDOVER_STATE_WORDS];
@@ -352,6 +398,10 @@ int main(int argc, char **argv)
             CHECK(pagk_sequence_start(ctx, &frame, c, list ? nc : 0));
         else
             CHECK(pagk_sequence_step(ctx, &frame, rot[k - 1].data(), c, list ? nc : 0, mode));
+        if (depth) {   // no waiting here: the record of frame k - depth + 1 is due, later frames are in flight
+            if (fetch_due(&ctx, 1, false, k, nf, depth)) return 2;
+            continue;
+        }
         CHECK(pagk_sequence_read(ctx, sp.cap, nullptr, keys_un.data(), nullptr, nullptr, nullptr, state, nullptr));
         printf("frame %d: %d %d %d %d %d\n", k, state[0], state[1], state[2], state[3], state[4]);
     }

@@ -1704,7 +1704,8 @@ int pagk_sequence_read(pagk_ctx *ctx, int32_t cap, float *keys, float *keys_un, 
  * 0 for PatchMatch), the first `cap` rows each.  Any array may be NULL.  PAGK_E_ARG before the first pagk_sequence_step. */
 int pagk_sequence_read_pair(pagk_ctx *ctx, int32_t cap, uint8_t *status, float *pt_predict, float *pt_predict_un, float *err);
 /* Host-side words, nothing synchronised (Examples/Demo/RealSenseD435i.cpp:199-321 has no counterpart), PAGK_SEQ_STATUS_WORDS
- * int32: [0] frames handed in, [1] 1 if the last step was a graph replay, [2] graphs held, [3] 0. */
+ * int32: [0] frames handed in, [1] 1 if the last step was a graph replay, [2] graphs held, [3] the depth of the result
+ * ring (pagk_sequence_results_create), 0 without one. */
 int pagk_sequence_status(pagk_ctx *ctx, int32_t *words);
 
 /* ---- The sensor form of the sequence: raw frames and the IMU window in, tracked features out --------------------------- */
@@ -1871,6 +1872,81 @@ int pagk_sequence_group_start_sensor(pagk_ctx *lead, const pagk_image *raws, con
  * before anything is enqueued: a refusal of any camera's frame, window or list returns PAGK_E_ARG and changes nothing. */
 int pagk_sequence_group_step_sensor(pagk_ctx *lead, const pagk_image *raws, const pagk_imu_window *windows,
                                     const float *const *cand, const int32_t *n_cand, int32_t mode);
+
+/* ---- The result ring of a sequence: every frame's results through pinned blocks, with track ids ------------------------ */
+/* The output half of the loop (no counterpart in the reference, whose loop reads its Frame objects on the host:
+ * Examples/Demo/RealSenseD435i.cpp:237-321).  pagk_sequence_read, pagk_sequence_read_pair and pagk_sequence_read_velocity
+ * synchronise the stream and see the last frame handed in only.  A sequence with a result ring packs, as the last launch of
+ * every frame (inside the captured chain), everything those three calls deliver plus a persistent track id and an age per
+ * row into ONE record on the device; behind the step (behind the graph launch, outside any capture) one asynchronous copy
+ * puts the record of frame f into pinned block f % depth and records that block's event -- the mirror image of the input
+ * copy in front of the step.  pagk_sequence_fetch(f) waits for that copy only, while later frames are in flight.
+ * Opt-in: a sequence without a ring issues exactly the launches it issued before the ring existed.
+ * The record of frame f (frame 0 is the start): a header (frame, cap, n_live = state[0], n_new, next_id, t), the state and
+ * info words, key set f on all `cap` rows (keys, keys_un, keys_normal, index_in_last, live, track_id, age, velocity) and
+ * pair (f - 1, f) over the rows of key set f - 1 (status, pt_predict, pt_predict_un, err; all zero for frame 0).  Every array
+ * is byte for byte what the three read calls return when called in lock-step after frame f; velocity is zeros unless this is
+ * a sensor sequence with flow_velocity; t is the frame's time stamp for a sensor sequence and 0 for a plain one.
+ *   track ids  (the library's own definition; the reference has only mvPtIndexInLastFrame, src/frame.cpp:135,192,
+ *              include/frame.h:80)  At a start next_id = 0.  For row j of the new key set, with i = index_in_last[j]:
+ *                j >= n_live:  track_id = -1, age = 0;
+ *                i >= 0:       track_id = track_id_last[i], age = age_last[i] + 1;
+ *                otherwise:    track_id = next_id + (the number of rows j' < j with j' < n_live and index_in_last[j'] < 0),
+ *                              age = 0.
+ *              n_new is the number of rows below n_live with index_in_last < 0; after the frame next_id += n_new, and the
+ *              header carries that value.  The rank is a count in row order: new rows need not follow the survivors.  A
+ *              restart (pagk_sequence_start called again) begins at 0 again and empties the ring.
+ * Groups: the members of a group either all have a ring of one depth or none has; a group step then packs every camera's
+ * record in one launch (the camera is the grid's second dimension, from a third table the lead owns) and enqueues one copy
+ * and one event per member behind the graph, in front of the event the members' streams wait for.  pagk_sequence_fetch and
+ * pagk_sequence_poll on a member keep working while it is grouped.
+ * Out of scope: one contiguous record for a whole rig, ids that survive a restart, releasing blocks explicitly,
+ * Lucas-Kanade's info words. */
+typedef struct pagk_results_layout {
+    int64_t header, state, info;                                   /* byte offsets of the parts of a record, in this order, ... */
+    int64_t keys, keys_un, keys_normal, index_in_last, live, track_id, age, velocity;
+    int64_t status, pt_predict, pt_predict_un, err;                /* ... each a multiple of 256 */
+    int64_t bytes;                                                 /* the record's size: the last part's end, rounded up to 256 */
+    int32_t cap, sensor;                                           /* what it was asked for */
+} pagk_results_layout;
+typedef struct pagk_sequence_result {
+    int32_t frame, cap, n_live, n_new;   /* the header: the frame's number, the rows of every array, state[0], new tracks */
+    int64_t next_id;                     /* the id the next new track gets */
+    double t;                            /* sensor sequence: the frame's time stamp; 0 otherwise */
+    const int32_t *state, *info;         /* PAGK_HANDOVER_STATE_WORDS and PAGK_DETECT_INFO_WORDS int32 */
+    const float *keys, *keys_un, *keys_normal;   /* cap x 2 floats each */
+    const int32_t *index_in_last;        /* cap int32 */
+    const uint8_t *live;                 /* cap bytes */
+    const int64_t *track_id;             /* cap int64: -1 at and beyond n_live */
+    const int32_t *age;                  /* cap int32: frames since the track was new */
+    const float *velocity;               /* cap x 2 floats */
+    const uint8_t *status;               /* pair (frame - 1, frame): cap bytes, ... */
+    const float *pt_predict, *pt_predict_un, *err;   /* ... cap x 2, cap x 2 and cap floats */
+} pagk_sequence_result;
+/* Where the parts of a record lie (no counterpart in the reference: Examples/Demo/RealSenseD435i.cpp:237-321 keeps Frame
+ * objects): header | state | info | keys | keys_un | keys_normal | index_in_last | live | track_id | age | velocity | status
+ * | pt_predict | pt_predict_un | err, every part on a multiple of 256 bytes.  The header part starts with int32 frame, cap,
+ * n_live, n_new, int64 next_id, f64 t.  `sensor` (0 or 1) changes what velocity and t mean, not an offset.  PAGK_E_ARG for
+ * cap outside 1 .. PAGK_LK_MAX_ROWS, a sensor flag that is neither, or a NULL layout.  Needs no device. */
+int pagk_sequence_results_layout(int32_t cap, int32_t sensor, pagk_results_layout *layout);
+/* Gives the context's sequence a result ring of `depth` (2 .. 8) pinned blocks and events (no counterpart in the reference:
+ * Examples/Demo/RealSenseD435i.cpp:199-321 has no device to copy from).  Called after pagk_sequence_create[_sensor] and
+ * before the first pagk_sequence_start[_sensor].  The parts on the device -- one record, track_id[2][cap] (int64) and
+ * age[2][cap] (int32) by parity, next_id -- are a buffer of the context of their own, state and not scratch
+ * (pagk_selftest_fill_workspaces leaves them alone); the layout of the sequence's own block does not change.  PAGK_E_ARG with
+ * a text in pagk_last_error: without a sequence, for a second call, after a start, while grouped, inside a capture, for a
+ * depth out of range.  pagk_sequence_destroy and pagk_destroy free the ring. */
+int pagk_sequence_results_create(pagk_ctx *ctx, int32_t depth);
+/* The record of frame `frame` (no counterpart in the reference: Examples/Demo/RealSenseD435i.cpp:237-321 reads the Frame it
+ * just made): waits for the copy of that frame only, never for the stream, and fills *result with the header's scalars and
+ * const views into the pinned block (zero copy).  Valid frames: frames handed in - depth <= frame < frames handed in, frame
+ * 0 being the start; PAGK_E_ARG with a text for every other frame, for a frame from before a restart and for a sequence
+ * without a ring.  The views stay valid until the call that hands in frame `frame + depth` (which rewrites the block), a
+ * restart, or pagk_sequence_destroy.  Works on a member of a group.  Returns the launch-error word as the read calls do. */
+int pagk_sequence_fetch(pagk_ctx *ctx, int32_t frame, pagk_sequence_result *result);
+/* 1 if the copy of frame `frame` has completed, 0 if not yet (no counterpart in the reference:
+ * Examples/Demo/RealSenseD435i.cpp:237-321 is synchronous); nothing is waited for.  PAGK_E_ARG as pagk_sequence_fetch. */
+int pagk_sequence_poll(pagk_ctx *ctx, int32_t frame);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,27 @@ class SequenceSensor(C.Structure):
                 ("imu_cap", C.c_int32), ("Rbc", C.c_float * 9), ("flow_velocity", C.c_int32)]
 
 
+RESULTS_PARTS = ("header", "state", "info", "keys", "keys_un", "keys_normal", "index_in_last", "live", "track_id", "age",
+                 "velocity", "status", "pt_predict", "pt_predict_un", "err")
+
+
+class ResultsLayout(C.Structure):
+    """pagk_results_layout (include/pagk.h "The result ring of a sequence"): the byte offsets of a record's parts, its size."""
+    _fields_ = [(name, C.c_int64) for name in RESULTS_PARTS] + [("bytes", C.c_int64), ("cap", C.c_int32), ("sensor", C.c_int32)]
+
+
+class SequenceResult(C.Structure):
+    """pagk_sequence_result (include/pagk.h): the header of a frame's record and views into its pinned block."""
+    _fields_ = [("frame", C.c_int32), ("cap", C.c_int32), ("n_live", C.c_int32), ("n_new", C.c_int32), ("next_id", C.c_int64),
+                ("t", C.c_double)] + [(name, C.c_void_p) for name in RESULTS_PARTS[1:]]
+
+
+# part of a record -> (dtype, columns): what Context.sequence_fetch copies out of the views
+RESULTS_ARRAYS = {"keys": (np.float32, 2), "keys_un": (np.float32, 2), "keys_normal": (np.float32, 2),
+                  "index_in_last": (np.int32, 1), "live": (np.uint8, 1), "track_id": (np.int64, 1), "age": (np.int32, 1),
+                  "velocity": (np.float32, 2), "status": (np.uint8, 1), "pt_predict": (np.float32, 2),
+                  "pt_predict_un": (np.float32, 2), "err": (np.float32, 1)}
+
 IMU_MAX_SAMPLES = 64
 SEQ_PATCHMATCH, SEQ_LK = 0, 1
 SEQ_GRAPH, SEQ_DIRECT = 0, 1
@@ -443,6 +464,12 @@ def declare(lib) -> None:
                            ("pagk_sequence_group_step_sensor", [vp, vp, vp, vp, vp, i32])):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_sequence_results_create"):
+        for name, args in (("pagk_sequence_results_layout", [i32, i32, _P(ResultsLayout)]),
+                           ("pagk_sequence_results_create", [vp, i32]), ("pagk_sequence_fetch", [vp, i32, _P(SequenceResult)]),
+                           ("pagk_sequence_poll", [vp, i32])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
     if hasattr(lib, "pagk_lk_track_flow"):
         lib.pagk_lk_track_flow.restype = C.c_int
         lib.pagk_lk_track_flow.argtypes = [vp, _P(LkParams), _P(Params), _P(Image), _P(Image), i32, vp, vp, vp, vp, vp, vp, vp,
@@ -623,6 +650,7 @@ EXPORTED_SYMBOLS = [
     "pagk_sequence_group_step", "pagk_sequence_group_status",
     "pagk_sequence_group_sensor_check", "pagk_sequence_group_create_sensor", "pagk_sequence_group_start_sensor",
     "pagk_sequence_group_step_sensor",
+    "pagk_sequence_results_layout", "pagk_sequence_results_create", "pagk_sequence_fetch", "pagk_sequence_poll",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
 ]
@@ -791,6 +819,15 @@ def sequence_params_default(**overrides) -> SequenceParams:
 def sequence_params_check(p: SequenceParams) -> int:
     """pagk_sequence_params_check: PAGK_OK, or the code pagk_sequence_create refuses these parameters with (needs no device)."""
     return int(load().pagk_sequence_params_check(C.byref(p)))
+
+
+def sequence_results_layout(cap: int, sensor: int = 0) -> ResultsLayout:
+    """pagk_sequence_results_layout: where the parts of a frame's record lie (needs no device).  ValueError when refused."""
+    lay = ResultsLayout()
+    rc = int(load().pagk_sequence_results_layout(int(cap), int(sensor), C.byref(lay)))
+    if rc != PAGK_OK:
+        raise ValueError(f"pagk_sequence_results_layout refuses cap {cap}, sensor {sensor}")
+    return lay
 
 
 def sequence_group_check(p: SequenceParams) -> int:
@@ -1874,7 +1911,37 @@ class Context:
         """pagk_sequence_status -> dict(frames, last_was_graph, graphs); nothing is synchronised."""
         w = np.zeros(SEQ_STATUS_WORDS, np.int32)
         self._check(self.lib.pagk_sequence_status(self.h, _ptr(w)), "pagk_sequence_status")
-        return dict(frames=int(w[0]), last_was_graph=bool(w[1]), graphs=int(w[2]))
+        return dict(frames=int(w[0]), last_was_graph=bool(w[1]), graphs=int(w[2]), results_depth=int(w[3]))
+
+    # the result ring of the sequence (include/pagk.h "The result ring of a sequence") ------------------------------------
+    def sequence_results_create(self, depth: int):
+        """pagk_sequence_results_create: `depth` (2 .. 8) pinned result blocks, in front of the first start."""
+        self._check(self.lib.pagk_sequence_results_create(self.h, int(depth)), "pagk_sequence_results_create")
+
+    def sequence_fetch(self, frame: int) -> dict:
+        """pagk_sequence_fetch -> the record of `frame` as a dict of COPIES (the views die with the block's next frame): the
+        header's scalars (frame, cap, n_live, n_new, next_id, t), state, info and every array on all cap rows."""
+        r = SequenceResult()
+        self._check(self.lib.pagk_sequence_fetch(self.h, int(frame), C.byref(r)), "pagk_sequence_fetch")
+        cap = int(r.cap)
+        out = dict(frame=int(r.frame), cap=cap, n_live=int(r.n_live), n_new=int(r.n_new), next_id=int(r.next_id), t=float(r.t))
+
+        def view(name, dtype, count):
+            buf = (C.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(getattr(r, name))
+            return np.frombuffer(buf, dtype).copy()
+        out["state"] = view("state", np.int32, HANDOVER_STATE_WORDS)
+        out["info"] = view("info", np.int32, DETECT_INFO_WORDS)
+        for name, (dtype, cols) in RESULTS_ARRAYS.items():
+            a = view(name, dtype, cap * cols)
+            out[name] = a.reshape(cap, 2) if cols == 2 else a
+        return out
+
+    def sequence_poll(self, frame: int) -> bool:
+        """pagk_sequence_poll: has the copy of `frame` completed?  Nothing is waited for."""
+        rc = int(self.lib.pagk_sequence_poll(self.h, int(frame)))
+        if rc < 0:
+            self._check(rc, "pagk_sequence_poll")
+        return rc == 1
 
     # the sensor form of the sequence and the gyro integration (src/gyro_aided_tracker.cpp:511-587) ------------------------
     def gyro_integrate(self, Rbc, camera: Params, window: ImuWindow):

@@ -22,6 +22,7 @@
 #include "pagk_gyro_kernel.h"
 #include "pagk_group_kernel.h"
 #include "pagk_group_sensor_kernel.h"
+#include "pagk_results_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
 #include "pagk_prio_env.h"
@@ -90,6 +91,19 @@ struct SeqState {
     const float *rot = nullptr;   // what the prediction reads: the caller's nine floats in the input block, or k_gyro_integrate's
     float *rot_out = nullptr, *rcl = nullptr, *vel = nullptr;   // sensor parts: rot9 | Rcl, the flow velocities
     double t_last = 0.0;          // the previous frame's time
+    // the result ring (pagk_sequence_results_create; depth 0: none): the device parts lie in buf[RESULTS], the blocks are pinned
+    struct Results {
+        static constexpr int kMaxDepth = 8;
+        int depth = 0;
+        size_t bytes = 0;             // of a record
+        uint8_t *rec = nullptr;       // the record the pack writes
+        int64_t *id[2] = {}, *next[2] = {};   // by parity: track ids, next_id
+        int32_t *age[2] = {};
+        void *pinned[kMaxDepth] = {};
+        hipEvent_t copied[kMaxDepth] = {};
+        int frame_of[kMaxDepth] = {};   // the frame whose copy the block's event stands behind (-1: none)
+    } res;
+    bool ever_started = false;
 };
 
 // The sequence group of k contexts (pagk_sequence_group_*): every member's ctx->group points here, members[0] is the lead and
@@ -104,6 +118,8 @@ struct GroupState {
     // The group's kind: k sensor sequences (pagk_sequence_group_create_sensor).  The lead's buf[GROUP_SENSOR] then holds a
     // second table, of the stages a sensor step adds (pagk_group_sensor_kernel.h): record [parity * k + camera].
     bool sensor = false;
+    // every member has a result ring (of one depth): the lead's buf[GROUP_RESULTS] holds a third table, of k_group_results_pack
+    bool rings = false;
     int n_cells = 0;             // (detector 2) the cells of the FAST grid, the same for every member
     // what the tables were built from, per member: a workspace that moved since then invalidates them
     struct Held {
@@ -112,6 +128,8 @@ struct GroupState {
         // the sensor group's: the FAST workspace, the map entries, both frame slots' level 0, the sequence's block
         const void *fast, *entries, *level0[2], *seq;
         int rect_w, rect_h, rect_wp;
+        const void *results;   // with result rings: the member's buf[RESULTS] and its sequence's block (the third table)
+        const void *results_seq;
     };
     std::vector<Held> held;
 };
@@ -159,6 +177,8 @@ struct pagk_ctx {
         SEQ,           // the sequence the context owns (pagk_sequence_*): input block, two key sets, work arrays, state and info words
         GROUP,         // the sequence group this context leads (pagk_sequence_group_*): the argument table of its batched kernels, 2 k records
         GROUP_SENSOR,  // ... of k sensor sequences (pagk_sequence_group_*_sensor): the table of the stages they add, 2 k records
+        RESULTS,       // the result ring of the sequence (pagk_sequence_results_create): one record, track ids and ages by parity, next_id
+        GROUP_RESULTS, // ... of a group whose members have rings: the table of k_group_results_pack, 2 k records
         kBufs
     };
     DevBuf buf[kBufs];
@@ -1359,7 +1379,7 @@ int pagk_create(pagk_ctx **out, int device)
     ctx->stream = ctx->own_stream;
     ctx->buf[pagk_ctx::FEAT].mirrored = true;
     for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER, pagk_ctx::GROUP,
-                  pagk_ctx::GROUP_SENSOR})
+                  pagk_ctx::RESULTS, pagk_ctx::GROUP_RESULTS, pagk_ctx::GROUP_SENSOR})
         ctx->buf[b].state = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
@@ -5227,6 +5247,11 @@ int seq_feed(pagk_ctx *ctx, SeqState &q, const pagk_image *frame, const float *r
         memcpy(pin + q.off_ncand, &n_cand, sizeof n_cand);
         if (n_cand) memcpy(pin + q.off_cand, cand, (size_t)n_cand * 8);
     }
+    if (q.res.depth) {   // what k_results_pack reads of the frame: its number and its time (spare bytes of the n_cand part)
+        const int32_t frame_no = q.started ? q.frames : 0;
+        const double t = win ? win->t_cur : t0;
+        memcpy(pin + q.off_ncand + kResultsFrameOff, &frame_no, 4), memcpy(pin + q.off_ncand + kResultsTimeOff, &t, 8);
+    }
     HIPCHK(ctx, hipMemcpyAsync(q.in, pin, q.in_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipEventRecord(q.read_done[k], ctx->stream));
     q.recorded[k] = true;
@@ -5306,6 +5331,55 @@ FlowVelocityArgs seq_flow_args(const SeqState &q, int c)
     return f;
 }
 
+// the arguments of the pack of a frame of parity c: key set c, the pair's arrays, the ids of parity 1 - c
+ResultsArgs seq_results_args(const SeqState &q, int c)
+{
+    const SeqState::KeySet &s = q.set[c];
+    ResultsArgs a;
+    memset(&a, 0, sizeof a);
+    a.words = q.in + q.off_ncand, a.state = q.state, a.info = q.info;
+    a.keys = s.keys, a.keys_un = s.keys_un, a.keys_normal = s.keys_normal, a.index_in_last = s.index_in_last, a.live = s.live;
+    a.velocity = q.sensor && q.s.flow_velocity ? q.vel : nullptr;
+    a.status = q.st, a.pt_predict = q.pp, a.pt_predict_un = q.ppu, a.err = q.lk_err;
+    a.id_last = q.res.id[1 - c], a.age_last = q.res.age[1 - c], a.next_last = q.res.next[1 - c];
+    a.id_cur = q.res.id[c], a.age_cur = q.res.age[c], a.next_cur = q.res.next[c];
+    a.rec = q.res.rec, a.cap = q.p.cap, a.sensor = q.sensor ? 1 : 0;
+    return a;
+}
+
+unsigned results_blocks(int32_t cap) { return (unsigned)((cap + 1023) / 1024); }
+
+// the last launch of a frame with a result ring: everything the read calls deliver, ids and ages, into the record
+int seq_results_pack(pagk_ctx *ctx, SeqState &q, int c)
+{
+    const ResultsArgs a = seq_results_args(q, c);
+    hipLaunchKernelGGL(k_results_pack, dim3(results_blocks(q.p.cap)), dim3(1024), 0, ctx->stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    return PAGK_OK;
+}
+
+// Behind the step (the graph launch or the direct issue) and outside any capture: the record of frame `frame` into its pinned
+// block, and the block's event.  The mirror image of seq_feed's input copy.
+int seq_results_post(pagk_ctx *ctx, SeqState &q, int frame)
+{
+    if (!q.res.depth) return PAGK_OK;
+    const int b = frame % q.res.depth;
+    HIPCHK(ctx, hipMemcpyAsync(q.res.pinned[b], q.res.rec, q.res.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(q.res.copied[b], ctx->stream));
+    q.res.frame_of[b] = frame;
+    return PAGK_OK;
+}
+
+void seq_results_free(SeqState &q)
+{
+    for (int k = 0; k < SeqState::Results::kMaxDepth; k++) {
+        if (q.res.pinned[k]) (void)hipHostFree(q.res.pinned[k]);
+        if (q.res.copied[k]) (void)hipEventDestroy(q.res.copied[k]);
+        q.res.pinned[k] = nullptr, q.res.copied[k] = nullptr;
+    }
+    q.res.depth = 0;
+}
+
 // The work of a frame of parity c: frame slot c is the current frame, slot 1 - c the reference; key set 1 - c holds the
 // reference keypoints, set c receives the next pair's.
 int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
@@ -5351,11 +5425,13 @@ int seq_issue(pagk_ctx *ctx, SeqState &q, int c)
         if (rc) return rc;
     }
     rc = seq_handover(ctx, q, q.st, c);
-    if (rc || !q.sensor || !q.s.flow_velocity) return rc;
-    const FlowVelocityArgs f = seq_flow_args(q, c);   // src/frame.cpp:139-143, on the key set just written
-    hipLaunchKernelGGL(k_flow_velocity, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, ctx->stream, f);
-    HIPCHK(ctx, hipGetLastError());
-    return PAGK_OK;
+    if (rc) return rc;
+    if (q.sensor && q.s.flow_velocity) {
+        const FlowVelocityArgs f = seq_flow_args(q, c);   // src/frame.cpp:139-143, on the key set just written
+        hipLaunchKernelGGL(k_flow_velocity, dim3((unsigned)((p.cap + 255) / 256)), dim3(256), 0, ctx->stream, f);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return q.res.depth ? seq_results_pack(ctx, q, c) : PAGK_OK;
 }
 
 // the sequence of a call, or nullptr with the reason in ctx->err
@@ -5567,11 +5643,14 @@ int pagk_sequence_destroy(pagk_ctx *ctx)
         if (q->pinned[k]) (void)hipHostFree(q->pinned[k]);
         if (q->read_done[k]) (void)hipEventDestroy(q->read_done[k]);
     }
+    seq_results_free(*q);
     ctx->seq = nullptr;
     delete q;
     bool alive = false;
     for (int k = 0; k < pagk_ctx::kGraphs; k++) alive = alive || ctx->graph_execs[k];
-    return alive ? PAGK_OK : release(ctx, ctx->buf[pagk_ctx::SEQ]);   // (a graph of the caller's cannot point into it, but stay safe)
+    if (alive) return PAGK_OK;   // (a graph of the caller's cannot point into them, but stay safe)
+    const int rc = release(ctx, ctx->buf[pagk_ctx::RESULTS]);
+    return rc ? rc : release(ctx, ctx->buf[pagk_ctx::SEQ]);
 }
 
 // the sequence of a call of the plain (`sensor` false) or the sensor form; the other kind is refused with a text
@@ -5608,8 +5687,14 @@ static int seq_start(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const 
         return PAGK_E_NOMEM;
     }
     q->started = q->stepped = false;
+    q->ever_started = true;
     int rc = seq_feed(ctx, *q, frame, nullptr, cand, n_cand, nullptr, t0);
     if (rc || (rc = seq_frame(ctx, *q, 0)) || (rc = seq_handover(ctx, *q, q->zero, 0))) return rc;
+    if (q->res.depth) {   // ids begin at 0 again, the ring is empty, frame 0 is the start's record
+        HIPCHK(ctx, hipMemsetAsync(q->res.next[0], 0, 256, ctx->stream));
+        for (int &f : q->res.frame_of) f = -1;
+        if ((rc = seq_results_pack(ctx, *q, 0)) || (rc = seq_results_post(ctx, *q, 0))) return rc;
+    }
     q->started = true, q->frames = 1, q->last_graph = false, q->t_last = t0;
     return PAGK_OK;
 }
@@ -5663,6 +5748,7 @@ static int seq_step(pagk_ctx *ctx, SeqState *q, const pagk_image *frame, const f
         q->direct_done[c] = true;
         q->last_graph = false;
     }
+    if ((rc = seq_results_post(ctx, *q, q->frames))) return rc;
     q->frames++;
     q->stepped = true;
     return PAGK_OK;
@@ -5777,8 +5863,136 @@ int pagk_sequence_status(pagk_ctx *ctx, int32_t *words)
     words[0] = q.started ? q.frames : 0;
     words[1] = q.last_graph ? 1 : 0;
     words[2] = (q.graph[0] >= 0) + (q.graph[1] >= 0);
-    words[3] = 0;
+    words[3] = q.res.depth;
     return PAGK_OK;
+}
+
+// ---- the result ring of a sequence (no counterpart in the reference, which hands over mvPtIndexInLastFrame: src/frame.cpp:135,192) ----
+int pagk_sequence_results_layout(int32_t cap, int32_t sensor, pagk_results_layout *layout)
+{
+    if (!layout || cap < 1 || cap > kLkMaxRows || (sensor & ~1)) return PAGK_E_ARG;
+    int64_t off[kResultsParts + 1];
+    results_layout(cap, off);
+    memset(layout, 0, sizeof *layout);
+    layout->header = off[RES_HEADER], layout->state = off[RES_STATE], layout->info = off[RES_INFO], layout->keys = off[RES_KEYS];
+    layout->keys_un = off[RES_KEYS_UN], layout->keys_normal = off[RES_KEYS_NORMAL], layout->index_in_last = off[RES_INDEX];
+    layout->live = off[RES_LIVE], layout->track_id = off[RES_TRACK_ID], layout->age = off[RES_AGE];
+    layout->velocity = off[RES_VELOCITY], layout->status = off[RES_STATUS], layout->pt_predict = off[RES_PT_PREDICT];
+    layout->pt_predict_un = off[RES_PT_PREDICT_UN], layout->err = off[RES_ERR], layout->bytes = off[kResultsParts];
+    layout->cap = cap, layout->sensor = sensor;
+    return PAGK_OK;
+}
+
+int pagk_sequence_results_create(pagk_ctx *ctx, int32_t depth)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_results_create");
+    if (!q || seq_grouped(ctx, "pagk_sequence_results_create")) return PAGK_E_ARG;
+    const char *why = nullptr;
+    if (q->res.depth) why = "the sequence has a result ring already";
+    else if (q->ever_started) why = "after pagk_sequence_start: the ring is made in front of the first frame";
+    else if (in_capture(ctx)) why = "inside a graph capture";
+    else if (depth < 2 || depth > SeqState::Results::kMaxDepth) why = "depth is outside 2 .. 8";
+    if (why) {
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_results_create: %s", why);
+        return PAGK_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)q->p.cap;
+    int64_t off[kResultsParts + 1];
+    results_layout(q->p.cap, off);
+    // the record | track_id[2][cap] | age[2][cap] | next_id[2]
+    const size_t sizes[6] = {(size_t)off[kResultsParts], n * 8, n * 8, n * 4, n * 4, 256};
+    const Layout<6> lay(sizes);
+    DevBuf &b = ctx->buf[pagk_ctx::RESULTS];
+    int rc = reserve(ctx, b, lay.total, NOT_IN_CAPTURE_NOR_UNDER_GRAPH, "the result ring's block", "destroy the graphs first");
+    if (rc) return rc;
+    SeqState::Results &r = q->res;
+    r.bytes = sizes[0];
+    r.rec = lay.at<uint8_t>(b.ptr, 0);
+    r.id[0] = lay.at<int64_t>(b.ptr, 1), r.id[1] = lay.at<int64_t>(b.ptr, 2);
+    r.age[0] = lay.at<int32_t>(b.ptr, 3), r.age[1] = lay.at<int32_t>(b.ptr, 4);
+    r.next[0] = lay.at<int64_t>(b.ptr, 5), r.next[1] = r.next[0] + 16;   // (each parity's word in a 128-byte half of its own)
+    for (int k = 0; k < depth; k++) {
+        if (hipHostMalloc(&r.pinned[k], r.bytes, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&r.copied[k], hipEventDisableTiming) != hipSuccess) {
+            snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_results_create: no pinned result block of %zu bytes", r.bytes);
+            seq_results_free(*q);
+            return PAGK_E_NOMEM;
+        }
+        memset(r.pinned[k], 0, r.bytes);
+        r.frame_of[k] = -1;
+    }
+    // (state of its own, which pagk_selftest_fill_workspaces leaves alone: the padding of the record stays zero)
+    if (hipMemsetAsync(b.ptr, 0, lay.total, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        seq_results_free(*q);
+        snprintf(ctx->err, sizeof(ctx->err), "pagk_sequence_results_create: the block could not be cleared");
+        return PAGK_E_HIP;
+    }
+    r.depth = depth;
+    return PAGK_OK;
+}
+
+// the block of `frame`, or -1 with the reason in ctx->err
+static int results_block(pagk_ctx *ctx, SeqState *q, const char *what, int32_t frame)
+{
+    const SeqState::Results &r = q->res;
+    if (!r.depth) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: the sequence has no result ring (pagk_sequence_results_create)", what);
+        return -1;
+    }
+    const int submitted = q->started ? q->frames : 0;
+    if (frame < 0 || frame >= submitted || frame < submitted - r.depth || r.frame_of[frame % r.depth] != frame) {
+        snprintf(ctx->err, sizeof(ctx->err), "%s: frame %d is outside the ring (%d frames handed in, depth %d)", what, frame, submitted,
+                 r.depth);
+        return -1;
+    }
+    return frame % r.depth;
+}
+
+int pagk_sequence_fetch(pagk_ctx *ctx, int32_t frame, pagk_sequence_result *result)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_fetch");
+    if (!q || !result) return PAGK_E_ARG;
+    const int b = results_block(ctx, q, "pagk_sequence_fetch", frame);
+    if (b < 0) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipEventSynchronize(q->res.copied[b]));   // this frame's copy only, never the stream
+    const uint8_t *base = static_cast<const uint8_t *>(q->res.pinned[b]);
+    int64_t off[kResultsParts + 1];
+    results_layout(q->p.cap, off);
+    ResultsHeader h;
+    memcpy(&h, base + off[RES_HEADER], sizeof h);
+    memset(result, 0, sizeof *result);
+    result->frame = h.frame, result->cap = h.cap, result->n_live = h.n_live, result->n_new = h.n_new;
+    result->next_id = h.next_id, result->t = h.t;
+    result->state = reinterpret_cast<const int32_t *>(base + off[RES_STATE]);
+    result->info = reinterpret_cast<const int32_t *>(base + off[RES_INFO]);
+    result->keys = reinterpret_cast<const float *>(base + off[RES_KEYS]);
+    result->keys_un = reinterpret_cast<const float *>(base + off[RES_KEYS_UN]);
+    result->keys_normal = reinterpret_cast<const float *>(base + off[RES_KEYS_NORMAL]);
+    result->index_in_last = reinterpret_cast<const int32_t *>(base + off[RES_INDEX]);
+    result->live = base + off[RES_LIVE];
+    result->track_id = reinterpret_cast<const int64_t *>(base + off[RES_TRACK_ID]);
+    result->age = reinterpret_cast<const int32_t *>(base + off[RES_AGE]);
+    result->velocity = reinterpret_cast<const float *>(base + off[RES_VELOCITY]);
+    result->status = base + off[RES_STATUS];
+    result->pt_predict = reinterpret_cast<const float *>(base + off[RES_PT_PREDICT]);
+    result->pt_predict_un = reinterpret_cast<const float *>(base + off[RES_PT_PREDICT_UN]);
+    result->err = reinterpret_cast<const float *>(base + off[RES_ERR]);
+    return lv_check(ctx);
+}
+
+int pagk_sequence_poll(pagk_ctx *ctx, int32_t frame)
+{
+    SeqState *q = seq_of(ctx, "pagk_sequence_poll");
+    if (!q) return PAGK_E_ARG;
+    const int b = results_block(ctx, q, "pagk_sequence_poll", frame);
+    if (b < 0) return PAGK_E_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = hipEventQuery(q->res.copied[b]);
+    if (e == hipErrorNotReady) return 0;
+    HIPCHK(ctx, e);
+    return 1;
 }
 
 // ---- the sequence group: k cameras stepped together (Examples/Demo/RealSenseD435i.cpp:199-321, one loop per camera) -----------
@@ -5834,12 +6048,13 @@ GroupState::Held group_held(pagk_ctx *c)
     const DevBuf &hint = c->buf[pagk_ctx::PRIO_HINT];
     return {c->buf[pagk_ctx::FIT].ptr, c->buf[pagk_ctx::HAND].ptr, hint.ptr, hint.bytes, c->buf[pagk_ctx::FAST].ptr,
             c->buf[pagk_ctx::RECT_ENTRIES].ptr, {c->slots[0].u8[0], c->slots[1].u8[0]}, c->buf[pagk_ctx::SEQ].ptr,
-            c->rect_w, c->rect_h, c->rect_wp};
+            c->rect_w, c->rect_h, c->rect_wp, c->buf[pagk_ctx::RESULTS].ptr, c->buf[pagk_ctx::SEQ].ptr};
 }
 
-bool group_held_equal(const GroupState::Held &a, const GroupState::Held &b, bool sensor)
+bool group_held_equal(const GroupState::Held &a, const GroupState::Held &b, bool sensor, bool rings)
 {
     if (a.fit != b.fit || a.hand != b.hand || a.hint != b.hint || a.hint_bytes != b.hint_bytes) return false;
+    if (rings && (a.results != b.results || a.results_seq != b.results_seq)) return false;
     return !sensor || (a.fast == b.fast && a.entries == b.entries && a.level0[0] == b.level0[0] && a.level0[1] == b.level0[1] &&
                        a.seq == b.seq && a.rect_w == b.rect_w && a.rect_h == b.rect_h && a.rect_wp == b.rect_wp);
 }
@@ -5948,7 +6163,7 @@ int group_table(pagk_ctx *lead, GroupState &g)
     const int k = (int)g.members.size();
     if (g.table_built) {
         for (int j = 0; j < k; j++) {
-            if (!group_held_equal(group_held(g.members[j]), g.held[j], g.sensor)) {
+            if (!group_held_equal(group_held(g.members[j]), g.held[j], g.sensor, g.rings)) {
                 snprintf(lead->err, sizeof(lead->err), "a workspace of member %d moved under the group's table (a call outside the group made it "
                          "grow): destroy the group (pagk_sequence_group_destroy)", j);
                 return PAGK_E_ARG;
@@ -5959,11 +6174,13 @@ int group_table(pagk_ctx *lead, GroupState &g)
     try {
         std::vector<GroupRec> host((size_t)2 * k);
         std::vector<RigRec> rig(g.sensor ? (size_t)2 * k : 0);
+        std::vector<ResultsArgs> packs(g.rings ? (size_t)2 * k : 0);
         for (int c = 0; c < 2; c++)
             for (int j = 0; j < k; j++) {
                 pagk_ctx *m = g.members[j];
                 int rc = group_record(m, c, &host[(size_t)c * k + j]);
                 if (!rc && g.sensor) rc = rig_record(m, c, &rig[(size_t)c * k + j]);
+                if (!rc && g.rings) packs[(size_t)c * k + j] = seq_results_args(*m->seq, c);
                 if (rc) {
                     if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
                     return rc;
@@ -5981,9 +6198,12 @@ int group_table(pagk_ctx *lead, GroupState &g)
             HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_SENSOR].ptr, rig.data(), rig.size() * sizeof(RigRec),
                                         hipMemcpyHostToDevice, lead->stream));
         }
+        if (g.rings)
+            HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_RESULTS].ptr, packs.data(), packs.size() * sizeof(ResultsArgs),
+                                        hipMemcpyHostToDevice, lead->stream));
         HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP].ptr, host.data(), host.size() * sizeof(GroupRec), hipMemcpyHostToDevice,
                                     lead->stream));
-        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host and rig are locals)
+        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host, rig and packs are locals)
     } catch (const std::bad_alloc &) {
         return PAGK_E_NOMEM;
     }
@@ -6069,6 +6289,10 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
     hipLaunchKernelGGL(k_group_handover_keys, dim3(1, kk), dim3(1024), 0, s, table);
     if (g.sensor && sn.flow_velocity)
         hipLaunchKernelGGL(k_rig_flow_velocity, dim3((unsigned)((p.cap + 255) / 256), kk), dim3(256), 0, s, rig);
+    if (g.rings) {   // the last launch, as in seq_issue: every camera's record
+        const ResultsArgs *packs = static_cast<const ResultsArgs *>(lead->buf[pagk_ctx::GROUP_RESULTS].ptr) + (size_t)c * k;
+        hipLaunchKernelGGL(k_group_results_pack, dim3(results_blocks(p.cap), kk), dim3(1024), 0, s, packs);
+    }
     HIPCHK(lead, hipGetLastError());
     return PAGK_OK;
 }
@@ -6097,6 +6321,7 @@ void group_drop(GroupState *g)
         id = -1;
     }
     (void)release(lead, lead->buf[pagk_ctx::GROUP]);
+    if (g->rings) (void)release(lead, lead->buf[pagk_ctx::GROUP_RESULTS]);
     if (g->sensor) (void)release(lead, lead->buf[pagk_ctx::GROUP_SENSOR]);
     for (pagk_ctx *m : g->members) m->group = nullptr;
     delete g;
@@ -6138,6 +6363,8 @@ static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const cha
         if (in_capture(c)) return refuse("is inside a graph capture", j);
         if (memcmp(&c->seq->p, &lead->seq->p, sizeof(pagk_sequence_params)) != 0)
             return refuse("is configured differently from the lead: the parameters of a group are byte-equal", j);
+        if (c->seq->res.depth != lead->seq->res.depth)
+            return refuse("differs from the lead in its result ring: all members have one of the same depth, or none has", j);
         if (sensor) {   // everything of the sensor block but Rbc: every camera has its own extrinsic rotation
             pagk_sequence_sensor a = c->seq->s;
             memcpy(a.Rbc, lead->seq->s.Rbc, sizeof a.Rbc);
@@ -6159,9 +6386,13 @@ static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const cha
     if (sensor && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_SENSOR], align_up((size_t)2 * k * sizeof(RigRec), kPartAlign),
                                 NOT_IN_CAPTURE, "the sensor group's table")))
         return rc;
+    const bool rings = lead->seq->res.depth != 0;
+    if (rings && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_RESULTS], align_up((size_t)2 * k * sizeof(ResultsArgs), kPartAlign),
+                               NOT_IN_CAPTURE, "the group's table of result records")))
+        return rc;
     GroupState *g = new (std::nothrow) GroupState();
     if (!g) return PAGK_E_NOMEM;
-    g->sensor = sensor;
+    g->sensor = sensor, g->rings = rings;
     try {
         g->members.assign(ctxs, ctxs + k);
     } catch (const std::bad_alloc &) {
@@ -6313,6 +6544,14 @@ static int group_step(pagk_ctx *lead, const char *what, bool sensor, const pagk_
             g.direct_done[c] = true;
         }
         g.last_graph = replay;
+        // behind the graph, in front of the event every member's stream waits for: every member's record into its own ring
+        for (int j = 0; j < k; j++) {
+            pagk_ctx *m = g.members[j];
+            if ((rc = seq_results_post(m, *m->seq, m->seq->frames))) {
+                if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
+                return rc;
+            }
+        }
         for (pagk_ctx *m : g.members) {
             m->seq->frames++;
             m->seq->stepped = true;

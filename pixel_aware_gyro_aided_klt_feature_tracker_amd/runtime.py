@@ -755,10 +755,13 @@ class DeviceSequence:
     SequenceTracker is the same loop for a Python host that keeps its results on the device.
     With `sensor` (a capi.SequenceSensor) it is the sensor form: start(raw, t=...) and step(raw, window=...) take what the
     camera and the IMU deliver (raw frames through the context's maps, set with ctx.rectify_set_maps before; a
-    capi.imu_window), and read_velocity() returns mvFlowVelocityInNormalPlane."""
+    capi.imu_window), and read_velocity() returns mvFlowVelocityInNormalPlane.
+    With `results` (2 .. 8) the sequence has a result ring of that depth (pagk_sequence_results_create): fetch(frame) returns
+    the record of any of the last `results` frames -- everything read, read_pair and read_velocity deliver, track ids and
+    ages -- as a dict of copies without draining the stream, poll(frame) whether its copy has arrived."""
 
     def __init__(self, sp: "capi.SequenceParams", device: int = 0, ctx: "capi.Context | None" = None,
-                 sensor: "capi.SequenceSensor | None" = None):
+                 sensor: "capi.SequenceSensor | None" = None, results: "int | None" = None):
         self._own = ctx is None
         self.ctx = capi.Context(device) if ctx is None else ctx
         self.sp = sp
@@ -773,6 +776,12 @@ class DeviceSequence:
                 self.ctx.close()
             raise
         self._open = True
+        if results is not None:
+            try:
+                self.ctx.sequence_results_create(int(results))
+            except Exception:
+                self.close()
+                raise
 
     def start(self, frame, candidates=None, t: "float | None" = None):
         if self.sensor is not None:
@@ -803,6 +812,12 @@ class DeviceSequence:
     def status(self) -> dict:
         return self.ctx.sequence_status()
 
+    def fetch(self, frame: int) -> dict:
+        return self.ctx.sequence_fetch(frame)
+
+    def poll(self, frame: int) -> bool:
+        return self.ctx.sequence_poll(frame)
+
     def close(self):
         if self._open:
             self._open = False
@@ -821,10 +836,11 @@ class DeviceSequenceGroup:
     or 2 (FAST); `rbc` gives every camera its own Rbc (k arrays of nine numbers; default: the block's), `maps` its own
     rectification maps (k pairs (map_x, map_y), required with raw = 1).  start(frames, cands, t=[...]) takes the raw frames and
     their time stamps, step(frames, windows=[...], cands=...) one capi.ImuWindow per camera; cands is None with detector 2;
-    read_velocity(j) returns camera j's flow velocities."""
+    read_velocity(j) returns camera j's flow velocities.
+    With `results` (2 .. 8) every member has a result ring of that depth: fetch(j, frame) and poll(j, frame) are camera j's."""
 
     def __init__(self, sp: "capi.SequenceParams", k: int, device: int = 0, sensor: "capi.SequenceSensor | None" = None,
-                 rbc=None, maps=None):
+                 rbc=None, maps=None, results: "int | None" = None):
         ok = capi.sequence_group_check(sp) if sensor is None else capi.sequence_group_sensor_check(sp, sensor)
         if ok != capi.PAGK_OK:
             raise ValueError("pagk_sequence_group_check refuses these parameters" if sensor is None else
@@ -838,7 +854,7 @@ class DeviceSequenceGroup:
         try:
             for j in range(self.k):
                 if sensor is None:
-                    self.seqs.append(DeviceSequence(sp, device))
+                    self.seqs.append(DeviceSequence(sp, device, results=results))
                     continue
                 ctx = capi.Context(device)
                 try:
@@ -848,7 +864,7 @@ class DeviceSequenceGroup:
                     if rbc is not None:
                         own = capi.SequenceSensor.from_buffer_copy(sensor)
                         own.Rbc = (capi.C.c_float * 9)(*[float(x) for x in np.asarray(rbc[j], np.float32).reshape(9)])
-                    seq = DeviceSequence(sp, ctx=ctx, sensor=own)
+                    seq = DeviceSequence(sp, ctx=ctx, sensor=own, results=results)
                 except Exception:
                     ctx.close()
                     raise
@@ -884,6 +900,12 @@ class DeviceSequenceGroup:
 
     def read_pair(self, j: int, cap: "int | None" = None) -> dict:
         return self.seqs[j].read_pair(cap)
+
+    def fetch(self, j: int, frame: int) -> dict:
+        return self.seqs[j].fetch(frame)
+
+    def poll(self, j: int, frame: int) -> bool:
+        return self.seqs[j].poll(frame)
 
     def status(self) -> dict:
         return self.group.status()

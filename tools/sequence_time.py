@@ -29,6 +29,17 @@ mismatch is exit code 20); a step of (a) or (b) is one frame of the whole rig, a
 With --cameras K --sensor [--detect-fast] the rig is one of sensor sequences (pagk_sequence_group_*_sensor): raw RGB frames,
 IMU windows and, with --detect-fast, the FAST top-up instead of the lists; the same three arms.
     python tools/sequence_time.py --cameras 8 --sensor --detect-fast
+
+With --results DEPTH [--cameras K] the script measures what the loop costs when every frame's results are consumed (include/pagk.h
+"The result ring of a sequence"), for one camera and, with --cameras K, for the group of K as well, PatchMatch with validation:
+(a) a result ring of DEPTH blocks, frame k fetched (pagk_sequence_fetch, zero copy) after frame k + DEPTH - 1 was handed in;
+(b) the calls there were before the ring, in lock-step: pagk_sequence_read and pagk_sequence_read_pair after every frame, into
+arrays allocated once; (c) the loop that reads nothing.  First the records of (a) are compared byte for byte with the arrays of
+(b) on every frame (exit code 20 on a mismatch), then the arms take turns window by window.  --only-c measures arm (c) alone and
+touches nothing the ring added; with --tree DIR the package and the test helpers come from another built checkout, so the same
+file measures (c) on the parent commit's tree in the same session.
+
+    python tools/sequence_time.py --results 4 --cameras 8 --out profiles/sequence_results_time.json
 """
 import argparse
 import json
@@ -40,6 +51,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:   # (before the package is imported)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -56,6 +69,9 @@ def main() -> int:
     ap.add_argument("--sensor", action="store_true", help="add the sensor sequence and its plain counterpart")
     ap.add_argument("--cameras", type=int, default=0, help="measure a rig of K cameras: the group against K sequences in turn")
     ap.add_argument("--detect-fast", action="store_true", help="with --cameras K --sensor: the FAST top-up instead of the lists")
+    ap.add_argument("--results", type=int, default=0, help="measure the loop with every frame read: a result ring of this depth")
+    ap.add_argument("--only-c", action="store_true", help="with --results: arm (c), the loop that reads nothing, alone")
+    ap.add_argument("--tree", default=None, help="a built checkout to import the package and the test helpers from")
     a = ap.parse_args()
     threading.Timer(a.limit, lambda: os._exit(124)).start()
 
@@ -76,6 +92,8 @@ def main() -> int:
         return capi.sequence_params_default(track=p, lk=capi.lk_params_default(), fit=fitp, tracker=tracker, lk_initial_flow=flow,
                                             width=W, height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0,
                                             cand_cap=len(cand), validate=1, sigma=1.0)
+    if a.results:
+        return results(a, capi, runtime, sp(capi.SEQ_PATCHMATCH, 0), imgs, rot9, cands)
     if a.cameras and a.sensor:
         return rig_sensor(a, capi, runtime, sp(capi.SEQ_PATCHMATCH, 0), p, imgs, cands)
     if a.cameras:
@@ -398,6 +416,151 @@ def rig_sensor(a, capi, runtime, sp, p, imgs, cands) -> int:
     for sq in singles:
         sq._own = True
         sq.close()
+    os._exit(0)
+
+
+def results(a, capi, runtime, sp, imgs, rot9, cands) -> int:
+    """--results DEPTH [--cameras K]: (a) the ring, pipelined, (b) read and read_pair in lock-step, (c) nothing read."""
+    import ctypes as C
+    D = a.results
+    SET = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state", "info")
+    PAIR = ("status", "pt_predict", "pt_predict_un", "err")
+    out = {"workload": f"{W}x{H}, {N} keypoints, h = 10, validation on, graph mode, {a.steps} steps a window, {a.windows} windows "
+                       f"taking turns; ring depth {D}", "tree": ROOT if a.tree else "this",
+           "unit": "us per frame (of the whole rig for a group; host clock around a window, synchronised at both ends)"}
+
+    class Rig:
+        """K cameras (K = 0: one sequence, no group) with or without rings; camera j's list of frame k is rolled by 13 j."""
+
+        def __init__(self, K, depth):
+            self.K, self.n = K, max(K, 1)
+            kw = {"results": depth} if depth else {}
+            self.group = runtime.DeviceSequenceGroup(sp, K, **kw) if K else None
+            self.seqs = self.group.seqs if K else [runtime.DeviceSequence(sp, **kw)]
+            self.lists = [[np.roll(c, 13 * j, axis=0) for c in cands] for j in range(self.n)]
+            self.handed = 0
+            self.res = capi.SequenceResult() if depth else None
+            self.arrays = dict(keys=np.zeros((CAP, 2), np.float32), keys_un=np.zeros((CAP, 2), np.float32),
+                               keys_normal=np.zeros((CAP, 2), np.float32), index_in_last=np.zeros(CAP, np.int32),
+                               live=np.zeros(CAP, np.uint8), state=np.zeros(8, np.int32), info=np.zeros(8, np.int32),
+                               status=np.zeros(CAP, np.uint8), pt_predict=np.zeros((CAP, 2), np.float32),
+                               pt_predict_un=np.zeros((CAP, 2), np.float32), err=np.zeros(CAP, np.float32))
+            self.ptr = {k: v.ctypes.data for k, v in self.arrays.items()}
+
+        def hand_in(self, k):
+            if self.group:
+                fr, ls = [imgs[k]] * self.K, [self.lists[j][k] for j in range(self.K)]
+                self.group.start(fr, ls) if k == 0 else self.group.step(fr, [rot9[k - 1]] * self.K, ls, mode="graph")
+            elif k == 0:
+                self.seqs[0].start(imgs[0], self.lists[0][0])
+            else:
+                self.seqs[0].step(imgs[k], rot9[k - 1], self.lists[0][k], mode="graph")
+            self.handed = 1 if k == 0 else self.handed + 1
+
+        def read(self, j, pair=True):
+            """pagk_sequence_read (and pagk_sequence_read_pair) of camera j into the arrays allocated once."""
+            c, p = self.seqs[j].ctx, self.ptr
+            c._check(c.lib.pagk_sequence_read(c.h, CAP, *(p[n] for n in SET)), "pagk_sequence_read")
+            if pair:
+                c._check(c.lib.pagk_sequence_read_pair(c.h, CAP, *(p[n] for n in PAIR)), "pagk_sequence_read_pair")
+            return self.arrays
+
+        def fetch(self, j, frame):
+            c = self.seqs[j].ctx
+            c._check(c.lib.pagk_sequence_fetch(c.h, frame, C.byref(self.res)), "pagk_sequence_fetch")
+            return self.res
+
+        def sync(self):
+            for sq in self.seqs:
+                sq.ctx.sync()
+
+        def close(self):
+            if self.group:
+                self.group.close()
+            else:
+                self.seqs[0].close()
+
+    def window(step, sync):
+        sync()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            step(1 + i % (NF - 1))
+        sync()
+        return (time.perf_counter() - t0) / a.steps * 1e6
+
+    for K in ([0] + ([a.cameras] if a.cameras else [])):
+        title = f"group of {K}" if K else "one camera"
+        arm_c = Rig(K, 0)
+        arms = {"(c) nothing read": arm_c}
+        if not a.only_c:
+            arm_a, arm_b = Rig(K, D), Rig(K, 0)
+            arms = {f"(a) ring of {D}, fetch of frame k after frame k + {D - 1}": arm_a, "(b) read + read_pair after every frame": arm_b,
+                    "(c) nothing read": arm_c}
+            # 1. results first: the lock-step arrays of (b) per frame and camera, then the records of (a), fetched pipelined
+            want = []
+            for k in range(NF):
+                arm_b.hand_in(k)
+                want.append([{n: v.copy() for n, v in arm_b.read(j, pair=k > 0).items()} for j in range(arm_b.n)])
+
+            def compare(f):
+                for j in range(arm_a.n):
+                    rec = arm_a.seqs[j].fetch(f)
+                    for n in SET + (PAIR if f else ()):
+                        if rec[n].tobytes() != want[f][j][n].tobytes():
+                            print(f"{title}: camera {j} frame {f}: {n} of the record differs from the lock-step read: nothing is reported",
+                                  file=sys.stderr)
+                            os._exit(20)
+            for k in range(NF):
+                arm_a.hand_in(k)
+                if k >= D - 1:
+                    compare(k - D + 1)
+            for f in range(max(NF - D + 1, 0), NF):
+                compare(f)
+            for k in range(NF):
+                arm_c.hand_in(k)
+            for j in range(arm_c.n):
+                last = arm_c.read(j)
+                for n in SET + PAIR:
+                    if last[n].tobytes() != want[NF - 1][j][n].tobytes():
+                        print(f"{title}: camera {j}: {n} of the loop that reads nothing differs: nothing is reported", file=sys.stderr)
+                        os._exit(20)
+            print(f"results ({title}): every record of (a) equals the lock-step arrays of (b) on all {NF} frames, and (c) ends where (b) does")
+
+            def step_a(k):
+                arm_a.hand_in(k)
+                f = arm_a.handed - D
+                if f >= 0:
+                    for j in range(arm_a.n):
+                        arm_a.fetch(j, f)
+
+            def step_b(k):
+                arm_b.hand_in(k)
+                for j in range(arm_b.n):
+                    arm_b.read(j)
+        loops = {}
+        for name, r in arms.items():
+            r.hand_in(0)                                           # every arm starts again: frame numbers from 0
+            loops[name] = (step_a if name.startswith("(a)") else step_b if name.startswith("(b)") else r.hand_in, r.sync)
+        times = {name: [] for name in loops}
+        for step, sync in loops.values():
+            window(step, sync)                                     # warm-up
+        for _ in range(a.windows):
+            for name, (step, sync) in loops.items():
+                times[name].append(window(step, sync))
+        block = {}
+        for name, v in times.items():
+            block[name] = dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))
+            print(f"{title}: {name:58s} {block[name]['median']:8.1f} us ({block[name]['min']:.1f} - {block[name]['max']:.1f})")
+        if not a.only_c:
+            ka, kb = [n for n in block if n.startswith("(a)")][0], [n for n in block if n.startswith("(b)")][0]
+            block["a_range_below_b_range"] = bool(block[ka]["max"] < block[kb]["min"])
+        out[title] = block
+        for r in arms.values():
+            r.close()
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
     os._exit(0)
 
 
