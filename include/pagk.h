@@ -552,9 +552,13 @@ int pagk_selftest_corner_response(pagk_ctx *ctx, const pagk_image *img, float *R
  * (Examples/Demo/RealSenseD435i.cpp:184-190, Examples/ROS/.../feature_tracker.cpp:367-371), so Frame::DetectKeyPoints
  * (src/frame.cpp:156-218) takes its first branch, pORBextractor->DetectFeatures(mGray, mMask, keypoints) (:172-179):
  * ORBextractor::DetectFeatures (src/ORBextractor.cc:1148-1205), ComputeKeyPointsOctTree (:789-871), DistributeOctTree
- * (:563-787), ExtractorNode::DivideNode (:505-561).  This section is that branch for nlevels = 1.  Parity with OpenCV's
- * cv::FAST is NOT claimed (it cannot be built here); the contract is this definition, bit for bit (restated in plain C in
- * tests/fast_detect_ref.c).  It is integer arithmetic throughout, so a host with OpenCV can pin it.  More than one
+ * (:563-787), ExtractorNode::DivideNode (:505-561).  This section is that branch for nlevels = 1.  What is pinned: every
+ * statement of the reference this section reads -- the cell arithmetic, both skips, the fall-back pass, DistributeOctTree and
+ * DivideNode -- against the reference's own src/ORBextractor.cc, compiled unchanged (oracle/_ref/ref_orb, oracle/README.md),
+ * through the plain-C restatement tests/fast_detect_ref.c and on the device, bit for bit.  What remains a definition: cv::FAST
+ * itself (m(p), the score, the suppression below; it cannot be built here, is integer arithmetic throughout, and a host with
+ * OpenCV can pin it), and the order of nodes of equal size in the sort of :708, which the reference takes from their addresses
+ * (the "creation number" rule below is that order under an allocator whose addresses ascend).  More than one
  * level is "ORB over a scale pyramid" below (pagk_orb_extractor); computeOrientation / IC_Angle (DetectKeyPoints reads key.pt only) and the
  * descriptors are pagk_orb_describe_device below ("ORB descriptors and matching").
  *   input      an 8-bit image W x H (level 0 of a frame slot, read through its pitch).  At level 0 without orientation
@@ -742,9 +746,11 @@ int pagk_undistort_maps(double fx, double fy, double cx, double cy, const double
  * distance filter.  The detector half is pagk_detect_fast_device with mask = NULL (ComputeKeyPointsOctTree for the one
  * level the front-ends construct); this section is the describe and the match half, for nlevels = 1 (more
  * levels: "ORB over a scale pyramid" below, which runs this section's definition on every level).
- * Parity contract: parity with OpenCV's own arithmetic (GaussianBlur, fastAtan2, cvRound, BFMatcher) is NOT claimed (it
- * cannot be built here); the contract is this definition, bit for bit (restated in plain C in tests/orb_ref.c).  It follows
- * OpenCV 3.4's scalar code paths step by step and says where it is the library's own rule.
+ * Parity contract: IC_Angle and computeOrbDescriptor (:101-171) are pinned to the reference's own src/ORBextractor.cc,
+ * compiled unchanged (oracle/_ref/ref_orb, oracle/README.md), through the plain-C restatement tests/orb_ref.c and on the
+ * device, bit for bit.  OpenCV's own arithmetic under them (GaussianBlur, fastAtan2, cvRound), the sine and cosine of a
+ * float, and BFMatcher remain this definition (they cannot be built here); it follows OpenCV 3.4's scalar code paths step by
+ * step and says where it is the library's own rule.  The matcher and its filter (FindFeatureMatches) are not pinned.
  *   pattern    the 512 sampling points of bit_pattern_31_ (:174) are the host's: 1024 int32, x then y per point, pair q of
  *              the descriptor = points 2q and 2q + 1.  Every coordinate lies in [-13, 13] (the reference's table spans
  *              [-13, 12], largest radius 18.38): every rotated tap then rounds to at most 18 < EDGE_THRESHOLD = 19.
@@ -846,8 +852,11 @@ int pagk_orb_match(pagk_ctx *ctx, const pagk_orb_params *params, int32_t nq, con
  * the value they ship ("int nLevels = 1;    // 8", Examples/Demo/RealSenseD435i.cpp:187).  This section is the extractor for
  * 1 <= nlevels <= PAGK_ORB_MAX_LEVELS.  The two n_levels fields of pagk_fast_params and pagk_orb_params describe the
  * one-level calls above and keep refusing anything but 1; the levels of this section come from pagk_orb_extractor.
- * Parity contract: parity with OpenCV (cv::resize, cv::FAST, GaussianBlur) is NOT claimed; the contract is this definition,
- * bit for bit (restated in plain C in tests/orb_levels_ref.c, on top of tests/fast_detect_ref.c and tests/orb_ref.c).
+ * Parity contract: the constructor's tables, ComputePyramid's sizes, the per-level loop, the packing and the mask test are
+ * pinned to the reference's own src/ORBextractor.cc, compiled unchanged (oracle/_ref/ref_orb, oracle/README.md), through the
+ * plain-C restatement tests/orb_levels_ref.c (on top of tests/fast_detect_ref.c and tests/orb_ref.c) and on the device, bit
+ * for bit.  OpenCV under them (cv::resize, cv::FAST, GaussianBlur, copyMakeBorder) and pow remain this definition; no output
+ * depends on the border copyMakeBorder writes, on any level.
  *   scales     (:439-455) sc[0] = 1.0f, sc[l] = sc[l - 1] * scale_factor (one f32 rounding per level), inv[l] = 1.0f / sc[l].
  *   sizes      (:1211-1212) W_l = cvRound((float)W * inv[l]), H_l = cvRound((float)H * inv[l]), ties to even; W and H are
  *              always the ORIGINAL image's.  Every level must be a legal input of the one-level detector: 62 <= W_l, H_l <=

@@ -16,6 +16,7 @@
  * All "file:line" citations are relative to /root/reference.
  */
 #include "pagk_oracle.h"
+#include "pagk_oracle_cv.h"
 
 #include <math.h>
 #include <pthread.h>
@@ -1287,4 +1288,160 @@ void pagk_oracle_mat_inv2(const float *m, float *o)
     const double dinv = det != 0 ? 1. / det : 0;
     const float i00 = (float)(m[3] * dinv), i01 = (float)(-m[1] * dinv), i10 = (float)(-m[2] * dinv), i11 = (float)(m[0] * dinv);
     o[0] = i00, o[1] = i01, o[2] = i10, o[3] = i11;
+}
+
+/* ---- OpenCV's arithmetic under the reference's src/ORBextractor.cc, as include/pagk.h defines it ("FAST cells and
+ * quadtree", "ORB descriptors and matching", "ORB over a scale pyramid").  Sequential and literal. ------------------------- */
+static const int FAST_RX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+static const int FAST_RY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+
+/* m(p): the largest, over the 16 arcs of 9 ring pixels and both signs, of the smallest difference along the arc */
+static int fast9_m(const uint8_t *p, int64_t step)
+{
+    int d[16], best = -1000;
+    for (int r = 0; r < 16; r++) d[r] = (int)p[FAST_RY[r] * step + FAST_RX[r]] - (int)p[0];
+    for (int start = 0; start < 16; start++) {
+        int lo = 1000, hi = 1000;
+        for (int k = 0; k < 9; k++) {
+            const int v = d[(start + k) & 15];
+            if (v < lo) lo = v;
+            if (-v < hi) hi = -v;
+        }
+        if (lo > best) best = lo;
+        if (hi > best) best = hi;
+    }
+    return best;
+}
+
+int pagk_oracle_fast9(const uint8_t *sub, int64_t step, int32_t w, int32_t h, int32_t threshold, int32_t cap, int32_t *xys)
+{
+    if (!sub || w < 1 || h < 1 || step < w || cap < 0 || (cap > 0 && !xys)) return PAGK_E_ARG;
+    if (w < 7 || h < 7) return 0;
+    /* the score map with a frame of one zero pixel around the sub-image */
+    const size_t pitch = (size_t)w + 2;
+    int32_t *S = (int32_t *)calloc(pitch * ((size_t)h + 2), sizeof(int32_t));
+    if (!S) return PAGK_E_NOMEM;
+    for (int y = 3; y < h - 3; y++)
+        for (int x = 3; x < w - 3; x++) {
+            const int m = fast9_m(sub + (int64_t)y * step + x, step);
+            S[(size_t)(y + 1) * pitch + x + 1] = m > threshold ? m - 1 : 0;
+        }
+    int n = 0, rc = 0;
+    for (int y = 3; y < h - 3 && rc >= 0; y++)
+        for (int x = 3; x < w - 3; x++) {
+            const int32_t *c = S + (size_t)(y + 1) * pitch + x + 1;
+            const int32_t s = c[0];
+            const int p = (int)pitch;
+            if (s > c[-p - 1] && s > c[-p] && s > c[-p + 1] && s > c[-1] && s > c[1] && s > c[p - 1] && s > c[p] && s > c[p + 1]) {
+                if (n >= cap) {
+                    rc = PAGK_E_ARG;
+                    break;
+                }
+                xys[3 * n] = x, xys[3 * n + 1] = y, xys[3 * n + 2] = s;
+                n++;
+            }
+        }
+    free(S);
+    return rc < 0 ? rc : n;
+}
+
+static int round_even_f(float v) { return (int)lrintf(v); }
+
+int pagk_oracle_resize_linear(const uint8_t *src, int32_t sw, int32_t sh, int64_t sstep, uint8_t *dst, int32_t dw, int32_t dh,
+                              int64_t dstep)
+{
+    if (!src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1 || sstep < sw || dstep < dw) return PAGK_E_ARG;
+    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
+    for (int dy = 0; dy < dh; dy++) {
+        /* rows: both indices clipped, the fraction kept */
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        const int sy = (int)floorf(fy);
+        fy -= (float)sy;
+        const int b0 = round_even_f((1.f - fy) * 2048.f), b1 = round_even_f(fy * 2048.f);
+        const int y0 = sy < 0 ? 0 : (sy < sh ? sy : sh - 1), y1 = sy + 1 < 0 ? 0 : (sy + 1 < sh ? sy + 1 : sh - 1);
+        const uint8_t *r0 = src + (int64_t)y0 * sstep, *r1 = src + (int64_t)y1 * sstep;
+        for (int dx = 0; dx < dw; dx++) {
+            /* columns: below 0 and at the last column a single tap of weight 2048 */
+            float fx = (float)((dx + 0.5) * scale_x - 0.5);
+            int sx = (int)floorf(fx);
+            fx -= (float)sx;
+            if (sx < 0) fx = 0, sx = 0;
+            const int single = sx + 1 >= sw;
+            if (sx >= sw - 1) fx = 0, sx = sw - 1;
+            const int a0 = round_even_f((1.f - fx) * 2048.f), a1 = round_even_f(fx * 2048.f);
+            const int S0 = single ? r0[sx] * 2048 : r0[sx] * a0 + r0[sx + 1] * a1;
+            const int S1 = single ? r1[sx] * 2048 : r1[sx] * a0 + r1[sx + 1] * a1;
+            dst[(int64_t)dy * dstep + dx] = (uint8_t)(((((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2) & 255);
+        }
+    }
+    return 0;
+}
+
+static int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+
+int pagk_oracle_border_reflect101(uint8_t *buf, int64_t step, int32_t w, int32_t h, int32_t border, int32_t fill)
+{
+    if (!buf || border < 0 || w <= border || h <= border || step < (int64_t)w + 2 * border || fill > 255) return PAGK_E_ARG;
+    const uint8_t *in = buf + (int64_t)border * step + border;
+    for (int y = -border; y < h + border; y++)
+        for (int x = -border; x < w + border; x++) {
+            if (y >= 0 && y < h && x >= 0 && x < w) continue;
+            buf[(int64_t)(y + border) * step + x + border] =
+                fill >= 0 ? (uint8_t)fill : in[(int64_t)reflect101(y, h) * step + reflect101(x, w)];
+        }
+    return 0;
+}
+
+int pagk_oracle_blur7(const uint8_t *img, int32_t w, int32_t h, int64_t step, const int32_t *wt, uint8_t *out, int64_t ostep)
+{
+    if (!img || !wt || !out || w < 4 || h < 4 || step < w || ostep < w) return PAGK_E_ARG;
+    int32_t *tmp = (int32_t *)malloc((size_t)w * (size_t)h * sizeof(int32_t));
+    if (!tmp) return PAGK_E_NOMEM;
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            int32_t s = 0;
+            for (int k = -3; k <= 3; k++) s += wt[abs(k)] * img[(int64_t)y * step + reflect101(x + k, w)];
+            tmp[(size_t)y * w + x] = s;
+        }
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            int32_t s = 0;
+            for (int k = -3; k <= 3; k++) s += wt[abs(k)] * tmp[(size_t)reflect101(y + k, h) * w + x];
+            out[(int64_t)y * ostep + x] = (uint8_t)((s + 32768) >> 16);
+        }
+    free(tmp);
+    return 0;
+}
+
+float pagk_oracle_fast_atan2(float y, float x)
+{
+    const float p1 = 0x1.ca44dep+5f, p3 = -0x1.2aaddcp+4f, p5 = 0x1.1d3f7ep+3f, p7 = -0x1.4515b2p+1f;
+    const float eps = 0x1p-52f; /* (float)DBL_EPSILON */
+    const float ax = fabsf(x), ay = fabsf(y);
+    float a, c, c2;
+    if (ax >= ay) {
+        c = ay / (ax + eps);
+        c2 = c * c;
+        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    } else {
+        c = ax / (ay + eps);
+        c2 = c * c;
+        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    }
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}
+
+double pagk_oracle_pow_int(double base, double n, int32_t *ok)
+{
+    const int k = n >= 0 && n <= 64 ? (int)n : -1;
+    if (k < 0 || (double)k != n) {
+        if (ok) *ok = 0;
+        return 0.0;
+    }
+    double p = 1.0;
+    for (int l = 0; l < k; l++) p *= base;
+    if (ok) *ok = 1;
+    return p;
 }

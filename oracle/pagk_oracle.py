@@ -72,6 +72,22 @@ def load():
         lib.pagk_oracle_match_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         lib.pagk_oracle_mat_inv3d.restype = None
         lib.pagk_oracle_mat_inv3d.argtypes = [vp, vp]
+        # pagk_oracle_cv.h: OpenCV's arithmetic under the reference's ORB extractor
+        i64 = C.c_int64
+        lib.pagk_oracle_fast9.restype = C.c_int
+        lib.pagk_oracle_fast9.argtypes = [vp, i64, i32, i32, i32, i32, vp]
+        lib.pagk_oracle_resize_linear.restype = C.c_int
+        lib.pagk_oracle_resize_linear.argtypes = [vp, i32, i32, i64, vp, i32, i32, i64]
+        lib.pagk_oracle_border_reflect101.restype = C.c_int
+        lib.pagk_oracle_border_reflect101.argtypes = [vp, i64, i32, i32, i32, i32]
+        lib.pagk_oracle_blur7.restype = C.c_int
+        lib.pagk_oracle_blur7.argtypes = [vp, i32, i32, i64, vp, vp, i64]
+        lib.pagk_oracle_fast_atan2.restype = f32
+        lib.pagk_oracle_fast_atan2.argtypes = [f32, f32]
+        lib.pagk_oracle_pow_int.restype = C.c_double
+        lib.pagk_oracle_pow_int.argtypes = [C.c_double, C.c_double, vp]
+        lib.pagk_oracle_sin_cos.restype = None
+        lib.pagk_oracle_sin_cos.argtypes = [C.c_double, vp, vp]
         _lib = lib
     return _lib
 
@@ -269,3 +285,59 @@ def mat_inv3d(M) -> np.ndarray:
     M, out = _mat3(M), np.zeros(9, np.float64)
     load().pagk_oracle_mat_inv3d(M.ctypes.data, out.ctypes.data)
     return out
+
+
+# ---- pagk_oracle_cv.h ------------------------------------------------------------------------------------------------------
+def fast9(sub: np.ndarray, threshold: int) -> np.ndarray:
+    """cv::FAST(sub, keys, threshold, true) -> (n, 3) int32 rows of x, y, score; sub may be a view with a row stride."""
+    sub = np.asarray(sub, np.uint8)
+    assert sub.strides[1] == 1
+    h, w = sub.shape
+    cap = ((w + 1) // 2) * ((h + 1) // 2) + 1
+    out = np.zeros((cap, 3), np.int32)
+    n = load().pagk_oracle_fast9(sub.ctypes.data, sub.strides[0], w, h, int(threshold), cap, out.ctypes.data)
+    assert n >= 0
+    return out[:n].copy()
+
+
+def resize_linear(src: np.ndarray, dw: int, dh: int) -> np.ndarray:
+    src = np.asarray(src, np.uint8)
+    assert src.strides[1] == 1
+    dst = np.zeros((dh, dw), np.uint8)
+    assert load().pagk_oracle_resize_linear(src.ctypes.data, src.shape[1], src.shape[0], src.strides[0], dst.ctypes.data, dw, dh, dw) == 0
+    return dst
+
+
+def border_reflect101(img: np.ndarray, border: int, fill: int = -1) -> np.ndarray:
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape
+    buf = np.zeros((h + 2 * border, w + 2 * border), np.uint8)
+    buf[border:border + h, border:border + w] = img
+    assert load().pagk_oracle_border_reflect101(buf.ctypes.data, buf.strides[0], w, h, border, fill) == 0
+    return buf
+
+
+def blur7(img: np.ndarray, weights=(54, 49, 34, 18)) -> np.ndarray:
+    img = np.asarray(img, np.uint8)
+    assert img.strides[1] == 1
+    h, w = img.shape
+    wt, out = np.array(weights, np.int32), np.zeros((h, w), np.uint8)
+    assert load().pagk_oracle_blur7(img.ctypes.data, w, h, img.strides[0], wt.ctypes.data, out.ctypes.data, w) == 0
+    return out
+
+
+def fast_atan2(y, x) -> np.float32:
+    return np.float32(load().pagk_oracle_fast_atan2(float(np.float32(y)), float(np.float32(x))))
+
+
+def pow_int(base: float, n: float):
+    """-> the repeated product, or None where n is no integer in [0, 64]"""
+    ok = C.c_int32(0)
+    p = load().pagk_oracle_pow_int(float(base), float(n), C.addressof(ok))
+    return float(p) if ok.value else None
+
+
+def sin_cos(x: float):
+    sn, cs = C.c_double(0), C.c_double(0)
+    load().pagk_oracle_sin_cos(float(x), C.addressof(sn), C.addressof(cs))
+    return sn.value, cs.value

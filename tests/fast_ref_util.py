@@ -195,7 +195,7 @@ def model_detect(img, mask, n_features, cap=None, *, ini=INI_TH, mn=MIN_TH, reve
         L.append([(int(hx * f(i)), 0, int(hx * f(i + 1)), g["max_by"] - BORDER, buckets[i]), seq])
         seq += 1
     L = [e for e in L if e[0][4]]
-    passes = inner = ties = 0
+    passes = inner = ties = broke = best_ties = 0
     longest = len(L)
     done = False
 
@@ -233,7 +233,7 @@ def model_detect(img, mask, n_features, cap=None, *, ini=INI_TH, mn=MIN_TH, reve
                 ties += len(sizes) - len(set(sizes))
                 order = sorted(cand, key=lambda c: (len(c[0][4]), -c[1] if reverse_tie else c[1]))
                 cand = []
-                for e in reversed(order):
+                for left, e in zip(range(len(order) - 1, -1, -1), reversed(order)):
                     for c in children_of(e):
                         L.insert(0, c)
                         if len(c[0][4]) > 1:
@@ -241,6 +241,7 @@ def model_detect(img, mask, n_features, cap=None, *, ini=INI_TH, mn=MIN_TH, reve
                     L.remove(e)
                     longest = max(longest, len(L))
                     if len(L) >= N:
+                        broke += left > 0     # the walk ends with candidates left (src/ORBextractor.cc:754)
                         break
                 if len(L) >= N or len(L) == prev:
                     done = True
@@ -253,6 +254,7 @@ def model_detect(img, mask, n_features, cap=None, *, ini=INI_TH, mn=MIN_TH, reve
         for k in ks[1:]:
             if k[2] > b[2]:
                 b = k
+        best_ties += sum(k[2] == b[2] for k in ks) > 1      # the first of equal responses stays (:776)
         x, y = b[0] + BORDER, b[1] + BORDER
         if mask is not None and mask[int(y), int(x)] == 0:
             continue
@@ -261,7 +263,7 @@ def model_detect(img, mask, n_features, cap=None, *, ini=INI_TH, mn=MIN_TH, reve
         n += 1
     info[:6] = (n, cells["n"], cells["first_empty"], cells["empty"], len(L), passes)
     return dict(keypoints=kp, response=resp, info=info, n=n, stats=dict(ties=ties, inner=inner, n_ini=g["n_ini"], longest=longest),
-                cells=cells)
+                cells=cells, branches=dict(broke=broke, best_ties=best_ties))
 
 
 # ---- images ------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,10 @@ tests/golden/ref_shim/tracker/<case>.npz holds the same for oracle/_ref/ref_trac
 src/gyro_aided_tracker.cpp, compiled unchanged under its own header -- over reference_cases.TRACKER_CASES: every input array as
 in_<name>, every array the binary wrote as out_<name> (oracle/ref_shim/ref_tracker.cpp lists them).  Arrays only.
 
+tests/golden/ref_shim/orb/<case>.npz holds the same for oracle/_ref/ref_orb -- the reference's own src/ORBextractor.cc, compiled
+unchanged under its own header -- over the committed rows of reference_cases.ORB_CASES (oracle/ref_shim/ref_orb.cpp lists the
+arrays).  level_0 is the input image and is left out.  Arrays only; the sampling pattern in them is the tests' own.
+
 Kept apart from tests/golden/ref/, which stays reserved for a real OpenCV + Eigen build (tools/ref_dump/).
 
 Needs the binary (`make -C oracle ref` where the reference's sources are).  The files are written with fixed zip timestamps:
@@ -71,10 +75,20 @@ def tracker_arrays(c, workdir, binary=None):
     return {**{"in_" + k: v for k, v in inp.items()}, **{"out_" + k: v for k, v in out.items()}}
 
 
+def orb_arrays(c, workdir, binary=None):
+    inp = rc.make_orb_inputs(c)
+    out, proc = rc.run_orb(inp, workdir, c.name, **({"binary": binary} if binary else {}))
+    if out is None:
+        raise RuntimeError(f"{c.name}: ref_orb exited with {proc.returncode}: {proc.stderr}")
+    assert np.array_equal(out["level_0"], inp["img"])
+    return {**{"in_" + k: v for k, v in inp.items()}, **{"out_" + k: v for k, v in out.items() if k != "level_0"}}
+
+
 def main():
-    if not os.path.exists(rc.REF_BIN) or not os.path.exists(rc.TRK_BIN):
-        sys.exit(f"{rc.REF_BIN} or {rc.TRK_BIN} is missing: make -C oracle ref (needs the reference's sources)")
+    if not os.path.exists(rc.REF_BIN) or not os.path.exists(rc.TRK_BIN) or not os.path.exists(rc.ORB_BIN):
+        sys.exit(f"{rc.REF_BIN}, {rc.TRK_BIN} or {rc.ORB_BIN} is missing: make -C oracle ref (needs the reference's sources)")
     os.makedirs(rc.TRK_FIXTURE_DIR, exist_ok=True)
+    os.makedirs(rc.ORB_FIXTURE_DIR, exist_ok=True)
     with tempfile.TemporaryDirectory() as workdir:
         for name in rc.committed_cases():
             a = patchmatch_arrays(rc.case(name), workdir)
@@ -90,6 +104,11 @@ def main():
             path = os.path.join(rc.TRK_FIXTURE_DIR, c.name + ".npz")
             save_npz(path, **tracker_arrays(c, workdir))
             print(f"tracker/{c.name}: {os.path.getsize(path)} bytes")
+        for c in rc.ORB_CASES:
+            if c.committed:
+                path = os.path.join(rc.ORB_FIXTURE_DIR, c.name + ".npz")
+                save_npz(path, **orb_arrays(c, workdir))
+                print(f"orb/{c.name}: {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

@@ -617,3 +617,170 @@ def load_tracker_fixture(name):
     """-> (inputs, the compiled reference's outputs) of tests/golden/ref_shim/tracker/<name>.npz"""
     z = np.load(os.path.join(TRK_FIXTURE_DIR, name + ".npz"), allow_pickle=False)
     return ({k[3:]: z[k] for k in z.files if k.startswith("in_")}, {k[4:]: z[k] for k in z.files if k.startswith("out_")})
+
+
+# ==== the ORB extractor: oracle/_ref/ref_orb, the reference's own src/ORBextractor.cc compiled unchanged ======================
+# One row per branch of ComputeKeyPointsOctTree, DistributeOctTree / DivideNode, the constructor, ComputePyramid, DetectFeatures'
+# mask test, IC_Angle and computeOrbDescriptor (the `what` of every row says which), at the smallest size that reaches it.
+# tests/test_reference_orb_cpu.py holds the restatements and numpy models to the binary on this table and asserts that every
+# branch named is reached, tests/golden/make_ref_shim.py writes the binary's outputs to tests/golden/ref_shim/orb/<case>.npz,
+# tests/test_reference_orb_gpu.py holds the device entry points to those files.  The sampling pattern is an input of a case
+# (the tests' seeded patterns and corner_pattern()): the reference's own table is in no file of this repository.
+ORB_BIN = os.path.join(ROOT, "oracle", "_ref", "ref_orb")
+ORB_BIN_SAN = os.path.join(ROOT, "oracle", "_ref", "ref_orb_san")
+ORB_FIXTURE_DIR = os.path.join(FIXTURE_DIR, "orb")
+
+
+@dataclasses.dataclass(frozen=True)
+class OrbCase:
+    name: str
+    what: str          # the statements of src/ORBextractor.cc the row exists for
+    image: str         # a key of orb_image()
+    n_features: int
+    n_levels: int = 1
+    scale: float = 1.2
+    mode: str = "detect"       # detect: DetectFeatures(); extract: operator()
+    pattern: str = ""          # extract: "seed<k>" (orb_ref_util.seeded_pattern(k)) or "corner" (corner_pattern())
+    mask: str = ""             # detect: a key of orb_mask()
+    ini: int = 20
+    mn: int = 7
+    committed: bool = True     # False: too large for a fixture, CPU only
+
+
+def _planted(w, h, pixels, background=40):
+    img = np.full((h, w), background, np.uint8)
+    for x, y, v in pixels:
+        img[y, x] = v
+    return img
+
+
+def _patch(w, h, seed):
+    """A texture in the left half of a flat frame: level images that compress (a fixture's size)."""
+    import detect_ref_util as du
+    t = du.texture_image(synth, w, h, seed)
+    t[:, w // 2:] = 90
+    return t
+
+
+def _mixed(w, h, seed):
+    """A texture whose middle third has 0.3 of the contrast (cells whose first FAST pass is empty and whose second is not) and
+    whose right third is flat (cells empty after both)."""
+    import detect_ref_util as du
+    t = du.texture_image(synth, w, h, seed).astype(np.float64)
+    a, b = w // 3, 2 * w // 3
+    t[:, a:b] = 127.5 + (t[:, a:b] - 127.5) * 0.3
+    t[:, b:] = 90
+    return np.clip(np.rint(t), 0, 255).astype(np.uint8)
+
+
+# single bright pixels on a flat background: a keypoint each, score value - 41; (45, 30) lies on node 0's right edge of a
+# 91 x 62 frame (x - 16 == int(hX) == 29 with hX = 29.5); (60, 25) and (61, 25) have equal scores and are neighbours: both
+# dropped; no other pixel within 15 of (30, 40): its disc has m10 = m01 = 0
+PLANTED_91x62 = ((45, 30, 200), (60, 25, 150), (61, 25, 150), (70, 40, 120), (74, 44, 120), (30, 40, 180), (24, 22, 90), (66, 19, 99))
+
+
+def orb_image(name):
+    import detect_ref_util as du
+    import fast_ref_util as fu
+    if name == "planted pixels":
+        return fu.planted_pixels()[0]
+    if name == "flat 255":
+        return np.full((240, 320), 255, np.uint8)
+    kind, _, rest = name.partition(" ")
+    w, h = (int(v) for v in kind.split("x")) if "x" in kind and kind[0].isdigit() else (0, 0)
+    if rest.startswith("noise"):
+        return du.noise_image(w, h, int(rest[5:] or 3))
+    if rest.startswith("texture"):
+        return du.texture_image(synth, w, h, int(rest[7:] or 2))
+    if rest.startswith("patch"):
+        return _patch(w, h, int(rest[5:] or 7))
+    if rest.startswith("mixed"):
+        return _mixed(w, h, int(rest[5:] or 7))
+    if rest == "planted":
+        return _planted(w, h, PLANTED_91x62)
+    if rest == "pixels":
+        return fu.planted_pixels(w, h)[0]
+    raise KeyError(name)
+
+
+def orb_mask(name, w, h):
+    import detect_ref_util as du
+    if name == "holes":
+        return du.holes_mask(w, h)
+    if name == "right half":   # zero where x >= W / 2
+        m = np.ones((h, w), np.uint8)
+        m[:, w // 2:] = 0
+        return m
+    raise KeyError(name)
+
+
+def orb_pattern(name):
+    import orb_ref_util as ou
+    return ou.corner_pattern() if name == "corner" else ou.seeded_pattern(int(name[4:]))
+
+
+def make_orb_inputs(c, descending=False, border_a5=False, own_table=False):
+    img = np.ascontiguousarray(orb_image(c.image))
+    inp = dict(img=img, cfg=np.array([c.n_features, c.n_levels, c.ini, c.mn, int(c.mode == "extract"), int(descending), int(border_a5),
+                                      int(own_table)], np.int32), scale=np.array([c.scale], np.float32))
+    if c.mask:
+        inp["mask"] = np.ascontiguousarray(orb_mask(c.mask, img.shape[1], img.shape[0]))
+    if c.mode == "extract" and not own_table:
+        inp["pattern"] = np.ascontiguousarray(orb_pattern(c.pattern), np.int32)
+    return inp
+
+
+def run_orb(inputs, workdir, name, binary=ORB_BIN):
+    """The compiled reference extractor on one case -> (its outputs or None, the finished process)."""
+    fin, fout = os.path.join(str(workdir), name + ".orb"), os.path.join(str(workdir), name + ".out")
+    write_arrays(fin, inputs)
+    if os.path.exists(fout):
+        os.remove(fout)
+    proc = subprocess.run([binary, fin, fout], capture_output=True, text=True)
+    return (read_arrays(fout) if proc.returncode == 0 else None), proc
+
+
+def orb_case(name):
+    return next(c for c in ORB_CASES if c.name == name)
+
+
+def load_orb_fixture(name):
+    """-> (inputs, the compiled reference's outputs) of tests/golden/ref_shim/orb/<name>.npz"""
+    z = np.load(os.path.join(ORB_FIXTURE_DIR, name + ".npz"), allow_pickle=False)
+    inp, out = {k[3:]: z[k] for k in z.files if k.startswith("in_")}, {k[4:]: z[k] for k in z.files if k.startswith("out_")}
+    out["level_0"] = inp["img"]   # ComputePyramid's level 0 is the image: stored once
+    return inp, out
+
+
+ORB_CASES = (
+    # ---- the cells of ComputeKeyPointsOctTree (:797-852)
+    OrbCase("one_cell_62x62", "one cell (:808-811); the inner loop entered (:697) and left mid-walk (:754); 22 nodes for N = 20", "62x62 noise3", 20),
+    OrbCase("nini2_boundary_key", "nIni = 2 with hX = 29.5 (:567-569): a key at x = 29 = int(hX) falls to node 0 (:593); two neighbours of "
+            "equal score, both dropped by cv::FAST; isolated pixels: m10 = m01 = 0 in IC_Angle; "
+            " ends by size == prevSize (:693)", "91x62 planted", 30, mode="extract", pattern="seed31"),
+    OrbCase("nini2_ties_91x62", "nIni = 2; nodes of equal size in the sort of :708; equal responses in a node: the first stays (:776)", "91x62 noise3", 30),
+    OrbCase("round_2p5_107x62", "round() half away from zero (:567): 75 / 30 = 2.5 -> nIni = 3", "107x62 noise3", 30),
+    OrbCase("round_0p5_62x92", "round() half away from zero (:567): 30 / 60 = 0.5 -> nIni = 1", "62x92 noise3", 30),
+    OrbCase("column_skip_813x62", "26 columns of 31: the last starts at maxBorderX - 6 and is skipped (:827)", "813x62 texture2", 200),
+    OrbCase("row_skip_468x903", "29 rows of 31: the last starts at maxBorderY - 3 and is skipped (:818); 468 wide keeps nIni at 1",
+            "468x903 pixels", 300),
+    OrbCase("fallback_152x92", "cells whose first pass is empty and whose second is not, and cells empty after both (:836-842)",
+            "152x92 mixed7", 60),
+    # ---- DistributeOctTree and DivideNode (:505-787)
+    OrbCase("prev_size_planted", "every node ends with one key: size == prevSize below N (:693)", "planted pixels", 400),
+    OrbCase("inner_320x240", "the inner loop (:700-761) with 53 sort ties, left mid-walk; 15 nodes whose best response is shared", "320x240 texture2", 100),
+    OrbCase("n1_160x120", "N = 1: done after the first round by size >= N (:693)", "160x120 texture12", 1),
+    OrbCase("flat_255", "no keypoint at all: every cell empty after both passes, an empty list", "flat 255", 100),
+    # ---- the constructor (:434-470), ComputePyramid (:1207-1230), the packing and the mask (:1066-1205)
+    OrbCase("levels8_240x224", "8 levels at 1.2, the last 67 x 63; odd parents in resize; half of the frame flat (the fixture's size)", "240x224 patch21", 300, 8, 1.2, "extract", "seed31"),
+    OrbCase("levels2_1p5_corner", "2 levels at 1.5; corner_pattern(): taps reach 18", "160x120 texture12", 120, 2, 1.5, "extract", "corner"),
+    OrbCase("quota_tie_1p4", "nDesiredFeaturesPerScale = 94.5: cvRound gives 94 (:466)", "120x100 noise3", 162, 2, 1.4, "extract", "seed7"),
+    OrbCase("quota_zero_last", "quotas 1, 1, 0: the last level runs with N = 0 (:470, :693)", "120x100 noise3", 2, 3, 1.2),
+    OrbCase("size_tie_75x75", "75 * (1 / 1.2f) = 62.5 in float: cvRound gives 62 (:1212); on level 1 keypoints 19 from every border; "
+            "angles in every octant", "75x75 noise3", 1000, 2, 1.2, "extract", "seed31"),
+    OrbCase("masked_levels4", "DetectFeatures with a mask: keypoints of levels >= 1 dropped at mask[int(y s), int(x s)] (:1199-1203)",
+            "240x224 patch21", 300, 4, 1.2, mask="holes"),
+    # ---- too large for a fixture: CPU only
+    OrbCase("texture_640x480_n400", "280 cells, 201 sort ties", "640x480 texture7", 400, committed=False),
+    OrbCase("texture_752x480_n1000", "nIni = 2 on 336 cells; 4 levels", "752x480 texture1", 1000, 4, 1.2, "extract", "seed31", committed=False),
+)
