@@ -10,11 +10,13 @@
 // Prints one line per frame: the hand-over's state words [total reach_flag survivors added rejected].
 // Build: g++ -std=c++17 -I include examples/sequence_loop.cpp -L <pkg> -l:libpagk_hip.so -Wl,-rpath,<pkg>
 //
-//   sequence_loop <seq.bin> <target_n> <cap> --cameras K [--direct]
+//   sequence_loop <seq.bin> <target_n> <cap> --cameras K [--lk | --lk-gyro] [--direct]
 //
 // A rig: K copies of the loop stepped together through a sequence group (pagk_sequence_group_*), every stage of a frame one
 // launch for all cameras.  Camera j sees the file's frames and rotations and, so that the cameras differ, the candidate
 // list of frame (k + j) mod n_frames.  Prints "camera j frame k: ..." with the same state words, camera by camera per frame.
+// With --lk or --lk-gyro the rig tracks with Lucas-Kanade (pagk_sequence_group_create_lk): the baseline arm of the
+// comparison (src/gyro_aided_tracker.cpp:353-380) through the same calls.
 //
 //   sequence_loop <dir> <target_n> <cap> --sensor [--lk | --lk-gyro] [--detect | --detect-fast] [--direct]
 //
@@ -26,9 +28,9 @@
 // width floats each) | one candidate list (n_cand x 2 floats) per frame.  Prints the same state words.
 // Build: add -DPAGK_EXAMPLE_SENSOR -I <pkg>/csrc/host -l:libpagk_tracker.so
 //
-//   sequence_loop <dir> <target_n> <cap> --sensor --cameras K [--detect-fast] [--direct]
+//   sequence_loop <dir> <target_n> <cap> --sensor --cameras K [--lk | --lk-gyro] [--detect-fast] [--direct]
 //
-// A rig of sensor sequences (pagk_sequence_group_*_sensor): K contexts, each with the file's maps and Rbc, stepped together
+// A rig of sensor sequences (pagk_sequence_group_*_sensor; with --lk or --lk-gyro pagk_sequence_group_create_lk): K contexts, each with the file's maps and Rbc, stepped together
 // with the raw frames and the IMU window as they come from disk.  So that the cameras differ, camera j sees the raw frame
 // (k + j) mod n_frames and (without --detect-fast) the candidate list of that frame.  Prints "camera j frame k: ...".
 //
@@ -101,7 +103,8 @@ static int rig_loop(const pagk_sequence_params &sp, int K, int mode, int depth, 
         if (rc == PAGK_OK && depth) rc = pagk_sequence_results_create(ctxs[j], depth);
         if (rc != PAGK_OK) return fprintf(stderr, "pagk_sequence_create -> %s (%s)\n", pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
     }
-    CHECK(pagk_sequence_group_create(ctxs.data(), K));
+    // (the Lucas-Kanade group is made by its own call and driven by the same ones)
+    CHECK(sp.tracker == PAGK_SEQ_LK ? pagk_sequence_group_create_lk(ctxs.data(), K) : pagk_sequence_group_create(ctxs.data(), K));
     std::vector<pagk_image> frames(K);
     std::vector<const float *> lists(K);
     std::vector<int32_t> counts(K, nc);
@@ -254,8 +257,9 @@ static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int 
     if (in.load(dir)) return 1;
     const int ws = in.ws, hs = in.hs, cn = in.cn, nc = in.nc, nf = in.nf;
     pagk_sequence_sensor ss;
-    if (!in.configure(sp, ss) || pagk_sequence_group_sensor_check(&sp, &ss) != PAGK_OK)
-        return fprintf(stderr, "--sensor --cameras: PatchMatch with the file's candidate lists or --detect-fast\n"), 1;
+    const bool lk = sp.tracker == PAGK_SEQ_LK;
+    if (!in.configure(sp, ss) || (lk ? pagk_sequence_group_lk_check(&sp, &ss) : pagk_sequence_group_sensor_check(&sp, &ss)) != PAGK_OK)
+        return fprintf(stderr, "--sensor --cameras: PatchMatch or Lucas-Kanade with the file's candidate lists or --detect-fast\n"), 1;
     std::vector<pagk_ctx *> ctxs(K, nullptr);
     for (int j = 0; j < K; j++) {
         int rc = pagk_create(&ctxs[j], 0);
@@ -266,7 +270,7 @@ static int sensor_rig_loop(const std::string &dir, pagk_sequence_params sp, int 
             (depth && (rc = pagk_sequence_results_create(ctxs[j], depth)) != PAGK_OK))
             return fprintf(stderr, "camera %d -> %s (%s)\n", j, pagk_strerror(rc), pagk_last_error(ctxs[j])), 2;
     }
-    CHECK(pagk_sequence_group_create_sensor(ctxs.data(), K));
+    CHECK(lk ? pagk_sequence_group_create_lk(ctxs.data(), K) : pagk_sequence_group_create_sensor(ctxs.data(), K));
     const bool list = sp.detector == 0;
     pagk_seq::ImuWindow windows(in.imu);
     std::vector<std::vector<uint8_t>> raw(K);
@@ -379,8 +383,9 @@ int main(int argc, char **argv)
     sp.cand_cap = nc > 0 ? nc : 1;
     if (pagk_sequence_params_check(&sp) != PAGK_OK) return fprintf(stderr, "the parameters are refused\n"), 1;
     if (cameras) {
-        if (cameras < 1 || cameras > 64 || pagk_sequence_group_check(&sp) != PAGK_OK)
-            return fprintf(stderr, "--cameras: 1 .. 64 cameras, PatchMatch with the file's candidate lists\n"), 1;
+        const int ok_rig = sp.tracker == PAGK_SEQ_LK ? pagk_sequence_group_lk_check(&sp, nullptr) : pagk_sequence_group_check(&sp);
+        if (cameras < 1 || cameras > 64 || ok_rig != PAGK_OK)
+            return fprintf(stderr, "--cameras: 1 .. 64 cameras, PatchMatch or Lucas-Kanade with the file's candidate lists\n"), 1;
         return rig_loop(sp, cameras, mode, depth, nf, w, h, nc, img, cand, rot);
     }
 

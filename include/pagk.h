@@ -1790,7 +1790,8 @@ int pagk_sequence_read_velocity(pagk_ctx *ctx, int32_t cap, float *v);
  * legacy default stream.
  * The group serves PatchMatch with the caller's candidate lists (tracker PAGK_SEQ_PATCHMATCH, detector 0), with or without
  * the gyro prediction and the validation.  Out of scope of the group: Lucas-Kanade, the Harris and FAST detectors, sensor
- * sequences (pagk_sequence_create_sensor), cameras that are configured differently, contexts on different devices. */
+ * sequences (pagk_sequence_create_sensor), cameras that are configured differently, contexts on different devices.
+ * (Lucas-Kanade has a group call of its own: "Lucas-Kanade in the sequence groups", pagk_sequence_group_create_lk.) */
 /* PAGK_OK iff pagk_sequence_group_create accepts sequences of these parameters (Examples/Demo/RealSenseD435i.cpp:199-321, one
  * loop per camera): pagk_sequence_params_check passes, tracker == PAGK_SEQ_PATCHMATCH and detector == 0; validate and
  * track.has_gyro_predict_initial may each be 0 or 1.  PAGK_E_ARG (or the nested check's code) otherwise.  Needs no device. */
@@ -1851,7 +1852,8 @@ int pagk_sequence_group_status(pagk_ctx *lead, int32_t *words);
  * directly, and replayed afterwards; a captured step is one linear chain.
  * The sensor group serves PatchMatch with the caller's candidate lists (detector 0) or the FAST detector (detector 2), with
  * or without the prediction, the validation, raw frames and the flow velocities.  What stays out: the Harris detector,
- * Lucas-Kanade, cameras whose parameters differ (anything but Rbc and the maps), contexts on different devices. */
+ * Lucas-Kanade, cameras whose parameters differ (anything but Rbc and the maps), contexts on different devices.
+ * (Lucas-Kanade has a group call of its own: "Lucas-Kanade in the sequence groups", pagk_sequence_group_create_lk.) */
 /* PAGK_OK iff pagk_sequence_group_create_sensor accepts sensor sequences of these blocks (Examples/Demo/RealSenseD435i.cpp:
  * 199-321, one loop per camera): pagk_sequence_params_check and pagk_sequence_sensor_check pass, tracker ==
  * PAGK_SEQ_PATCHMATCH and detector is 0 or 2; validate, track.has_gyro_predict_initial, raw and flow_velocity may each be 0
@@ -1956,6 +1958,55 @@ int pagk_sequence_fetch(pagk_ctx *ctx, int32_t frame, pagk_sequence_result *resu
 /* 1 if the copy of frame `frame` has completed, 0 if not yet (no counterpart in the reference:
  * Examples/Demo/RealSenseD435i.cpp:237-321 is synchronous); nothing is waited for.  PAGK_E_ARG as pagk_sequence_fetch. */
 int pagk_sequence_poll(pagk_ctx *ctx, int32_t frame);
+
+/* ---- Lucas-Kanade in the sequence groups: tracker type 0 for k cameras ------------------------------------------------ */
+/* The image-only baseline the reference exists to be compared against (tracker type 0, OPENCV_OPTICAL_FLOW_PYR_LK,
+ * src/gyro_aided_tracker.cpp:353-380) and its open experiment, Lucas-Kanade started from the gyro prediction (:364-365), for a
+ * rig: k contexts on one device, each holding a Lucas-Kanade sequence (tracker PAGK_SEQ_LK), all plain
+ * (pagk_sequence_create) or all sensor sequences (pagk_sequence_create_sensor), stepped together.  It lifts Lucas-Kanade from
+ * the "Out of scope" list of the plain group and from the "What stays out" list of the sensor group: both arms of the
+ * comparison then run through the same machinery.  Per camera, after every frame, every array of pagk_sequence_read and
+ * pagk_sequence_read_pair (err included), every array of pagk_sequence_read_velocity of a sensor member and every record of
+ * a result ring is byte for byte that of the same sequence stepped alone with the same inputs, in PAGK_SEQ_GRAPH and in
+ * PAGK_SEQ_DIRECT.
+ * A frame of one Lucas-Kanade camera enqueues a copy of its level 0, one pyrDown launch per pyramid level, a clear of the
+ * info words and the flow kernel, which is one wavefront per feature (250 workgroups at 1000 keypoints: a latency chain).  A
+ * group step issues each of them ONCE for all cameras, the camera being a dimension of the grid, from a table of its own the
+ * lead owns.  The issue order on the lead's stream is that of one Lucas-Kanade sequence, stage by stage:
+ *   1. with raw = 1 the rectification of all cameras into their frame slots; otherwise one launch that copies every camera's
+ *      frame into its parity copy of level 0 (Lucas-Kanade reads level 0 in place for a whole pair);
+ *   2. pagk_frame_set_device_batch on the slots' level 0; the pyrDown levels 1 .. top, one launch per level;
+ *   3. for sensor members the gyro integration (always, also when nothing predicts); the prediction when lk_initial_flow;
+ *   4. the clear of every camera's info words, then the flow kernel of the rig: one launch of k x ceil(cap / 4) workgroups;
+ *   5. the validation on Lucas-Kanade's status when `validate`; the hand-over (with detector 2 the plan and the FAST
+ *      detector, every camera under its own skip word); the flow velocities when flow_velocity; the pack of the result
+ *      records when the members have rings.  No Step 3 runs: type 0 never enters it.
+ * Graph mode follows the groups' rule: the first step runs member by member (that sizes every member's pyramid buffers and,
+ * with FAST, its detector workspace), the second as batched launches outside a capture, then each parity is captured at its
+ * next step and replayed; a captured step is one linear chain on the lead's stream.
+ * pagk_sequence_group_start and pagk_sequence_group_step drive a Lucas-Kanade group of plain members,
+ * pagk_sequence_group_start_sensor and pagk_sequence_group_step_sensor one of sensor members, under every rule of those
+ * calls (rot9 == NULL only when lk_initial_flow == 0); pagk_sequence_group_status, pagk_sequence_group_destroy and
+ * pagk_destroy of a member serve it as they serve the other groups.  What stays out: PatchMatch (the two other group calls
+ * serve it), the Harris detector, a mixture of plain and sensor members, cameras whose parameters differ, contexts on
+ * different devices. */
+/* PAGK_OK iff pagk_sequence_group_create_lk accepts sequences of these blocks (Examples/Demo/RealSenseD435i.cpp:199-321, one
+ * loop per camera, with the tracker of src/gyro_aided_tracker.cpp:353-380); s: the sensor block of sensor members, NULL for
+ * plain sequences.  pagk_sequence_params_check passes and, with s, pagk_sequence_sensor_check; tracker == PAGK_SEQ_LK,
+ * lk_initial_flow 0 or 1; detector == 0 for plain sequences, 0 or 2 (FAST) for sensor sequences; validate, raw and
+ * flow_velocity may each be 0 or 1.  PAGK_E_ARG (or the nested check's code) otherwise, so for PatchMatch and the Harris
+ * detector.  Needs no device. */
+int pagk_sequence_group_lk_check(const pagk_sequence_params *p, const pagk_sequence_sensor *s);
+/* Makes ctxs[0 .. k-1] a group of Lucas-Kanade sequences (Examples/Demo/RealSenseD435i.cpp:199-321, the objects k loops keep
+ * between frames; src/gyro_aided_tracker.cpp:353-380 is their tracker); ctxs[0] is the lead, and the kind of the group, plain
+ * or sensor, follows from the members.  Refuses, with a text in pagk_last_error(ctxs[0]), everything
+ * pagk_sequence_group_create refuses but the sensor sequence (parameters that are not byte-equal, sensor blocks that differ
+ * in anything but Rbc and result rings of different depths among them), a mixture of plain and sensor members, and
+ * parameters that pagk_sequence_group_lk_check refuses.  While grouped a member's own start, step and destroy calls return
+ * PAGK_E_ARG and its read calls keep working.  Calls outside the group that move a member's pyramid buffers
+ * (pagk_lk_pyramid_device with a deeper max_level on slot 0 or 1), its frame slots or its sequence invalidate the tables
+ * like those the other groups name: the next step returns PAGK_E_ARG and the group has to be destroyed. */
+int pagk_sequence_group_create_lk(pagk_ctx *const *ctxs, int32_t k);
 
 #ifdef __cplusplus
 }

@@ -464,6 +464,11 @@ def declare(lib) -> None:
                            ("pagk_sequence_group_step_sensor", [vp, vp, vp, vp, vp, i32])):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = args
+    if hasattr(lib, "pagk_sequence_group_create_lk"):
+        for name, args in (("pagk_sequence_group_lk_check", [_P(SequenceParams), _P(SequenceSensor)]),
+                           ("pagk_sequence_group_create_lk", [vp, i32])):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = args
     if hasattr(lib, "pagk_sequence_results_create"):
         for name, args in (("pagk_sequence_results_layout", [i32, i32, _P(ResultsLayout)]),
                            ("pagk_sequence_results_create", [vp, i32]), ("pagk_sequence_fetch", [vp, i32, _P(SequenceResult)]),
@@ -650,6 +655,7 @@ EXPORTED_SYMBOLS = [
     "pagk_sequence_group_step", "pagk_sequence_group_status",
     "pagk_sequence_group_sensor_check", "pagk_sequence_group_create_sensor", "pagk_sequence_group_start_sensor",
     "pagk_sequence_group_step_sensor",
+    "pagk_sequence_group_lk_check", "pagk_sequence_group_create_lk",
     "pagk_sequence_results_layout", "pagk_sequence_results_create", "pagk_sequence_fetch", "pagk_sequence_poll",
     "pagk_assoc_params_default", "pagk_assoc_params_check", "pagk_match_features_device", "pagk_search_gyro_predict_device",
     "pagk_search_gyro_predict", "pagk_search_klt_device", "pagk_search_klt",
@@ -840,20 +846,31 @@ def sequence_group_sensor_check(p: SequenceParams, s: "SequenceSensor") -> int:
     return int(load().pagk_sequence_group_sensor_check(C.byref(p), C.byref(s)))
 
 
+def sequence_group_lk_check(p: SequenceParams, s: "SequenceSensor | None" = None) -> int:
+    """pagk_sequence_group_lk_check: PAGK_OK if Lucas-Kanade sequences of these blocks (s: the sensor block of sensor
+    sequences, None for plain ones) can form a group (needs no device)."""
+    return int(load().pagk_sequence_group_lk_check(C.byref(p), C.byref(s) if s is not None else None))
+
+
 class SequenceGroup:
     """pagk_sequence_group_*: k contexts, each with a plain sequence of the same parameters, stepped together.  contexts[0] is
     the lead; per camera the results are those of its sequence stepped alone (Context.sequence_read / sequence_read_pair).
     With sensor=True the contexts hold sensor sequences (pagk_sequence_group_*_sensor): start_sensor and step_sensor take the
-    raw frames, time stamps and IMU windows; with detector 2 candidates is None."""
+    raw frames, time stamps and IMU windows; with detector 2 candidates is None.
+    With lk=True the contexts hold Lucas-Kanade sequences (pagk_sequence_group_create_lk), plain ones or, with sensor=True,
+    sensor sequences; the same start and step calls drive the group."""
 
-    def __init__(self, contexts, sensor: bool = False):
+    def __init__(self, contexts, sensor: bool = False, lk: bool = False):
         self.ctxs = list(contexts)
         self.lib = load()
         self.lead = self.ctxs[0]
         self.k = len(self.ctxs)
         self.sensor = bool(sensor)
         handles = (C.c_void_p * self.k)(*(c.h for c in self.ctxs))
-        if self.sensor:
+        self.lk = bool(lk)
+        if self.lk:
+            self.lead._check(self.lib.pagk_sequence_group_create_lk(handles, self.k), "pagk_sequence_group_create_lk")
+        elif self.sensor:
             self.lead._check(self.lib.pagk_sequence_group_create_sensor(handles, self.k), "pagk_sequence_group_create_sensor")
         else:
             self.lead._check(self.lib.pagk_sequence_group_create(handles, self.k), "pagk_sequence_group_create")

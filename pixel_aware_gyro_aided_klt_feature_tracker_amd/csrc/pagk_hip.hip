@@ -22,6 +22,7 @@
 #include "pagk_gyro_kernel.h"
 #include "pagk_group_kernel.h"
 #include "pagk_group_sensor_kernel.h"
+#include "pagk_group_lk_kernel.h"
 #include "pagk_results_kernel.h"
 #include "pagk_layout.h"
 #include "pagk_select.h"
@@ -120,6 +121,9 @@ struct GroupState {
     bool sensor = false;
     // every member has a result ring (of one depth): the lead's buf[GROUP_RESULTS] holds a third table, of k_group_results_pack
     bool rings = false;
+    // every member tracks with Lucas-Kanade (pagk_sequence_group_create_lk; plain or sensor members): the lead's buf[GROUP_LK]
+    // holds the table of the Lucas-Kanade stages (pagk_group_lk_kernel.h): record [parity * k + camera]
+    bool lk = false;
     int n_cells = 0;             // (detector 2) the cells of the FAST grid, the same for every member
     // what the tables were built from, per member: a workspace that moved since then invalidates them
     struct Held {
@@ -130,6 +134,10 @@ struct GroupState {
         int rect_w, rect_h, rect_wp;
         const void *results;   // with result rings: the member's buf[RESULTS] and its sequence's block (the third table)
         const void *results_seq;
+        // the Lucas-Kanade group's: the pyrDown levels of slots 0 and 1 (the parity copies of level 0 lie in the sequence's
+        // block, the rectified ones in the frame slots: `seq` and `level0`)
+        const void *lk_pyr[2];
+        size_t lk_pyr_bytes[2];
     };
     std::vector<Held> held;
 };
@@ -179,6 +187,7 @@ struct pagk_ctx {
         GROUP_SENSOR,  // ... of k sensor sequences (pagk_sequence_group_*_sensor): the table of the stages they add, 2 k records
         RESULTS,       // the result ring of the sequence (pagk_sequence_results_create): one record, track ids and ages by parity, next_id
         GROUP_RESULTS, // ... of a group whose members have rings: the table of k_group_results_pack, 2 k records
+        GROUP_LK,      // ... of a group of Lucas-Kanade sequences (pagk_sequence_group_create_lk): the table of pagk_group_lk_kernel.h, 2 k records
         kBufs
     };
     DevBuf buf[kBufs];
@@ -1379,7 +1388,7 @@ int pagk_create(pagk_ctx **out, int device)
     ctx->stream = ctx->own_stream;
     ctx->buf[pagk_ctx::FEAT].mirrored = true;
     for (int b : {pagk_ctx::RECT_ENTRIES, pagk_ctx::ORB_PATTERN, pagk_ctx::PRIO_HINT, pagk_ctx::DISPATCH_ORDER, pagk_ctx::GROUP,
-                  pagk_ctx::RESULTS, pagk_ctx::GROUP_RESULTS, pagk_ctx::GROUP_SENSOR})
+                  pagk_ctx::RESULTS, pagk_ctx::GROUP_RESULTS, pagk_ctx::GROUP_LK, pagk_ctx::GROUP_SENSOR})
         ctx->buf[b].state = true;
     if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->cus = 0;
     if (hipMalloc(&ctx->queue, 256) != hipSuccess) {
@@ -3798,6 +3807,17 @@ extern "C++" Layout<kLkMaxLevels> lk_layout(const int *lw, const int *lh, int to
 
 bool lk_slot_ok(const FrameSlot &s) { return s.valid && s.img0; }
 
+// the arguments of the pyrDown launch that builds level l (1 .. top) of slot s in `base` (of one launch, or of a group's record)
+extern "C++" LkPyrArgs lk_pyr_args(const FrameSlot &s, const Layout<kLkMaxLevels> &lay, void *base, const int *lw, const int *lh, int l)
+{
+    LkPyrArgs a;
+    a.src = l == 1 ? s.img0 : lay.at<uint8_t>(base, l - 2);
+    a.spitch = l == 1 ? (long long)s.pitch0 : (long long)lw[l - 1];
+    a.dst = lay.at<uint8_t>(base, l - 1);
+    a.sw = lw[l - 1], a.sh = lh[l - 1], a.dw = lw[l], a.dh = lh[l];
+    return a;
+}
+
 // (slots 4 and 5 are the host-buffer form's own)
 int lk_pyramid_slot(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot)
 {
@@ -3818,11 +3838,7 @@ int lk_pyramid_slot(pagk_ctx *ctx, const pagk_lk_params *params, int32_t slot)
     }
     ctx->lk_pyr[slot].top = -1;   // nothing valid until every level has been enqueued
     for (int l = 1; l <= top; l++) {
-        LkPyrArgs a;
-        a.src = l == 1 ? s.img0 : lay.at<uint8_t>(pyr.ptr, l - 2);
-        a.spitch = l == 1 ? (long long)s.pitch0 : (long long)lw[l - 1];
-        a.dst = lay.at<uint8_t>(pyr.ptr, l - 1);
-        a.sw = lw[l - 1], a.sh = lh[l - 1], a.dw = lw[l], a.dh = lh[l];
+        const LkPyrArgs a = lk_pyr_args(s, lay, pyr.ptr, lw, lh, l);
         hipLaunchKernelGGL(k_lk_pyrdown, dim3((unsigned)((a.dw + 63) / 64), (unsigned)((a.dh + 3) / 4)), dim3(256), 0, ctx->stream, a);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -3916,11 +3932,25 @@ LkFlowKernel lk_flow_kernel(int win)
     }
 }
 
+// ... and k_group_lk_flow (pagk_group_lk_kernel.h), every camera of a Lucas-Kanade group in one launch: the same chooser
+using LkGroupFlowKernel = void (*)(const LkGroupRec *);
+LkGroupFlowKernel lk_group_flow_kernel(int win)
+{
+    switch (lk_npix(win)) {
+        case 1: return k_group_lk_flow<1>;
+        case 2: return k_group_lk_flow<2>;
+        case 4: return k_group_lk_flow<4>;
+        case 8: return k_group_lk_flow<8>;
+        default: return k_group_lk_flow<16>;
+    }
+}
+
+// The arguments of k_lk_flow: of one launch, or of one camera's record of a Lucas-Kanade group.
 // cam: the camera of d_pt_out_dist (required with it); d_pt_init, d_status_in, d_pt_out_dist may be nullptr
-int lk_flow_slots(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam, int32_t slot_ref, int32_t slot_cur,
-                  int32_t cap, const float *d_pt_ref, const float *d_pt_init, const uint8_t *d_status_in, const int32_t *d_n,
-                  float *d_pt_out, float *d_pt_out_dist, uint8_t *d_status, uint8_t *d_status_raw, float *d_err, float *d_flow,
-                  int32_t *d_info)
+int lk_flow_args(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam, int32_t slot_ref, int32_t slot_cur,
+                 int32_t cap, const float *d_pt_ref, const float *d_pt_init, const uint8_t *d_status_in, const int32_t *d_n,
+                 float *d_pt_out, float *d_pt_out_dist, uint8_t *d_status, uint8_t *d_status_raw, float *d_err, float *d_flow,
+                 int32_t *d_info, LkFlowArgs *out)
 {
     if (d_pt_out_dist && !cam) return PAGK_E_ARG;
     LkFlowArgs f = {};
@@ -3936,6 +3966,19 @@ int lk_flow_slots(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params
         f.k1 = cam->dist_coef[0], f.k2 = cam->dist_coef[1], f.p1 = cam->dist_coef[2], f.p2 = cam->dist_coef[3];
         f.k3 = cam->n_dist_coef == 5 ? cam->dist_coef[4] : 0.0f;
     }
+    *out = f;
+    return PAGK_OK;
+}
+
+int lk_flow_slots(pagk_ctx *ctx, const pagk_lk_params *params, const pagk_params *cam, int32_t slot_ref, int32_t slot_cur,
+                  int32_t cap, const float *d_pt_ref, const float *d_pt_init, const uint8_t *d_status_in, const int32_t *d_n,
+                  float *d_pt_out, float *d_pt_out_dist, uint8_t *d_status, uint8_t *d_status_raw, float *d_err, float *d_flow,
+                  int32_t *d_info)
+{
+    LkFlowArgs f;
+    int rc = lk_flow_args(ctx, params, cam, slot_ref, slot_cur, cap, d_pt_ref, d_pt_init, d_status_in, d_n, d_pt_out, d_pt_out_dist,
+                          d_status, d_status_raw, d_err, d_flow, d_info, &f);
+    if (rc) return rc;
     HIPCHK(ctx, hipMemsetAsync(d_info, 0, kLkInfoWords * sizeof(int32_t), ctx->stream));
     hipLaunchKernelGGL(lk_flow_kernel(f.t.win), dim3((unsigned)((cap + 3) / 4)), dim3(256), 0, ctx->stream, f);
     HIPCHK(ctx, hipGetLastError());
@@ -6048,12 +6091,18 @@ GroupState::Held group_held(pagk_ctx *c)
     const DevBuf &hint = c->buf[pagk_ctx::PRIO_HINT];
     return {c->buf[pagk_ctx::FIT].ptr, c->buf[pagk_ctx::HAND].ptr, hint.ptr, hint.bytes, c->buf[pagk_ctx::FAST].ptr,
             c->buf[pagk_ctx::RECT_ENTRIES].ptr, {c->slots[0].u8[0], c->slots[1].u8[0]}, c->buf[pagk_ctx::SEQ].ptr,
-            c->rect_w, c->rect_h, c->rect_wp, c->buf[pagk_ctx::RESULTS].ptr, c->buf[pagk_ctx::SEQ].ptr};
+            c->rect_w, c->rect_h, c->rect_wp, c->buf[pagk_ctx::RESULTS].ptr, c->buf[pagk_ctx::SEQ].ptr,
+            {c->buf[pagk_ctx::LK_PYR].ptr, c->buf[pagk_ctx::LK_PYR + 1].ptr},
+            {c->buf[pagk_ctx::LK_PYR].bytes, c->buf[pagk_ctx::LK_PYR + 1].bytes}};
 }
 
-bool group_held_equal(const GroupState::Held &a, const GroupState::Held &b, bool sensor, bool rings)
+bool group_held_equal(const GroupState::Held &a, const GroupState::Held &b, bool sensor, bool rings, bool lk)
 {
     if (a.fit != b.fit || a.hand != b.hand || a.hint != b.hint || a.hint_bytes != b.hint_bytes) return false;
+    if (lk && (a.lk_pyr[0] != b.lk_pyr[0] || a.lk_pyr[1] != b.lk_pyr[1] || a.lk_pyr_bytes[0] != b.lk_pyr_bytes[0] ||
+               a.lk_pyr_bytes[1] != b.lk_pyr_bytes[1] || a.level0[0] != b.level0[0] || a.level0[1] != b.level0[1] ||
+               a.seq != b.seq))
+        return false;
     if (rings && (a.results != b.results || a.results_seq != b.results_seq)) return false;
     return !sensor || (a.fast == b.fast && a.entries == b.entries && a.level0[0] == b.level0[0] && a.level0[1] == b.level0[1] &&
                        a.seq == b.seq && a.rect_w == b.rect_w && a.rect_h == b.rect_h && a.rect_wp == b.rect_wp);
@@ -6157,13 +6206,44 @@ int rig_record(pagk_ctx *ctx, int c, RigRec *out)
     return PAGK_OK;
 }
 
+// Camera j's record of parity c of the Lucas-Kanade stages: the arguments its own launches of seq_frame and lk_flow_slots
+// would carry (the copy of level 0, lk_pyramid_slot's pyrDown launches of slot c, k_lk_flow of slots 1 - c and c).
+int lk_record(pagk_ctx *ctx, int c, LkGroupRec *out)
+{
+    SeqState &q = *ctx->seq;
+    const pagk_sequence_params &p = q.p;
+    const SeqState::KeySet &ref = q.set[1 - c];
+    LkGroupRec r;
+    memset(&r, 0, sizeof r);
+    const bool raw = q.sensor && q.s.raw;
+    const FrameSlot &s = ctx->slots[c];
+    // level 0 of slot c as seq_frame leaves it: the rectified slot, or the parity's copy of the frame
+    if (!lk_slot_ok(s) || s.w != p.width || s.h != p.height || s.pitch0 != p.width || s.img0 != (raw ? s.u8[0] : q.img[c])) {
+        snprintf(ctx->err, sizeof(ctx->err), "frame slot %d no longer holds the sequence's frame", c);
+        return PAGK_E_ARG;
+    }
+    const bool init = p.lk_initial_flow != 0;   // (as seq_issue hands them to lk_flow_slots)
+    int rc = lk_flow_args(ctx, &p.lk, &p.track, 1 - c, c, p.cap, ref.keys_un, init ? q.pu : nullptr, init ? q.st_in : ref.live, q.state,
+                          q.ppu, q.pp, q.st, nullptr, q.lk_err, nullptr, q.lk_info, &r.flow);
+    if (rc) return rc;
+    int lw[kLkMaxLevels], lh[kLkMaxLevels];
+    const int top = lk_levels(s.w, s.h, &p.lk, lw, lh);
+    const Layout<kLkMaxLevels> lay = lk_layout(lw, lh, top);
+    const DevBuf &pyr = ctx->buf[pagk_ctx::LK_PYR + c];
+    if (top < 0 || top != r.flow.t.top || (top > 0 && (!pyr.ptr || pyr.bytes < lay.total))) return PAGK_E_ARG;
+    for (int l = 1; l <= top; l++) r.pyr[l - 1] = lk_pyr_args(s, lay, pyr.ptr, lw, lh, l);
+    if (!raw) r.copy_src = q.in, r.copy_dst = q.img[c], r.copy_bytes = (long long)p.width * p.height;
+    *out = r;
+    return PAGK_OK;
+}
+
 // The tables, once per group: after the member-by-member step every buffer a record points into has its final size.
 int group_table(pagk_ctx *lead, GroupState &g)
 {
     const int k = (int)g.members.size();
     if (g.table_built) {
         for (int j = 0; j < k; j++) {
-            if (!group_held_equal(group_held(g.members[j]), g.held[j], g.sensor, g.rings)) {
+            if (!group_held_equal(group_held(g.members[j]), g.held[j], g.sensor, g.rings, g.lk)) {
                 snprintf(lead->err, sizeof(lead->err), "a workspace of member %d moved under the group's table (a call outside the group made it "
                          "grow): destroy the group (pagk_sequence_group_destroy)", j);
                 return PAGK_E_ARG;
@@ -6175,12 +6255,14 @@ int group_table(pagk_ctx *lead, GroupState &g)
         std::vector<GroupRec> host((size_t)2 * k);
         std::vector<RigRec> rig(g.sensor ? (size_t)2 * k : 0);
         std::vector<ResultsArgs> packs(g.rings ? (size_t)2 * k : 0);
+        std::vector<LkGroupRec> lks(g.lk ? (size_t)2 * k : 0);
         for (int c = 0; c < 2; c++)
             for (int j = 0; j < k; j++) {
                 pagk_ctx *m = g.members[j];
                 int rc = group_record(m, c, &host[(size_t)c * k + j]);
                 if (!rc && g.sensor) rc = rig_record(m, c, &rig[(size_t)c * k + j]);
                 if (!rc && g.rings) packs[(size_t)c * k + j] = seq_results_args(*m->seq, c);
+                if (!rc && g.lk) rc = lk_record(m, c, &lks[(size_t)c * k + j]);
                 if (rc) {
                     if (m != lead) snprintf(lead->err, sizeof(lead->err), "camera %d: %s", j, m->err);
                     return rc;
@@ -6198,12 +6280,15 @@ int group_table(pagk_ctx *lead, GroupState &g)
             HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_SENSOR].ptr, rig.data(), rig.size() * sizeof(RigRec),
                                         hipMemcpyHostToDevice, lead->stream));
         }
+        if (g.lk)
+            HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_LK].ptr, lks.data(), lks.size() * sizeof(LkGroupRec),
+                                        hipMemcpyHostToDevice, lead->stream));
         if (g.rings)
             HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP_RESULTS].ptr, packs.data(), packs.size() * sizeof(ResultsArgs),
                                         hipMemcpyHostToDevice, lead->stream));
         HIPCHK(lead, hipMemcpyAsync(lead->buf[pagk_ctx::GROUP].ptr, host.data(), host.size() * sizeof(GroupRec), hipMemcpyHostToDevice,
                                     lead->stream));
-        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host, rig and packs are locals)
+        HIPCHK(lead, hipStreamSynchronize(lead->stream));   // (host, rig, packs and lks are locals)
     } catch (const std::bad_alloc &) {
         return PAGK_E_NOMEM;
     }
@@ -6224,7 +6309,8 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
     const float *pt_ref[K], *pt_init[K], *affine[K];
     const uint8_t *status_in[K];
     pagk_outputs out[K];
-    const bool predicts = p.track.has_gyro_predict_initial != 0;
+    // (Lucas-Kanade starts from the prediction when lk_initial_flow says so, as seq_issue decides)
+    const bool predicts = g.lk ? p.lk_initial_flow != 0 : p.track.has_gyro_predict_initial != 0;
     const pagk_sequence_sensor &sn = lead->seq->s;
     const bool raw = g.sensor && sn.raw;
     for (int j = 0; j < k; j++) {
@@ -6232,7 +6318,8 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
         const SeqState::KeySet &ref = q.set[1 - c];
         slot_cur[j] = c, slot_ref[j] = 1 - c, width[j] = p.width, height[j] = p.height, step[j] = p.width, n[j] = p.cap;
         // raw frames: the slot's own level 0, in place, as rect_into_slot builds one camera's pyramid
-        data[j] = raw ? ctxs[j]->slots[c].u8[0] : q.in;
+        // (Lucas-Kanade reads level 0 in place for a whole pair: the parity's own copy of the frame, as seq_frame makes it)
+        data[j] = raw ? ctxs[j]->slots[c].u8[0] : g.lk ? q.img[c] : q.in;
         pt_ref[j] = ref.keys_un, affine[j] = q.aff;
         pt_init[j] = predicts ? q.pu : ref.keys_un;              // (as seq_issue hands them to pagk_track_device)
         status_in[j] = predicts ? q.st_in : ref.live;
@@ -6258,13 +6345,32 @@ int group_issue(pagk_ctx *lead, GroupState &g, int c)
         }
         HIPCHK(lead, hipGetLastError());
     }
+    const LkGroupRec *lks = g.lk ? static_cast<const LkGroupRec *>(lead->buf[pagk_ctx::GROUP_LK].ptr) + (size_t)c * k : nullptr;
+    if (g.lk && !raw) {   // every camera's frame into its parity copy of level 0 (seq_frame's copy)
+        const int64_t px = (int64_t)p.width * p.height;
+        hipLaunchKernelGGL(k_group_lk_copy, dim3((unsigned)((px + 4095) / 4096), kk), dim3(256), 0, s, lks);
+        HIPCHK(lead, hipGetLastError());
+    }
     int rc = pagk_frame_set_device_batch(ctxs, k, slot_cur, data, width, height, step, p.track.pyramids);
     if (rc) return rc;
+    if (g.lk) {   // lk_pyramid_slot's launches, one per level for the rig: the level sizes are the group's
+        int lw[kLkMaxLevels], lh[kLkMaxLevels];
+        const int top = lk_levels(p.width, p.height, &p.lk, lw, lh);
+        for (int l = 1; l <= top; l++)
+            hipLaunchKernelGGL(k_group_lk_pyrdown, dim3((unsigned)((lw[l] + 63) / 64), (unsigned)((lh[l] + 3) / 4), kk), dim3(256), 0, s,
+                               lks, l);
+        HIPCHK(lead, hipGetLastError());
+    }
     if (g.sensor) hipLaunchKernelGGL(k_rig_gyro_integrate, dim3(1, kk), dim3(64), 0, s, rig);   // (always, as seq_issue does)
     if (predicts) hipLaunchKernelGGL(k_group_gyro_predict, dim3((unsigned)((p.cap + 255) / 256), kk), dim3(256), 0, s, table);
     HIPCHK(lead, hipGetLastError());
-    if ((rc = pagk_track_device_batch(ctxs, k, &p.track, slot_ref, slot_cur, n, pt_ref, pt_init, affine, status_in, out))) return rc;
-    hipLaunchKernelGGL(k_group_post_filter, dim3(1, kk), dim3(1024), 0, s, table);
+    if (g.lk) {   // lk_flow_slots' clear of the info words and its launch; type 0 never enters Step 3
+        hipLaunchKernelGGL(k_group_lk_clear, dim3(1, kk), dim3(64), 0, s, lks);
+        hipLaunchKernelGGL(lk_group_flow_kernel(2 * p.lk.half_patch + 1), dim3((unsigned)((p.cap + 3) / 4), kk), dim3(256), 0, s, lks);
+    } else {
+        if ((rc = pagk_track_device_batch(ctxs, k, &p.track, slot_ref, slot_cur, n, pt_ref, pt_init, affine, status_in, out))) return rc;
+        hipLaunchKernelGGL(k_group_post_filter, dim3(1, kk), dim3(1024), 0, s, table);
+    }
     HIPCHK(lead, hipGetLastError());
     if (p.validate) {
         hipLaunchKernelGGL(k_group_fit_compact, dim3(1, kk), dim3(1024), 0, s, table);
@@ -6323,6 +6429,7 @@ void group_drop(GroupState *g)
     (void)release(lead, lead->buf[pagk_ctx::GROUP]);
     if (g->rings) (void)release(lead, lead->buf[pagk_ctx::GROUP_RESULTS]);
     if (g->sensor) (void)release(lead, lead->buf[pagk_ctx::GROUP_SENSOR]);
+    if (g->lk) (void)release(lead, lead->buf[pagk_ctx::GROUP_LK]);
     for (pagk_ctx *m : g->members) m->group = nullptr;
     delete g;
 }
@@ -6336,8 +6443,9 @@ int pagk_sequence_group_check(const pagk_sequence_params *p)
     return p->tracker == PAGK_SEQ_PATCHMATCH && p->detector == 0 ? PAGK_OK : PAGK_E_ARG;
 }
 
-// pagk_sequence_group_create (`sensor` false) and pagk_sequence_group_create_sensor: one list of refusals, one GroupState
-static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const char *what)
+// pagk_sequence_group_create (`sensor` false), pagk_sequence_group_create_sensor and pagk_sequence_group_create_lk (`lk`: the
+// kind, plain or sensor, is the lead's, and every member's): one list of refusals, one GroupState
+static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const char *what, bool lk = false)
 {
     if (!ctxs || !ctxs[0]) return PAGK_E_ARG;
     pagk_ctx *lead = ctxs[0];
@@ -6356,6 +6464,9 @@ static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const cha
         for (int i = 0; i < j; i++)
             if (ctxs[i] == c) return refuse("is listed twice", j);
         if (!c->seq) return refuse("has no sequence (pagk_sequence_create)", j);
+        if (lk && j == 0) sensor = c->seq->sensor;
+        if (lk && c->seq->sensor != sensor)
+            return refuse("mixes plain and sensor sequences: the members of a Lucas-Kanade group are all of the lead's kind", j);
         if (!sensor && c->seq->sensor)
             return refuse("holds a sensor sequence: out of scope of the group (pagk_sequence_group_create_sensor)", j);
         if (sensor && !c->seq->sensor) return refuse("holds a plain sequence (pagk_sequence_group_create)", j);
@@ -6372,7 +6483,14 @@ static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const cha
                 return refuse("is configured differently from the lead: the sensor blocks of a group differ in Rbc only", j);
         }
     }
-    if (sensor ? pagk_sequence_group_sensor_check(&lead->seq->p, &lead->seq->s) : pagk_sequence_group_check(&lead->seq->p)) {
+    if (lk) {
+        if (pagk_sequence_group_lk_check(&lead->seq->p, sensor ? &lead->seq->s : nullptr)) {
+            snprintf(lead->err, sizeof(lead->err), "%s: the group serves Lucas-Kanade (tracker type 0) with %s", what,
+                     sensor ? "the caller's candidate lists or the FAST detector (pagk_sequence_group_lk_check)"
+                            : "the caller's candidate lists (pagk_sequence_group_lk_check)");
+            return PAGK_E_ARG;
+        }
+    } else if (sensor ? pagk_sequence_group_sensor_check(&lead->seq->p, &lead->seq->s) : pagk_sequence_group_check(&lead->seq->p)) {
         snprintf(lead->err, sizeof(lead->err), "%s: the group serves PatchMatch with %s", what,
                  sensor ? "the caller's candidate lists or the FAST detector (pagk_sequence_group_sensor_check)"
                         : "the caller's candidate lists (pagk_sequence_group_check)");
@@ -6386,13 +6504,16 @@ static int group_create(pagk_ctx *const *ctxs, int32_t k, bool sensor, const cha
     if (sensor && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_SENSOR], align_up((size_t)2 * k * sizeof(RigRec), kPartAlign),
                                 NOT_IN_CAPTURE, "the sensor group's table")))
         return rc;
+    if (lk && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_LK], align_up((size_t)2 * k * sizeof(LkGroupRec), kPartAlign),
+                            NOT_IN_CAPTURE, "the Lucas-Kanade group's table")))
+        return rc;
     const bool rings = lead->seq->res.depth != 0;
     if (rings && (rc = reserve(lead, lead->buf[pagk_ctx::GROUP_RESULTS], align_up((size_t)2 * k * sizeof(ResultsArgs), kPartAlign),
                                NOT_IN_CAPTURE, "the group's table of result records")))
         return rc;
     GroupState *g = new (std::nothrow) GroupState();
     if (!g) return PAGK_E_NOMEM;
-    g->sensor = sensor, g->rings = rings;
+    g->sensor = sensor, g->rings = rings, g->lk = lk;
     try {
         g->members.assign(ctxs, ctxs + k);
     } catch (const std::bad_alloc &) {
@@ -6415,6 +6536,19 @@ int pagk_sequence_group_sensor_check(const pagk_sequence_params *p, const pagk_s
 int pagk_sequence_group_create_sensor(pagk_ctx *const *ctxs, int32_t k)
 {
     return group_create(ctxs, k, true, "pagk_sequence_group_create_sensor");
+}
+
+int pagk_sequence_group_lk_check(const pagk_sequence_params *p, const pagk_sequence_sensor *s)
+{
+    int rc = pagk_sequence_params_check(p);
+    if (rc || (s && (rc = pagk_sequence_sensor_check(s)))) return rc;
+    // the detectors whose batched kernels exist for the kind of group: the caller's lists, and FAST for sensor members
+    return p->tracker == PAGK_SEQ_LK && (p->detector == 0 || (s && p->detector == 2)) ? PAGK_OK : PAGK_E_ARG;
+}
+
+int pagk_sequence_group_create_lk(pagk_ctx *const *ctxs, int32_t k)
+{
+    return group_create(ctxs, k, false, "pagk_sequence_group_create_lk", true);
 }
 
 int pagk_sequence_group_destroy(pagk_ctx *lead)
@@ -6479,7 +6613,7 @@ static int group_step(pagk_ctx *lead, const char *what, bool sensor, const pagk_
             return PAGK_E_ARG;
         }
     }
-    if (!sensor && p.track.has_gyro_predict_initial && !rot9) {
+    if (!sensor && (g.lk ? p.lk_initial_flow : p.track.has_gyro_predict_initial) && !rot9) {
         snprintf(lead->err, sizeof(lead->err), "%s: this tracker predicts: rot9 is required", what);
         return PAGK_E_ARG;
     }

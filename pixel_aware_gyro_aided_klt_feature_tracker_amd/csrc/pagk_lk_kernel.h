@@ -48,22 +48,26 @@ struct LkPyrArgs {
     int sw, sh, dw, dh;
 };
 
-__global__ __launch_bounds__(256) void k_lk_pyrdown(LkPyrArgs a)
+// the body of k_lk_pyrdown and of k_group_lk_pyrdown (pagk_group_lk_kernel.h): blockIdx.x and blockIdx.y tile the level.
+// (The arguments one by one, as the other *_body functions take theirs: behind a struct the compiler schedules the kernel differently.)
+__device__ __forceinline__ void lk_pyrdown_body(const uint8_t *src, long long spitch, uint8_t *dst, int sw, int sh, int dw, int dh)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= a.dw || y >= a.dh) return;
+    if (x >= dw || y >= dh) return;
     int cx[5];
 #pragma unroll
-    for (int i = 0; i < 5; i++) cx[i] = lk_reflect(2 * x + i - 2, a.sw);
+    for (int i = 0; i < 5; i++) cx[i] = lk_reflect(2 * x + i - 2, sw);
     int s = 128;
 #pragma unroll
     for (int j = 0; j < 5; j++) {
-        const uint8_t *row = a.src + (long long)lk_reflect(2 * y + j - 2, a.sh) * a.spitch;
+        const uint8_t *row = src + (long long)lk_reflect(2 * y + j - 2, sh) * spitch;
         const int r = row[cx[0]] + row[cx[4]] + 4 * (row[cx[1]] + row[cx[3]]) + 6 * row[cx[2]];
         s += (j == 0 || j == 4 ? 1 : (j == 2 ? 6 : 4)) * r;
     }
-    a.dst[(size_t)y * a.dw + x] = (uint8_t)(s >> 8);
+    dst[(size_t)y * dw + x] = (uint8_t)(s >> 8);
 }
+
+__global__ __launch_bounds__(256) void k_lk_pyrdown(LkPyrArgs a) { lk_pyrdown_body(a.src, a.spitch, a.dst, a.sw, a.sh, a.dw, a.dh); }
 
 // ---- the tracker ----------------------------------------------------------------------------------------------------
 struct LkLevel {

@@ -837,13 +837,21 @@ class DeviceSequenceGroup:
     rectification maps (k pairs (map_x, map_y), required with raw = 1).  start(frames, cands, t=[...]) takes the raw frames and
     their time stamps, step(frames, windows=[...], cands=...) one capi.ImuWindow per camera; cands is None with detector 2;
     read_velocity(j) returns camera j's flow velocities.
-    With `results` (2 .. 8) every member has a result ring of that depth: fetch(j, frame) and poll(j, frame) are camera j's."""
+    With `results` (2 .. 8) every member has a result ring of that depth: fetch(j, frame) and poll(j, frame) are camera j's.
+    With sp.tracker == capi.SEQ_LK it is the Lucas-Kanade group (pagk_sequence_group_create_lk): tracker type 0, the image-only
+    baseline, or with lk_initial_flow Lucas-Kanade started from the gyro prediction; plain members with the caller's lists,
+    sensor members with detector 0 or 2.  Everything else -- start, step, the read calls, the rings -- is as above."""
 
     def __init__(self, sp: "capi.SequenceParams", k: int, device: int = 0, sensor: "capi.SequenceSensor | None" = None,
                  rbc=None, maps=None, results: "int | None" = None):
-        ok = capi.sequence_group_check(sp) if sensor is None else capi.sequence_group_sensor_check(sp, sensor)
+        lk = sp.tracker == capi.SEQ_LK
+        if lk:
+            ok = capi.sequence_group_lk_check(sp, sensor)
+        else:
+            ok = capi.sequence_group_check(sp) if sensor is None else capi.sequence_group_sensor_check(sp, sensor)
         if ok != capi.PAGK_OK:
-            raise ValueError("pagk_sequence_group_check refuses these parameters" if sensor is None else
+            raise ValueError("pagk_sequence_group_lk_check refuses these parameters" if lk else
+                             "pagk_sequence_group_check refuses these parameters" if sensor is None else
                              "pagk_sequence_group_sensor_check refuses these parameters")
         if sensor is None and (rbc is not None or maps is not None):
             raise ValueError("rbc and maps belong to the sensor form")
@@ -870,7 +878,7 @@ class DeviceSequenceGroup:
                     raise
                 seq._own = True          # (the context was made here: close() closes it)
                 self.seqs.append(seq)
-            self.group = capi.SequenceGroup([s.ctx for s in self.seqs], sensor=sensor is not None)
+            self.group = capi.SequenceGroup([s.ctx for s in self.seqs], sensor=sensor is not None, lk=lk)
         except Exception:
             self.close()
             raise

@@ -4,7 +4,10 @@
     rocprofv3 --kernel-trace --stats -d out -- python tools/sequence_group_trace.py --cameras 2 --arm group
 
 (the timed loops of sequence_time.py replay graphs and leave through os._exit, which a trace does not survive).  --arm group
-steps a sequence group of K cameras, --arm singles K sequences one after another; 96 steps of the rig after the start."""
+steps a sequence group of K cameras, --arm singles K sequences one after another; 96 steps of the rig after the start.
+--lk and --lk-gyro make the rig a Lucas-Kanade one (pagk_sequence_group_create_lk); --tree DIR imports the package and the test
+helpers from another built checkout (--arm singles --cameras 1 on the parent commit's tree: the single-camera path, kernel by
+kernel)."""
 import argparse
 import os
 import sys
@@ -12,6 +15,8 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:   # (before the package is imported)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
@@ -24,6 +29,9 @@ def main() -> int:
     ap.add_argument("--cameras", type=int, default=2)
     ap.add_argument("--arm", choices=("group", "singles"), default="group")
     ap.add_argument("--steps", type=int, default=96)
+    ap.add_argument("--lk", action="store_true", help="Lucas-Kanade (tracker type 0)")
+    ap.add_argument("--lk-gyro", action="store_true", help="Lucas-Kanade started from the gyro prediction")
+    ap.add_argument("--tree", default=None, help="a built checkout to import the package and the test helpers from")
     a = ap.parse_args()
     import handover_ref_util as hu
     from pixel_aware_gyro_aided_klt_feature_tracker_amd import capi, runtime, synth
@@ -33,8 +41,9 @@ def main() -> int:
     cand = np.stack([8 + u[0::2] * (W - 16), 8 + u[1::2] * (H - 16)], axis=1).astype(np.float32)
     lists = [[np.roll(cand, 97 * k + 13 * j, axis=0) for k in range(NF)] for j in range(K)]
     p = capi.make_params(half_patch=10, iterations=30, pyramids=3, has_gyro=True, camera=cam)
-    sp = capi.sequence_params_default(track=p, fit=capi.fit_params_default(seed=0x5EED0F17), tracker=capi.SEQ_PATCHMATCH, width=W,
-                                      height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0, cand_cap=len(cand),
+    tracker = capi.SEQ_LK if a.lk or a.lk_gyro else capi.SEQ_PATCHMATCH
+    sp = capi.sequence_params_default(track=p, lk=capi.lk_params_default(), fit=capi.fit_params_default(seed=0x5EED0F17),
+                                      tracker=tracker, lk_initial_flow=1 if a.lk_gyro else 0, width=W, height=H, cap=CAP, target_n=N, new_point_threshold=N * RATIO, detector=0, cand_cap=len(cand),
                                       validate=1, sigma=1.0)
     if a.arm == "group":
         g = runtime.DeviceSequenceGroup(sp, K)

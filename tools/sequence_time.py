@@ -30,6 +30,12 @@ With --cameras K --sensor [--detect-fast] the rig is one of sensor sequences (pa
 IMU windows and, with --detect-fast, the FAST top-up instead of the lists; the same three arms.
     python tools/sequence_time.py --cameras 8 --sensor --detect-fast
 
+With --cameras K --lk | --lk-gyro [--sensor [--detect-fast]] the rig tracks with Lucas-Kanade (pagk_sequence_group_create_lk):
+tracker type 0, the image-only baseline, or Lucas-Kanade started from the gyro prediction; the same three arms, (b) being what a
+rig had before the Lucas-Kanade group.  With --only-c (plain rigs) arm (c), the single sequence, is measured alone; with --tree DIR
+on the parent commit's built checkout, so that the single-camera path of the two commits is compared in one session.
+    python tools/sequence_time.py --cameras 8 --lk-gyro
+
 With --results DEPTH [--cameras K] the script measures what the loop costs when every frame's results are consumed (include/pagk.h
 "The result ring of a sequence"), for one camera and, with --cameras K, for the group of K as well, PatchMatch with validation:
 (a) a result ring of DEPTH blocks, frame k fetched (pagk_sequence_fetch, zero copy) after frame k + DEPTH - 1 was handed in;
@@ -70,7 +76,9 @@ def main() -> int:
     ap.add_argument("--cameras", type=int, default=0, help="measure a rig of K cameras: the group against K sequences in turn")
     ap.add_argument("--detect-fast", action="store_true", help="with --cameras K --sensor: the FAST top-up instead of the lists")
     ap.add_argument("--results", type=int, default=0, help="measure the loop with every frame read: a result ring of this depth")
-    ap.add_argument("--only-c", action="store_true", help="with --results: arm (c), the loop that reads nothing, alone")
+    ap.add_argument("--only-c", action="store_true", help="with --results or --cameras K --lk: arm (c) alone")
+    ap.add_argument("--lk", action="store_true", help="with --cameras K: the rig tracks with Lucas-Kanade (tracker type 0)")
+    ap.add_argument("--lk-gyro", action="store_true", help="with --cameras K: Lucas-Kanade started from the gyro prediction")
     ap.add_argument("--tree", default=None, help="a built checkout to import the package and the test helpers from")
     a = ap.parse_args()
     threading.Timer(a.limit, lambda: os._exit(124)).start()
@@ -94,10 +102,14 @@ def main() -> int:
                                             cand_cap=len(cand), validate=1, sigma=1.0)
     if a.results:
         return results(a, capi, runtime, sp(capi.SEQ_PATCHMATCH, 0), imgs, rot9, cands)
+    if (a.lk or a.lk_gyro) and (not a.cameras or (a.lk and a.lk_gyro)):
+        ap.error("--lk and --lk-gyro select the arm of a rig: one of them, with --cameras K")
+    rig_sp = sp(capi.SEQ_LK, 1 if a.lk_gyro else 0) if a.lk or a.lk_gyro else sp(capi.SEQ_PATCHMATCH, 0)
+    a.arm = "Lucas-Kanade started from the gyro prediction" if a.lk_gyro else "Lucas-Kanade" if a.lk else "PatchMatch"
     if a.cameras and a.sensor:
-        return rig_sensor(a, capi, runtime, sp(capi.SEQ_PATCHMATCH, 0), p, imgs, cands)
+        return rig_sensor(a, capi, runtime, rig_sp, p, imgs, cands)
     if a.cameras:
-        return rig(a, runtime, sp(capi.SEQ_PATCHMATCH, 0), imgs, rot9, cands)
+        return rig(a, runtime, rig_sp, imgs, rot9, cands)
     arms = {"sequence PatchMatch": sp(capi.SEQ_PATCHMATCH, 0), "sequence LK": sp(capi.SEQ_LK, 0),
             "sequence LK gyro-started": sp(capi.SEQ_LK, 1)}
 
@@ -211,6 +223,8 @@ def rig(a, runtime, sp, imgs, rot9, cands) -> int:
     """--cameras K: the group, K sequences one after another, one sequence."""
     K = a.cameras
     lists = [[np.roll(c, 13 * j, axis=0) for c in cands] for j in range(K)]      # camera j's candidate list of frame k
+    if a.only_c:
+        return rig_only_c(a, runtime, sp, imgs, rot9, lists[0])
     group = runtime.DeviceSequenceGroup(sp, K)
     singles = [runtime.DeviceSequence(sp) for _ in range(K)]
     names = ("keys", "keys_un", "keys_normal", "index_in_last", "live", "state", "info")
@@ -270,8 +284,8 @@ def rig(a, runtime, sp, imgs, rot9, cands) -> int:
     for _ in range(a.windows):
         for name, (step, sync) in loops.items():
             times[name].append(window(step, sync))
-    res = {"workload": f"{K} cameras, each {W}x{H}, {N} keypoints, h = 10, validation on, graph mode, {a.steps} steps a window, "
-                       f"{a.windows} windows taking turns",
+    res = {"workload": f"{K} cameras, each {W}x{H}, {N} keypoints, {a.arm}, h = 10, validation on, graph mode, {a.steps} steps a "
+                       f"window, {a.windows} windows taking turns",
            "unit": "us per rig frame for (a) and (b), per frame for (c) (host clock around a window, synchronised at both ends)",
            "group_status": group.status(), "loops": {}}
     for name, v in times.items():
@@ -281,7 +295,8 @@ def rig(a, runtime, sp, imgs, rot9, cands) -> int:
     res["a_range_below_b_range"] = bool(ga["max"] < gb["min"])
     try:   # the single path as the parent commit recorded it
         with open(os.path.join(ROOT, "profiles", "sequence_time.json")) as f:
-            res["parent_one_sequence"] = json.load(f)["loops"]["sequence PatchMatch"]
+            res["parent_one_sequence"] = json.load(f)["loops"]["sequence LK gyro-started" if a.lk_gyro else "sequence LK" if a.lk
+                                                               else "sequence PatchMatch"]
     except (OSError, KeyError, ValueError):
         pass
     print(json.dumps(res))
@@ -291,6 +306,32 @@ def rig(a, runtime, sp, imgs, rot9, cands) -> int:
     group.close()
     for sq in singles:
         sq.close()
+    os._exit(0)
+
+
+def rig_only_c(a, runtime, sp, imgs, rot9, lists) -> int:
+    """--cameras K --only-c: arm (c) of the rig, one sequence, alone (with --tree: on another built checkout)."""
+    sq = runtime.DeviceSequence(sp)
+    sq.start(imgs[0], lists[0])
+
+    def window():
+        sq.ctx.sync()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            k = 1 + i % (NF - 1)
+            sq.step(imgs[k], rot9[k - 1], lists[k], mode="graph")
+        sq.ctx.sync()
+        return (time.perf_counter() - t0) / a.steps * 1e6
+    window()                                                   # warm-up
+    v = [window() for _ in range(a.windows)]
+    res = {"workload": f"one camera, {W}x{H}, {N} keypoints, {a.arm}, h = 10, validation on, graph mode, {a.steps} steps a window, "
+                       f"{a.windows} windows", "tree": ROOT if a.tree else "this", "unit": "us per frame",
+           "loops": {"(c) one sequence": dict(median=round(float(np.median(v)), 1), min=round(min(v), 1), max=round(max(v), 1))}}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    sq.close()
     os._exit(0)
 
 
@@ -398,7 +439,7 @@ def rig_sensor(a, capi, runtime, sp, p, imgs, cands) -> int:
     for _ in range(a.windows):
         for name, (step, sync) in loops.items():
             times[name].append(window(step, sync))
-    res = {"workload": f"{K} cameras, each {W}x{H} maps from 3-channel raw frames, {N} keypoints, h = 10, validation on, "
+    res = {"workload": f"{K} cameras, each {W}x{H} maps from 3-channel raw frames, {N} keypoints, {a.arm}, h = 10, validation on, "
                        f"{'FAST top-up' if a.detect_fast else 'candidate lists'}, graph mode, {a.steps} steps a window, {a.windows} windows "
                        "taking turns; one start per 8 steps is inside every figure",
            "unit": "us per rig frame for (a) and (b), per frame for (c) (host clock around a window, synchronised at both ends)",
